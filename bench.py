@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- the reference's headline measurement on MI355X (BASELINE.json): M rank-queries/s and
 patterns/s (regexes/s) of batched FM-index backward search over an index resident in HBM, with the
-achieved fraction of the HBM roofline and the CPU path timed beside it.
+achieved fraction of the HBM roofline and (with --full) the CPU path timed beside it.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c4|c5|tiny|c4tiny]
+    python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c4|c5|tiny|c4tiny] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line; `--full` adds the sub-records that take runs of
+their own (cpu_baseline, replayed_batch_ms, miss_none, host_path, rank_only, exchange, fresh_batch, host_delivered).
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy; the inputs are seeded, the
+same from run to run.
 
 `--gpus N` with N > 1 starts the N ranks itself (a child `python -m torch.distributed.run
 --nproc-per-node N bench.py ...`, before this process touches any GPU) and relays rank 0's JSON line; when
@@ -89,6 +94,23 @@ C4_ALPHABET = "abcdefghijklmnopqrstuvwxyz \n"
 def log(rank, *a):
     if rank == 0:
         print("[bench]", *a, file=sys.stderr, flush=True)
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: what the timed path handed its caller in its last step, as DIR/<name>.npy in float64 (every value
+    here -- row numbers below 2^53, lengths, ids, counts -- is exact in it).  Over 64 MB in all, each array keeps a fixed,
+    seeded sample of its entries (in index order), the same from run to run."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {name: np.asarray(a).reshape(-1) for name, a in arrays.items()}
+    total = 8 * sum(a.size for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            keep = a.size * DUMP_BYTES // total
+            a = a[np.sort(np.random.default_rng(0xD0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
 
 
 # ---------------------------------------------------------------- launching N ranks
@@ -639,7 +661,7 @@ def run_literal(args, torch, dist, findex_amd, rank, world, local, device, use_d
     log(rank, "index: n=2^%d sigma=%d, %.1f GiB in HBM (%d symbols x %d blocks x %d B), built in %.1f ms (+%.1fs setup)"
         % (log2n, n_sigma, st["index_bytes"] / 2**30, st["n_symbols"], st["n_blocks"], st["block_bytes"],
            st["build_ms"], time.time() - t0))
-    want_cpu = world == 1 and rank == 0 and not args.no_cpu_baseline
+    want_cpu = args.full and world == 1 and rank == 0 and not args.no_cpu_baseline
     if not want_cpu:
         del bwt
         torch.cuda.empty_cache()
@@ -730,6 +752,15 @@ def run_literal(args, torch, dist, findex_amd, rank, world, local, device, use_d
     dt = time.perf_counter() - t0
     if use_dist and gather.overflow(step_no[0] - 1):       # (a collective; outside the timed region) more wide intervals than the packed form's escape list holds
         raise SystemExit("bench: the last step's escape list overflowed -- the exchange must run in the 16-byte form (--exchange pairs)")
+    if args.dump_outputs and rank == 0:
+        # the last step's intervals as its caller holds them: this rank's slot, or (N > 1) every rank's, as delivered to rank 0
+        last = step_no[0] - 1
+        if use_dist:
+            got = [gather.intervals(gather.out[last % gather.depth], r) for r in range(world)]
+            sp_l, ep_l = np.concatenate([g[0] for g in got]), np.concatenate([g[1] for g in got])
+        else:
+            sp_l, ep_l = (t.cpu().numpy() for t in gather.slot(last))
+        dump_outputs(args.dump_outputs, {"sp": sp_l, "ep": ep_l})
     timed = [p for p in ev if p]
     kernel_ms = sum(a.elapsed_time(b) for a, b in timed) / len(timed)
     # the work of exactly the timed steps
@@ -756,7 +787,7 @@ def run_literal(args, torch, dist, findex_amd, rank, world, local, device, use_d
         e1.record()
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / reps
-    replayed_ms = replay(max(args.steps, 5))
+    replayed_ms = replay(max(args.steps, 5)) if args.full else None
 
     # ---- the same ring asked with FMX_SEARCH_MISS_NONE (fmx.h): a pattern that does not occur may come back as (0, 0) -- None in
     # the reference either way (findex.scala:30) -- which spares the kernel the walk to the loop's values at the failing step.
@@ -786,9 +817,9 @@ def run_literal(args, torch, dist, findex_amd, rank, world, local, device, use_d
         return {"ms_per_step": ms, "patterns_per_sec": k / (ms * 1e-3), "requests_per_launch": reqs, "requests_G_per_s": reqs / ms / 1e6,
                 "what": "the ring's steps through fmx_search_batch_ex_dev with FMX_SEARCH_MISS_NONE: hits bit-equal to the plain call's, "
                         "every miss sp >= ep, the reference-equivalent step count unchanged; %d back-to-back steps" % reps}
-    miss_none_rec = miss_none(max(args.steps, 10)) if not (use_dist or os.environ.get("FMX_BENCH_NO_MISS_NONE")) else None      # (the variable: A/B runs against older libraries)
+    miss_none_rec = miss_none(max(args.steps, 10)) if args.full and not (use_dist or os.environ.get("FMX_BENCH_NO_MISS_NONE")) else None      # (the variable: A/B runs against older libraries)
 
-    exchange = measure_exchange(args, torch, dist, hip, gather, k, device, stream, use_dist)
+    exchange = measure_exchange(args, torch, dist, hip, gather, k, device, stream, use_dist) if args.full else None
     tot = torch.tensor([dt, float(ranks_per_step), float(hits), kernel_ms], dtype=torch.float64, device=device)
     if use_dist:
         mx = tot.clone()
@@ -882,7 +913,7 @@ def run_literal(args, torch, dist, findex_amd, rank, world, local, device, use_d
         "patterns_per_sec": world * k * args.steps / dt,
         "ring_batches": ring,
         "ms_per_step_is": "steps rotate through %d distinct pattern batches (seeds differ): no step sees a batch the device has just "
-                          "searched; the same step on ONE replayed batch: replayed_batch_ms" % ring,
+                          "searched; the same step on ONE replayed batch (--full): replayed_batch_ms" % ring,
         "replayed_batch_ms": replayed_ms,
         "miss_none": miss_none_rec,
         # co-headline: what the memory system is asked per second; `value` counts the reference's occ evaluations,
@@ -926,13 +957,13 @@ def run_literal(args, torch, dist, findex_amd, rank, world, local, device, use_d
         },
         "roofline": roof,
     }
-    if world == 1 and not args.no_host_path:
+    if args.full and world == 1 and not args.no_host_path:
         # (batch 0's intervals again: sp0 / ep0 held the replayed batch's, which they are)
         out["host_path"] = measure_host_path(torch, hip, pats, off, sp0, ep0, k, m)
         log(rank, "host path: pageable %.3f ms, page-locked %.3f ms, lean (no offsets, 8-byte intervals) %.3f ms per call"
             % (out["host_path"]["pageable"]["ms_per_call"], out["host_path"]["page_locked"]["ms_per_call"],
                out["host_path"]["lean_pageable"]["ms_per_call"]))
-    if world == 1 and rank == 0 and not args.no_rank_only:      # (like the CPU leg: at N = 1 only -- the other ranks would have left)
+    if args.full and world == 1 and rank == 0 and not args.no_rank_only:      # (like the CPU leg: at N = 1 only -- the other ranks would have left)
         # (after everything else that uses this handle's tables, before the CPU leg, which does not use the handle)
         out["rank_only"] = measure_rank_only(args, torch, hip, batches, k, stream, device, onehot, rank)
     if want_cpu:
@@ -981,7 +1012,7 @@ def run_regex(args, torch, dist, findex_amd, rank, world, local, device, use_dis
     st = hip.stats()
     log(rank, "index: n=2^%d sigma=%d, %.1f GiB in HBM, built in %.1f ms (+%.1fs setup)"
         % (log2n, len(C4_ALPHABET), st["index_bytes"] / 2**30, st["build_ms"], time.time() - t0))
-    want_cpu = world == 1 and rank == 0 and not args.no_cpu_baseline
+    want_cpu = args.full and world == 1 and rank == 0 and not args.no_cpu_baseline
     if not want_cpu:
         del bwt
         torch.cuda.empty_cache()
@@ -991,23 +1022,25 @@ def run_regex(args, torch, dist, findex_amd, rank, world, local, device, use_dis
     cap = 1 << 22
     lim = dict(mode="reference", maxBranching=REF_LIMITS[0], maxIterations=REF_LIMITS[1]) if ref_mode else dict(max_steps=max_len)
 
-    # ---- a batch that arrives as strings and is matched once: front-end + resident + first match (fresh_batch)
     hip.stats()                  # tables of the index built (k-mer table): not part of a batch's cost
     findex_amd.ReTree.prepare_batch(hip, trees[:16]).match_raw(cap=cap, **lim)
-    t0 = time.perf_counter()
-    fresh_trees = findex_amd.ReTree.compile_batch(res)
-    t1 = time.perf_counter()
-    fresh = findex_amd.ReTree.prepare_batch(hip, fresh_trees)
-    t2 = time.perf_counter()
-    fresh.match_raw(cap=cap, copy=False, **lim)
-    t3 = time.perf_counter()
-    fresh_batch = {"regexes_per_s": k / (t3 - t0), "seconds_per_batch": t3 - t0, "compile_s": t1 - t0,
-                   "resident_s": t2 - t1, "first_match_s": t3 - t2, "host_threads": effective_cores(),
-                   "what": "fmx_regex_compile_batch (all host cores) + fmx_regex_batch_create + the first "
-                           "fmx_regex_batch_match of %d regexes given as strings, results in page-locked host memory" % k}
-    del fresh, fresh_trees
-    log(rank, "fresh batch of %d regexes: compile %.3fs + resident %.3fs + first match %.3fs (workload generation %.1fs)"
-        % (k, t1 - t0, t2 - t1, t3 - t2, t_gen))
+    fresh_batch = None
+    if args.full:
+        # ---- a batch that arrives as strings and is matched once: front-end + resident + first match (fresh_batch)
+        t0 = time.perf_counter()
+        fresh_trees = findex_amd.ReTree.compile_batch(res)
+        t1 = time.perf_counter()
+        fresh = findex_amd.ReTree.prepare_batch(hip, fresh_trees)
+        t2 = time.perf_counter()
+        fresh.match_raw(cap=cap, copy=False, **lim)
+        t3 = time.perf_counter()
+        fresh_batch = {"regexes_per_s": k / (t3 - t0), "seconds_per_batch": t3 - t0, "compile_s": t1 - t0,
+                       "resident_s": t2 - t1, "first_match_s": t3 - t2, "host_threads": effective_cores(),
+                       "what": "fmx_regex_compile_batch (all host cores) + fmx_regex_batch_create + the first "
+                               "fmx_regex_batch_match of %d regexes given as strings, results in page-locked host memory" % k}
+        del fresh, fresh_trees
+        log(rank, "fresh batch of %d regexes: compile %.3fs + resident %.3fs + first match %.3fs (workload generation %.1fs)"
+            % (k, t1 - t0, t2 - t1, t3 - t2, t_gen))
     batch = findex_amd.ReTree.prepare_batch(hip, trees)
     # a ring of resident batches the steps rotate through (round 5, like the literal workloads' pattern batches): no call
     # matches the batch the device has just matched.  Batch 0 is the one the CPU baseline checks.
@@ -1029,20 +1062,23 @@ def run_regex(args, torch, dist, findex_amd, rank, world, local, device, use_dis
     d_per = torch.empty(max(k, 1), dtype=torch.int32, device=device)
 
     step_no = [0]
+    last = {}           # what the latest call handed its caller (--dump-outputs)
 
     def step(b=None):
         if b is None:
             b = batches[step_no[0] % ring]
             step_no[0] += 1
         if ref_mode:
-            out, _ = b.match_raw(cap=cap, copy=False, **lim)
+            out, per = b.match_raw(cap=cap, copy=False, **lim)
             n_res = out.size
+            last["ref"] = (out, per)
             if use_dist:
                 d_out[: 3 * n_res].copy_(torch.from_numpy(out.view(np.int64).reshape(-1)))
         else:
             n_res = b.match_dev(d_out.data_ptr(), cap, d_per.data_ptr(), max_steps=max_len)
+        last["n_res"] = n_res
         if use_dist:        # the path's one exchange: every rank receives every rank's result list (sizes, then payload)
-            all_gather_varlen(d_out[: 3 * n_res])
+            last["gathered"] = all_gather_varlen(d_out[: 3 * n_res])
         return n_res
 
     # what a call executes, averaged over the ring's batches (device counters; they differ by a per cent or two)
@@ -1077,17 +1113,33 @@ def run_regex(args, torch, dist, findex_amd, rank, world, local, device, use_dis
         dist.barrier()
     dt = time.perf_counter() - t0
     kernel_ms = sum(kms) / len(kms)
-    # ... and the same call on ONE batch replayed (what rounds 1-4 reported)
-    for _ in range(2):
-        step(batch)
-    torch.cuda.synchronize()
-    tr = time.perf_counter()
-    for _ in range(max(args.steps, 5)):
-        step(batch)
-    torch.cuda.synchronize()
-    replayed_ms = (time.perf_counter() - tr) / max(args.steps, 5) * 1e3
+    if args.dump_outputs and rank == 0:
+        # the last call's result list (every rank's, N > 1) and, on one rank, its per-regex counts
+        if use_dist:
+            got = torch.cat(last["gathered"]).cpu().numpy().view(RESULT_DTYPE)
+            per = None
+        elif ref_mode:
+            got, per = last["ref"]
+        else:
+            got = d_out[: 3 * last["n_res"]].cpu().numpy().view(RESULT_DTYPE)
+            per = d_per[:k].cpu().numpy()
+        arrays = {"result_" + f: got[f] for f in ("regex", "len", "sp", "ep")}
+        if per is not None:
+            arrays["per_regex"] = per
+        dump_outputs(args.dump_outputs, arrays)
+    replayed_ms = None
+    if args.full:
+        # ... and the same call on ONE batch replayed (what rounds 1-4 reported)
+        for _ in range(2):
+            step(batch)
+        torch.cuda.synchronize()
+        tr = time.perf_counter()
+        for _ in range(max(args.steps, 5)):
+            step(batch)
+        torch.cuda.synchronize()
+        replayed_ms = (time.perf_counter() - tr) / max(args.steps, 5) * 1e3
     host_delivered = None
-    if not ref_mode:        # the same call with the results written into page-locked host memory (PCIe-inclusive)
+    if args.full and not ref_mode:        # the same call with the results written into page-locked host memory (PCIe-inclusive)
         for _ in range(3):
             batch.match_raw(max_steps=max_len, cap=cap, copy=False)
         th = time.perf_counter()
@@ -1204,7 +1256,7 @@ def run_regex(args, torch, dist, findex_amd, rank, world, local, device, use_dis
         "regexes_per_sec": world * k * args.steps / dt,
         "ring_batches": ring,
         "ms_per_step_is": "calls rotate through %d distinct resident regex batches (seeds differ): no call matches the batch the device "
-                          "has just matched; the same call on ONE batch replayed: replayed_batch_ms" % ring,
+                          "has just matched; the same call on ONE batch replayed (--full): replayed_batch_ms" % ring,
         "replayed_batch_ms": replayed_ms,
         "regexes_per_sec_is": "a RESIDENT batch (compiled and on the device) matched again and again; a batch given as "
                               "strings and matched once runs at fresh_batch.regexes_per_s",
@@ -1260,7 +1312,15 @@ def main():
                     help="N > 1, literal workloads: the gather is delivered to rank 0 only (default) or to every rank")
     ap.add_argument("--check-launch", action="store_true",
                     help="rendezvous + sharding + gather over gloo without any GPU work (tests the launcher)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the sub-records beside the headline, each a run of its own: the CPU baseline, the replayed batch, "
+                         "MISS_NONE, the host path, the tables-off pass, the exchange forms (N > 1), the regex fresh batch and "
+                         "host delivery (without it: set up, warm up, the timed steps, the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args, sys.argv[1:]))

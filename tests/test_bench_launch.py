@@ -62,3 +62,28 @@ def test_driver_shapes_dry_run(workload, ranks, extra):
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][-1])
     assert out["n_gpus"] == ranks and out["config"]["ranks_in_group"] == ranks and workload in out["config"]["workload"]
+
+
+def test_steps_must_be_positive():
+    p = run_bench(["--gpus", "1"] + ["--steps", "0"])
+    assert p.returncode != 0 and "--steps" in p.stderr
+
+
+def test_dump_outputs_float64_bounded_and_repeatable(tmp_path):
+    """--dump-outputs: float64 arrays; small outputs whole, large ones as the same seeded sample every time, 64 MB at most."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    small = np.arange(1000, dtype=np.int64) * 3
+    bench.dump_outputs(str(tmp_path / "a"), {"sp": small, "ep": small + 1})
+    got = np.load(tmp_path / "a" / "sp.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, small)
+    big = np.arange(6_000_000, dtype=np.uint64) * np.uint64(1 << 20)       # 2 x 48 MB as float64
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"sp": big, "ep": big + np.uint64(7)})
+    sizes = sum(os.path.getsize(tmp_path / "b" / f) for f in ("sp.npy", "ep.npy"))
+    assert sizes <= bench.DUMP_BYTES + 1024
+    b_sp, b_ep = np.load(tmp_path / "b" / "sp.npy"), np.load(tmp_path / "b" / "ep.npy")
+    assert np.array_equal(b_sp, np.load(tmp_path / "c" / "sp.npy"))
+    assert b_sp.size > 0 and np.all(np.diff(b_sp) > 0) and np.array_equal(b_ep, b_sp + 7)
+    assert np.all(b_sp % (1 << 20) == 0)

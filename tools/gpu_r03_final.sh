@@ -7,19 +7,19 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 python -c "import __graft_entry__ as g; g.build()" > $O/build.log 2>&1 || { echo build failed; exit 1; }
 if [ $PART = all ] || [ $PART = bench ]; then
   for wl in c3 c4 c4ref c2 c5; do
-    timeout -k 10 400 python bench.py --workload $wl > $O/${wl}_bench.json 2> $O/${wl}_bench.log; echo "$wl rc=$?"
+    timeout -k 10 400 python bench.py --full --workload $wl > $O/${wl}_bench.json 2> $O/${wl}_bench.log; echo "$wl rc=$?"
   done
-  FMX_JUMP=0 timeout -k 10 400 python bench.py --workload c3 --no-cpu-baseline > $O/c3_nojump_bench.json 2> $O/c3_nojump_bench.log; echo "c3 (no jump table) rc=$?"
-  FMX_ROWS=0 timeout -k 10 400 python bench.py --workload c5 --no-cpu-baseline > $O/c5_norows_bench.json 2> $O/c5_norows_bench.log; echo "c5 (no row table) rc=$?"
+  FMX_JUMP=0 timeout -k 10 400 python bench.py --full --workload c3 --no-cpu-baseline > $O/c3_nojump_bench.json 2> $O/c3_nojump_bench.log; echo "c3 (no jump table) rc=$?"
+  FMX_ROWS=0 timeout -k 10 400 python bench.py --full --workload c5 --no-cpu-baseline > $O/c5_norows_bench.json 2> $O/c5_norows_bench.log; echo "c5 (no row table) rc=$?"
   for wl in tiny c4tiny c4reftiny; do
-    timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29571 bench.py --gpus 1 --workload $wl --steps 10 --warmup 2 > $O/${wl}_rccl1.json 2> $O/${wl}_rccl1.log; echo "$wl (1-rank RCCL) rc=$?"
+    timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29571 bench.py --full --gpus 1 --workload $wl --steps 10 --warmup 2 > $O/${wl}_rccl1.json 2> $O/${wl}_rccl1.log; echo "$wl (1-rank RCCL) rc=$?"
   done
   timeout -k 10 300 python tools/calcgaps_chain.py 27 128 2>&1 | grep -v amdgpu.ids > $O/calcgaps_chain.txt
   timeout -k 10 300 python tools/measure_host_path.py c3 2>&1 | grep -v amdgpu.ids > $O/host_path.txt; tail -3 $O/host_path.txt
 fi
 if [ $PART = all ] || [ $PART = prof ]; then
   for wl in c3 c4 c4ref c5; do
-    (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$O/bench_trace_$wl -- python3 $REPO/bench.py --workload $wl --no-cpu-baseline > $REPO/$O/${wl}_bench_under_rocprof.json 2> $REPO/$O/${wl}_bench_under_rocprof.err); echo "rocprof bench $wl exit $?"
+    (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$O/bench_trace_$wl -- python3 $REPO/bench.py --full --workload $wl --no-cpu-baseline > $REPO/$O/${wl}_bench_under_rocprof.json 2> $REPO/$O/${wl}_bench_under_rocprof.err); echo "rocprof bench $wl exit $?"
     python - $O $wl <<'PY'
 import csv,glob,sys
 O,wl=sys.argv[1],sys.argv[2]

@@ -54,7 +54,7 @@ c3bound)
   ;;
 bench:*)
   wl=${PART#bench:}
-  timeout -k 10 500 python bench.py --workload $wl > $O/${wl}_bench.json 2> $O/${wl}_bench.log; echo "bench $wl rc=$?"
+  timeout -k 10 500 python bench.py --full --workload $wl > $O/${wl}_bench.json 2> $O/${wl}_bench.log; echo "bench $wl rc=$?"
   python - $O/${wl}_bench.json <<'PY'
 import json,sys
 try:
@@ -95,7 +95,7 @@ overlap)
   # does the exchange run beside the next step's search?  one-rank RCCL (its gather is a device kernel like any rank's),
   # the collective's stream at default / high priority, the search kernel on all / fewer workgroups per CU
   for prio in 0 1; do for wgs in 0 4 3 2; do
-    FMX_BENCH_NCCL_PRIO=$prio FMX_SEARCH_WGS=$( [ $wgs = 0 ] && echo 8 || echo $wgs ) timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29571 bench.py --gpus 1 --workload c3 --steps 20 --warmup 3 --no-cpu-baseline > $O/overlap_p${prio}_w${wgs}.json 2> $O/overlap_p${prio}_w${wgs}.log
+    FMX_BENCH_NCCL_PRIO=$prio FMX_SEARCH_WGS=$( [ $wgs = 0 ] && echo 8 || echo $wgs ) timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29571 bench.py --full --gpus 1 --workload c3 --steps 20 --warmup 3 --no-cpu-baseline > $O/overlap_p${prio}_w${wgs}.json 2> $O/overlap_p${prio}_w${wgs}.log
     python - $O/overlap_p${prio}_w${wgs}.json $prio $wgs <<'PY'
 import json,sys
 try:
@@ -108,7 +108,7 @@ PY
   ;;
 rccl1:*)
   wl=${PART#rccl1:}
-  timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29571 bench.py --gpus 1 --workload $wl --steps 10 --warmup 2 --no-cpu-baseline > $O/${wl}_one_rank_rccl.json 2> $O/${wl}_one_rank_rccl.log; echo "$wl (1-rank RCCL) rc=$?"
+  timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29571 bench.py --full --gpus 1 --workload $wl --steps 10 --warmup 2 --no-cpu-baseline > $O/${wl}_one_rank_rccl.json 2> $O/${wl}_one_rank_rccl.log; echo "$wl (1-rank RCCL) rc=$?"
   python - $O/${wl}_one_rank_rccl.json <<'PY'
 import json,sys
 try:
@@ -121,7 +121,7 @@ PY
   ;;
 trace:*)
   wl=${PART#trace:}
-  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$O/trace_$wl -- python3 $REPO/bench.py --workload $wl --no-cpu-baseline --no-host-path > $REPO/$O/${wl}_bench_under_rocprof.json 2> $REPO/$O/${wl}_bench_under_rocprof.err); echo "rocprof bench $wl exit $?"
+  (cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$O/trace_$wl -- python3 $REPO/bench.py --full --workload $wl --no-cpu-baseline --no-host-path > $REPO/$O/${wl}_bench_under_rocprof.json 2> $REPO/$O/${wl}_bench_under_rocprof.err); echo "rocprof bench $wl exit $?"
   python - $O $wl <<'PY'
 import csv,glob,sys
 O,wl=sys.argv[1],sys.argv[2]

@@ -16,7 +16,7 @@ for stage in "$@"; do
       echo "smoke exit $rc"; [ $rc -eq 0 ] || { tail -20 $OUT/smoke.log; exit 1; } ;;
     bench:*)
       wl=${stage#bench:}
-      timeout -k 10 600 python bench.py --workload $wl > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err; rc=$?
+      timeout -k 10 600 python bench.py --full --workload $wl > $OUT/bench_$wl.json 2> $OUT/bench_$wl.err; rc=$?
       echo "bench $wl exit $rc"; tail -4 $OUT/bench_$wl.err; [ $rc -eq 0 ] || exit 1
       python - <<PY
 import json
@@ -30,7 +30,7 @@ PY
       ;;
     trace:*)
       wl=${stage#trace:}
-      (cd /tmp && export TMPDIR=/tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$OUT/bench_trace_$wl -- python3 $REPO/bench.py --workload $wl --no-cpu-baseline > $REPO/$OUT/bench_under_rocprof_$wl.json 2> $REPO/$OUT/bench_under_rocprof_$wl.err); rc=$?
+      (cd /tmp && export TMPDIR=/tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $REPO/$OUT/bench_trace_$wl -- python3 $REPO/bench.py --full --workload $wl --no-cpu-baseline > $REPO/$OUT/bench_under_rocprof_$wl.json 2> $REPO/$OUT/bench_under_rocprof_$wl.err); rc=$?
       echo "rocprof bench $wl exit $rc"; [ $rc -eq 0 ] || { tail -5 $OUT/bench_under_rocprof_$wl.err; exit 1; } ;;
     prof:*)
       wl=${stage#prof:}
