@@ -78,6 +78,38 @@ JNIEXPORT jlong JNICALL FN(openBlock0)(JNIEnv *e, jobject self, jbyteArray bwt, 
 
 JNIEXPORT void JNICALL FN(close0)(JNIEnv *e, jobject self, jlong h) { fmx_close(H(h)); }
 
+/* ---- construction from text: BWTMerger2.merge(FileBWTReader), bwtmerger.scala:654-1261 */
+JNIEXPORT jlong JNICALL FN(openText0)(JNIEnv *e, jobject self, jbyteArray text, jint device) {
+  jsize n = (*e)->GetArrayLength(e, text);
+  jbyte *t = in_bytes(e, text, n);
+  fmx_index *h = 0;
+  int rc = t ? fmx_open_text((const uint8_t *)t, (uint64_t)n, device, &h) : FMX_ERR_NOMEM;
+  free(t);
+  rethrow(e, rc);
+  return (jlong)(intptr_t)h;
+}
+
+/* X.bwt + X.aux of the text: fmx_bwt_from_text, then fmx_write_bwt in the reference's format */
+JNIEXPORT void JNICALL FN(bwtFilesFromText0)(JNIEnv *e, jobject self, jbyteArray text, jstring bwtPath, jstring auxPath,
+                                             jboolean bigEndian, jint device) {
+  jsize n = (*e)->GetArrayLength(e, text);
+  jbyte *t = in_bytes(e, text, n);
+  uint8_t *bwt = malloc((size_t)n + 1);
+  int64_t counts[256];
+  uint64_t eof = 0;
+  int rc = (t && bwt) ? fmx_bwt_from_text((const uint8_t *)t, (uint64_t)n, bwt, &eof, counts, device) : FMX_ERR_NOMEM;
+  free(t);
+  if (rc == FMX_OK) {
+    const char *b = (*e)->GetStringUTFChars(e, bwtPath, 0);
+    const char *a = (*e)->GetStringUTFChars(e, auxPath, 0);
+    rc = (b && a) ? fmx_write_bwt(b, a, bwt, (uint64_t)n + 1, eof, counts, bigEndian ? 1 : 0) : FMX_ERR_NOMEM;
+    if (b) (*e)->ReleaseStringUTFChars(e, bwtPath, b);
+    if (a) (*e)->ReleaseStringUTFChars(e, auxPath, a);
+  }
+  free(bwt);
+  rethrow(e, rc);
+}
+
 /* ---- scalars: SuffixAlgo.n / cf, findex.scala:10-12 */
 JNIEXPORT jlong JNICALL FN(n0)(JNIEnv *e, jobject self, jlong h) {
   uint64_t v = 0;

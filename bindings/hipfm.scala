@@ -61,9 +61,20 @@ object HipFM {
   @native def regexBatchMatchDirect0(h: Long, batch: Long, limits: Array[Int], maxFrontier: Long, out: ByteBuffer,
                                      perRegex: ByteBuffer, status: Array[Int]): Long
   @native def stats0(h: Long, counters: Array[Long], ms: Array[Double]): Unit
+  @native def openText0(text: Array[Byte], device: Int): Long
+  @native def bwtFilesFromText0(text: Array[Byte], bwtPath: String, auxPath: String, bigEndian: Boolean, device: Int): Unit
 
   val MATCH_FRONTIER = 0      // every match, breadth of the whole batch at once (the throughput path)
   val MATCH_REFERENCE = 1     // ReTree._matchSA's own queue order and limits (re2/retree.scala:618-653)
+
+  /** The index of a text, built on the device (fmx_open_text): what HipFMSearcher would open from the X.bwt / X.aux that
+    * BWTMerger2.merge(FileBWTReader) writes for it -- the BWT of the reversed text -- without the files.  No byte 0. */
+  def fromText(text: Array[Byte], device: Int = 0): HipFMSearcher = new HipFMSearcher(openText0(text, device))
+
+  /** The drop-in for `BWTMerger2.merge` over a `FileBWTReader` (bwtmerger.scala:654-1261): X.bwt and X.aux of the text
+    * (fmx_bwt_from_text + fmx_write_bwt), big-endian as the reference writes them unless bigEndian = false. */
+  def bwtFilesFromText(text: Array[Byte], bwtPath: String, auxPath: String, bigEndian: Boolean = true, device: Int = 0): Unit =
+    bwtFilesFromText0(text, bwtPath, auxPath, bigEndian, device)
 
   def latin1(s: String): Array[Byte] = s.map(_.toByte).toArray
   def fromLatin1(b: Array[Byte]): String = new String(b.map(x => (x & 0xff).toChar))
@@ -141,11 +152,11 @@ trait HipSuffixAlgo extends SuffixAlgo {
 
 /** Same constructor arguments and sibling-file rule as NaiveFMSearcher (bwtmerger.scala:335-338, 17-36); X.fm is not
   * read (its content is a function of X.bwt and X.aux; `writeFm` produces it for the reference's own tools). */
-class HipFMSearcher(filename: String, bigEndian: Boolean = true, device: Int = 0)
-    extends SuffixWalkingAlgo with HipSuffixAlgo {
+class HipFMSearcher private[fmindex] (opened: Long) extends SuffixWalkingAlgo with HipSuffixAlgo {
   import HipFM._
-  protected val hbox =
-    new AtomicLong(open0(BWTTempStorage.genBWTFilename(filename), BWTTempStorage.genAuxFilename(filename), bigEndian, device))
+  def this(filename: String, bigEndian: Boolean = true, device: Int = 0) =
+    this(HipFM.open0(BWTTempStorage.genBWTFilename(filename), BWTTempStorage.genAuxFilename(filename), bigEndian, device))
+  protected val hbox = new AtomicLong(opened)
   val K = 256
   lazy val eof: Long = eof0(h)
   def handle: Long = h

@@ -77,6 +77,10 @@ SYMBOLS = {
     "fmx_open_dev": (_i32, [_vp, _u64, _u64, _vp, _i32, _vp, _P(_vp)]),
     "fmx_open_block": (_i32, [_vp, _u64, _vp, _u64, _i32, _P(_vp)]),
     "fmx_close": (_i32, [_vp]),
+    "fmx_bwt_from_text": (_i32, [_vp, _u64, _vp, _P(_u64), _vp, _i32]),
+    "fmx_bwt_from_text_dev": (_i32, [_vp, _u64, _vp, _vp, _P(_u64), _vp, _i32, _vp]),
+    "fmx_open_text": (_i32, [_vp, _u64, _i32, _P(_vp)]),
+    "fmx_write_bwt": (_i32, [_cp, _cp, _vp, _u64, _u64, _vp, _i32]),
     "fmx_index_config_set": (_i32, [_vp, _cp, _cp]),
     "fmx_prepare": (_i32, [_vp, _u32]),
     "fmx_prepare_ex": (_i32, [_vp, _u32, _u64]),

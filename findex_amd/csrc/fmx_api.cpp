@@ -1246,6 +1246,137 @@ int fmx_write_fm(const fmx_index *idx, const char *path) {
   return FMX_OK;
 }
 
+// ---------------------------------------------------------------- construction from text (fmx_sufsort.hip)
+static constexpr uint64_t kMaxTextLen = 0xfffffffeull;       // 2^32 - 2: len + 1 suffixes fit u32
+
+// What is checked before the device is touched; host text (may be null for the _dev form) is scanned for byte 0.
+static int text_args(const void *text, uint64_t len, const uint8_t *host_text) {
+  if (!text) return arg_fail("text is null");
+  if (len == 0) return arg_fail("len must be >= 1");
+  if (len > kMaxTextLen) {
+    g_err = "text of " + std::to_string(len) + " bytes: construction takes at most 2^32 - 2 bytes (u32 suffix indices)";
+    return FMX_ERR_UNSUPPORTED;
+  }
+  if (host_text && std::memchr(host_text, 0, (size_t)len)) {
+    g_err = "the text contains byte 0 (findex's readers escape it; counts[0] must be 0)";
+    return FMX_ERR_UNSUPPORTED;
+  }
+  return FMX_OK;
+}
+
+static int use_text_device(int device) {
+  int ndev = 0;
+  hipError_t e = hipGetDeviceCount(&ndev);
+  if (e != hipSuccess || ndev == 0) { g_err = "no HIP device available (libfmx has no CPU fallback)"; return FMX_ERR_HIP; }
+  if (device < 0 || device >= ndev) return arg_fail("device index out of range");
+  HIP_TRY(hipSetDevice(device), "hipSetDevice");
+  return FMX_OK;
+}
+
+static int not_capturing(hipStream_t st) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  HIP_TRY(hipStreamIsCapturing(st, &cs), "hipStreamIsCapturing");
+  if (cs != hipStreamCaptureStatusNone) {
+    g_err = "index construction allocates and synchronises: not under a stream capture";
+    return FMX_ERR_HIP;
+  }
+  return FMX_OK;
+}
+
+// The host-pointer forms: text to HBM, construction, BWT to `bwt_out` (host) or into a handle (fmx_open_text).
+static int text_to_device_bwt(const uint8_t *text, uint64_t len, int device, uint8_t *bwt_out, uint64_t *eof,
+                              int64_t counts[256], fmx_index **idx_out) {
+  int rc = use_text_device(device);
+  if (rc) return rc;
+  const uint64_t n = len + 1;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
+  const uint64_t need = sufsort_peak_bytes(len, false) + len + n;
+  if (need > free_b) {
+    g_err = "suffix sort of " + std::to_string(len) + " bytes needs " + std::to_string(need) + " bytes of device memory, " +
+            std::to_string((unsigned long long)free_b) + " are free";
+    return FMX_ERR_NOMEM;
+  }
+  struct Bufs {
+    void *text = nullptr, *bwt = nullptr;
+    ~Bufs() { if (text) (void)hipFree(text); if (bwt) (void)hipFree(bwt); }
+  } b;
+  StreamGuard own;
+  HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
+  hipError_t e = hipMalloc(&b.text, len);
+  if (e == hipSuccess) e = hipMalloc(&b.bwt, n);
+  if (e != hipSuccess) { g_err = std::string("hipMalloc(text, bwt): ") + hipGetErrorString(e); return FMX_ERR_NOMEM; }
+  HIP_TRY(hipMemcpyAsync(b.text, text, len, hipMemcpyHostToDevice, own.s), "H2D(text)");
+  rc = sufsort_bwt(b.text, len, b.bwt, nullptr, eof, counts, own.s, 0);
+  if (rc) return rc;
+  (void)hipFree(b.text);
+  b.text = nullptr;
+  if (bwt_out) {
+    HIP_TRY(hipMemcpyAsync(bwt_out, b.bwt, n, hipMemcpyDeviceToHost, own.s), "D2H(bwt)");
+    HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
+    return FMX_OK;
+  }
+  return open_common(b.bwt, true, nullptr, n, *eof, counts, device, own.s, idx_out);
+}
+
+int fmx_bwt_from_text(const uint8_t *text, uint64_t len, uint8_t *bwt, uint64_t *eof, int64_t counts[256], int device) {
+  int rc = text_args(text, len, text);
+  if (rc) return rc;
+  if (!bwt || !eof || !counts) return arg_fail("null argument");
+  return text_to_device_bwt(text, len, device, bwt, eof, counts, nullptr);
+}
+
+int fmx_bwt_from_text_dev(const void *d_text, uint64_t len, void *d_bwt, void *d_sa_or_null, uint64_t *eof,
+                          int64_t counts[256], int device, void *stream) {
+  int rc = text_args(d_text, len, nullptr);
+  if (rc) return rc;
+  if (!d_bwt || !eof || !counts) return arg_fail("null argument");
+  if ((rc = use_text_device(device))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = not_capturing(st))) return rc;
+  return sufsort_bwt(d_text, len, d_bwt, d_sa_or_null, eof, counts, st, 0);
+}
+
+int fmx_open_text(const uint8_t *text, uint64_t len, int device, fmx_index **out) {
+  if (!out) return arg_fail("out is null");
+  *out = nullptr;
+  int rc = text_args(text, len, text);
+  if (rc) return rc;
+  uint64_t eof = 0;
+  int64_t counts[256];
+  return text_to_device_bwt(text, len, device, nullptr, &eof, counts, out);
+}
+
+// BWTLoader / AUXLoader's formats (bwtmerger.scala:130-174): int64 size, int64 eof, the bytes; 256 int64 counts.
+int fmx_write_bwt(const char *bwt_path, const char *aux_path, const uint8_t *bwt, uint64_t n, uint64_t eof,
+                  const int64_t counts[256], int big_endian) {
+  if (!bwt_path || !aux_path || !bwt || !counts) return arg_fail("null argument");
+  if (n < 1 || eof >= n) return arg_fail("need n >= 1 and eof < n");
+  auto put = [big_endian](uint8_t *p, uint64_t v) {
+    for (int i = 0; i < 8; i++) p[big_endian ? i : 7 - i] = (uint8_t)(v >> (56 - 8 * i));
+  };
+  {
+    FILE *f = std::fopen(bwt_path, "wb");
+    if (!f) { g_err = std::string("cannot create ") + bwt_path; return FMX_ERR_IO; }
+    std::unique_ptr<FILE, int (*)(FILE *)> guard(f, std::fclose);
+    uint8_t hdr[16];
+    put(hdr, n);
+    put(hdr + 8, eof);
+    if (std::fwrite(hdr, 1, 16, f) != 16 || std::fwrite(bwt, 1, (size_t)n, f) != n) {
+      g_err = std::string("short write on ") + bwt_path;
+      return FMX_ERR_IO;
+    }
+    if (std::fclose(guard.release()) != 0) { g_err = std::string("short write on ") + bwt_path; return FMX_ERR_IO; }
+  }
+  uint8_t aux[2048];
+  for (int c = 0; c < 256; c++) put(aux + 8 * c, (uint64_t)counts[c]);
+  FILE *f = std::fopen(aux_path, "wb");
+  if (!f) { g_err = std::string("cannot create ") + aux_path; return FMX_ERR_IO; }
+  const bool ok = std::fwrite(aux, 1, sizeof aux, f) == sizeof aux;
+  if ((std::fclose(f) != 0) || !ok) { g_err = std::string("short write on ") + aux_path; return FMX_ERR_IO; }
+  return FMX_OK;
+}
+
 // ---------------------------------------------------------------- statistics
 int fmx_stats(const fmx_index *idx, fmx_stats_t *out) {
   if (!idx || !out) return arg_fail("null argument");

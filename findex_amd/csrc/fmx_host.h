@@ -201,6 +201,12 @@ int hip_fail(hipError_t e, const char *what);   // records the message, returns 
 // fmx_build.hip
 int build_index(Index *h, hipStream_t st, const int64_t *given_counts);   // returns an FMX_* status
 
+// fmx_sufsort.hip: index construction from text (fmx_bwt_from_text*, fmx_open_text); arguments checked by the caller,
+// `extra` = device bytes the caller still allocates, counted in the free-memory check.  Synchronises `st`.
+uint64_t sufsort_peak_bytes(uint64_t len, bool sa_given);
+int sufsort_bwt(const void *d_text, uint64_t len, void *d_bwt, void *d_sa_or_null, uint64_t *eof, int64_t counts[256],
+                hipStream_t st, uint64_t extra);
+
 // fmx_kernels.hip (launch_psi, launch_next_substr: fmx_select.hip)
 hipError_t launch_occ(const Index *h, const void *d_c, const void *d_i, void *d_out, uint64_t k, hipStream_t st);
 hipError_t launch_prev_range(const Index *h, const void *d_sp, const void *d_ep, const void *d_c, void *d_sp1,

@@ -1,0 +1,470 @@
+// fmx_sufsort.hip -- index construction: text -> suffix array -> BWT + EOF row + counts, on the device.
+//
+// The reference builds its BWT with BWTMerger2.merge over a FileBWTReader (bwtmerger.scala:654-1261): the input file is
+// reversed (copyReverse, :1106-1108), sorted block by block and merged on disk, and sa2BWT (:782-810) writes row i as the
+// byte before suffix SA[i], with the row of the whole string (the EOF row) filled by a neighbour's byte.  Here the whole
+// string s = reverse(text) + 0 is suffix-sorted in HBM by prefix doubling:
+//
+//   round 1  : every suffix keyed by its first 8 bytes (big-endian u64, 0 past the end), one LSD radix sort -> h = 8.
+//              0 is the unique smallest symbol, so a suffix whose first 8 bytes reach the sentinel is already alone.
+//   round r  : only the suffixes still in groups of two or more (the ACTIVE list, in SA order) are re-sorted, keyed by
+//              (rank[i], rank[i + h]) packed into 2 * ceil(log2 n) bits; rank[i] is the SA position of the head of i's
+//              group, so an active group occupies the same SA positions before and after its members are re-sorted.
+//              Then the new group heads are flagged, max-scanned and scattered into rank[], singletons leave the list.
+//   emit     : bwt[j] = s[sa[j] - 1]; the row with sa[j] == 0 is eof; the 256-entry histogram of the text.
+//
+// Radix sort: 8-bit digits, one pass = k_sa_hist (per 4096-key tile histogram, digit-major) + exclusive scan +
+// k_sa_scatter (stable: a tile goes through in 256-key chunks, each key's place among its digit's keys from eight
+// wave ballots).  Everything is u32 index / u64 key; a loop index is u64, so positions >= 2^31 stay unsigned throughout.
+//
+// Working set (bytes per suffix, n = len + 1): s (1) + sa (4) + rank (4) + two key buffers (16) + two value buffers (8)
+// + the active list (4) = 37, plus the digit histograms (1/4) and the scan partials (< 1/500).  The host-pointer entry
+// points add the text and the BWT in HBM (2).  No library sort, no host sort.
+#include <fmx.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "fmx_host.h"
+
+namespace fmx {
+
+constexpr int kSaThreads = 256;
+constexpr uint32_t kSaTile = 4096;                  // keys per radix tile: 16 chunks of 256
+constexpr uint32_t kScanTile = 2048;                // elements per scan block: 8 per thread
+constexpr int kScanSum = 0, kScanMax = 1;
+
+__device__ __forceinline__ uint32_t scan_op(int op, uint32_t a, uint32_t b) { return op == kScanMax ? (a > b ? a : b) : a + b; }
+
+static unsigned sa_grid(uint64_t m) {
+  const uint64_t b = (m + kSaThreads - 1) / kSaThreads;
+  return (unsigned)(b < 1 ? 1 : b > 8192 ? 8192 : b);
+}
+
+// s[j] = text[len - 1 - j], s[len .. len + 7] = 0 (the sentinel and the padding the first-round keys read);
+// *zero != 0 when the text holds a 0 byte.
+__global__ __launch_bounds__(kSaThreads) void k_sa_reverse(const uint8_t *__restrict__ text, uint64_t len,
+                                                           uint8_t *__restrict__ s, uint32_t *__restrict__ zero) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  bool z = false;
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < len + 8; j += stride) {
+    if (j < len) {
+      const uint8_t c = text[len - 1 - j];
+      z |= c == 0;
+      s[j] = c;
+    } else {
+      s[j] = 0;
+    }
+  }
+  if (z) atomicOr(zero, 1u);
+}
+
+// round 1: key = s[i .. i + 7] big-endian, value = i
+__global__ __launch_bounds__(kSaThreads) void k_sa_init(const uint8_t *__restrict__ s, uint64_t n,
+                                                        unsigned long long *__restrict__ key, uint32_t *__restrict__ val) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    unsigned long long k = 0;
+    for (int t = 0; t < 8; t++) k = (k << 8) | s[i + t];
+    key[i] = k;
+    val[i] = (uint32_t)i;
+  }
+}
+
+// round r: active suffix i = sa[ap[k]] keyed by (rank[i], rank[i + h]); i + h < n for every active suffix (a suffix whose
+// h-prefix reaches the sentinel is alone in its group), the bound below only keeps a broken invariant in bounds
+__global__ __launch_bounds__(kSaThreads) void k_sa_keys(const uint32_t *__restrict__ ap, uint64_t m,
+                                                        const uint32_t *__restrict__ sa, const uint32_t *__restrict__ rank,
+                                                        uint64_t n, uint64_t h, int bits,
+                                                        unsigned long long *__restrict__ key, uint32_t *__restrict__ val) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < m; k += stride) {
+    const uint32_t i = sa[ap[k]];
+    const uint64_t i2 = (uint64_t)i + h;
+    const uint32_t r2 = i2 < n ? rank[i2] : 0u;
+    key[k] = ((unsigned long long)rank[i] << bits) | r2;
+    val[k] = i;
+  }
+}
+
+// ---- LSD radix sort of (u64 key, u32 value), 8 bits per pass
+__global__ __launch_bounds__(kSaThreads) void k_sa_hist(const unsigned long long *__restrict__ key, uint64_t m, int shift,
+                                                        uint32_t *__restrict__ hist /* [256][ntiles] */, uint64_t ntiles) {
+  __shared__ uint32_t h[256];
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  const uint64_t base = (uint64_t)blockIdx.x * kSaTile;
+  for (uint32_t c = 0; c < kSaTile; c += kSaThreads) {
+    const uint64_t idx = base + c + threadIdx.x;
+    if (idx < m) atomicAdd(&h[(key[idx] >> shift) & 255u], 1u);
+  }
+  __syncthreads();
+  hist[(uint64_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
+}
+
+// hist: the exclusive scan of k_sa_hist's output = where this tile's first key of each digit goes.  Stable: inside a
+// 256-key chunk a key's place is its lane rank among the wave's keys of its digit (eight ballots) plus the counts of
+// the waves before it; chunks follow each other through base[].
+__global__ __launch_bounds__(kSaThreads) void k_sa_scatter(const unsigned long long *__restrict__ kin,
+                                                           const uint32_t *__restrict__ vin,
+                                                           unsigned long long *__restrict__ kout,
+                                                           uint32_t *__restrict__ vout, uint64_t m, int shift,
+                                                           const uint32_t *__restrict__ hist, uint64_t ntiles) {
+  __shared__ uint32_t base[256];
+  __shared__ uint32_t wc[kSaThreads / 64][256];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned long long lt = (1ull << lane) - 1;
+  base[tid] = hist[(uint64_t)tid * ntiles + blockIdx.x];
+  const uint64_t tile = (uint64_t)blockIdx.x * kSaTile;
+  for (uint32_t c = 0; c < kSaTile; c += kSaThreads) {
+    const uint64_t idx = tile + c + tid;
+    const bool valid = idx < m;
+    const unsigned long long k = valid ? kin[idx] : 0ull;
+    const uint32_t v = valid ? vin[idx] : 0u;
+    const uint32_t d = (uint32_t)(k >> shift) & 255u;
+    for (int w = 0; w < kSaThreads / 64; w++) wc[w][tid] = 0;
+    __syncthreads();
+    unsigned long long mm = __ballot(valid);
+    for (int b = 0; b < 8; b++) {
+      const bool bit = (d >> b) & 1u;
+      const unsigned long long bb = __ballot(bit);
+      mm &= bit ? bb : ~bb;
+    }
+    const uint32_t r = (uint32_t)__popcll(mm & lt);
+    if (valid && r == 0) wc[wave][d] = (uint32_t)__popcll(mm);
+    __syncthreads();
+    if (valid) {
+      uint32_t dst = base[d] + r;
+      for (int w = 0; w < wave; w++) dst += wc[w][d];
+      kout[dst] = k;
+      vout[dst] = v;
+    }
+    __syncthreads();
+    uint32_t add = 0;
+    for (int w = 0; w < kSaThreads / 64; w++) add += wc[w][tid];
+    base[tid] += add;
+    __syncthreads();
+  }
+}
+
+// ---- scans of u32 (sum or max; inclusive or exclusive), 2048 elements per block, block totals scanned recursively
+__global__ __launch_bounds__(kSaThreads) void k_sa_scan_tile(uint32_t *__restrict__ d, uint64_t len,
+                                                             uint32_t *__restrict__ sums, int op, int exclusive) {
+  __shared__ uint32_t t[kSaThreads];
+  const uint64_t base = (uint64_t)blockIdx.x * kScanTile + (uint64_t)threadIdx.x * 8;
+  uint32_t x[8], acc = 0;                   // 0 is the identity of both operators
+  for (int e = 0; e < 8; e++) {
+    x[e] = base + e < len ? d[base + e] : 0u;
+    acc = scan_op(op, acc, x[e]);
+  }
+  t[threadIdx.x] = acc;
+  __syncthreads();
+  for (int off = 1; off < kSaThreads; off <<= 1) {
+    const uint32_t y = (int)threadIdx.x >= off ? t[threadIdx.x - off] : 0u;
+    __syncthreads();
+    t[threadIdx.x] = scan_op(op, t[threadIdx.x], y);
+    __syncthreads();
+  }
+  uint32_t run = threadIdx.x ? t[threadIdx.x - 1] : 0u;
+  for (int e = 0; e < 8; e++) {
+    const uint32_t before = run;
+    run = scan_op(op, run, x[e]);
+    if (base + e < len) d[base + e] = exclusive ? before : run;
+  }
+  if (threadIdx.x == kSaThreads - 1) sums[blockIdx.x] = t[kSaThreads - 1];
+}
+
+__global__ __launch_bounds__(kSaThreads) void k_sa_scan_add(uint32_t *__restrict__ d, uint64_t len,
+                                                            const uint32_t *__restrict__ sums, int op) {
+  const uint32_t carry = sums[blockIdx.x];
+  const uint64_t base = (uint64_t)blockIdx.x * kScanTile;
+  for (uint32_t e = threadIdx.x; e < kScanTile; e += kSaThreads)
+    if (base + e < len) d[base + e] = scan_op(op, carry, d[base + e]);
+}
+
+// ---- group heads and ranks
+__device__ __forceinline__ bool sa_head(const unsigned long long *key, uint64_t k) { return k == 0 || key[k] != key[k - 1]; }
+
+__global__ __launch_bounds__(kSaThreads) void k_sa_heads(const unsigned long long *__restrict__ key, uint64_t m,
+                                                         uint32_t *__restrict__ hp) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < m; k += stride)
+    hp[k] = sa_head(key, k) ? (uint32_t)k : 0u;
+}
+
+// hp: the max-scanned heads (index of k's group head in the sorted list).  ap == nullptr in round 1 (the list is all of
+// SA, position k).  Writes sa and rank; keep[k] = 1 when k's group has two members or more.
+__global__ __launch_bounds__(kSaThreads) void k_sa_rank(const unsigned long long *__restrict__ key,
+                                                        const uint32_t *__restrict__ val, const uint32_t *__restrict__ hp,
+                                                        const uint32_t *__restrict__ ap, uint64_t m,
+                                                        uint32_t *__restrict__ sa, uint32_t *__restrict__ rank,
+                                                        uint32_t *__restrict__ keep) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < m; k += stride) {
+    const uint32_t i = val[k];
+    const uint32_t pos = ap ? ap[k] : (uint32_t)k;
+    sa[pos] = i;
+    rank[i] = ap ? ap[hp[k]] : hp[k];
+    const bool single = sa_head(key, k) && (k + 1 == m || key[k + 1] != key[k]);
+    keep[k] = single ? 0u : 1u;
+  }
+}
+
+// incl: the inclusive sum of keep; the kept SA positions move to the front of the next active list, in order
+__global__ __launch_bounds__(kSaThreads) void k_sa_compact(const uint32_t *__restrict__ incl, const uint32_t *__restrict__ ap,
+                                                           uint64_t m, uint32_t *__restrict__ ap_next) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < m; k += stride) {
+    const uint32_t before = k ? incl[k - 1] : 0u;
+    if (incl[k] != before) ap_next[before] = ap ? ap[k] : (uint32_t)k;
+  }
+}
+
+// ---- the BWT: bwt[j] = s[sa[j] - 1], eof = the row with sa[j] == 0, counts = the histogram of the other rows
+__global__ __launch_bounds__(kSaThreads) void k_sa_emit(const uint8_t *__restrict__ s, const uint32_t *__restrict__ sa,
+                                                        uint64_t n, uint8_t *__restrict__ bwt,
+                                                        unsigned long long *__restrict__ out /* [0] eof, [1..256] counts */) {
+  __shared__ uint32_t h[256];
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {
+    const uint32_t p = sa[j];
+    if (p == 0) {
+      out[0] = j;
+    } else {
+      const uint8_t c = s[p - 1];
+      bwt[j] = c;
+      atomicAdd(&h[c], 1u);
+    }
+  }
+  __syncthreads();
+  if (h[threadIdx.x]) atomicAdd(&out[1 + threadIdx.x], (unsigned long long)h[threadIdx.x]);
+}
+
+// the EOF row's filler, sa2BWT (bwtmerger.scala:799-806): the byte of the row above, of the row below for eof == 0
+__global__ void k_sa_eof_fill(const uint8_t *__restrict__ s, const uint32_t *__restrict__ sa, uint64_t n,
+                              uint8_t *__restrict__ bwt, const unsigned long long *__restrict__ out) {
+  const uint64_t e = out[0];
+  if (e >= n || n < 2) return;
+  const uint32_t q = e > 0 ? sa[e - 1] : sa[1];
+  bwt[e] = q ? s[q - 1] : 0;
+}
+
+// ---- host side
+namespace {
+
+struct DevMem {                 // every temporary of one construction; freed on every return path
+  std::vector<void *> ps;
+  ~DevMem() { for (void *p : ps) (void)hipFree(p); }
+  hipError_t get(void **out, size_t bytes) {
+    *out = nullptr;
+    hipError_t e = hipMalloc(out, bytes ? bytes : 16);
+    if (e == hipSuccess) ps.push_back(*out);
+    return e;
+  }
+};
+
+uint64_t ntiles_of(uint64_t m) { return (m + kSaTile - 1) / kSaTile; }
+
+uint64_t scan_partials(uint64_t len) {         // u32 slots the recursive scan of len elements needs for its block totals
+  uint64_t t = 0;
+  while (len > 1) { len = (len + kScanTile - 1) / kScanTile; t += len; }
+  return t + 1;
+}
+
+hipError_t scan_u32(uint32_t *d, uint64_t len, int op, bool exclusive, uint32_t *partials, hipStream_t st) {
+  if (len == 0) return hipSuccess;
+  const uint64_t nb = (len + kScanTile - 1) / kScanTile;
+  hipLaunchKernelGGL(k_sa_scan_tile, dim3((unsigned)nb), dim3(kSaThreads), 0, st, d, len, partials, op, exclusive ? 1 : 0);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || nb == 1) return e;
+  // the block totals: their exclusive scan (a max's exclusive prefix is the max of the blocks before)
+  if ((e = scan_u32(partials, nb, op, true, partials + nb, st)) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_sa_scan_add, dim3((unsigned)nb), dim3(kSaThreads), 0, st, d, len, partials, op);
+  return hipGetLastError();
+}
+
+// Sorts m (key, value) pairs by the key's low `bits` bits; the result is in (*k, *v), the other pair of buffers is free.
+hipError_t radix_sort(unsigned long long **k, uint32_t **v, unsigned long long **k_alt, uint32_t **v_alt, uint64_t m,
+                      int bits, uint32_t *hist, uint32_t *partials, hipStream_t st, int *passes) {
+  const uint64_t nt = ntiles_of(m);
+  *passes = 0;
+  for (int shift = 0; shift < bits; shift += 8) {
+    hipLaunchKernelGGL(k_sa_hist, dim3((unsigned)nt), dim3(kSaThreads), 0, st, *k, m, shift, hist, nt);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if ((e = scan_u32(hist, 256 * nt, kScanSum, true, partials, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_sa_scatter, dim3((unsigned)nt), dim3(kSaThreads), 0, st, *k, *v, *k_alt, *v_alt, m, shift, hist, nt);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    std::swap(*k, *k_alt);
+    std::swap(*v, *v_alt);
+    ++*passes;
+  }
+  return hipSuccess;
+}
+
+// FMX_SUFSORT_LOG=<file>: one JSON line per construction appended to the file (tools/build_text_bench.py reads it)
+struct RoundLog { uint64_t h, active; int passes; float ms; double bytes; };
+
+void write_log(const char *path, uint64_t n, double alloc_ms, double total_ms, const std::vector<RoundLog> &rounds,
+               uint64_t peak) {
+  FILE *f = std::fopen(path, "a");
+  if (!f) return;
+  std::fprintf(f, "{\"n\": %llu, \"peak_bytes\": %llu, \"alloc_ms\": %.3f, \"total_ms\": %.3f, \"rounds\": [",
+               (unsigned long long)n, (unsigned long long)peak, alloc_ms, total_ms);
+  for (size_t r = 0; r < rounds.size(); r++)
+    std::fprintf(f, "%s{\"h\": %llu, \"active\": %llu, \"passes\": %d, \"kernel_ms\": %.3f, \"bytes\": %.0f}", r ? ", " : "",
+                 (unsigned long long)rounds[r].h, (unsigned long long)rounds[r].active, rounds[r].passes, rounds[r].ms,
+                 rounds[r].bytes);
+  std::fprintf(f, "]}\n");
+  std::fclose(f);
+}
+
+// Modelled bytes of one round over m keys with `passes` radix passes (what the kernels read and write once each):
+// keys/init 24 m, per pass hist 8 m + scatter 24 m, heads 12 m, scans ~16 m, rank 28 m, compact 12 m.
+double round_bytes(uint64_t m, int passes, bool first) {
+  return (double)m * ((first ? 21.0 : 24.0) + 32.0 * passes + 12.0 + 16.0 + 28.0 + 12.0);
+}
+
+}  // namespace
+
+uint64_t sufsort_peak_bytes(uint64_t len, bool sa_given) {
+  const uint64_t n = len + 1;
+  const uint64_t nt = ntiles_of(n);
+  const uint64_t scan_len = std::max<uint64_t>(n, 256 * nt);
+  return (n + 8) + (sa_given ? 0 : 4 * n) + 4 * n + 16 * n + 12 * n + 4 * 256 * nt + 4 * scan_partials(scan_len) +
+         8 * 257 + 4096;
+}
+
+// The construction proper (include/fmx.h, fmx_bwt_from_text_dev): d_text[len] -> d_bwt[len + 1], eof, counts, and the
+// suffix array of s into d_sa when it is given.  Arguments are checked by the caller; `extra` device bytes the caller
+// still has to allocate are counted in the free-memory check.  Synchronises `st`.
+int sufsort_bwt(const void *d_text, uint64_t len, void *d_bwt, void *d_sa_user, uint64_t *eof, int64_t counts[256],
+                hipStream_t st, uint64_t extra) {
+  const uint64_t n = len + 1;
+  const uint64_t peak = sufsort_peak_bytes(len, d_sa_user != nullptr);
+  size_t free_b = 0, total_b = 0;
+  hipError_t e = hipMemGetInfo(&free_b, &total_b);
+  if (e != hipSuccess) return hip_fail(e, "hipMemGetInfo");
+  if (peak + extra > free_b) {
+    set_error("suffix sort of " + std::to_string(len) + " bytes needs " + std::to_string(peak + extra) +
+              " bytes of device memory, " + std::to_string((unsigned long long)free_b) + " are free");
+    return FMX_ERR_NOMEM;
+  }
+  const char *log_path = std::getenv("FMX_SUFSORT_LOG");
+  const auto t0 = std::chrono::steady_clock::now();
+  DevMem mem;
+  uint8_t *s = nullptr;
+  uint32_t *sa = nullptr, *rank = nullptr, *ap = nullptr, *hist = nullptr, *partials = nullptr, *v0 = nullptr, *v1 = nullptr,
+           *flag = nullptr;
+  unsigned long long *k0 = nullptr, *k1 = nullptr, *out = nullptr;
+  const uint64_t nt = ntiles_of(n);
+  const uint64_t scan_len = std::max<uint64_t>(n, 256 * nt);
+#define SA_ALLOC(p, bytes)                                                         \
+  do {                                                                             \
+    if ((e = mem.get((void **)&(p), (bytes))) != hipSuccess) {                     \
+      set_error(std::string("hipMalloc(suffix sort): ") + hipGetErrorString(e));   \
+      return FMX_ERR_NOMEM;                                                        \
+    }                                                                              \
+  } while (0)
+  SA_ALLOC(s, n + 8);
+  if (d_sa_user) sa = static_cast<uint32_t *>(d_sa_user);
+  else SA_ALLOC(sa, 4 * n);
+  SA_ALLOC(rank, 4 * n);
+  SA_ALLOC(k0, 8 * n);
+  SA_ALLOC(k1, 8 * n);
+  SA_ALLOC(v0, 4 * n);
+  SA_ALLOC(v1, 4 * n);
+  SA_ALLOC(ap, 4 * n);
+  SA_ALLOC(hist, 4 * 256 * nt);
+  SA_ALLOC(partials, 4 * scan_partials(scan_len));
+  SA_ALLOC(out, 8 * 257 + 8);
+#undef SA_ALLOC
+  flag = reinterpret_cast<uint32_t *>(out + 257);
+  const double alloc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+#define SA_TRY(call, what)                       \
+  do {                                           \
+    if ((e = (call)) != hipSuccess) return hip_fail(e, what); \
+  } while (0)
+#define SA_LAUNCH(...)                                              \
+  do {                                                              \
+    hipLaunchKernelGGL(__VA_ARGS__);                                \
+    SA_TRY(hipGetLastError(), "suffix sort kernel launch");          \
+  } while (0)
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 2; i++) if (ev[i]) (void)hipEventDestroy(ev[i]); } } evg{ev};
+  if (log_path) {
+    SA_TRY(hipEventCreate(&ev[0]), "hipEventCreate");
+    SA_TRY(hipEventCreate(&ev[1]), "hipEventCreate");
+  }
+  std::vector<RoundLog> rounds;
+  SA_TRY(hipMemsetAsync(out, 0, 8 * 257 + 8, st), "hipMemsetAsync");
+  SA_LAUNCH(k_sa_reverse, dim3(sa_grid(n + 8)), dim3(kSaThreads), 0, st, static_cast<const uint8_t *>(d_text), len, s, flag);
+  uint32_t zero = 0;
+  SA_TRY(hipMemcpyAsync(&zero, flag, 4, hipMemcpyDeviceToHost, st), "D2H");
+  SA_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+  if (zero) {
+    set_error("the text contains byte 0 (findex's readers escape it; counts[0] must be 0)");
+    return FMX_ERR_UNSUPPORTED;
+  }
+  const int bits = 64 - __builtin_clzll((unsigned long long)(n - 1));      // significant bits of a rank (n >= 2)
+  uint64_t m = n, h = 0;
+  uint32_t *list = nullptr;                   // the active list (SA positions); nullptr in round 1: all of them
+  while (m > 0) {
+    if (log_path) SA_TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+    unsigned long long *k = k0, *ka = k1;
+    uint32_t *v = v0, *va = v1;
+    if (h == 0) SA_LAUNCH(k_sa_init, dim3(sa_grid(m)), dim3(kSaThreads), 0, st, s, n, k, v);
+    else SA_LAUNCH(k_sa_keys, dim3(sa_grid(m)), dim3(kSaThreads), 0, st, list, m, sa, rank, n, h, bits, k, v);
+    int passes = 0;
+    SA_TRY(radix_sort(&k, &v, &ka, &va, m, h == 0 ? 64 : 2 * bits, hist, partials, st, &passes), "radix sort");
+    // the free key buffer holds the heads (first m u32) and the keep flags (next m u32)
+    uint32_t *hp = reinterpret_cast<uint32_t *>(ka), *keep = hp + m;
+    SA_LAUNCH(k_sa_heads, dim3(sa_grid(m)), dim3(kSaThreads), 0, st, k, m, hp);
+    SA_TRY(scan_u32(hp, m, kScanMax, false, partials, st), "scan");
+    SA_LAUNCH(k_sa_rank, dim3(sa_grid(m)), dim3(kSaThreads), 0, st, k, v, hp, list, m, sa, rank, keep);
+    SA_TRY(scan_u32(keep, m, kScanSum, false, partials, st), "scan");
+    // the next list goes to the free value buffer; the old list's buffer becomes a value buffer
+    uint32_t *next = va;
+    SA_LAUNCH(k_sa_compact, dim3(sa_grid(m)), dim3(kSaThreads), 0, st, keep, list, m, next);
+    uint32_t m_next = 0;
+    SA_TRY(hipMemcpyAsync(&m_next, keep + (m - 1), 4, hipMemcpyDeviceToHost, st), "D2H");
+    if (log_path) SA_TRY(hipEventRecord(ev[1], st), "hipEventRecord");
+    SA_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if (log_path) {
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+      rounds.push_back({h == 0 ? 8 : 2 * h, m, passes, ms, round_bytes(m, passes, h == 0)});
+    }
+    if ((uint64_t)m_next >= m && h != 0) {    // a round that separates nothing would loop for ever
+      set_error("suffix sort made no progress (internal error)");
+      return FMX_ERR_HIP;
+    }
+    // buffers: v0/v1 are the value buffers, ap the list; rotate so that the list lives in `next`
+    if (next == v0) { v0 = ap; } else { v1 = ap; }
+    ap = next;
+    list = ap;
+    m = m_next;
+    h = h == 0 ? 8 : 2 * h;
+  }
+  SA_LAUNCH(k_sa_emit, dim3(sa_grid(n)), dim3(kSaThreads), 0, st, s, sa, n, static_cast<uint8_t *>(d_bwt), out);
+  SA_LAUNCH(k_sa_eof_fill, dim3(1), dim3(1), 0, st, s, sa, n, static_cast<uint8_t *>(d_bwt), out);
+  unsigned long long host_out[257];
+  SA_TRY(hipMemcpyAsync(host_out, out, sizeof host_out, hipMemcpyDeviceToHost, st), "D2H");
+  SA_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+#undef SA_LAUNCH
+#undef SA_TRY
+  *eof = host_out[0];
+  for (int c = 0; c < 256; c++) counts[c] = (int64_t)host_out[1 + c];
+  if (log_path)
+    write_log(log_path, n, alloc_ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(),
+              rounds, peak);
+  return FMX_OK;
+}
+
+}  // namespace fmx

@@ -97,6 +97,17 @@ class HipFMSearcher:
         return cls(_handle=h)
 
     @classmethod
+    def from_text(cls, text, device=0):
+        """fmx_open_text: the index BWTMerger2.merge(FileBWTReader) would write for this text (the BWT of the reversed
+        text, so that search(reversed pattern) counts the pattern's occurrences), built on the device."""
+        L = _lib.load()
+        t = np.frombuffer(bytes(text), dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else \
+            np.ascontiguousarray(text, dtype=np.uint8).reshape(-1)
+        h = ctypes.c_void_p()
+        _lib.check(L.fmx_open_text(_ptr(t), t.size, int(device), ctypes.byref(h)))
+        return cls(_handle=h)
+
+    @classmethod
     def from_block(cls, bwt, bucketStarts, rk0, device=0):
         """`new NaiveBWTSearcher(bwt, bucketStarts, rk0)` (findex.scala:459-506): one merge block's BWT, the caller's
         bucket starts, row rk0 skipped."""

@@ -151,6 +151,36 @@ int fmx_open_dev(const void *d_bwt, uint64_t n, uint64_t eof, const int64_t *cou
 int fmx_open_block(const uint8_t *bwt, uint64_t n, const int64_t bucket_starts[256], uint64_t rk0, int device,
                    fmx_index **out);
 int fmx_close(fmx_index *idx);          /* NULL: nothing to close, FMX_OK */
+
+/* ---- construction from text: BWTMerger2.merge(FileBWTReader), bwtmerger.scala:654-1261 --------------
+ * text -> BWT of reverse(text) + EOF, as the merger writes it (copyReverse :1106-1108, sa2BWT :782-810, aux
+ * :841-856): bwt[i] is the byte before suffix SA[i] of s = reverse(text) + sentinel, *eof the row whose suffix is
+ * all of s, filled with the byte of the row above (of the row below when eof == 0); counts[c] = occurrences of c
+ * in the text.  A hand-written suffix sort on the device (prefix doubling over LSD radix sorts).
+ *  - 1 <= len <= 2^32 - 2 (n = len + 1 suffixes, u32 indices); len > 2^32 - 2 -> FMX_ERR_UNSUPPORTED.
+ *  - NULL pointer or len == 0 -> FMX_ERR_ARG; a 0 byte in the text -> FMX_ERR_UNSUPPORTED (the reference's readers
+ *    escape byte 0 and counts[0] must be 0, as for fmx_open_block).  These are checked before the device is touched
+ *    (the 0 byte of a device-resident text is found by the first kernel: FMX_ERR_UNSUPPORTED then too).  A valid text
+ *    without a device: FMX_ERR_HIP, no CPU fallback.
+ *  - Construction ALLOCATES AND SYNCHRONISES: it is not a _dev call in the sense of the fmx_prepare contract, and it
+ *    returns FMX_ERR_HIP under a stream capture.  Peak device memory: ~37.3 bytes per text byte of temporaries (4 of
+ *    them the suffix array, which a given d_sa_or_null replaces; the host-pointer forms add 2 for the text and the BWT
+ *    in HBM), checked against the free HBM before anything is allocated: FMX_ERR_NOMEM, with the need in the message.  Every temporary is freed
+ *    before the call returns; the same text gives the same bytes on every run.
+ * fmx_bwt_from_text     : host text in, host bwt[len + 1] out.
+ * fmx_bwt_from_text_dev : device text in, device bwt[len + 1] out, enqueued on `stream` (a hipStream_t, NULL: the
+ *                         null stream) and synchronised; d_sa_or_null, when given, receives the suffix array of s
+ *                         (u32[len + 1]).  eof and counts are host pointers.
+ * fmx_open_text         : the index of the text, as fmx_open of the files fmx_bwt_from_text would give (the BWT
+ *                         never leaves the device).
+ * fmx_write_bwt         : X.bwt (BWTLoader, :144-174: int64 size, int64 eof, then the n bytes) and X.aux (AUXLoader,
+ *                         :130-142: 256 int64 counts), big- or little-endian; host only. */
+int fmx_bwt_from_text(const uint8_t *text, uint64_t len, uint8_t *bwt, uint64_t *eof, int64_t counts[256], int device);
+int fmx_bwt_from_text_dev(const void *d_text, uint64_t len, void *d_bwt, void *d_sa_or_null, uint64_t *eof,
+                          int64_t counts[256], int device, void *stream);
+int fmx_open_text(const uint8_t *text, uint64_t len, int device, fmx_index **out);
+int fmx_write_bwt(const char *bwt_path, const char *aux_path, const uint8_t *bwt, uint64_t n, uint64_t eof,
+                  const int64_t counts[256], int big_endian);
 /* One handle's own table policy (the keys fmx_config_set lists as table keys; FMX_ERR_ARG for any other key or a bad value).
  * Tables that exist are not touched: fmx_drop_tables + fmx_prepare rebuild under the new policy. */
 int fmx_index_config_set(fmx_index *idx, const char *key, const char *value);
