@@ -451,7 +451,7 @@ JNIEXPORT void JNICALL FN(prepareEx0)(JNIEnv *e, jobject self, jlong h, jint wha
   rethrow(e, budgetBytes < 0 ? FMX_ERR_ARG : fmx_prepare_ex((fmx_index *)H(h), (unsigned)what, (uint64_t)budgetBytes));
 }
 
-/* fmx_index_config_set: one handle's own table policy ("ktab", "jump", "jump_pairs", "jump_chars", "tables_after", "table_budget") */
+/* fmx_index_config_set: one handle's own table policy ("ktab", "jump", "jump_pairs", "search_lanes", "jump_chars", "tables_after", "table_budget") */
 JNIEXPORT void JNICALL FN(indexConfigSet0)(JNIEnv *e, jobject self, jlong h, jstring key, jstring value) {
   const char *k = (*e)->GetStringUTFChars(e, key, 0);
   const char *v = (*e)->GetStringUTFChars(e, value, 0);

@@ -199,7 +199,7 @@ class HipFMSearcher private[fmindex] (opened: Long) extends SuffixWalkingAlgo wi
   def prepare(what: Int): Unit = prepare0(h, what)
   /** The same under a budget: at most budgetBytes of device memory for all derived tables of this handle (fmx_prepare_ex). */
   def prepare(what: Int, budgetBytes: Long): Unit = prepareEx0(h, what, budgetBytes)
-  /** This handle's own table policy (fmx_index_config_set): "ktab", "jump", "jump_pairs", "jump_chars", "tables_after", "table_budget". */
+  /** This handle's own table policy (fmx_index_config_set): "ktab", "jump", "jump_pairs", "search_lanes", "jump_chars", "tables_after", "table_budget". */
   def configSet(key: String, value: String): Unit = indexConfigSet0(h, key, value)
   def dropTables(): Unit = dropTables0(h, 4 | 8)
 }

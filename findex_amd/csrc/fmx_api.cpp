@@ -518,7 +518,7 @@ int fmx_index_config_set(fmx_index *idx, const char *key, const char *value) {
   const int pr = policy_set(H(idx)->policy, key, value, &why);
   if (pr == 0) return FMX_OK;
   if (pr == 2) return arg_fail(why);
-  return arg_fail("not a per-handle key (ktab, jump, jump_pairs, jump_chars, tables_after, table_budget)");
+  return arg_fail("not a per-handle key (ktab, jump, jump_pairs, search_lanes, jump_chars, tables_after, table_budget)");
 }
 
 int fmx_host_alloc(size_t bytes, void **out) {

@@ -56,6 +56,7 @@ struct TablePolicy {
   std::atomic<int> ktab{1};                    // the k-mer jump table: 1 auto, 0 off
   std::atomic<int> jump_mode{7};               // bit 0: row table (R1), bit 1: row jump table (J), bit 2: three-step row table (R3)
   std::atomic<int> jump_pairs{-1};             // -1 auto (indexes of 2^30 rows and more, when 32 n bytes fit), 0 never, 1 whenever they fit
+  std::atomic<int> search_lanes{-1};           // -1 auto (pairs of lanes from k >= CUs x 512 patterns), 0 quads, 1 pairs of lanes where they can
   std::atomic<int> jump_chars{9};
   std::atomic<long long> tables_after{-1};     // patterns before a search builds tables; -1 auto
   // the BUDGET: device bytes all derived tables of this handle (k-mer, row, row jump, select) may hold together
@@ -65,6 +66,7 @@ struct TablePolicy {
   TablePolicy(const TablePolicy &o) { *this = o; }
   TablePolicy &operator=(const TablePolicy &o) {
     ktab.store(o.ktab.load()); jump_mode.store(o.jump_mode.load()); jump_pairs.store(o.jump_pairs.load());
+    search_lanes.store(o.search_lanes.load());
     jump_chars.store(o.jump_chars.load()); tables_after.store(o.tables_after.load());
     budget_bytes.store(o.budget_bytes.load()); budget_ppb.store(o.budget_ppb.load());
     return *this;

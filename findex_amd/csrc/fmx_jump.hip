@@ -169,6 +169,13 @@ int policy_set(TablePolicy &p, const char *key, const char *value, const char **
     else { *why = "jump_pairs must be auto, on or off"; return 2; }
     return 0;
   }
+  if (is("search_lanes")) {
+    if (val("auto")) p.search_lanes.store(-1);
+    else if (val("quads")) p.search_lanes.store(0);
+    else if (val("pairs")) p.search_lanes.store(1);
+    else { *why = "search_lanes must be auto, quads or pairs"; return 2; }
+    return 0;
+  }
   if (is("jump_chars")) {
     uint64_t v = 0;
     if (!parse_u64(value, &v) || v < 8 || v > 11) { *why = "jump_chars must be 8, 9, 10 or 11"; return 2; }
@@ -322,10 +329,9 @@ static hipError_t build_jump(const Index *h, hipStream_t st) {
   // handle's budget (table_room).
   // Pairs of entries (32 bytes per row: up to 2 jc steps per request, k_search4<.., JT = 2>) where the quad layout's index
   // is large enough for requests to be what binds (n >= 2^30) and twice the table fits beside everything else and inside the
-  // budget; "jump_pairs" = "auto" | "on" | "off" (per handle: fmx_index_config_set); FMX_JUMP_PAIRS=0|1 overrides it (tests)
+  // budget; "jump_pairs" = "auto" | "on" | "off" (per handle: fmx_index_config_set)
   const uint64_t room = table_room(h, 8ull << 30);
-  const char *pe = getenv("FMX_JUMP_PAIRS");
-  const int pcfg = pe ? (atoi(pe) != 0 ? 1 : 0) : h->policy.jump_pairs.load(std::memory_order_relaxed);
+  const int pcfg = h->policy.jump_pairs.load(std::memory_order_relaxed);
   const bool want_pairs = r3 && h->layout != kLayoutBytes && (pcfg < 0 ? h->n >= (1ull << 30) : pcfg != 0);
   const bool pairs = want_pairs && 2 * bytes <= room;
   if (pairs) bytes *= 2;

@@ -385,7 +385,7 @@ class HipFMSearcher:
         _lib.check(self._L.fmx_drop_tables(self._h, (4 if jump else 0) | (8 if frontier else 0) | (1 if ktab else 0)))
 
     def config_set(self, key, value):
-        """fmx_index_config_set: this handle's own table policy ("ktab", "jump", "jump_pairs", "jump_chars", "tables_after",
+        """fmx_index_config_set: this handle's own table policy ("ktab", "jump", "jump_pairs", "search_lanes", "jump_chars", "tables_after",
         "table_budget"); tables that exist stay until drop_tables."""
         _lib.check(self._L.fmx_index_config_set(self._h, key.encode(), str(value).encode()))
 

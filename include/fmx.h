@@ -62,7 +62,7 @@ typedef struct fmx_regex_batch fmx_regex_batch;   /* a set of compiled regexes m
 
 const char *fmx_last_error(void);
 int fmx_abi_version(void);
-/* Process-wide options.  The table keys ("ktab", "jump", "jump_pairs", "jump_chars", "tables_after", "table_budget") are the
+/* Process-wide options.  The table keys ("ktab", "jump", "jump_pairs", "search_lanes", "jump_chars", "tables_after", "table_budget") are the
  * DEFAULTS a handle copies when it is opened; fmx_index_config_set changes one handle's own copy afterwards, so two handles
  * in one process (one JVM) can differ.  key "layout": "auto" (default: one-hot bit-vectors, one 64-byte block per
  * rank query, when sigma*n/7 bytes fit in free HBM and n < 2^37; else BWT bytes + checkpoints, two
@@ -83,6 +83,10 @@ int fmx_abi_version(void);
  *     row it lands on, side by side in 32 bytes -- one memory request (a 64-byte sector either way) then serves up to
  *     2 x jump_chars steps.  32 n bytes; "auto" builds pairs for the one-hot layout when the index has 2^30 rows or more
  *     and 32 n bytes + 8 GiB are free ("on": whenever they are free);
+ *     Key "search_lanes": "auto" (default) / "quads" / "pairs", a test and diagnosis key: with a row jump table and the
+ *     three-step row table on the one-hot layout, a search may serve each pattern by a pair of lanes instead of four (32
+ *     patterns per wave instead of 16).  "auto" does so for batches of at least 512 patterns per compute unit (131 072 on
+ *     an MI355X), "quads" never, "pairs" whenever those tables are there.  Results are the same either way;
  *   - the three-step row table: the same with three characters, 8 n bytes -- built instead where the jump table does
  *     not fit; the one-row part of every pattern is then walked by one lane per pattern;
  *   - the row table: BWT'[r] and LF r in 8 bytes per row -- the regex frontier steps its one-row elements with it

@@ -1,5 +1,28 @@
 """Shared test helpers (CPU only, numpy)."""
 import numpy as np
+import pytest
+
+_table_keys = {}        # the table keys table_default has set for the running test, and their values
+
+
+@pytest.fixture
+def table_default():
+    """fmx_config_set for a table key ("jump_pairs", "search_lanes", ...): the default that handles opened afterwards copy.
+    Call it as table_default(key, value); every key it set is "auto" again after the test."""
+    import findex_amd
+
+    def set_key(key, value):
+        findex_amd.config_set(key, value)
+        _table_keys[key] = value
+    yield set_key
+    for key in list(_table_keys):
+        findex_amd.config_set(key, "auto")
+        del _table_keys[key]
+
+
+def table_key(key):
+    """The value table_default gave `key` in the running test ("auto" when it set none)."""
+    return _table_keys.get(key, "auto")
 
 
 def bwt_of_text(text: bytes):

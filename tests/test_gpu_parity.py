@@ -9,7 +9,8 @@ import pytest
 import findex_amd
 import oracle
 from oracle import retree as R
-from helpers import bwt_of_text, lf_walk_patterns, pack_patterns, synth_bwt
+from helpers import bwt_of_text, lf_walk_patterns, pack_patterns, synth_bwt, table_key
+from helpers import table_default  # noqa: F401  (a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -28,8 +29,8 @@ def pair_from_mem(bwt, eof, counts):
 
 def jump_row_bytes(layout="onehot"):
     """Bytes per row of the row jump table these small indexes get: 16, or 32 when pairs of entries are forced on
-    (FMX_JUMP_PAIRS=1; by default only indexes of 2^30 rows and more get pairs; never the bytes layout)."""
-    return 32 if (os.environ.get("FMX_JUMP_PAIRS") == "1" and layout != "bytes") else 16
+    ("jump_pairs" = "on"; by default only indexes of 2^30 rows and more get pairs; never the bytes layout)."""
+    return 32 if (table_key("jump_pairs") == "on" and layout != "bytes") else 16
 
 
 def check_occ(hip, orc, rng, k, symbols):
@@ -2374,6 +2375,7 @@ bwt, eof, counts = synth_bwt(3_000_000, 97, 120, 23)
 hip = findex_amd.HipFMSearcher.from_mem(bwt, eof, counts)
 if mode == "pairs":
     hip.config_set("jump_pairs", "on")
+    hip.config_set("search_lanes", "pairs")
 else:
     hip.config_set("jump", "rows3")
 hip.prepare(ktab=True, jump=True)
@@ -2432,8 +2434,7 @@ def test_last_rounds_drawn_by_ticket(layout, mode):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, FMX_TRACE="1", FMX_SEARCH_WGS="1", FMX_SEARCH_G2="1" if mode == "pairs" else "0")
-    env.pop("FMX_SEARCH_TICKETS", None)
+    env = dict(os.environ, FMX_TRACE="1", FMX_SEARCH_WGS="1")
     r = subprocess.run([sys.executable, "-c", _TICKET_SCRIPT, root, layout, mode], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
     import re
@@ -2444,11 +2445,10 @@ def test_last_rounds_drawn_by_ticket(layout, mode):
 
 
 @pytest.mark.parametrize("which", ["modes", "repeats", "walks"])
-def test_pairs_of_lanes_with_single_entries(which, monkeypatch):
+def test_pairs_of_lanes_with_single_entries(which, table_default):
     """The pair-of-lanes kernel over a row jump table of SINGLE entries (k_search4<.., JT = 1, .., G2>: an index under 2^30 rows,
     or one whose budget has no room for pairs of entries): forced onto the small shapes of the row-table tests."""
-    monkeypatch.delenv("FMX_JUMP_PAIRS", raising=False)
-    monkeypatch.setenv("FMX_SEARCH_G2", "1")
+    table_default("search_lanes", "pairs")
     if which == "modes":
         test_row_jump_table_on_and_off_agree("onehot")
     elif which == "repeats":
@@ -2458,15 +2458,15 @@ def test_pairs_of_lanes_with_single_entries(which, monkeypatch):
 
 
 @pytest.mark.parametrize("which", ["modes", "repeats", "spans", "walks", "ragged"])
-def test_pairs_of_lanes_search_kernel(which, monkeypatch):
+def test_pairs_of_lanes_search_kernel(which, table_default):
     """k_search4<.., G2> (round 5): a pattern served by a PAIR of lanes, 32 patterns per wave, the dictionary's blocks
     fetched as two 32-byte halves, pattern spans of up to 2 KiB staged -- by default only for batches that give every wave
-    several batches (the C3 tests at full size run it), forced here on the small ones (FMX_SEARCH_G2=1, with the pair table
-    it needs: FMX_JUMP_PAIRS=1): the row-table tests in every mode and entry width, the repetitive texts (intervals of two
+    several batches (the C3 tests at full size run it), forced here on the small ones ("search_lanes" = "pairs", with the pair
+    table: "jump_pairs" = "on"): the row-table tests in every mode and entry width, the repetitive texts (intervals of two
     rows: lane t looks up row sp + t), the staged spans' edges, the parked walks, and ragged lengths 0 .. 70 around the
     2 KiB span limit -- all against the oracle, executed steps included."""
-    monkeypatch.setenv("FMX_JUMP_PAIRS", "1")
-    monkeypatch.setenv("FMX_SEARCH_G2", "1")
+    table_default("jump_pairs", "on")
+    table_default("search_lanes", "pairs")
     if which == "modes":
         test_row_jump_table_on_and_off_agree("onehot")
     elif which == "repeats":
@@ -2495,15 +2495,15 @@ def test_pairs_of_lanes_search_kernel(which, monkeypatch):
 
 
 @pytest.mark.parametrize("kernel", ["quads", "pairs"])
-def test_misses_as_none(kernel, monkeypatch):
+def test_misses_as_none(kernel, table_default):
     """FMX_SEARCH_MISS_NONE (fmx.h): a pattern that does not occur may come back as (0, 0) -- SuffixAlgo.search returns None for
     it either way (findex.scala:30) -- so the kernels with a row jump table park nothing to walk for it.  Hits bit-equal to the
     oracle's, every miss sp >= ep, and the count of the reference loop's steps (rank_queries) what the oracle counts, misses
     included; through the host form, the device form and the 8-byte form, with ragged lengths and a third of the patterns
     mutated anywhere; by quads and by pairs of lanes.  At least some misses must really have been cut short (0, 0)."""
     torch = _torch()
-    monkeypatch.setenv("FMX_JUMP_PAIRS", "1")
-    monkeypatch.setenv("FMX_SEARCH_G2", "1" if kernel == "pairs" else "0")
+    table_default("jump_pairs", "on")
+    table_default("search_lanes", kernel)
     bwt, eof, counts = synth_bwt(600_000, 97, 120, 31)
     hip, orc = pair_from_mem(bwt, eof, counts)
     hip.prepare(ktab=True, jump=True)
@@ -2597,13 +2597,13 @@ def test_result_groups_of_every_size_are_ordered():
 
 
 @pytest.mark.parametrize("which", ["modes", "repeats", "spans", "walks", "census"])
-def test_row_jump_table_as_pairs_of_entries(which, monkeypatch):
+def test_row_jump_table_as_pairs_of_entries(which, table_default):
     """The row jump table as pairs J[r] | J[LF^jc r] (32 bytes per row, k_search4<.., JT = 2>: up to 2 x jump_chars steps
     per request; by default only for indexes of 2^30 rows and more -- the C3 tests at full size run it -- forced here on the
     small ones): the row-table tests in every mode and entry width, the repetitive texts (intervals of a few rows: the
     first entries only), the staged spans' edges, the parked walks (a pattern that agrees with a pair's first entry and
     not with its second jumps nine steps and parks behind them) and the residency census, all against the oracle."""
-    monkeypatch.setenv("FMX_JUMP_PAIRS", "1")
+    table_default("jump_pairs", "on")
     if which == "modes":
         test_row_jump_table_on_and_off_agree("onehot")
     elif which == "repeats":
