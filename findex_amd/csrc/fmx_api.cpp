@@ -274,6 +274,8 @@ static void destroy(Index *h) {
   if (h->d_ktab) (void)hipFree(h->d_ktab);
   if (h->d_kt_dense) (void)hipFree(h->d_kt_dense);
   if (h->d_kt_levels) (void)hipFree(h->d_kt_levels);
+  if (h->d_kt_ext) (void)hipFree(h->d_kt_ext);
+  if (h->d_kt_ovf) (void)hipFree(h->d_kt_ovf);
   if (h->d_jump) (void)hipFree(h->d_jump);
   if (h->d_row1) (void)hipFree(h->d_row1);
   if (h->d_row3) (void)hipFree(h->d_row3);

@@ -39,6 +39,10 @@ struct KTab {
   uint32_t k = 0, sigma = 0;
   // the regex frontier's row table (fmx_jump.hip, row1_get): per row BWT'[r] << 40 | LF r, or nullptr
   const unsigned long long *row1 = nullptr;
+  // level ext_k + 1 (fmx_ktab.hip, build_kext; nullptr: none): per ext_k-mer Z a 32-byte entry -- Z's insertion point, its
+  // row count and the (ext_k + 1)-th characters of its rows -- and the overflow lists of the entries that hold more than 26
+  const uint4 *ext = nullptr, *ovf = nullptr;
+  uint32_t ext_k = 0;
 };
 
 // Host-resident rank dictionary of a (block-sized) index, for ONE dependent chain of rank queries (fmx_hostrank.cpp):
@@ -54,6 +58,7 @@ struct HostRank {
 // open; fmx_index_config_set changes one handle's own copy afterwards (a table that exists stays until fmx_drop_tables).
 struct TablePolicy {
   std::atomic<int> ktab{1};                    // the k-mer jump table: 1 auto, 0 off
+  std::atomic<int> ktab_ext{-1};               // its level K+1 (fmx_ktab.hip): -1 auto (where the row jump table is built as pairs), 0 off, 1 whenever it fits
   std::atomic<int> jump_mode{7};               // bit 0: row table (R1), bit 1: row jump table (J), bit 2: three-step row table (R3)
   std::atomic<int> jump_pairs{-1};             // -1 auto (indexes of 2^30 rows and more, when 32 n bytes fit), 0 never, 1 whenever they fit
   std::atomic<int> search_lanes{-1};           // -1 auto (pairs of lanes from k >= CUs x 512 patterns), 0 quads, 1 pairs of lanes where they can
@@ -65,7 +70,7 @@ struct TablePolicy {
   TablePolicy() = default;
   TablePolicy(const TablePolicy &o) { *this = o; }
   TablePolicy &operator=(const TablePolicy &o) {
-    ktab.store(o.ktab.load()); jump_mode.store(o.jump_mode.load()); jump_pairs.store(o.jump_pairs.load());
+    ktab.store(o.ktab.load()); ktab_ext.store(o.ktab_ext.load()); jump_mode.store(o.jump_mode.load()); jump_pairs.store(o.jump_pairs.load());
     search_lanes.store(o.search_lanes.load());
     jump_chars.store(o.jump_chars.load()); tables_after.store(o.tables_after.load());
     budget_bytes.store(o.budget_bytes.load()); budget_ppb.store(o.budget_ppb.load());
@@ -111,7 +116,8 @@ struct Index {
   mutable bool kt_ready = false;
   mutable KTab kt;
   mutable void *d_ktab = nullptr, *d_kt_dense = nullptr, *d_kt_levels = nullptr;
-  mutable uint64_t kt_bytes = 0;
+  mutable void *d_kt_ext = nullptr, *d_kt_ovf = nullptr;      // level K+1 and its overflow lists (KTab::ext, ::ovf)
+  mutable uint64_t kt_bytes = 0;                              // (all of the above)
   // row jump table (fmx_jump.hip), built at the first literal search
   mutable std::mutex jt_mu;
   mutable bool jt_ready = false;

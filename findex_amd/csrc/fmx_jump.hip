@@ -131,7 +131,12 @@ __global__ __launch_bounds__(kJThreads) void k_row3_init(DevIndex ix, unsigned l
 
 // ---- the table policy (fmx_host.h, TablePolicy): process defaults, copied by a handle at open
 TablePolicy &default_policy() {
-  static TablePolicy p;
+  static TablePolicy p = [] {
+    TablePolicy d;
+    // FMX_KTAB_EXT=0 / 1: the default of "ktab_ext" for a process that cannot call fmx_config_set (A/B runs of a benchmark)
+    if (const char *e = getenv("FMX_KTAB_EXT")) d.ktab_ext.store(atoi(e) ? 1 : 0);
+    return d;
+  }();
   return p;
 }
 
@@ -151,6 +156,13 @@ int policy_set(TablePolicy &p, const char *key, const char *value, const char **
     if (val("auto")) p.ktab.store(1);
     else if (val("off")) p.ktab.store(0);
     else { *why = "ktab must be auto or off"; return 2; }
+    return 0;
+  }
+  if (is("ktab_ext")) {
+    if (val("auto")) p.ktab_ext.store(-1);
+    else if (val("on")) p.ktab_ext.store(1);
+    else if (val("off")) p.ktab_ext.store(0);
+    else { *why = "ktab_ext must be auto, on or off"; return 2; }
     return 0;
   }
   if (is("jump")) {
@@ -391,7 +403,9 @@ int drop_tables(Index *h, unsigned what) {
     if (h->d_ktab) (void)hipFree(h->d_ktab);
     if (h->d_kt_dense) (void)hipFree(h->d_kt_dense);
     if (h->d_kt_levels) (void)hipFree(h->d_kt_levels);
-    h->d_ktab = h->d_kt_dense = h->d_kt_levels = nullptr;
+    if (h->d_kt_ext) (void)hipFree(h->d_kt_ext);
+    if (h->d_kt_ovf) (void)hipFree(h->d_kt_ovf);
+    h->d_ktab = h->d_kt_dense = h->d_kt_levels = h->d_kt_ext = h->d_kt_ovf = nullptr;
     tables_account(h, -(int64_t)h->kt_bytes);
     h->kt_bytes = 0;
     h->kt = KTab{};

@@ -25,11 +25,12 @@ namespace fmx {
 
 constexpr int kKtThreads = 256;
 
-// level j+1 from level j: entry (code, c) = step(T_j[code], symbol c); one lane group per new entry
+// level j+1 from level j: entry (code, c) = step(T_j[code], symbol c); one lane group per new entry.  full != 0 (level K+1's
+// insertion points, build_kext): every step is taken, also on an empty interval -- (sp, ep) = the images of 0 and n.
 template <bool WIDE, uint32_t LAYOUT>
 __global__ __launch_bounds__(kKtThreads) void k_ktab_level(DevIndex ix, const uint4 *__restrict__ prev, uint4 *__restrict__ next,
                                                             uint64_t n_prev, uint32_t sigma, uint32_t level,
-                                                            const uint8_t *__restrict__ sym_of /* [sigma] */) {
+                                                            const uint8_t *__restrict__ sym_of /* [sigma] */, uint32_t full) {
   __shared__ uint64_t s_cf[256];
   __shared__ uint16_t s_slot[256];
   for (int c = threadIdx.x; c < 256; c += blockDim.x) { s_cf[c] = ix.cf[c]; s_slot[c] = ix.slot[c]; }
@@ -50,13 +51,191 @@ __global__ __launch_bounds__(kKtThreads) void k_ktab_level(DevIndex ix, const ui
       steps = p.y >> 24;
       ep = ((uint64_t)p.w << 32) | p.z;
     }
-    if (sp < ep) {                      // still alive: one more step of the reference's loop
+    if (sp < ep || full) {              // still alive: one more step of the reference's loop
       backward_step<WIDE, LAYOUT>(ix, c, s_slot[c], s_cf[c], lc, sp, ep);
       steps++;
     }
     if (lc.t == 0)
       next[e] = make_uint4((uint32_t)sp, (uint32_t)(sp >> 32) | (steps << 24), (uint32_t)ep, (uint32_t)(ep >> 32));
   }
+}
+
+// ---- level K+1 (build_kext).  A search's first K+1 steps consume Y = its last K+1 characters; the rows whose suffix starts
+// with Y are the sub-range of Z's interval I_Z (Z = the first K characters of Y, in text order) whose (K+1)-th character is
+// y (Y's last, the search's first): the rows are sorted, so those characters do not decrease across I_Z, and
+//     Y's interval = [sp_Z + #(characters < y), sp_Z + #(characters <= y)).
+// E[code of Z] holds that list (the same code as T's: Z's last character is the most significant digit), 32 bytes:
+//   bytes 0..4  sp_Z, the images of row 0 under Z's steps -- Z's insertion point, defined whether Z occurs or not;
+//   byte 5      |I_Z| when it is at most kExtCap, else 0xFF: the list is in the overflow array;
+//   bytes 6..31 the characters, the row of suffix sp_Z first; unused bytes 0xFF (never below a character, and counted
+//               as "<= y" only when y = 255: then the count is |I_Z|);
+//   overflow:   bytes 6..10 the list's offset in the overflow array in 16-byte units, bytes 11..15 |I_Z|; the list is
+//               padded with 0xFF to a multiple of 16 bytes.
+// The (K+1)-th character of the suffix of row q is F[r], r the row K steps of LF behind q (q = LF^K r): the bucket of r.
+// An index where some list is longer than kExtMaxList (a text: its common words' k-mers hold millions of rows) gets no level
+// K+1: a lookup counts its list 32 bytes per round trip, so the lists it may meet are held to two rounds.
+constexpr uint32_t kExtCap = 26, kExtMaxList = 64;
+
+// E's headers: the last of K full steps (k_ktab_level, full = 1, gave the levels before it); an overflowing entry draws its
+// list's place from units[0] (16-byte units), units[1] = the longest list
+template <bool WIDE, uint32_t LAYOUT>
+__global__ __launch_bounds__(kKtThreads) void k_kext_head(DevIndex ix, const uint4 *__restrict__ prev, uint4 *__restrict__ ext,
+                                                           uint64_t n_prev, uint32_t sigma, const uint8_t *__restrict__ sym_of,
+                                                           unsigned long long *__restrict__ units) {
+  __shared__ uint64_t s_cf[256];
+  __shared__ uint16_t s_slot[256];
+  for (int c = threadIdx.x; c < 256; c += blockDim.x) { s_cf[c] = ix.cf[c]; s_slot[c] = ix.slot[c]; }
+  __syncthreads();
+  constexpr int G = Lay<LAYOUT>::G;
+  const LaneConst lc = lane_const<G>();
+  const uint64_t total = n_prev * sigma;
+  const uint64_t ngroups = (uint64_t)gridDim.x * (kKtThreads / G);
+  for (uint64_t e = ((uint64_t)blockIdx.x * kKtThreads + threadIdx.x) / G; e < total; e += ngroups) {
+    const uint32_t c = sym_of[e % sigma];
+    uint64_t sp = 0, ep = ix.n;
+    if (prev) {
+      const uint4 p = prev[e / sigma];
+      sp = (((uint64_t)p.y << 32) | p.x) & ((1ull << 56) - 1);
+      ep = ((uint64_t)p.w << 32) | p.z;
+    }
+    backward_step<WIDE, LAYOUT>(ix, c, s_slot[c], s_cf[c], lc, sp, ep);
+    if (lc.t == 0) {
+      const uint64_t cnt = ep - sp;
+      uint4 lo = make_uint4((uint32_t)sp, ((uint32_t)(sp >> 32) & 0xFFu) | ((uint32_t)cnt << 8) | 0xFFFF0000u, ~0u, ~0u);
+      if (cnt > kExtCap) {
+        const uint64_t off = atomicAdd(units, (unsigned long long)((cnt + 15) / 16));
+        atomicMax(units + 1, (unsigned long long)cnt);
+        lo = make_uint4((uint32_t)sp, ((uint32_t)(sp >> 32) & 0xFFu) | 0xFF00u | ((uint32_t)off << 16),
+                        ((uint32_t)(off >> 16) & 0xFFFFFFu) | ((uint32_t)cnt << 24), (uint32_t)(cnt >> 8));
+      }
+      ext[2 * e] = lo;
+      ext[2 * e + 1] = make_uint4(~0u, ~0u, ~0u, ~0u);
+    }
+  }
+}
+
+// E's characters: per row r the K steps of LF from it -- Z's code and q = LF^K r -- and F[r] into Z's list at q - sp_Z.
+// Rows whose K characters are not all in the table's alphabet (the end-of-text symbol, 0) belong to no entry.
+template <bool WIDE, uint32_t LAYOUT>
+__global__ __launch_bounds__(kKtThreads) void k_kext_fill(DevIndex ix, const uint4 *__restrict__ ext, uint8_t *__restrict__ extb,
+                                                           uint8_t *__restrict__ ovf, const uint8_t *__restrict__ dense,
+                                                           uint32_t sigma, uint32_t K) {
+  __shared__ uint64_t s_cf[256];
+  __shared__ uint16_t s_slot[256];
+  __shared__ uint8_t s_dense[256];
+  for (int c = threadIdx.x; c < 256; c += blockDim.x) { s_cf[c] = ix.cf[c]; s_slot[c] = ix.slot[c]; s_dense[c] = dense[c]; }
+  __syncthreads();
+  constexpr int G = Lay<LAYOUT>::G;
+  const LaneConst lc = lane_const<G>();
+  const uint64_t ngroups = (uint64_t)gridDim.x * (kKtThreads / G);
+  for (uint64_t r0 = ((uint64_t)blockIdx.x * kKtThreads + threadIdx.x) / G; r0 < ix.n; r0 += ngroups) {
+    uint64_t r = r0, code = 0;
+    bool ok = true;
+    for (uint32_t s = 0; s < K && ok; s++) {      // (group-uniform: every lane of the group walks the same row)
+      const uint32_t c = r == ix.eof ? 0u : ix.bwt[r];
+      const uint32_t d = s_dense[c];
+      ok = d != 0xFFu;
+      if (ok) {
+        code = code * sigma + d;
+        r = s_cf[c] + rank_excl<WIDE, LAYOUT>(ix, c, s_slot[c], r, lc);
+      }
+    }
+    if (!ok || lc.t != 0) continue;
+    uint32_t f = 0;                                // F[r0]: the largest symbol whose bucket starts at or below r0 (C[] does not decrease)
+    for (uint32_t step = 128; step; step >>= 1)
+      if (s_cf[f + step] <= r0) f += step;
+    const uint4 hd = ext[2 * code];
+    const uint64_t sp = hd.x | ((uint64_t)(hd.y & 0xFFu) << 32);
+    const uint64_t slot = r - sp;
+    if (((hd.y >> 8) & 0xFFu) != 0xFFu) {
+      extb[32 * code + 6 + slot] = (uint8_t)f;
+    } else {
+      const uint64_t off = (hd.y >> 16) | ((uint64_t)(hd.z & 0xFFFFFFu) << 16);
+      ovf[16 * off + slot] = (uint8_t)f;
+    }
+  }
+}
+
+// Level K+1 of the table whose K levels are built, for KE = the K a search uses (a multiple of four, fmx_search.hip plan_of).
+// It serves the kernels with a row jump table of pairs (k_search4<.., KX>) and is built where they will run ("auto": a
+// one-hot index for which "jump_pairs" asks for pairs, when the 32-byte entries, the 8 n bytes of the three-step table and
+// the 32 n bytes of the pairs all fit beside each other and the margins -- it never takes the pairs' place), or whenever it
+// fits ("on").  Leaves h->kt.ext null when it is not built; a failure is no error (the kernels without the level serve).
+static void build_kext(const Index *h, hipStream_t st, uint32_t KE, const uint8_t *d_sym, const uint8_t *d_dense) {
+  const int mode = h->policy.ktab_ext.load(std::memory_order_relaxed);
+  if (mode == 0 || KE == 0 || h->layout != kLayoutOneHot || h->block_mode || h->n > (1ull << 32)) return;      // (the kernels that use it are not WIDE)
+  const uint32_t sigma = h->nslots;
+  uint64_t codes = 1;
+  for (uint32_t j = 0; j < KE; j++) codes *= sigma;
+  const uint64_t ext_bytes = codes * 32, ovf_reserve = std::max<uint64_t>(ext_bytes / 32, 64ull << 20);
+  if (ext_bytes > (16ull << 30)) return;
+  if (mode < 0) {
+    const int pcfg = h->policy.jump_pairs.load(std::memory_order_relaxed);
+    const bool pairs = (pcfg < 0 ? h->n >= (1ull << 30) : pcfg != 0) && (h->policy.jump_mode.load(std::memory_order_relaxed) & 6) == 6;
+    if (!pairs || ext_bytes + ovf_reserve + 40 * h->n + (8ull << 30) > table_room(h, 0)) return;
+  } else if (ext_bytes + ovf_reserve > table_room(h, 1ull << 30)) {
+    return;
+  }
+  const uint64_t per_wg = kKtThreads / 4;
+  auto grid_for = [&](uint64_t items) { return (int)std::min<uint64_t>((items + per_wg - 1) / per_wg, (uint64_t)h->cu_count * 8); };
+  uint64_t tmp_entries = 0;
+  for (uint64_t j = 1, c = sigma; j < KE; j++, c *= sigma) tmp_entries += c;      // levels 1 .. KE-1, every step taken
+  void *d_ext = nullptr, *d_ovf = nullptr, *d_tmp = nullptr, *d_units = nullptr;
+  hipError_t e = table_malloc(h, &d_ext, ext_bytes);
+  if (e == hipSuccess) e = hipMalloc(&d_tmp, std::max<uint64_t>(tmp_entries, 1) * 16 + 256);
+  if (e == hipSuccess) { d_units = static_cast<uint8_t *>(d_tmp) + std::max<uint64_t>(tmp_entries, 1) * 16; e = hipMemsetAsync(d_units, 0, 16, st); }
+  uint64_t off = 0, n_prev = 1;
+  const uint4 *prev = nullptr;
+  for (uint32_t lv = 0; lv + 1 < KE && e == hipSuccess; lv++) {
+    uint4 *next = static_cast<uint4 *>(d_tmp) + off;
+    const uint64_t n_next = n_prev * sigma;
+    const int grid = grid_for(n_next);
+#define CALL(W, L) k_ktab_level<W, L><<<grid, kKtThreads, 0, st>>>(h->dev, prev, next, n_prev, sigma, lv, d_sym, 1u)
+    FMX_LAYOUT_DISPATCH(h, CALL);
+#undef CALL
+    e = hipGetLastError();
+    prev = next;
+    off += n_next;
+    n_prev = n_next;
+  }
+  if (e == hipSuccess) {
+    const int grid = grid_for(codes);
+#define CALL(W, L) k_kext_head<W, L><<<grid, kKtThreads, 0, st>>>(h->dev, prev, static_cast<uint4 *>(d_ext), n_prev, sigma, d_sym, static_cast<unsigned long long *>(d_units))
+    FMX_LAYOUT_DISPATCH(h, CALL);
+#undef CALL
+    e = hipGetLastError();
+  }
+  unsigned long long units[2] = {0, 0};
+  if (e == hipSuccess) e = hipMemcpyAsync(units, d_units, 16, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess && units[1] > kExtMaxList) e = hipErrorNotSupported;      // (not an error: no level)
+  const uint64_t ovf_bytes = std::max<uint64_t>(units[0], 1) * 16;
+  if (e == hipSuccess && ovf_bytes > table_room(h, mode < 0 ? 40 * h->n + (8ull << 30) : (1ull << 30))) e = hipErrorOutOfMemory;      // (a skewed text)
+  if (e == hipSuccess) e = table_malloc(h, &d_ovf, ovf_bytes);
+  if (e == hipSuccess) e = hipMemsetAsync(d_ovf, 0xFF, ovf_bytes, st);
+  if (e == hipSuccess) {
+    const int grid = grid_for(h->n);
+#define CALL(W, L) k_kext_fill<W, L><<<grid, kKtThreads, 0, st>>>(h->dev, static_cast<const uint4 *>(d_ext), static_cast<uint8_t *>(d_ext), static_cast<uint8_t *>(d_ovf), d_dense, sigma, KE)
+    FMX_LAYOUT_DISPATCH(h, CALL);
+#undef CALL
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (d_tmp) (void)hipFree(d_tmp);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (d_ext) (void)hipFree(d_ext);
+    if (d_ovf) (void)hipFree(d_ovf);
+    return;
+  }
+  h->d_kt_ext = d_ext;
+  h->d_kt_ovf = d_ovf;
+  h->kt.ext = static_cast<const uint4 *>(d_ext);
+  h->kt.ovf = static_cast<const uint4 *>(d_ovf);
+  h->kt.ext_k = KE;
+  h->kt_bytes += ext_bytes + ovf_bytes;
+  note_table_build(h, ext_bytes + ovf_bytes + tmp_entries * 16);
+  tables_account(h, (int64_t)(ext_bytes + ovf_bytes));
 }
 
 // Chooses K, allocates and fills the levels.  Called under h->kt_mu by ktab_get.
@@ -104,7 +283,7 @@ static hipError_t build_ktab(const Index *h, hipStream_t st) {
     const uint64_t n_next = n_prev * sigma;
     const uint64_t per_wg = kKtThreads / (h->layout == kLayoutBytes ? 8 : 4);
     const int grid = (int)std::min<uint64_t>((n_next + per_wg - 1) / per_wg, (uint64_t)h->cu_count * 8);
-#define CALL(W, L) k_ktab_level<W, L><<<grid, kKtThreads, 0, st>>>(h->dev, prev, next, n_prev, sigma, lv, (const uint8_t *)d_sym)
+#define CALL(W, L) k_ktab_level<W, L><<<grid, kKtThreads, 0, st>>>(h->dev, prev, next, n_prev, sigma, lv, (const uint8_t *)d_sym, 0u)
     FMX_LAYOUT_DISPATCH(h, CALL);
 #undef CALL
     e = hipGetLastError();
@@ -117,8 +296,8 @@ static hipError_t build_ktab(const Index *h, hipStream_t st) {
   if (e == hipSuccess) e = hipMalloc(&d_levels, sizeof h->kt.level);
   if (e == hipSuccess) e = hipMemcpyAsync(d_levels, h->kt.level, sizeof h->kt.level, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);      // `dense` / `sym_of` go out of scope
-  if (d_sym) (void)hipFree(d_sym);
   if (e != hipSuccess) {
+    if (d_sym) (void)hipFree(d_sym);
     if (d_all) (void)hipFree(d_all);
     if (d_dense) (void)hipFree(d_dense);
     if (d_levels) (void)hipFree(d_levels);
@@ -135,6 +314,9 @@ static hipError_t build_ktab(const Index *h, hipStream_t st) {
   h->kt_bytes = all * 16 + 256;
   note_table_build(h, h->kt_bytes);
   tables_account(h, (int64_t)h->kt_bytes);
+  // level K+1 over the K-mers of the level a search uses (plan_of: 12, 8 or 4)
+  build_kext(h, st, k >= 12 ? 12u : k >= 8 ? 8u : k >= 4 ? 4u : 0u, static_cast<const uint8_t *>(d_sym), static_cast<const uint8_t *>(d_dense));
+  (void)hipFree(d_sym);      // (build_kext has synchronised the stream)
   return hipSuccess;
 }
 

@@ -128,9 +128,9 @@ static hipError_t search_tables(const Index *h, uint32_t k, hipStream_t st, bool
 struct SearchPlan {
   bool wide;
   uint32_t layout, kt, jt, rw;
-  bool r3t, g2;
+  bool r3t, g2, kx;
   bool operator==(const SearchPlan &o) const {
-    return wide == o.wide && layout == o.layout && kt == o.kt && jt == o.jt && rw == o.rw && r3t == o.r3t && g2 == o.g2;
+    return wide == o.wide && layout == o.layout && kt == o.kt && jt == o.jt && rw == o.rw && r3t == o.r3t && g2 == o.g2 && kx == o.kx;
   }
 };
 
@@ -140,13 +140,16 @@ struct SearchPlan {
 // the three-step row table, or the regex frontier's one-step row table where the handle has that one already (C5: 49 -> 75 G
 // rank queries/s with R1).  g2: a pair of lanes per pattern instead of a quad (only where can_pair_lanes).
 static SearchPlan plan_of(const Index *h, const SearchTables &t, bool g2) {
-  SearchPlan p{h->layout == kLayoutBytes || h->n > (1ull << 32), h->layout, 0u, 0u, 0u, false, false};      // (FMX_LAYOUT_DISPATCH)
+  SearchPlan p{h->layout == kLayoutBytes || h->n > (1ull << 32), h->layout, 0u, 0u, 0u, false, false, false};      // (FMX_LAYOUT_DISPATCH)
   // the search uses the k-mer table's levels in steps of four characters (all levels are kept: fmx_ktab.hip)
   p.kt = t.kt.k >= 12 ? 12u : t.kt.k >= 8 ? 8u : t.kt.k >= 4 ? 4u : 0u;
   if (t.jt) {
     p.jt = h->jump_pairs ? 2u : 1u;      // (pairs are built from the three-step table: it is there)
     p.r3t = t.r3 != nullptr;
     p.g2 = g2;
+    // level KT + 1 of the k-mer table (fmx_ktab.hip, build_kext) serves the kernels with pairs of row jump entries; "ktab_ext" =
+    // "off" on the handle switches it off for its searches (the level stays until fmx_drop_tables)
+    p.kx = t.kt.ext && t.kt.ext_k == p.kt && p.jt == 2u && p.r3t && !p.wide && h->policy.ktab_ext.load(std::memory_order_relaxed) != 0;
   } else {
     p.rw = t.r3 ? 3u : t.r1 ? 1u : 0u;
   }
@@ -179,9 +182,9 @@ struct SearchForm {
 #define FMX_SEARCHLOG_FN_(...)
 #endif
 };
-#define FMX_FORM_(W, L, KT, JT, RW, R3T, G2)                                                                    \
-  {{W, L, KT, JT, RW, R3T, G2}, &search4_launch<W, L, KT, JT, RW, R3T, G2>, &search4_occupancy<W, L, KT, JT, RW, R3T, G2> \
-   FMX_SEARCHLOG_FN_(W, L, KT, JT, RW, R3T, G2)},
+#define FMX_FORM_(W, L, KT, JT, RW, R3T, G2, KX)                                                                            \
+  {{W, L, KT, JT, RW, R3T, G2, KX}, &search4_launch<W, L, KT, JT, RW, R3T, G2, KX>, &search4_occupancy<W, L, KT, JT, RW, R3T, G2, KX> \
+   FMX_SEARCHLOG_FN_(W, L, KT, JT, RW, R3T, G2, KX)},
 static const SearchForm kForms[] = {FMX_SEARCH4_LIST(FMX_FORM_)};
 #undef FMX_FORM_
 #undef FMX_SEARCHLOG_FN_
@@ -199,7 +202,7 @@ static std::atomic<const SearchForm *> g_last_form{nullptr};
 static const SearchForm *find_form(const SearchPlan &p) {
   for (const SearchForm &f : kForms)
     if (f.plan == p) return &f;
-  fprintf(stderr, "[fmx] no k_search4<%d,%u,%u,%u,%u,%d,%d> in FMX_SEARCH4_LIST\n", (int)p.wide, p.layout, p.kt, p.jt, p.rw, (int)p.r3t, (int)p.g2);
+  fprintf(stderr, "[fmx] no k_search4<%d,%u,%u,%u,%u,%d,%d,%d> in FMX_SEARCH4_LIST\n", (int)p.wide, p.layout, p.kt, p.jt, p.rw, (int)p.r3t, (int)p.g2, (int)p.kx);
   return nullptr;
 }
 
@@ -222,6 +225,8 @@ static Search4Args form_args(const Index *h, const SearchPlan &p, const SearchTa
   a.ktab = p.kt ? t.kt.level[p.kt - 1] : nullptr;
   a.kdense = t.kt.dense;
   a.ksigma = t.kt.sigma;
+  a.kext = p.kx ? t.kt.ext : nullptr;
+  a.kovf = p.kx ? t.kt.ovf : nullptr;
   a.jtab = t.jt;
   a.jc = h->jump_chars;
   a.r3tab = p.rw == 1u ? t.r1 : (p.r3t || p.rw == 3u) ? t.r3 : nullptr;      // (the one-step table is passed in the same argument)
@@ -256,8 +261,8 @@ static hipError_t calibrate_form(const Index *h, const SearchPlan &p, const Sear
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) return e;
       got = census_read(h, grid, api, st);
-      if (knobs().trace) fprintf(stderr, "[fmx] k_search4<%d,%u,%u,%d,%u,%d,%d> census: %d of the %d workgroups per CU the occupancy query allows were resident\n",
-                                 (int)p.wide, p.layout, p.kt, (int)p.jt, p.rw, (int)p.r3t, (int)p.g2, got, api);
+      if (knobs().trace) fprintf(stderr, "[fmx] k_search4<%d,%u,%u,%d,%u,%d,%d,%d> census: %d of the %d workgroups per CU the occupancy query allows were resident\n",
+                                 (int)p.wide, p.layout, p.kt, (int)p.jt, p.rw, (int)p.r3t, (int)p.g2, (int)p.kx, got, api);
       if (got && got == last) rs.admitted.store(got);
       last = got;
     }
@@ -288,8 +293,8 @@ static hipError_t launch_form(const Index *h, const SearchPlan &p, const SearchT
   if (knobs().trace) {      // (what the kernel will make of it: k_search4, "The last rounds are DRAWN")
     const uint64_t Pw = 64u / G, nbatch = ((uint64_t)k + Pw - 1) / Pw, nw = (uint64_t)grid * (kSThreads / 64), rounds = nbatch / nw;
     const bool pooled = (p.g2 || p.rw != 0u) && area && rounds >= kPoolRounds + 2u;
-    fprintf(stderr, "[fmx] k_search4<%d,%u,%u,%d,%u,%d,%d>: %llu batches over %llu waves, the last %llu drawn from ticket area %u\n", (int)p.wide, p.layout, p.kt,
-            (int)p.jt, p.rw, (int)p.r3t, (int)p.g2, (unsigned long long)nbatch, (unsigned long long)nw,
+    fprintf(stderr, "[fmx] k_search4<%d,%u,%u,%d,%u,%d,%d,%d>: %llu batches over %llu waves, the last %llu drawn from ticket area %u\n", (int)p.wide, p.layout, p.kt,
+            (int)p.jt, p.rw, (int)p.r3t, (int)p.g2, (int)p.kx, (unsigned long long)nbatch, (unsigned long long)nw,
             (unsigned long long)(pooled ? nbatch - (rounds - kPoolRounds) * nw : 0), pooled ? area : 0u);
   }
   Search4Args a = form_args(h, p, t);

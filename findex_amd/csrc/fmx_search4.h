@@ -110,15 +110,21 @@ static __device__ unsigned long long g_searchlog[1u << 15][4];      // (each uni
 #ifndef FMX_SEARCH_WAVES_G2
 #define FMX_SEARCH_WAVES_G2 5
 #endif
-template <bool WIDE, uint32_t LAYOUT, uint32_t KT, uint32_t JT, uint32_t RW, bool R3T, bool G2 = false>
+// KX (with KT and a row jump table of pairs): the k-mer table's level KT + 1 (fmx_ktab.hip, build_kext) -- a pattern's first
+// KT + 1 steps are ONE 32-byte lookup, the entry of the KT characters in front of its last one: that entry's insertion point
+// plus the count of its rows' next characters below (up to) the pattern's last.  What was a k-mer lookup and a rank step
+// (two dependent round trips per batch, the second with two blocks when sp and ep straddle one) is one.
+template <bool WIDE, uint32_t LAYOUT, uint32_t KT, uint32_t JT, uint32_t RW, bool R3T, bool G2 = false, bool KX = false>
 __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? FMX_SEARCH_WAVES_G2 : FMX_SEARCH_WAVES, 8))) void k_search4(DevIndex ix, const uint4 *__restrict__ ktab, const uint8_t *__restrict__ kdense,
-                                                        uint32_t ksigma, const uint4 *__restrict__ jtab, const uint32_t jc,
+                                                        uint32_t ksigma, const uint4 *__restrict__ kext, const uint4 *__restrict__ kovf,
+                                                        const uint4 *__restrict__ jtab, const uint32_t jc,
                                                         const unsigned long long *__restrict__ r3tab, const uint8_t *__restrict__ pat,
                                                         const PatOff po,
                                                         uint64_t *__restrict__ sp_out, uint64_t *__restrict__ ep_out,
                                                         uint32_t k, unsigned long long *__restrict__ counters, const uint64_t pk_cap,
                                                         const uint32_t spin) {
   static_assert(!G2 || LAYOUT == kLayoutOneHot, "pairs of lanes serve the one-hot layout only");
+  static_assert(!KX || (KT != 0 && JT == 2u && RW == 0u && LAYOUT == kLayoutOneHot), "level KT + 1 serves the kernels with pairs of row jump entries");
   constexpr int G = G2 ? 2 : Lay<LAYOUT>::G;     // lanes per pattern
   constexpr uint32_t P = 64 / G;                 // patterns per wave
   constexpr uint32_t RG = G2 ? 4u : (uint32_t)G; // rows of an interval a group can look up in the row tables at once (a pair's lanes take two rows each)
@@ -357,7 +363,8 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
       uint64_t wsp = actw ? s_park_row[wave_in_wg][slot] : 0ull;
       uint32_t wj = (uint32_t)(wsp >> 56);                       // steps that are known to succeed (the lookup that parked it saw them)
       const bool wnone = wj == 0xFFu;                            // FMX_SEARCH_MISS_NONE: parked as None -- nothing to walk, (0, 0) to write
-      wj = wnone ? 0u : wj;
+      const bool wkx = KX && actw && wj == 0xFEu;                // level KT + 1 found the pattern's last KT + 1 characters absent (below)
+      wj = (wnone || wkx) ? 0u : wj;
       wsp &= (1ull << 56) - 1;
       if constexpr (R3T && kLast) {
         // ... three of them at a time by the three-step row table: one 8-byte load where the step loop below spends three
@@ -379,10 +386,32 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
           r3l += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(go && t == 0));
         }
       }
-      uint64_t wep = wsp + ((actw && !wnone) ? 1u : 0u);
+      uint64_t wep = wsp + ((actw && !wnone && !wkx) ? 1u : 0u);
       uint64_t wbegin = 0, wend = 0;
       if (actw) po.get(wpid, wbegin, wend);
       const uint32_t wlen = (uint32_t)(wend - wbegin);
+      if constexpr (KX) {
+        // Y = the last KT + 1 characters do not occur; wsp = Y's insertion point.  The reference's loop went empty at step KT
+        // (its values: (ins Y, ins Y), KT + 1 steps) if X = the last KT characters occur, else earlier -- where level KT's
+        // entry of X says, with its steps.  One lookup of X decides (here, not in every pattern's batch).
+        if (__builtin_amdgcn_ballot_w64(wkx)) {
+          uint32_t code = 0;
+#pragma unroll
+          for (uint32_t j = 0; j < KT; j++) code = code * ksigma + s_dense[wkx ? pat[wend - 1 - j] : 0u];
+          const uint4 xe = ktab[wkx ? code : 0u];
+          if (wkx) {
+            const uint64_t xsp = (((uint64_t)xe.y << 32) | xe.x) & ((1ull << 56) - 1), xep = ((uint64_t)xe.w << 32) | xe.z;
+            if (xsp < xep) {
+              steps += KT + 1u;
+            } else {
+              wsp = xsp;
+              wep = xep;
+              steps += xe.y >> 24;
+            }
+          }
+          ktl += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(wkx && t == 0));
+        }
+      }
       for (;;) {                                               // eight steps at a time
         const uint32_t wrem = wlen - wit;
         if (!__builtin_amdgcn_ballot_w64(actw && wsp < wep && wrem != 0u)) break;
@@ -581,6 +610,7 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
     };
     if (KT == 0) { issue_ahead(); if constexpr (AHEAD) stage_park(nxt_stage, par ^ 1u); }
     uint64_t sp = 0, ep = ix.n;
+    bool kx_parked = false;                                   // KX: parked by the prologue (its last KT + 1 characters do not occur)
     // symbols without a vector: absent (x = 0) or the EOF symbol (x = 1)
     auto special = [&](uint64_t cfc, uint64_t vb, uint64_t x) { return cfc + ((vb == 1 && x > ix.eof) ? 1u : 0u); };
     if (KT == 0) {
@@ -611,23 +641,103 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
         elig = elig && d != 0xFFu;
         code = code * ksigma + d;
       }
+      // KX: a pattern of more than KT characters whose last KT + 1 are all in the table's alphabet takes level KT + 1's entry
+      // of Z = the KT characters in front of its last one (its steps 1 .. KT) instead -- one lookup for KT + 1 steps
+      bool ex = false;
+      uint32_t chk = 0;                                        // KX: the chunk step KT starts (its character in byte lane 0)
+      uint32_t zcode = 0;
+      if constexpr (KX) {
+        chk = chunk(KT / 4);
+        bool ez = elig && len > KT;
+#pragma unroll
+        for (uint32_t j = 1; j <= KT; j++) {
+          const uint32_t d = s_dense[((j < KT ? tailq.c[j < KT ? j >> 2 : 0u] : chk) >> (8u * (j & 3u))) & 0xFFu];
+          ez = ez && d != 0xFFu;
+          zcode = zcode * ksigma + d;
+        }
+        ex = ez;
+      }
       // every lane loads (a group that is not eligible reads entry 0 and ignores it): a load under `if (elig)` is merged with
       // a default value right behind it, and the compiler puts the wait for the load there -- before the loads below
-      const uint4 ent = ktab[elig ? code : 0u];
+      // (KX: lanes 0 and 1 of the group load the two halves of the 32-byte entry -- one sector, one request -- the quads'
+      // lanes 2 and 3 the same again)
+      const uint4 *ksrc = ktab + (elig ? code : 0u);
+      if constexpr (KX) { if (ex) ksrc = kext + 2ull * zcode + (t & 1u); }
+      const uint4 ent = *ksrc;
       issue_ahead();
-      if (elig) {
+      if (elig && !ex) {
         sp = (((uint64_t)ent.y << 32) | ent.x) & ((1ull << 56) - 1);
         ep = ((uint64_t)ent.w << 32) | ent.z;
         steps += ent.y >> 24;           // the reference's loop ran this many steps on these characters
       }
       ktl += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(elig && t == 0));
       if constexpr (AHEAD) stage_park(nxt_stage, par ^ 1u);      // it was requested beside the entry and has arrived with it
-      if (__builtin_amdgcn_ballot_w64(act && !elig)) {
-        for (uint32_t j = 0; j < KT; j++) {
-          const bool stepping = act && !elig && j < len && sp < ep;
-          if (!__builtin_amdgcn_ballot_w64(stepping)) break;
+      if constexpr (KX) {
+        if (__builtin_amdgcn_ballot_w64(ex)) {
+          // Y's interval = [sp_Z + #(characters < y), sp_Z + #(characters <= y)), y = the pattern's last character: each lane
+          // of the pair counts its half of the entry (the first half's bytes 0 .. 5 are the header), the pair adds them up
+          const uint32_t half = t & 1u, y = tailq.c[0] & 0xFFu;
+          const uint32_t h1 = gbc0(ent.y);
+          const bool big = ((h1 >> 8) & 0xFFu) == 0xFFu;       // the list is in the overflow array
+          uint32_t lt = 0, le = 0;
+          auto count16 = [&](const uint4 &w, uint32_t from) {
+#pragma unroll
+            for (uint32_t b = 0; b < 16; b++) {
+              const uint32_t x = ((b < 4 ? w.x : b < 8 ? w.y : b < 12 ? w.z : w.w) >> (8u * (b & 3u))) & 0xFFu;
+              lt += (b >= from && x < y) ? 1u : 0u;
+              le += (b >= from && x <= y) ? 1u : 0u;
+            }
+          };
+          if (ex && !big) count16(ent, half ? 0u : 6u);
+          uint32_t cnt = (h1 >> 8) & 0xFFu;
+          if (__builtin_amdgcn_ballot_w64(ex && big)) {
+            // one more dependent load (32 bytes per round, lists of up to 64: build_kext) from the overflow list: ~1 % of the
+            // entries at C3
+            const uint32_t h2 = gbc0(ent.z), h3 = gbc0(ent.w);
+            const uint64_t off = (h1 >> 16) | ((uint64_t)(h2 & 0xFFFFFFu) << 16);
+            const uint32_t bc = (h2 >> 24) | (h3 << 8);          // (fewer than 2^32 rows: the level is built up to n = 2^32)
+            if (ex && big) cnt = bc;
+            for (uint32_t i = 0;; i++) {
+              const bool more = ex && big && 32u * i < bc;
+              if (!__builtin_amdgcn_ballot_w64(more)) break;
+              uint4 w = make_uint4(~0u, ~0u, ~0u, ~0u);
+              if (more && 32u * i + 16u * half < bc) w = kovf[off + 2u * i + half];
+              if (more) count16(w, 0u);
+              ktl += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(more && t == 0));
+            }
+          }
+          lt = gbc0(lt) + gbc1(lt);
+          le = y == 255u ? cnt : gbc0(le) + gbc1(le);          // (unused bytes are 0xFF)
+          const uint64_t spz = gbc0(ent.x) | ((uint64_t)(h1 & 0xFFu) << 32);
+          if (ex) {
+            sp = spz + lt;
+            ep = spz + le;
+          }
+          // an empty Y: the reference's values depend on where its loop went empty -- the last walk finds that out with one
+          // lookup of level KT (walk_parked), so that no batch waits for it
+          const bool kxp = ex && sp >= ep;
+          const unsigned long long pm = __builtin_amdgcn_ballot_w64(kxp && t == 0);
+          if (pm) {
+            const uint32_t slot = npark + (uint32_t)__builtin_popcountll(pm & ((1ull << lane64) - 1ull));
+            if (kxp && t == 0) { s_park_row[wave_in_wg][slot] = sp | (0xFEull << 56); s_park_pid[wave_in_wg][slot] = pid; s_park_it[wave_in_wg][slot] = KT + 1u; }
+            npark += (uint32_t)__builtin_popcountll(pm);
+          }
+          kx_parked = kxp;
+          if (ex && !kxp) steps += KT + 1u;
+        }
+      }
+      // the patterns no table entry served walk their first steps (KX: up to step KT, which a pattern served by level KT
+      // takes here too -- on a character without a vector: no memory)
+      constexpr uint32_t kWalk = KX ? KT + 1u : KT;
+      if (__builtin_amdgcn_ballot_w64(act && !(KX ? ex : elig))) {
+        for (uint32_t j = 0; j < kWalk; j++) {
+          const bool stepping = act && (KX ? (!ex && j >= (elig ? KT : 0u)) : !elig) && j < len && sp < ep;
+          if (!__builtin_amdgcn_ballot_w64(stepping)) {
+            if (KX && j < KT) continue;
+            break;
+          }
           if (stepping) {
-            const uint32_t c = (tailq.c[j >> 2] >> (8u * (j & 3u))) & 0xFFu;
+            const uint32_t c = ((j < KT ? tailq.c[j < KT ? j >> 2 : 0u] : chk) >> (8u * (j & 3u))) & 0xFFu;
             const uint4 e = s_tab[c];
             if constexpr (G2) {      // (backward_step of fmx_device.h is written for the layout's own lane group)
               const uint64_t cfc = ((uint64_t)e.y << 32) | e.x, vb = ((uint64_t)e.w << 32) | e.z;
@@ -653,12 +763,14 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
           }
         }
       }
-      ch = chunk(KT / 4);              // the chunk step KT starts
+      if constexpr (KX) ch = chk >> 8;  // the rest of the chunk step KT started: the loop begins at step KT + 1
+      else ch = chunk(KT / 4);         // the chunk step KT starts
     }
+    constexpr uint32_t kIt0 = KX ? KT + 1u : (KT ? KT : 1u);  // the first step of the loop
     uint32_t skip = 0;                                         // steps this group has jumped over and still sits out
-    uint32_t cursor_it = KT ? KT : 1u;                         // the step (ch, nx) stand for
-    bool deferred = false;                                     // this group's pattern was handed on (walk list / rows list)
-    for (uint32_t it = KT ? KT : 1u;; it++) {                  // `it` is wave-uniform
+    uint32_t cursor_it = kIt0;                                 // the step (ch, nx) stand for
+    bool deferred = kx_parked;                                 // this group's pattern was handed on (walk list / rows list)
+    for (uint32_t it = kIt0;; it++) {                          // `it` is wave-uniform
       bool alive = it < len && sp < ep;
       if constexpr (RW != 0u) {      // one row: the rest is a lane's, in the wave's next rows phase
         const bool hand = alive && (ep - sp) == 1 && (RW == 1u || (len - it) % RW == 0u);
@@ -1100,6 +1212,7 @@ struct Search4Args {
   const uint4 *ktab;
   const uint8_t *kdense;
   uint32_t ksigma;
+  const uint4 *kext, *kovf;         // level KT + 1 and its overflow lists (KX only)
   const uint4 *jtab;
   uint32_t jc;
   const unsigned long long *r3tab;
@@ -1114,56 +1227,59 @@ struct Search4Args {
 
 // A kernel launched with <<<>>> is instantiated in the unit that launches it: these wrappers are, by the unit of their
 // (WIDE, LAYOUT) pair, for exactly the entries of FMX_SEARCH4_LIST.
-template <bool WIDE, uint32_t LAYOUT, uint32_t KT, uint32_t JT, uint32_t RW, bool R3T, bool G2>
+template <bool WIDE, uint32_t LAYOUT, uint32_t KT, uint32_t JT, uint32_t RW, bool R3T, bool G2, bool KX>
 void search4_launch(const Search4Args &a, int grid, hipStream_t st) {
-  k_search4<WIDE, LAYOUT, KT, JT, RW, R3T, G2><<<grid, kSThreads, 0, st>>>(a.ix, a.ktab, a.kdense, a.ksigma, a.jtab, a.jc, a.r3tab, a.pat, a.po,
+  k_search4<WIDE, LAYOUT, KT, JT, RW, R3T, G2, KX><<<grid, kSThreads, 0, st>>>(a.ix, a.ktab, a.kdense, a.ksigma, a.kext, a.kovf, a.jtab, a.jc, a.r3tab, a.pat, a.po,
                                                                        a.sp_out, a.ep_out, a.k, a.counters, a.pk_cap, a.spin);
 }
 // what the occupancy query answers for the instantiation (0: it failed)
-template <bool WIDE, uint32_t LAYOUT, uint32_t KT, uint32_t JT, uint32_t RW, bool R3T, bool G2>
+template <bool WIDE, uint32_t LAYOUT, uint32_t KT, uint32_t JT, uint32_t RW, bool R3T, bool G2, bool KX>
 int search4_occupancy() {
   int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_search4<WIDE, LAYOUT, KT, JT, RW, R3T, G2>, kSThreads, 0) != hipSuccess) return 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_search4<WIDE, LAYOUT, KT, JT, RW, R3T, G2, KX>, kSThreads, 0) != hipSuccess) return 0;
   return nb;
 }
 #ifdef FMX_SEARCHLOG
-template <bool WIDE, uint32_t LAYOUT, uint32_t KT, uint32_t JT, uint32_t RW, bool R3T, bool G2>
+template <bool WIDE, uint32_t LAYOUT, uint32_t KT, uint32_t JT, uint32_t RW, bool R3T, bool G2, bool KX>
 int search4_searchlog(void *out, size_t bytes) {      // the log of this instantiation's unit
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_searchlog), bytes < sizeof g_searchlog ? bytes : sizeof g_searchlog) == hipSuccess ? 0 : -1;
 }
 #endif
 
-// Every instantiation of k_search4 that exists, X(WIDE, LAYOUT, KT, JT, RW, R3T, G2) -- what a handle's tables select
+// Every instantiation of k_search4 that exists, X(WIDE, LAYOUT, KT, JT, RW, R3T, G2, KX) -- what a handle's tables select
 // (fmx_search.hip, plan_of), for each KT of the k-mer table:
 //   JT 2   the row jump table holds pairs of entries -- built only from the three-step table R3 and never for the bytes layout
 //          (fmx_jump.hip, build_jump), so always with R3T and only one-hot; G2 = pairs of lanes ("search_lanes"), one-hot only;
+//          KX = level KT + 1 of the k-mer table (fmx_ktab.hip, build_kext: one-hot indexes of up to 2^32 rows, so not WIDE);
 //   JT 1   single entries, with or without R3 (the "jump" = "jumps" policy builds no R3);
 //   JT 0   no jump table: RW 3 with R3, RW 1 with the frontier's row table R1 only, RW 0 with none.
 #define FMX_SEARCH4_ONEHOT_KT(X, W, KT) \
-  X(W, kLayoutOneHot, KT, 2, 0, true, true) X(W, kLayoutOneHot, KT, 2, 0, true, false) \
-  X(W, kLayoutOneHot, KT, 1, 0, true, true) X(W, kLayoutOneHot, KT, 1, 0, true, false) X(W, kLayoutOneHot, KT, 1, 0, false, false) \
-  X(W, kLayoutOneHot, KT, 0, 3, false, false) X(W, kLayoutOneHot, KT, 0, 1, false, false) X(W, kLayoutOneHot, KT, 0, 0, false, false)
+  X(W, kLayoutOneHot, KT, 2, 0, true, true, false) X(W, kLayoutOneHot, KT, 2, 0, true, false, false) \
+  X(W, kLayoutOneHot, KT, 1, 0, true, true, false) X(W, kLayoutOneHot, KT, 1, 0, true, false, false) X(W, kLayoutOneHot, KT, 1, 0, false, false, false) \
+  X(W, kLayoutOneHot, KT, 0, 3, false, false, false) X(W, kLayoutOneHot, KT, 0, 1, false, false, false) X(W, kLayoutOneHot, KT, 0, 0, false, false, false)
+#define FMX_SEARCH4_ONEHOT_KX(X, KT) X(false, kLayoutOneHot, KT, 2, 0, true, true, true) X(false, kLayoutOneHot, KT, 2, 0, true, false, true)
 #define FMX_SEARCH4_BYTES_KT(X, KT) \
-  X(true, kLayoutBytes, KT, 1, 0, true, false) X(true, kLayoutBytes, KT, 1, 0, false, false) \
-  X(true, kLayoutBytes, KT, 0, 3, false, false) X(true, kLayoutBytes, KT, 0, 1, false, false) X(true, kLayoutBytes, KT, 0, 0, false, false)
+  X(true, kLayoutBytes, KT, 1, 0, true, false, false) X(true, kLayoutBytes, KT, 1, 0, false, false, false) \
+  X(true, kLayoutBytes, KT, 0, 3, false, false, false) X(true, kLayoutBytes, KT, 0, 1, false, false, false) X(true, kLayoutBytes, KT, 0, 0, false, false, false)
 // one unit each (WIDE: the one-hot layout above 2^32 rows; the bytes layout is always wide)
 #define FMX_SEARCH4_ONEHOT(X, W) \
   FMX_SEARCH4_ONEHOT_KT(X, W, 0) FMX_SEARCH4_ONEHOT_KT(X, W, 4) FMX_SEARCH4_ONEHOT_KT(X, W, 8) FMX_SEARCH4_ONEHOT_KT(X, W, 12)
+#define FMX_SEARCH4_ONEHOT_LEVELX(X) FMX_SEARCH4_ONEHOT_KX(X, 4) FMX_SEARCH4_ONEHOT_KX(X, 8) FMX_SEARCH4_ONEHOT_KX(X, 12)
 #define FMX_SEARCH4_BYTES(X) FMX_SEARCH4_BYTES_KT(X, 0) FMX_SEARCH4_BYTES_KT(X, 4) FMX_SEARCH4_BYTES_KT(X, 8) FMX_SEARCH4_BYTES_KT(X, 12)
-#define FMX_SEARCH4_LIST(X) FMX_SEARCH4_ONEHOT(X, false) FMX_SEARCH4_ONEHOT(X, true) FMX_SEARCH4_BYTES(X)
+#define FMX_SEARCH4_LIST(X) FMX_SEARCH4_ONEHOT(X, false) FMX_SEARCH4_ONEHOT(X, true) FMX_SEARCH4_BYTES(X) FMX_SEARCH4_ONEHOT_LEVELX(X)
 
 // Declared here for every unit, defined by one: `extern template` keeps the others (fmx_search.hip) from compiling them.
 #ifdef FMX_SEARCHLOG
-#define FMX_SEARCH4_SEARCHLOG_(D, W, L, KT, JT, RW, R3T, G2) D int search4_searchlog<W, L, KT, JT, RW, R3T, G2>(void *, size_t);
+#define FMX_SEARCH4_SEARCHLOG_(D, W, L, KT, JT, RW, R3T, G2, KX) D int search4_searchlog<W, L, KT, JT, RW, R3T, G2, KX>(void *, size_t);
 #else
-#define FMX_SEARCH4_SEARCHLOG_(D, W, L, KT, JT, RW, R3T, G2)
+#define FMX_SEARCH4_SEARCHLOG_(D, W, L, KT, JT, RW, R3T, G2, KX)
 #endif
-#define FMX_SEARCH4_WRAPPERS_(D, W, L, KT, JT, RW, R3T, G2)                                        \
-  D void search4_launch<W, L, KT, JT, RW, R3T, G2>(const Search4Args &, int, hipStream_t);         \
-  D int search4_occupancy<W, L, KT, JT, RW, R3T, G2>();                                            \
-  FMX_SEARCH4_SEARCHLOG_(D, W, L, KT, JT, RW, R3T, G2)
-#define FMX_SEARCH4_EXTERN(W, L, KT, JT, RW, R3T, G2) FMX_SEARCH4_WRAPPERS_(extern template, W, L, KT, JT, RW, R3T, G2)
-#define FMX_SEARCH4_INSTANTIATE(W, L, KT, JT, RW, R3T, G2) FMX_SEARCH4_WRAPPERS_(template, W, L, KT, JT, RW, R3T, G2)
+#define FMX_SEARCH4_WRAPPERS_(D, W, L, KT, JT, RW, R3T, G2, KX)                                    \
+  D void search4_launch<W, L, KT, JT, RW, R3T, G2, KX>(const Search4Args &, int, hipStream_t);     \
+  D int search4_occupancy<W, L, KT, JT, RW, R3T, G2, KX>();                                        \
+  FMX_SEARCH4_SEARCHLOG_(D, W, L, KT, JT, RW, R3T, G2, KX)
+#define FMX_SEARCH4_EXTERN(W, L, KT, JT, RW, R3T, G2, KX) FMX_SEARCH4_WRAPPERS_(extern template, W, L, KT, JT, RW, R3T, G2, KX)
+#define FMX_SEARCH4_INSTANTIATE(W, L, KT, JT, RW, R3T, G2, KX) FMX_SEARCH4_WRAPPERS_(template, W, L, KT, JT, RW, R3T, G2, KX)
 FMX_SEARCH4_LIST(FMX_SEARCH4_EXTERN)
 
 }  // namespace fmx
