@@ -316,6 +316,53 @@ JNIEXPORT void JNICALL FN(writeFm0)(JNIEnv *e, jobject self, jlong h, jstring pa
   rethrow(e, rc);
 }
 
+/* ---- locate (SALoader / SACreator, bwtmerger.scala:214-249,535-556): out[q] = SA[rows[q]] */
+JNIEXPORT void JNICALL FN(locateBatch0)(JNIEnv *e, jobject self, jlong h, jlongArray rows, jlongArray out) {
+  jsize k = (*e)->GetArrayLength(e, rows);
+  if ((*e)->GetArrayLength(e, out) < k) { rethrow(e, FMX_ERR_ARG); return; }
+  jlong *pr = in_longs(e, rows, k);
+  jlong *po = malloc(sizeof(jlong) * (size_t)(k > 0 ? k : 1));
+  int rc = (pr && po) ? fmx_locate_batch(H(h), (const uint64_t *)pr, (size_t)k, (uint64_t *)po) : FMX_ERR_NOMEM;
+  if (rc == FMX_OK && k > 0) (*e)->SetLongArrayRegion(e, out, 0, k, po);
+  free(po);
+  free(pr);
+  rethrow(e, rc);
+}
+
+/* intervals [sp, ep): outOff = k + 1 offsets, outPos = the positions (at most its length); returns the total */
+JNIEXPORT jlong JNICALL FN(locateIntervals0)(JNIEnv *e, jobject self, jlong h, jlongArray sp, jlongArray ep, jlong maxPer,
+                                             jlongArray outOff, jlongArray outPos) {
+  jsize k = (*e)->GetArrayLength(e, sp);
+  jsize cap = (*e)->GetArrayLength(e, outPos);
+  if ((*e)->GetArrayLength(e, ep) != k || (*e)->GetArrayLength(e, outOff) < k + 1 || maxPer < 0) { rethrow(e, FMX_ERR_ARG); return 0; }
+  jlong *ps = in_longs(e, sp, k);
+  jlong *pe = in_longs(e, ep, k);
+  jlong *po = malloc(sizeof(jlong) * (size_t)(k + 1));
+  jlong *pp = malloc(sizeof(jlong) * (size_t)(cap > 0 ? cap : 1));
+  int rc = (ps && pe && po && pp) ? fmx_locate_intervals(H(h), (const uint64_t *)ps, (const uint64_t *)pe, (size_t)k, (uint64_t)maxPer,
+                                                         (uint64_t *)po, (uint64_t *)pp, (size_t)cap)
+                                  : FMX_ERR_NOMEM;
+  jlong total = (rc == FMX_OK || rc == FMX_ERR_OVERFLOW) ? po[k] : 0;
+  if (rc == FMX_OK) {
+    (*e)->SetLongArrayRegion(e, outOff, 0, k + 1, po);
+    if (total > 0) (*e)->SetLongArrayRegion(e, outPos, 0, (jsize)total, pp);
+  }
+  free(pp);
+  free(po);
+  free(pe);
+  free(ps);
+  rethrow(e, rc);
+  return total;
+}
+
+/* SACreator.create: the reference's X.sa */
+JNIEXPORT void JNICALL FN(writeSa0)(JNIEnv *e, jobject self, jlong h, jstring path) {
+  const char *p = (*e)->GetStringUTFChars(e, path, 0);
+  int rc = p ? fmx_write_sa(H(h), p) : FMX_ERR_NOMEM;
+  if (p) (*e)->ReleaseStringUTFChars(e, path, p);
+  rethrow(e, rc);
+}
+
 /* The same into direct ByteBuffers: out = cap fmx_result records of 24 bytes (u32 regex, u32 len, u64 sp, u64 ep,
  * native byte order), perRegex = k u32 counts or null.  With buffers from hostAlloc0 the device writes the grouped
  * results and the counts into them itself, behind the search and before the call's one synchronisation
@@ -443,7 +490,7 @@ JNIEXPORT jint JNICALL FN(calcGapsChain0)(JNIEnv *e, jobject self, jlong h, jbyt
 }
 
 /* fmx_prepare: build the k-mer jump table (what & 1) / the select directory (what & 2) / the literal search's row tables (what & 4) /
- * the regex frontier's row table (what & 8) now, not at the threshold or at first use */
+ * the regex frontier's row table (what & 8) / the locate samples (what & 32) now, not at the threshold or at first use */
 JNIEXPORT void JNICALL FN(prepare0)(JNIEnv *e, jobject self, jlong h, jint what) { rethrow(e, fmx_prepare(H(h), (unsigned)what)); }
 
 /* fmx_prepare_ex: the same under a budget of device bytes for all derived tables of the handle (0: the handle's own policy) */

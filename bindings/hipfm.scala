@@ -39,6 +39,9 @@ object HipFM {
   @native def prevSubstr0(h: Long, sp: Long, len: Int): Array[Byte]
   @native def nextSubstrBatch0(h: Long, rows: Array[Long], len: Int, out: Array[Byte], outLen: Array[Int]): Unit
   @native def writeFm0(h: Long, path: String): Unit
+  @native def locateBatch0(h: Long, rows: Array[Long], out: Array[Long]): Unit
+  @native def locateIntervals0(h: Long, sp: Array[Long], ep: Array[Long], maxPer: Long, outOff: Array[Long], outPos: Array[Long]): Long
+  @native def writeSa0(h: Long, path: String): Unit
   @native def hostAlloc0(bytes: Long): ByteBuffer
   @native def hostFree0(buf: ByteBuffer): Unit
   @native def regexCompile0(latin1: Array[Byte], lineOnly: Boolean): Long
@@ -177,6 +180,23 @@ class HipFMSearcher private[fmindex] (opened: Long) extends SuffixWalkingAlgo wi
   /** FMCreator.create (bwtmerger.scala:424-533) from the device structure. */
   def writeFm(path: String): Unit = writeFm0(h, path)
 
+  /** SALoader.read (bwtmerger.scala:214-249) without X.sa: SA[row] from the handle's sampled suffix array (built on first use). */
+  def locate(rows: Array[Long]): Array[Long] = {
+    val out = new Array[Long](rows.length)
+    locateBatch0(h, rows, out)
+    out
+  }
+  /** Positions of rows sp .. sp + min(ep - sp, maxPer) - 1 of each interval (maxPer 0: all), interval i's at off(i) until off(i + 1). */
+  def locate(sp: Array[Long], ep: Array[Long], maxPer: Long): (Array[Long], Array[Long]) = {
+    val total = sp.indices.map(i => math.max(0L, if (maxPer > 0) math.min(ep(i) - sp(i), maxPer) else ep(i) - sp(i))).sum
+    val off = new Array[Long](sp.length + 1)
+    val pos = new Array[Long](total.toInt)
+    locateIntervals0(h, sp, ep, maxPer, off, pos)
+    (off, pos)
+  }
+  /** SACreator.create (bwtmerger.scala:535-556): the reference's X.sa from the device structure. */
+  def writeSa(path: String): Unit = writeSa0(h, path)
+
   /** A batch in page-locked direct buffers (little-endian): the library moves it by DMA, pipelined against the
     * search.  `pat` = pattern bytes, `off` = k+1 longs, `out` receives sp[0..k) then ep[0..k) as longs. */
   def searchBatchDirect(pat: ByteBuffer, off: ByteBuffer, out: ByteBuffer, k: Long): Unit =
@@ -195,7 +215,7 @@ class HipFMSearcher private[fmindex] (opened: Long) extends SuffixWalkingAlgo wi
   def searchBatchPackedDirect(pat: ByteBuffer, len: Int, out: ByteBuffer, k: Long, escapeCap: Long): Unit =
     searchBatchPackedDirect0(h, pat, len, out, k, escapeCap)
 
-  /** Build the derived tables now (fmx_prepare: 1 = k-mer table, 2 = select directory, 4 = the literal search's row tables, 8 = the regex frontier's) / free the row tables. */
+  /** Build the derived tables now (fmx_prepare: 1 = k-mer table, 2 = select directory, 4 = the literal search's row tables, 8 = the regex frontier's, 32 = the locate samples) / free the row tables. */
   def prepare(what: Int): Unit = prepare0(h, what)
   /** The same under a budget: at most budgetBytes of device memory for all derived tables of this handle (fmx_prepare_ex). */
   def prepare(what: Int, budgetBytes: Long): Unit = prepareEx0(h, what, budgetBytes)

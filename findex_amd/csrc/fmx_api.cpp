@@ -282,6 +282,8 @@ static void destroy(Index *h) {
   if (h->d_sel_dir) (void)hipFree(h->d_sel_dir);
   if (h->d_sel_off) (void)hipFree(h->d_sel_off);
   if (h->d_sel_shift) (void)hipFree(h->d_sel_shift);
+  if (h->d_loc_marks) (void)hipFree(h->d_loc_marks);
+  if (h->d_loc_samples) (void)hipFree(h->d_loc_samples);
   for (CallCtx *c : h->ctx_pool) free_ctx(c);
   delete h;
 }
@@ -520,7 +522,7 @@ int fmx_index_config_set(fmx_index *idx, const char *key, const char *value) {
   const int pr = policy_set(H(idx)->policy, key, value, &why);
   if (pr == 0) return FMX_OK;
   if (pr == 2) return arg_fail(why);
-  return arg_fail("not a per-handle key (ktab, jump, jump_pairs, search_lanes, jump_chars, tables_after, table_budget)");
+  return arg_fail("not a per-handle key (ktab, jump, jump_pairs, search_lanes, jump_chars, tables_after, table_budget, locate_sample)");
 }
 
 int fmx_host_alloc(size_t bytes, void **out) {
@@ -614,8 +616,12 @@ int fmx_open_block(const uint8_t *bwt, uint64_t n, const int64_t bucket_starts[2
 
 int fmx_prepare(const fmx_index *idx, unsigned what) {
   if (!idx) return arg_fail("null argument");
-  if (what & ~(unsigned)(FMX_PREPARE_KTAB | FMX_PREPARE_SELECT | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_SEARCH)) return arg_fail("unknown fmx_prepare flag");
+  if (what & ~(unsigned)(FMX_PREPARE_KTAB | FMX_PREPARE_SELECT | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_SEARCH | FMX_PREPARE_LOCATE)) return arg_fail("unknown fmx_prepare flag");
   const Index *h = H(idx);
+  if (what & FMX_PREPARE_LOCATE) {
+    const int lc = locate_check(h);
+    if (lc) return lc;
+  }
   int rc = use_device(h);
   if (rc) return rc;
   CtxLease lease(h);
@@ -637,6 +643,10 @@ int fmx_prepare(const fmx_index *idx, unsigned what) {
     const unsigned long long *r1 = nullptr;
     HIP_TRY(row1_get(h, lease.c->stream, &r1), "row table");
   }
+  if (what & FMX_PREPARE_LOCATE) {
+    rc = locate_prepare(h, lease.c->stream);
+    if (rc) return rc;
+  }
   // the literal search kernel this handle's tables select, calibrated here (its residency census: fmx_search.hip) so that no
   // _dev call ever has to read anything back
   if (what & (FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_SEARCH)) HIP_TRY(search_calibrate(h, lease.c->stream), "search calibration");
@@ -654,7 +664,7 @@ int fmx_prepare_ex(fmx_index *idx, unsigned what, uint64_t budget_bytes) {
 
 int fmx_drop_tables(fmx_index *idx, unsigned what) {
   if (!idx) return arg_fail("null argument");
-  if (!what || (what & ~(unsigned)(FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER))) return arg_fail("fmx_drop_tables frees the k-mer table and the row tables (FMX_PREPARE_KTAB, FMX_PREPARE_JUMP, FMX_PREPARE_FRONTIER)");
+  if (!what || (what & ~(unsigned)(FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_LOCATE))) return arg_fail("fmx_drop_tables frees the k-mer table, the row tables and the locate samples (FMX_PREPARE_KTAB, FMX_PREPARE_JUMP, FMX_PREPARE_FRONTIER, FMX_PREPARE_LOCATE)");
   Index *h = H(idx);
   int rc = use_device(h);
   if (rc) return rc;
@@ -1243,6 +1253,130 @@ int fmx_write_fm(const fmx_index *idx, const char *path) {
   for (uint64_t o = 0; o < h->n * 4; o += chunk) {
     const size_t len = (size_t)std::min<uint64_t>(chunk, h->n * 4 - o);
     HIP_TRY(hipMemcpy(buf.data(), (const uint8_t *)dfm.p + o, len, hipMemcpyDeviceToHost), "D2H(fm)");
+    if (std::fwrite(buf.data(), 1, len, f) != len) { g_err = "short write"; return FMX_ERR_IO; }
+  }
+  return FMX_OK;
+}
+
+// ---------------------------------------------------------------- locate (fmx_locate.hip; SALoader / SACreator / bwtFm2sa)
+// The samples are built here when a call finds none (under the handle's lock, as the select directory at the first Psi).
+static int locate_ready(const Index *h, hipStream_t st) {
+  {
+    std::lock_guard<std::mutex> lk(h->loc_mu);
+    if (h->loc_ready) return FMX_OK;
+  }
+  if (st) return locate_prepare(h, st);
+  CtxLease lease(h);
+  if (!lease.c) return FMX_ERR_HIP;
+  return locate_prepare(h, lease.c->stream);
+}
+
+int fmx_locate_batch(const fmx_index *idx, const uint64_t *rows, size_t k, uint64_t *out_pos) {
+  if (!idx || (k && (!rows || !out_pos))) return arg_fail("null argument");
+  const Index *h = H(idx);
+  int rc = locate_check(h);
+  if (rc) return rc;
+  for (size_t q = 0; q < k; q++)
+    if (rows[q] >= h->n) return arg_fail("row out of range (reference: SALoader reads past X.sa)");
+  if ((rc = use_device(h)) || !k) return rc;
+  if ((rc = locate_ready(h, nullptr))) return rc;
+  const HostIn ins[] = {{rows, k * 8}};
+  const HostOut outs[] = {{out_pos, k * 8}};
+  return run_io(h, ins, 1, outs, 1, [&](hipStream_t st, const void *const *di, void *const *dout) {
+    return launch_locate(h, di[0], k, dout[0], st);
+  });
+}
+
+int fmx_locate_batch_dev(const fmx_index *idx, const void *d_rows, size_t k, void *d_out_pos, void *stream) {
+  if (!idx || (k && (!d_rows || !d_out_pos))) return arg_fail("null argument");
+  const Index *h = H(idx);
+  int rc = locate_check(h);
+  if (rc) return rc;
+  if ((rc = use_device(h)) || !k) return rc;
+  if ((rc = locate_ready(h, (hipStream_t)stream))) return rc;
+  HIP_TRY(launch_locate(h, d_rows, k, d_out_pos, (hipStream_t)stream), "k_locate");
+  return FMX_OK;
+}
+
+int fmx_locate_intervals(const fmx_index *idx, const uint64_t *sp, const uint64_t *ep, size_t k, uint64_t max_per,
+                         uint64_t *out_off, uint64_t *out_pos, size_t cap) {
+  if (!idx || !out_off || (k && (!sp || !ep)) || (cap && !out_pos)) return arg_fail("null argument");
+  const Index *h = H(idx);
+  int rc = locate_check(h);
+  if (rc) return rc;
+  const uint64_t lim = max_per ? max_per : ~0ull;
+  uint64_t total = 0;
+  for (size_t i = 0; i < k; i++) {
+    if (sp[i] > h->n || ep[i] > h->n) return arg_fail("interval out of range (sp, ep <= n)");
+    out_off[i] = total;
+    total += ep[i] > sp[i] ? std::min<uint64_t>(ep[i] - sp[i], lim) : 0;
+  }
+  out_off[k] = total;
+  const uint64_t m = std::min<uint64_t>(total, cap);
+  std::vector<uint64_t> rows(m);
+  for (size_t i = 0, o = 0; i < k && o < m; i++)
+    for (uint64_t t = 0; t < out_off[i + 1] - out_off[i] && o < m; t++) rows[o++] = sp[i] + t;
+  if (m && (rc = fmx_locate_batch(idx, rows.data(), m, out_pos))) return rc;
+  if (total > cap) {
+    g_err = "locate_intervals: " + std::to_string(total) + " positions, room for " + std::to_string(cap);
+    return FMX_ERR_OVERFLOW;
+  }
+  return FMX_OK;
+}
+
+int fmx_locate_intervals_dev(const fmx_index *idx, const void *d_sp, const void *d_ep, size_t k, uint64_t max_per,
+                             void *d_out_off, void *d_out_pos, size_t cap, void *stream) {
+  if (!idx || !d_out_off || (k && (!d_sp || !d_ep)) || (cap && !d_out_pos)) return arg_fail("null argument");
+  const Index *h = H(idx);
+  int rc = locate_check(h);
+  if (rc) return rc;
+  if ((rc = use_device(h))) return rc;
+  if ((rc = locate_ready(h, (hipStream_t)stream))) return rc;
+  HIP_TRY(launch_locate_intervals(h, d_sp, d_ep, k, max_per, d_out_off, d_out_pos, cap, (hipStream_t)stream), "k_locate");
+  return FMX_OK;
+}
+
+int fmx_locate_info(const fmx_index *idx, uint32_t *rate, uint64_t *bytes, double *build_ms) {
+  if (!idx) return arg_fail("null argument");
+  const Index *h = H(idx);
+  std::lock_guard<std::mutex> lk(h->loc_mu);
+  if (rate) *rate = h->loc_ready ? h->loc_rate : (uint32_t)h->policy.locate_sample.load(std::memory_order_relaxed);
+  if (bytes) *bytes = h->loc_ready ? h->loc_bytes : 0;
+  if (build_ms) *build_ms = h->loc_ready ? h->loc_build_ms : 0.0;
+  return FMX_OK;
+}
+
+// SACreator.create (bwtmerger.scala:542-555): n big-endian int32 values, SA[row] at byte 4 row.
+int fmx_write_sa(const fmx_index *idx, const char *path) {
+  if (!idx || !path) return arg_fail("null argument");
+  const Index *h = H(idx);
+  int rc = locate_check(h);
+  if (rc) return rc;
+  if (h->n >= (1ull << 32)) { g_err = "X.sa holds 4-byte entries (SACreator, bwtmerger.scala:548): n must be < 2^32"; return FMX_ERR_UNSUPPORTED; }
+  FILE *f = std::fopen(path, "wb");
+  if (!f) { g_err = std::string("cannot create ") + path; return FMX_ERR_IO; }
+  std::unique_ptr<FILE, int (*)(FILE *)> guard(f, std::fclose);
+  if ((rc = use_device(h))) return rc;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
+  const uint64_t need = locate_write_sa_bytes(h);
+  if (need > free_b) {
+    g_err = "fmx_write_sa needs " + std::to_string(need) + " bytes of device memory, " + std::to_string((unsigned long long)free_b) + " are free";
+    return FMX_ERR_NOMEM;
+  }
+  struct Buf {
+    void *p = nullptr;
+    ~Buf() { if (p) (void)hipFree(p); }
+  } d;
+  HIP_TRY(hipMalloc(&d.p, h->n * 4), "hipMalloc(sa)");
+  CtxLease lease(h);
+  if (!lease.c) return FMX_ERR_HIP;
+  if ((rc = locate_write_sa(h, lease.c->stream, (uint32_t *)d.p))) return rc;
+  const size_t chunk = 64u << 20;
+  std::vector<uint8_t> buf(std::min<uint64_t>(chunk, h->n * 4));
+  for (uint64_t o = 0; o < h->n * 4; o += chunk) {
+    const size_t len = (size_t)std::min<uint64_t>(chunk, h->n * 4 - o);
+    HIP_TRY(hipMemcpy(buf.data(), (const uint8_t *)d.p + o, len, hipMemcpyDeviceToHost), "D2H(sa)");
     if (std::fwrite(buf.data(), 1, len, f) != len) { g_err = "short write"; return FMX_ERR_IO; }
   }
   return FMX_OK;

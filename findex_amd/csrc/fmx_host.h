@@ -67,6 +67,7 @@ struct TablePolicy {
   // the BUDGET: device bytes all derived tables of this handle (k-mer, row, row jump, select) may hold together
   std::atomic<uint64_t> budget_bytes{~0ull};   // ~0: none (what fits beside the margins)
   std::atomic<uint32_t> budget_ppb{0};         // != 0: a fraction (billionths) of the HBM that is free when a table is decided, the handle's own tables counted as free
+  std::atomic<int> locate_sample{32};          // "locate_sample": the rate s of the locate samples (rows with SA % s == 0), 1 .. 4096
   TablePolicy() = default;
   TablePolicy(const TablePolicy &o) { *this = o; }
   TablePolicy &operator=(const TablePolicy &o) {
@@ -74,6 +75,7 @@ struct TablePolicy {
     search_lanes.store(o.search_lanes.load());
     jump_chars.store(o.jump_chars.load()); tables_after.store(o.tables_after.load());
     budget_bytes.store(o.budget_bytes.load()); budget_ppb.store(o.budget_ppb.load());
+    locate_sample.store(o.locate_sample.load());
     return *this;
   }
 };
@@ -160,6 +162,16 @@ struct Index {
   mutable bool sel_ready = false;
   mutable void *d_sel_dir = nullptr, *d_sel_off = nullptr, *d_sel_shift = nullptr;
   mutable uint64_t sel_bytes = 0;
+  // sampled suffix array for locate (fmx_locate.hip), built by fmx_prepare(FMX_PREPARE_LOCATE) or the first locate call;
+  // outside the table budget (the search tables never see it)
+  mutable std::mutex loc_mu;
+  mutable bool loc_ready = false;
+  mutable void *d_loc_marks = nullptr;          // one-hot rank blocks over the rows: bit r set <=> SA[r] % loc_rate == 0
+  mutable void *d_loc_samples = nullptr;        // SA of the marked rows in row order: u32, or u64 when loc_wide
+  mutable uint32_t loc_rate = 0;
+  mutable bool loc_wide = false;
+  mutable uint64_t loc_bytes = 0;
+  mutable double loc_build_ms = 0.0;
   mutable uint64_t launches = 0;
   mutable double last_kernel_ms = 0.0;
   // the handle's host thread for the one-process-several-GPUs entry points (made at the first such call; fmx_hostpar.h)
@@ -199,6 +211,18 @@ hipError_t jump_get(const Index *h, hipStream_t st, const uint4 **out, bool buil
 hipError_t row1_get(const Index *h, hipStream_t st, const unsigned long long **out, bool build = true);   // fmx_jump.hip (nullptr: none)
 hipError_t row3_get(const Index *h, hipStream_t st, const unsigned long long **out, bool build = true);   // fmx_jump.hip (nullptr: none)
 int drop_tables(Index *h, unsigned what);       // fmx_jump.hip: fmx_drop_tables
+
+// fmx_locate.hip: the locate samples.  locate_prepare builds them under loc_mu (allocates, synchronises `st`; an FMX_*
+// status with its message); launch_locate* need them built.  locate_write_sa: every row's SA as big-endian u32 into
+// d_sa_be (n < 2^32), the handle's own samples untouched; locate_write_sa_bytes: the device bytes that takes, d_sa_be included.
+int locate_check(const Index *h);               // FMX_ERR_UNSUPPORTED for handles locate cannot serve
+int locate_prepare(const Index *h, hipStream_t st);
+void locate_drop(Index *h);
+int locate_write_sa(const Index *h, hipStream_t st, uint32_t *d_sa_be);
+uint64_t locate_write_sa_bytes(const Index *h);
+hipError_t launch_locate(const Index *h, const void *d_rows, uint64_t k, void *d_out, hipStream_t st);
+hipError_t launch_locate_intervals(const Index *h, const void *d_sp, const void *d_ep, uint64_t k, uint64_t max_per,
+                                   void *d_off, void *d_pos, uint64_t cap, hipStream_t st);
 // fmx_search.hip: the residency census of the k_search4 instantiation this handle's full-size searches use now, taken with
 // calibration launches on `st` (synchronises it): fmx_prepare's last step, never a _dev call's.
 hipError_t search_calibrate(const Index *h, hipStream_t st);

@@ -188,6 +188,13 @@ int policy_set(TablePolicy &p, const char *key, const char *value, const char **
     else { *why = "search_lanes must be auto, quads or pairs"; return 2; }
     return 0;
   }
+  if (is("locate_sample")) {
+    char *end = nullptr;
+    const long v = std::strtol(value, &end, 10);
+    if (end == value || *end || v < 1 || v > 4096) { *why = "locate_sample must be an integer 1 .. 4096"; return 2; }
+    p.locate_sample.store((int)v);
+    return 0;
+  }
   if (is("jump_chars")) {
     uint64_t v = 0;
     if (!parse_u64(value, &v) || v < 8 || v > 11) { *why = "jump_chars must be 8, 9, 10 or 11"; return 2; }
@@ -425,6 +432,7 @@ int drop_tables(Index *h, unsigned what) {
     tables_account(h, -(int64_t)h->row1_bytes);
     h->d_row1 = nullptr; h->row1_bytes = 0; h->r1_ready = false;
   }
+  if (what & 32u) locate_drop(h);     // the locate samples (FMX_PREPARE_LOCATE)
   return 0;
 }
 

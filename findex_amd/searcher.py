@@ -225,6 +225,71 @@ class HipFMSearcher:
         """FMCreator.create (bwtmerger.scala:452-532): write the reference's .fm file."""
         _lib.check(self._L.fmx_write_fm(self._h, str(path).encode()))
 
+    # ---- locate: SALoader / SACreator (bwtmerger.scala:214-249,535-556), Util.bwtFm2sa (util.scala:213-224)
+    def locate(self, rows):
+        """fmx_locate_batch: SA[row] for each row (the position in reverse(text) + sentinel of the row's suffix)."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        out = np.zeros(rows.size, dtype=np.uint64)
+        _lib.check(self._L.fmx_locate_batch(self._h, _ptr(rows), rows.size, _ptr(out)))
+        return out
+
+    def locate_dev(self, d_rows, k, d_out, stream=0):
+        """fmx_locate_batch_dev: device pointers; a row >= n gets UINT64_MAX."""
+        _lib.check(self._L.fmx_locate_batch_dev(self._h, _dp(d_rows), int(k), _dp(d_out), _dp(stream)))
+
+    def locate_intervals(self, sp, ep, max_per=None):
+        """fmx_locate_intervals: (off, pos) -- interval i's positions are pos[off[i]:off[i + 1]], rows sp[i] ..
+        sp[i] + min(ep[i] - sp[i], max_per) - 1 in row order."""
+        sp = np.ascontiguousarray(sp, dtype=np.uint64)
+        ep = np.ascontiguousarray(ep, dtype=np.uint64)
+        if sp.size != ep.size:
+            raise ValueError("sp and ep differ in length")
+        cnt = np.where(ep > sp, ep - sp, 0).astype(np.uint64)
+        if max_per is not None:
+            cnt = np.minimum(cnt, np.uint64(max_per))
+        cap = int(cnt.sum())
+        off = np.zeros(sp.size + 1, dtype=np.uint64)
+        pos = np.zeros(max(cap, 1), dtype=np.uint64)
+        _lib.check(self._L.fmx_locate_intervals(self._h, _ptr(sp), _ptr(ep), sp.size, int(max_per or 0), _ptr(off),
+                                                _ptr(pos), cap))
+        return off, pos[:cap]
+
+    def locate_intervals_dev(self, d_sp, d_ep, k, d_off, d_pos, cap, max_per=None, stream=0):
+        """fmx_locate_intervals_dev: d_off gets k + 1 offsets (d_off[k] = the total, which may exceed cap)."""
+        _lib.check(self._L.fmx_locate_intervals_dev(self._h, _dp(d_sp), _dp(d_ep), int(k), int(max_per or 0), _dp(d_off),
+                                                    _dp(d_pos), int(cap), _dp(stream)))
+
+    @staticmethod
+    def text_offsets(sa, n, m):
+        """Where a text string of length m begins in the indexed text, for the SA values of the rows a search for its
+        reverse found: n - 1 - SA - m (the index holds reverse(text) + sentinel, n = len(text) + 1 rows)."""
+        sa = np.asarray(sa, dtype=np.uint64)
+        return (np.uint64(n - 1 - m) - sa).astype(np.uint64) if sa.size else sa.astype(np.uint64)
+
+    def locate_text(self, q, max_hits=None):
+        """Sorted text offsets of the occurrences of q (overlapping ones included) -- at most max_hits of them."""
+        q = bytes(q)
+        if not q:
+            raise ValueError("empty pattern")
+        r = self.search(q[::-1])
+        if r is None:
+            return np.zeros(0, dtype=np.uint64)
+        sp, ep = r
+        if max_hits is not None:
+            ep = min(ep, sp + int(max_hits))
+        pos = self.locate(np.arange(sp, ep, dtype=np.uint64))
+        return np.sort(self.text_offsets(pos, self.n, len(q)))
+
+    def locate_info(self):
+        """fmx_locate_info: (rate, device bytes, build ms) of the locate samples; 0 bytes when not built."""
+        rate, nbytes, ms = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_double()
+        _lib.check(self._L.fmx_locate_info(self._h, ctypes.byref(rate), ctypes.byref(nbytes), ctypes.byref(ms)))
+        return int(rate.value), int(nbytes.value), float(ms.value)
+
+    def write_sa(self, path):
+        """SACreator.create (bwtmerger.scala:535-556): write the reference's X.sa (n big-endian int32)."""
+        _lib.check(self._L.fmx_write_sa(self._h, str(path).encode()))
+
     # ---- batched forms (host arrays in, host arrays out)
     def occ_batch(self, c, i):
         c = np.ascontiguousarray(c, dtype=np.uint8)
@@ -370,19 +435,23 @@ class HipFMSearcher:
                                                _ptr(ranks), ctypes.byref(done)))
         return ranks[: text.size], int(done.value)
 
-    def prepare(self, ktab=True, select=False, jump=False, frontier=False, search=False, budget_bytes=0):
+    def prepare(self, ktab=True, select=False, jump=False, frontier=False, search=False, budget_bytes=0, locate=False):
         """fmx_prepare[_ex]: build the k-mer jump table / the select directory / the literal search's row tables (J, R3) / the
-        regex frontier's row table now instead of at the threshold or at first use, and calibrate the search kernel they
-        select (`search` alone: only that).  budget_bytes != 0: the handle's "table_budget" first (fmx_prepare_ex)."""
-        what = (1 if ktab else 0) | (2 if select else 0) | (4 if jump else 0) | (8 if frontier else 0) | (16 if search else 0)
+        regex frontier's row table / the locate samples now instead of at the threshold or at first use, and calibrate the
+        search kernel they select (`search` alone: only that).  budget_bytes != 0: the handle's "table_budget" first
+        (fmx_prepare_ex)."""
+        what = (1 if ktab else 0) | (2 if select else 0) | (4 if jump else 0) | (8 if frontier else 0) | (16 if search else 0) \
+            | (32 if locate else 0)
         if budget_bytes:
             _lib.check(self._L.fmx_prepare_ex(self._h, what, int(budget_bytes)))
         else:
             _lib.check(self._L.fmx_prepare(self._h, what))
 
-    def drop_tables(self, jump=True, frontier=True, ktab=False):
-        """fmx_drop_tables: free the row jump table and the three-step row table / the frontier's row table / the k-mer table."""
-        _lib.check(self._L.fmx_drop_tables(self._h, (4 if jump else 0) | (8 if frontier else 0) | (1 if ktab else 0)))
+    def drop_tables(self, jump=True, frontier=True, ktab=False, locate=False):
+        """fmx_drop_tables: free the row jump table and the three-step row table / the frontier's row table / the k-mer table /
+        the locate samples."""
+        _lib.check(self._L.fmx_drop_tables(self._h, (4 if jump else 0) | (8 if frontier else 0) | (1 if ktab else 0)
+                                           | (32 if locate else 0)))
 
     def config_set(self, key, value):
         """fmx_index_config_set: this handle's own table policy ("ktab", "jump", "jump_pairs", "search_lanes", "jump_chars", "tables_after",

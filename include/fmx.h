@@ -62,7 +62,8 @@ typedef struct fmx_regex_batch fmx_regex_batch;   /* a set of compiled regexes m
 
 const char *fmx_last_error(void);
 int fmx_abi_version(void);
-/* Process-wide options.  The table keys ("ktab", "jump", "jump_pairs", "search_lanes", "jump_chars", "tables_after", "table_budget") are the
+/* Process-wide options.  The table keys ("ktab", "jump", "jump_pairs", "search_lanes", "jump_chars", "tables_after", "table_budget",
+ * "locate_sample": the locate samples' rate, fmx_locate_batch) are the
  * DEFAULTS a handle copies when it is opened; fmx_index_config_set changes one handle's own copy afterwards, so two handles
  * in one process (one JVM) can differ.  key "layout": "auto" (default: one-hot bit-vectors, one 64-byte block per
  * rank query, when sigma*n/7 bytes fit in free HBM and n < 2^37; else BWT bytes + checkpoints, two
@@ -206,12 +207,13 @@ int fmx_index_config_set(fmx_index *idx, const char *key, const char *value);
  * call only enqueues.  A table that cannot be built (no memory, no budget) is left out: searches then walk every step on
  * the rank dictionary, with the same results.  The time spent is reported as fmx_stats_t.tables_build_ms.
  * fmx_prepare_ex: the same under a budget -- budget_bytes != 0 becomes the handle's "table_budget" first. */
-enum { FMX_PREPARE_KTAB = 1, FMX_PREPARE_SELECT = 2, FMX_PREPARE_JUMP = 4, FMX_PREPARE_FRONTIER = 8, FMX_PREPARE_SEARCH = 16 };
+enum { FMX_PREPARE_KTAB = 1, FMX_PREPARE_SELECT = 2, FMX_PREPARE_JUMP = 4, FMX_PREPARE_FRONTIER = 8, FMX_PREPARE_SEARCH = 16,
+       FMX_PREPARE_LOCATE = 32 /* the locate samples (fmx_locate_batch below); fmx_drop_tables frees them */ };
 int fmx_prepare(const fmx_index *idx, unsigned what);
 int fmx_prepare_ex(fmx_index *idx, unsigned what, uint64_t budget_bytes);
-/* Frees derived tables again (what = FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER in any combination: the
- * k-mer table / the row jump table and the three-step row table, 16-32 n + 8 n bytes / the frontier's row table, 8 n
- * bytes) and forgets the handle's pattern count, so that they come back only by fmx_prepare or when the threshold is met
+/* Frees derived tables again (what = FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_LOCATE in any
+ * combination: the k-mer table / the row jump table and the three-step row table, 16-32 n + 8 n bytes / the frontier's row
+ * table, 8 n bytes / the locate samples) and forgets the handle's pattern count, so that they come back only by fmx_prepare or when the threshold is met
  * anew (under the handle's policy as it is then).  No other call may be using the handle. */
 int fmx_drop_tables(fmx_index *idx, unsigned what);
 
@@ -359,6 +361,40 @@ int fmx_calc_gaps_chain(const fmx_index *idx, const uint8_t *c, size_t k, uint64
  * and tests can consume an index this engine prepared.  n must be < 0xffffffff (the reference has
  * no 8-byte entry format, :465-469). */
 int fmx_write_fm(const fmx_index *idx, const char *path);
+
+/* ---- locate: the text position of a suffix-array row -- SALoader (bwtmerger.scala:214-249) reading the X.sa that
+ * SACreator (:535-556) writes, and Util.bwtFm2sa (util.scala:213-224), the same walk over in-memory arrays.
+ * Definitions: s = reverse(text) + sentinel, n = len + 1 rows; SA[row] = position in s of the row's suffix, so
+ * SA[eof] = 0, SA[0] = n - 1 and SA[LF(r)] = SA[r] - 1 for every r != eof.  A search for reverse(q), q a text string of
+ * length m, has rows r; q begins at text offset n - 1 - SA[r] - m (LCPSearcher.getStringOn, :322-333, reads the text there).
+ * The handle keeps a SAMPLED suffix array: the rows with SA % s == 0 (s = the key "locate_sample", 1 .. 4096, default 32;
+ * fmx_config_set: the default, fmx_index_config_set: one handle's own), as a bit-vector over the rows in the one-hot
+ * rank-block format (~n / 7 bytes) and their SA values in row order (4 n / s bytes; 8 n / s above 2^32 rows).  It is
+ * built from the BWT alone by inverting it on the device (fmx_open of .bwt/.aux has no suffix array), by
+ * fmx_prepare(FMX_PREPARE_LOCATE) or else by the first locate call -- which then allocates and synchronises, like the
+ * select directory at the first Psi call.  It is outside the table budget and changes no other table.  An index that is
+ * not the BWT of one text (its LF cycle through row 0 is shorter than n) gets FMX_ERR_FORMAT; fmx_open_block handles
+ * get FMX_ERR_UNSUPPORTED.  A locate walks LF from the row to the next sampled row: (s - 1) / 2 steps on average.
+ * fmx_locate_batch     : out_pos[q] = SA[rows[q]]; FMX_ERR_ARG for a row >= n.
+ * fmx_locate_batch_dev : the same on device pointers; a row >= n gets UINT64_MAX.  With the samples prepared it only
+ *                        enqueues (safe inside a stream capture).
+ * fmx_locate_intervals : interval i gets the SA of rows sp[i] .. sp[i] + min(ep[i] - sp[i], max_per) - 1 (max_per 0: no
+ *                        limit; an interval with ep <= sp: none), in row order; out_off (k + 1 entries) = the exclusive scan
+ *                        of those counts, out_off[k] = the total.  Nothing is written past out_pos[cap - 1]; the host form
+ *                        returns FMX_ERR_OVERFLOW when the total exceeds cap (out_off complete, the first cap positions
+ *                        written); the _dev form leaves the total in d_out_off[k] for the caller to check.
+ * fmx_locate_info      : the rate, device bytes and build time (ms) of the samples; 0 bytes when they are not built.
+ * fmx_write_sa         : SACreator's X.sa: n big-endian int32 values, SA[row] at byte 4 row.  n must be < 2^32
+ *                        (FMX_ERR_UNSUPPORTED otherwise, as fmx_write_fm); uses the inversion at s = 1 into a temporary of
+ *                        4 n bytes, the handle's own samples untouched. */
+int fmx_locate_batch(const fmx_index *idx, const uint64_t *rows, size_t k, uint64_t *out_pos);
+int fmx_locate_batch_dev(const fmx_index *idx, const void *d_rows, size_t k, void *d_out_pos, void *stream);
+int fmx_locate_intervals(const fmx_index *idx, const uint64_t *sp, const uint64_t *ep, size_t k, uint64_t max_per,
+                         uint64_t *out_off, uint64_t *out_pos, size_t cap);
+int fmx_locate_intervals_dev(const fmx_index *idx, const void *d_sp, const void *d_ep, size_t k, uint64_t max_per,
+                             void *d_out_off, void *d_out_pos, size_t cap, void *stream);
+int fmx_locate_info(const fmx_index *idx, uint32_t *rate, uint64_t *bytes, double *build_ms);
+int fmx_write_sa(const fmx_index *idx, const char *path);
 
 /* ---- regex: REParser.re2post (re2/re2.scala:50-185) + ReTree.apply (re2/retree.scala:156-370).
  * Bytes of `re` are Latin-1 characters.  FMX_ERR_SYNTAX / FMX_ERR_MATCH mirror the reference's
