@@ -112,23 +112,75 @@ def open_pair(bwt, eof, counts):
     return findex_amd.HipFMSearcher.from_mem(bwt, eof, counts), oracle.NaiveFMSearcher.from_mem(bwt, eof, counts)
 
 
+def biased_bwt(n, probs, seed):
+    """Symbols 1 .. len(probs) drawn with those probabilities: a mildly biased text, whose rarest k-mers do not occur."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    bwt = rng.choice(np.arange(1, len(probs) + 1, dtype=np.uint8), size=n, p=probs).astype(np.uint8)
+    eof = n // 3
+    counts = np.bincount(bwt, minlength=256).astype(np.int64)
+    counts[bwt[eof]] -= 1
+    return bwt, eof, counts
+
+
+def kmer_rows(orc, syms, ke):
+    """The number of rows of every one of the sigma^KE k-mers, by the oracle."""
+    grid = np.array(np.meshgrid(*[syms] * ke, indexing="ij"), dtype=np.uint8).reshape(ke, -1).T
+    buf = np.ascontiguousarray(grid).reshape(-1)
+    sp, ep, _ = orc.search_batch(buf, np.arange(grid.shape[0] + 1, dtype=np.uint64) * ke)
+    return np.where(ep > sp, ep - sp, 0).astype(np.int64)
+
+
+EXT_MAX_LIST = 64       # kExtMaxList (fmx_ktab.hip): an index with a longer list gets no level K+1
+
+# (n, lowest symbol, highest symbol, seed, symbol probabilities or None for uniform, the KE the shape must give).  K is the
+# largest with sigma^K <= n / 8 (build_ktab) and KE the largest multiple of four up to it: 8^4 <= 2^13 < 8^5; 16^4 <= 2^16 <
+# 16^5; 4^5 <= 2^10 < 4^6 (K = 5, used as 4); 3^8 = 6561 <= 2^13 < 3^9; 2^13 <= 2^13 (K = 13, used as 12); and the two
+# biased texts, chosen with the oracle so that every KE-mer has at most 64 rows while more than 1 % of them have none
+# (a stronger bias, or a Fibonacci word, would give lists longer than 64 and silently test the kernels without the level):
+# 3^8 <= 2^13, and 2^12 <= 2^12 < 2^13.
+SHAPES = {
+    "sigma8-mean16": (1 << 16, 1, 8, 11, None, 4),
+    "sigma16-mean8": (1 << 19, 1, 16, 12, None, 4),
+    "sigma4-mean32": (1 << 13, 1, 4, 13, None, 4),
+    "sigma3-ke8": (1 << 16, 1, 3, 14, None, 8),
+    "sigma2-ke12": (1 << 16, 1, 2, 15, None, 12),
+    "sigma3-ke8-biased": (1 << 16, 1, 3, 22, (0.39, 0.38, 0.23), 8),
+    "sigma2-ke12-biased": (1 << 15, 1, 2, 24, (0.59, 0.41), 12),
+}
+ABSENT_KMERS = ("sigma16-mean8", "sigma3-ke8-biased", "sigma2-ke12-biased")      # the shapes with k-mers that do not occur
+
+
+def test_shapes_reach_every_depth_the_level_is_compiled_for():
+    assert {s[5] for s in SHAPES.values()} == {4, 8, 12}
+
+
 @pytest.mark.parametrize("lanes", ["pairs", "quads"])
-@pytest.mark.parametrize("shape", [(1 << 16, 1, 8, 11), (1 << 19, 1, 16, 12), (1 << 13, 1, 4, 13)],
-                         ids=["sigma8-mean16", "sigma16-mean8", "sigma4-mean32"])
-def test_level_matches_oracle(table_default, lanes, shape):
-    n, lo, hi, seed = shape
+@pytest.mark.parametrize("name", list(SHAPES))
+def test_level_matches_oracle(table_default, lanes, name):
+    n, lo, hi, seed, probs, want_ke = SHAPES[name]
     table_default("jump_pairs", "on")
+    bwt, eof, counts = synth_bwt(n, lo, hi, seed) if probs is None else biased_bwt(n, probs, seed)
+    syms = [int(s) for s in np.nonzero(counts)[0] if s != 0]
+    assert len(syms) == hi - lo + 1
+    table_default("ktab_ext", "off")
+    without, _ = open_pair(bwt, eof, counts)
+    without.prepare(ktab=True)
     table_default("ktab_ext", "on")
-    bwt, eof, counts = synth_bwt(n, lo, hi, seed)
     hip, orc = open_pair(bwt, eof, counts)
+    hip.prepare(ktab=True)
+    # the level was built: sigma^KE entries of 32 bytes (and the overflow lists) beside the same levels
+    assert hip.stats()["tables_held_bytes"] >= without.stats()["tables_held_bytes"] + 32 * len(syms) ** want_ke
+    without.close()
     hip.prepare(ktab=True, jump=True)
     st = hip.stats()
     ke = ke_of(st["ktab_k"])
-    assert ke >= 4 and st["jump_bytes"] == 32 * n, st
-    syms = [int(s) for s in np.nonzero(counts)[0] if s != 0]
+    assert ke == want_ke and st["jump_bytes"] == 32 * n, st
     pats = patterns_for(orc, syms, ke, seed) + absent_neighbours(orc, syms, ke, seed)
     za, xa = classify(orc, pats, ke)
-    if shape[2] == 16:      # (only this shape has k-mers that do not occur: 16^4 of them for a mean of 8 rows)
+    if probs is not None:
+        rows = kmer_rows(orc, syms, ke)
+        assert int(rows.max()) <= EXT_MAX_LIST and float((rows == 0).mean()) >= 0.01, (int(rows.max()), float((rows == 0).mean()))
+    if name in ABSENT_KMERS:
         assert za > 0 and xa > 0, (za, xa)
     on, off = run_both_ways(hip, orc, pats, lanes)
     # the level serves the hits: fewer rank-dictionary lines, the same reference steps
