@@ -355,6 +355,27 @@ JNIEXPORT jlong JNICALL FN(locateIntervals0)(JNIEnv *e, jobject self, jlong h, j
   return total;
 }
 
+/* ---- LCP (LCPSuffixWalkingAlgo.getLCP, findex.scala:59-62; LCPLoader, bwtmerger.scala:176-211): out[q] = LCP[rows[q]] */
+JNIEXPORT void JNICALL FN(lcpBatch0)(JNIEnv *e, jobject self, jlong h, jlongArray rows, jintArray out) {
+  jsize k = (*e)->GetArrayLength(e, rows);
+  if ((*e)->GetArrayLength(e, out) < k) { rethrow(e, FMX_ERR_ARG); return; }
+  jlong *pr = in_longs(e, rows, k);
+  jint *po = malloc(sizeof(jint) * (size_t)(k > 0 ? k : 1));
+  int rc = (pr && po) ? fmx_lcp_batch(H(h), (const uint64_t *)pr, (size_t)k, (uint32_t *)po) : FMX_ERR_NOMEM;
+  if (rc == FMX_OK && k > 0) (*e)->SetIntArrayRegion(e, out, 0, k, po);
+  free(po);
+  free(pr);
+  rethrow(e, rc);
+}
+
+/* LCPCreator.create: the reference's X.lcp */
+JNIEXPORT void JNICALL FN(writeLcp0)(JNIEnv *e, jobject self, jlong h, jstring path) {
+  const char *p = (*e)->GetStringUTFChars(e, path, 0);
+  int rc = p ? fmx_write_lcp(H(h), p) : FMX_ERR_NOMEM;
+  if (p) (*e)->ReleaseStringUTFChars(e, path, p);
+  rethrow(e, rc);
+}
+
 /* SACreator.create: the reference's X.sa */
 JNIEXPORT void JNICALL FN(writeSa0)(JNIEnv *e, jobject self, jlong h, jstring path) {
   const char *p = (*e)->GetStringUTFChars(e, path, 0);
@@ -490,7 +511,7 @@ JNIEXPORT jint JNICALL FN(calcGapsChain0)(JNIEnv *e, jobject self, jlong h, jbyt
 }
 
 /* fmx_prepare: build the k-mer jump table (what & 1) / the select directory (what & 2) / the literal search's row tables (what & 4) /
- * the regex frontier's row table (what & 8) / the locate samples (what & 32) now, not at the threshold or at first use */
+ * the regex frontier's row table (what & 8) / the locate samples (what & 32) / the LCP array (what & 64) now, not at the threshold or at first use */
 JNIEXPORT void JNICALL FN(prepare0)(JNIEnv *e, jobject self, jlong h, jint what) { rethrow(e, fmx_prepare(H(h), (unsigned)what)); }
 
 /* fmx_prepare_ex: the same under a budget of device bytes for all derived tables of the handle (0: the handle's own policy) */

@@ -4,6 +4,8 @@
 // and libfmx.so.  It adds, and changes nothing else:
 //   class HipFMSearcher(filename, bigEndian)  extends SuffixWalkingAlgo   -- drop-in for NaiveFMSearcher
 //                                                                            (bwtmerger.scala:335-421)
+//   class HipLCPSearcher(filename, bigEndian) extends HipFMSearcher with LCPSuffixWalkingAlgo
+//                                                                         -- drop-in for LCPSearcher (bwtmerger.scala:322-333)
 //   class HipBWTSearcher(bwt, bucketStarts, rk0) extends SuffixAlgo       -- drop-in for NaiveBWTSearcher
 //                                                                            (findex.scala:459-506)
 //   object HipRegex                                                       -- ReTree.matchSA (re2/retree.scala:570-653)
@@ -42,6 +44,8 @@ object HipFM {
   @native def locateBatch0(h: Long, rows: Array[Long], out: Array[Long]): Unit
   @native def locateIntervals0(h: Long, sp: Array[Long], ep: Array[Long], maxPer: Long, outOff: Array[Long], outPos: Array[Long]): Long
   @native def writeSa0(h: Long, path: String): Unit
+  @native def lcpBatch0(h: Long, rows: Array[Long], out: Array[Int]): Unit
+  @native def writeLcp0(h: Long, path: String): Unit
   @native def hostAlloc0(bytes: Long): ByteBuffer
   @native def hostFree0(buf: ByteBuffer): Unit
   @native def regexCompile0(latin1: Array[Byte], lineOnly: Boolean): Long
@@ -197,6 +201,15 @@ class HipFMSearcher private[fmindex] (opened: Long) extends SuffixWalkingAlgo wi
   /** SACreator.create (bwtmerger.scala:535-556): the reference's X.sa from the device structure. */
   def writeSa(path: String): Unit = writeSa0(h, path)
 
+  /** LCPLoader.read (bwtmerger.scala:176-211) without X.lcp: LCP[row] from the handle's LCP array (built on first use). */
+  def lcp(rows: Array[Long]): Array[Int] = {
+    val out = new Array[Int](rows.length)
+    lcpBatch0(h, rows, out)
+    out
+  }
+  /** LCPCreator.create (bwtmerger.scala:558-652): the reference's X.lcp (n - 1 entries) from the device structure. */
+  def writeLcp(path: String): Unit = writeLcp0(h, path)
+
   /** A batch in page-locked direct buffers (little-endian): the library moves it by DMA, pipelined against the
     * search.  `pat` = pattern bytes, `off` = k+1 longs, `out` receives sp[0..k) then ep[0..k) as longs. */
   def searchBatchDirect(pat: ByteBuffer, off: ByteBuffer, out: ByteBuffer, k: Long): Unit =
@@ -215,13 +228,25 @@ class HipFMSearcher private[fmindex] (opened: Long) extends SuffixWalkingAlgo wi
   def searchBatchPackedDirect(pat: ByteBuffer, len: Int, out: ByteBuffer, k: Long, escapeCap: Long): Unit =
     searchBatchPackedDirect0(h, pat, len, out, k, escapeCap)
 
-  /** Build the derived tables now (fmx_prepare: 1 = k-mer table, 2 = select directory, 4 = the literal search's row tables, 8 = the regex frontier's, 32 = the locate samples) / free the row tables. */
+  /** Build the derived tables now (fmx_prepare: 1 = k-mer table, 2 = select directory, 4 = the literal search's row tables, 8 = the regex frontier's, 32 = the locate samples, 64 = the LCP array) / free the row tables. */
   def prepare(what: Int): Unit = prepare0(h, what)
   /** The same under a budget: at most budgetBytes of device memory for all derived tables of this handle (fmx_prepare_ex). */
   def prepare(what: Int, budgetBytes: Long): Unit = prepareEx0(h, what, budgetBytes)
   /** This handle's own table policy (fmx_index_config_set): "ktab", "jump", "jump_pairs", "search_lanes", "jump_chars", "tables_after", "table_budget". */
   def configSet(key: String, value: String): Unit = indexConfigSet0(h, key, value)
   def dropTables(): Unit = dropTables0(h, 4 | 8)
+}
+
+/** Drop-in for LCPSearcher (bwtmerger.scala:322-333): getLCP from the handle's LCP array instead of X.lcp, getStringOn as the
+  * reference has it -- the data file read from fsize - SA(i), with SA(i) from the handle's sampled suffix array instead of
+  * X.sa.  Neither X.lcp nor X.sa has to exist. */
+class HipLCPSearcher(filename: String, bigEndian: Boolean = true, device: Int = 0)
+    extends HipFMSearcher(filename, bigEndian, device) with LCPSuffixWalkingAlgo {
+  val dataFile = new java.io.File(BWTTempStorage.genDataFilename(filename))
+  val fsize = dataFile.length.toInt
+  val inr = new java.io.RandomAccessFile(dataFile, "r")
+  def getLCP(i: Int): Int = lcp(Array(i.toLong))(0)
+  def getStringOn(i: Int): Iterator[Char] = new StringPosReader(inr, fsize - locate(Array(i.toLong))(0).toInt)
 }
 
 object HipFMSearcher {

@@ -10,13 +10,14 @@ package is the thin host-side mirror of the reference's Scala interface for that
     ReTree(postfix).matchSA(sa)                    ReTree(postfix).matchSA(sa)
     SAResult(sa,len,sp,ep)                         SAResult
     BWTMerger2.merge(FileBWTReader) -> X.bwt/.aux  bwt_from_text(text) + write_bwt(...), python -m findex_amd.index
+    LCPSuffixWalkingAlgo.getLCP, LCPCreator        HipFMSearcher.getLCP / .lcp / .write_lcp, lcp_from_text(text)
 
 There is no CPU fallback: importing works anywhere, but every compute call needs the built
 library and a HIP device and fails loudly otherwise.
 """
 from ._lib import FmxError, MatchError, Re2PostSyntax, LIB_PATH, load  # noqa: F401
 from .searcher import HipFMSearcher  # noqa: F401
-from .construct import bwt_from_text, bwt_from_text_dev, write_bwt  # noqa: F401
+from .construct import bwt_from_text, bwt_from_text_dev, lcp_from_text, lcp_from_text_dev, write_bwt  # noqa: F401
 from .regex import DFA, NFA, REParser, ReTree, SAResult, CompiledRegexes  # noqa: F401
 
 
@@ -58,4 +59,4 @@ def config_set(key, value):
     _lib.check(_lib.load().fmx_config_set(key.encode(), str(value).encode()))
 
 
-__all__ = ["bwt_from_text", "bwt_from_text_dev", "write_bwt", "config_set", "set_layout", "set_checkpoints", "set_ktab", "set_jump", "set_pipeline", "HipFMSearcher", "REParser", "ReTree", "SAResult", "NFA", "DFA", "CompiledRegexes", "FmxError", "MatchError", "Re2PostSyntax"]
+__all__ = ["bwt_from_text", "bwt_from_text_dev", "lcp_from_text", "lcp_from_text_dev", "write_bwt", "config_set", "set_layout", "set_checkpoints", "set_ktab", "set_jump", "set_pipeline", "HipFMSearcher", "REParser", "ReTree", "SAResult", "NFA", "DFA", "CompiledRegexes", "FmxError", "MatchError", "Re2PostSyntax"]

@@ -120,6 +120,15 @@ SYMBOLS = {
     "fmx_locate_intervals_dev": (_i32, [_vp, _vp, _vp, _sz, _u64, _vp, _vp, _sz, _vp]),
     "fmx_locate_info": (_i32, [_vp, _P(_u32), _P(_u64), _P(ctypes.c_double)]),
     "fmx_write_sa": (_i32, [_vp, _cp]),
+    "fmx_lcp_from_text_dev": (_i32, [_vp, _u64, _vp, _vp, _i32, _vp]),
+    "fmx_lcp_from_text": (_i32, [_vp, _u64, _vp, _i32]),
+    "fmx_lcp_batch": (_i32, [_vp, _vp, _sz, _vp]),
+    "fmx_lcp_batch_dev": (_i32, [_vp, _vp, _sz, _vp, _vp]),
+    "fmx_lcp_range": (_i32, [_vp, _u64, _u64, _vp]),
+    "fmx_lcp_range_dev": (_i32, [_vp, _u64, _u64, _vp, _vp]),
+    "fmx_lcp_info": (_i32, [_vp, _P(_u64), _P(ctypes.c_double), _P(_u32), _P(_u64), _P(_u64)]),
+    "fmx_write_lcp": (_i32, [_vp, _cp]),
+    "fmx_lcp_last_phases": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double)]),
     "fmx_occ_host": (_i32, [_vp, _i32, ctypes.c_int64, _P(_u64)]),
     "fmx_calc_gaps_chain": (_i32, [_vp, _vp, _sz, _u64, _i32, _u64, _vp, _P(_sz)]),
     "fmx_regex_compile": (_i32, [_cp, _i32, _P(_vp)]),

@@ -43,6 +43,34 @@ def bwt_from_text_dev(d_text, length, d_bwt, d_sa=0, device=0, stream=0):
     return int(eof.value), counts
 
 
+def lcp_from_text(text, device=0):
+    """fmx_lcp_from_text: the LCP array of reverse(text) + sentinel in the reference's convention (Util.bwtFm2LCP,
+    util.scala:153-212; LCPCreator, bwtmerger.scala:558-652): entry r is the longest common prefix of the suffixes of rows
+    r and r + 1, the last entry 0.  Suffix sort and LCP run on the device.  Returns uint32[len + 1]."""
+    L = _lib.load()
+    t = _text_array(text)
+    lcp = np.zeros(t.size + 1, dtype=np.uint32)
+    _lib.check(L.fmx_lcp_from_text(_ptr(t), t.size, _ptr(lcp), int(device)))
+    return lcp
+
+
+def lcp_from_text_dev(d_text, length, d_sa, d_lcp, device=0, stream=0):
+    """fmx_lcp_from_text_dev: device pointers -- text[length] and the suffix array bwt_from_text_dev left in d_sa
+    (u32[length + 1]) in, the LCP array (u32[length + 1]) out.  Allocates 5 (length + 1) bytes and synchronises `stream`."""
+    L = _lib.load()
+    _lib.check(L.fmx_lcp_from_text_dev(ctypes.c_void_p(int(d_text) or None), int(length), ctypes.c_void_p(int(d_sa) or None),
+                                       ctypes.c_void_p(int(d_lcp) or None), int(device), ctypes.c_void_p(int(stream) or None)))
+
+
+def lcp_last_phases():
+    """fmx_lcp_last_phases: device ms of this thread's last lcp_from_text[_dev] in its three phases (successor array,
+    text-order pass, gather)."""
+    L = _lib.load()
+    a, b, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+    _lib.check(L.fmx_lcp_last_phases(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+    return float(a.value), float(b.value), float(c.value)
+
+
 def write_bwt(bwt_path, aux_path, bwt, eof, counts, bigEndian=True):
     """fmx_write_bwt: X.bwt (int64 size, int64 eof, the bytes; BWTLoader) and X.aux (256 int64; AUXLoader)."""
     L = _lib.load()

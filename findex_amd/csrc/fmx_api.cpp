@@ -284,6 +284,7 @@ static void destroy(Index *h) {
   if (h->d_sel_shift) (void)hipFree(h->d_sel_shift);
   if (h->d_loc_marks) (void)hipFree(h->d_loc_marks);
   if (h->d_loc_samples) (void)hipFree(h->d_loc_samples);
+  if (h->d_lcp) (void)hipFree(h->d_lcp);
   for (CallCtx *c : h->ctx_pool) free_ctx(c);
   delete h;
 }
@@ -616,10 +617,14 @@ int fmx_open_block(const uint8_t *bwt, uint64_t n, const int64_t bucket_starts[2
 
 int fmx_prepare(const fmx_index *idx, unsigned what) {
   if (!idx) return arg_fail("null argument");
-  if (what & ~(unsigned)(FMX_PREPARE_KTAB | FMX_PREPARE_SELECT | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_SEARCH | FMX_PREPARE_LOCATE)) return arg_fail("unknown fmx_prepare flag");
+  if (what & ~(unsigned)(FMX_PREPARE_KTAB | FMX_PREPARE_SELECT | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_SEARCH | FMX_PREPARE_LOCATE | FMX_PREPARE_LCP)) return arg_fail("unknown fmx_prepare flag");
   const Index *h = H(idx);
   if (what & FMX_PREPARE_LOCATE) {
     const int lc = locate_check(h);
+    if (lc) return lc;
+  }
+  if (what & FMX_PREPARE_LCP) {
+    const int lc = lcp_check(h);
     if (lc) return lc;
   }
   int rc = use_device(h);
@@ -647,6 +652,10 @@ int fmx_prepare(const fmx_index *idx, unsigned what) {
     rc = locate_prepare(h, lease.c->stream);
     if (rc) return rc;
   }
+  if (what & FMX_PREPARE_LCP) {
+    rc = lcp_prepare(h, lease.c->stream);
+    if (rc) return rc;
+  }
   // the literal search kernel this handle's tables select, calibrated here (its residency census: fmx_search.hip) so that no
   // _dev call ever has to read anything back
   if (what & (FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_SEARCH)) HIP_TRY(search_calibrate(h, lease.c->stream), "search calibration");
@@ -664,7 +673,7 @@ int fmx_prepare_ex(fmx_index *idx, unsigned what, uint64_t budget_bytes) {
 
 int fmx_drop_tables(fmx_index *idx, unsigned what) {
   if (!idx) return arg_fail("null argument");
-  if (!what || (what & ~(unsigned)(FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_LOCATE))) return arg_fail("fmx_drop_tables frees the k-mer table, the row tables and the locate samples (FMX_PREPARE_KTAB, FMX_PREPARE_JUMP, FMX_PREPARE_FRONTIER, FMX_PREPARE_LOCATE)");
+  if (!what || (what & ~(unsigned)(FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_LOCATE | FMX_PREPARE_LCP))) return arg_fail("fmx_drop_tables frees the k-mer table, the row tables, the locate samples and the LCP array (FMX_PREPARE_KTAB, FMX_PREPARE_JUMP, FMX_PREPARE_FRONTIER, FMX_PREPARE_LOCATE, FMX_PREPARE_LCP)");
   Index *h = H(idx);
   int rc = use_device(h);
   if (rc) return rc;
@@ -1382,6 +1391,120 @@ int fmx_write_sa(const fmx_index *idx, const char *path) {
   return FMX_OK;
 }
 
+// ---------------------------------------------------------------- LCP (fmx_lcp.hip; LCPSuffixWalkingAlgo / LCPLoader / LCPCreator)
+static thread_local double g_lcp_phases[3] = {0.0, 0.0, 0.0};
+
+// The array is built here when a call finds none (under the handle's lock, as the locate samples at the first locate).
+static int lcp_ready(const Index *h, hipStream_t st) {
+  {
+    std::lock_guard<std::mutex> lk(h->lcp_mu);
+    if (h->lcp_ready) return FMX_OK;
+  }
+  if (st) return lcp_prepare(h, st);
+  CtxLease lease(h);
+  if (!lease.c) return FMX_ERR_HIP;
+  return lcp_prepare(h, lease.c->stream);
+}
+
+int fmx_lcp_batch(const fmx_index *idx, const uint64_t *rows, size_t k, uint32_t *out) {
+  if (!idx || (k && (!rows || !out))) return arg_fail("null argument");
+  const Index *h = H(idx);
+  int rc = lcp_check(h);
+  if (rc) return rc;
+  for (size_t q = 0; q < k; q++)
+    if (rows[q] >= h->n) return arg_fail("row out of range (reference: LCPLoader reads past X.lcp)");
+  if ((rc = use_device(h)) || !k) return rc;
+  if ((rc = lcp_ready(h, nullptr))) return rc;
+  const HostIn ins[] = {{rows, k * 8}};
+  const HostOut outs[] = {{out, k * 4}};
+  return run_io(h, ins, 1, outs, 1, [&](hipStream_t st, const void *const *di, void *const *dout) {
+    return launch_lcp_gather(h, di[0], k, dout[0], st);
+  });
+}
+
+int fmx_lcp_batch_dev(const fmx_index *idx, const void *d_rows, size_t k, void *d_out, void *stream) {
+  if (!idx || (k && (!d_rows || !d_out))) return arg_fail("null argument");
+  const Index *h = H(idx);
+  int rc = lcp_check(h);
+  if (rc) return rc;
+  if ((rc = use_device(h)) || !k) return rc;
+  if ((rc = lcp_ready(h, (hipStream_t)stream))) return rc;
+  HIP_TRY(launch_lcp_gather(h, d_rows, k, d_out, (hipStream_t)stream), "k_lcp_rows");
+  return FMX_OK;
+}
+
+static int lcp_range_args(const fmx_index *idx, uint64_t first, uint64_t count, const void *out) {
+  if (!idx || (count && !out)) return arg_fail("null argument");
+  const Index *h = H(idx);
+  int rc = lcp_check(h);
+  if (rc) return rc;
+  if (first > h->n || count > h->n - first) return arg_fail("range out of the array (first + count <= n)");
+  return FMX_OK;
+}
+
+int fmx_lcp_range(const fmx_index *idx, uint64_t first, uint64_t count, uint32_t *out) {
+  int rc = lcp_range_args(idx, first, count, out);
+  if (rc) return rc;
+  const Index *h = H(idx);
+  if ((rc = use_device(h)) || !count) return rc;
+  if ((rc = lcp_ready(h, nullptr))) return rc;
+  HIP_TRY(hipMemcpy(out, static_cast<const uint32_t *>(h->d_lcp) + first, count * 4, hipMemcpyDeviceToHost), "D2H(lcp)");
+  return FMX_OK;
+}
+
+int fmx_lcp_range_dev(const fmx_index *idx, uint64_t first, uint64_t count, void *d_out, void *stream) {
+  int rc = lcp_range_args(idx, first, count, d_out);
+  if (rc) return rc;
+  const Index *h = H(idx);
+  if ((rc = use_device(h)) || !count) return rc;
+  if ((rc = lcp_ready(h, (hipStream_t)stream))) return rc;
+  HIP_TRY(hipMemcpyAsync(d_out, static_cast<const uint32_t *>(h->d_lcp) + first, count * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream),
+          "D2D(lcp)");
+  return FMX_OK;
+}
+
+int fmx_lcp_info(const fmx_index *idx, uint64_t *bytes, double *build_ms, uint32_t *max_lcp, uint64_t *max_row, uint64_t *sum_lcp) {
+  if (!idx) return arg_fail("null argument");
+  const Index *h = H(idx);
+  std::lock_guard<std::mutex> lk(h->lcp_mu);
+  if (bytes) *bytes = h->lcp_ready ? h->lcp_bytes : 0;
+  if (build_ms) *build_ms = h->lcp_ready ? h->lcp_build_ms : 0.0;
+  if (max_lcp) *max_lcp = h->lcp_ready ? h->lcp_max : 0;
+  if (max_row) *max_row = h->lcp_ready ? h->lcp_max_row : 0;
+  if (sum_lcp) *sum_lcp = h->lcp_ready ? h->lcp_sum : 0;
+  return FMX_OK;
+}
+
+// LCPCreator.create (bwtmerger.scala:558-652): big-endian int32, LCP[r] at byte 4 r, slots 0 .. n - 2 (the loop never
+// writes slot n - 1): 4 (n - 1) bytes.
+int fmx_write_lcp(const fmx_index *idx, const char *path) {
+  if (!idx || !path) return arg_fail("null argument");
+  const Index *h = H(idx);
+  int rc = lcp_check(h);
+  if (rc) return rc;
+  if ((rc = use_device(h))) return rc;
+  if ((rc = lcp_ready(h, nullptr))) return rc;
+  FILE *f = std::fopen(path, "wb");
+  if (!f) { g_err = std::string("cannot create ") + path; return FMX_ERR_IO; }
+  std::unique_ptr<FILE, int (*)(FILE *)> guard(f, std::fclose);
+  const uint64_t entries = h->n - 1, chunk = 16u << 20;
+  std::vector<uint32_t> buf((size_t)std::min<uint64_t>(chunk, entries));
+  for (uint64_t o = 0; o < entries; o += chunk) {
+    const size_t len = (size_t)std::min<uint64_t>(chunk, entries - o);
+    HIP_TRY(hipMemcpy(buf.data(), static_cast<const uint32_t *>(h->d_lcp) + o, len * 4, hipMemcpyDeviceToHost), "D2H(lcp)");
+    for (size_t i = 0; i < len; i++) buf[i] = __builtin_bswap32(buf[i]);
+    if (std::fwrite(buf.data(), 4, len, f) != len) { g_err = "short write"; return FMX_ERR_IO; }
+  }
+  return FMX_OK;
+}
+
+int fmx_lcp_last_phases(double *phi_ms, double *plcp_ms, double *gather_ms) {
+  if (phi_ms) *phi_ms = g_lcp_phases[0];
+  if (plcp_ms) *plcp_ms = g_lcp_phases[1];
+  if (gather_ms) *gather_ms = g_lcp_phases[2];
+  return FMX_OK;
+}
+
 // ---------------------------------------------------------------- construction from text (fmx_sufsort.hip)
 static constexpr uint64_t kMaxTextLen = 0xfffffffeull;       // 2^32 - 2: len + 1 suffixes fit u32
 
@@ -1471,6 +1594,81 @@ int fmx_bwt_from_text_dev(const void *d_text, uint64_t len, void *d_bwt, void *d
   hipStream_t st = (hipStream_t)stream;
   if ((rc = not_capturing(st))) return rc;
   return sufsort_bwt(d_text, len, d_bwt, d_sa_or_null, eof, counts, st, 0);
+}
+
+// The LCP array without a handle: s = reverse(text) + sentinel on the device, then the core (fmx_lcp.hip).
+static int lcp_from_device_text(const void *d_text, uint64_t len, const void *d_sa, void *d_lcp, int device, hipStream_t st,
+                                uint64_t extra) {
+  const uint64_t n = len + 1;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
+  const uint64_t need = lcp_text_bytes(n) + lcp_core_bytes(n) + extra;
+  if (need > free_b) {
+    g_err = "the LCP array of " + std::to_string(len) + " bytes needs " + std::to_string(need) + " bytes of device memory, " +
+            std::to_string((unsigned long long)free_b) + " are free";
+    return FMX_ERR_NOMEM;
+  }
+  struct Buf {
+    void *p = nullptr;
+    ~Buf() { if (p) (void)hipFree(p); }
+  } s;
+  hipError_t e = hipMalloc(&s.p, lcp_text_bytes(n));
+  if (e != hipSuccess) { g_err = std::string("hipMalloc(LCP): ") + hipGetErrorString(e); return FMX_ERR_NOMEM; }
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
+  lcp_reverse_text(static_cast<const uint8_t *>(d_text), len, static_cast<uint8_t *>(s.p), cus, st);
+  HIP_TRY(hipGetLastError(), "k_lcp_reverse");
+  LcpInfo info;
+  const int rc = lcp_core(static_cast<const uint8_t *>(s.p), n, static_cast<const uint32_t *>(d_sa), static_cast<uint32_t *>(d_lcp), cus, st,
+                          &info);
+  if (rc) return rc;
+  for (int i = 0; i < 3; i++) g_lcp_phases[i] = info.phase_ms[i];
+  return FMX_OK;
+}
+
+int fmx_lcp_from_text_dev(const void *d_text, uint64_t len, const void *d_sa, void *d_lcp, int device, void *stream) {
+  if (!d_text || !d_sa || !d_lcp) return arg_fail("null argument");
+  int rc = text_args(d_text, len, nullptr);
+  if (rc) return rc;
+  if ((rc = use_text_device(device))) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = not_capturing(st))) return rc;
+  return lcp_from_device_text(d_text, len, d_sa, d_lcp, device, st, 0);
+}
+
+int fmx_lcp_from_text(const uint8_t *text, uint64_t len, uint32_t *lcp, int device) {
+  if (!text || !lcp) return arg_fail("null argument");
+  int rc = text_args(text, len, text);
+  if (rc) return rc;
+  if ((rc = use_text_device(device))) return rc;
+  const uint64_t n = len + 1;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
+  // the sort's temporaries are gone when the LCP's come; text, BWT / LCP (one buffer, 4 n) and the suffix array stay throughout
+  const uint64_t need = len + 4 * n + 4 * n + std::max<uint64_t>(sufsort_peak_bytes(len, true), lcp_text_bytes(n) + lcp_core_bytes(n));
+  if (need > free_b) {
+    g_err = "suffix sort and LCP array of " + std::to_string(len) + " bytes need " + std::to_string(need) + " bytes of device memory, " +
+            std::to_string((unsigned long long)free_b) + " are free";
+    return FMX_ERR_NOMEM;
+  }
+  struct Bufs {
+    void *text = nullptr, *sa = nullptr, *out = nullptr;
+    ~Bufs() { if (text) (void)hipFree(text); if (sa) (void)hipFree(sa); if (out) (void)hipFree(out); }
+  } b;
+  StreamGuard own;
+  HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
+  hipError_t e = hipMalloc(&b.text, len);
+  if (e == hipSuccess) e = hipMalloc(&b.sa, 4 * n);
+  if (e == hipSuccess) e = hipMalloc(&b.out, 4 * n);          // the BWT first (n bytes of it), then the LCP array
+  if (e != hipSuccess) { g_err = std::string("hipMalloc(text, sa, lcp): ") + hipGetErrorString(e); return FMX_ERR_NOMEM; }
+  HIP_TRY(hipMemcpyAsync(b.text, text, len, hipMemcpyHostToDevice, own.s), "H2D(text)");
+  uint64_t eof = 0;
+  int64_t counts[256];
+  if ((rc = sufsort_bwt(b.text, len, b.out, b.sa, &eof, counts, own.s, 0))) return rc;
+  if ((rc = lcp_from_device_text(b.text, len, b.sa, b.out, device, own.s, 0))) return rc;
+  HIP_TRY(hipMemcpyAsync(lcp, b.out, 4 * n, hipMemcpyDeviceToHost, own.s), "D2H(lcp)");
+  HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
+  return FMX_OK;
 }
 
 int fmx_open_text(const uint8_t *text, uint64_t len, int device, fmx_index **out) {

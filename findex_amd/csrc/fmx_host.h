@@ -172,6 +172,15 @@ struct Index {
   mutable bool loc_wide = false;
   mutable uint64_t loc_bytes = 0;
   mutable double loc_build_ms = 0.0;
+  // LCP array (fmx_lcp.hip), built by fmx_prepare(FMX_PREPARE_LCP) or the first LCP call; u32[n], outside the table
+  // budget like the locate samples
+  mutable std::mutex lcp_mu;
+  mutable bool lcp_ready = false;
+  mutable void *d_lcp = nullptr;
+  mutable uint64_t lcp_bytes = 0;
+  mutable double lcp_build_ms = 0.0;
+  mutable uint32_t lcp_max = 0;                 // the largest entry, the first row that holds it, the sum of all entries
+  mutable uint64_t lcp_max_row = 0, lcp_sum = 0;
   mutable uint64_t launches = 0;
   mutable double last_kernel_ms = 0.0;
   // the handle's host thread for the one-process-several-GPUs entry points (made at the first such call; fmx_hostpar.h)
@@ -223,6 +232,28 @@ uint64_t locate_write_sa_bytes(const Index *h);
 hipError_t launch_locate(const Index *h, const void *d_rows, uint64_t k, void *d_out, hipStream_t st);
 hipError_t launch_locate_intervals(const Index *h, const void *d_sp, const void *d_ep, uint64_t k, uint64_t max_per,
                                    void *d_off, void *d_pos, uint64_t cap, hipStream_t st);
+// the inversion with s and a native-endian SA as outputs (n < 2^32): d_sa[row] = SA[row], d_s[v] = s[v] for v < n - 1 and
+// the sentinel 0 at d_s[n - 1]; locate_invert_text_bytes: the device bytes of its temporaries (the outputs not counted).
+int locate_invert_text(const Index *h, hipStream_t st, uint32_t *d_sa, uint8_t *d_s);
+uint64_t locate_invert_text_bytes(const Index *h);
+
+// fmx_lcp.hip: the LCP array.  lcp_core: LCP[n] of s from s and its suffix array, all in device memory;
+// d_s is s itself (lcp_text_bytes(n) bytes: s, the sentinel 0 last, and zero padding); allocates 4 n bytes, synchronises `st`, returns an FMX_*
+// status with its message.  max / first row of the max / sum of the array come back through the pointers (may be null).
+struct LcpInfo {
+  uint32_t max = 0;
+  uint64_t max_row = 0, sum = 0;
+  float phase_ms[3] = {0, 0, 0};                // k_lcp_phi, k_lcp_plcp, k_lcp_gather: device events
+};
+uint64_t lcp_core_bytes(uint64_t n);            // device bytes lcp_core allocates
+uint64_t lcp_text_bytes(uint64_t n);            // device bytes of s with the padding the comparisons read
+int lcp_core(const uint8_t *d_s, uint64_t n, const uint32_t *d_sa, uint32_t *d_lcp, int cu_count, hipStream_t st, LcpInfo *info);
+void lcp_reverse_text(const uint8_t *d_text, uint64_t len, uint8_t *d_s, int cu_count, hipStream_t st);   // s = reverse(text) + 0
+int lcp_check(const Index *h);                  // FMX_ERR_UNSUPPORTED for handles that have no LCP array
+int lcp_prepare(const Index *h, hipStream_t st);   // builds the handle's array under lcp_mu (allocates, synchronises `st`)
+void lcp_drop(Index *h);
+hipError_t launch_lcp_gather(const Index *h, const void *d_rows, uint64_t k, void *d_out, hipStream_t st);
+
 // fmx_search.hip: the residency census of the k_search4 instantiation this handle's full-size searches use now, taken with
 // calibration launches on `st` (synchronises it): fmx_prepare's last step, never a _dev call's.
 hipError_t search_calibrate(const Index *h, hipStream_t st);

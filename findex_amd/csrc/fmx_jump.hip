@@ -433,6 +433,7 @@ int drop_tables(Index *h, unsigned what) {
     h->d_row1 = nullptr; h->row1_bytes = 0; h->r1_ready = false;
   }
   if (what & 32u) locate_drop(h);     // the locate samples (FMX_PREPARE_LOCATE)
+  if (what & 64u) lcp_drop(h);        // the LCP array (FMX_PREPARE_LCP)
   return 0;
 }
 

@@ -164,11 +164,13 @@ __global__ __launch_bounds__(kLocThreads) void k_inv_rank_round(const uint32_t *
 // ---------------------------------------------------------------- pass 2: every row with its SA
 // Segment q: rows starts[q], LF starts[q], ... (dist[q] of them) with SA D[q] - 1, D[q] - 2, ...  The row of every SA
 // value v with v % rate == 0 goes to tmp[v / rate]; with sa_be set instead, every row's SA goes there as a big-endian
-// u32 (the X.sa file, rate 1).
-template <bool WIDE, uint32_t LAYOUT>
+// u32 (the X.sa file, rate 1).  TEXT (the LCP array's build, fmx_lcp.hip): every row's SA goes to sa_ne as a native u32
+// and the row's BWT byte, which is s[SA - 1], to s_out -- the inversion walks s backwards, so it can write it down.
+template <bool WIDE, uint32_t LAYOUT, bool TEXT>
 __global__ __launch_bounds__(kLocThreads) void k_inv_fill(DevIndex ix, const uint64_t *__restrict__ starts, uint64_t S,
                                                          const uint64_t *__restrict__ dist, const uint64_t *__restrict__ D,
-                                                         uint32_t rate, uint64_t *__restrict__ tmp, uint32_t *__restrict__ sa_be) {
+                                                         uint32_t rate, uint64_t *__restrict__ tmp, uint32_t *__restrict__ sa_be,
+                                                         uint32_t *__restrict__ sa_ne, uint8_t *__restrict__ s_out) {
   __shared__ LocTables tb;
   loc_stage(ix, tb);
   constexpr int G = Lay<LAYOUT>::G;
@@ -192,7 +194,10 @@ __global__ __launch_bounds__(kLocThreads) void k_inv_fill(DevIndex ix, const uin
 #pragma unroll
       for (int j = 0; j < 2; j++)
         if (act[j] && lc.t == 0) {
-          if (sa_be) sa_be[r[j]] = __builtin_bswap32((uint32_t)v[j]);
+          if (TEXT) {
+            sa_ne[r[j]] = (uint32_t)v[j];
+            if (v[j] > 0 && v[j] < ix.n) s_out[v[j] - 1] = ix.bwt[r[j]];
+          } else if (sa_be) sa_be[r[j]] = __builtin_bswap32((uint32_t)v[j]);
           else if (ph[j] == 0) tmp[v[j] / rate] = r[j];
         }
       bool mv[2];
@@ -503,7 +508,8 @@ static uint64_t sample_bytes(uint64_t n, uint32_t rate) {
 static int loc_hip(hipError_t e, const char *what) { return hip_fail(e, what); }
 
 // The inversion: every segment's SA, then pass 2 into tmp (rate != 0) or into sa_be (X.sa).  Synchronises `st`.
-static int invert(const Index *h, hipStream_t st, LocMem &mem, uint32_t rate, uint64_t *tmp, uint32_t *sa_be) {
+static int invert(const Index *h, hipStream_t st, LocMem &mem, uint32_t rate, uint64_t *tmp, uint32_t *sa_be,
+                  uint32_t *sa_ne = nullptr, uint8_t *s_out = nullptr) {
   const uint64_t n = h->n;
   uint64_t target;
   uint32_t thresh;
@@ -572,9 +578,15 @@ static int invert(const Index *h, hipStream_t st, LocMem &mem, uint32_t rate, ui
     return FMX_ERR_FORMAT;
   }
   // pass 2
-#define FILL(W, L)                                                                                         \
-  k_inv_fill<W, L><<<loc_grid(h, S, kLocThreads / Lay<L>::G), kLocThreads, 0, st>>>(h->dev, d_starts, S, d_dist, D0, \
-                                                                                    rate ? rate : 1u, tmp, sa_be)
+#define FILL(W, L)                                                                                                      \
+  do {                                                                                                                  \
+    if (sa_ne)                                                                                                          \
+      k_inv_fill<W, L, true><<<loc_grid(h, S, kLocThreads / Lay<L>::G), kLocThreads, 0, st>>>(h->dev, d_starts, S, d_dist, D0, \
+                                                                                              1u, nullptr, nullptr, sa_ne, s_out); \
+    else                                                                                                                \
+      k_inv_fill<W, L, false><<<loc_grid(h, S, kLocThreads / Lay<L>::G), kLocThreads, 0, st>>>(h->dev, d_starts, S, d_dist, D0, \
+                                                                                               rate ? rate : 1u, tmp, sa_be, nullptr, nullptr); \
+  } while (0)
   FMX_LAYOUT_DISPATCH(h, FILL);
 #undef FILL
   if ((e = hipGetLastError()) != hipSuccess) return loc_hip(e, "k_inv_fill");
@@ -699,6 +711,17 @@ int locate_write_sa(const Index *h, hipStream_t st, uint32_t *d_sa_be) {
 }
 
 uint64_t locate_write_sa_bytes(const Index *h) { return inv_temp_bytes(h->n, 0) + h->n * 4; }
+
+// The LCP array's inputs (fmx_lcp.hip): d_sa[row] = SA[row] and d_s[v] = s[v] for v < n - 1; the caller has zeroed d_s, so
+// the sentinel s[n - 1] = 0 is there already.
+int locate_invert_text(const Index *h, hipStream_t st, uint32_t *d_sa, uint8_t *d_s) {
+  int rc = loc_supported(h);
+  if (rc) return rc;
+  LocMem mem;
+  return invert(h, st, mem, 0, nullptr, nullptr, d_sa, d_s);
+}
+
+uint64_t locate_invert_text_bytes(const Index *h) { return inv_temp_bytes(h->n, 0); }
 
 static LocDev loc_dev(const Index *h) {
   LocDev ld;

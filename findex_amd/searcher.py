@@ -290,6 +290,42 @@ class HipFMSearcher:
         """SACreator.create (bwtmerger.scala:535-556): write the reference's X.sa (n big-endian int32)."""
         _lib.check(self._L.fmx_write_sa(self._h, str(path).encode()))
 
+    # ---- LCP: LCPSuffixWalkingAlgo.getLCP (findex.scala:59-62), LCPLoader / LCPCreator (bwtmerger.scala:176-211,558-652)
+    def getLCP(self, i):
+        """LCPSuffixWalkingAlgo.getLCP(i): the longest common prefix of the suffixes of rows i and i + 1 (0 for the last row)."""
+        return int(self.lcp([int(i)])[0])
+
+    def lcp(self, rows=None):
+        """fmx_lcp_batch: LCP[row] for each row (uint32); rows=None: the whole array (fmx_lcp_range, LCPLoader.readAll)."""
+        if rows is None:
+            out = np.zeros(self.n, dtype=np.uint32)
+            _lib.check(self._L.fmx_lcp_range(self._h, 0, self.n, _ptr(out)))
+            return out
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        out = np.zeros(rows.size, dtype=np.uint32)
+        _lib.check(self._L.fmx_lcp_batch(self._h, _ptr(rows), rows.size, _ptr(out)))
+        return out
+
+    def lcp_dev(self, d_rows, k, d_out, stream=0):
+        """fmx_lcp_batch_dev: device pointers (u64 rows, u32 out); a row >= n gets UINT32_MAX."""
+        _lib.check(self._L.fmx_lcp_batch_dev(self._h, _dp(d_rows), int(k), _dp(d_out), _dp(stream)))
+
+    def lcp_range_dev(self, first, count, d_out, stream=0):
+        """fmx_lcp_range_dev: LCP[first .. first + count) into device memory (u32)."""
+        _lib.check(self._L.fmx_lcp_range_dev(self._h, int(first), int(count), _dp(d_out), _dp(stream)))
+
+    def lcp_info(self):
+        """fmx_lcp_info: (device bytes, build ms, largest entry, the first row that holds it, sum of all entries); 0 bytes
+        when the array is not built."""
+        nbytes, ms, mx, row, total = ctypes.c_uint64(), ctypes.c_double(), ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_uint64()
+        _lib.check(self._L.fmx_lcp_info(self._h, ctypes.byref(nbytes), ctypes.byref(ms), ctypes.byref(mx), ctypes.byref(row),
+                                        ctypes.byref(total)))
+        return int(nbytes.value), float(ms.value), int(mx.value), int(row.value), int(total.value)
+
+    def write_lcp(self, path):
+        """LCPCreator.create (bwtmerger.scala:558-652): write the reference's X.lcp (n - 1 big-endian int32)."""
+        _lib.check(self._L.fmx_write_lcp(self._h, str(path).encode()))
+
     # ---- batched forms (host arrays in, host arrays out)
     def occ_batch(self, c, i):
         c = np.ascontiguousarray(c, dtype=np.uint8)
@@ -435,23 +471,24 @@ class HipFMSearcher:
                                                _ptr(ranks), ctypes.byref(done)))
         return ranks[: text.size], int(done.value)
 
-    def prepare(self, ktab=True, select=False, jump=False, frontier=False, search=False, budget_bytes=0, locate=False):
+    def prepare(self, ktab=True, select=False, jump=False, frontier=False, search=False, budget_bytes=0, locate=False,
+                lcp=False):
         """fmx_prepare[_ex]: build the k-mer jump table / the select directory / the literal search's row tables (J, R3) / the
-        regex frontier's row table / the locate samples now instead of at the threshold or at first use, and calibrate the
+        regex frontier's row table / the locate samples / the LCP array now instead of at the threshold or at first use, and calibrate the
         search kernel they select (`search` alone: only that).  budget_bytes != 0: the handle's "table_budget" first
         (fmx_prepare_ex)."""
         what = (1 if ktab else 0) | (2 if select else 0) | (4 if jump else 0) | (8 if frontier else 0) | (16 if search else 0) \
-            | (32 if locate else 0)
+            | (32 if locate else 0) | (64 if lcp else 0)
         if budget_bytes:
             _lib.check(self._L.fmx_prepare_ex(self._h, what, int(budget_bytes)))
         else:
             _lib.check(self._L.fmx_prepare(self._h, what))
 
-    def drop_tables(self, jump=True, frontier=True, ktab=False, locate=False):
+    def drop_tables(self, jump=True, frontier=True, ktab=False, locate=False, lcp=False):
         """fmx_drop_tables: free the row jump table and the three-step row table / the frontier's row table / the k-mer table /
-        the locate samples."""
+        the locate samples / the LCP array."""
         _lib.check(self._L.fmx_drop_tables(self._h, (4 if jump else 0) | (8 if frontier else 0) | (1 if ktab else 0)
-                                           | (32 if locate else 0)))
+                                           | (32 if locate else 0) | (64 if lcp else 0)))
 
     def config_set(self, key, value):
         """fmx_index_config_set: this handle's own table policy ("ktab", "jump", "jump_pairs", "search_lanes", "jump_chars", "tables_after",

@@ -208,12 +208,13 @@ int fmx_index_config_set(fmx_index *idx, const char *key, const char *value);
  * the rank dictionary, with the same results.  The time spent is reported as fmx_stats_t.tables_build_ms.
  * fmx_prepare_ex: the same under a budget -- budget_bytes != 0 becomes the handle's "table_budget" first. */
 enum { FMX_PREPARE_KTAB = 1, FMX_PREPARE_SELECT = 2, FMX_PREPARE_JUMP = 4, FMX_PREPARE_FRONTIER = 8, FMX_PREPARE_SEARCH = 16,
-       FMX_PREPARE_LOCATE = 32 /* the locate samples (fmx_locate_batch below); fmx_drop_tables frees them */ };
+       FMX_PREPARE_LOCATE = 32 /* the locate samples (fmx_locate_batch below); fmx_drop_tables frees them */,
+       FMX_PREPARE_LCP = 64 /* the LCP array (fmx_lcp_batch below); fmx_drop_tables frees it */ };
 int fmx_prepare(const fmx_index *idx, unsigned what);
 int fmx_prepare_ex(fmx_index *idx, unsigned what, uint64_t budget_bytes);
-/* Frees derived tables again (what = FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_LOCATE in any
- * combination: the k-mer table / the row jump table and the three-step row table, 16-32 n + 8 n bytes / the frontier's row
- * table, 8 n bytes / the locate samples) and forgets the handle's pattern count, so that they come back only by fmx_prepare or when the threshold is met
+/* Frees derived tables again (what = FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_LOCATE |
+ * FMX_PREPARE_LCP in any combination: the k-mer table / the row jump table and the three-step row table, 16-32 n + 8 n bytes /
+ * the frontier's row table, 8 n bytes / the locate samples / the LCP array, 4 n bytes) and forgets the handle's pattern count, so that they come back only by fmx_prepare or when the threshold is met
  * anew (under the handle's policy as it is then).  No other call may be using the handle. */
 int fmx_drop_tables(fmx_index *idx, unsigned what);
 
@@ -395,6 +396,48 @@ int fmx_locate_intervals_dev(const fmx_index *idx, const void *d_sp, const void 
                              void *d_out_off, void *d_out_pos, size_t cap, void *stream);
 int fmx_locate_info(const fmx_index *idx, uint32_t *rate, uint64_t *bytes, double *build_ms);
 int fmx_write_sa(const fmx_index *idx, const char *path);
+
+/* ---- LCP: LCPSuffixWalkingAlgo.getLCP (findex.scala:59-62) over the X.lcp that LCPCreator.create (bwtmerger.scala:558-652)
+ * writes and LCPLoader (:176-211) reads; Util.bwtFm2LCP (util.scala:153-212) is the same over in-memory arrays.
+ * Definitions: s, n and SA as for locate.  LCP[r] = length of the longest common prefix of the suffixes of rows r and r + 1
+ * for r < n - 1, LCP[n - 1] = 0: a row is paired with the row BELOW it (the reference's convention, not the textbooks').
+ * The sentinel is unique, so LCP[0] = 0 and no comparison runs past the end of s.
+ * The array is built on the device from s and its suffix array (successor array, a pass in text order that
+ * carries the match length from one position to the next, a gather back into row order).  Like construction the builds
+ * ALLOCATE AND SYNCHRONISE (FMX_ERR_HIP under a stream capture), check their need against the free HBM first
+ * (FMX_ERR_NOMEM with the need in the message) and free every temporary on every path.  Inputs with long repeats (a run of
+ * one letter) are correct and terminate; they are not fast.
+ * fmx_lcp_from_text_dev : no handle.  d_text = the text (len bytes), d_sa = the suffix array of s as fmx_bwt_from_text_dev
+ *                         leaves it in d_sa_or_null (u32[len + 1]), d_lcp = u32[len + 1] out.  1 <= len <= 2^32 - 2.  Peak
+ *                         device memory 5 (len + 1) bytes beside the caller's three arrays.  Every index read from d_sa is
+ *                         clamped below n: a d_sa that is no suffix array gives unspecified values, never a wild access.
+ * fmx_lcp_from_text     : host text in, host lcp[len + 1] out: the suffix sort of fmx_bwt_from_text_dev, then the above.
+ * A handle (fmx_open of .bwt/.aux has neither text nor suffix array) gets both from the inversion that builds the locate
+ * samples, then runs the same core.  It keeps u32 LCP[n], 4 n bytes, outside the table budget: built by
+ * fmx_prepare(FMX_PREPARE_LCP) or else by the first call below that needs it, freed by fmx_drop_tables(FMX_PREPARE_LCP) and
+ * fmx_close.  fmx_open_block handles and n >= 2^32 get FMX_ERR_UNSUPPORTED; an index that is not the BWT of one text
+ * FMX_ERR_FORMAT (as locate).
+ * fmx_lcp_batch     : getLCP(i) / LCPLoader.read(i) for k rows: out[q] = LCP[rows[q]]; FMX_ERR_ARG for a row >= n.
+ * fmx_lcp_batch_dev : the same on device pointers (u64 rows, u32 out); a row >= n gets UINT32_MAX.  With the array prepared
+ *                     it only enqueues (safe inside a stream capture).
+ * fmx_lcp_range[_dev] : LCPLoader.readAll's slice: out[t] = LCP[first + t], first + count <= n (FMX_ERR_ARG otherwise); the
+ *                     device form is one device-to-device copy and, with the array prepared, only enqueues.
+ * fmx_lcp_info      : device bytes of the array (0: not built), its build time (ms), the largest entry, the FIRST row that
+ *                     holds it and the sum of all entries; any pointer may be NULL.
+ * fmx_write_lcp     : LCPCreator's X.lcp: no header, big-endian int32, LCP[r] at byte 4 r for r = 0 .. n - 2 -- n - 1
+ *                     entries, 4 (n - 1) bytes, as the reference's loop writes it (it never writes slot n - 1).
+ * fmx_lcp_last_phases : device time (ms) the calling thread's last array build spent in its three phases (successor array,
+ *                     text-order pass, gather): what tools/lcp_bench.py reports. */
+int fmx_lcp_from_text_dev(const void *d_text, uint64_t len, const void *d_sa, void *d_lcp, int device, void *stream);
+int fmx_lcp_from_text(const uint8_t *text, uint64_t len, uint32_t *lcp, int device);
+int fmx_lcp_batch(const fmx_index *idx, const uint64_t *rows, size_t k, uint32_t *out);
+int fmx_lcp_batch_dev(const fmx_index *idx, const void *d_rows, size_t k, void *d_out, void *stream);
+int fmx_lcp_range(const fmx_index *idx, uint64_t first, uint64_t count, uint32_t *out);
+int fmx_lcp_range_dev(const fmx_index *idx, uint64_t first, uint64_t count, void *d_out, void *stream);
+int fmx_lcp_info(const fmx_index *idx, uint64_t *bytes, double *build_ms, uint32_t *max_lcp, uint64_t *max_row,
+                 uint64_t *sum_lcp);
+int fmx_write_lcp(const fmx_index *idx, const char *path);
+int fmx_lcp_last_phases(double *phi_ms, double *plcp_ms, double *gather_ms);
 
 /* ---- regex: REParser.re2post (re2/re2.scala:50-185) + ReTree.apply (re2/retree.scala:156-370).
  * Bytes of `re` are Latin-1 characters.  FMX_ERR_SYNTAX / FMX_ERR_MATCH mirror the reference's
