@@ -807,12 +807,18 @@ int fmx_lf_walk_batch_dev(const fmx_index *idx, const void *d_rows, size_t k, ui
   return FMX_OK;
 }
 
+// A Psi launch that found the select directory missing on a capturing stream has recorded its own message
+// (ensure_select, fmx_select.hip): keep it.
+static int select_status(hipError_t e, const char *what) {
+  if (e == hipSuccess) return FMX_OK;
+  return e == hipErrorStreamCaptureUnsupported ? FMX_ERR_HIP : hip_fail(e, what);
+}
+
 int fmx_psi_batch_dev(const fmx_index *idx, const void *d_rows, void *d_out, size_t k, void *stream) {
   if (!idx || (k && (!d_rows || !d_out))) return arg_fail("null argument");
   int rc = use_device(H(idx));
   if (rc) return rc;
-  HIP_TRY(launch_psi(H(idx), d_rows, d_out, k, (hipStream_t)stream), "k_psi");
-  return FMX_OK;
+  return select_status(launch_psi(H(idx), d_rows, d_out, k, (hipStream_t)stream), "k_psi");
 }
 
 int fmx_next_substr_batch_dev(const fmx_index *idx, const void *d_rows, size_t k, uint32_t len, void *d_out,
@@ -820,8 +826,7 @@ int fmx_next_substr_batch_dev(const fmx_index *idx, const void *d_rows, size_t k
   if (!idx || (k && (!d_rows || !d_out_len || (len && !d_out)))) return arg_fail("null argument");
   int rc = use_device(H(idx));
   if (rc) return rc;
-  HIP_TRY(launch_next_substr(H(idx), d_rows, k, len, d_out, d_out_len, (hipStream_t)stream), "k_next_substr");
-  return FMX_OK;
+  return select_status(launch_next_substr(H(idx), d_rows, k, len, d_out, d_out_len, (hipStream_t)stream), "k_next_substr");
 }
 
 // ---------------------------------------------------------------- host-pointer entry points

@@ -223,10 +223,19 @@ __global__ __launch_bounds__(kSelThreads) void k_next_substr(DevIndex ix, SelDir
 
 // ---------------------------------------------------------------- host side
 // Builds the directory on first use (most handles never extract text; C3's costs 4 GiB and a pass over the block
-// headers).  Guarded by the handle's mutex; the pointers never change afterwards.
+// headers).  Guarded by the handle's mutex; the pointers never change afterwards.  The build allocates and synchronises
+// `st`, so it is refused while `st` is capturing (as the locate samples and the LCP array are): the message is recorded
+// here and hipErrorStreamCaptureUnsupported tells the entry point to keep it.  A build that fails leaves nothing allocated.
 static hipError_t ensure_select(const Index *h, hipStream_t st, SelDir *out) {
   std::lock_guard<std::mutex> lk(h->sel_mu);
   if (!h->sel_ready) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    hipError_t ec = hipStreamIsCapturing(st, &cs);
+    if (ec != hipSuccess) return ec;
+    if (cs != hipStreamCaptureStatusNone) {
+      set_error("the select directory is built by fmx_prepare(FMX_PREPARE_SELECT) or a first Psi / nextSubstr call outside a stream capture");
+      return hipErrorStreamCaptureUnsupported;
+    }
     const auto t_build = std::chrono::steady_clock::now();
     std::vector<uint64_t> off(h->nslots + 1, 0), totals(h->nslots ? h->nslots : 1, 0);
     std::vector<uint8_t> shift(h->nslots ? h->nslots : 1, 0);
@@ -261,7 +270,13 @@ static hipError_t ensure_select(const Index *h, hipStream_t st, SelDir *out) {
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);           // the host vectors go out of scope
     if (d_tot) (void)hipFree(d_tot);
-    if (e != hipSuccess) return e;
+    if (e != hipSuccess) {
+      for (void **p : {&h->d_sel_dir, &h->d_sel_off, &h->d_sel_shift}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+      }
+      return e;
+    }
     h->sel_bytes = entries * 4;
     tables_account(h, (int64_t)h->sel_bytes);      // (Psi cannot do without it: counted against the budget, never refused by it)
     h->sel_ready = true;

@@ -227,7 +227,15 @@ int fmx_device(const fmx_index *idx, int *device);
 
 /* ---- batched rank: SuffixAlgo.occ(c,i), findex.scala:13; NaiveFMSearcher.occ bwtmerger.scala:354-375.
  * out[q] = #{p <= i[q] : BWT'[p] == c[q]}, BWT' = BWT with slot eof read as symbol 0; i = -1 gives 0;
- * i >= n is clamped to n-1 (what the binary search returns for any key past the last entry). */
+ * i >= n is clamped to n-1 (what the binary search returns for any key past the last entry).
+ * THE DEVICE FORMS BELOW CANNOT VALIDATE THEIR OPERANDS (the host forms reject them with FMX_ERR_ARG); their kernels
+ * clamp them instead, before any address is formed, so that no operand value leads outside the index:
+ *   fmx_occ_batch_dev                              : i as above;
+ *   fmx_prev_range_batch_dev                       : sp > n and ep > n are read as n (sp > ep is not an error there: the
+ *                                                    two ranks are computed independently);
+ *   fmx_lf_walk_batch_dev, fmx_psi_batch_dev,
+ *   fmx_next_substr_batch_dev                      : a row >= n is read as n-1.
+ * The answer is that of the clamped operand. */
 int fmx_occ_batch(const fmx_index *idx, const uint8_t *c, const int64_t *i, uint64_t *out, size_t k);
 int fmx_occ_batch_dev(const fmx_index *idx, const void *d_c, const void *d_i, void *d_out, size_t k, void *stream);
 
@@ -326,7 +334,11 @@ int fmx_psi_batch_dev(const fmx_index *idx, const void *d_rows, void *d_out, siz
 int fmx_next_substr_batch_dev(const fmx_index *idx, const void *d_rows, size_t k, uint32_t len, void *d_out,
                               void *d_out_len, void *stream);
 /* The first Psi / nextSubstr call on a handle builds a select directory on the device (at most ~n bytes; it is
- * counted in fmx_stats_t.index_bytes from then on). */
+ * counted in fmx_stats_t.index_bytes from then on).  The build allocates and synchronises the stream, so like the
+ * locate samples and the LCP array it happens in fmx_prepare(FMX_PREPARE_SELECT) or in a first call OUTSIDE a stream
+ * capture: without the directory, fmx_psi_batch_dev / fmx_next_substr_batch_dev on a capturing stream return
+ * FMX_ERR_HIP ("... outside a stream capture"), allocate nothing and leave the capture valid.  A build that fails
+ * frees what it had allocated. */
 int fmx_next_substr(const fmx_index *idx, uint64_t sp, uint32_t len, uint8_t *out, uint32_t *out_len);
 /* the same for k rows at once (rendering a result list): out is k*len bytes, row q's string at q*len, out_len[q]
  * bytes of it written. */

@@ -89,3 +89,51 @@ def pack_patterns(pats):
         off[i + 1] = off[i] + len(p)
     buf = np.frombuffer(b"".join(pats), dtype=np.uint8).copy() if pats and int(off[-1]) else np.zeros(0, dtype=np.uint8)
     return buf, off
+
+
+# ---------------------------------------------------------------- designed indexes (tests/test_gpu_primitives.py)
+ONEHOT_BLOCK = 448      # BWT positions per block of the one-hot layout
+BYTES_BLOCK = 128       # ... of the bytes layout
+
+
+def index_of_bwt(bwt, eof):
+    """(bwt, eof, counts) for given BWT bytes: counts exclude the filler at slot eof, as synth_bwt does it."""
+    bwt = np.ascontiguousarray(bwt, dtype=np.uint8)
+    counts = np.bincount(bwt, minlength=256).astype(np.int64)
+    counts[bwt[eof]] -= 1
+    return bwt, int(eof), counts
+
+
+def clustered_bwt(eof, n=200_000):
+    """Symbol 1 in the first and the last quarter, symbol 2 between them: every S-th occurrence of symbol 1 is sampled
+    at the density of n/2 occurrences in n rows, so the sample that spans the gap covers n/2 rows of blocks.  Symbol 200
+    at both ends and around the first one-hot block edge, symbol 7 once in the middle."""
+    bwt = np.full(n, 2, dtype=np.uint8)
+    bwt[: n // 4] = 1
+    bwt[3 * n // 4:] = 1
+    bwt[[0, 447, 448, 449, n - 1]] = 200
+    bwt[100_000] = 7
+    return index_of_bwt(bwt, eof)
+
+
+def one_symbol_bwt(n, eof=None):
+    """Density 1: every row holds symbol 97."""
+    return index_of_bwt(np.full(n, 97, dtype=np.uint8), n // 3 if eof is None else eof)
+
+
+def geometric_bwt(n=300_007, seed=5):
+    """Symbol c with probability about 2^-c, c = 1..16: densities from 1/2 down to 2^-16."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    return index_of_bwt(np.minimum(rng.geometric(0.5, size=n), 16).astype(np.uint8), n // 3)
+
+
+def sparse_alphabet_bwt(n=50_001, seed=6):
+    """Symbols {1, 3, 128, 254, 255} with absent ones between them.  1 and 128 share the rows; 254 occurs once, at the
+    first position of a block, and 255 once, at the last position of a block (multiples of 896 begin a block of both
+    sizes); 3 sits on both sides of the first block edge of either size and in the last row."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    bwt = np.where(rng.random(n) < 0.5, 1, 128).astype(np.uint8)
+    bwt[[BYTES_BLOCK - 1, BYTES_BLOCK, ONEHOT_BLOCK - 1, ONEHOT_BLOCK, n - 1]] = 3
+    bwt[896 * 5] = 254
+    bwt[896 * 20 - 1] = 255
+    return index_of_bwt(bwt, n // 3)

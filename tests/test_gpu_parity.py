@@ -1860,6 +1860,19 @@ def test_full_size_properties(log2n, extra, sigma):
     off = (np.arange(k + 1, dtype=np.uint64) * m)
     sp, ep = hip.search_batch(pats.reshape(-1), off)
     assert (sp < ep).all() and (sp <= end).all() and (end < ep).all()
+    if (log2n, extra, sigma) == (32, 12345, 16):
+        # the select kernel's 64-bit path: Psi undoes one LF step.  LF sends only ~extra of the n rows past 2^32 (the last
+        # ones of the last symbol), so random rows hardly ever land there: every row past 2^32 is asked as well, from the
+        # other side (LF undoes Psi)
+        r20 = rows[:20000]
+        _, e1 = hip.lf_walk_batch(r20, 1, want_bytes=False)
+        assert np.array_equal(hip.psi_batch(e1), r20)
+        high = np.arange(1 << 32, n, dtype=np.uint64)
+        back = hip.psi_batch(high)
+        b2, e2 = hip.lf_walk_batch(back, 1)
+        assert np.array_equal(e2, high) and bool((back < np.uint64(n)).all())
+        assert bool((b2 == sigma).all()) and bool((np.diff(back.astype(np.int64)) > 0).all())   # the last symbol's last occurrences, in order
+        assert bool((np.concatenate([e1, e2]) >= np.uint64(1 << 32)).any())
     # the oracle at the config's own size: the reference algorithm (inverted lists + binary-search occ,
     # bwtmerger.scala:354-375, findex.scala:15-31) over this very BWT, 100k+ patterns (hits, and misses made by
     # replacing one byte) and random occ / getPrevRange operands, bit for bit, executed steps included
