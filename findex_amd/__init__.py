@@ -11,6 +11,7 @@ package is the thin host-side mirror of the reference's Scala interface for that
     SAResult(sa,len,sp,ep)                         SAResult
     BWTMerger2.merge(FileBWTReader) -> X.bwt/.aux  bwt_from_text(text) + write_bwt(...), python -m findex_amd.index
     LCPSuffixWalkingAlgo.getLCP, LCPCreator        HipFMSearcher.getLCP / .lcp / .write_lcp, lcp_from_text(text)
+    DirBWTReader(dir) -> one stream, IndexerApp    Corpus.from_dir(dir), HipCorpusSearcher, python -m findex_amd.index --dir
 
 There is no CPU fallback: importing works anywhere, but every compute call needs the built
 library and a HIP device and fails loudly otherwise.
@@ -18,6 +19,7 @@ library and a HIP device and fails loudly otherwise.
 from ._lib import FmxError, MatchError, Re2PostSyntax, LIB_PATH, load  # noqa: F401
 from .searcher import HipFMSearcher  # noqa: F401
 from .construct import bwt_from_text, bwt_from_text_dev, lcp_from_text, lcp_from_text_dev, write_bwt  # noqa: F401
+from .corpus import Corpus, HipCorpusSearcher, escape, is_binary, list_files  # noqa: F401
 from .regex import DFA, NFA, REParser, ReTree, SAResult, CompiledRegexes  # noqa: F401
 
 
@@ -59,4 +61,4 @@ def config_set(key, value):
     _lib.check(_lib.load().fmx_config_set(key.encode(), str(value).encode()))
 
 
-__all__ = ["bwt_from_text", "bwt_from_text_dev", "lcp_from_text", "lcp_from_text_dev", "write_bwt", "config_set", "set_layout", "set_checkpoints", "set_ktab", "set_jump", "set_pipeline", "HipFMSearcher", "REParser", "ReTree", "SAResult", "NFA", "DFA", "CompiledRegexes", "FmxError", "MatchError", "Re2PostSyntax"]
+__all__ = ["Corpus", "HipCorpusSearcher", "escape", "is_binary", "list_files", "bwt_from_text", "bwt_from_text_dev", "lcp_from_text", "lcp_from_text_dev", "write_bwt", "config_set", "set_layout", "set_checkpoints", "set_ktab", "set_jump", "set_pipeline", "HipFMSearcher", "REParser", "ReTree", "SAResult", "NFA", "DFA", "CompiledRegexes", "FmxError", "MatchError", "Re2PostSyntax"]

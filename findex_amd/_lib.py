@@ -129,6 +129,22 @@ SYMBOLS = {
     "fmx_lcp_info": (_i32, [_vp, _P(_u64), _P(ctypes.c_double), _P(_u32), _P(_u64), _P(_u64)]),
     "fmx_write_lcp": (_i32, [_vp, _cp]),
     "fmx_lcp_last_phases": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double)]),
+    "fmx_corpus_build": (_i32, [_vp, _u64, _vp, _u64, _i32, _P(_vp)]),
+    "fmx_corpus_build_dev": (_i32, [_vp, _u64, _vp, _u64, _i32, _vp, _P(_vp)]),
+    "fmx_corpus_free": (_i32, [_vp]),
+    "fmx_corpus_info": (_i32, [_vp, _P(_u64), _P(_u64), _P(_u64), _P(_u64), _P(ctypes.c_double), _P(_u32)]),
+    "fmx_corpus_stream": (_i32, [_vp, _vp, _u64]),
+    "fmx_corpus_stream_dev": (_i32, [_vp, _P(_vp), _P(_u64)]),
+    "fmx_corpus_drop_stream": (_i32, [_vp]),
+    "fmx_corpus_open_index": (_i32, [_vp, _vp, _P(_vp)]),
+    "fmx_corpus_tables": (_i32, [_vp, _vp, _vp, _vp]),
+    "fmx_corpus_from_tables": (_i32, [_vp, _vp, _vp, _u64, _u64, _i32, _P(_vp)]),
+    "fmx_corpus_map": (_i32, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    "fmx_corpus_map_dev": (_i32, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "fmx_corpus_doc_list": (_i32, [_vp, _vp, _vp, _vp, _sz, _u64, _u64, _vp, _vp, _vp, _sz]),
+    "fmx_corpus_doc_list_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _u64, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "fmx_corpus_doc_list_phases": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double)]),
+    "fmx_corpus_escape": (_i32, [_vp, _sz, _vp, _sz, _P(_sz)]),
     "fmx_occ_host": (_i32, [_vp, _i32, ctypes.c_int64, _P(_u64)]),
     "fmx_calc_gaps_chain": (_i32, [_vp, _vp, _sz, _u64, _i32, _u64, _vp, _P(_sz)]),
     "fmx_regex_compile": (_i32, [_cp, _i32, _P(_vp)]),

@@ -1,0 +1,306 @@
+"""A directory of files as one index -- the drop-in for findex's DirBWTReader (bwtreader.scala:17-173), the input side of the
+reference's IndexerApp -- and, beyond the reference, the way back from a hit to (file, offset).
+
+The STREAM that gets indexed: the files of a directory first, then its subdirectories recursively (recursiveListFiles,
+:44-62); files that look binary dropped (Util.isBinary, util.scala:20-44); in every file raw byte 0 -> '\\' '0', raw 1 ->
+'\\' '1', raw 255 -> '\\' 'f' (:144-155; the backslash itself is NOT escaped, the reference's quirk); one separator byte 1
+after every file, the last included (:133-137).  File.listFiles has no defined order; this package fixes one: names compared
+as bytes, ascending, a directory's files before its subdirectories.
+
+Walking the tree is host work and lives here; escaping, the map and the document listing run on the device (libfmx:
+fmx_corpus_*, csrc/fmx_corpus.hip).  There is no CPU fallback."""
+import ctypes
+import os
+import struct
+
+import numpy as np
+
+from . import _lib
+from .searcher import HipFMSearcher, _dp, _ptr
+
+MAGIC = b"FMXDOCS1"
+SEPARATOR = 1
+NO_DOC = 0xFFFFFFFF
+
+
+def is_binary(path):
+    """Util.isBinary (util.scala:20-44) as DirBWTReader uses it: a 0 among the first 1024 bytes, an empty file (an empty read
+    is None, which the reader treats as binary) or a file that cannot be opened."""
+    try:
+        with open(path, "rb") as f:
+            head = f.read(1024)
+    except OSError:
+        return True
+    return not head or b"\0" in head
+
+
+def list_files(root, filter_binary=True):
+    """The files under `root` in stream order: a directory's files (names as bytes, ascending), then its subdirectories
+    (likewise) recursively.  Returns paths relative to `root`, '/'-separated, as bytes."""
+    root_b = os.fsencode(root)
+    out = []
+
+    def walk(d, rel):
+        try:
+            names = sorted(os.listdir(d))
+        except OSError:
+            return
+        dirs = []
+        for nm in names:
+            p = os.path.join(d, nm)
+            if os.path.isdir(p):
+                dirs.append(nm)
+            elif os.path.isfile(p) and not (filter_binary and is_binary(p)):
+                out.append(rel + nm)
+        for nm in dirs:
+            walk(os.path.join(d, nm), rel + nm + b"/")
+
+    walk(root_b, b"")
+    return out
+
+
+def escape(b):
+    """fmx_corpus_escape: `b` as it stands in the stream (0, 1 and 255 become two bytes each)."""
+    L = _lib.load()
+    src = np.frombuffer(bytes(b), dtype=np.uint8)
+    out = np.zeros(max(2 * src.size, 1), dtype=np.uint8)
+    n = ctypes.c_size_t()
+    _lib.check(L.fmx_corpus_escape(_ptr(src), src.size, _ptr(out), out.size, ctypes.byref(n)))
+    return out[: n.value].tobytes()
+
+
+def write_docs(path, doc_start, raw_len, esc_pos, names):
+    """X.docs, little-endian: magic FMXDOCS1; u64 n_docs, n_esc, stream_len; doc_start[n_docs + 1], raw_len[n_docs],
+    esc_pos[n_esc] as u64; name offsets [n_docs + 1] as u64; the name bytes (paths relative to the root, '/'-separated)."""
+    doc_start, raw_len, esc_pos = (np.asarray(a, dtype=np.uint64).reshape(-1) for a in (doc_start, raw_len, esc_pos))
+    names = [bytes(nm) for nm in names]
+    if doc_start.size != raw_len.size + 1 or len(names) != raw_len.size or raw_len.size < 1:
+        raise ValueError("doc_start, raw_len and names disagree about the number of documents")
+    off = np.zeros(raw_len.size + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(nm) for nm in names])
+    with open(path, "wb") as f:
+        f.write(MAGIC + struct.pack("<QQQ", raw_len.size, esc_pos.size, int(doc_start[-1])))
+        for a in (doc_start, raw_len, esc_pos, off):
+            f.write(a.astype("<u8").tobytes())
+        f.write(b"".join(names))
+
+
+def read_docs(path):
+    """(doc_start, raw_len, esc_pos, names) of an X.docs file; ValueError for a wrong magic or a truncated file."""
+    with open(path, "rb") as f:
+        blob = f.read()
+    if len(blob) < 32 or blob[:8] != MAGIC:
+        raise ValueError("%s: not an FMXDOCS1 file" % path)
+    n_docs, n_esc, stream_len = struct.unpack_from("<QQQ", blob, 8)
+    words = (n_docs + 1) + n_docs + n_esc + (n_docs + 1)
+    if n_docs < 1 or len(blob) < 32 + 8 * words:
+        raise ValueError("%s: truncated (%d documents, %d escapes need %d bytes of tables)" % (path, n_docs, n_esc, 8 * words))
+    a = np.frombuffer(blob, dtype="<u8", count=words, offset=32).astype(np.uint64)
+    doc_start, raw_len = a[: n_docs + 1], a[n_docs + 1: 2 * n_docs + 1]
+    esc_pos, name_off = a[2 * n_docs + 1: 2 * n_docs + 1 + n_esc], a[2 * n_docs + 1 + n_esc:]
+    names_at = 32 + 8 * words
+    if int(name_off[0]) != 0 or np.any(np.diff(name_off.astype(np.int64)) < 0) or len(blob) != names_at + int(name_off[-1]):
+        raise ValueError("%s: truncated or trailing bytes (the name table does not end with the file)" % path)
+    if int(doc_start[-1]) != stream_len:
+        raise ValueError("%s: doc_start does not end at the stream length" % path)
+    names = [blob[names_at + int(name_off[d]): names_at + int(name_off[d + 1])] for d in range(n_docs)]
+    return doc_start, raw_len, esc_pos, names
+
+
+class Corpus:
+    """fmx_corpus: the stream of a list of documents in HBM (until drop_stream) and the map from stream positions to
+    (document, offset).  `names[d]` is document d's path relative to the root, as bytes."""
+
+    def __init__(self, handle, names, device=0):
+        self._L = _lib.load()
+        self._c = handle
+        self.names = list(names)
+        self.device = int(device)
+        self.n_docs, self.stream_len, self.n_esc = self.info()[:3]
+        if len(self.names) != self.n_docs:
+            raise ValueError("%d names for %d documents" % (len(self.names), self.n_docs))
+
+    # ---- constructors
+    @classmethod
+    def from_documents(cls, docs, names=None, device=0):
+        """fmx_corpus_build over the given raw documents (a list of bytes), in their order."""
+        L = _lib.load()
+        docs = [bytes(d) for d in docs]
+        raw = np.frombuffer(b"".join(docs), dtype=np.uint8)
+        ends = np.cumsum([len(d) for d in docs], dtype=np.uint64) if docs else np.zeros(0, dtype=np.uint64)
+        h = ctypes.c_void_p()
+        _lib.check(L.fmx_corpus_build(_ptr(raw), raw.size, _ptr(ends), ends.size, int(device), ctypes.byref(h)))
+        return cls(h, names if names is not None else [b"%d" % d for d in range(len(docs))], device)
+
+    @classmethod
+    def from_dir(cls, root, filter_binary=True, device=0):
+        """DirBWTReader over `root`: list_files, read, build.  A file that vanishes or cannot be read between the listing and
+        the read is dropped like one that cannot be opened."""
+        names, docs = [], []
+        for rel in list_files(root, filter_binary=filter_binary):
+            try:
+                with open(os.path.join(os.fsencode(root), *rel.split(b"/")), "rb") as f:
+                    docs.append(f.read())
+                names.append(rel)
+            except OSError:
+                continue
+        if not docs:
+            raise ValueError("%s: no files to index" % (root,))
+        return cls.from_documents(docs, names, device)
+
+    @classmethod
+    def load(cls, path, device=0):
+        """The map alone from an X.docs side file (fmx_corpus_from_tables): no stream, so no build_index."""
+        L = _lib.load()
+        doc_start, raw_len, esc_pos, names = read_docs(path)
+        h = ctypes.c_void_p()
+        _lib.check(L.fmx_corpus_from_tables(_ptr(doc_start), _ptr(raw_len), _ptr(esc_pos), raw_len.size, esc_pos.size,
+                                            int(device), ctypes.byref(h)))
+        return cls(h, names, device)
+
+    def close(self):
+        if getattr(self, "_c", None):
+            self._L.fmx_corpus_free(self._c)
+            self._c = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._c
+
+    # ---- what it holds
+    def info(self):
+        """fmx_corpus_info: (n_docs, stream_len, n_esc, device bytes, build ms, tile bytes)."""
+        a, b, c, d = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        ms, tile = ctypes.c_double(), ctypes.c_uint32()
+        _lib.check(self._L.fmx_corpus_info(self._c, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d),
+                                           ctypes.byref(ms), ctypes.byref(tile)))
+        return int(a.value), int(b.value), int(c.value), int(d.value), float(ms.value), int(tile.value)
+
+    def stream(self):
+        """fmx_corpus_stream: the escaped stream as a uint8 array (what X.data holds)."""
+        out = np.empty(self.stream_len, dtype=np.uint8)
+        _lib.check(self._L.fmx_corpus_stream(self._c, _ptr(out), out.size))
+        return out
+
+    def stream_dev(self):
+        """fmx_corpus_stream_dev: (device pointer, length)."""
+        p, n = ctypes.c_void_p(), ctypes.c_uint64()
+        _lib.check(self._L.fmx_corpus_stream_dev(self._c, ctypes.byref(p), ctypes.byref(n)))
+        return int(p.value), int(n.value)
+
+    def drop_stream(self):
+        _lib.check(self._L.fmx_corpus_drop_stream(self._c))
+
+    def tables(self):
+        """fmx_corpus_tables: (doc_start[n_docs + 1], raw_len[n_docs], esc_pos[n_esc]) as uint64 arrays."""
+        ds = np.zeros(self.n_docs + 1, dtype=np.uint64)
+        rl = np.zeros(self.n_docs, dtype=np.uint64)
+        ep = np.zeros(self.n_esc, dtype=np.uint64)
+        _lib.check(self._L.fmx_corpus_tables(self._c, _ptr(ds), _ptr(rl), _ptr(ep)))
+        return ds, rl, ep
+
+    def build_index(self, stream=0):
+        """fmx_corpus_open_index: the stream's index, built on the device from the stream in HBM -> HipFMSearcher."""
+        h = ctypes.c_void_p()
+        _lib.check(self._L.fmx_corpus_open_index(self._c, _dp(stream), ctypes.byref(h)))
+        return HipFMSearcher(_handle=h)
+
+    def map(self, pos):
+        """fmx_corpus_map: (doc uint32, esc_off uint64, raw_off uint64) per stream position; doc = 0xFFFFFFFF at or past the
+        end of the stream."""
+        pos = np.ascontiguousarray(pos, dtype=np.uint64).reshape(-1)
+        doc = np.zeros(pos.size, dtype=np.uint32)
+        eo = np.zeros(pos.size, dtype=np.uint64)
+        ro = np.zeros(pos.size, dtype=np.uint64)
+        _lib.check(self._L.fmx_corpus_map(self._c, _ptr(pos), pos.size, _ptr(doc), _ptr(eo), _ptr(ro)))
+        return doc, eo, ro
+
+    def map_dev(self, d_pos, k, d_doc, d_esc_off, d_raw_off, stream=0):
+        """fmx_corpus_map_dev: device pointers; only enqueues."""
+        _lib.check(self._L.fmx_corpus_map_dev(self._c, _dp(d_pos), int(k), _dp(d_doc), _dp(d_esc_off), _dp(d_raw_off), _dp(stream)))
+
+    def save(self, path):
+        """X.docs (write_docs) from the device's tables."""
+        ds, rl, ep = self.tables()
+        write_docs(path, ds, rl, ep, self.names)
+
+
+class HipCorpusSearcher:
+    """A corpus and the searcher of its stream: where does q occur, in which files?"""
+
+    def __init__(self, corpus, searcher=None):
+        self.corpus = corpus
+        self.searcher = searcher if searcher is not None else corpus.build_index()
+        if self.searcher.n != corpus.stream_len + 1:
+            raise ValueError("the index has %d rows, the corpus stream %d bytes" % (self.searcher.n, corpus.stream_len))
+        self._L = _lib.load()
+
+    @classmethod
+    def open(cls, base, bigEndian=True, device=0):
+        """X.bwt / X.aux / X.docs as `python -m findex_amd.index --dir D --out X` writes them."""
+        return cls(Corpus.load(str(base) + ".docs", device=device), HipFMSearcher(str(base) + ".bwt", bigEndian=bigEndian, device=device))
+
+    def close(self):
+        self.searcher.close()
+        self.corpus.close()
+
+    def locate_docs(self, q, max_hits=None):
+        """(doc, raw_off) arrays of the occurrences of the raw bytes q, sorted by (doc, raw_off): q is escaped, its reverse
+        searched, the rows located (locate_text's arithmetic with the escaped length) and the positions mapped."""
+        pos = self.searcher.locate_text(escape(q), max_hits=max_hits)
+        doc, _, raw = self.corpus.map(pos)
+        order = np.lexsort((raw, doc))
+        return doc[order], raw[order]
+
+    def _intervals(self, queries):
+        esc = [escape(q)[::-1] for q in queries]
+        if any(not e for e in esc):
+            raise ValueError("empty pattern")
+        off = np.zeros(len(esc) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(e) for e in esc])
+        sp, ep = self.searcher.search_batch(np.frombuffer(b"".join(esc), dtype=np.uint8), off)
+        return esc, sp, ep
+
+    def list_docs(self, queries, max_per=None, cap=None):
+        """fmx_corpus_doc_list per query: the CSR triple (off[k + 1], doc[], cnt[]) -- query i occurs cnt[j] times in
+        document doc[j] for off[i] <= j < off[i + 1], documents ascending.  Queries of one escaped length share a call."""
+        queries = [bytes(q) for q in queries]
+        esc, sp, ep = self._intervals(queries)
+        lens = np.array([len(e) for e in esc], dtype=np.uint64)
+        per = [(np.zeros(0, np.uint32), np.zeros(0, np.uint32))] * len(queries)
+        for m in sorted(set(lens.tolist())):
+            sel = np.nonzero(lens == m)[0]
+            o, d, c = self._doc_list(sp[sel], ep[sel], m, max_per, cap)
+            for t, i in enumerate(sel.tolist()):
+                per[i] = (d[int(o[t]):int(o[t + 1])], c[int(o[t]):int(o[t + 1])])
+        off = np.zeros(len(queries) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([p[0].size for p in per])
+        cat = (lambda j: np.concatenate([p[j] for p in per]) if per else np.zeros(0, np.uint32))
+        return off, cat(0), cat(1)
+
+    def _doc_list(self, sp, ep, pat_len, max_per=None, cap=None):
+        sp = np.ascontiguousarray(sp, dtype=np.uint64)
+        ep = np.ascontiguousarray(ep, dtype=np.uint64)
+        if cap is None:
+            cnt = np.where(ep > sp, ep - sp, 0).astype(np.uint64)
+            if max_per is not None:
+                cnt = np.minimum(cnt, np.uint64(max_per))
+            cap = int(np.minimum(cnt, np.uint64(self.corpus.n_docs + 1)).sum())
+        off = np.zeros(sp.size + 1, dtype=np.uint64)
+        doc = np.zeros(max(cap, 1), dtype=np.uint32)
+        cnt = np.zeros(max(cap, 1), dtype=np.uint32)
+        _lib.check(self._L.fmx_corpus_doc_list(self.corpus.handle, self.searcher.handle, _ptr(sp), _ptr(ep), sp.size, int(pat_len),
+                                               int(max_per or 0), _ptr(off), _ptr(doc), _ptr(cnt), int(cap)))
+        m = min(int(cap), int(off[-1]))
+        return off, doc[:m], cnt[:m]
+
+    def count_docs(self, q):
+        """In how many documents q occurs."""
+        off, _, _ = self.list_docs([q])
+        return int(off[1])

@@ -270,6 +270,17 @@ uint64_t sufsort_peak_bytes(uint64_t len, bool sa_given);
 int sufsort_bwt(const void *d_text, uint64_t len, void *d_bwt, void *d_sa_or_null, uint64_t *eof, int64_t counts[256],
                 hipStream_t st, uint64_t extra);
 
+// fmx_sufsort.hip's scan and sort, for the other units that need one (fmx_corpus.hip).  scan_u32: in place over len u32 (sum or
+// max, inclusive or exclusive), partials = scan_partials(len) u32 of scratch.  radix_sort: m (u64 key, u32 value) pairs by the
+// key's low `bits` bits, 8 per pass; the result is in (*k, *v), the other pair of buffers is free afterwards; hist = 256 *
+// radix_tiles(m) u32, partials = scan_partials(max(m, 256 * radix_tiles(m))) u32; m < 2^32.  Both only enqueue on `st`.
+constexpr int kScanSum = 0, kScanMax = 1;
+uint64_t scan_partials(uint64_t len);
+uint64_t radix_tiles(uint64_t m);
+hipError_t scan_u32(uint32_t *d, uint64_t len, int op, bool exclusive, uint32_t *partials, hipStream_t st);
+hipError_t radix_sort(unsigned long long **k, uint32_t **v, unsigned long long **k_alt, uint32_t **v_alt, uint64_t m,
+                      int bits, uint32_t *hist, uint32_t *partials, hipStream_t st, int *passes);
+
 // fmx_kernels.hip (launch_psi, launch_next_substr: fmx_select.hip)
 hipError_t launch_occ(const Index *h, const void *d_c, const void *d_i, void *d_out, uint64_t k, hipStream_t st);
 hipError_t launch_prev_range(const Index *h, const void *d_sp, const void *d_ep, const void *d_c, void *d_sp1,

@@ -36,7 +36,6 @@ namespace fmx {
 constexpr int kSaThreads = 256;
 constexpr uint32_t kSaTile = 4096;                  // keys per radix tile: 16 chunks of 256
 constexpr uint32_t kScanTile = 2048;                // elements per scan block: 8 per thread
-constexpr int kScanSum = 0, kScanMax = 1;
 
 __device__ __forceinline__ uint32_t scan_op(int op, uint32_t a, uint32_t b) { return op == kScanMax ? (a > b ? a : b) : a + b; }
 
@@ -271,6 +270,11 @@ struct DevMem {                 // every temporary of one construction; freed on
 
 uint64_t ntiles_of(uint64_t m) { return (m + kSaTile - 1) / kSaTile; }
 
+}  // namespace
+
+// (scan_partials, scan_u32, radix_tiles and radix_sort are declared in fmx_host.h: fmx_corpus.hip sorts and scans with them too)
+uint64_t radix_tiles(uint64_t m) { return ntiles_of(m); }
+
 uint64_t scan_partials(uint64_t len) {         // u32 slots the recursive scan of len elements needs for its block totals
   uint64_t t = 0;
   while (len > 1) { len = (len + kScanTile - 1) / kScanTile; t += len; }
@@ -307,6 +311,8 @@ hipError_t radix_sort(unsigned long long **k, uint32_t **v, unsigned long long *
   }
   return hipSuccess;
 }
+
+namespace {
 
 // FMX_SUFSORT_LOG=<file>: one JSON line per construction appended to the file (tools/build_text_bench.py reads it)
 struct RoundLog { uint64_t h, active; int passes; float ms; double bytes; };

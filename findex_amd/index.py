@@ -1,4 +1,5 @@
 """python -m findex_amd.index X.txt [--little-endian] [--device N] [--fm] [--sa] [--lcp]
+python -m findex_amd.index --dir D --out X [--no-filter-binary] [--data] [--little-endian] [--device N] [--fm] [--sa] [--lcp]
 
 Writes X.bwt and X.aux next to the input (BWTTempStorage.genBWTFilename / genAuxFilename, bwtmerger.scala:17-24: the
 extension swapped), the files BWTMerger2.merge(FileBWTReader) writes -- the BWT of the reversed file -- big-endian
@@ -7,7 +8,13 @@ findex's readers escape it, and this tool does no escaping.
 
 --fm, --sa and --lcp add the sibling files the reference's IndexerApp and SACreator write (genFMFilename / genSAFilename /
 genLCPFilename: the extension swapped): X.fm (FMCreator), X.sa (SACreator: n big-endian int32) and X.lcp (LCPCreator:
-n - 1 big-endian int32), through the writers of the handle opened on the two files just written."""
+n - 1 big-endian int32), through the writers of the handle opened on the two files just written.
+
+--dir D --out X indexes a directory the way the reference's IndexerApp does through DirBWTReader (bwtreader.scala:17-173):
+the files of D in a fixed order, binary ones dropped unless --no-filter-binary, bytes 0, 1 and 255 escaped, a separator
+byte 1 after every file (findex_amd/corpus.py).  It writes X.bwt and X.aux of that stream, X.docs (this project's own side
+file: which stream positions belong to which file), and with --data X.data, the stream itself -- what
+DirBWTReader(caching = true) leaves at genDataFilename.  Escaping and the suffix sort run on the device."""
 import argparse
 import os
 import sys
@@ -27,7 +34,11 @@ def sibling_names(path):
 
 def parser():
     ap = argparse.ArgumentParser(prog="python -m findex_amd.index", description=__doc__.split("\n\n")[1])
-    ap.add_argument("text")
+    ap.add_argument("text", nargs="?", help="the file to index (the single-file form)")
+    ap.add_argument("--dir", help="index every file under this directory (needs --out)")
+    ap.add_argument("--out", help="with --dir: the outputs are OUT.bwt, OUT.aux, OUT.docs ...")
+    ap.add_argument("--no-filter-binary", action="store_true", help="with --dir: keep files that look binary")
+    ap.add_argument("--data", action="store_true", help="with --dir: also write OUT.data, the escaped stream")
     ap.add_argument("--little-endian", action="store_true", help="write little-endian headers and counts")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--fm", action="store_true", help="also write X.fm (FMCreator)")
@@ -38,12 +49,61 @@ def parser():
 
 def planned_outputs(a):
     """The files a run with the parsed arguments `a` writes, in the order it writes them."""
+    if getattr(a, "dir", None):
+        base = a.out + ".x"             # (the name functions swap an extension: OUT itself is the stem)
+        fm, sa, lcp = sibling_names(base)
+        return list(output_names(base)) + [a.out + ".docs"] + ([a.out + ".data"] if a.data else []) + \
+            ([fm] if a.fm else []) + ([sa] if a.sa else []) + ([lcp] if a.lcp else [])
     fm, sa, lcp = sibling_names(a.text)
     return list(output_names(a.text)) + ([fm] if a.fm else []) + ([sa] if a.sa else []) + ([lcp] if a.lcp else [])
 
 
+def main_dir(a):
+    """The --dir form: X.bwt, X.aux, X.docs, then X.data and the siblings that were asked for."""
+    from .corpus import Corpus
+    from .construct import bwt_from_text, write_bwt
+    try:
+        corpus = Corpus.from_dir(a.dir, filter_binary=not a.no_filter_binary, device=a.device)
+    except ValueError as e:
+        print(str(e), file=sys.stderr)
+        return 2
+    outs = planned_outputs(a)
+    bwt_path, aux_path, docs_path = outs[:3]
+    try:
+        stream = corpus.stream()
+        corpus.drop_stream()            # (the files need the stream on the host anyway; the sort gets the HBM)
+        bwt, eof, counts = bwt_from_text(stream, device=a.device)
+        write_bwt(bwt_path, aux_path, bwt, eof, counts, bigEndian=not a.little_endian)
+        corpus.save(docs_path)
+        print("%s: %d files, n = %d, eof = %d -> %s, %s, %s" % (a.dir, corpus.n_docs, bwt.size, eof, bwt_path, aux_path, docs_path))
+        if a.data:
+            stream.tofile(a.out + ".data")
+            print("%s: -> %s" % (a.dir, a.out + ".data"))
+    finally:
+        corpus.close()
+    if a.fm or a.sa or a.lcp:
+        from .searcher import HipFMSearcher
+        fm_path, sa_path, lcp_path = sibling_names(a.out + ".x")
+        hip = HipFMSearcher.from_mem(bwt, eof, counts, device=a.device)
+        try:
+            for wanted, write, path in ((a.fm, hip.write_fm, fm_path), (a.sa, hip.write_sa, sa_path), (a.lcp, hip.write_lcp, lcp_path)):
+                if wanted:
+                    write(path)
+                    print("%s: -> %s" % (a.dir, path))
+        finally:
+            hip.close()
+    return 0
+
+
 def main(argv=None):
-    a = parser().parse_args(argv)
+    ap = parser()
+    a = ap.parse_args(argv)
+    if a.dir:
+        if a.text or not a.out:
+            ap.error("--dir takes --out X and no text file")
+        return main_dir(a)
+    if a.out or a.data or a.no_filter_binary or not a.text:
+        ap.error("a text file, or --dir D --out X")
     with open(a.text, "rb") as f:
         data = f.read()
     if not data:

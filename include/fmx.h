@@ -451,6 +451,84 @@ int fmx_lcp_info(const fmx_index *idx, uint64_t *bytes, double *build_ms, uint32
 int fmx_write_lcp(const fmx_index *idx, const char *path);
 int fmx_lcp_last_phases(double *phi_ms, double *plcp_ms, double *gather_ms);
 
+/* ---- corpus: a directory of files as ONE index -- DirBWTReader (bwtreader.scala:17-173), the input side of the reference's
+ * IndexerApp -- and, beyond the reference, the way back from a stream position to (document, offset).
+ * The STREAM: the documents in the caller's order; in each, raw byte 0 becomes '\' '0', raw 1 becomes '\' '1' and raw 255
+ * becomes '\' 'f' (:144-155; the backslash itself is not escaped, the reference's quirk), and after every document, the last
+ * one included, comes one separator byte 1 (:133-137).  Byte 1 therefore occurs only between documents: no match of an
+ * escaped pattern spans two of them.  Which files make up the documents, and in which order, is the host's business
+ * (findex_amd/corpus.py: list_files); this ABI takes their raw bytes back to back and their end offsets.
+ * An fmx_corpus is bound to one device.  It owns the MAP -- doc_start[n_docs + 1] (each document's first stream position,
+ * the last entry the stream length; strictly increasing), esc_pos[n_esc] (the stream position of each escape's backslash,
+ * ascending) and the escapes in front of each document -- and, until fmx_corpus_drop_stream, the stream itself in HBM.
+ * Limits: 1 <= n_docs < 2^32 - 1, 1 <= stream length <= 2^32 - 2 (the suffix sort's): FMX_ERR_UNSUPPORTED beyond.
+ * fmx_corpus_build     : raw[raw_len] on the host, doc_ends[n_docs] (non-decreasing, repeated for empty documents, the last
+ *                        == raw_len; FMX_ERR_ARG otherwise) -> a corpus.  The stream is built on the device (a count pass per
+ *                        tile of raw bytes, a scan, an emit pass through LDS; no atomics: the same input gives the same bytes
+ *                        on every run).  Like index construction it ALLOCATES AND SYNCHRONISES: FMX_ERR_HIP under a stream
+ *                        capture; what it needs is checked against the free HBM first -- before the first allocation the part
+ *                        known without the escape count, after the count pass the exact rest (FMX_ERR_NOMEM with the need in
+ *                        the message); every temporary is freed on every path.
+ * fmx_corpus_build_dev : the same with the raw bytes already in HBM (doc_ends stays a host pointer), on `stream`.
+ * fmx_corpus_info      : documents, stream length, escapes, device bytes held, build time (ms), and the build's tile size in
+ *                        raw bytes (what tests aim at); any pointer may be NULL, and so may the corpus (then only the tile
+ *                        size is meaningful).
+ * fmx_corpus_stream    : the stream copied to the host (cap >= stream length, FMX_ERR_OVERFLOW otherwise): what
+ *                        DirBWTReader(caching = true) leaves at genDataFilename, X.data.
+ * fmx_corpus_stream_dev: the stream's device pointer (valid until the stream is dropped or the corpus freed).
+ * fmx_corpus_drop_stream: frees the stream in HBM; the map stays.
+ * fmx_corpus_open_index: fmx_bwt_from_text_dev over the stream, then fmx_open_dev on its output -- no host round trip of the
+ *                        text; an ordinary fmx_index (close it with fmx_close; it does not depend on the corpus).
+ * fmx_corpus_tables    : host copies of doc_start[n_docs + 1], raw_len[n_docs] (each document's length on disk) and
+ *                        esc_pos[n_esc]; any pointer may be NULL.
+ * fmx_corpus_from_tables: a corpus (map only, no stream) from such copies; tables that contradict each other: FMX_ERR_FORMAT.
+ * fmx_corpus_map       : for k stream positions p: doc = the largest d with doc_start[d] <= p, esc_off = p - doc_start[d]
+ *                        (the offset in the escaped document), raw_off = esc_off - #{e in esc_pos : doc_start[d] <= e < p}
+ *                        (the offset in the file on disk).  The second byte of an escape maps to the raw offset of the byte it
+ *                        stands for; a separator maps to (d, the raw length of d); p >= stream length gives doc = UINT32_MAX
+ *                        (and UINT64_MAX offsets).  Two binary searches per position.
+ * fmx_corpus_map_dev   : the same on device pointers (u64 pos, u32 doc, u64 offsets); it only enqueues (safe inside a stream
+ *                        capture).
+ * fmx_corpus_doc_list  : for k row intervals (sp, ep) of `idx` -- the index of this corpus' stream -- found by searching the
+ *                        reverse of an escaped pattern of pat_len stream bytes: the distinct documents of each interval's
+ *                        first min(ep - sp, max_per) rows (max_per 0: all) with their hit counts, in CSR form: out_off[k + 1],
+ *                        out_doc[], out_cnt[]; within an interval the documents ascend.  Nothing is written past entry
+ *                        cap - 1; the host form returns FMX_ERR_OVERFLOW when out_off[k] > cap (out_off complete, the first
+ *                        cap entries written), the _dev form leaves the total in d_out_off[k] for the caller to check.  Locate,
+ *                        map, a radix sort of (interval, document) keys, heads and compaction, all on the device.  Both forms
+ *                        allocate and synchronise (FMX_ERR_HIP under a stream capture).
+ * fmx_corpus_doc_list_phases: device time (ms) of the calling thread's last listing in its four phases.
+ * fmx_corpus_free      : NULL is FMX_OK.
+ * fmx_corpus_escape    : host helper: a query escaped the way the stream is (at most 2 len bytes; *out_len = the bytes
+ *                        needed, FMX_ERR_OVERFLOW when cap is smaller). */
+typedef struct fmx_corpus fmx_corpus;
+int fmx_corpus_build(const uint8_t *raw, uint64_t raw_len, const uint64_t *doc_ends, uint64_t n_docs, int device,
+                     fmx_corpus **out);
+int fmx_corpus_build_dev(const void *d_raw, uint64_t raw_len, const uint64_t *doc_ends, uint64_t n_docs, int device,
+                         void *stream, fmx_corpus **out);
+int fmx_corpus_free(fmx_corpus *corpus);
+int fmx_corpus_info(const fmx_corpus *corpus, uint64_t *n_docs, uint64_t *stream_len, uint64_t *n_esc, uint64_t *bytes,
+                    double *build_ms, uint32_t *tile_bytes);
+int fmx_corpus_stream(const fmx_corpus *corpus, uint8_t *out, uint64_t cap);
+int fmx_corpus_stream_dev(const fmx_corpus *corpus, const void **d_stream, uint64_t *stream_len);
+int fmx_corpus_drop_stream(fmx_corpus *corpus);
+int fmx_corpus_open_index(const fmx_corpus *corpus, void *stream, fmx_index **out);
+int fmx_corpus_tables(const fmx_corpus *corpus, uint64_t *doc_start, uint64_t *raw_len, uint64_t *esc_pos);
+int fmx_corpus_from_tables(const uint64_t *doc_start, const uint64_t *raw_len, const uint64_t *esc_pos, uint64_t n_docs,
+                           uint64_t n_esc, int device, fmx_corpus **out);
+int fmx_corpus_map(const fmx_corpus *corpus, const uint64_t *pos, size_t k, uint32_t *doc, uint64_t *esc_off,
+                   uint64_t *raw_off);
+int fmx_corpus_map_dev(const fmx_corpus *corpus, const void *d_pos, size_t k, void *d_doc, void *d_esc_off,
+                       void *d_raw_off, void *stream);
+int fmx_corpus_doc_list(const fmx_corpus *corpus, const fmx_index *idx, const uint64_t *sp, const uint64_t *ep, size_t k,
+                        uint64_t pat_len, uint64_t max_per, uint64_t *out_off, uint32_t *out_doc, uint32_t *out_cnt,
+                        size_t cap);
+int fmx_corpus_doc_list_dev(const fmx_corpus *corpus, const fmx_index *idx, const void *d_sp, const void *d_ep, size_t k,
+                            uint64_t pat_len, uint64_t max_per, void *d_out_off, void *d_out_doc, void *d_out_cnt,
+                            size_t cap, void *stream);
+int fmx_corpus_doc_list_phases(double *locate_ms, double *map_ms, double *sort_ms, double *compact_ms);
+int fmx_corpus_escape(const uint8_t *in, size_t len, uint8_t *out, size_t cap, size_t *out_len);
+
 /* ---- regex: REParser.re2post (re2/re2.scala:50-185) + ReTree.apply (re2/retree.scala:156-370).
  * Bytes of `re` are Latin-1 characters.  FMX_ERR_SYNTAX / FMX_ERR_MATCH mirror the reference's
  * "re2post syntax" exception and scala.MatchError. */
