@@ -107,6 +107,7 @@ def lib():
     L.orc_sampled_cf.restype = i64
     L.orc_sampled_cf.argtypes = [vp, i32]
     L.orc_sampled_search_batch.argtypes = [vp, vp, vp, u64, vp, vp, vp, i32]
+    L.orc_sampled_prev_range_batch.argtypes = [vp, vp, vp, vp, vp, vp, u64, i32]
     _lib = L
     return L
 
@@ -413,7 +414,7 @@ class NaiveFMSearcher:
 
 
 class SampledFMSearcher:
-    """occ / cf / search over per-256-position symbol checkpoints + a scan of the BWT bytes (fmx_oracle.c, "Sampled-checkpoint
+    """occ / cf / search / getPrevRange over per-256-position symbol checkpoints + a scan of the BWT bytes (fmx_oracle.c, "Sampled-checkpoint
     variant"): the CPU baseline for indexes the inverted lists cannot describe (n > 2^32, or no 6 n bytes of host memory) --
     BASELINE.md's "sampled popcount structure".  Same function as NaiveFMSearcher.occ / .search, another data structure;
     held to it by tests/test_oracle_kat.py.  The BWT array is NOT copied: keep it alive."""
@@ -457,6 +458,30 @@ class SampledFMSearcher:
         steps = np.zeros(k, dtype=np.uint32)
         self._L.orc_sampled_search_batch(self._h, _ptr(pat), _ptr(off), k, _ptr(sp), _ptr(ep), _ptr(steps), int(threads))
         return sp, ep, steps
+
+    def prev_range_batch(self, sp, ep, c, threads=1):
+        """getPrevRange for arrays of (sp, ep, c) in one call on `threads` cores -> (sp1, ep1); an empty range is
+        sp1 >= ep1, as NaiveFMSearcher.prev_range_batch reports it."""
+        sp = np.ascontiguousarray(sp, dtype=np.uint64)
+        ep = np.ascontiguousarray(ep, dtype=np.uint64)
+        c = np.ascontiguousarray(c, dtype=np.uint8)
+        if not (sp.size == ep.size == c.size):
+            raise ValueError("sp, ep and c differ in length")
+        sp1 = np.zeros(sp.size, dtype=np.uint64)
+        ep1 = np.zeros(sp.size, dtype=np.uint64)
+        self._L.orc_sampled_prev_range_batch(self._h, _ptr(sp), _ptr(ep), _ptr(c), _ptr(sp1), _ptr(ep1), sp.size, int(threads))
+        return sp1, ep1
+
+    def getPrevRange(self, sp, ep, c):
+        """SuffixAlgo.getPrevRange with orc_get_prev_range's semantics: (cf(c) + occ(c, sp - 1), cf(c) + occ(c, ep - 1)),
+        or None unless the first is smaller.  With .n, what oracle.retree.ReTree._matchSA needs of an index."""
+        if not 0 <= int(c) < 256:
+            raise IndexOutOfBounds(c)
+        c = int(c)
+        base = self.cf(c)
+        a = base + int(self._L.orc_sampled_occ(self._h, c, int(sp) - 1))
+        b = base + int(self._L.orc_sampled_occ(self._h, c, int(ep) - 1))
+        return (a, b) if a < b else None
 
 
 class SAISNaiveSearcher(NaiveFMSearcher):

@@ -804,3 +804,20 @@ int orc_sampled_search_batch(const orc_sampled *s, const uint8_t *pat, const uin
   (void)threads;
   return ORC_OK;
 }
+
+/* SuffixAlgo.getPrevRange, F/findex.scala:33-35, over the sampled occ, for k (sp, ep, c) triples: the same two values
+ * orc_get_prev_range writes (a = cf(c) + occ(c, sp - 1), b = cf(c) + occ(c, ep - 1)); an empty range is a >= b.  One call is
+ * one level of a regex frontier on an index the inverted lists cannot describe. */
+int orc_sampled_prev_range_batch(const orc_sampled *s, const uint64_t *sp, const uint64_t *ep, const uint8_t *c,
+                                 uint64_t *sp1, uint64_t *ep1, uint64_t k, int threads) {
+#ifdef _OPENMP
+#pragma omp parallel for schedule(dynamic, 256) num_threads(threads > 0 ? threads : 1)
+#endif
+  for (int64_t q = 0; q < (int64_t)k; q++) {
+    const int ch = c[q];
+    sp1[q] = (uint64_t)((int64_t)s->bs[ch] + sampled_occ(s, ch, (int64_t)sp[q] - 1));
+    ep1[q] = (uint64_t)((int64_t)s->bs[ch] + sampled_occ(s, ch, (int64_t)ep[q] - 1));
+  }
+  (void)threads;
+  return ORC_OK;
+}

@@ -137,3 +137,88 @@ def sparse_alphabet_bwt(n=50_001, seed=6):
     bwt[896 * 5] = 254
     bwt[896 * 20 - 1] = 255
     return index_of_bwt(bwt, n // 3)
+
+
+# ---------------------------------------------------------------- regex oracles shared by the GPU regex modules
+class _OIdx:
+    """What oracle.engines and oracle.retree ask of an index: .n and getPrevRange."""
+
+    def __init__(self, sa):
+        self.sa, self.n = sa, sa.n
+
+    def getPrevRange(self, sp, ep, c):
+        return self.sa.getPrevRange(sp, ep, c)
+
+
+def oracle_results_capped(bwt, eof, counts, re, max_len):
+    """All matches of length <= max_len: breadth-first over the oracle's getPrevRange."""
+    import oracle
+    from oracle import retree as R
+    orc = oracle.NaiveFMSearcher.from_mem(bwt, eof, counts)
+    t = R.ReTree(R.re2post(re)).tables()
+    front = [(0, 0, orc.n, s) for s in t["firsts"]]
+    out = []
+    while front:
+        nxt = []
+        for ln, sp, ep, s in front:
+            r = orc.getPrevRange(sp, ep, t["c"][s])
+            if r is None:
+                continue
+            if t["isLast"][s]:
+                out.append((ln + 1, r[0], r[1]))
+            elif ln + 1 < max_len:
+                nxt += [(ln + 1, r[0], r[1], f) for f in t["follows"][s]]
+        front = nxt
+    return out
+
+
+FRONTIER_DTYPE = np.dtype([("regex", np.uint32), ("len", np.uint32), ("sp", np.uint64), ("ep", np.uint64)])
+
+
+def frontier_oracle(orc, tables, max_len=0, **batch_kw):
+    """oracle_results_capped for a whole batch of regexes (`tables`: a list of ReTree.tables() dicts) with one
+    orc.prev_range_batch call per level: every frontier element of the level is stepped by its state's byte, a non-empty
+    range is emitted when the state isLast and else expanded into the state's follows while len + 1 < max_len (0: no cap),
+    multiplicity kept.  -> (structured array of (regex, len, sp, ep) sorted by those four, getPrevRange evaluations made,
+    whether the cap cut an element that had follows).  `batch_kw` goes to prev_range_batch (threads=)."""
+    st_c, st_last, st_regex, fol_off, fol, firsts = [], [], [], [0], [], []
+    for j, t in enumerate(tables):
+        base = len(st_c)
+        st_c += t["c"]
+        st_last += [bool(x) for x in t["isLast"]]
+        st_regex += [j] * len(t["c"])
+        for f in t["follows"]:
+            fol += [base + x for x in f]
+            fol_off.append(len(fol))
+        firsts += [base + x for x in t["firsts"]]
+    st_c = np.asarray(st_c, dtype=np.uint8)
+    st_last = np.asarray(st_last, dtype=bool)
+    st_regex = np.asarray(st_regex, dtype=np.uint32)
+    fol_off = np.asarray(fol_off, dtype=np.int64)
+    fol = np.asarray(fol, dtype=np.int64)
+    st = np.asarray(firsts, dtype=np.int64)
+    sp = np.zeros(st.size, dtype=np.uint64)
+    ep = np.full(st.size, orc.n, dtype=np.uint64)
+    parts, calls, level, truncated = [], 0, 0, False
+    while st.size:
+        a, b = orc.prev_range_batch(sp, ep, st_c[st], **batch_kw)
+        calls += int(st.size)
+        level += 1
+        ok = a < b
+        emit = ok & st_last[st]
+        part = np.zeros(int(emit.sum()), dtype=FRONTIER_DTYPE)
+        part["regex"], part["len"], part["sp"], part["ep"] = st_regex[st[emit]], level, a[emit], b[emit]
+        parts.append(part)
+        grow = ok & ~st_last[st]
+        src = st[grow]
+        cnt = fol_off[src + 1] - fol_off[src]
+        if max_len and level >= max_len:
+            truncated = truncated or bool((cnt > 0).any())
+            break
+        total = int(cnt.sum())
+        first = np.repeat(fol_off[src] - (np.cumsum(cnt) - cnt), cnt)      # follows of one element are consecutive
+        st = fol[first + np.arange(total, dtype=np.int64)]
+        sp = np.repeat(a[grow], cnt)
+        ep = np.repeat(b[grow], cnt)
+    out = np.concatenate(parts) if parts else np.zeros(0, dtype=FRONTIER_DTYPE)
+    return out[np.lexsort((out["ep"], out["sp"], out["len"], out["regex"]))], calls, truncated

@@ -9,7 +9,7 @@ import pytest
 import findex_amd
 import oracle
 from oracle import retree as R
-from helpers import bwt_of_text, lf_walk_patterns, pack_patterns, synth_bwt, table_key
+from helpers import _OIdx, bwt_of_text, lf_walk_patterns, oracle_results_capped, pack_patterns, synth_bwt, table_key
 from helpers import table_default  # noqa: F401  (a fixture)
 
 pytestmark = pytest.mark.gpu
@@ -1196,26 +1196,6 @@ def test_random_regexes_all_engines_vs_oracle(testdata):
     assert n_thompson > 50
 
 
-def oracle_results_capped(bwt, eof, counts, re, max_len):
-    """All matches of length <= max_len: breadth-first over the oracle's getPrevRange."""
-    orc = oracle.NaiveFMSearcher.from_mem(bwt, eof, counts)
-    t = R.ReTree(R.re2post(re)).tables()
-    front = [(0, 0, orc.n, s) for s in t["firsts"]]
-    out = []
-    while front:
-        nxt = []
-        for ln, sp, ep, s in front:
-            r = orc.getPrevRange(sp, ep, t["c"][s])
-            if r is None:
-                continue
-            if t["isLast"][s]:
-                out.append((ln + 1, r[0], r[1]))
-            elif ln + 1 < max_len:
-                nxt += [(ln + 1, r[0], r[1], f) for f in t["follows"][s]]
-        front = nxt
-    return out
-
-
 def test_regex_overflow_is_reported():
     bwt, eof, counts = synth_bwt(200_000, 97, 100, 3)
     hip = findex_amd.HipFMSearcher.from_mem(bwt, eof, counts)
@@ -1551,14 +1531,6 @@ def test_sharded_search_and_match_two_ranks_rccl():
 
 
 # ---------------------------------------------------------------- the reference's other two engines
-class _OIdx:
-    def __init__(self, sa):
-        self.sa, self.n = sa, sa.n
-
-    def getPrevRange(self, sp, ep, c):
-        return self.sa.getPrevRange(sp, ep, c)
-
-
 def test_thompson_engine(testdata):
     """REParser.createNFA + REParser.matchSA (re2.scala:264-334,568-693) on the frontier kernel:
     the reference's vectors (T/REParser.scala:219-234,292-307) and the oracle's restatement."""

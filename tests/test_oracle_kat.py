@@ -265,3 +265,113 @@ def test_sampled_checkpoint_oracle_equals_the_inverted_lists(testdata):
         assert np.array_equal(wsp, gsp) and np.array_equal(wep, gep) and np.array_equal(wst, gst), name
         assert int((wsp < wep).sum()) > 50, name
         b.close()
+
+
+def _sampled_pair(bwt, eof):
+    counts = oracle.histogram(bwt, eof)
+    return oracle.NaiveFMSearcher.from_mem(bwt, eof, counts), oracle.SampledFMSearcher(bwt, eof, threads=2)
+
+
+def test_sampled_checkpoint_oracle_get_prev_range(testdata):
+    """SampledFMSearcher.getPrevRange / prev_range_batch (what a regex frontier asks of an index, for indexes of more than
+    2^32 rows) equal NaiveFMSearcher's: on the golden `words` index and on a four-letter index of 300 007 rows, for random
+    (sp, ep, c) and for sp = 0, ep = n, sp = ep, ranges that hold the EOF row or begin or end at it, a byte that the text
+    does not have, and byte 0 (the EOF symbol: one row)."""
+    from helpers import synth_bwt
+    rng = np.random.default_rng(31)
+    wbwt, _, weof = oracle.load_bwt_file(os.path.join(testdata, "words.bwt"), bigEndian=True)
+    sbwt, seof, _ = synth_bwt(300_007, 97, 100, 17)
+    for name, bwt, eof in (("words", np.array(wbwt, dtype=np.uint8), weof), ("synthetic", sbwt, seof)):
+        a, b = _sampled_pair(bwt, eof)
+        n = a.n
+        assert b.n == n and b.eof == a.eof == eof
+        present = [int(c) for c in np.unique(bwt)]
+        absent = next(c for c in range(1, 256) if c not in present)
+        syms = np.asarray(present + [0, absent, 255], dtype=np.uint8)
+        k = 4000
+        lo = rng.integers(0, n + 1, k)
+        hi = rng.integers(0, n + 1, k)
+        sp, ep = np.minimum(lo, hi), np.maximum(lo, hi)
+        narrow = rng.random(k) < 0.5            # half of them a few rows wide: the ranges a deep frontier holds
+        ep = np.where(narrow, np.minimum(sp + rng.integers(0, 4, k), n), ep)
+        c = syms[rng.integers(0, syms.size, k)]
+        edges = [(0, n), (0, 0), (n, n), (0, 1), (n - 1, n), (eof, eof + 1), (eof, eof), (eof + 1, eof + 1), (0, eof), (0, eof + 1),
+                 (eof, n), (eof + 1, n), (eof - 1, eof + 2), (255, 257), (256, 256), (256, 512), (n - 300, n)]
+        esp = np.repeat([e[0] for e in edges], syms.size)
+        eep = np.repeat([e[1] for e in edges], syms.size)
+        ec = np.tile(syms, len(edges))
+        sp, ep, c = np.concatenate([sp, esp]), np.concatenate([ep, eep]), np.concatenate([c, ec])
+        wa, wb = a.prev_range_batch(sp, ep, c)
+        for threads in (1, 3):
+            ga, gb = b.prev_range_batch(sp, ep, c, threads=threads)
+            assert np.array_equal(ga, wa) and np.array_equal(gb, wb), (name, threads)
+        hits = int((wa < wb).sum())
+        assert hits > 1000 and int((wa >= wb).sum()) > 1000, (name, hits)
+        for j in list(range(k, sp.size)) + list(range(0, 300)):      # the scalar form: every edge, some of the random ones
+            want = a.getPrevRange(int(sp[j]), int(ep[j]), int(c[j]))
+            assert b.getPrevRange(int(sp[j]), int(ep[j]), int(c[j])) == want, (name, int(sp[j]), int(ep[j]), int(c[j]))
+            assert (want is None) == bool(wa[j] >= wb[j])
+        assert a.getPrevRange(0, n, 0) == b.getPrevRange(0, n, 0) == (0, 1)
+        assert b.getPrevRange(0, n, absent) is None and b.getPrevRange(5, 5, present[0]) is None
+        with pytest.raises(oracle.IndexOutOfBounds):
+            b.getPrevRange(0, n, 256)
+        b.close()
+
+
+def test_sampled_checkpoint_oracle_replays_matchSA(testdata):
+    """ReTree._matchSA (the pure-Python replay of the reference's priority-queue loop) over a SampledFMSearcher gives what the
+    C replay gives over the inverted lists -- elements, newest-first order, elements left in the queue and pops -- for the
+    regexes of test_gpu_parity.REF_REGEXES under the reference's default limits and under limits that bind early."""
+    from oracle import retree as R
+    from test_gpu_parity import REF_REGEXES
+    wbwt, _, weof = oracle.load_bwt_file(os.path.join(testdata, "words.bwt"), bigEndian=True)
+    a, b = _sampled_pair(np.array(wbwt, dtype=np.uint8), weof)
+    cut = 0
+    for re in REF_REGEXES:
+        tree = R.ReTree(R.re2post(re, True))
+        for mb, mi in ((1024, 1000), (16, 50)):
+            want, left, pops = a.match_tables(tree.tables(), mb, mi)
+            ret, front, gpops = tree._matchSA(b, mb, mi)
+            assert ret == want and len(front) == left and gpops == pops, (re, mb, mi)
+            cut += left > 0
+    assert cut > 0          # some of them were cut off by a limit
+
+
+def test_frontier_oracle_equals_the_element_by_element_search():
+    """helpers.frontier_oracle (a batch of regexes breadth-first, one prev_range_batch call per level) gives what
+    helpers.oracle_results_capped gives regex by regex, over either structure: results with their multiplicity, and as many
+    getPrevRange evaluations as the element-by-element search makes."""
+    from oracle import retree as R
+    from helpers import frontier_oracle, oracle_results_capped, synth_bwt
+    bwt, eof, counts = synth_bwt(70_001, 97, 100, 23)
+    a, b = _sampled_pair(bwt, eof)
+    res = ["abcd", "a[ab]*d", "(ab|cd)+d", "c[a-d]*d", "x(a|a)", "(a*b*)*c", "[a-d][a-d][a-d]d", "ab?c", "dz", "d[a-d]*"]
+    tables = [R.ReTree(R.re2post(re)).tables() for re in res]
+    # (always under a cap: on i.i.d. bytes LF has short cycles, and a starred regex can follow one for ever)
+    for max_len in (1, 2, 5, 9, 14):
+        want = sorted((j,) + key for j, re in enumerate(res) for key in oracle_results_capped(bwt, eof, counts, re, max_len))
+        for orc, kw in ((a, {}), (b, {}), (b, {"threads": 3})):
+            got, calls, truncated = frontier_oracle(orc, tables, max_len, **kw)
+            assert list(zip(got["regex"].tolist(), got["len"].tolist(), got["sp"].tolist(), got["ep"].tolist())) == want, max_len
+            assert truncated, max_len
+    assert len(want) > 500
+    # the evaluations: one regex, counted by a searcher that counts
+    class Counting:
+        def __init__(self, sa):
+            self.sa, self.n, self.calls = sa, sa.n, 0
+
+        def getPrevRange(self, sp, ep, c):
+            self.calls += 1
+            return self.sa.getPrevRange(sp, ep, c)
+
+    cnt = Counting(b)
+    t = tables[1]
+    front = [(0, 0, cnt.n, s) for s in t["firsts"]]
+    while front:
+        nxt = []
+        for ln, sp, ep, s in front:
+            r = cnt.getPrevRange(sp, ep, t["c"][s])
+            if r is not None and not t["isLast"][s] and ln + 1 < 9:
+                nxt += [(ln + 1, r[0], r[1], f) for f in t["follows"][s]]
+        front = nxt
+    assert frontier_oracle(a, [t], 9)[1] == cnt.calls > 100
