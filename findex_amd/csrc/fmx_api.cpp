@@ -33,6 +33,8 @@ int layout_preference() { return g_layout_pref.load(std::memory_order_relaxed); 
 static std::atomic<uint64_t> g_serial{0};
 static std::atomic<int> g_force_superblocks{0};
 static std::atomic<int> g_validate{0};
+// fmx_config_set("pipeline", ..): large host batches in page-locked memory cut into chunks over three streams
+static std::atomic<int> g_pipeline{0};
 bool validate_device_operands() { return g_validate.load(std::memory_order_relaxed) != 0; }
 bool force_superblocks() { return g_force_superblocks.load(std::memory_order_relaxed) != 0; }
 
@@ -41,28 +43,39 @@ static int arg_fail(const char *msg) {
   return FMX_ERR_ARG;
 }
 
-struct StreamGuard {
-  hipStream_t s = nullptr;
-  ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
-};
-
-struct DevBuf {        // a device pointer borrowed from the call's context (Call::alloc)
-  void *p = nullptr;
-};
-
-struct EventPair {     // the call context's two events (not owned)
-  hipEvent_t a = nullptr, b = nullptr;
-};
-
-#define HIP_TRY(call, what)                            \
-  do {                                                 \
-    hipError_t e__ = (call);                           \
-    if (e__ != hipSuccess) return hip_fail(e__, what); \
-  } while (0)
-
 static int use_device(const Index *h) {
   HIP_TRY(hipSetDevice(h->device), "hipSetDevice");
   return FMX_OK;
+}
+
+int use_device_index(int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { g_err = "no HIP device available (libfmx has no CPU fallback)"; return FMX_ERR_HIP; }
+  if (device < 0 || device >= ndev) return arg_fail("device index out of range");
+  HIP_TRY(hipSetDevice(device), "hipSetDevice");
+  return FMX_OK;
+}
+
+int not_capturing(hipStream_t st, const char *what) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  HIP_TRY(hipStreamIsCapturing(st, &cs), "hipStreamIsCapturing");
+  if (cs != hipStreamCaptureStatusNone) {
+    g_err = std::string(what) + " allocates and synchronises: not under a stream capture";
+    return FMX_ERR_HIP;
+  }
+  return FMX_OK;
+}
+
+// What a handle builds at first use (the locate samples, the LCP array) is built here when a call finds none.
+int ensure_built(const Index *h, std::mutex &mu, const bool &flag, int (*prepare)(const Index *, hipStream_t), hipStream_t st) {
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    if (flag) return FMX_OK;
+  }
+  if (st) return prepare(h, st);
+  CtxLease lease(h);
+  if (!lease.c) return FMX_ERR_HIP;
+  return prepare(h, lease.c->stream);
 }
 
 static void free_ctx(CallCtx *c) {
@@ -131,9 +144,9 @@ class Call {
     return c_ ? FMX_OK : FMX_ERR_HIP;
   }
   // next scratch buffer of the call, at least `bytes` long
-  hipError_t alloc(DevBuf &b, size_t bytes) {
+  hipError_t alloc(void **p, size_t bytes) {
     if (next_ >= CallCtx::kBufs) return hipErrorOutOfMemory;
-    return ctx_scratch(c_, next_++, bytes, &b.p);
+    return ctx_scratch(c_, next_++, bytes, p);
   }
   // pinned host staging of at least `bytes`
   hipError_t pinned(void **out, size_t bytes) {
@@ -159,20 +172,30 @@ class Call {
   }
   hipEvent_t ev_a() const { return c_->ev_a; }
   hipEvent_t ev_b() const { return c_->ev_b; }
-  // Runs `enqueue` on the context's stream and records the device time between the two events.
+  // Runs enqueue(stream, ev_a, ev_b) on the context's stream, waits for it and records the device time between the two
+  // events.  events = false: it gets null events and records none; the call counts as a launch, its time is not taken.
   template <class F>
-  int timed(F enqueue) {
-    EventPair ev{c_->ev_a, c_->ev_b};
-    int rc = enqueue(c_->stream, ev);
+  int timed(F enqueue, bool events = true) {
+    int rc = enqueue(c_->stream, events ? c_->ev_a : nullptr, events ? c_->ev_b : nullptr);
     if (rc != FMX_OK) { (void)hipStreamSynchronize(c_->stream); return rc; }
     HIP_TRY(hipStreamSynchronize(c_->stream), "hipStreamSynchronize");
     float ms = 0;
-    if (hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess) {
+    if (!events || hipEventElapsedTime(&ms, c_->ev_a, c_->ev_b) == hipSuccess) {
       std::lock_guard<std::mutex> lk(h_->mu);
-      h_->last_kernel_ms = ms;
+      if (events) h_->last_kernel_ms = ms;
       h_->launches++;
     }
     return FMX_OK;
+  }
+  // One launch alone between the two events: launch(stream) -> hipError_t
+  template <class L>
+  int timed_launch(L launch, const char *what) {
+    return timed([&](hipStream_t st, hipEvent_t ev_a, hipEvent_t ev_b) {
+      HIP_TRY(hipEventRecord(ev_a, st), "hipEventRecord");
+      HIP_TRY(launch(st), what);
+      HIP_TRY(hipEventRecord(ev_b, st), "hipEventRecord");
+      return (int)FMX_OK;
+    });
   }
 
  private:
@@ -303,11 +326,9 @@ static int open_common(const void *src, bool src_on_device, FILE *src_file, uint
   if (!src && !src_file && n) return arg_fail("bwt is null");
   if (n < 1 || eof >= n) return arg_fail("need n >= 1 and eof < n");
   if (n >= (1ull << 38)) { g_err = "n >= 2^38 is not supported"; return FMX_ERR_UNSUPPORTED; }
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev == 0) { g_err = "no HIP device available (libfmx has no CPU fallback)"; return FMX_ERR_HIP; }
-  if (device < 0 || device >= ndev) return arg_fail("device index out of range");
-  HIP_TRY(hipSetDevice(device), "hipSetDevice");
+  int rc = use_device_index(device);
+  if (rc) return rc;
+  hipError_t e = hipSuccess;
   Index *h = new (std::nothrow) Index();
   if (!h) { g_err = "out of host memory"; return FMX_ERR_NOMEM; }
   h->serial = ++g_serial;
@@ -326,7 +347,6 @@ static int open_common(const void *src, bool src_on_device, FILE *src_file, uint
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) h->cu_count = prop.multiProcessorCount;
   StreamGuard own;
   hipStream_t st = user_stream;
-  int rc = FMX_OK;
   do {
     if (!st) {
       if ((e = hipStreamCreate(&own.s)) != hipSuccess) { rc = hip_fail(e, "hipStreamCreate"); break; }
@@ -365,9 +385,13 @@ static int open_common(const void *src, bool src_on_device, FILE *src_file, uint
 static inline Index *H(fmx_index *p) { return reinterpret_cast<Index *>(p); }
 static inline const Index *H(const fmx_index *p) { return reinterpret_cast<const Index *>(p); }
 
-// Operands in, kernel, results out.  Small calls (the single-query forms a per-call adapter makes) pack all
-// operands into one pinned staging buffer and travel as ONE copy each way; large calls copy each array
-// directly between the caller's memory and its own device buffer.
+// Operands in, kernel, results out.  Where the kernel finds its operands and leaves its results depends on how much travels:
+//   tiny (the single-query forms a per-call adapter makes: getPrevRange / occ / search): in the page-locked staging buffer
+//     itself -- the kernel reads its few operand bytes over the link and writes its results there (the buffer is mapped into
+//     the device's address space like every hipHostMalloc allocation).  No copies, and no events around the kernel either
+//     (19.7 against 24.4 against 33.1 us per fmx_occ_batch of one query): fmx_stats_t.last_kernel_ms is not updated by such a call;
+//   small: all operands packed into the staging buffer travel as ONE copy each way;
+//   large: every array is copied between the caller's memory and its own device buffer.
 struct HostIn { const void *src; size_t bytes; };
 struct HostOut { void *dst; size_t bytes; };      // dst == nullptr: device scratch of that size, nothing comes back
 constexpr size_t kSmallCall = 256u << 10;
@@ -382,87 +406,56 @@ static int run_io(const Index *h, const HostIn *ins, int nin, const HostOut *out
   size_t in_total = 0, out_total = 0;
   for (int j = 0; j < nin; j++) in_total += up16(ins[j].bytes);
   for (int j = 0; j < nout; j++) out_total += up16(outs[j].bytes);
+  const bool staged = in_total + out_total <= kSmallCall, tiny = in_total + out_total <= kTinyCall;
   const void *din[CallCtx::kBufs] = {nullptr};
   void *dout[CallCtx::kBufs] = {nullptr};
-  if (in_total + out_total <= kSmallCall) {
+  uint8_t *hin = nullptr, *hout = nullptr;          // staging: the operands, and the results behind them
+  void *a = nullptr, *b = nullptr;                  // their device images
+  if (staged) {
     void *pin = nullptr;
     HIP_TRY(call.pinned(&pin, kSmallCall), "hipHostMalloc");
-    DevBuf a, b;
-    HIP_TRY(call.alloc(a, kSmallCall), "hipMalloc");
-    HIP_TRY(call.alloc(b, kSmallCall), "hipMalloc");
-    uint8_t *hp = static_cast<uint8_t *>(pin);
+    HIP_TRY(call.alloc(&a, kSmallCall), "hipMalloc");
+    HIP_TRY(call.alloc(&b, kSmallCall), "hipMalloc");
+    hin = static_cast<uint8_t *>(pin);
+    hout = hin + in_total;
+    uint8_t *ibase = tiny ? hin : static_cast<uint8_t *>(a), *obase = tiny ? hout : static_cast<uint8_t *>(b);
     size_t o = 0;
     for (int j = 0; j < nin; j++) {
-      if (ins[j].bytes) std::memcpy(hp + o, ins[j].src, ins[j].bytes);
-      din[j] = static_cast<uint8_t *>(a.p) + o;
+      if (ins[j].bytes) std::memcpy(hin + o, ins[j].src, ins[j].bytes);
+      din[j] = ibase + o;
       o += up16(ins[j].bytes);
     }
-    size_t oo = 0;
-    for (int j = 0; j < nout; j++) { dout[j] = static_cast<uint8_t *>(b.p) + oo; oo += up16(outs[j].bytes); }
-    uint8_t *hout = hp + in_total;                 // results come back behind the operands
-    // The single-query forms (a per-call adapter's getPrevRange / occ / search): no copies at all -- the kernel reads its
-    // few operand bytes from the page-locked staging buffer over the link and writes its results there (the buffer is
-    // mapped into the device's address space like every hipHostMalloc allocation).  Two copy submissions less per call.
-    // No events around the kernel either (19.7 against 24.4 against 33.1 us per fmx_occ_batch of one query):
-    // fmx_stats_t.last_kernel_ms is not updated by such a call.  FMX_TINY_DIRECT=0: as every other small call; 1: with events.
-    static const int tiny_direct = getenv("FMX_TINY_DIRECT") ? atoi(getenv("FMX_TINY_DIRECT")) : 2;
-    if (tiny_direct && in_total + out_total <= kTinyCall) {
-      o = 0;
-      for (int j = 0; j < nin; j++) { din[j] = hp + o; o += up16(ins[j].bytes); }
-      oo = 0;
-      for (int j = 0; j < nout; j++) { dout[j] = hout + oo; oo += up16(outs[j].bytes); }
-      if (tiny_direct == 2) {
-        const hipError_t le = launch(call.stream(), din, dout);
-        const hipError_t se = hipStreamSynchronize(call.stream());
-        if (le != hipSuccess) return hip_fail(le, "kernel launch");
-        if (se != hipSuccess) return hip_fail(se, "hipStreamSynchronize");
-        { std::lock_guard<std::mutex> lk(h->mu); h->launches++; }
-        rc = FMX_OK;
-      } else {
-        rc = call.timed([&](hipStream_t st, EventPair &ev) {
-          HIP_TRY(hipEventRecord(ev.a, st), "hipEventRecord");
-          HIP_TRY(launch(st, din, dout), "kernel launch");
-          HIP_TRY(hipEventRecord(ev.b, st), "hipEventRecord");
-          return (int)FMX_OK;
-        });
-      }
-      if (rc != FMX_OK) return rc;
-      oo = 0;
-      for (int j = 0; j < nout; j++) {
-        if (outs[j].bytes && outs[j].dst) std::memcpy(outs[j].dst, hout + oo, outs[j].bytes);
-        oo += up16(outs[j].bytes);
-      }
-      return FMX_OK;
-    }
-    rc = call.timed([&](hipStream_t st, EventPair &ev) {
-      if (in_total) HIP_TRY(hipMemcpyAsync(a.p, hp, in_total, hipMemcpyHostToDevice, st), "H2D");
-      HIP_TRY(hipEventRecord(ev.a, st), "hipEventRecord");
-      HIP_TRY(launch(st, din, dout), "kernel launch");
-      HIP_TRY(hipEventRecord(ev.b, st), "hipEventRecord");
-      if (out_total) HIP_TRY(hipMemcpyAsync(hout, b.p, out_total, hipMemcpyDeviceToHost, st), "D2H");
-      return (int)FMX_OK;
-    });
-    if (rc != FMX_OK) return rc;
-    oo = 0;
-    for (int j = 0; j < nout; j++) {
-      if (outs[j].bytes && outs[j].dst) std::memcpy(outs[j].dst, hout + oo, outs[j].bytes);
-      oo += up16(outs[j].bytes);
-    }
-    return FMX_OK;
+    o = 0;
+    for (int j = 0; j < nout; j++) { dout[j] = obase + o; o += up16(outs[j].bytes); }
+  } else {
+    for (int j = 0; j < nin; j++) { void *p = nullptr; HIP_TRY(call.alloc(&p, ins[j].bytes), "hipMalloc"); din[j] = p; }
+    for (int j = 0; j < nout; j++) HIP_TRY(call.alloc(&dout[j], outs[j].bytes), "hipMalloc");
   }
-  DevBuf bufs[CallCtx::kBufs];
-  for (int j = 0; j < nin; j++) { HIP_TRY(call.alloc(bufs[j], ins[j].bytes), "hipMalloc"); din[j] = bufs[j].p; }
-  for (int j = 0; j < nout; j++) { HIP_TRY(call.alloc(bufs[nin + j], outs[j].bytes), "hipMalloc"); dout[j] = bufs[nin + j].p; }
-  return call.timed([&](hipStream_t st, EventPair &ev) {
-    for (int j = 0; j < nin; j++)
-      if (ins[j].bytes) HIP_TRY(hipMemcpyAsync(bufs[j].p, ins[j].src, ins[j].bytes, hipMemcpyHostToDevice, st), "H2D");
-    HIP_TRY(hipEventRecord(ev.a, st), "hipEventRecord");
+  rc = call.timed([&](hipStream_t st, hipEvent_t ev_a, hipEvent_t ev_b) {
+    if (!staged) {
+      for (int j = 0; j < nin; j++)
+        if (ins[j].bytes) HIP_TRY(hipMemcpyAsync(const_cast<void *>(din[j]), ins[j].src, ins[j].bytes, hipMemcpyHostToDevice, st), "H2D");
+    } else if (!tiny && in_total) {
+      HIP_TRY(hipMemcpyAsync(a, hin, in_total, hipMemcpyHostToDevice, st), "H2D");
+    }
+    if (ev_a) HIP_TRY(hipEventRecord(ev_a, st), "hipEventRecord");
     HIP_TRY(launch(st, din, dout), "kernel launch");
-    HIP_TRY(hipEventRecord(ev.b, st), "hipEventRecord");
-    for (int j = 0; j < nout; j++)
-      if (outs[j].bytes && outs[j].dst) HIP_TRY(hipMemcpyAsync(outs[j].dst, dout[j], outs[j].bytes, hipMemcpyDeviceToHost, st), "D2H");
+    if (ev_b) HIP_TRY(hipEventRecord(ev_b, st), "hipEventRecord");
+    if (!staged) {
+      for (int j = 0; j < nout; j++)
+        if (outs[j].bytes && outs[j].dst) HIP_TRY(hipMemcpyAsync(outs[j].dst, dout[j], outs[j].bytes, hipMemcpyDeviceToHost, st), "D2H");
+    } else if (!tiny && out_total) {
+      HIP_TRY(hipMemcpyAsync(hout, b, out_total, hipMemcpyDeviceToHost, st), "D2H");
+    }
     return (int)FMX_OK;
-  });
+  }, !tiny);
+  if (rc != FMX_OK || !staged) return rc;
+  size_t o = 0;
+  for (int j = 0; j < nout; j++) {
+    if (outs[j].bytes && outs[j].dst) std::memcpy(outs[j].dst, hout + o, outs[j].bytes);
+    o += up16(outs[j].bytes);
+  }
+  return FMX_OK;
 }
 
 }  // namespace fmx
@@ -473,9 +466,6 @@ extern "C" {
 
 const char *fmx_last_error(void) { return g_err.c_str(); }
 int fmx_abi_version(void) { return FMX_ABI_VERSION; }
-
-// fmx_config_set("pipeline", ..): large host batches in page-locked memory cut into chunks over three streams
-static std::atomic<int> g_pipeline{0};
 
 int fmx_config_set(const char *key, const char *value) {
   if (!key || !value) return arg_fail("null argument");
@@ -842,145 +832,112 @@ int fmx_occ_batch(const fmx_index *idx, const uint8_t *c, const int64_t *i, uint
   });
 }
 
-int fmx_search_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, uint64_t *sp, uint64_t *ep,
-                     size_t k) {
-  return fmx_search_batch_ex(idx, pat, off, sp, ep, k, nullptr);
+// ---- fmx_search_batch_ex: the checks, the batch they describe, and the three ways it travels
+constexpr size_t kPipelineMin = 128u << 10;       // patterns: smaller batches go through run_io
+
+struct HostBatch {
+  const uint8_t *pat = nullptr;           // the `total` pattern bytes in use (null: none)
+  const uint64_t *off = nullptr;          // k + 1 offsets into pat, the first 0 (null: k patterns of fixed_len bytes each)
+  std::vector<uint64_t> rebased;          // ... their storage where the caller's do not begin at 0
+  uint64_t total = 0, pack_cap = ~0ull;   // pack_cap != ~0: the 8-byte form into sp alone, an escape list of that many entries
+  size_t k = 0, out_words = 0;            // k == 0: nothing to search; out_words: u64 words of sp (k, or fmx_packed_words)
+  uint32_t fixed_len = 0, flags = 0;      // flags: kSearchMissNone
+  uint64_t *sp = nullptr, *ep = nullptr;
+  bool packed() const { return pack_cap != ~0ull; }
+  hipError_t launch(const Index *h, const void *d_pat, const void *d_off, void *d_sp, void *d_ep, hipStream_t st) const {
+    return launch_search(h, d_pat, off ? d_off : nullptr, d_sp, d_ep, k, st, fixed_len, pack_cap, flags);
+  }
+};
+
+static bool offsets_monotonic(const uint64_t *off, size_t a, size_t b) {      // off[a] <= off[a+1] <= .. <= off[b]
+  unsigned bad = 0;
+  for (size_t q = a; q < b; q++) bad |= off[q + 1] < off[q];
+  return bad == 0;
 }
 
-int fmx_search_batch_ex(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, uint64_t *sp, uint64_t *ep,
-                        size_t k, const fmx_search_opts *opts) {
-  const uint32_t fixed = opts ? opts->fixed_len : 0u;
+// (i) Whatever refuses a batch before a byte travels, in the order the failures are reported, and the batch as the paths
+// below take it (b->k == 0: an empty one, answered here).  The lean forms (round 4): equal-length patterns travel without
+// offsets (8 B per pattern less up the link) and the intervals come back in the 8-byte form (8 B per pattern less down):
+// 56 -> 40 B per 32-character pattern.
+// Offsets must be non-decreasing (a kernel would read a "negative" pattern as 2^64 bytes).  Walking a million of them on
+// the host takes 0.37 ms -- a quarter of a large call -- so large batches are checked where it is free: by a kernel on the
+// uploaded copy (search_whole_arrays), or chunk by chunk on the host while the uploads run (search_pipelined).
+static int search_batch_checks(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, uint64_t *sp, uint64_t *ep, size_t k,
+                               const fmx_search_opts *opts, HostBatch *b) {
   if (opts && (opts->packed & ~(FMX_SEARCH_PACKED | FMX_SEARCH_MISS_NONE))) return arg_fail("fmx_search_opts.packed: unknown bits");
+  const uint32_t fixed = b->fixed_len = opts ? opts->fixed_len : 0u;
   const bool packed = opts && (opts->packed & FMX_SEARCH_PACKED);
-  const uint32_t sflags = (opts && (opts->packed & FMX_SEARCH_MISS_NONE)) ? kSearchMissNone : 0u;
-  const size_t esc = packed ? (size_t)opts->escape_cap : 0;
   if (!idx || (k && ((!off && !fixed) || !sp || (!ep && !packed)))) return arg_fail("null argument");
-  const Index *h = H(idx);
-  int rc = use_device(h);
+  int rc = use_device(H(idx));
   if (rc) return rc;
   if (!k) { if (packed && sp) sp[0] = 0; return FMX_OK; }
-  if (fixed || packed || sflags) {
-    // ---- the lean forms of a host batch (round 4): equal-length patterns travel without offsets (8 B per pattern less
-    // up the link) and the intervals come back in the 8-byte form (8 B per pattern less down): 56 -> 40 B per
-    // 32-character pattern.  Whole arrays up, one chain of kernels, one array down, like the default path below.
-    uint64_t lo = 0, total = (uint64_t)fixed * k;
-    if (!fixed) {
-      unsigned bad = off[k] < off[0];
-      for (size_t q = 0; q < k; q++) bad |= off[q + 1] < off[q];
-      if (bad) return arg_fail("pattern offsets must be non-decreasing");
-      lo = off[0];
-      total = off[k] - off[0];
-    }
-    if (total && !pat) return arg_fail("pat is null");
-    const size_t out_words = packed ? fmx_packed_words(k, esc) : k;
-    if (k < (128u << 10) && !lo) {
-      HostIn ins[2] = {{total ? pat : nullptr, (size_t)total}, {off, fixed ? 0 : (k + 1) * 8}};
-      HostOut outs[2] = {{sp, out_words * 8}, {packed ? nullptr : ep, k * 8}};
-      return run_io(h, ins, 2, outs, 2, [&](hipStream_t st, const void *const *di, void *const *dout) {
-        return launch_search(h, di[0], fixed ? nullptr : di[1], dout[0], dout[1], k, st, fixed, packed ? (uint64_t)esc : ~0ull, sflags);
-      });
-    }
-    Call c0(h);
-    if ((rc = c0.init()) != FMX_OK) return rc;
-    DevBuf d_pat, d_off, d_sp, d_ep;
-    HIP_TRY(c0.alloc(d_pat, (size_t)total + 16), "hipMalloc");
-    HIP_TRY(c0.alloc(d_off, fixed ? 16 : (k + 1) * 8), "hipMalloc");
-    HIP_TRY(c0.alloc(d_sp, out_words * 8), "hipMalloc");
-    HIP_TRY(c0.alloc(d_ep, k * 8), "hipMalloc");
-    if (total) HIP_TRY(hipMemcpy(d_pat.p, pat + lo, (size_t)total, hipMemcpyHostToDevice), "H2D(patterns)");
-    if (!fixed) {
-      if (lo) {
-        std::vector<uint64_t> roff(k + 1);
-        for (size_t q = 0; q <= k; q++) roff[q] = off[q] - lo;
-        HIP_TRY(hipMemcpy(d_off.p, roff.data(), (k + 1) * 8, hipMemcpyHostToDevice), "H2D(offsets)");
-      } else {
-        HIP_TRY(hipMemcpy(d_off.p, off, (k + 1) * 8, hipMemcpyHostToDevice), "H2D(offsets)");
-      }
-    }
-    rc = c0.timed([&](hipStream_t st, EventPair &ev) {
-      HIP_TRY(hipEventRecord(ev.a, st), "hipEventRecord");
-      HIP_TRY(launch_search(h, d_pat.p, fixed ? nullptr : d_off.p, d_sp.p, d_ep.p, k, st, fixed, packed ? (uint64_t)esc : ~0ull, sflags), "k_search");
-      HIP_TRY(hipEventRecord(ev.b, st), "hipEventRecord");
-      return (int)FMX_OK;
-    });
-    if (rc != FMX_OK) return rc;
-    HIP_TRY(hipMemcpy(sp, d_sp.p, out_words * 8, hipMemcpyDeviceToHost), packed ? "D2H(packed)" : "D2H(sp)");
-    if (!packed) HIP_TRY(hipMemcpy(ep, d_ep.p, k * 8, hipMemcpyDeviceToHost), "D2H(ep)");
-    return FMX_OK;
+  uint64_t lo = 0;
+  b->total = (uint64_t)fixed * k;
+  if (!fixed) {
+    if ((k < kPipelineMin && !offsets_monotonic(off, 0, k)) || off[k] < off[0]) return arg_fail("pattern offsets must be non-decreasing");
+    lo = off[0];
+    b->total = off[k] - lo;
+    b->off = off;
   }
-  // Offsets must be non-decreasing (a kernel would read a "negative" pattern as 2^64 bytes).  Walking a million of
-  // them on the host takes 0.37 ms -- a quarter of a large call -- so large batches are checked where it is free:
-  // chunk by chunk on the host while the uploads run (page-locked buffers), or by a kernel on the uploaded copy.
-  constexpr size_t kPipelineMin = 128u << 10;     // patterns
-  auto monotonic = [&](size_t a, size_t b) {      // off[a] <= off[a+1] <= .. <= off[b]
-    unsigned bad = 0;
-    for (size_t q = a; q < b; q++) bad |= off[q + 1] < off[q];
-    return bad == 0;
-  };
-  if (k < kPipelineMin && !monotonic(0, k)) return arg_fail("pattern offsets must be non-decreasing");
-  if (off[k] < off[0]) return arg_fail("pattern offsets must be non-decreasing");
-  const uint64_t lo = off[0], total = off[k] - off[0];
-  if (total && !pat) return arg_fail("pat is null");
-  // offsets are rebased so that only the bytes in use travel
-  std::vector<uint64_t> roff;
-  const uint64_t *offp = off;
-  if (lo) {
-    roff.resize(k + 1);
-    for (size_t q = 0; q <= k; q++) roff[q] = off[q] - lo;
-    offp = roff.data();
+  if (b->total && !pat) return arg_fail("pat is null");
+  if (lo) {                             // offsets are rebased so that only the bytes in use travel
+    b->rebased.resize(k + 1);
+    for (size_t q = 0; q <= k; q++) b->rebased[q] = off[q] - lo;
+    b->off = b->rebased.data();
   }
-  // Small batches: one copy each way through run_io.  Large batches: whole arrays up with one synchronous copy each,
-  // one chain of kernels, whole arrays down (1.30 ms for 1M x 32 bytes here, from pageable and page-locked memory alike:
-  // the copies run at the link's 53 GB/s).  With fmx_config_set("pipeline", "on") large batches in page-locked caller
-  // memory (fmx_host_alloc, or the caller's own hipHostMalloc / registered pages) are pipelined instead: the batch is
-  // cut into chunks of patterns, chunk j's bytes and offsets go up on one stream, are searched on a second and come
-  // back on a third, so the copies of one chunk run beside the kernels of another and both directions of the link are
-  // busy.  Offsets stay absolute: every chunk is copied to its own place of one device image of the batch.  Off by
-  // default: on this platform asynchronous copies are slower than synchronous ones (one chunk, no overlap at all:
-  // 1.67 ms) and the overlap does not reliably win that back -- 1.08 to 1.7 ms with 4 chunks from box to box.
-  if (k < kPipelineMin) {
-    const HostIn ins[] = {{total ? pat + lo : nullptr, (size_t)total}, {offp, (k + 1) * 8}};
-    const HostOut outs[] = {{sp, k * 8}, {ep, k * 8}};
-    return run_io(h, ins, 2, outs, 2, [&](hipStream_t st, const void *const *di, void *const *dout) {
-      return launch_search(h, di[0], di[1], dout[0], dout[1], k, st);
-    });
+  b->pat = b->total ? pat + lo : nullptr;
+  b->k = k;
+  b->flags = (opts && (opts->packed & FMX_SEARCH_MISS_NONE)) ? kSearchMissNone : 0u;
+  if (packed) b->pack_cap = opts->escape_cap;
+  b->out_words = packed ? fmx_packed_words(k, (size_t)opts->escape_cap) : k;
+  b->sp = sp;
+  b->ep = ep;
+  return FMX_OK;
+}
+
+// (iii) Large batches: whole arrays up with one synchronous copy each, one chain of kernels, whole arrays down (1.30 ms for
+// 1M x 32 bytes here, from pageable and page-locked memory alike: the copies run at the link's 53 GB/s).  "Asynchronous"
+// copies of pageable caller memory are staged piecewise by the runtime and block the calling thread (measured: 8 chunks,
+// 0.37 ms each, nothing overlapped).
+static int search_whole_arrays(const Index *h, const HostBatch &b, Call &c0, void *d_pat, void *d_off, void *d_sp, void *d_ep) {
+  if (b.total) HIP_TRY(hipMemcpy(d_pat, b.pat, (size_t)b.total, hipMemcpyHostToDevice), "H2D(patterns)");
+  if (b.off) {
+    HIP_TRY(hipMemcpy(d_off, b.off, (b.k + 1) * 8, hipMemcpyHostToDevice), "H2D(offsets)");
+    bool ok = true;
+    HIP_TRY(check_offsets(h, d_off, b.k, c0.stream(), &ok), "k_check_offsets");
+    if (!ok) return arg_fail("pattern offsets must be non-decreasing");
   }
-  Call c0(h), c1(h), c2(h);
-  if ((rc = c0.init()) != FMX_OK || (rc = c1.init()) != FMX_OK || (rc = c2.init()) != FMX_OK) return rc;
-  DevBuf d_pat, d_off, d_sp, d_ep;
-  HIP_TRY(c0.alloc(d_pat, (size_t)total + 16), "hipMalloc");
-  HIP_TRY(c0.alloc(d_off, (k + 1) * 8), "hipMalloc");
-  HIP_TRY(c0.alloc(d_sp, k * 8), "hipMalloc");
-  HIP_TRY(c0.alloc(d_ep, k * 8), "hipMalloc");
-  auto pinned1 = [](const void *p) {
+  const int rc = c0.timed_launch([&](hipStream_t st) { return b.launch(h, d_pat, d_off, d_sp, d_ep, st); }, "k_search");
+  if (rc != FMX_OK) return rc;
+  HIP_TRY(hipMemcpy(b.sp, d_sp, b.out_words * 8, hipMemcpyDeviceToHost), b.packed() ? "D2H(packed)" : "D2H(sp)");
+  if (!b.packed()) HIP_TRY(hipMemcpy(b.ep, d_ep, b.k * 8, hipMemcpyDeviceToHost), "D2H(ep)");
+  return FMX_OK;
+}
+
+// Page-locked at both ends: a partly registered buffer must not take the asynchronous path.
+static bool host_pinned(const void *p, size_t bytes) {
+  auto pinned1 = [](const void *q) {
     hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (hipPointerGetAttributes(&a, q) != hipSuccess) { (void)hipGetLastError(); return false; }
     return a.type == hipMemoryTypeHost;
   };
-  // both ends of a buffer: a partly registered one must not take the asynchronous path
-  auto pinned = [&](const void *p, size_t bytes) {
-    return pinned1(p) && (bytes == 0 || pinned1(static_cast<const uint8_t *>(p) + bytes - 1));
-  };
-  if (!g_pipeline.load(std::memory_order_relaxed) || !(pinned(sp, k * 8) && pinned(ep, k * 8) && pinned(offp, (k + 1) * 8) && (!total || pinned(pat + lo, (size_t)total)))) {
-    // Pageable caller memory: "asynchronous" copies of it are staged piecewise by the runtime and block the calling
-    // thread (measured: 8 chunks, 0.37 ms each, nothing overlapped), while one synchronous copy per array runs at
-    // link speed.  So: whole arrays up, one kernel, whole arrays down.
-    if (total) HIP_TRY(hipMemcpy(d_pat.p, pat + lo, (size_t)total, hipMemcpyHostToDevice), "H2D(patterns)");
-    HIP_TRY(hipMemcpy(d_off.p, offp, (k + 1) * 8, hipMemcpyHostToDevice), "H2D(offsets)");
-    bool ok = true;
-    HIP_TRY(check_offsets(h, d_off.p, k, c0.stream(), &ok), "k_check_offsets");
-    if (!ok) return arg_fail("pattern offsets must be non-decreasing");
-    rc = c0.timed([&](hipStream_t st, EventPair &ev) {
-      HIP_TRY(hipEventRecord(ev.a, st), "hipEventRecord");
-      HIP_TRY(launch_search(h, d_pat.p, d_off.p, d_sp.p, d_ep.p, k, st), "k_search");
-      HIP_TRY(hipEventRecord(ev.b, st), "hipEventRecord");
-      return (int)FMX_OK;
-    });
-    if (rc != FMX_OK) return rc;
-    HIP_TRY(hipMemcpy(sp, d_sp.p, k * 8, hipMemcpyDeviceToHost), "D2H(sp)");
-    HIP_TRY(hipMemcpy(ep, d_ep.p, k * 8, hipMemcpyDeviceToHost), "D2H(ep)");
-    return FMX_OK;
-  }
+  return pinned1(p) && (bytes == 0 || pinned1(static_cast<const uint8_t *>(p) + bytes - 1));
+}
+
+// (iv) With fmx_config_set("pipeline", "on") large batches of the default form in page-locked caller memory (fmx_host_alloc,
+// or the caller's own hipHostMalloc / registered pages) are pipelined instead: the batch is cut into chunks of patterns,
+// chunk j's bytes and offsets go up on one stream, are searched on a second and come back on a third, so the copies of one
+// chunk run beside the kernels of another and both directions of the link are busy.  Offsets stay absolute: every chunk is
+// copied to its own place of one device image of the batch.  Off by default: on this platform asynchronous copies are
+// slower than synchronous ones (one chunk, no overlap at all: 1.67 ms) and the overlap does not reliably win that back --
+// 1.08 to 1.7 ms with 4 chunks from box to box.
+static int search_pipelined(const Index *h, const HostBatch &b, Call &c0, void *d_pat, void *d_off, void *d_sp, void *d_ep) {
+  const size_t k = b.k;
+  const uint64_t *offp = b.off, total = b.total;
+  uint64_t *sp = b.sp, *ep = b.ep;
+  Call c1(h), c2(h);
+  int rc;
+  if ((rc = c1.init()) != FMX_OK || (rc = c2.init()) != FMX_OK) return rc;
   static const size_t nchunk = [] { const char *e = getenv("FMX_PIPE_CHUNKS"); const int v = e ? atoi(e) : 4; return (size_t)(v < 1 ? 1 : (v > 64 ? 64 : v)); }();
   static const bool trace = getenv("FMX_TRACE") != nullptr;
   const auto t_begin = std::chrono::steady_clock::now();
@@ -1010,26 +967,26 @@ int fmx_search_batch_ex(const fmx_index *idx, const uint8_t *pat, const uint64_t
   HIP_TRY(hipEventRecord(c0.ev_a(), run), "hipEventRecord");
   HIP_TRY(hipStreamWaitEvent(up, c0.ev_a(), 0), "hipStreamWaitEvent");      // the buffers' previous users are done
   for (size_t j = 0; j < nchunk; j++) {
-    const size_t a = k * j / nchunk, b = k * (j + 1) / nchunk;
-    const uint64_t b0 = offp[a], b1 = offp[b];
+    const size_t a = k * j / nchunk, e = k * (j + 1) / nchunk;
+    const uint64_t b0 = offp[a], b1 = offp[e];
     if (b1 > b0)
-      HIP_TRY(hipMemcpyAsync((uint8_t *)d_pat.p + b0, pat + lo + b0, (size_t)(b1 - b0), hipMemcpyHostToDevice, up), "H2D(patterns)");
-    // chunk j needs offsets a .. b: entry b is also the next chunk's first, copied by both (same value)
-    HIP_TRY(hipMemcpyAsync((uint64_t *)d_off.p + a, offp + a, (b - a + 1) * 8, hipMemcpyHostToDevice, up), "H2D(offsets)");
+      HIP_TRY(hipMemcpyAsync((uint8_t *)d_pat + b0, b.pat + b0, (size_t)(b1 - b0), hipMemcpyHostToDevice, up), "H2D(patterns)");
+    // chunk j needs offsets a .. e: entry e is also the next chunk's first, copied by both (same value)
+    HIP_TRY(hipMemcpyAsync((uint64_t *)d_off + a, offp + a, (e - a + 1) * 8, hipMemcpyHostToDevice, up), "H2D(offsets)");
     HIP_TRY(hipEventRecord(cev[j], up), "hipEventRecord");
   }
   mark("uploads enqueued", nchunk);
   for (size_t j = 0; j < nchunk; j++) {
-    const size_t a = k * j / nchunk, b = k * (j + 1) / nchunk;
+    const size_t a = k * j / nchunk, e = k * (j + 1) / nchunk;
     HIP_TRY(hipStreamWaitEvent(run, cev[j], 0), "hipStreamWaitEvent");
-    if (a == b) continue;
-    if (!monotonic(a, b)) return arg_fail("pattern offsets must be non-decreasing");      // while the uploads are under way
-    HIP_TRY(launch_search(h, d_pat.p, (const uint64_t *)d_off.p + a, (uint64_t *)d_sp.p + a, (uint64_t *)d_ep.p + a, b - a, run),
+    if (a == e) continue;
+    if (!offsets_monotonic(offp, a, e)) return arg_fail("pattern offsets must be non-decreasing");      // while the uploads are under way
+    HIP_TRY(launch_search(h, d_pat, (const uint64_t *)d_off + a, (uint64_t *)d_sp + a, (uint64_t *)d_ep + a, e - a, run),
             "k_search");
     HIP_TRY(hipEventRecord(kev[j], run), "hipEventRecord");
     HIP_TRY(hipStreamWaitEvent(down, kev[j], 0), "hipStreamWaitEvent");
-    HIP_TRY(hipMemcpyAsync(sp + a, (uint64_t *)d_sp.p + a, (b - a) * 8, hipMemcpyDeviceToHost, down), "D2H(sp)");
-    HIP_TRY(hipMemcpyAsync(ep + a, (uint64_t *)d_ep.p + a, (b - a) * 8, hipMemcpyDeviceToHost, down), "D2H(ep)");
+    HIP_TRY(hipMemcpyAsync(sp + a, (uint64_t *)d_sp + a, (e - a) * 8, hipMemcpyDeviceToHost, down), "D2H(sp)");
+    HIP_TRY(hipMemcpyAsync(ep + a, (uint64_t *)d_ep + a, (e - a) * 8, hipMemcpyDeviceToHost, down), "D2H(ep)");
     mark("chunk enqueued", j);
   }
   HIP_TRY(hipEventRecord(c2.ev_a(), down), "hipEventRecord");
@@ -1045,6 +1002,38 @@ int fmx_search_batch_ex(const fmx_index *idx, const uint8_t *pat, const uint64_t
     h->launches += nchunk;
   }
   return FMX_OK;
+}
+
+int fmx_search_batch_ex(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, uint64_t *sp, uint64_t *ep,
+                        size_t k, const fmx_search_opts *opts) {
+  HostBatch b;
+  int rc = search_batch_checks(idx, pat, off, sp, ep, k, opts, &b);
+  if (rc != FMX_OK || !b.k) return rc;
+  const Index *h = H(idx);
+  if (k < kPipelineMin) {               // (ii) small batches: one copy each way
+    const HostIn ins[] = {{b.pat, (size_t)b.total}, {b.off, b.off ? (k + 1) * 8 : 0}};
+    const HostOut outs[] = {{sp, b.out_words * 8}, {b.packed() ? nullptr : ep, k * 8}};
+    return run_io(h, ins, 2, outs, 2, [&](hipStream_t st, const void *const *di, void *const *dout) {
+      return b.launch(h, di[0], di[1], dout[0], dout[1], st);
+    });
+  }
+  Call c0(h);
+  if ((rc = c0.init()) != FMX_OK) return rc;
+  void *d_pat = nullptr, *d_off = nullptr, *d_sp = nullptr, *d_ep = nullptr;
+  HIP_TRY(c0.alloc(&d_pat, (size_t)b.total + 16), "hipMalloc");
+  HIP_TRY(c0.alloc(&d_off, b.off ? (k + 1) * 8 : 16), "hipMalloc");
+  HIP_TRY(c0.alloc(&d_sp, b.out_words * 8), "hipMalloc");
+  HIP_TRY(c0.alloc(&d_ep, k * 8), "hipMalloc");
+  const bool lean = b.fixed_len || b.packed() || b.flags;
+  if (!lean && g_pipeline.load(std::memory_order_relaxed) && host_pinned(sp, k * 8) && host_pinned(ep, k * 8) &&
+      host_pinned(b.off, (k + 1) * 8) && (!b.total || host_pinned(b.pat, (size_t)b.total)))
+    return search_pipelined(h, b, c0, d_pat, d_off, d_sp, d_ep);
+  return search_whole_arrays(h, b, c0, d_pat, d_off, d_sp, d_ep);
+}
+
+int fmx_search_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, uint64_t *sp, uint64_t *ep,
+                     size_t k) {
+  return fmx_search_batch_ex(idx, pat, off, sp, ep, k, nullptr);
 }
 
 int fmx_search_batch_multi(fmx_index *const *idxs, size_t n_idx, const uint8_t *pat, const uint64_t *off,
@@ -1246,14 +1235,9 @@ int fmx_write_fm(const fmx_index *idx, const char *path) {
   if (rc) return rc;
   Call call(h);
   if ((rc = call.init()) != FMX_OK) return rc;
-  DevBuf dfm;
-  HIP_TRY(call.alloc(dfm, h->n * 4), "hipMalloc(fm)");
-  rc = call.timed([&](hipStream_t st, EventPair &ev) {
-    HIP_TRY(hipEventRecord(ev.a, st), "hipEventRecord");
-    HIP_TRY(launch_fm_fill(h, dfm.p, st), "k_fm_fill");
-    HIP_TRY(hipEventRecord(ev.b, st), "hipEventRecord");
-    return (int)FMX_OK;
-  });
+  void *dfm = nullptr;
+  HIP_TRY(call.alloc(&dfm, h->n * 4), "hipMalloc(fm)");
+  rc = call.timed_launch([&](hipStream_t st) { return launch_fm_fill(h, dfm, st); }, "k_fm_fill");
   if (rc) return rc;
   FILE *f = std::fopen(path, "wb");
   if (!f) { g_err = std::string("cannot create ") + path; return FMX_ERR_IO; }
@@ -1266,25 +1250,13 @@ int fmx_write_fm(const fmx_index *idx, const char *path) {
   std::vector<uint8_t> buf(std::min<uint64_t>(chunk, h->n * 4));
   for (uint64_t o = 0; o < h->n * 4; o += chunk) {
     const size_t len = (size_t)std::min<uint64_t>(chunk, h->n * 4 - o);
-    HIP_TRY(hipMemcpy(buf.data(), (const uint8_t *)dfm.p + o, len, hipMemcpyDeviceToHost), "D2H(fm)");
+    HIP_TRY(hipMemcpy(buf.data(), (const uint8_t *)dfm + o, len, hipMemcpyDeviceToHost), "D2H(fm)");
     if (std::fwrite(buf.data(), 1, len, f) != len) { g_err = "short write"; return FMX_ERR_IO; }
   }
   return FMX_OK;
 }
 
 // ---------------------------------------------------------------- locate (fmx_locate.hip; SALoader / SACreator / bwtFm2sa)
-// The samples are built here when a call finds none (under the handle's lock, as the select directory at the first Psi).
-static int locate_ready(const Index *h, hipStream_t st) {
-  {
-    std::lock_guard<std::mutex> lk(h->loc_mu);
-    if (h->loc_ready) return FMX_OK;
-  }
-  if (st) return locate_prepare(h, st);
-  CtxLease lease(h);
-  if (!lease.c) return FMX_ERR_HIP;
-  return locate_prepare(h, lease.c->stream);
-}
-
 int fmx_locate_batch(const fmx_index *idx, const uint64_t *rows, size_t k, uint64_t *out_pos) {
   if (!idx || (k && (!rows || !out_pos))) return arg_fail("null argument");
   const Index *h = H(idx);
@@ -1293,7 +1265,7 @@ int fmx_locate_batch(const fmx_index *idx, const uint64_t *rows, size_t k, uint6
   for (size_t q = 0; q < k; q++)
     if (rows[q] >= h->n) return arg_fail("row out of range (reference: SALoader reads past X.sa)");
   if ((rc = use_device(h)) || !k) return rc;
-  if ((rc = locate_ready(h, nullptr))) return rc;
+  if ((rc = ensure_built(h, h->loc_mu, h->loc_ready, locate_prepare, nullptr))) return rc;
   const HostIn ins[] = {{rows, k * 8}};
   const HostOut outs[] = {{out_pos, k * 8}};
   return run_io(h, ins, 1, outs, 1, [&](hipStream_t st, const void *const *di, void *const *dout) {
@@ -1307,7 +1279,7 @@ int fmx_locate_batch_dev(const fmx_index *idx, const void *d_rows, size_t k, voi
   int rc = locate_check(h);
   if (rc) return rc;
   if ((rc = use_device(h)) || !k) return rc;
-  if ((rc = locate_ready(h, (hipStream_t)stream))) return rc;
+  if ((rc = ensure_built(h, h->loc_mu, h->loc_ready, locate_prepare, (hipStream_t)stream))) return rc;
   HIP_TRY(launch_locate(h, d_rows, k, d_out_pos, (hipStream_t)stream), "k_locate");
   return FMX_OK;
 }
@@ -1345,7 +1317,7 @@ int fmx_locate_intervals_dev(const fmx_index *idx, const void *d_sp, const void 
   int rc = locate_check(h);
   if (rc) return rc;
   if ((rc = use_device(h))) return rc;
-  if ((rc = locate_ready(h, (hipStream_t)stream))) return rc;
+  if ((rc = ensure_built(h, h->loc_mu, h->loc_ready, locate_prepare, (hipStream_t)stream))) return rc;
   HIP_TRY(launch_locate_intervals(h, d_sp, d_ep, k, max_per, d_out_off, d_out_pos, cap, (hipStream_t)stream), "k_locate");
   return FMX_OK;
 }
@@ -1378,19 +1350,17 @@ int fmx_write_sa(const fmx_index *idx, const char *path) {
     g_err = "fmx_write_sa needs " + std::to_string(need) + " bytes of device memory, " + std::to_string((unsigned long long)free_b) + " are free";
     return FMX_ERR_NOMEM;
   }
-  struct Buf {
-    void *p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-  } d;
-  HIP_TRY(hipMalloc(&d.p, h->n * 4), "hipMalloc(sa)");
+  DevMem mem;
+  void *d_sa = nullptr;
+  HIP_TRY(mem.get(&d_sa, h->n * 4), "hipMalloc(sa)");
   CtxLease lease(h);
   if (!lease.c) return FMX_ERR_HIP;
-  if ((rc = locate_write_sa(h, lease.c->stream, (uint32_t *)d.p))) return rc;
+  if ((rc = locate_write_sa(h, lease.c->stream, (uint32_t *)d_sa))) return rc;
   const size_t chunk = 64u << 20;
   std::vector<uint8_t> buf(std::min<uint64_t>(chunk, h->n * 4));
   for (uint64_t o = 0; o < h->n * 4; o += chunk) {
     const size_t len = (size_t)std::min<uint64_t>(chunk, h->n * 4 - o);
-    HIP_TRY(hipMemcpy(buf.data(), (const uint8_t *)d.p + o, len, hipMemcpyDeviceToHost), "D2H(sa)");
+    HIP_TRY(hipMemcpy(buf.data(), (const uint8_t *)d_sa + o, len, hipMemcpyDeviceToHost), "D2H(sa)");
     if (std::fwrite(buf.data(), 1, len, f) != len) { g_err = "short write"; return FMX_ERR_IO; }
   }
   return FMX_OK;
@@ -1398,18 +1368,6 @@ int fmx_write_sa(const fmx_index *idx, const char *path) {
 
 // ---------------------------------------------------------------- LCP (fmx_lcp.hip; LCPSuffixWalkingAlgo / LCPLoader / LCPCreator)
 static thread_local double g_lcp_phases[3] = {0.0, 0.0, 0.0};
-
-// The array is built here when a call finds none (under the handle's lock, as the locate samples at the first locate).
-static int lcp_ready(const Index *h, hipStream_t st) {
-  {
-    std::lock_guard<std::mutex> lk(h->lcp_mu);
-    if (h->lcp_ready) return FMX_OK;
-  }
-  if (st) return lcp_prepare(h, st);
-  CtxLease lease(h);
-  if (!lease.c) return FMX_ERR_HIP;
-  return lcp_prepare(h, lease.c->stream);
-}
 
 int fmx_lcp_batch(const fmx_index *idx, const uint64_t *rows, size_t k, uint32_t *out) {
   if (!idx || (k && (!rows || !out))) return arg_fail("null argument");
@@ -1419,7 +1377,7 @@ int fmx_lcp_batch(const fmx_index *idx, const uint64_t *rows, size_t k, uint32_t
   for (size_t q = 0; q < k; q++)
     if (rows[q] >= h->n) return arg_fail("row out of range (reference: LCPLoader reads past X.lcp)");
   if ((rc = use_device(h)) || !k) return rc;
-  if ((rc = lcp_ready(h, nullptr))) return rc;
+  if ((rc = ensure_built(h, h->lcp_mu, h->lcp_ready, lcp_prepare, nullptr))) return rc;
   const HostIn ins[] = {{rows, k * 8}};
   const HostOut outs[] = {{out, k * 4}};
   return run_io(h, ins, 1, outs, 1, [&](hipStream_t st, const void *const *di, void *const *dout) {
@@ -1433,7 +1391,7 @@ int fmx_lcp_batch_dev(const fmx_index *idx, const void *d_rows, size_t k, void *
   int rc = lcp_check(h);
   if (rc) return rc;
   if ((rc = use_device(h)) || !k) return rc;
-  if ((rc = lcp_ready(h, (hipStream_t)stream))) return rc;
+  if ((rc = ensure_built(h, h->lcp_mu, h->lcp_ready, lcp_prepare, (hipStream_t)stream))) return rc;
   HIP_TRY(launch_lcp_gather(h, d_rows, k, d_out, (hipStream_t)stream), "k_lcp_rows");
   return FMX_OK;
 }
@@ -1452,7 +1410,7 @@ int fmx_lcp_range(const fmx_index *idx, uint64_t first, uint64_t count, uint32_t
   if (rc) return rc;
   const Index *h = H(idx);
   if ((rc = use_device(h)) || !count) return rc;
-  if ((rc = lcp_ready(h, nullptr))) return rc;
+  if ((rc = ensure_built(h, h->lcp_mu, h->lcp_ready, lcp_prepare, nullptr))) return rc;
   HIP_TRY(hipMemcpy(out, static_cast<const uint32_t *>(h->d_lcp) + first, count * 4, hipMemcpyDeviceToHost), "D2H(lcp)");
   return FMX_OK;
 }
@@ -1462,7 +1420,7 @@ int fmx_lcp_range_dev(const fmx_index *idx, uint64_t first, uint64_t count, void
   if (rc) return rc;
   const Index *h = H(idx);
   if ((rc = use_device(h)) || !count) return rc;
-  if ((rc = lcp_ready(h, (hipStream_t)stream))) return rc;
+  if ((rc = ensure_built(h, h->lcp_mu, h->lcp_ready, lcp_prepare, (hipStream_t)stream))) return rc;
   HIP_TRY(hipMemcpyAsync(d_out, static_cast<const uint32_t *>(h->d_lcp) + first, count * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream),
           "D2D(lcp)");
   return FMX_OK;
@@ -1488,7 +1446,7 @@ int fmx_write_lcp(const fmx_index *idx, const char *path) {
   int rc = lcp_check(h);
   if (rc) return rc;
   if ((rc = use_device(h))) return rc;
-  if ((rc = lcp_ready(h, nullptr))) return rc;
+  if ((rc = ensure_built(h, h->lcp_mu, h->lcp_ready, lcp_prepare, nullptr))) return rc;
   FILE *f = std::fopen(path, "wb");
   if (!f) { g_err = std::string("cannot create ") + path; return FMX_ERR_IO; }
   std::unique_ptr<FILE, int (*)(FILE *)> guard(f, std::fclose);
@@ -1528,29 +1486,10 @@ static int text_args(const void *text, uint64_t len, const uint8_t *host_text) {
   return FMX_OK;
 }
 
-static int use_text_device(int device) {
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev == 0) { g_err = "no HIP device available (libfmx has no CPU fallback)"; return FMX_ERR_HIP; }
-  if (device < 0 || device >= ndev) return arg_fail("device index out of range");
-  HIP_TRY(hipSetDevice(device), "hipSetDevice");
-  return FMX_OK;
-}
-
-static int not_capturing(hipStream_t st) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  HIP_TRY(hipStreamIsCapturing(st, &cs), "hipStreamIsCapturing");
-  if (cs != hipStreamCaptureStatusNone) {
-    g_err = "index construction allocates and synchronises: not under a stream capture";
-    return FMX_ERR_HIP;
-  }
-  return FMX_OK;
-}
-
 // The host-pointer forms: text to HBM, construction, BWT to `bwt_out` (host) or into a handle (fmx_open_text).
 static int text_to_device_bwt(const uint8_t *text, uint64_t len, int device, uint8_t *bwt_out, uint64_t *eof,
                               int64_t counts[256], fmx_index **idx_out) {
-  int rc = use_text_device(device);
+  int rc = use_device_index(device);
   if (rc) return rc;
   const uint64_t n = len + 1;
   size_t free_b = 0, total_b = 0;
@@ -1595,9 +1534,9 @@ int fmx_bwt_from_text_dev(const void *d_text, uint64_t len, void *d_bwt, void *d
   int rc = text_args(d_text, len, nullptr);
   if (rc) return rc;
   if (!d_bwt || !eof || !counts) return arg_fail("null argument");
-  if ((rc = use_text_device(device))) return rc;
+  if ((rc = use_device_index(device))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if ((rc = not_capturing(st))) return rc;
+  if ((rc = not_capturing(st, "index construction"))) return rc;
   return sufsort_bwt(d_text, len, d_bwt, d_sa_or_null, eof, counts, st, 0);
 }
 
@@ -1613,18 +1552,15 @@ static int lcp_from_device_text(const void *d_text, uint64_t len, const void *d_
             std::to_string((unsigned long long)free_b) + " are free";
     return FMX_ERR_NOMEM;
   }
-  struct Buf {
-    void *p = nullptr;
-    ~Buf() { if (p) (void)hipFree(p); }
-  } s;
-  hipError_t e = hipMalloc(&s.p, lcp_text_bytes(n));
-  if (e != hipSuccess) { g_err = std::string("hipMalloc(LCP): ") + hipGetErrorString(e); return FMX_ERR_NOMEM; }
+  DevMem mem;
+  uint8_t *s = nullptr;
+  DEV_ALLOC(mem, s, lcp_text_bytes(n), "LCP");
   int cus = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
-  lcp_reverse_text(static_cast<const uint8_t *>(d_text), len, static_cast<uint8_t *>(s.p), cus, st);
+  lcp_reverse_text(static_cast<const uint8_t *>(d_text), len, s, cus, st);
   HIP_TRY(hipGetLastError(), "k_lcp_reverse");
   LcpInfo info;
-  const int rc = lcp_core(static_cast<const uint8_t *>(s.p), n, static_cast<const uint32_t *>(d_sa), static_cast<uint32_t *>(d_lcp), cus, st,
+  const int rc = lcp_core(s, n, static_cast<const uint32_t *>(d_sa), static_cast<uint32_t *>(d_lcp), cus, st,
                           &info);
   if (rc) return rc;
   for (int i = 0; i < 3; i++) g_lcp_phases[i] = info.phase_ms[i];
@@ -1635,9 +1571,9 @@ int fmx_lcp_from_text_dev(const void *d_text, uint64_t len, const void *d_sa, vo
   if (!d_text || !d_sa || !d_lcp) return arg_fail("null argument");
   int rc = text_args(d_text, len, nullptr);
   if (rc) return rc;
-  if ((rc = use_text_device(device))) return rc;
+  if ((rc = use_device_index(device))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if ((rc = not_capturing(st))) return rc;
+  if ((rc = not_capturing(st, "index construction"))) return rc;
   return lcp_from_device_text(d_text, len, d_sa, d_lcp, device, st, 0);
 }
 
@@ -1645,7 +1581,7 @@ int fmx_lcp_from_text(const uint8_t *text, uint64_t len, uint32_t *lcp, int devi
   if (!text || !lcp) return arg_fail("null argument");
   int rc = text_args(text, len, text);
   if (rc) return rc;
-  if ((rc = use_text_device(device))) return rc;
+  if ((rc = use_device_index(device))) return rc;
   const uint64_t n = len + 1;
   size_t free_b = 0, total_b = 0;
   HIP_TRY(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");

@@ -99,12 +99,6 @@ struct CommSet {
   }
 };
 
-#define HIP_TRY(call, what)                            \
-  do {                                                 \
-    hipError_t e__ = (call);                           \
-    if (e__ != hipSuccess) return hip_fail(e__, what); \
-  } while (0)
-
 int add_streams(CommSet *c) {
   for (size_t i = 0; i < c->comm.size(); i++) {
     HIP_TRY(hipSetDevice(c->device[i]), "hipSetDevice");

@@ -331,22 +331,6 @@ struct Corpus {
 
 namespace {
 
-struct CoMem {                  // the temporaries of one call; freed on every return path
-  std::vector<void *> ps;
-  ~CoMem() { for (void *p : ps) (void)hipFree(p); }
-  hipError_t get(void **out, size_t bytes) {
-    *out = nullptr;
-    const hipError_t e = hipMalloc(out, bytes ? bytes : 16);
-    if (e == hipSuccess) ps.push_back(*out);
-    return e;
-  }
-};
-
-struct CoStream {
-  hipStream_t s = nullptr;
-  ~CoStream() { if (s) (void)hipStreamDestroy(s); }
-};
-
 int co_arg(const char *msg) {
   set_error(msg);
   return FMX_ERR_ARG;
@@ -355,29 +339,6 @@ int co_arg(const char *msg) {
 unsigned co_grid(uint64_t m) {
   const uint64_t b = (m + kCoThreads - 1) / kCoThreads;
   return (unsigned)(b < 1 ? 1 : b > 8192 ? 8192 : b);
-}
-
-int co_use_device(int device) {
-  int ndev = 0;
-  const hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev == 0) {
-    set_error("no HIP device available (libfmx has no CPU fallback)");
-    return FMX_ERR_HIP;
-  }
-  if (device < 0 || device >= ndev) return co_arg("device index out of range");
-  if ((hipSetDevice(device)) != hipSuccess) return hip_fail(hipGetLastError(), "hipSetDevice");
-  return FMX_OK;
-}
-
-int co_not_capturing(hipStream_t st, const char *what) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  const hipError_t e = hipStreamIsCapturing(st, &cs);
-  if (e != hipSuccess) return hip_fail(e, "hipStreamIsCapturing");
-  if (cs != hipStreamCaptureStatusNone) {
-    set_error(std::string(what) + " allocates and synchronises: not under a stream capture");
-    return FMX_ERR_HIP;
-  }
-  return FMX_OK;
 }
 
 int co_room(uint64_t need, const char *what) {
@@ -391,20 +352,6 @@ int co_room(uint64_t need, const char *what) {
   }
   return FMX_OK;
 }
-
-#define CO_TRY(call, what)                                        \
-  do {                                                            \
-    const hipError_t e__ = (call);                                \
-    if (e__ != hipSuccess) return hip_fail(e__, what);            \
-  } while (0)
-#define CO_ALLOC(mem, p, bytes)                                                          \
-  do {                                                                                   \
-    const hipError_t e__ = (mem).get((void **)&(p), (bytes));                            \
-    if (e__ != hipSuccess) {                                                             \
-      set_error(std::string("hipMalloc(corpus): ") + hipGetErrorString(e__));            \
-      return FMX_ERR_NOMEM;                                                              \
-    }                                                                                    \
-  } while (0)
 
 int co_check_ends(const uint64_t *ends, uint64_t n_docs, uint64_t raw_len) {
   if (n_docs < 1) return co_arg("a corpus has at least one document");
@@ -427,8 +374,8 @@ int co_check_ends(const uint64_t *ends, uint64_t n_docs, uint64_t raw_len) {
 int co_finish(Corpus *c, hipStream_t st) {
   hipLaunchKernelGGL(k_corpus_doc_esc, dim3(co_grid(c->n_docs + 1)), dim3(kCoThreads), 0, st, c->d_doc_start, c->n_docs,
                      c->d_esc_pos, c->n_esc, c->d_doc_esc);
-  CO_TRY(hipGetLastError(), "k_corpus_doc_esc");
-  CO_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+  HIP_TRY(hipGetLastError(), "k_corpus_doc_esc");
+  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
   return FMX_OK;
 }
 
@@ -442,23 +389,23 @@ int co_build(const uint8_t *d_raw, uint64_t raw_len, const uint64_t *ends, uint6
   // the stream is raw_len + n_docs + escapes bytes: what is known before the count pass is checked now, the rest after it
   int rc = co_room(tmp + raw_len + n_docs + 8 * (n_docs + 1) + 4096, "the corpus stream");
   if (rc) return rc;
-  CoMem mem;
+  DevMem mem;
   unsigned long long *d_ends = nullptr;
   uint32_t *esc_cnt = nullptr, *tile_doc = nullptr, *partials = nullptr;
-  CO_ALLOC(mem, d_ends, 8 * n_docs);
-  CO_ALLOC(mem, esc_cnt, 4 * (ntiles + 1));
-  CO_ALLOC(mem, tile_doc, 4 * ntiles);
-  CO_ALLOC(mem, partials, 4 * parts);
-  CO_TRY(hipMemcpyAsync(d_ends, ends, 8 * n_docs, hipMemcpyHostToDevice, st), "H2D(ends)");
+  DEV_ALLOC(mem, d_ends, 8 * n_docs, "corpus");
+  DEV_ALLOC(mem, esc_cnt, 4 * (ntiles + 1), "corpus");
+  DEV_ALLOC(mem, tile_doc, 4 * ntiles, "corpus");
+  DEV_ALLOC(mem, partials, 4 * parts, "corpus");
+  HIP_TRY(hipMemcpyAsync(d_ends, ends, 8 * n_docs, hipMemcpyHostToDevice, st), "H2D(ends)");
   const int aligned = (reinterpret_cast<uintptr_t>(d_raw) & 15u) == 0 ? 1 : 0;
   const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, 4096);
   hipLaunchKernelGGL(k_corpus_count, dim3(grid), dim3(kCoThreads), 0, st, d_raw, raw_len, aligned, d_ends, n_docs, ntiles, esc_cnt,
                      tile_doc);
-  CO_TRY(hipGetLastError(), "k_corpus_count");
-  CO_TRY(scan_u32(esc_cnt, ntiles + 1, kScanSum, true, partials, st), "scan");
+  HIP_TRY(hipGetLastError(), "k_corpus_count");
+  HIP_TRY(scan_u32(esc_cnt, ntiles + 1, kScanSum, true, partials, st), "scan");
   uint32_t n_esc = 0;
-  CO_TRY(hipMemcpyAsync(&n_esc, esc_cnt + ntiles, 4, hipMemcpyDeviceToHost, st), "D2H");
-  CO_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+  HIP_TRY(hipMemcpyAsync(&n_esc, esc_cnt + ntiles, 4, hipMemcpyDeviceToHost, st), "D2H");
+  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
   const uint64_t stream_len = raw_len + n_esc + n_docs;
   if (stream_len > kCoMaxStream) {
     set_error("the corpus stream would be " + std::to_string(stream_len) + " bytes: at most 2^32 - 2 (the suffix sort's limit)");
@@ -480,7 +427,7 @@ int co_build(const uint8_t *d_raw, uint64_t raw_len, const uint64_t *ends, uint6
   }
   hipLaunchKernelGGL(k_corpus_emit, dim3(grid), dim3(kCoThreads), 0, st, d_raw, raw_len, aligned, d_ends, n_docs, ntiles, esc_cnt,
                      tile_doc, c->d_stream, c->d_doc_start, c->d_esc_pos);
-  CO_TRY(hipGetLastError(), "k_corpus_emit");
+  HIP_TRY(hipGetLastError(), "k_corpus_emit");
   if ((rc = co_finish(c.get(), st))) return rc;
   c->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   *out = c.release();
@@ -491,7 +438,7 @@ inline Corpus *C(fmx_corpus *p) { return reinterpret_cast<Corpus *>(p); }
 inline const Corpus *C(const fmx_corpus *p) { return reinterpret_cast<const Corpus *>(p); }
 
 int co_use(const Corpus *c) {
-  CO_TRY(hipSetDevice(c->device), "hipSetDevice");
+  HIP_TRY(hipSetDevice(c->device), "hipSetDevice");
   return FMX_OK;
 }
 
@@ -509,9 +456,9 @@ int fmx_corpus_build_dev(const void *d_raw, uint64_t raw_len, const uint64_t *do
   if (raw_len && !d_raw) return co_arg("null argument");
   int rc = co_check_ends(doc_ends, n_docs, raw_len);
   if (rc) return rc;
-  if ((rc = co_use_device(device))) return rc;
+  if ((rc = use_device_index(device))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if ((rc = co_not_capturing(st, "a corpus build"))) return rc;
+  if ((rc = not_capturing(st, "a corpus build"))) return rc;
   Corpus *c = nullptr;
   if ((rc = co_build(static_cast<const uint8_t *>(d_raw), raw_len, doc_ends, n_docs, device, st, &c))) return rc;
   *out = reinterpret_cast<fmx_corpus *>(c);
@@ -525,14 +472,14 @@ int fmx_corpus_build(const uint8_t *raw, uint64_t raw_len, const uint64_t *doc_e
   if (raw_len && !raw) return co_arg("null argument");
   int rc = co_check_ends(doc_ends, n_docs, raw_len);
   if (rc) return rc;
-  if ((rc = co_use_device(device))) return rc;
+  if ((rc = use_device_index(device))) return rc;
   if ((rc = co_room(2 * raw_len + 9 * n_docs + 4096, "the corpus stream"))) return rc;
-  CoMem mem;
-  CoStream own;
-  CO_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
+  DevMem mem;
+  StreamGuard own;
+  HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
   uint8_t *d_raw = nullptr;
-  CO_ALLOC(mem, d_raw, raw_len);
-  if (raw_len) CO_TRY(hipMemcpyAsync(d_raw, raw, raw_len, hipMemcpyHostToDevice, own.s), "H2D(raw)");
+  DEV_ALLOC(mem, d_raw, raw_len, "corpus");
+  if (raw_len) HIP_TRY(hipMemcpyAsync(d_raw, raw, raw_len, hipMemcpyHostToDevice, own.s), "H2D(raw)");
   Corpus *c = nullptr;
   const auto t0 = std::chrono::steady_clock::now();
   if ((rc = co_build(d_raw, raw_len, doc_ends, n_docs, device, own.s, &c))) return rc;
@@ -580,7 +527,7 @@ int fmx_corpus_stream(const fmx_corpus *corpus, uint8_t *out, uint64_t cap) {
   }
   int rc = co_use(c);
   if (rc) return rc;
-  CO_TRY(hipMemcpy(out, c->d_stream, c->stream_len, hipMemcpyDeviceToHost), "D2H(stream)");
+  HIP_TRY(hipMemcpy(out, c->d_stream, c->stream_len, hipMemcpyDeviceToHost), "D2H(stream)");
   return FMX_OK;
 }
 
@@ -604,12 +551,12 @@ int fmx_corpus_open_index(const fmx_corpus *corpus, void *stream, fmx_index **ou
   int rc = co_use(c);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if ((rc = co_not_capturing(st, "index construction"))) return rc;
+  if ((rc = not_capturing(st, "index construction"))) return rc;
   const uint64_t n = c->stream_len + 1;
   if ((rc = co_room(sufsort_peak_bytes(c->stream_len, false) + n, "the index of the corpus stream"))) return rc;
-  CoMem mem;
+  DevMem mem;
   uint8_t *d_bwt = nullptr;
-  CO_ALLOC(mem, d_bwt, n);
+  DEV_ALLOC(mem, d_bwt, n, "corpus");
   uint64_t eof = 0;
   int64_t counts[256];
   if ((rc = fmx_bwt_from_text_dev(c->d_stream, c->stream_len, d_bwt, nullptr, &eof, counts, c->device, stream))) return rc;
@@ -622,15 +569,15 @@ int fmx_corpus_tables(const fmx_corpus *corpus, uint64_t *doc_start, uint64_t *r
   int rc = co_use(c);
   if (rc) return rc;
   std::vector<uint32_t> ds(c->n_docs + 1), de(c->n_docs + 1);
-  CO_TRY(hipMemcpy(ds.data(), c->d_doc_start, 4 * (c->n_docs + 1), hipMemcpyDeviceToHost), "D2H(doc_start)");
-  CO_TRY(hipMemcpy(de.data(), c->d_doc_esc, 4 * (c->n_docs + 1), hipMemcpyDeviceToHost), "D2H(doc_esc)");
+  HIP_TRY(hipMemcpy(ds.data(), c->d_doc_start, 4 * (c->n_docs + 1), hipMemcpyDeviceToHost), "D2H(doc_start)");
+  HIP_TRY(hipMemcpy(de.data(), c->d_doc_esc, 4 * (c->n_docs + 1), hipMemcpyDeviceToHost), "D2H(doc_esc)");
   for (uint64_t d = 0; d <= c->n_docs; d++) {
     if (doc_start) doc_start[d] = ds[d];
     if (raw_len && d < c->n_docs) raw_len[d] = (uint64_t)(ds[d + 1] - ds[d] - 1) - (de[d + 1] - de[d]);
   }
   if (esc_pos && c->n_esc) {
     std::vector<uint32_t> ep(c->n_esc);
-    CO_TRY(hipMemcpy(ep.data(), c->d_esc_pos, 4 * c->n_esc, hipMemcpyDeviceToHost), "D2H(esc_pos)");
+    HIP_TRY(hipMemcpy(ep.data(), c->d_esc_pos, 4 * c->n_esc, hipMemcpyDeviceToHost), "D2H(esc_pos)");
     for (uint64_t i = 0; i < c->n_esc; i++) esc_pos[i] = ep[i];
   }
   return FMX_OK;
@@ -664,7 +611,7 @@ int fmx_corpus_from_tables(const uint64_t *doc_start, const uint64_t *raw_len, c
     ds[d] = (uint32_t)doc_start[d];
   }
   ds[n_docs] = (uint32_t)doc_start[n_docs];
-  int rc = co_use_device(device);
+  int rc = use_device_index(device);
   if (rc) return rc;
   if ((rc = co_room(8 * (n_docs + 1) + 4 * n_esc + 4096, "the corpus map"))) return rc;
   std::unique_ptr<Corpus> c(new Corpus);
@@ -679,8 +626,8 @@ int fmx_corpus_from_tables(const uint64_t *doc_start, const uint64_t *raw_len, c
     set_error(std::string("hipMalloc(corpus): ") + hipGetErrorString(he));
     return FMX_ERR_NOMEM;
   }
-  CO_TRY(hipMemcpy(c->d_doc_start, ds.data(), 4 * ds.size(), hipMemcpyHostToDevice), "H2D(doc_start)");
-  CO_TRY(hipMemcpy(c->d_esc_pos, ep.data(), 4 * ep.size(), hipMemcpyHostToDevice), "H2D(esc_pos)");
+  HIP_TRY(hipMemcpy(c->d_doc_start, ds.data(), 4 * ds.size(), hipMemcpyHostToDevice), "H2D(doc_start)");
+  HIP_TRY(hipMemcpy(c->d_esc_pos, ep.data(), 4 * ep.size(), hipMemcpyHostToDevice), "H2D(esc_pos)");
   if ((rc = co_finish(c.get(), nullptr))) return rc;
   *out = reinterpret_cast<fmx_corpus *>(c.release());
   return FMX_OK;
@@ -695,7 +642,7 @@ int fmx_corpus_map_dev(const fmx_corpus *corpus, const void *d_pos, size_t k, vo
   hipLaunchKernelGGL(k_corpus_map, dim3(co_grid(k)), dim3(kCoThreads), 0, (hipStream_t)stream, c->map(),
                      static_cast<const unsigned long long *>(d_pos), (uint64_t)k, static_cast<uint32_t *>(d_doc),
                      static_cast<unsigned long long *>(d_esc_off), static_cast<unsigned long long *>(d_raw_off));
-  CO_TRY(hipGetLastError(), "k_corpus_map");
+  HIP_TRY(hipGetLastError(), "k_corpus_map");
   return FMX_OK;
 }
 
@@ -705,18 +652,18 @@ int fmx_corpus_map(const fmx_corpus *corpus, const uint64_t *pos, size_t k, uint
   int rc = co_use(c);
   if (rc || !k) return rc;
   if ((rc = co_room(28 * (uint64_t)k + 4096, "a corpus map call"))) return rc;
-  CoMem mem;
+  DevMem mem;
   unsigned long long *d_pos = nullptr, *d_eo = nullptr, *d_ro = nullptr;
   uint32_t *d_doc = nullptr;
-  CO_ALLOC(mem, d_pos, 8 * k);
-  CO_ALLOC(mem, d_eo, 8 * k);
-  CO_ALLOC(mem, d_ro, 8 * k);
-  CO_ALLOC(mem, d_doc, 4 * k);
-  CO_TRY(hipMemcpy(d_pos, pos, 8 * k, hipMemcpyHostToDevice), "H2D(pos)");
+  DEV_ALLOC(mem, d_pos, 8 * k, "corpus");
+  DEV_ALLOC(mem, d_eo, 8 * k, "corpus");
+  DEV_ALLOC(mem, d_ro, 8 * k, "corpus");
+  DEV_ALLOC(mem, d_doc, 4 * k, "corpus");
+  HIP_TRY(hipMemcpy(d_pos, pos, 8 * k, hipMemcpyHostToDevice), "H2D(pos)");
   if ((rc = fmx_corpus_map_dev(corpus, d_pos, k, d_doc, d_eo, d_ro, nullptr))) return rc;
-  CO_TRY(hipMemcpy(doc, d_doc, 4 * k, hipMemcpyDeviceToHost), "D2H(doc)");
-  CO_TRY(hipMemcpy(esc_off, d_eo, 8 * k, hipMemcpyDeviceToHost), "D2H(esc_off)");
-  CO_TRY(hipMemcpy(raw_off, d_ro, 8 * k, hipMemcpyDeviceToHost), "D2H(raw_off)");
+  HIP_TRY(hipMemcpy(doc, d_doc, 4 * k, hipMemcpyDeviceToHost), "D2H(doc)");
+  HIP_TRY(hipMemcpy(esc_off, d_eo, 8 * k, hipMemcpyDeviceToHost), "D2H(esc_off)");
+  HIP_TRY(hipMemcpy(raw_off, d_ro, 8 * k, hipMemcpyDeviceToHost), "D2H(raw_off)");
   return FMX_OK;
 }
 
@@ -743,19 +690,19 @@ int fmx_corpus_doc_list_dev(const fmx_corpus *corpus, const fmx_index *idx, cons
   if ((uint64_t)k >= 0xffffffffull) return co_arg("too many intervals");
   if ((rc = co_use(c))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if ((rc = co_not_capturing(st, "a document listing"))) return rc;
+  if ((rc = not_capturing(st, "a document listing"))) return rc;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 5; i++) if (ev[i]) (void)hipEventDestroy(ev[i]); } } evg{ev};
-  for (int i = 0; i < 5; i++) CO_TRY(hipEventCreate(&ev[i]), "hipEventCreate");
-  CoMem mem;
+  for (int i = 0; i < 5; i++) HIP_TRY(hipEventCreate(&ev[i]), "hipEventCreate");
+  DevMem mem;
   unsigned long long *loc_off = nullptr;
   if ((rc = co_room(8 * ((uint64_t)k + 1) + 4096, "a document listing"))) return rc;
-  CO_ALLOC(mem, loc_off, 8 * ((uint64_t)k + 1));
+  DEV_ALLOC(mem, loc_off, 8 * ((uint64_t)k + 1), "corpus");
   // the row counts first (no positions: cap 0), then room for exactly that many
   if ((rc = fmx_locate_intervals_dev(idx, d_sp, d_ep, k, max_per, loc_off, nullptr, 0, stream))) return rc;
   unsigned long long rows = 0;
-  CO_TRY(hipMemcpyAsync(&rows, loc_off + k, 8, hipMemcpyDeviceToHost, st), "D2H");
-  CO_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+  HIP_TRY(hipMemcpyAsync(&rows, loc_off + k, 8, hipMemcpyDeviceToHost, st), "D2H");
+  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
   if (rows >= 0xffffffffull) {
     set_error("document listing of " + std::to_string(rows) + " rows: at most 2^32 - 2 per call (use max_per)");
     return FMX_ERR_UNSUPPORTED;
@@ -767,7 +714,7 @@ int fmx_corpus_doc_list_dev(const fmx_corpus *corpus, const fmx_index *idx, cons
   if (rows == 0) {
     hipLaunchKernelGGL(k_corpus_list_off, dim3(co_grid(k + 1)), dim3(kCoThreads), 0, st, nullptr, 0ull, nullptr, (uint64_t)k,
                        doc_bits, static_cast<unsigned long long *>(d_out_off));
-    CO_TRY(hipGetLastError(), "k_corpus_list_off");
+    HIP_TRY(hipGetLastError(), "k_corpus_list_off");
     for (double &p : g_list_phases) p = 0.0;
     return FMX_OK;
   }
@@ -775,39 +722,39 @@ int fmx_corpus_doc_list_dev(const fmx_corpus *corpus, const fmx_index *idx, cons
   if ((rc = co_room(8 * rows + 16 * rows + 8 * rows + 4 * hist_words + 4 * parts + 8192, "a document listing"))) return rc;
   unsigned long long *pos = nullptr, *k0 = nullptr, *k1 = nullptr;
   uint32_t *v0 = nullptr, *v1 = nullptr, *hist = nullptr, *partials = nullptr;
-  CO_ALLOC(mem, pos, 8 * rows);
-  CO_ALLOC(mem, k0, 8 * rows);
-  CO_ALLOC(mem, k1, 8 * rows);
-  CO_ALLOC(mem, v0, 4 * rows);
-  CO_ALLOC(mem, v1, 4 * rows);
-  CO_ALLOC(mem, hist, 4 * hist_words);
-  CO_ALLOC(mem, partials, 4 * parts);
-  CO_TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+  DEV_ALLOC(mem, pos, 8 * rows, "corpus");
+  DEV_ALLOC(mem, k0, 8 * rows, "corpus");
+  DEV_ALLOC(mem, k1, 8 * rows, "corpus");
+  DEV_ALLOC(mem, v0, 4 * rows, "corpus");
+  DEV_ALLOC(mem, v1, 4 * rows, "corpus");
+  DEV_ALLOC(mem, hist, 4 * hist_words, "corpus");
+  DEV_ALLOC(mem, partials, 4 * parts, "corpus");
+  HIP_TRY(hipEventRecord(ev[0], st), "hipEventRecord");
   if ((rc = fmx_locate_intervals_dev(idx, d_sp, d_ep, k, max_per, loc_off, pos, rows, stream))) return rc;
-  CO_TRY(hipEventRecord(ev[1], st), "hipEventRecord");
+  HIP_TRY(hipEventRecord(ev[1], st), "hipEventRecord");
   hipLaunchKernelGGL(k_corpus_list_keys, dim3(co_grid(rows)), dim3(kCoThreads), 0, st, c->map(), pos, (uint64_t)rows, loc_off,
                      (uint64_t)k, pat_len, doc_bits, k0, v0);
-  CO_TRY(hipGetLastError(), "k_corpus_list_keys");
-  CO_TRY(hipEventRecord(ev[2], st), "hipEventRecord");
+  HIP_TRY(hipGetLastError(), "k_corpus_list_keys");
+  HIP_TRY(hipEventRecord(ev[2], st), "hipEventRecord");
   unsigned long long *key = k0, *key_alt = k1;
   uint32_t *val = v0, *val_alt = v1;
   int passes = 0;
-  CO_TRY(radix_sort(&key, &val, &key_alt, &val_alt, rows, doc_bits + k_bits, hist, partials, st, &passes), "radix sort");
-  CO_TRY(hipEventRecord(ev[3], st), "hipEventRecord");
+  HIP_TRY(radix_sort(&key, &val, &key_alt, &val_alt, rows, doc_bits + k_bits, hist, partials, st, &passes), "radix sort");
+  HIP_TRY(hipEventRecord(ev[3], st), "hipEventRecord");
   uint32_t *head = reinterpret_cast<uint32_t *>(key_alt);           // the free key buffer holds the head flags
   hipLaunchKernelGGL(k_corpus_list_heads, dim3(co_grid(rows)), dim3(kCoThreads), 0, st, key, (uint64_t)rows, head);
-  CO_TRY(hipGetLastError(), "k_corpus_list_heads");
-  CO_TRY(scan_u32(head, rows, kScanSum, false, partials, st), "scan");
+  HIP_TRY(hipGetLastError(), "k_corpus_list_heads");
+  HIP_TRY(scan_u32(head, rows, kScanSum, false, partials, st), "scan");
   hipLaunchKernelGGL(k_corpus_list_off, dim3(co_grid(k + 1)), dim3(kCoThreads), 0, st, key, (uint64_t)rows, head, (uint64_t)k, doc_bits,
                      static_cast<unsigned long long *>(d_out_off));
-  CO_TRY(hipGetLastError(), "k_corpus_list_off");
+  HIP_TRY(hipGetLastError(), "k_corpus_list_off");
   if (cap) {
     hipLaunchKernelGGL(k_corpus_list_emit, dim3(co_grid(rows)), dim3(kCoThreads), 0, st, key, (uint64_t)rows, head, doc_bits, c->n_docs,
                        (uint64_t)cap, static_cast<uint32_t *>(d_out_doc), static_cast<uint32_t *>(d_out_cnt));
-    CO_TRY(hipGetLastError(), "k_corpus_list_emit");
+    HIP_TRY(hipGetLastError(), "k_corpus_list_emit");
   }
-  CO_TRY(hipEventRecord(ev[4], st), "hipEventRecord");
-  CO_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");        // the temporaries go when this returns
+  HIP_TRY(hipEventRecord(ev[4], st), "hipEventRecord");
+  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");        // the temporaries go when this returns
   for (int i = 0; i < 4; i++) {
     float ms = 0;
     (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
@@ -827,28 +774,28 @@ int fmx_corpus_doc_list(const fmx_corpus *corpus, const fmx_index *idx, const ui
     if (sp[i] > n || ep[i] > n) return co_arg("interval out of range (sp, ep <= n)");
   if ((rc = co_use(c))) return rc;
   if ((rc = co_room(24 * (uint64_t)k + 8 * (uint64_t)cap + 8192, "a document listing"))) return rc;
-  CoMem mem;
-  CoStream own;
-  CO_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
+  DevMem mem;
+  StreamGuard own;
+  HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
   unsigned long long *d_sp = nullptr, *d_ep = nullptr, *d_off = nullptr;
   uint32_t *d_doc = nullptr, *d_cnt = nullptr;
-  CO_ALLOC(mem, d_sp, 8 * k);
-  CO_ALLOC(mem, d_ep, 8 * k);
-  CO_ALLOC(mem, d_off, 8 * (k + 1));
-  CO_ALLOC(mem, d_doc, 4 * cap);
-  CO_ALLOC(mem, d_cnt, 4 * cap);
+  DEV_ALLOC(mem, d_sp, 8 * k, "corpus");
+  DEV_ALLOC(mem, d_ep, 8 * k, "corpus");
+  DEV_ALLOC(mem, d_off, 8 * (k + 1), "corpus");
+  DEV_ALLOC(mem, d_doc, 4 * cap, "corpus");
+  DEV_ALLOC(mem, d_cnt, 4 * cap, "corpus");
   if (k) {
-    CO_TRY(hipMemcpyAsync(d_sp, sp, 8 * k, hipMemcpyHostToDevice, own.s), "H2D(sp)");
-    CO_TRY(hipMemcpyAsync(d_ep, ep, 8 * k, hipMemcpyHostToDevice, own.s), "H2D(ep)");
+    HIP_TRY(hipMemcpyAsync(d_sp, sp, 8 * k, hipMemcpyHostToDevice, own.s), "H2D(sp)");
+    HIP_TRY(hipMemcpyAsync(d_ep, ep, 8 * k, hipMemcpyHostToDevice, own.s), "H2D(ep)");
   }
   if ((rc = fmx_corpus_doc_list_dev(corpus, idx, d_sp, d_ep, k, pat_len, max_per, d_off, d_doc, d_cnt, cap, own.s))) return rc;
-  CO_TRY(hipMemcpyAsync(out_off, d_off, 8 * (k + 1), hipMemcpyDeviceToHost, own.s), "D2H(off)");
-  CO_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
+  HIP_TRY(hipMemcpyAsync(out_off, d_off, 8 * (k + 1), hipMemcpyDeviceToHost, own.s), "D2H(off)");
+  HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
   const uint64_t total = out_off[k], m = std::min<uint64_t>(total, cap);
   if (m) {
-    CO_TRY(hipMemcpyAsync(out_doc, d_doc, 4 * m, hipMemcpyDeviceToHost, own.s), "D2H(doc)");
-    CO_TRY(hipMemcpyAsync(out_cnt, d_cnt, 4 * m, hipMemcpyDeviceToHost, own.s), "D2H(cnt)");
-    CO_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
+    HIP_TRY(hipMemcpyAsync(out_doc, d_doc, 4 * m, hipMemcpyDeviceToHost, own.s), "D2H(doc)");
+    HIP_TRY(hipMemcpyAsync(out_cnt, d_cnt, 4 * m, hipMemcpyDeviceToHost, own.s), "D2H(cnt)");
+    HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
   }
   if (total > cap) {
     set_error("corpus_doc_list: " + std::to_string(total) + " (interval, document) pairs, room for " + std::to_string(cap));

@@ -1079,28 +1079,6 @@ struct BigGroups {
   uint32_t ent[2 * kBigMax];     // (first result, count) of each such group
 };
 
-namespace {
-
-struct DevMem {
-  std::vector<void *> ptrs;
-  ~DevMem() { for (void *p : ptrs) (void)hipFree(p); }
-  template <class T>
-  hipError_t alloc(T **out, size_t count) {
-    void *p = nullptr;
-    hipError_t e = hipMalloc(&p, (count ? count : 1) * sizeof(T));
-    if (e == hipSuccess) { ptrs.push_back(p); *out = (T *)p; }
-    return e;
-  }
-};
-
-}  // namespace
-
-#define HIP_TRY(call, what)                            \
-  do {                                                 \
-    hipError_t e__ = (call);                           \
-    if (e__ != hipSuccess) return hip_fail(e__, what); \
-  } while (0)
-
 // What the host needs to fetch the grouped results: how many there are and how many groups were left unsorted
 // (written to pinned host memory by the grouping's last kernel, k_res_export).
 struct GroupTotals {

@@ -261,6 +261,50 @@ bool force_superblocks();                       // fmx_config_set("checkpoints",
 int layout_preference();                        // -1 auto, else kLayoutOneHot / kLayoutBytes (fmx_config_set)
 int hip_fail(hipError_t e, const char *what);   // records the message, returns FMX_ERR_HIP
 
+// ---- host helpers every unit shares
+#define HIP_TRY(call, what)                                   \
+  do {                                                        \
+    const hipError_t e__ = (call);                            \
+    if (e__ != hipSuccess) return ::fmx::hip_fail(e__, what); \
+  } while (0)
+
+struct DevMem {                 // the hipMalloc'ed temporaries of one call; freed on every return path
+  std::vector<void *> ps;
+  DevMem() = default;
+  DevMem(const DevMem &) = delete;
+  DevMem &operator=(const DevMem &) = delete;
+  ~DevMem() { for (void *p : ps) (void)hipFree(p); }
+  hipError_t get(void **out, size_t bytes) {
+    *out = nullptr;
+    const hipError_t e = hipMalloc(out, bytes ? bytes : 16);
+    if (e == hipSuccess) ps.push_back(*out);
+    return e;
+  }
+  template <class T>
+  hipError_t alloc(T **out, size_t count) { return get(reinterpret_cast<void **>(out), count * sizeof(T)); }
+};
+// p = `bytes` of device memory from the bag `mem`, or "hipMalloc(<what>): .." and FMX_ERR_NOMEM
+#define DEV_ALLOC(mem, p, bytes, what)                                                              \
+  do {                                                                                              \
+    const hipError_t e__ = (mem).get((void **)&(p), (bytes));                                       \
+    if (e__ != hipSuccess) {                                                                        \
+      ::fmx::set_error(std::string("hipMalloc(" what "): ") + hipGetErrorString(e__));              \
+      return FMX_ERR_NOMEM;                                                                         \
+    }                                                                                               \
+  } while (0)
+
+struct StreamGuard {            // a stream the call made for itself
+  hipStream_t s = nullptr;
+  ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
+};
+
+// fmx_api.cpp.  use_device_index: a device there is, `device` names one, hipSetDevice.  not_capturing: "<what> allocates and
+// synchronises: not under a stream capture" when `st` is being captured.  ensure_built: `prepare` (which takes `mu` itself
+// and looks again) on `st`, or on a stream of the handle's when st is null, unless `flag` says it has run.
+int use_device_index(int device);
+int not_capturing(hipStream_t st, const char *what);
+int ensure_built(const Index *h, std::mutex &mu, const bool &flag, int (*prepare)(const Index *, hipStream_t), hipStream_t st);
+
 // fmx_build.hip
 int build_index(Index *h, hipStream_t st, const int64_t *given_counts);   // returns an FMX_* status
 

@@ -26,12 +26,6 @@ namespace {
 
 constexpr uint32_t kHrShift = 8, kHrBlock = 1u << kHrShift;
 
-#define HIP_TRY(call, what)                            \
-  do {                                                 \
-    hipError_t e__ = (call);                           \
-    if (e__ != hipSuccess) return hip_fail(e__, what); \
-  } while (0)
-
 int host_rank_get(const Index *h, const HostRank **out) {
   std::lock_guard<std::mutex> lk(h->hr_mu);
   if (!h->hr) {

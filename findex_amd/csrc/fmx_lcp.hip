@@ -173,36 +173,32 @@ int lcp_core(const uint8_t *d_s, uint64_t n, const uint32_t *d_sa, uint32_t *d_l
       for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     }
   } tmp;
-  hipError_t e;
   const uint64_t nruns = (n + kRun - 1) / kRun;
-  if ((e = hipMalloc(&tmp.phi, nruns * kRun * 4)) != hipSuccess || (e = hipMalloc(&tmp.res, 64)) != hipSuccess) {
+  hipError_t e = hipMalloc(&tmp.phi, nruns * kRun * 4);
+  if (e == hipSuccess) e = hipMalloc(&tmp.res, 64);
+  if (e != hipSuccess) {
     set_error(std::string("hipMalloc(LCP): ") + hipGetErrorString(e));
     return FMX_ERR_NOMEM;
   }
   uint32_t *phi = static_cast<uint32_t *>(tmp.phi);
   unsigned long long *res = static_cast<unsigned long long *>(tmp.res);
-#define LCP_TRY(call, what)                                   \
-  do {                                                        \
-    if ((e = (call)) != hipSuccess) return hip_fail(e, what); \
-  } while (0)
-  for (hipEvent_t &ev : tmp.ev) LCP_TRY(hipEventCreate(&ev), "hipEventCreate");
-  LCP_TRY(hipMemsetAsync(res, 0, 64, st), "hipMemsetAsync");
+  for (hipEvent_t &ev : tmp.ev) HIP_TRY(hipEventCreate(&ev), "hipEventCreate");
+  HIP_TRY(hipMemsetAsync(res, 0, 64, st), "hipMemsetAsync");
   // the entries no row names (the padding; all of them when d_sa is no permutation) read as "no successor"
-  LCP_TRY(hipMemsetAsync(phi, 0xFF, nruns * kRun * 4, st), "hipMemsetAsync");
-  LCP_TRY(hipEventRecord(tmp.ev[0], st), "hipEventRecord");
+  HIP_TRY(hipMemsetAsync(phi, 0xFF, nruns * kRun * 4, st), "hipMemsetAsync");
+  HIP_TRY(hipEventRecord(tmp.ev[0], st), "hipEventRecord");
   k_lcp_phi<<<lcp_grid(cu_count, n), kLcpThreads, 0, st>>>(d_sa, n, phi);
-  LCP_TRY(hipGetLastError(), "k_lcp_phi");
-  LCP_TRY(hipEventRecord(tmp.ev[1], st), "hipEventRecord");
+  HIP_TRY(hipGetLastError(), "k_lcp_phi");
+  HIP_TRY(hipEventRecord(tmp.ev[1], st), "hipEventRecord");
   k_lcp_plcp<<<lcp_grid(cu_count, nruns), kLcpThreads, 0, st>>>(d_s, n, phi, nruns);
-  LCP_TRY(hipGetLastError(), "k_lcp_plcp");
-  LCP_TRY(hipEventRecord(tmp.ev[2], st), "hipEventRecord");
+  HIP_TRY(hipGetLastError(), "k_lcp_plcp");
+  HIP_TRY(hipEventRecord(tmp.ev[2], st), "hipEventRecord");
   k_lcp_gather<<<lcp_grid(cu_count, n), kLcpThreads, 0, st>>>(d_sa, phi, n, d_lcp, res);
-  LCP_TRY(hipGetLastError(), "k_lcp_gather");
-  LCP_TRY(hipEventRecord(tmp.ev[3], st), "hipEventRecord");
+  HIP_TRY(hipGetLastError(), "k_lcp_gather");
+  HIP_TRY(hipEventRecord(tmp.ev[3], st), "hipEventRecord");
   unsigned long long host[2] = {0, 0};
-  LCP_TRY(hipMemcpyAsync(host, res, 16, hipMemcpyDeviceToHost, st), "D2H(LCP summary)");
-  LCP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
-#undef LCP_TRY
+  HIP_TRY(hipMemcpyAsync(host, res, 16, hipMemcpyDeviceToHost, st), "D2H(LCP summary)");
+  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
   if (info) {
     info->max = (uint32_t)(host[0] >> 32);
     info->max_row = 0xFFFFFFFFull - (host[0] & 0xFFFFFFFFull);

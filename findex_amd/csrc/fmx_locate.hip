@@ -466,16 +466,6 @@ static inline unsigned flat_grid(const Index *h, uint64_t work) {
   return (unsigned)(want < cap ? want : cap);
 }
 
-struct LocMem {            // temporaries of one build, freed on every path
-  std::vector<void *> ps;
-  hipError_t get(void **p, size_t bytes) {
-    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-    if (e == hipSuccess) ps.push_back(*p);
-    return e;
-  }
-  ~LocMem() { for (void *p : ps) (void)hipFree(p); }
-};
-
 // How many starts: about n / 1024 (at least 4096 where n allows, at most 2^22); the threshold of the 32-bit hash.
 static void start_plan(uint64_t n, uint64_t *target, uint32_t *thresh) {
   uint64_t t = std::min<uint64_t>(std::max<uint64_t>(n >> 10, 4096), 1ull << 22);
@@ -505,62 +495,52 @@ static uint64_t sample_bytes(uint64_t n, uint32_t rate) {
   return nb * kBlockBytes + m * (n > (1ull << 32) ? 8 : 4);
 }
 
-static int loc_hip(hipError_t e, const char *what) { return hip_fail(e, what); }
-
 // The inversion: every segment's SA, then pass 2 into tmp (rate != 0) or into sa_be (X.sa).  Synchronises `st`.
-static int invert(const Index *h, hipStream_t st, LocMem &mem, uint32_t rate, uint64_t *tmp, uint32_t *sa_be,
+static int invert(const Index *h, hipStream_t st, DevMem &mem, uint32_t rate, uint64_t *tmp, uint32_t *sa_be,
                   uint32_t *sa_ne = nullptr, uint8_t *s_out = nullptr) {
   const uint64_t n = h->n;
   uint64_t target;
   uint32_t thresh;
   start_plan(n, &target, &thresh);
   const uint64_t runs = (n + kRunRows - 1) / kRunRows;
-  hipError_t e;
   uint32_t *d_cnt = nullptr;
   uint64_t *d_off = nullptr, *d_starts = nullptr;
-#define LOC_ALLOC(p, bytes)                                                           \
-  do {                                                                                \
-    if ((e = mem.get((void **)&(p), (bytes))) != hipSuccess) {                        \
-      set_error(std::string("hipMalloc(locate samples): ") + hipGetErrorString(e));   \
-      return FMX_ERR_NOMEM;                                                           \
-    }                                                                                 \
-  } while (0)
-  LOC_ALLOC(d_cnt, runs * 4);
-  LOC_ALLOC(d_off, runs * 8);
+  DEV_ALLOC(mem, d_cnt, runs * 4, "locate samples");
+  DEV_ALLOC(mem, d_off, runs * 8, "locate samples");
   k_inv_count<<<flat_grid(h, runs), kLocThreads, 0, st>>>(n, thresh, d_cnt, runs);
-  if ((e = hipGetLastError()) != hipSuccess) return loc_hip(e, "k_inv_count");
+  HIP_TRY(hipGetLastError(), "k_inv_count");
   std::vector<uint32_t> cnt(runs);
   std::vector<uint64_t> off(runs);
-  if ((e = hipMemcpyAsync(cnt.data(), d_cnt, runs * 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return loc_hip(e, "D2H(counts)");
-  if ((e = hipStreamSynchronize(st)) != hipSuccess) return loc_hip(e, "hipStreamSynchronize");
+  HIP_TRY(hipMemcpyAsync(cnt.data(), d_cnt, runs * 4, hipMemcpyDeviceToHost, st), "D2H(counts)");
+  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
   uint64_t S = 0;
   for (uint64_t t = 0; t < runs; t++) { off[t] = S; S += cnt[t]; }
   if (S > 2 * target + 1024) {
     set_error("locate: " + std::to_string(S) + " segment starts, more than the build planned for");
     return FMX_ERR_NOMEM;
   }
-  LOC_ALLOC(d_starts, S * 8);
-  if ((e = hipMemcpyAsync(d_off, off.data(), runs * 8, hipMemcpyHostToDevice, st)) != hipSuccess) return loc_hip(e, "H2D(offsets)");
+  DEV_ALLOC(mem, d_starts, S * 8, "locate samples");
+  HIP_TRY(hipMemcpyAsync(d_off, off.data(), runs * 8, hipMemcpyHostToDevice, st), "H2D(offsets)");
   k_inv_list<<<flat_grid(h, runs), kLocThreads, 0, st>>>(n, thresh, d_off, runs, d_starts);
-  if ((e = hipGetLastError()) != hipSuccess) return loc_hip(e, "k_inv_list");
+  HIP_TRY(hipGetLastError(), "k_inv_list");
   // pass 1
   uint32_t *d_next = nullptr, *nx0 = nullptr, *nx1 = nullptr;
   uint64_t *d_dist = nullptr, *D0 = nullptr, *D1 = nullptr;
-  LOC_ALLOC(d_next, S * 4);
-  LOC_ALLOC(d_dist, S * 8);
-  LOC_ALLOC(nx0, S * 4);
-  LOC_ALLOC(nx1, S * 4);
-  LOC_ALLOC(D0, S * 8);
-  LOC_ALLOC(D1, S * 8);
+  DEV_ALLOC(mem, d_next, S * 4, "locate samples");
+  DEV_ALLOC(mem, d_dist, S * 8, "locate samples");
+  DEV_ALLOC(mem, nx0, S * 4, "locate samples");
+  DEV_ALLOC(mem, nx1, S * 4, "locate samples");
+  DEV_ALLOC(mem, D0, S * 8, "locate samples");
+  DEV_ALLOC(mem, D1, S * 8, "locate samples");
 #define SEG(W, L)                                                                                          \
   k_inv_segments<W, L><<<loc_grid(h, S, kLocThreads / Lay<L>::G), kLocThreads, 0, st>>>(h->dev, d_starts, S, thresh, \
                                                                                         d_next, d_dist)
   FMX_LAYOUT_DISPATCH(h, SEG);
 #undef SEG
-  if ((e = hipGetLastError()) != hipSuccess) return loc_hip(e, "k_inv_segments");
+  HIP_TRY(hipGetLastError(), "k_inv_segments");
   // list ranking
   k_inv_rank_init<<<flat_grid(h, S), kLocThreads, 0, st>>>(d_next, d_dist, S, nx0, D0);
-  if ((e = hipGetLastError()) != hipSuccess) return loc_hip(e, "k_inv_rank_init");
+  HIP_TRY(hipGetLastError(), "k_inv_rank_init");
   int rounds = 1;
   while (rounds < 63 && (1ull << rounds) < S + 1) rounds++;
   for (int i = 0; i < rounds; i++) {
@@ -568,10 +548,10 @@ static int invert(const Index *h, hipStream_t st, LocMem &mem, uint32_t rate, ui
     std::swap(nx0, nx1);
     std::swap(D0, D1);
   }
-  if ((e = hipGetLastError()) != hipSuccess) return loc_hip(e, "k_inv_rank_round");
+  HIP_TRY(hipGetLastError(), "k_inv_rank_round");
   uint64_t cyc = 0;
-  if ((e = hipMemcpyAsync(&cyc, D0, 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return loc_hip(e, "D2H(cycle)");
-  if ((e = hipStreamSynchronize(st)) != hipSuccess) return loc_hip(e, "hipStreamSynchronize");
+  HIP_TRY(hipMemcpyAsync(&cyc, D0, 8, hipMemcpyDeviceToHost, st), "D2H(cycle)");
+  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
   if (cyc != n) {
     set_error("locate: the LF cycle through row 0 has " + std::to_string(cyc) + " of the index's " + std::to_string(n) +
               " rows -- not the BWT of one text (an i.i.d. byte string has several LF cycles)");
@@ -589,9 +569,8 @@ static int invert(const Index *h, hipStream_t st, LocMem &mem, uint32_t rate, ui
   } while (0)
   FMX_LAYOUT_DISPATCH(h, FILL);
 #undef FILL
-  if ((e = hipGetLastError()) != hipSuccess) return loc_hip(e, "k_inv_fill");
-  if ((e = hipStreamSynchronize(st)) != hipSuccess) return loc_hip(e, "hipStreamSynchronize");
-#undef LOC_ALLOC
+  HIP_TRY(hipGetLastError(), "k_inv_fill");
+  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
   return FMX_OK;
 }
 
@@ -652,7 +631,7 @@ int locate_prepare(const Index *h, hipStream_t st) {
     ~Guard() { if (!keep) { (void)hipFree(*a); (void)hipFree(*b); } }
   } guard{&d_marks, &d_samples};
   {
-    LocMem mem;
+    DevMem mem;
     uint64_t *tmp = nullptr;
     uint32_t *d_cnt = nullptr;
     uint64_t *d_pre = nullptr;
@@ -706,7 +685,7 @@ void locate_drop(Index *h) {
 int locate_write_sa(const Index *h, hipStream_t st, uint32_t *d_sa_be) {
   int rc = loc_supported(h);
   if (rc) return rc;
-  LocMem mem;
+  DevMem mem;
   return invert(h, st, mem, 0, nullptr, d_sa_be);
 }
 
@@ -717,7 +696,7 @@ uint64_t locate_write_sa_bytes(const Index *h) { return inv_temp_bytes(h->n, 0) 
 int locate_invert_text(const Index *h, hipStream_t st, uint32_t *d_sa, uint8_t *d_s) {
   int rc = loc_supported(h);
   if (rc) return rc;
-  LocMem mem;
+  DevMem mem;
   return invert(h, st, mem, 0, nullptr, nullptr, d_sa, d_s);
 }
 

@@ -461,12 +461,6 @@ __global__ __launch_bounds__(256) void k_ref_place(const RefResult *__restrict__
   }
 }
 
-#define HIP_TRY(call, what)                            \
-  do {                                                 \
-    hipError_t e__ = (call);                           \
-    if (e__ != hipSuccess) return hip_fail(e__, what); \
-  } while (0)
-
 
 // results per regex, newest first: the order of the reference's prepended list (:638)
 static void deliver_results(std::vector<RefResult> &tmp, fmx_result *out, uint32_t *per_regex_count) {

@@ -257,17 +257,6 @@ __global__ void k_sa_eof_fill(const uint8_t *__restrict__ s, const uint32_t *__r
 // ---- host side
 namespace {
 
-struct DevMem {                 // every temporary of one construction; freed on every return path
-  std::vector<void *> ps;
-  ~DevMem() { for (void *p : ps) (void)hipFree(p); }
-  hipError_t get(void **out, size_t bytes) {
-    *out = nullptr;
-    hipError_t e = hipMalloc(out, bytes ? bytes : 16);
-    if (e == hipSuccess) ps.push_back(*out);
-    return e;
-  }
-};
-
 uint64_t ntiles_of(uint64_t m) { return (m + kSaTile - 1) / kSaTile; }
 
 }  // namespace
@@ -355,8 +344,7 @@ int sufsort_bwt(const void *d_text, uint64_t len, void *d_bwt, void *d_sa_user, 
   const uint64_t n = len + 1;
   const uint64_t peak = sufsort_peak_bytes(len, d_sa_user != nullptr);
   size_t free_b = 0, total_b = 0;
-  hipError_t e = hipMemGetInfo(&free_b, &total_b);
-  if (e != hipSuccess) return hip_fail(e, "hipMemGetInfo");
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
   if (peak + extra > free_b) {
     set_error("suffix sort of " + std::to_string(len) + " bytes needs " + std::to_string(peak + extra) +
               " bytes of device memory, " + std::to_string((unsigned long long)free_b) + " are free");
@@ -371,49 +359,37 @@ int sufsort_bwt(const void *d_text, uint64_t len, void *d_bwt, void *d_sa_user, 
   unsigned long long *k0 = nullptr, *k1 = nullptr, *out = nullptr;
   const uint64_t nt = ntiles_of(n);
   const uint64_t scan_len = std::max<uint64_t>(n, 256 * nt);
-#define SA_ALLOC(p, bytes)                                                         \
-  do {                                                                             \
-    if ((e = mem.get((void **)&(p), (bytes))) != hipSuccess) {                     \
-      set_error(std::string("hipMalloc(suffix sort): ") + hipGetErrorString(e));   \
-      return FMX_ERR_NOMEM;                                                        \
-    }                                                                              \
-  } while (0)
-  SA_ALLOC(s, n + 8);
+  DEV_ALLOC(mem, s, n + 8, "suffix sort");
   if (d_sa_user) sa = static_cast<uint32_t *>(d_sa_user);
-  else SA_ALLOC(sa, 4 * n);
-  SA_ALLOC(rank, 4 * n);
-  SA_ALLOC(k0, 8 * n);
-  SA_ALLOC(k1, 8 * n);
-  SA_ALLOC(v0, 4 * n);
-  SA_ALLOC(v1, 4 * n);
-  SA_ALLOC(ap, 4 * n);
-  SA_ALLOC(hist, 4 * 256 * nt);
-  SA_ALLOC(partials, 4 * scan_partials(scan_len));
-  SA_ALLOC(out, 8 * 257 + 8);
-#undef SA_ALLOC
+  else DEV_ALLOC(mem, sa, 4 * n, "suffix sort");
+  DEV_ALLOC(mem, rank, 4 * n, "suffix sort");
+  DEV_ALLOC(mem, k0, 8 * n, "suffix sort");
+  DEV_ALLOC(mem, k1, 8 * n, "suffix sort");
+  DEV_ALLOC(mem, v0, 4 * n, "suffix sort");
+  DEV_ALLOC(mem, v1, 4 * n, "suffix sort");
+  DEV_ALLOC(mem, ap, 4 * n, "suffix sort");
+  DEV_ALLOC(mem, hist, 4 * 256 * nt, "suffix sort");
+  DEV_ALLOC(mem, partials, 4 * scan_partials(scan_len), "suffix sort");
+  DEV_ALLOC(mem, out, 8 * 257 + 8, "suffix sort");
   flag = reinterpret_cast<uint32_t *>(out + 257);
   const double alloc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-#define SA_TRY(call, what)                       \
-  do {                                           \
-    if ((e = (call)) != hipSuccess) return hip_fail(e, what); \
-  } while (0)
 #define SA_LAUNCH(...)                                              \
   do {                                                              \
     hipLaunchKernelGGL(__VA_ARGS__);                                \
-    SA_TRY(hipGetLastError(), "suffix sort kernel launch");          \
+    HIP_TRY(hipGetLastError(), "suffix sort kernel launch");        \
   } while (0)
   hipEvent_t ev[2] = {nullptr, nullptr};
   struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 2; i++) if (ev[i]) (void)hipEventDestroy(ev[i]); } } evg{ev};
   if (log_path) {
-    SA_TRY(hipEventCreate(&ev[0]), "hipEventCreate");
-    SA_TRY(hipEventCreate(&ev[1]), "hipEventCreate");
+    HIP_TRY(hipEventCreate(&ev[0]), "hipEventCreate");
+    HIP_TRY(hipEventCreate(&ev[1]), "hipEventCreate");
   }
   std::vector<RoundLog> rounds;
-  SA_TRY(hipMemsetAsync(out, 0, 8 * 257 + 8, st), "hipMemsetAsync");
+  HIP_TRY(hipMemsetAsync(out, 0, 8 * 257 + 8, st), "hipMemsetAsync");
   SA_LAUNCH(k_sa_reverse, dim3(sa_grid(n + 8)), dim3(kSaThreads), 0, st, static_cast<const uint8_t *>(d_text), len, s, flag);
   uint32_t zero = 0;
-  SA_TRY(hipMemcpyAsync(&zero, flag, 4, hipMemcpyDeviceToHost, st), "D2H");
-  SA_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+  HIP_TRY(hipMemcpyAsync(&zero, flag, 4, hipMemcpyDeviceToHost, st), "D2H");
+  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
   if (zero) {
     set_error("the text contains byte 0 (findex's readers escape it; counts[0] must be 0)");
     return FMX_ERR_UNSUPPORTED;
@@ -422,26 +398,26 @@ int sufsort_bwt(const void *d_text, uint64_t len, void *d_bwt, void *d_sa_user, 
   uint64_t m = n, h = 0;
   uint32_t *list = nullptr;                   // the active list (SA positions); nullptr in round 1: all of them
   while (m > 0) {
-    if (log_path) SA_TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+    if (log_path) HIP_TRY(hipEventRecord(ev[0], st), "hipEventRecord");
     unsigned long long *k = k0, *ka = k1;
     uint32_t *v = v0, *va = v1;
     if (h == 0) SA_LAUNCH(k_sa_init, dim3(sa_grid(m)), dim3(kSaThreads), 0, st, s, n, k, v);
     else SA_LAUNCH(k_sa_keys, dim3(sa_grid(m)), dim3(kSaThreads), 0, st, list, m, sa, rank, n, h, bits, k, v);
     int passes = 0;
-    SA_TRY(radix_sort(&k, &v, &ka, &va, m, h == 0 ? 64 : 2 * bits, hist, partials, st, &passes), "radix sort");
+    HIP_TRY(radix_sort(&k, &v, &ka, &va, m, h == 0 ? 64 : 2 * bits, hist, partials, st, &passes), "radix sort");
     // the free key buffer holds the heads (first m u32) and the keep flags (next m u32)
     uint32_t *hp = reinterpret_cast<uint32_t *>(ka), *keep = hp + m;
     SA_LAUNCH(k_sa_heads, dim3(sa_grid(m)), dim3(kSaThreads), 0, st, k, m, hp);
-    SA_TRY(scan_u32(hp, m, kScanMax, false, partials, st), "scan");
+    HIP_TRY(scan_u32(hp, m, kScanMax, false, partials, st), "scan");
     SA_LAUNCH(k_sa_rank, dim3(sa_grid(m)), dim3(kSaThreads), 0, st, k, v, hp, list, m, sa, rank, keep);
-    SA_TRY(scan_u32(keep, m, kScanSum, false, partials, st), "scan");
+    HIP_TRY(scan_u32(keep, m, kScanSum, false, partials, st), "scan");
     // the next list goes to the free value buffer; the old list's buffer becomes a value buffer
     uint32_t *next = va;
     SA_LAUNCH(k_sa_compact, dim3(sa_grid(m)), dim3(kSaThreads), 0, st, keep, list, m, next);
     uint32_t m_next = 0;
-    SA_TRY(hipMemcpyAsync(&m_next, keep + (m - 1), 4, hipMemcpyDeviceToHost, st), "D2H");
-    if (log_path) SA_TRY(hipEventRecord(ev[1], st), "hipEventRecord");
-    SA_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    HIP_TRY(hipMemcpyAsync(&m_next, keep + (m - 1), 4, hipMemcpyDeviceToHost, st), "D2H");
+    if (log_path) HIP_TRY(hipEventRecord(ev[1], st), "hipEventRecord");
+    HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     if (log_path) {
       float ms = 0;
       (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
@@ -461,10 +437,9 @@ int sufsort_bwt(const void *d_text, uint64_t len, void *d_bwt, void *d_sa_user, 
   SA_LAUNCH(k_sa_emit, dim3(sa_grid(n)), dim3(kSaThreads), 0, st, s, sa, n, static_cast<uint8_t *>(d_bwt), out);
   SA_LAUNCH(k_sa_eof_fill, dim3(1), dim3(1), 0, st, s, sa, n, static_cast<uint8_t *>(d_bwt), out);
   unsigned long long host_out[257];
-  SA_TRY(hipMemcpyAsync(host_out, out, sizeof host_out, hipMemcpyDeviceToHost, st), "D2H");
-  SA_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+  HIP_TRY(hipMemcpyAsync(host_out, out, sizeof host_out, hipMemcpyDeviceToHost, st), "D2H");
+  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
 #undef SA_LAUNCH
-#undef SA_TRY
   *eof = host_out[0];
   for (int c = 0; c < 256; c++) counts[c] = (int64_t)host_out[1 + c];
   if (log_path)
