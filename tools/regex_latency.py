@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Latency of single-regex matches through a resident batch (the interactive shape of ReTree.matchSA):
-a literal-heavy regex is a frontier of one or a few elements for many levels.  FMX_FRONTIER_TAIL=0 shows
-the grid-kernel-only path."""
+a literal-heavy regex is a frontier of one or a few elements for many levels, served by chains of short launches
+on the small grid (FMX_FRONTIER_CHAIN_SMALL, FMX_FRONTIER_ROUNDS_SMALL)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -22,5 +22,5 @@ for re in ("abcdabcdabcdabcdabcdabcd", "ab(c|d)abcdab[abc]dabcdabcd", "a[ab]*c")
         for _ in range(100):
             out, per = batch.match_raw(max_steps=64, cap=1 << 16)
         best = min(best, (time.perf_counter() - t0) / 100)
-    print("%-32s %4d results: %.1f us per call (kernels %.1f us)  [FMX_FRONTIER_TAIL=%s]"
-          % (re, out.size, best * 1e6, sa.stats()["last_kernel_ms"] * 1e3, os.environ.get("FMX_FRONTIER_TAIL", "1")))
+    print("%-32s %4d results: %.1f us per call (kernels %.1f us)"
+          % (re, out.size, best * 1e6, sa.stats()["last_kernel_ms"] * 1e3))

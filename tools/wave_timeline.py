@@ -86,7 +86,7 @@ if hasattr(L, "fmx_debug_phaselog"):
             print("late rounds (%d waves, %d rounds): cycles per round  take %.0f | stage %.0f | wait + ranks %.0f | bookkeeping %.0f  (total %.0f)"
                   % (m.sum(), n, tot[0] / n, tot[1] / n, tot[2] / n, tot[3] / n, tot.sum() / n))
 
-# ---- per-round trace of the waves that ended last (launch 0): held elements / pool / deepest length / narrow / express
+# ---- per-round trace of the waves that ended last (launch 0): held elements / pool / deepest length / narrow
 if hasattr(L, "fmx_debug_wavetrace"):
     tr = np.zeros((1 << 15, 128), dtype=np.uint32)
     L.fmx_debug_wavetrace.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
@@ -95,6 +95,6 @@ if hasattr(L, "fmx_debug_wavetrace"):
         order = np.argsort(e[:, 2])[::-1][:4]
         for wv in order:
             row = tr[wv]
-            txt = " ".join("%d/%d/L%d%s%s" % (v & 0xFF, (v >> 8) & 0xFFF, (v >> 20) & 0xFF, "n" if (v >> 28) & 1 else "", ("x%d" % (v >> 29)) if v >> 29 else "")
+            txt = " ".join("%d/%d/L%d%s" % (v & 0xFF, (v >> 8) & 0xFFF, (v >> 20) & 0xFF, "n" if (v >> 28) & 1 else "")
                            for v in row.tolist() if v)
             print("wave %d (held/pool/deepest by round): %s" % (wv, txt))
