@@ -281,12 +281,24 @@ int build_index(Index *h, hipStream_t st, const int64_t *given_counts) {
     } else {
       FMX_TRY(hipMalloc(&h->d_bv, bv_bytes ? bv_bytes : 16), "hipMalloc(rank dictionary)");
     }
-    FMX_TRY(hipMalloc(&h->d_cf, sizeof h->cf), "hipMalloc(cf)");
+    // cf and, behind it, the literal search kernel's per-symbol entries (DevIndex::symtab), which it used to work out from cf
+    // and slot at the start of every launch
+    uint64_t symtab[256][2];
+    FMX_TRY(hipMalloc(&h->d_cf, sizeof h->cf + sizeof symtab), "hipMalloc(cf)");
     FMX_TRY(hipMalloc(&h->d_slot, sizeof h->slot), "hipMalloc(slot)");
     FMX_TRY(hipMalloc((void **)&h->d_counters, kCounterBytes + kCensusBytes + kCalibScratchBytes + kTixBytes), "hipMalloc(counters)");
     FMX_TRY(hipMemsetAsync(h->d_counters, 0, kCounterBytes + kCensusBytes + kCalibScratchBytes + kTixBytes, st), "memset(counters)");
     FMX_TRY(hipMemcpyAsync(h->d_cf, h->cf, sizeof h->cf, hipMemcpyHostToDevice, st), "copy cf");
     FMX_TRY(hipMemcpyAsync(h->d_slot, h->slot, sizeof h->slot, hipMemcpyHostToDevice, st), "copy slot");
+    for (int c = 0; c < 256; c++) {
+      const uint16_t s = h->slot[c];
+      uint64_t vb = 0;
+      if (s < kSlotEof) vb = bytes_layout ? (uint64_t)s + 2 : (uint64_t)(uintptr_t)h->d_bv + (uint64_t)s * h->nblocks * kBlockBytes;
+      else if (s == kSlotEof) vb = 1;
+      symtab[c][0] = h->cf[c];
+      symtab[c][1] = vb;
+    }
+    FMX_TRY(hipMemcpyAsync((char *)h->d_cf + sizeof h->cf, symtab, sizeof symtab, hipMemcpyHostToDevice, st), "copy symtab");
     FMX_TRY(hipMemcpyAsync(d_sym, sym_of, sizeof sym_of, hipMemcpyHostToDevice, st), "copy sym");
     FMX_TRY(hipEventRecord(ev2, st), "hipEventRecord");
     if (bytes_layout) {

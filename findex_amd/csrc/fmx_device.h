@@ -59,7 +59,7 @@ template <uint32_t LAYOUT> struct Lay { static constexpr int G = LAYOUT == kLayo
 struct DevIndex {
   const uint4 *bv;        // one-hot layout: rank dictionary
   const uint8_t *bwt;     // BWT bytes, slot eof holds 0, zero-padded to whole 128-byte blocks
-  const uint64_t *cf;     // [256] C[] = first row of each symbol, NaiveFMSearcher.cf
+  const uint64_t *cf;     // [256] C[] = first row of each symbol, NaiveFMSearcher.cf; behind it the [256] entries of symtab()
   const uint16_t *slot;   // [256] symbol -> slot | kSlotNone | kSlotEof
   uint64_t n;
   uint64_t eof;
@@ -68,6 +68,10 @@ struct DevIndex {
   const uint64_t *sup;    // bytes layout
   uint32_t layout;
   uint32_t nslots;
+  // Per symbol {C[c], x}: x = byte address of the symbol's bit-vector (one-hot layout) or its slot + 2 (bytes layout), 0 for an
+  // absent symbol, 1 for the EOF symbol -- what k_search4 keeps in LDS, filled once per handle (build_index) in the same
+  // allocation as cf (no pointer of its own: the search kernels have no scalar register to spare).
+  __device__ __forceinline__ const uint4 *symtab() const { return reinterpret_cast<const uint4 *>(cf + 256); }
 };
 
 constexpr unsigned long long kPackWide = 0xFFFFFFull;      // width field of a packed interval that stands for "look in the escape list"

@@ -87,7 +87,8 @@ static uint32_t ticket_area(const Index *h, hipStream_t st) {
 }
 
 // full rounds of batches that are drawn with the partial last one: 2 by measurement -- C5 0.318-0.320 / 0.314-0.316 /
-// 0.315-0.316 ms, C3text 0.425 / 0.423 / 0.435 ms with 1 / 2 / 4: every drawn batch starts cold
+// 0.315-0.316 ms, C3text 0.425 / 0.423 / 0.435 ms with 1 / 2 / 4: every drawn batch starts cold; again with the shorter
+// ramp (profiles/ends_c3_ab.md): C3 0.1092 / 0.1104 / 0.1124 ms with 2 / 3 / 4
 constexpr uint32_t kPoolRounds = 2;
 
 // ---------------------------------------------------------------- which instantiation

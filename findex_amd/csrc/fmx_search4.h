@@ -99,8 +99,8 @@ __device__ __forceinline__ uint32_t pat_chunk(const uint8_t *__restrict__ pat, c
 #endif
 #ifdef FMX_SEARCHLOG
 // Diagnostic build only (tools/search_wave_timeline.py): begin and end of every wave of the last k_search4 launch on
-// the constant 100 MHz clock, and the batches it searched.
-static __device__ unsigned long long g_searchlog[1u << 15][4];      // (each unit that instantiates k_search4 has its own)
+// the constant 100 MHz clock, the batches it searched, and when it issued its first table lookup and drew its first ticket.
+static __device__ unsigned long long g_searchlog[1u << 15][6];      // (each unit that instantiates k_search4 has its own)
 #endif
 // G2 (round 5, one-hot layout only): a pattern is served by a PAIR of lanes instead of a quad -- 32 patterns per wave, the
 // dictionary's 64-byte block fetched as two 32-byte halves (fmx_device.h, Blk2).  tools/c3_halfbatch.py: with the same 1M
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
   constexpr uint32_t R = LAYOUT == kLayoutBytes ? 2u : 1u;    // memory requests per rank query
 #ifdef FMX_SEARCHLOG
   const unsigned long long sl_t0 = __builtin_amdgcn_s_memrealtime();
-  unsigned long long sl_t1 = 0;
+  unsigned long long sl_t1 = 0, sl_look = 0, sl_draw = 0;      // sl_look: the first table lookup goes out; sl_draw: the first ticket is drawn (0: never)
   uint32_t sl_batches = 0;
 #endif
   // the residency census (fmx_device.h): when this workgroup began
@@ -145,19 +145,34 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
     const unsigned long long c0 = __builtin_amdgcn_s_memrealtime();
     while (__builtin_amdgcn_s_memrealtime() - c0 < (spin & 0xFFFFu)) __builtin_amdgcn_s_sleep(32);
   }
+  const uint32_t wave = (blockIdx.x * kSThreads + threadIdx.x) >> 6;
+  const uint32_t nwaves = gridDim.x * (kSThreads / 64);
+  const uint32_t grp = (threadIdx.x & 63) / G;
+  auto load_off_raw = [&](uint64_t bt, uint64_t &v0, uint64_t &v1) {      // batches past the end read the last pattern's offsets
+    const uint64_t pid = bt * P + grp;
+    const uint64_t *p = po.at(pid < k ? pid : (uint64_t)k - 1);
+    v0 = p[0];
+    v1 = p[1];
+  };
   // per symbol: {C[c], x} with x = byte address of the symbol's bit-vector (one-hot layout) or its
-  // slot + 2 (bytes layout); x = 0 absent symbol, x = 1 the EOF symbol
+  // slot + 2 (bytes layout); x = 0 absent symbol, x = 1 the EOF symbol -- ix.symtab(), filled once per handle (build_index):
+  // one 16-byte load per thread.  The raw offsets of the wave's first two batches are requested beside it, before the
+  // barrier, and looked at behind it (until this was so, a launch's first lookups stood behind three dependent round trips
+  // -- these tables, the offsets, the pattern bytes -- in every wave at once: profiles/ends_c3_before_wave_timeline.txt).
+  static_assert(kSThreads == 256, "one thread per symbol fills the tables in LDS");
   __shared__ uint4 s_tab[256];
   __shared__ uint8_t s_dense[KT ? 256 : 4];      // byte -> dense symbol id of the k-mer table (0xFF: not in it)
   __shared__ uint16_t s_slot[KT ? 256 : 4];
-  for (int c = threadIdx.x; c < 256; c += blockDim.x) {
-    if (KT) { s_dense[c] = kdense[c]; s_slot[c] = ix.slot[c]; }
-    const uint64_t cf = ix.cf[c];
-    const uint16_t s = ix.slot[c];
-    uint64_t vb = 0;
-    if (s < kSlotEof) vb = LAYOUT == kLayoutBytes ? (uint64_t)s + 2 : (uint64_t)(uintptr_t)ix.bv + (uint64_t)s * ix.nblocks * kBlockBytes;
-    else if (s == kSlotEof) vb = 1;
-    s_tab[c] = make_uint4((uint32_t)cf, (uint32_t)(cf >> 32), (uint32_t)vb, (uint32_t)(vb >> 32));
+  uint64_t raw0a, raw0b, raw1a, raw1b;
+  {
+    const uint4 sym = ix.symtab()[threadIdx.x];
+    uint8_t dn = 0;
+    uint16_t sl = 0;
+    if (KT) { dn = kdense[threadIdx.x]; sl = ix.slot[threadIdx.x]; }
+    load_off_raw(wave, raw0a, raw0b);
+    load_off_raw((uint64_t)wave + nwaves, raw1a, raw1b);
+    if (KT) { s_dense[threadIdx.x] = dn; s_slot[threadIdx.x] = sl; }
+    s_tab[threadIdx.x] = sym;
   }
   __syncthreads();
   const LaneConst lc = lane_const<G2 ? 4 : G>();      // (a pair's lane takes its positions from t itself: rank_finish_g2)
@@ -191,9 +206,6 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
   // lane 0 / lane 1 of the group to all its lanes
   auto gbc0 = [&](uint32_t v) -> uint32_t { if constexpr (G2) return pair_bcast<0>(v); else return group_bcast<G, 0>(v); };
   auto gbc1 = [&](uint32_t v) -> uint32_t { if constexpr (G2) return pair_bcast<1>(v); else return group_bcast<G, 1>(v); };
-  const uint32_t wave = (blockIdx.x * kSThreads + threadIdx.x) >> 6;
-  const uint32_t nwaves = gridDim.x * (kSThreads / 64);
-  const uint32_t grp = (threadIdx.x & 63) / G;
   const uint32_t nbatch = (k + P - 1) / P;
   // The last rounds are DRAWN (round 5).  The batches are strided statically over the waves, every wave's pipeline knowing
   // two batches ahead which ones are its own -- and the launch ends with its slowest wave: the timelines
@@ -269,6 +281,9 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
   // A pattern's final interval (the lane that holds it calls).  pk_cap != ~0: straight into the 8-byte form (fmx.h) -- word
   // q of sp_out, wide intervals appended to the escape list behind word k -- instead of a pass of k_pack_intervals over
   // both arrays behind the search (every variant of this kernel finishes all of its patterns itself since round 5).
+  // (non-temporal: the kernel never reads a result again, and a launch's 16 MB of them need not stay in L2 beside the tables'
+  // lines -- C3 0.1102 -> 0.1092 ms on one box, profiles/ends_c3_ab.md)
+  auto st_out = [](auto *p, uint64_t v) { __builtin_nontemporal_store((decltype(*p + 0))v, p); };
   auto emit = [&](uint32_t q, uint64_t a, uint64_t b) {
     if (pk_cap != ~0ull) {
       unsigned long long *pk = reinterpret_cast<unsigned long long *>(sp_out);
@@ -277,21 +292,15 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
         const unsigned long long slot = atomicAdd(pk + k, 1ull);
         if (slot < pk_cap) { pk[(uint64_t)k + 1 + 2 * slot] = q; pk[(uint64_t)k + 2 + 2 * slot] = b; }
       }
-      pk[q] = a | ((w < kPackWide ? w : kPackWide) << 40);
+      st_out(pk + q, a | ((w < kPackWide ? w : kPackWide) << 40));
     } else {
-      sp_out[q] = a;
-      ep_out[q] = b;
+      st_out(sp_out + q, a);
+      st_out(ep_out + q, b);
     }
   };
   const uint32_t wave_in_wg = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const uint32_t lane64 = threadIdx.x & 63u;
   const uint64_t pat_addr = (uint64_t)(uintptr_t)pat;
-  auto load_off_raw = [&](uint64_t bt, uint64_t &v0, uint64_t &v1) {      // batches past the end read the last pattern's offsets
-    const uint64_t pid = bt * P + grp;
-    const uint64_t *p = po.at(pid < k ? pid : (uint64_t)k - 1);
-    v0 = p[0];
-    v1 = p[1];
-  };
   // (end, len) of group `grp` in batch bt from the raw offsets; groups past the end of the batch list get an empty
   // pattern at the end of the last one, so that a wave's span is always [begin of its lane 0, end of its lane 63)
   auto fix_off = [&](uint64_t bt, uint64_t v0, uint64_t v1, uint64_t &e, uint32_t &len) {
@@ -334,13 +343,8 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
   // lookups in the k-mer table (counters[9]), the row jump table (counters[10]) and the three-step row table (counters[11]):
   // counted per wave in scalar registers (a ballot's population count), not per lane
   uint32_t ktl = 0, jtl = 0, r3l = 0;
-  {
-    uint64_t a0, a1;
-    load_off_raw(wave, a0, a1);
-    fix_off(wave, a0, a1, end0, len0);
-    load_off_raw((uint64_t)wave + nwaves, a0, a1);
-    fix_off((uint64_t)wave + nwaves, a0, a1, end1, len1);
-  }
+  fix_off(wave, raw0a, raw0b, end0, len0);      // (requested before the barrier above)
+  fix_off((uint64_t)wave + nwaves, raw1a, raw1b, end1, len1);
   Stage cur = stage_issue(end0, len0);
   stage_park(cur, par);
   // without staging (the bytes layout) a batch's tail -- the chunks its k-mer lookup is made of -- is requested while the
@@ -663,6 +667,9 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
       // lanes 2 and 3 the same again)
       const uint4 *ksrc = ktab + (elig ? code : 0u);
       if constexpr (KX) { if (ex) ksrc = kext + 2ull * zcode + (t & 1u); }
+#ifdef FMX_SEARCHLOG
+      if (!sl_look) sl_look = __builtin_amdgcn_s_memrealtime();
+#endif
       const uint4 ent = *ksrc;
       issue_ahead();
       if (elig && !ex) {
@@ -1133,7 +1140,13 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
       const uint32_t pool = npool > shard ? (npool - shard + nshards - 1u) / nshards : 0u;               // this counter's batches
       const uint32_t mine = groups > shard ? (groups - shard + nshards - 1u) / nshards : 0u;             // ... its groups of waves
       const uint32_t drawers = mine * 32u - ((groups - 1u) % nshards == shard ? groups * 32u - nwaves : 0u);
+      // (tried: this first draw at the start of the wave's last strided batch, so that the first drawn batch does not begin
+      // with the atomic's round trip -- one more value through the strided loop: the C3 form 42 -> 44 spilled scalar and 4 -> 8
+      // spilled vector registers, the bytes layout's RW = 3 forms 73 -> 77 vector registers; not measured, not kept)
       uint32_t drawn = 0;
+#ifdef FMX_SEARCHLOG
+      sl_draw = __builtin_amdgcn_s_memrealtime();
+#endif
       if (lane64 == 0) drawn = (uint32_t)atomicAdd(tix, 1ull);
       for (;;) {
         const uint32_t tk = (uint32_t)__builtin_amdgcn_readfirstlane((int)drawn);
@@ -1185,6 +1198,7 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
   if ((threadIdx.x & 63u) == 0 && wave < (1u << 15)) {
     unsigned long long *e = g_searchlog[wave];
     e[0] = sl_t0; e[1] = ((sl_t1 - sl_t0) & 0xFFFFFFFFull) | ((sl_tw - sl_t0) << 32); e[2] = sl_t2; e[3] = __builtin_amdgcn_s_memrealtime() | ((unsigned long long)sl_batches << 48);
+    e[4] = sl_look; e[5] = sl_draw;
   }
 #endif
   if (threadIdx.x == 0 && blockIdx.x < kCensusBlocks)       // ... and when its first wave ended

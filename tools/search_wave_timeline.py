@@ -2,8 +2,9 @@
 """When do the waves of k_search4 begin and end?  Diagnostic build -DFMX_SEARCHLOG (works in the round-3 worktree too,
 patched with the same log):
     tools/build_variant.sh slog -DFMX_SEARCHLOG && FMX_LIB=findex_amd/lib/variants/libfmx_slog.so python tools/search_wave_timeline.py c5
-Prints the launch's span on the device's 100 MHz clock, when the waves began / entered their batch loop / left it /
-ended (percentiles), how long a batch took, and how many waves were alive at tenths of the span."""
+Prints the launch's span on the device's 100 MHz clock, when the waves began / entered their batch loop / issued their first
+table lookup / drew their first ticket / left the loop / ended (percentiles), how long a batch took, and how many waves were
+alive at tenths of the span.  A second argument 4 reads the log of a build from before the two marks (four words per wave)."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -11,6 +12,7 @@ import numpy as np, torch
 import bench, findex_amd
 from findex_amd import _lib
 wl = sys.argv[1] if len(sys.argv) > 1 else "c5"
+words = int(sys.argv[2]) if len(sys.argv) > 2 else 6
 log2n, sigma, k, m, seed = bench.LITERAL[wl]
 n = 1 << log2n
 dev = torch.device("cuda", 0)
@@ -28,7 +30,7 @@ for _ in range(5):
 torch.cuda.synchronize()
 L = _lib.load()
 L.fmx_debug_searchlog.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
-log = np.zeros((1 << 15, 4), dtype=np.uint64)
+log = np.zeros((1 << 15, words), dtype=np.uint64)
 assert L.fmx_debug_searchlog(log.ctypes.data_as(ctypes.c_void_p), log.nbytes) == 0
 print("device ms of the logged call (all its kernels): %.4f" % hip.last_kernel_ms())
 t3 = log[:, 3] & np.uint64((1 << 48) - 1)
@@ -48,6 +50,14 @@ def pct(name, v):
     print("%-34s min %7.1f  p10 %7.1f  p50 %7.1f  p90 %7.1f  p99 %7.1f  max %7.1f us" % ((name,) + tuple(q)))
 pct("wave begins at", (t0 - z) * T)
 pct("enters its batch loop at", (t1 - z) * T)
+if words >= 6:
+    look, draw = log[live, 4].astype(np.int64), log[live, 5].astype(np.int64)
+    pct("issues its first table lookup at", (look[look != 0] - z) * T)
+    if (draw != 0).any():
+        pct("draws its first ticket at", (draw[draw != 0] - z) * T)
+        pct("first ticket to the wave's end", (t3[draw != 0] - draw[draw != 0]) * T)
+        print("first ticket of the launch at %.1f us, median one at %.1f us; the launch ends %.1f us behind the median first ticket"
+              % ((draw[draw != 0].min() - z) * T, (np.median(draw[draw != 0]) - z) * T, (t3.max() - np.median(draw[draw != 0])) * T))
 pct("begins its last walk at", (tw - z) * T)
 pct("last walk takes", (t2 - tw) * T)
 pct("has walked at", (t2 - z) * T)
