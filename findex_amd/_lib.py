@@ -44,6 +44,16 @@ class fmx_search_opts(ctypes.Structure):
     _fields_ = [("fixed_len", ctypes.c_uint32), ("packed", ctypes.c_uint32), ("escape_cap", ctypes.c_uint64)]
 
 
+class fmx_approx_hit(ctypes.Structure):
+    _fields_ = [("pattern", ctypes.c_uint32), ("mismatches", ctypes.c_uint32), ("sp", ctypes.c_uint64),
+                ("ep", ctypes.c_uint64)]
+
+
+class fmx_approx_opts(ctypes.Structure):
+    _fields_ = [("max_mismatches", ctypes.c_uint32), ("sub_lo", ctypes.c_uint8), ("sub_hi", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint16)]
+
+
 class fmx_stats_t(ctypes.Structure):
     _fields_ = [("rank_queries", ctypes.c_uint64), ("backward_steps", ctypes.c_uint64),
                 ("launches", ctypes.c_uint64), ("last_kernel_ms", ctypes.c_double),
@@ -129,6 +139,9 @@ SYMBOLS = {
     "fmx_lcp_info": (_i32, [_vp, _P(_u64), _P(ctypes.c_double), _P(_u32), _P(_u64), _P(_u64)]),
     "fmx_write_lcp": (_i32, [_vp, _cp]),
     "fmx_lcp_last_phases": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double)]),
+    "fmx_search_approx_batch": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_approx_opts), _vp, _vp, _sz, _P(_sz)]),
+    "fmx_search_approx_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_approx_opts), _vp, _vp, _sz, _P(_sz), _vp]),
+    "fmx_approx_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(_u64), _P(_u64)]),
     "fmx_corpus_build": (_i32, [_vp, _u64, _vp, _u64, _i32, _P(_vp)]),
     "fmx_corpus_build_dev": (_i32, [_vp, _u64, _vp, _u64, _i32, _vp, _P(_vp)]),
     "fmx_corpus_free": (_i32, [_vp]),

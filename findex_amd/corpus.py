@@ -250,13 +250,31 @@ class HipCorpusSearcher:
         self.searcher.close()
         self.corpus.close()
 
-    def locate_docs(self, q, max_hits=None):
+    def locate_docs(self, q, max_hits=None, max_mismatches=0):
         """(doc, raw_off) arrays of the occurrences of the raw bytes q, sorted by (doc, raw_off): q is escaped, its reverse
-        searched, the rows located (locate_text's arithmetic with the escaped length) and the positions mapped."""
-        pos = self.searcher.locate_text(escape(q), max_hits=max_hits)
-        doc, _, raw = self.corpus.map(pos)
+        searched, the rows located (locate_text's arithmetic with the escaped length) and the positions mapped.
+
+        max_mismatches > 0 (up to 3): the windows of the stream within that many substituted bytes of the escaped q as well,
+        as (doc, raw_off, mismatches) sorted by (doc, raw_off); max_hits then bounds the rows taken of every distinct matching
+        string.  Bytes are substituted from 2 .. 254 only, so the separator byte 1 is never one of them and no hit spans two
+        files.  One known limit: q is compared in its escaped form, so a substitution may fall on one half of an escape pair
+        (the backslash or the digit that stand for a raw 0, 1 or 255) -- such a window counts one mismatch although its raw
+        bytes differ otherwise, and a window whose raw bytes differ in an escaped byte may be missed."""
+        if not max_mismatches:
+            pos = self.searcher.locate_text(escape(q), max_hits=max_hits)
+            doc, _, raw = self.corpus.map(pos)
+            order = np.lexsort((raw, doc))
+            return doc[order], raw[order]
+        esc = escape(q)
+        if not esc:
+            raise ValueError("empty pattern")
+        _, hits = self.searcher.search_approx_batch(np.frombuffer(esc[::-1], dtype=np.uint8), np.array([0, len(esc)], dtype=np.uint64),
+                                                    int(max_mismatches), sub=(2, 254))
+        off, sa = self.searcher.locate_intervals(hits["sp"], hits["ep"], max_per=max_hits)
+        mism = np.repeat(hits["mismatches"], np.diff(off).astype(np.int64))
+        doc, _, raw = self.corpus.map(HipFMSearcher.text_offsets(sa, self.searcher.n, len(esc)))
         order = np.lexsort((raw, doc))
-        return doc[order], raw[order]
+        return doc[order], raw[order], mism[order]
 
     def _intervals(self, queries):
         esc = [escape(q)[::-1] for q in queries]

@@ -1652,6 +1652,99 @@ int fmx_write_bwt(const char *bwt_path, const char *aux_path, const uint8_t *bwt
   return FMX_OK;
 }
 
+// ---------------------------------------------------------------- approximate search (fmx_approx.hip)
+static thread_local ApproxInfo g_approx_last;
+
+// What refuses a call before the device is touched; the budget and the range as the kernel takes them.
+static int approx_args(const fmx_index *idx, size_t k, const fmx_approx_opts *opts, const void *out_off, const void *out, size_t cap,
+                       const size_t *n_out, uint32_t *e, uint32_t *lo, uint32_t *hi) {
+  if (!n_out) return arg_fail("approx: n_out is null");
+  *e = 0; *lo = 1; *hi = 255;
+  if (opts) {
+    if (opts->max_mismatches > FMX_APPROX_MAX_MISMATCHES) return arg_fail("fmx_approx_opts.max_mismatches: 0 .. 3");
+    if (opts->reserved != 0) return arg_fail("fmx_approx_opts.reserved must be 0");
+    if ((opts->sub_lo == 0) != (opts->sub_hi == 0)) return arg_fail("fmx_approx_opts: symbol 0 is never substituted (sub_lo >= 1; 0, 0 = the default range)");
+    if (opts->sub_lo > opts->sub_hi) return arg_fail("fmx_approx_opts: sub_lo > sub_hi");
+    *e = opts->max_mismatches;
+    if (opts->sub_lo) { *lo = opts->sub_lo; *hi = opts->sub_hi; }
+  }
+  if ((uint64_t)k > (1ull << 26)) return arg_fail("approx: at most 2^26 patterns per call");
+  if ((uint64_t)cap >= (1ull << 32)) return arg_fail("approx: cap must be below 2^32");
+  if (!out_off || (cap && !out)) return arg_fail("null argument");
+  if (!idx) return arg_fail("approx: the handle is null");
+  return approx_check(H(idx));
+}
+
+static int approx_overflow(const ApproxInfo &info, size_t cap) {
+  g_err = "search_approx: " + std::to_string(info.total) + " hits, room for " + std::to_string(cap);
+  return FMX_ERR_OVERFLOW;
+}
+
+int fmx_search_approx_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k, const fmx_approx_opts *opts,
+                                void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream) {
+  uint32_t e, lo, hi;
+  int rc = approx_args(idx, k, opts, d_out_off, d_out, cap, n_out, &e, &lo, &hi);
+  if (rc) return rc;
+  if (k && !d_off) return arg_fail("null argument");
+  const Index *h = H(idx);
+  if ((rc = use_device(h))) return rc;
+  if ((rc = not_capturing((hipStream_t)stream, "an approximate search"))) return rc;
+  ApproxInfo info;
+  rc = approx_search(h, d_pat, d_off, k, e, lo, hi, d_out_off, d_out, cap, (hipStream_t)stream, &info);
+  g_approx_last = info;
+  if (rc) return rc;
+  *n_out = (size_t)info.total;
+  return info.total > cap ? approx_overflow(info, cap) : FMX_OK;
+}
+
+int fmx_search_approx_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k, const fmx_approx_opts *opts,
+                            uint64_t *out_off, fmx_approx_hit *out, size_t cap, size_t *n_out) {
+  uint32_t e, lo, hi;
+  if (k && (uint64_t)k <= (1ull << 26) && off && !offsets_monotonic(off, 0, k)) return arg_fail("pattern offsets must be non-decreasing");
+  int rc = approx_args(idx, k, opts, out_off, out, cap, n_out, &e, &lo, &hi);
+  if (rc) return rc;
+  if (k && !off) return arg_fail("null argument");
+  const uint64_t lo_off = k ? off[0] : 0, total_bytes = k ? off[k] - lo_off : 0;
+  if (total_bytes && !pat) return arg_fail("pat is null");
+  const Index *h = H(idx);
+  if ((rc = use_device(h))) return rc;
+  DevMem mem;
+  StreamGuard own;
+  HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
+  uint8_t *d_pat = nullptr;
+  uint64_t *d_off = nullptr, *d_out_off = nullptr;
+  fmx_approx_hit *d_out = nullptr;
+  DEV_ALLOC(mem, d_pat, total_bytes, "approx patterns");
+  DEV_ALLOC(mem, d_off, 8 * (k + 1), "approx offsets");
+  DEV_ALLOC(mem, d_out_off, 8 * (k + 1), "approx offsets");
+  DEV_ALLOC(mem, d_out, sizeof(fmx_approx_hit) * cap, "approx hits");
+  if (k) {
+    std::vector<uint64_t> rebased(k + 1);                  // only the bytes in use travel
+    for (size_t q = 0; q <= k; q++) rebased[q] = off[q] - lo_off;
+    HIP_TRY(hipMemcpyAsync(d_off, rebased.data(), 8 * (k + 1), hipMemcpyHostToDevice, own.s), "H2D(offsets)");
+    if (total_bytes) HIP_TRY(hipMemcpyAsync(d_pat, pat + lo_off, total_bytes, hipMemcpyHostToDevice, own.s), "H2D(patterns)");
+    HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
+  }
+  ApproxInfo info;
+  rc = approx_search(h, d_pat, d_off, k, e, lo, hi, d_out_off, d_out, cap, own.s, &info);
+  g_approx_last = info;
+  if (rc) return rc;
+  *n_out = (size_t)info.total;
+  if (info.total > cap) return approx_overflow(info, cap);
+  HIP_TRY(hipMemcpyAsync(out_off, d_out_off, 8 * (k + 1), hipMemcpyDeviceToHost, own.s), "D2H(offsets)");
+  if (info.total) HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(fmx_approx_hit) * info.total, hipMemcpyDeviceToHost, own.s), "D2H(hits)");
+  HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
+  return FMX_OK;
+}
+
+int fmx_approx_last(double *search_ms, double *sort_ms, uint64_t *steps, uint64_t *requests) {
+  if (search_ms) *search_ms = g_approx_last.search_ms;
+  if (sort_ms) *sort_ms = g_approx_last.sort_ms;
+  if (steps) *steps = g_approx_last.steps;
+  if (requests) *requests = g_approx_last.requests;
+  return FMX_OK;
+}
+
 // ---------------------------------------------------------------- statistics
 int fmx_stats(const fmx_index *idx, fmx_stats_t *out) {
   if (!idx || !out) return arg_fail("null argument");

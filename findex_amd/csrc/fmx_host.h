@@ -254,6 +254,18 @@ int lcp_prepare(const Index *h, hipStream_t st);   // builds the handle's array 
 void lcp_drop(Index *h);
 hipError_t launch_lcp_gather(const Index *h, const void *d_rows, uint64_t k, void *d_out, hipStream_t st);
 
+// fmx_approx.hip: approximate search.  approx_check: FMX_ERR_UNSUPPORTED for handles it does not serve.
+// approx_search: the hits of k patterns within e substitutions from [lo, hi], device pointers throughout; allocates,
+// synchronises `st`, frees its temporaries on every path.  info->total is the exact number of hits; when it exceeds cap
+// nothing is ordered and d_out_off / d_out are unspecified.
+struct ApproxInfo {
+  uint64_t total = 0, steps = 0, requests = 0;
+  double search_ms = 0.0, sort_ms = 0.0;      // device events: the search kernel, the ordering step
+};
+int approx_check(const Index *h);
+int approx_search(const Index *h, const void *d_pat, const void *d_off, uint64_t k, uint32_t e, uint32_t lo, uint32_t hi,
+                  void *d_out_off, void *d_out, uint64_t cap, hipStream_t st, ApproxInfo *info);
+
 // fmx_search.hip: the residency census of the k_search4 instantiation this handle's full-size searches use now, taken with
 // calibration launches on `st` (synchronises it): fmx_prepare's last step, never a _dev call's.
 hipError_t search_calibrate(const Index *h, hipStream_t st);

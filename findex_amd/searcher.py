@@ -326,6 +326,62 @@ class HipFMSearcher:
         """LCPCreator.create (bwtmerger.scala:558-652): write the reference's X.lcp (n - 1 big-endian int32)."""
         _lib.check(self._L.fmx_write_lcp(self._h, str(path).encode()))
 
+    # ---- approximate search: up to three substituted bytes (fmx_search_approx_batch, DESIGN.md 15)
+    APPROX_HIT = np.dtype([("pattern", np.uint32), ("mismatches", np.uint32), ("sp", np.uint64), ("ep", np.uint64)])
+
+    @staticmethod
+    def _approx_opts(max_mismatches, sub):
+        lo, hi = (int(sub[0]), int(sub[1]))
+        if not (0 <= lo <= 255 and 0 <= hi <= 255 and 0 <= int(max_mismatches) < 2 ** 32):
+            raise ValueError("max_mismatches or sub out of range")
+        return _lib.fmx_approx_opts(int(max_mismatches), lo, hi, 0)
+
+    def search_approx_batch(self, pat, off, max_mismatches, sub=(1, 255), cap=None):
+        """fmx_search_approx_batch: every string within max_mismatches (0 .. 3) substitutions of each pattern that occurs,
+        the substituted bytes taken from sub = (lo, hi).  -> (off[k + 1], hits): pattern q's hits are
+        hits[off[q]:off[q + 1]], a structured array (pattern, mismatches, sp, ep) by ascending sp.  cap=None: a counting
+        call sizes the buffer; with a cap that is too small the library's FMX_ERR_OVERFLOW is raised."""
+        pat = np.ascontiguousarray(pat, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        k = max(off.size - 1, 0)
+        opts = self._approx_opts(max_mismatches, sub)
+        n_out = ctypes.c_size_t()
+        out_off = np.zeros(k + 1, dtype=np.uint64)
+        if cap is None:
+            rc = self._L.fmx_search_approx_batch(self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts), _ptr(out_off), None, 0,
+                                                 ctypes.byref(n_out))
+            if rc != 9:                      # FMX_ERR_OVERFLOW: n_out is the exact total
+                _lib.check(rc)
+                return out_off, np.zeros(0, dtype=self.APPROX_HIT)
+            cap = int(n_out.value)
+        hits = np.zeros(max(int(cap), 1), dtype=self.APPROX_HIT)
+        _lib.check(self._L.fmx_search_approx_batch(self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts), _ptr(out_off),
+                                                   _ptr(hits), int(cap), ctypes.byref(n_out)))
+        return out_off, hits[: int(n_out.value)]
+
+    def search_approx(self, pat, max_mismatches, sub=(1, 255)):
+        """One pattern: the list of (sp, ep, mismatches), by ascending sp."""
+        pat = bytes(pat)
+        _, hits = self.search_approx_batch(np.frombuffer(pat, dtype=np.uint8), np.array([0, len(pat)], dtype=np.uint64),
+                                           max_mismatches, sub)
+        return [(int(h["sp"]), int(h["ep"]), int(h["mismatches"])) for h in hits]
+
+    def search_approx_batch_dev(self, d_pat, d_off, k, max_mismatches, d_out_off, d_out, cap, sub=(1, 255), stream=0):
+        """fmx_search_approx_batch_dev: device pointers (u8 patterns, u64 offsets[k + 1], u64 out_off[k + 1], 24-byte hit
+        records); allocates and synchronises.  -> the exact number of hits (FMX_ERR_OVERFLOW is raised when it exceeds cap)."""
+        opts = self._approx_opts(max_mismatches, sub)
+        n_out = ctypes.c_size_t()
+        _lib.check(self._L.fmx_search_approx_batch_dev(self._h, _dp(d_pat), _dp(d_off), int(k), ctypes.byref(opts), _dp(d_out_off),
+                                                       _dp(d_out), int(cap), ctypes.byref(n_out), _dp(stream)))
+        return int(n_out.value)
+
+    def approx_last(self):
+        """fmx_approx_last: (search kernel ms, ordering ms, backward steps, rank-dictionary requests) of this thread's last
+        approximate search."""
+        a, b, c, d = ctypes.c_double(), ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64()
+        _lib.check(self._L.fmx_approx_last(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
+        return float(a.value), float(b.value), int(c.value), int(d.value)
+
     # ---- batched forms (host arrays in, host arrays out)
     def occ_batch(self, c, i):
         c = np.ascontiguousarray(c, dtype=np.uint8)

@@ -451,6 +451,51 @@ int fmx_lcp_info(const fmx_index *idx, uint64_t *bytes, double *build_ms, uint32
 int fmx_write_lcp(const fmx_index *idx, const char *path);
 int fmx_lcp_last_phases(double *phi_ms, double *plcp_ms, double *gather_ms);
 
+/* ---- approximate search: literal patterns with up to FMX_APPROX_MAX_MISMATCHES substituted bytes (Hamming distance; no
+ * insertions or deletions).  Beyond the reference.  DESIGN.md 15.
+ * For pattern P of m bytes (matched last byte first, as fmx_search_batch takes it), a budget e = max_mismatches and a
+ * substitution range [sub_lo, sub_hi], a HIT is a byte string Q of m bytes that differs from P in d <= e positions, holds a
+ * byte of the range at every differing position, and for which the reference's search(Q) loop (findex.scala:15-31) ends with
+ * sp < ep.  It is reported as (pattern, d, sp, ep) with (sp, ep) exactly what fmx_search_batch returns for Q.  The definition
+ * rests on cf / occ alone, so it holds for any handle (distinct Q of one length have disjoint intervals: LF is a permutation).
+ * Symbol 0, the EOF slot, is never substituted (sub_lo >= 1); where Q agrees with P it holds whatever byte P holds.  An empty
+ * pattern has the one hit (0, n) with d = 0; with e = 0 the hits are the patterns fmx_search_batch finds, with its intervals.
+ * Results are in CSR form: pattern q's hits are out[out_off[q] .. out_off[q + 1]), by ascending sp (unique within a pattern),
+ * out_off[k] == *n_out: the same input gives the same bytes on every run.
+ * opts == NULL: e = 0 and the default range 1 .. 255 (sub_lo = sub_hi = 0 asks for the default range too).
+ * Capacity: when the batch has more than cap hits nothing is written past out[cap - 1] and the call returns FMX_ERR_OVERFLOW
+ * with *n_out = the EXACT total (out and out_off are then unspecified: call again with cap >= *n_out); cap == 0 with
+ * out == NULL is the counting call.
+ * FMX_ERR_ARG, decided before the device is touched: a null handle, n_out or out_off; max_mismatches above the maximum;
+ * sub_lo > sub_hi, or exactly one of them 0; reserved != 0; decreasing offsets (host form); k > 2^26; cap >= 2^32.
+ * FMX_ERR_UNSUPPORTED: fmx_open_block handles (and indexes of 2^38 rows or more).
+ * fmx_search_approx_batch_dev: device pointers for patterns, offsets and outputs, n_out a host pointer.  Both forms ALLOCATE
+ * AND SYNCHRONISE (FMX_ERR_HIP under a stream capture) and free every temporary on every path: 24 cap bytes of staging, and
+ * 24 bytes per hit of sort keys and values, beside a quarter megabyte of counters.  They use the rank dictionary only, build no derived
+ * table and do not count as patterns seen; their steps are added to the handle's counters (rank_queries, backward_steps,
+ * search_requests) and the call to launches.
+ * fmx_approx_last: the calling thread's last call: device time (ms) of the search kernel and of the ordering step, backward
+ * steps executed, rank-dictionary requests issued; any pointer may be NULL. */
+#define FMX_APPROX_MAX_MISMATCHES 3
+typedef struct fmx_approx_hit {
+  uint32_t pattern;
+  uint32_t mismatches;
+  uint64_t sp;
+  uint64_t ep;
+} fmx_approx_hit; /* 24 bytes */
+typedef struct fmx_approx_opts {
+  uint32_t max_mismatches; /* 0 .. FMX_APPROX_MAX_MISMATCHES */
+  uint8_t sub_lo, sub_hi;  /* substitution symbols, inclusive; 0,0 = the default 1 .. 255 */
+  uint16_t reserved;       /* must be 0 */
+} fmx_approx_opts;
+int fmx_search_approx_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k,
+                            const fmx_approx_opts *opts, uint64_t *out_off /* k + 1 */, fmx_approx_hit *out, size_t cap,
+                            size_t *n_out);
+int fmx_search_approx_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k,
+                                const fmx_approx_opts *opts, void *d_out_off, void *d_out, size_t cap, size_t *n_out,
+                                void *stream);
+int fmx_approx_last(double *search_ms, double *sort_ms, uint64_t *steps, uint64_t *requests);
+
 /* ---- corpus: a directory of files as ONE index -- DirBWTReader (bwtreader.scala:17-173), the input side of the reference's
  * IndexerApp -- and, beyond the reference, the way back from a stream position to (document, offset).
  * The STREAM: the documents in the caller's order; in each, raw byte 0 becomes '\' '0', raw 1 becomes '\' '1' and raw 255
