@@ -12,7 +12,8 @@
 // on the wave's stack in LDS (a node that pushes has d <= e - 2: at most two frames), and the wave descends into the
 // round's children one at a time; the match child is taken last, as the continuation of the loop.
 // The one-row rule: a node of exactly one row has one non-empty child, the symbol BWT'[sp] (0 on the EOF row, which no
-// range holds) -- it tries that symbol and nothing else.
+// range holds) -- where that symbol is a candidate other than P[i - 1] the node tries it and nothing else; otherwise it
+// makes the match step alone, like a node without budget.
 //
 // Hits go to a staging area of `cap` records in the order they are found (one atomic per wave and round, positions from
 // a ballot prefix; appends past cap are counted, not written); a radix sort of pattern << 38 | sp with the staging index
@@ -195,7 +196,7 @@ __global__ __launch_bounds__(kApThreads) void k_approx(DevIndex ix, const uint8_
           break;
         }
         if (pushed) { node = false; continue; }
-        if (one && bsym != pc) { node = false; continue; }   // the node's only row holds another symbol: no match child
+        if (one && nc) { node = false; continue; }           // the node tried its row's symbol: no match child
       }
       step(pc, sp, ep, lane == 0);                           // the match child: every group makes the same step
       i--;

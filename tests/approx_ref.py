@@ -1,4 +1,5 @@
-"""Two independent expectations for the approximate search (fmx_search_approx_batch); neither uses the library.
+"""Two independent expectations for the approximate search (fmx_search_approx_batch), window_hits and dfs_hits, and walk,
+the kernel's own walk restated with the backward steps it makes; none uses the library.
 
 A hit of pattern P with budget e and substitution range [lo, hi] is a string Q of len(P) bytes that differs from P in
 d <= e positions, holds a byte of the range at each of them and occurs in the index; it is reported as (sp, ep, d) with
@@ -74,6 +75,73 @@ def dfs_hits(orc, P, e, lo=1, hi=255):
 
     walk(len(P), 0, 0, orc.n)
     return sorted(out)
+
+
+def occurring(orc, lo=0, hi=255):
+    """The symbols of [lo, hi] that occur in the index (occ over all rows; the filler byte of the EOF slot is no occurrence),
+    ascending; kept on the searcher."""
+    memo = orc.__dict__.setdefault("_approx_occurring", {})
+    if (lo, hi) not in memo:
+        memo[(lo, hi)] = np.array([c for c in range(lo, hi + 1) if orc.occ(c, orc.n - 1) > 0], dtype=np.uint8)
+    return memo[(lo, hi)]
+
+
+def row_symbol(orc, row):
+    """BWT'[row]: the symbol of the row, 0 on the EOF row.  From bwt_read where the searcher has it, else from occ alone:
+    the one symbol whose count grows at the row."""
+    if hasattr(orc, "bwt_read"):
+        return int(orc.bwt_read(row))
+    for c in occurring(orc, 1, 255).tolist():
+        if orc.occ(c, row) != orc.occ(c, row - 1):
+            return c
+    return 0
+
+
+def walk(orc, P, e, lo=1, hi=255):
+    """The walk of fmx_approx.hip as DESIGN.md 15 describes it, restated over the oracle, with the backward steps it makes.
+    The candidates are the symbols of [lo, hi] that occur in the index.  A node (i bytes left, d mismatches, sp, ep):
+      * with d < e and more than one row: one step per candidate c != P[i - 1], every non-empty one a child with d + 1;
+        then the match step with P[i - 1];
+      * with d < e and exactly one row (the one-row rule): it tries BWT'[sp] alone, and only if that differs from P[i - 1]
+        and is a candidate -- one step, and no match child; otherwise it makes the match step;
+      * with d == e (an exact tail, or e = 0): the match step only, until the interval is empty or the pattern is through.
+    Every step counts, the one that empties an interval included.  -> (sorted list of (sp, ep, d), steps)."""
+    P = bytes(P)
+    cand = occurring(orc, lo, hi)
+    is_cand = set(cand.tolist())
+    hits = []
+    steps = 0
+
+    def node(i, d, sp, ep):
+        nonlocal steps
+        while i > 0:                                         # the match child is the continuation of the loop
+            pc = P[i - 1]
+            if d < e:
+                if ep - sp == 1:
+                    b = row_symbol(orc, sp)
+                    if b != pc and b in is_cand:
+                        steps += 1
+                        r = orc.getPrevRange(sp, ep, b)
+                        if r is not None:
+                            node(i - 1, d + 1, int(r[0]), int(r[1]))
+                        return
+                else:
+                    cs = cand[cand != pc]
+                    if cs.size:
+                        a, b = orc.prev_range_batch(np.full(cs.size, sp, dtype=np.uint64), np.full(cs.size, ep, dtype=np.uint64), cs)
+                        steps += int(cs.size)
+                        for j in np.nonzero(a < b)[0].tolist():
+                            node(i - 1, d + 1, int(a[j]), int(b[j]))
+            steps += 1
+            r = orc.getPrevRange(sp, ep, pc)
+            if r is None:
+                return
+            sp, ep = int(r[0]), int(r[1])
+            i -= 1
+        hits.append((sp, ep, d))
+
+    node(len(P), 0, 0, orc.n)
+    return sorted(hits), steps
 
 
 def within(hits, e):

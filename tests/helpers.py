@@ -1,4 +1,6 @@
 """Shared test helpers (CPU only, numpy)."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -222,3 +224,47 @@ def frontier_oracle(orc, tables, max_len=0, **batch_kw):
         ep = np.repeat(b[grow], cnt)
     out = np.concatenate(parts) if parts else np.zeros(0, dtype=FRONTIER_DTYPE)
     return out[np.lexsort((out["ep"], out["sp"], out["len"], out["regex"]))], calls, truncated
+
+
+# ---------------------------------------------------------------- shared by the modules that open an index above 2^32 rows
+def forward_string(orc, row, length, syms=b"abcd"):
+    """The first `length` bytes of the suffix of `row`, from cf and occ alone: the first byte is the bucket the row lies
+    in, the next row is the position of that byte's (row - cf + 1)-th occurrence in the BWT (binary search over occ).
+    `syms`: the symbols the index holds."""
+    syms = [0] + list(syms)
+    cf = {c: orc.cf(c) for c in syms}
+    out = bytearray()
+    for _ in range(length):
+        c = max(s for s in syms if cf[s] <= row)
+        assert c != 0, "the walk reached the end of the text"
+        out.append(c)
+        k = row - cf[c] + 1
+        lo, hi = 0, orc.n - 1
+        while lo < hi:
+            mid = (lo + hi) // 2
+            if orc.occ(c, mid) >= k:
+                hi = mid
+            else:
+                lo = mid + 1
+        row = lo
+    return bytes(out)
+
+
+_fault = []
+
+
+def ends_at_a_fault(test):
+    """A HIP error in one case ends the work on the device there: the cases after it, of this module and of every other
+    that uses this guard, fail without touching the device again."""
+    @functools.wraps(test)
+    def run(*args, **kw):
+        import findex_amd
+        if _fault:
+            pytest.fail("an earlier case ended with a HIP error, nothing more is started on the device: " + _fault[0])
+        try:
+            return test(*args, **kw)
+        except findex_amd.FmxError as e:
+            if e.code == 5:      # FMX_ERR_HIP
+                _fault.append(str(e))
+            raise
+    return run

@@ -45,6 +45,64 @@ def test_the_two_references_agree_on_tiny_inputs():
     assert approx_ref.window_hits(s, b"", 2) == approx_ref.dfs_hits(orc, b"", 2) == [(0, 61, 0)]
 
 
+def test_the_restated_walk_against_both_references_and_the_oracles_steps():
+    """approx_ref.walk on the same tiny inputs: its hits are dfs_hits' (which has no one-row shortcut and no candidate
+    list), for the ranges that leave letters out and for byte 0 as well; at e = 0 its steps are the oracle's search_batch
+    steps; and its steps obey what the description fixes without any kernel: a larger budget never makes fewer steps, and a
+    range without a letter of the index makes exactly the steps of e = 0."""
+    from helpers import pack_patterns
+    rng = np.random.default_rng(7)
+    s = bytes(rng.integers(97, 100, 60, dtype=np.uint8))
+    orc = approx_ref.index_of(s)[0]
+    pats = [bytes(P) for m in range(1, 5) for P in itertools.product(b"abc", repeat=m)]
+    pats += [bytes(P) for m in range(1, 4) for P in itertools.product(b"ab\0", repeat=m)]
+    pats += [b"", s[:12], s[20:44], s[-9:], s, s + b"a", b"z" + s[3:9], s[3:9] + b"z"]
+    buf, off = pack_patterns(pats)
+    _, _, exact = orc.search_batch(buf, off)
+    one_row = 0
+    for P, st0 in zip(pats, exact.tolist()):
+        before = None
+        for e in range(4):
+            hits, steps = approx_ref.walk(orc, P, e)
+            assert hits == approx_ref.dfs_hits(orc, P, e), (P, e)
+            assert before is None or steps >= before, (P, e)
+            before = steps
+            if e == 0:
+                assert steps == st0, (P, steps, st0)
+            one_row += sum(1 for sp, ep, d in hits if ep - sp == 1 and d == e)
+        for sub in ((98, 99), (97, 97), (99, 255)):
+            assert approx_ref.walk(orc, P, 2, *sub)[0] == approx_ref.dfs_hits(orc, P, 2, *sub), (P, sub)
+        hits, steps = approx_ref.walk(orc, P, 3, 1, 96)
+        assert hits == approx_ref.dfs_hits(orc, P, 0) and steps == st0, P
+    assert one_row > 500                                     # hits that were reached through nodes of one row
+    assert approx_ref.walk(orc, b"", 2) == ([(0, 61, 0)], 0)
+    # the step count by hand: sigma = 3, one pattern byte, e = 1: two candidates and the match step
+    assert approx_ref.walk(orc, b"a", 1)[1] == 3 and approx_ref.walk(orc, b"a", 1, 98, 99)[1] == 3
+    assert approx_ref.walk(orc, b"z", 1)[1] == 4 and approx_ref.walk(orc, b"a", 1, 97, 97)[1] == 1
+
+
+def test_the_restated_walk_on_a_synthetic_bwt_and_the_sampled_searcher():
+    """A BWT that is no text's (the EOF slot first, in the middle, last), and oracle.SampledFMSearcher, which has no
+    bwt_read: the row's symbol comes from occ there.  Both searchers give the same hits and the same steps."""
+    import oracle
+    from helpers import lf_walk_patterns, synth_bwt
+    for eof in (0, 150, 299):
+        index = synth_bwt(300, 97, 100, seed=9, eof=eof)
+        orc = oracle.NaiveFMSearcher.from_mem(*index)
+        smp = oracle.SampledFMSearcher(index[0], eof)
+        rng = np.random.default_rng(eof)
+        pats = lf_walk_patterns(orc, rng, 30, 7, 0.5, alphabet=[97, 98, 99, 100])
+        for r in range(0, 300, 37):
+            assert approx_ref.row_symbol(smp, r) == approx_ref.row_symbol(orc, r) == (0 if r == eof else int(index[0][r]))
+        assert approx_ref.row_symbol(smp, eof) == 0
+        for P in pats:
+            for e in range(3):
+                got = approx_ref.walk(orc, P, e)
+                assert got[0] == approx_ref.dfs_hits(orc, P, e), (eof, P, e)
+                assert approx_ref.walk(smp, P, e) == got, (eof, P, e)
+        smp.close()
+
+
 def test_struct_layouts():
     assert ctypes.sizeof(_lib.fmx_approx_hit) == 24
     assert ctypes.sizeof(_lib.fmx_approx_opts) == 8

@@ -1,7 +1,10 @@
 """Approximate search on the device (fmx_search_approx_batch) against tests/approx_ref.py, in both layouts:
 real texts with dense and wide alphabets against the sliding window, synthetic BWTs around the block edges against the
-walk over getPrevRange, the one-row rule and the EOF row, e = 0 against the exact search, degenerate shapes, capacity,
-order and determinism, the device form and a stream capture, and the corpus searcher."""
+walk over getPrevRange, the one-row rule and the EOF row, e = 0 against the exact search, batches of three times as many
+patterns as a grid can have waves (e = 0 .. 3), patterns of up to 3001 bytes, degenerate shapes, capacity, order and
+determinism, the device form and a stream capture, and the corpus searcher.  Where a test passes `steps`, the backward steps
+fmx_approx_last reports are held to approx_ref.walk, the walk of DESIGN.md 15 restated over the oracle -- never to a count
+read off the library."""
 import ctypes
 import os
 
@@ -22,6 +25,14 @@ HIT = findex_amd.HipFMSearcher.APPROX_HIT
 OVERFLOW = 9
 
 
+def waves_max():
+    """More waves than a launch of k_approx can have resident: a CU holds at most 2048 threads, 8 workgroups of 256, four
+    waves each.  An upper bound, not the occupancy query the library makes: a batch of 3 * waves_max() patterns and more
+    makes every wave's loop over the batch go round at least three times."""
+    import torch
+    return 8 * 4 * torch.cuda.get_device_properties(0).multi_processor_count
+
+
 def open_index(index, layout):
     findex_amd.set_layout(layout)
     try:
@@ -39,13 +50,29 @@ def expected_arrays(per_pattern):
     return np.array(off, dtype=np.uint64), np.array(rows, dtype=HIT) if rows else np.zeros(0, dtype=HIT)
 
 
-def check(hip, pats, e, per_pattern, sub=(1, 255), what=None):
-    """One batch against its expectation, per-pattern lists of (sp, ep, d)."""
+def check(hip, pats, e, per_pattern, sub=(1, 255), what=None, steps=None):
+    """One batch against its expectation, per-pattern lists of (sp, ep, d); with `steps`, the backward steps approx_ref.walk
+    makes for the batch, also what fmx_approx_last reports of the call."""
     buf, off = pack_patterns(pats)
     got_off, got = hip.search_approx_batch(buf, off, e, sub=sub)
     exp_off, exp = expected_arrays(per_pattern)
     assert np.array_equal(got_off, exp_off), (what, e)
     assert got.tobytes() == exp.tobytes(), (what, e)
+    if steps is not None:
+        _, _, got_steps, requests = hip.approx_last()
+        print("%s e=%d: %d steps (walk: %d), %d requests" % (what, e, got_steps, steps, requests))
+        assert got_steps == steps, (what, e, got_steps, steps)
+        assert 0 < requests <= 4 * steps, (what, e, requests, steps)
+
+
+def walk_steps(orc, pats, e, per_pattern, sub=(1, 255)):
+    """The steps approx_ref.walk makes for the batch; its hits must be the expectation's on the way."""
+    total = 0
+    for p, want in zip(pats, per_pattern):
+        hits, steps = approx_ref.walk(orc, p, e, *sub)
+        assert hits == sorted(want), (p, e)
+        total += steps
+    return total
 
 
 def mutated(rng, s, m, alphabet, k=200):
@@ -152,17 +179,19 @@ def synth():
         orc = oracle.NaiveFMSearcher.from_mem(*index)
         rng = np.random.default_rng(n + eof)
         pats = [p for m in (8, 16) for p in lf_walk_patterns(orc, rng, k, m, 0.5, alphabet=list(range(lo, hi + 1)))]
-        out.append((index, (lo, hi, n, eof), pats, [approx_ref.dfs_hits(orc, p, 2) for p in pats]))
+        full = [approx_ref.dfs_hits(orc, p, 2) for p in pats]
+        steps = [walk_steps(orc, pats, e, [approx_ref.within(h, e) for h in full]) for e in range(3)]
+        out.append((index, (lo, hi, n, eof), pats, full, steps))
     return out
 
 
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_synthetic_bwts_against_the_walk(synth, layout):
     found = 0
-    for index, shape, pats, full in synth:
+    for index, shape, pats, full, steps in synth:
         hip = open_index(index, layout)
         for e in range(3):
-            check(hip, pats, e, [approx_ref.within(h, e) for h in full], what=shape)
+            check(hip, pats, e, [approx_ref.within(h, e) for h in full], what=shape, steps=steps[e])
         found += sum(len(h) for h in full)
         hip.close()
     assert found > 800
@@ -189,12 +218,14 @@ def prefix_case():
         for y in (s[m], 122):
             pats.append(bytes([y]) + base)
             kind.append("extended")
-    return s, pats, kind, [approx_ref.window_hits(s, p, 2) for p in pats]
+    full = [approx_ref.window_hits(s, p, 2) for p in pats]
+    orc = approx_ref.index_of(s)[0]
+    return s, pats, kind, full, [walk_steps(orc, pats, e, [approx_ref.within(h, e) for h in full]) for e in range(3)]
 
 
 @pytest.mark.parametrize("layout", LAYOUTS)
 def test_one_row_rule_and_the_eof_row(prefix_case, layout):
-    s, pats, kind, full = prefix_case
+    s, pats, kind, full, steps = prefix_case
     for e in (1, 2):
         exp = [approx_ref.within(h, e) for h in full]
         # the text's own beginning is found, exactly and behind one replaced byte; one byte further in front it is not
@@ -204,7 +235,7 @@ def test_one_row_rule_and_the_eof_row(prefix_case, layout):
     assert all(not approx_ref.within(h, 0) for h, kd in zip(full, kind) if kd == "first")
     hip = open_text(s, layout)
     for e in (0, 1, 2):
-        check(hip, pats, e, [approx_ref.within(h, e) for h in full], what="prefix")
+        check(hip, pats, e, [approx_ref.within(h, e) for h in full], what="prefix", steps=steps[e])
     hip.close()
 
 
@@ -214,7 +245,13 @@ def test_budget_zero_is_the_exact_search(layout):
     index = synth_bwt(4500, 97, 100, seed=31)
     orc = oracle.NaiveFMSearcher.from_mem(*index)
     rng = np.random.default_rng(32)
-    pats = lf_walk_patterns(orc, rng, 5000, 16, 0.5, alphabet=[97, 98, 99, 100])      # more patterns than a grid has waves
+    walks = lf_walk_patterns(orc, rng, 5000, 16, 0.5, alphabet=[97, 98, 99, 100])
+    # more patterns than three times the waves any grid can have: the 5000 walks over and over, each time in another order
+    k = 3 * waves_max() + 5
+    order = np.concatenate([rng.permutation(len(walks)) for _ in range(-(-k // len(walks)))])[:k]
+    assert k > len(walks) and sorted(order[:len(walks)].tolist()) == list(range(len(walks)))
+    pats = [walks[j] for j in order.tolist()]
+    print("e = 0: k = %d patterns, at most %d waves" % (k, waves_max()))
     buf, off = pack_patterns(pats)
     hip = open_index(index, layout)
     hip.config_set("jump", "off")
@@ -229,7 +266,7 @@ def test_budget_zero_is_the_exact_search(layout):
     seen, launches = st["patterns_seen"], st["launches"]
     got_off, hits = hip.search_approx_batch(buf, off, 0)
     found = sp < ep
-    assert 1000 < int(found.sum()) < 4500
+    assert 1000 < int(found[:len(walks)].sum()) < 4500       # (the first 5000 are the walks themselves, each once)
     assert np.array_equal(np.diff(got_off.astype(np.int64)), found.astype(np.int64))
     assert np.array_equal(hits["pattern"], np.nonzero(found)[0]) and not hits["mismatches"].any()
     assert np.array_equal(hits["sp"], sp[found]) and np.array_equal(hits["ep"], ep[found])
@@ -247,6 +284,191 @@ def test_budget_zero_is_the_exact_search(layout):
     assert L.fmx_search_approx_batch(hip.handle, buf.ctypes.data, off.ctypes.data, off.size - 1, None, o2.ctypes.data,
                                      h2.ctypes.data, h2.size, ctypes.byref(n_out)) == 0
     assert n_out.value == hits.size and np.array_equal(o2, got_off) and h2.tobytes() == hits.tobytes()
+    hip.close()
+
+
+# ---------------------------------------------------------------- several patterns per wave, e >= 1
+class Pool:
+    """Distinct patterns with their hits at e = 3 (flat arrays, each pattern's by ascending sp) and their walk steps per
+    budget: a batch is an array of pool indices, and its expectation is expanded from the pool's with numpy."""
+
+    def __init__(self, s, pats, budgets):
+        orc = approx_ref.index_of(s)[0]
+        self.pats = pats
+        self.len = np.array([len(p) for p in pats])
+        full = [approx_ref.window_hits(s, p, 3) for p in pats]
+        self.hits = np.array([h for hs in full for h in hs], dtype=np.int64).reshape(-1, 3)      # (sp, ep, d)
+        self.owner = np.repeat(np.arange(len(pats)), [len(hs) for hs in full])
+        self.steps = {e: np.array([walk_steps(orc, [p], e, [approx_ref.within(hs, e)]) for p, hs in zip(pats, full)],
+                                  dtype=np.int64) for e in budgets}
+
+    def expected(self, idx, e):
+        """-> (off, records, steps) of the batch [pats[j] for j in idx] at budget e."""
+        keep = self.hits[:, 2] <= e
+        hits, owner = self.hits[keep], self.owner[keep]
+        cnt = np.bincount(owner, minlength=len(self.pats))
+        first = np.cumsum(cnt) - cnt
+        per = cnt[idx]
+        off = np.concatenate([[0], np.cumsum(per)])
+        src = np.repeat(first[idx] - off[:-1], per) + np.arange(int(off[-1]))
+        rows = np.zeros(int(off[-1]), dtype=HIT)
+        rows["pattern"] = np.repeat(np.arange(idx.size), per)
+        rows["sp"], rows["ep"], rows["mismatches"] = hits[src, 0], hits[src, 1], hits[src, 2]
+        return off.astype(np.uint64), rows, int(self.steps[e][idx].sum())
+
+
+@pytest.fixture(scope="module")
+def many(abcd_text):
+    """k = 3 * waves_max() + 5 patterns drawn with repetition from a pool over the abcd text: lengths 1, 6, 12 and 24 with
+    0 - 2 bytes replaced, the empty pattern, and patterns that have no hit at any budget; and a second draw from the pool's
+    patterns of at most 12 bytes for e = 3 (a pattern of 6 bytes has some 350 hits there)."""
+    s = abcd_text
+    rng = np.random.default_rng(38)
+    pats = [b"", b"z" * 4, b"z" * 8, b"z" * 24, s[5:9] + b"zzzz" + s[13:17]]
+    for m in (1, 6, 12, 24):
+        pats += mutated(rng, s, m, [97, 98, 99, 100], 80)
+    pats = sorted(set(pats))
+    short = [p for p in pats if len(p) <= 12]
+    pool = Pool(s, pats, (1, 2))
+    pool3 = Pool(s, short, (3,))
+    W = waves_max()
+    k = 3 * W + 5
+    idx = rng.integers(0, len(pats), k)
+    idx3 = rng.integers(0, len(short), k)
+    return pool, idx, pool3, idx3, W
+
+
+def test_many_expectations_are_the_ones_the_kernel_needs(many):
+    pool, idx, pool3, idx3, W = many
+    k = idx.size
+    print("several patterns per wave: k = %d, waves_max = %d, pool of %d (%d of at most 12 bytes)"
+          % (k, W, len(pool.pats), len(pool3.pats)))
+    assert k >= 3 * W and k % 4 != 0 and 200 <= len(pool.pats) <= 400
+    for p, ix in ((pool, idx), (pool3, idx3)):
+        # a wave takes the patterns q, q + its stride, ...: whatever the stride (at most W), neighbours in that order differ
+        assert (ix[:-W] != ix[W:]).mean() > 0.95 and (p.len[ix[:-W]] != p.len[ix[W:]]).mean() > 0.4
+        assert (ix[:-4] != ix[4:]).mean() > 0.95
+        assert (p.len[ix] == 0).sum() >= 10
+    none = np.setdiff1d(np.arange(len(pool.pats)), pool.owner)
+    assert none.size >= 4 and np.isin(idx, none).sum() >= 50          # patterns without a hit at e = 3, and so at any budget
+    assert len({len(p) for p in pool.pats}) >= 7
+    for e in (1, 2):
+        _, rows, steps = pool.expected(idx, e)
+        print("e = %d: %d hits, %d steps" % (e, rows.size, steps))
+        assert rows.size > 50_000 and (rows["mismatches"] == e).sum() > 25_000
+    _, rows, steps = pool3.expected(idx3, 3)
+    print("e = 3: %d hits, %d steps" % (rows.size, steps))
+    assert 1_000_000 < rows.size < 5_000_000 and (rows["mismatches"] == 3).sum() > 500_000
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_several_patterns_per_wave(many, abcd_text, layout):
+    """Every wave's loop over the batch goes round three times and more, with e = 1, 2 and 3: the wave starts each pattern
+    from the root, whatever depth, round and frames the one before left behind.  Offsets and record bytes exactly, the
+    call's steps those of approx_ref.walk, and the handle's counters moved by them once per launch."""
+    pool, idx, pool3, idx3, W = many
+    hip = open_text(abcd_text, layout)
+    for p, ix, budgets in ((pool, idx, (1, 2)), (pool3, idx3, (3,))):
+        buf, off = pack_patterns([p.pats[j] for j in ix.tolist()])
+        for e in budgets:
+            exp_off, exp, steps = p.expected(ix, e)
+            assert 50_000 < exp.size < 5_000_000                    # asserted before the call: 24 bytes a record
+            st0 = hip.stats()
+            got_off, got = hip.search_approx_batch(buf, off, e)
+            st1 = hip.stats()
+            assert np.array_equal(got_off, exp_off), e
+            assert got.tobytes() == exp.tobytes(), e
+            _, _, got_steps, requests = hip.approx_last()
+            print("%s e = %d: k = %d, %d hits, %d steps (walk: %d), %d requests" % (layout, e, ix.size, got.size, got_steps, steps, requests))
+            assert got_steps == steps and 0 < requests <= 4 * steps, (e, got_steps, steps, requests)
+            # the counting call and the call that fetched the hits
+            assert st1["launches"] == st0["launches"] + 2
+            assert st1["backward_steps"] - st0["backward_steps"] == 2 * steps, e
+    hip.close()
+
+
+# ---------------------------------------------------------------- step counts on real texts, e = 1 .. 3
+@pytest.fixture(scope="module")
+def counted(dense, wide):
+    """One dense and one wide-alphabet batch with the steps of approx_ref.walk: 40 patterns each of 6 and of 24 bytes over
+    the abcd text, 8 each of 6 and of 12 bytes over the text of 255 symbols (a node of several rows steps 254 candidates
+    there, so the walk is not cheap on the host)."""
+    s, per_m = dense["abcd"]
+    pats = per_m[6][0][:40] + per_m[24][0][:40]
+    full = per_m[6][1][:40] + per_m[24][1][:40]
+    ws, cases = wide
+    by_m = {m: (p, f) for m, e, p, f in cases if e == 3}
+    wpats = by_m[6][0][:8] + by_m[12][0][:8]
+    wfull = by_m[6][1][:8] + by_m[12][1][:8]
+    out = []
+    for name, text, pp, ff in (("abcd", s, pats, full), ("wide", ws, wpats, wfull)):
+        orc = approx_ref.index_of(text)[0]
+        out.append((name, text, pp, ff, {e: walk_steps(orc, pp, e, [approx_ref.within(h, e) for h in ff]) for e in (1, 2, 3)}))
+    return out
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_step_counts_on_a_dense_and_a_wide_alphabet(counted, layout):
+    for name, text, pats, full, steps in counted:
+        hip = open_text(text, layout)
+        for e in (1, 2, 3):
+            check(hip, pats, e, [approx_ref.within(h, e) for h in full], what=name, steps=steps[e])
+        hip.close()
+
+
+# ---------------------------------------------------------------- long and ragged patterns
+LONG_M = (0, 1, 25, 64, 65, 255, 256, 257, 1000, 2999, 3000, 3001)
+
+
+@pytest.fixture(scope="module")
+def long_case(abcd_text):
+    """Per length the text's own substring and copies with one, two and three bytes replaced, at the first, a middle and
+    the last position; 3000 is the whole text, and 3001 -- as long as the index, its sentinel included -- the text with
+    byte 0 behind it and in front of it (the loop steps from the row of the whole text to the sentinel's: both occur), and a
+    pattern of that length that does not occur.  In mixed order."""
+    s = abcd_text
+    rng = np.random.default_rng(39)
+    pats = []
+    for m in LONG_M:
+        if m > len(s):
+            bases = [s + b"\0", b"\0" + s, s[1:] + b"ab"]
+        else:
+            at = 0 if m >= len(s) - 1 else int(rng.integers(1, len(s) - m))
+            bases = [s[at:at + m]]
+        for base in bases:
+            pats.append(base)
+            where = sorted({0, m // 2, m - 1}) if m else []
+            for pos in [(p,) for p in where] + ([(where[0], where[-1]), tuple(where[:2])] if len(where) >= 2 else []) + \
+                    ([tuple(where)] if len(where) == 3 else []):
+                p = bytearray(base)
+                for j in pos:
+                    p[j] = 97 + (p[j] - 97 + 1 + int(rng.integers(0, 3))) % 4 if p[j] else 97
+                pats.append(bytes(p))
+    pats = [pats[j] for j in rng.permutation(len(pats)).tolist()]
+    full = [approx_ref.window_hits(s, p, 3) for p in pats]
+    orc = approx_ref.index_of(s)[0]
+    steps = [walk_steps(orc, pats, e, [approx_ref.within(h, e) for h in full]) for e in range(4)]
+    return pats, full, steps
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_long_and_ragged_patterns(long_case, abcd_text, layout):
+    """An exact tail walks i - 1 steps in one lane group and a long pattern lives under the one-row rule: up to 3001 bytes,
+    hits behind three replaced bytes 1000 and more bytes apart, the whole text, and the text with its sentinel."""
+    s = abcd_text
+    pats, full, steps = long_case
+    assert {len(p) for p in pats} == set(LONG_M)
+    deep = [len(p) for p, h in zip(pats, full) if len(p) >= 1000 and any(d == 3 for _, _, d in h)]
+    print("long patterns: %d of %d bytes in all, with a hit at d = 3: lengths %s; steps %s"
+          % (len(pats), sum(len(p) for p in pats), sorted(deep), steps))
+    assert deep and max(deep) >= 3000
+    eof = approx_ref.index_of(s)[0].eof
+    assert full[pats.index(s)] == full[pats.index(s + b"\0")] == [(eof, eof + 1, 0)]      # the row of the whole text
+    assert full[pats.index(b"\0" + s)] == [(0, 1, 0)]                                      # the sentinel's row
+    assert not full[pats.index(s[1:] + b"ab")]
+    hip = open_text(s, layout)
+    for e in range(4):
+        check(hip, pats, e, [approx_ref.within(h, e) for h in full], what="long", steps=steps[e])
     hip.close()
 
 

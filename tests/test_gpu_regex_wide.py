@@ -17,7 +17,6 @@ comparison.
 The index, both handles and the oracle are made once for the module.  Searches run under a level cap throughout: on i.i.d.
 bytes LF has short cycles, and a starred regex can follow one for ever.
 """
-import functools
 import gc
 import time
 
@@ -26,7 +25,7 @@ import pytest
 
 import findex_amd
 from oracle import retree as R
-from helpers import _OIdx, frontier_oracle
+from helpers import _OIdx, ends_at_a_fault, forward_string, frontier_oracle
 import search_forms as sf
 
 pytestmark = pytest.mark.gpu
@@ -50,28 +49,6 @@ DEEP = ["d[a-d]*d", "c[a-d]*d", "a[a-d]*a", "a[ab]*d", "d[cd]*a", "d[a-d]*"]
 
 
 # ---------------------------------------------------------------- inputs, from the oracle alone
-def forward_string(orc, row, length):
-    """The first `length` bytes of the suffix of `row`, from cf and occ alone: the first byte is the bucket the row lies
-    in, the next row is the position of that byte's (row - cf + 1)-th occurrence in the BWT (binary search over occ)."""
-    syms = [0] + list(SYMS)
-    cf = {c: orc.cf(c) for c in syms}
-    out = bytearray()
-    for _ in range(length):
-        c = max(s for s in syms if cf[s] <= row)
-        assert c != 0, "the walk reached the end of the text"
-        out.append(c)
-        k = row - cf[c] + 1
-        lo, hi = 0, orc.n - 1
-        while lo < hi:
-            mid = (lo + hi) // 2
-            if orc.occ(c, mid) >= k:
-                hi = mid
-            else:
-                lo = mid + 1
-        row = lo
-    return bytes(out)
-
-
 def line_regexes(orc, line):
     """Regexes whose results hold the rows line - 1 and line.  A regex steps its first byte first, so the result of a
     literal is the interval of the suffixes that begin with the literal reversed: the prefixes of the two rows' suffixes,
@@ -234,24 +211,6 @@ def check_frontier_calls(w, hip, count_steps):
 
 
 # ---------------------------------------------------------------- the cases
-_fault = []
-
-
-def ends_at_a_fault(test):
-    """A HIP error in one case ends the module there: the cases after it fail without touching the device again."""
-    @functools.wraps(test)
-    def run(*args, **kw):
-        if _fault:
-            pytest.fail("an earlier case ended with a HIP error, nothing more is started on the device: " + _fault[0])
-        try:
-            return test(*args, **kw)
-        except findex_amd.FmxError as e:
-            if e.code == 5:      # FMX_ERR_HIP
-                _fault.append(str(e))
-            raise
-    return run
-
-
 @pytest.mark.parametrize("layout", LAYOUTS)
 @ends_at_a_fault
 def test_frontier_without_tables(wide, layout):
