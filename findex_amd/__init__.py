@@ -12,6 +12,8 @@ package is the thin host-side mirror of the reference's Scala interface for that
     BWTMerger2.merge(FileBWTReader) -> X.bwt/.aux  bwt_from_text(text) + write_bwt(...), python -m findex_amd.index
     LCPSuffixWalkingAlgo.getLCP, LCPCreator        HipFMSearcher.getLCP / .lcp / .write_lcp, lcp_from_text(text)
     DirBWTReader(dir) -> one stream, IndexerApp    Corpus.from_dir(dir), HipCorpusSearcher, python -m findex_amd.index --dir
+    (beyond the reference)                         HipFMSearcher.match_stats_batch / .mems_batch / .match_stats_text / .mems_text,
+                                                   HipCorpusSearcher.shared_passages
 
 There is no CPU fallback: importing works anywhere, but every compute call needs the built
 library and a HIP device and fails loudly otherwise.

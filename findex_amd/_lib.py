@@ -54,6 +54,20 @@ class fmx_approx_opts(ctypes.Structure):
                 ("reserved", ctypes.c_uint16)]
 
 
+FMX_MSTAT_MAX_LEN = 4096
+FMX_MSTAT_TILE = 512                  # positions per workgroup tile of the walk kernel (fmx.h)
+MSTAT_GROUPS = {"onehot": 16, "bytes": 8}      # lane groups per wave: quads, octets (fmx_device.h, Lay<LAYOUT>::G)
+
+
+class fmx_mstat_opts(ctypes.Structure):
+    _fields_ = [("max_len", ctypes.c_uint32), ("min_len", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+
+class fmx_mem_hit(ctypes.Structure):
+    _fields_ = [("pattern", ctypes.c_uint32), ("len", ctypes.c_uint32), ("end", ctypes.c_uint64), ("sp", ctypes.c_uint64),
+                ("ep", ctypes.c_uint64)]
+
+
 class fmx_stats_t(ctypes.Structure):
     _fields_ = [("rank_queries", ctypes.c_uint64), ("backward_steps", ctypes.c_uint64),
                 ("launches", ctypes.c_uint64), ("last_kernel_ms", ctypes.c_double),
@@ -142,6 +156,11 @@ SYMBOLS = {
     "fmx_search_approx_batch": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_approx_opts), _vp, _vp, _sz, _P(_sz)]),
     "fmx_search_approx_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_approx_opts), _vp, _vp, _sz, _P(_sz), _vp]),
     "fmx_approx_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(_u64), _P(_u64)]),
+    "fmx_match_stats_batch": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_mstat_opts), _vp, _vp, _vp]),
+    "fmx_match_stats_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _u64, _P(fmx_mstat_opts), _vp, _vp, _vp, _vp]),
+    "fmx_mems_batch": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_mstat_opts), _vp, _vp, _sz, _P(_sz)]),
+    "fmx_mems_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _u64, _P(fmx_mstat_opts), _vp, _vp, _sz, _P(_sz), _vp]),
+    "fmx_mstat_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(_u64), _P(_u64)]),
     "fmx_corpus_build": (_i32, [_vp, _u64, _vp, _u64, _i32, _P(_vp)]),
     "fmx_corpus_build_dev": (_i32, [_vp, _u64, _vp, _u64, _i32, _vp, _P(_vp)]),
     "fmx_corpus_free": (_i32, [_vp]),

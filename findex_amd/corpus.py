@@ -276,6 +276,30 @@ class HipCorpusSearcher:
         order = np.lexsort((raw, doc))
         return doc[order], raw[order], mism[order]
 
+    def shared_passages(self, q, min_len, max_len=None, max_per=None):
+        """Which stretches of the raw bytes q stand in the corpus, and where: rows (q_off, len, doc, raw_off) of a uint64
+        array sorted by (q_off, doc, raw_off) -- the passage that begins at byte q_off of q begins at byte raw_off of
+        document doc.  q is escaped and its maximal exact matches with the stream of min_len stream bytes and more are
+        taken (HipFMSearcher.mems_text; at most max_per positions per match), the positions mapped by the corpus and q_off
+        mapped back to the raw query by the escape's own prefix counts.  `len` is in stream (escaped) bytes.  The escaped q
+        never holds the separator byte 1, so no passage spans two files.  One known limit: the query is compared in its
+        escaped form, so a match may begin or end inside an escape pair (the backslash or the digit that stand for a raw
+        0, 1 or 255); its q_off and raw_off are then those of the byte the pair stands for."""
+        raw = np.frombuffer(bytes(q), dtype=np.uint8)
+        special = (raw == 0) | (raw == 1) | (raw == 255)
+        first = np.arange(raw.size, dtype=np.int64) + np.cumsum(special) - special      # where raw byte i begins in the escaped q
+        esc = escape(q)
+        to_raw = np.zeros(len(esc), dtype=np.uint64)
+        to_raw[first] = np.arange(raw.size, dtype=np.uint64)
+        to_raw[first[special] + 1] = np.nonzero(special)[0].astype(np.uint64)
+        rows = self.searcher.mems_text(esc, min_len, max_len, max_per)
+        out = np.zeros((rows.shape[0], 4), dtype=np.uint64)
+        if rows.shape[0]:
+            doc, _, raw_off = self.corpus.map(rows[:, 2])
+            out[:, 0], out[:, 1], out[:, 2], out[:, 3] = to_raw[rows[:, 0].astype(np.int64)], rows[:, 1], doc, raw_off
+            out = out[np.lexsort((out[:, 3], out[:, 2], out[:, 0]))]
+        return out
+
     def _intervals(self, queries):
         esc = [escape(q)[::-1] for q in queries]
         if any(not e for e in esc):

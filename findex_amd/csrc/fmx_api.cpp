@@ -1745,6 +1745,171 @@ int fmx_approx_last(double *search_ms, double *sort_ms, uint64_t *steps, uint64_
   return FMX_OK;
 }
 
+// ---------------------------------------------------------------- matching statistics and MEMs (fmx_mstat.hip)
+static thread_local MstatInfo g_mstat_last;
+
+// What refuses a call before the device is touched; max_len and min_len as the kernels take them.
+static int mstat_args(const fmx_index *idx, size_t k, uint64_t n_bytes, const fmx_mstat_opts *opts, uint32_t *max_len,
+                      uint32_t *min_len) {
+  *max_len = FMX_MSTAT_MAX_LEN;
+  *min_len = 1;
+  if (opts) {
+    if (opts->max_len > FMX_MSTAT_MAX_LEN) return arg_fail("fmx_mstat_opts.max_len: 1 .. 4096 (0 = the maximum)");
+    if (opts->reserved[0] != 0 || opts->reserved[1] != 0) return arg_fail("fmx_mstat_opts.reserved must be 0");
+    if (opts->max_len) *max_len = opts->max_len;
+    if (opts->min_len > *max_len) return arg_fail("fmx_mstat_opts: min_len > max_len");
+    if (opts->min_len) *min_len = opts->min_len;
+  }
+  if ((uint64_t)k > (1ull << 26)) return arg_fail("matching statistics: at most 2^26 patterns per call");
+  if (n_bytes >= (1ull << 32)) return arg_fail("matching statistics: n_bytes must be below 2^32");
+  if (!idx) return arg_fail("matching statistics: the handle is null");
+  return mstat_check(H(idx));
+}
+
+// the host forms' offsets: off[0] == 0, non-decreasing; *n_bytes = off[k]
+static int mstat_host_offsets(const uint64_t *off, size_t k, uint64_t *n_bytes) {
+  *n_bytes = 0;
+  if ((uint64_t)k > (1ull << 26)) return FMX_OK;           // (refused by mstat_args, with its own message)
+  if (k && !off) return arg_fail("null argument");
+  if (k && off[0] != 0) return arg_fail("matching statistics: off[0] must be 0");
+  if (k && !offsets_monotonic(off, 0, k)) return arg_fail("pattern offsets must be non-decreasing");
+  *n_bytes = k ? off[k] : 0;
+  return FMX_OK;
+}
+
+static int mems_overflow(const MstatInfo &info, size_t cap) {
+  g_err = "mems: " + std::to_string(info.total) + " hits, room for " + std::to_string(cap);
+  return FMX_ERR_OVERFLOW;
+}
+
+int fmx_match_stats_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k, uint64_t n_bytes,
+                              const fmx_mstat_opts *opts, void *d_len, void *d_sp, void *d_ep, void *stream) {
+  uint32_t max_len, min_len;
+  if (n_bytes && !d_len) return arg_fail("matching statistics: d_len is null");
+  int rc = mstat_args(idx, k, n_bytes, opts, &max_len, &min_len);
+  if (rc) return rc;
+  if (n_bytes && (!d_pat || !d_off)) return arg_fail("null argument");
+  const Index *h = H(idx);
+  if ((rc = use_device(h))) return rc;
+  HIP_TRY(mstat_enqueue(h, d_pat, d_off, k, n_bytes, max_len, d_len, d_sp, d_ep, nullptr, (hipStream_t)stream), "k_mstat");
+  return FMX_OK;
+}
+
+// the host forms' upload: patterns and offsets into the bag
+static int mstat_upload(DevMem &mem, const uint8_t *pat, const uint64_t *off, size_t k, uint64_t n_bytes, uint8_t **d_pat,
+                        uint64_t **d_off, hipStream_t st) {
+  DEV_ALLOC(mem, *d_pat, n_bytes, "patterns");
+  DEV_ALLOC(mem, *d_off, 8 * ((uint64_t)k + 1), "offsets");
+  if (k) HIP_TRY(hipMemcpyAsync(*d_off, off, 8 * ((uint64_t)k + 1), hipMemcpyHostToDevice, st), "H2D(offsets)");
+  else HIP_TRY(hipMemsetAsync(*d_off, 0, 8, st), "memset");
+  if (n_bytes) HIP_TRY(hipMemcpyAsync(*d_pat, pat, n_bytes, hipMemcpyHostToDevice, st), "H2D(patterns)");
+  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+  return FMX_OK;
+}
+
+int fmx_match_stats_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k, const fmx_mstat_opts *opts,
+                          uint32_t *out_len, uint64_t *out_sp, uint64_t *out_ep) {
+  uint32_t max_len, min_len;
+  uint64_t n_bytes;
+  int rc = mstat_host_offsets(off, k, &n_bytes);
+  if (rc) return rc;
+  if (n_bytes && n_bytes < (1ull << 32) && (!out_len || !pat)) return arg_fail("matching statistics: null argument");
+  if ((rc = mstat_args(idx, k, n_bytes, opts, &max_len, &min_len))) return rc;
+  const Index *h = H(idx);
+  if ((rc = use_device(h))) return rc;
+  const uint64_t outs = n_bytes * (4 + (out_sp ? 8 : 0) + (out_ep ? 8 : 0));
+  if ((rc = mstat_room(mstat_bytes(n_bytes, false) + n_bytes + 8 * ((uint64_t)k + 1) + outs + 64, "fmx_match_stats_batch"))) return rc;
+  DevMem mem;
+  StreamGuard own;
+  HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
+  uint8_t *d_pat = nullptr;
+  uint64_t *d_off = nullptr, *d_sp = nullptr, *d_ep = nullptr;
+  uint32_t *d_len = nullptr;
+  if ((rc = mstat_upload(mem, pat, off, k, n_bytes, &d_pat, &d_off, own.s))) return rc;
+  DEV_ALLOC(mem, d_len, 4 * n_bytes, "matching statistics");
+  if (out_sp) DEV_ALLOC(mem, d_sp, 8 * n_bytes, "matching statistics");
+  if (out_ep) DEV_ALLOC(mem, d_ep, 8 * n_bytes, "matching statistics");
+  MstatInfo info;
+  rc = mstat_run(h, d_pat, d_off, k, n_bytes, max_len, min_len, d_len, d_sp, d_ep, false, nullptr, nullptr, 0, own.s, &info);
+  g_mstat_last = info;
+  if (rc) return rc;
+  if (n_bytes) {
+    HIP_TRY(hipMemcpyAsync(out_len, d_len, 4 * n_bytes, hipMemcpyDeviceToHost, own.s), "D2H(len)");
+    if (out_sp) HIP_TRY(hipMemcpyAsync(out_sp, d_sp, 8 * n_bytes, hipMemcpyDeviceToHost, own.s), "D2H(sp)");
+    if (out_ep) HIP_TRY(hipMemcpyAsync(out_ep, d_ep, 8 * n_bytes, hipMemcpyDeviceToHost, own.s), "D2H(ep)");
+    HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
+  }
+  return FMX_OK;
+}
+
+static int mems_args(const void *out_off, const void *out, size_t cap, const size_t *n_out) {
+  if (!n_out) return arg_fail("mems: n_out is null");
+  if ((uint64_t)cap >= (1ull << 32)) return arg_fail("mems: cap must be below 2^32");
+  if (!out_off || (cap && !out)) return arg_fail("null argument");
+  return FMX_OK;
+}
+
+int fmx_mems_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k, uint64_t n_bytes,
+                       const fmx_mstat_opts *opts, void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream) {
+  uint32_t max_len, min_len;
+  int rc = mems_args(d_out_off, d_out, cap, n_out);
+  if (rc) return rc;
+  if ((rc = mstat_args(idx, k, n_bytes, opts, &max_len, &min_len))) return rc;
+  if (!d_off || (n_bytes && !d_pat)) return arg_fail("null argument");
+  const Index *h = H(idx);
+  if ((rc = use_device(h))) return rc;
+  if ((rc = not_capturing((hipStream_t)stream, "a MEM call"))) return rc;
+  MstatInfo info;
+  rc = mstat_run(h, d_pat, d_off, k, n_bytes, max_len, min_len, nullptr, nullptr, nullptr, true, d_out_off, d_out, cap,
+                 (hipStream_t)stream, &info);
+  g_mstat_last = info;
+  if (rc) return rc;
+  *n_out = (size_t)info.total;
+  return info.total > cap ? mems_overflow(info, cap) : FMX_OK;
+}
+
+int fmx_mems_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k, const fmx_mstat_opts *opts,
+                   uint64_t *out_off, fmx_mem_hit *out, size_t cap, size_t *n_out) {
+  uint32_t max_len, min_len;
+  uint64_t n_bytes;
+  int rc = mems_args(out_off, out, cap, n_out);
+  if (rc) return rc;
+  if ((rc = mstat_host_offsets(off, k, &n_bytes))) return rc;
+  if (n_bytes && n_bytes < (1ull << 32) && !pat) return arg_fail("pat is null");
+  if ((rc = mstat_args(idx, k, n_bytes, opts, &max_len, &min_len))) return rc;
+  const Index *h = H(idx);
+  if ((rc = use_device(h))) return rc;
+  if ((rc = mstat_room(mstat_bytes(n_bytes, true) + n_bytes + 16 * ((uint64_t)k + 1) + sizeof(fmx_mem_hit) * (uint64_t)cap + 64,
+                       "fmx_mems_batch"))) return rc;
+  DevMem mem;
+  StreamGuard own;
+  HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
+  uint8_t *d_pat = nullptr;
+  uint64_t *d_off = nullptr, *d_out_off = nullptr;
+  fmx_mem_hit *d_out = nullptr;
+  if ((rc = mstat_upload(mem, pat, off, k, n_bytes, &d_pat, &d_off, own.s))) return rc;
+  DEV_ALLOC(mem, d_out_off, 8 * ((uint64_t)k + 1), "MEM offsets");
+  DEV_ALLOC(mem, d_out, sizeof(fmx_mem_hit) * cap, "MEM hits");
+  MstatInfo info;
+  rc = mstat_run(h, d_pat, d_off, k, n_bytes, max_len, min_len, nullptr, nullptr, nullptr, true, d_out_off, d_out, cap, own.s, &info);
+  g_mstat_last = info;
+  if (rc) return rc;
+  *n_out = (size_t)info.total;
+  if (info.total > cap) return mems_overflow(info, cap);
+  HIP_TRY(hipMemcpyAsync(out_off, d_out_off, 8 * ((uint64_t)k + 1), hipMemcpyDeviceToHost, own.s), "D2H(offsets)");
+  if (info.total) HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(fmx_mem_hit) * info.total, hipMemcpyDeviceToHost, own.s), "D2H(hits)");
+  HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
+  return FMX_OK;
+}
+
+int fmx_mstat_last(double *walk_ms, double *compact_ms, uint64_t *steps, uint64_t *requests) {
+  if (walk_ms) *walk_ms = g_mstat_last.walk_ms;
+  if (compact_ms) *compact_ms = g_mstat_last.compact_ms;
+  if (steps) *steps = g_mstat_last.steps;
+  if (requests) *requests = g_mstat_last.requests;
+  return FMX_OK;
+}
+
 // ---------------------------------------------------------------- statistics
 int fmx_stats(const fmx_index *idx, fmx_stats_t *out) {
   if (!idx || !out) return arg_fail("null argument");

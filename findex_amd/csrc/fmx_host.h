@@ -266,6 +266,26 @@ int approx_check(const Index *h);
 int approx_search(const Index *h, const void *d_pat, const void *d_off, uint64_t k, uint32_t e, uint32_t lo, uint32_t hi,
                   void *d_out_off, void *d_out, uint64_t cap, hipStream_t st, ApproxInfo *info);
 
+// fmx_mstat.hip: matching statistics and maximal exact matches.  mstat_check: FMX_ERR_UNSUPPORTED for handles
+// they do not serve.  mstat_enqueue: the statistics of the n_bytes pattern bytes, device pointers throughout (d_sp / d_ep may
+// be null); it only enqueues on `st`; counters == nullptr: the handle's own.  mstat_run: the same with the call's own
+// counters and timing, and, with `mems`, the compaction into d_out_off[k + 1] / d_out[cap] (the statistics are then
+// temporaries of the call, d_len / d_sp / d_ep ignored); allocates, synchronises `st`, frees its temporaries on every path.
+// info->total is the exact number of hits; records past cap are not written.  mstat_bytes: the device bytes mstat_run
+// allocates; mstat_room: FMX_ERR_NOMEM with the need in the message when `need` exceeds the free device memory.
+struct MstatInfo {
+  uint64_t total = 0, steps = 0, requests = 0;
+  double walk_ms = 0.0, compact_ms = 0.0;       // device events: k_mstat, the flag / scan / write steps
+};
+int mstat_check(const Index *h);
+hipError_t mstat_enqueue(const Index *h, const void *d_pat, const void *d_off, uint64_t k, uint64_t n_bytes, uint32_t max_len,
+                         void *d_len, void *d_sp, void *d_ep, unsigned long long *counters, hipStream_t st);
+uint64_t mstat_bytes(uint64_t n_bytes, bool mems);
+int mstat_room(uint64_t need, const char *what);
+int mstat_run(const Index *h, const void *d_pat, const void *d_off, uint64_t k, uint64_t n_bytes, uint32_t max_len,
+              uint32_t min_len, void *d_len, void *d_sp, void *d_ep, bool mems, void *d_out_off, void *d_out, uint64_t cap,
+              hipStream_t st, MstatInfo *info);
+
 // fmx_search.hip: the residency census of the k_search4 instantiation this handle's full-size searches use now, taken with
 // calibration launches on `st` (synchronises it): fmx_prepare's last step, never a _dev call's.
 hipError_t search_calibrate(const Index *h, hipStream_t st);

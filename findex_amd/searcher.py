@@ -382,6 +382,108 @@ class HipFMSearcher:
         _lib.check(self._L.fmx_approx_last(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
         return float(a.value), float(b.value), int(c.value), int(d.value)
 
+    # ---- matching statistics and maximal exact matches (fmx_match_stats_batch, fmx_mems_batch)
+    MEM_HIT = np.dtype([("pattern", np.uint32), ("len", np.uint32), ("end", np.uint64), ("sp", np.uint64), ("ep", np.uint64)])
+
+    @staticmethod
+    def _mstat_opts(max_len, min_len=0):
+        max_len, min_len = int(max_len or 0), int(min_len or 0)
+        if not (0 <= max_len < 2 ** 32 and 0 <= min_len < 2 ** 32):
+            raise ValueError("max_len or min_len out of range")
+        return _lib.fmx_mstat_opts(max_len, min_len, (0, 0))
+
+    @staticmethod
+    def _mstat_batch(pat, off):
+        pat = np.ascontiguousarray(pat, dtype=np.uint8).reshape(-1)
+        off = np.ascontiguousarray(off, dtype=np.uint64).reshape(-1)
+        k = off.size - 1
+        if k < 0:
+            raise ValueError("off needs k+1 entries")
+        if k and int(off[-1]) != pat.size:
+            raise ValueError("the offsets must cover the pattern buffer: off[k] == len(pat)")
+        return pat, off, k
+
+    def match_stats_batch(self, pat, off, max_len=None, intervals=True):
+        """fmx_match_stats_batch: (len, sp, ep), parallel to `pat` -- for byte j of pattern q the number of backward steps
+        over pat[j], pat[j - 1], .. that keep a non-empty interval (at most min(j - off[q] + 1, max_len); max_len=None:
+        4096) and the interval after them.  intervals=False: sp and ep are None."""
+        pat, off, k = self._mstat_batch(pat, off)
+        opts = self._mstat_opts(max_len)
+        ln = np.zeros(pat.size, dtype=np.uint32)
+        sp = np.zeros(pat.size, dtype=np.uint64) if intervals else None
+        ep = np.zeros(pat.size, dtype=np.uint64) if intervals else None
+        _lib.check(self._L.fmx_match_stats_batch(self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts), _ptr(ln),
+                                                 _ptr(sp) if intervals else None, _ptr(ep) if intervals else None))
+        return ln, sp, ep
+
+    def match_stats_batch_dev(self, d_pat, d_off, k, n_bytes, d_len, d_sp=0, d_ep=0, max_len=None, stream=0):
+        """fmx_match_stats_batch_dev: device pointers (u8 patterns, u64 offsets[k + 1], u32 len[n_bytes], u64 sp / ep or 0);
+        only enqueues on `stream`."""
+        opts = self._mstat_opts(max_len)
+        _lib.check(self._L.fmx_match_stats_batch_dev(self._h, _dp(d_pat), _dp(d_off), int(k), int(n_bytes), ctypes.byref(opts),
+                                                     _dp(d_len), _dp(d_sp), _dp(d_ep), _dp(stream)))
+
+    def mems_batch(self, pat, off, min_len, max_len=None, cap=None):
+        """fmx_mems_batch: (off[k + 1], hits) -- pattern q's maximal exact matches of min_len bytes and more are
+        hits[off[q]:off[q + 1]], a structured array (pattern, len, end, sp, ep) by ascending end; the match is
+        P[end - len : end].  A hit with len == max_len is saturated.  cap=None: a counting call sizes the buffer; with a
+        cap that is too small the library's FMX_ERR_OVERFLOW is raised."""
+        pat, off, k = self._mstat_batch(pat, off)
+        opts = self._mstat_opts(max_len, min_len)
+        n_out = ctypes.c_size_t()
+        out_off = np.zeros(k + 1, dtype=np.uint64)
+        if cap is None:
+            rc = self._L.fmx_mems_batch(self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts), _ptr(out_off), None, 0,
+                                        ctypes.byref(n_out))
+            if rc != 9:                      # FMX_ERR_OVERFLOW: n_out is the exact total
+                _lib.check(rc)
+                return out_off, np.zeros(0, dtype=self.MEM_HIT)
+            cap = int(n_out.value)
+        hits = np.zeros(max(int(cap), 1), dtype=self.MEM_HIT)
+        _lib.check(self._L.fmx_mems_batch(self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts), _ptr(out_off), _ptr(hits),
+                                          int(cap), ctypes.byref(n_out)))
+        return out_off, hits[: int(n_out.value)]
+
+    def mems_batch_dev(self, d_pat, d_off, k, n_bytes, min_len, d_out_off, d_out, cap, max_len=None, stream=0):
+        """fmx_mems_batch_dev: device pointers (u64 out_off[k + 1], 32-byte hit records); allocates and synchronises.  -> the
+        exact number of hits (FMX_ERR_OVERFLOW is raised when it exceeds cap)."""
+        opts = self._mstat_opts(max_len, min_len)
+        n_out = ctypes.c_size_t()
+        _lib.check(self._L.fmx_mems_batch_dev(self._h, _dp(d_pat), _dp(d_off), int(k), int(n_bytes), ctypes.byref(opts),
+                                              _dp(d_out_off), _dp(d_out), int(cap), ctypes.byref(n_out), _dp(stream)))
+        return int(n_out.value)
+
+    def mstat_last(self):
+        """fmx_mstat_last: (walk kernel ms, compaction ms, backward steps, rank-dictionary requests) of this thread's last
+        host or MEM call."""
+        a, b, c, d = ctypes.c_double(), ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64()
+        _lib.check(self._L.fmx_mstat_last(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
+        return float(a.value), float(b.value), int(c.value), int(d.value)
+
+    def match_stats_text(self, q, max_len=None):
+        """ms[i] = the length of the longest prefix of q[i:] that occurs in the indexed text (capped at max_len), for a handle
+        that indexes reverse(text) as from_text and locate_text have it: the statistics of reverse(q), flipped."""
+        q = bytes(q)
+        ln, _, _ = self.match_stats_batch(np.frombuffer(q[::-1], dtype=np.uint8), np.array([0, len(q)], dtype=np.uint64),
+                                          max_len, intervals=False)
+        return ln[::-1].copy()
+
+    def mems_text(self, q, min_len, max_len=None, max_per=None):
+        """The maximal exact matches of q with the indexed text, as rows (q_off, len, text_off) of a uint64 array sorted by
+        (q_off, text_off): q[q_off : q_off + len] stands at text_off; at most max_per text positions per match.  The MEMs of
+        reverse(q), located, each with its own length (text_offsets)."""
+        q = bytes(q)
+        _, hits = self.mems_batch(np.frombuffer(q[::-1], dtype=np.uint8), np.array([0, len(q)], dtype=np.uint64), min_len, max_len)
+        off, sa = self.locate_intervals(hits["sp"], hits["ep"], max_per=max_per)
+        cnt = np.diff(off).astype(np.int64)
+        ln = np.repeat(hits["len"].astype(np.uint64), cnt)
+        q_off = np.repeat(np.uint64(len(q)) - hits["end"], cnt)
+        out = np.zeros((sa.size, 3), dtype=np.uint64)
+        if sa.size:
+            out[:, 0], out[:, 1], out[:, 2] = q_off, ln, np.uint64(self.n - 1) - ln - sa
+            out = out[np.lexsort((out[:, 2], out[:, 0]))]
+        return out
+
     # ---- batched forms (host arrays in, host arrays out)
     def occ_batch(self, c, i):
         c = np.ascontiguousarray(c, dtype=np.uint8)

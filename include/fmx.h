@@ -496,6 +496,58 @@ int fmx_search_approx_batch_dev(const fmx_index *idx, const void *d_pat, const v
                                 void *stream);
 int fmx_approx_last(double *search_ms, double *sort_ms, uint64_t *steps, uint64_t *requests);
 
+/* ---- matching statistics and maximal exact matches (MEMs) of long queries.  Beyond the reference.  DESIGN.md 16.
+ * The batch is k patterns, contiguous in pat: pattern q is pat[off[q] .. off[q + 1]), off[0] == 0, off[k] == n_bytes.  The
+ * statistics are PARALLEL TO pat: entry j belongs to byte j.  For byte j of pattern q let e = j - off[q] + 1 and
+ * L = min(e, max_len): the reference's loop (findex.scala:15-31) runs from (0, n) over pat[j], pat[j - 1], .., stops before
+ * the first step whose result is empty and after L steps at the latest.  len[j] = the steps completed, (sp[j], ep[j]) = the
+ * interval after the last of them, (0, n) when len[j] == 0.  A walk never crosses into pattern q - 1.  On the BWT of a text
+ * len[j] is the length of the longest suffix of pat[off[q] .. j], capped at max_len, that occurs, and (sp, ep) what
+ * fmx_search_batch returns for that suffix; byte 0 in a pattern is treated as the exact search treats it.
+ * MEMs: with min_len >= 1, byte j ends a reported match iff len[j] >= min_len and (j is the last byte of its pattern or
+ * len[j + 1] <= len[j]); the hit is (pattern q, len, end = e, sp, ep), the match P[end - len .. end), left-maximal by
+ * construction.  A hit with len == max_len is SATURATED: it may be a piece of a longer match, and a run of saturated
+ * positions is reported position by position (raise max_len).  Output is CSR: out_off[k + 1], a pattern's hits by ascending
+ * end -- the same input gives the same bytes on every run.
+ * fmx_match_stats_batch_dev ONLY ENQUEUES (no allocation, copy or synchronisation: safe inside a stream capture) and cannot
+ * validate its operands: a position that no pattern covers gets len 0, (0, n), and no operand value leads outside pat or the
+ * index.  The host form and both MEM forms ALLOCATE AND SYNCHRONISE (the _dev MEM form: FMX_ERR_HIP under a stream capture,
+ * decided before anything is allocated); their need -- for the MEM calls 20 bytes per pattern byte of statistics plus 4 for
+ * the scan -- is checked against the free HBM first (FMX_ERR_NOMEM with the need in the message), and every temporary is
+ * freed on every path.  fmx_mems_batch: FMX_ERR_OVERFLOW with the exact *n_out when the hits exceed cap (records past cap
+ * are not written); cap == 0 with out == NULL is the counting call.
+ * FMX_ERR_ARG, decided before the device is touched: a null handle or output; max_len > FMX_MSTAT_MAX_LEN; min_len >
+ * max_len; reserved != 0; off[0] != 0 or decreasing offsets (host forms); k > 2^26; n_bytes >= 2^32; cap >= 2^32.
+ * FMX_ERR_UNSUPPORTED: fmx_open_block handles.
+ * All forms use the rank dictionary only, build no derived table and do not count as patterns seen; every executed step,
+ * the one that empties an interval included, is added to the handle's counters (rank_queries, backward_steps,
+ * search_requests).  fmx_mstat_last: the calling thread's last host or MEM call (the enqueue-only form does not update it):
+ * device time (ms) of the walk kernel and of the compaction, steps executed, rank-dictionary requests; any pointer may be NULL.
+ * FMX_MSTAT_TILE: the positions a workgroup of the walk kernel takes at a time (what tests aim at). */
+#define FMX_MSTAT_MAX_LEN 4096
+#define FMX_MSTAT_TILE 512
+typedef struct fmx_mstat_opts {
+  uint32_t max_len;     /* 1 .. FMX_MSTAT_MAX_LEN; 0 = the maximum */
+  uint32_t min_len;     /* MEMs only; 0 = 1 */
+  uint32_t reserved[2]; /* must be 0 */
+} fmx_mstat_opts;
+typedef struct fmx_mem_hit {
+  uint32_t pattern;
+  uint32_t len;
+  uint64_t end;
+  uint64_t sp;
+  uint64_t ep;
+} fmx_mem_hit; /* 32 bytes */
+int fmx_match_stats_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k, const fmx_mstat_opts *opts,
+                          uint32_t *out_len, uint64_t *out_sp_or_null, uint64_t *out_ep_or_null);
+int fmx_match_stats_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k, uint64_t n_bytes,
+                              const fmx_mstat_opts *opts, void *d_len, void *d_sp_or_null, void *d_ep_or_null, void *stream);
+int fmx_mems_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k, const fmx_mstat_opts *opts,
+                   uint64_t *out_off /* k + 1 */, fmx_mem_hit *out, size_t cap, size_t *n_out);
+int fmx_mems_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k, uint64_t n_bytes,
+                       const fmx_mstat_opts *opts, void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream);
+int fmx_mstat_last(double *walk_ms, double *compact_ms, uint64_t *steps, uint64_t *requests);
+
 /* ---- corpus: a directory of files as ONE index -- DirBWTReader (bwtreader.scala:17-173), the input side of the reference's
  * IndexerApp -- and, beyond the reference, the way back from a stream position to (document, offset).
  * The STREAM: the documents in the caller's order; in each, raw byte 0 becomes '\' '0', raw 1 becomes '\' '1' and raw 255
