@@ -125,6 +125,7 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
                                                         const uint32_t spin) {
   static_assert(!G2 || LAYOUT == kLayoutOneHot, "pairs of lanes serve the one-hot layout only");
   static_assert(!KX || (KT != 0 && JT == 2u && RW == 0u && LAYOUT == kLayoutOneHot), "level KT + 1 serves the kernels with pairs of row jump entries");
+  static_assert(!KX || KT % 4u == 0u, "walk_last reads the last KT bytes of a level KT + 1 park as whole dwords");
   constexpr int G = G2 ? 2 : Lay<LAYOUT>::G;     // lanes per pattern
   constexpr uint32_t P = 64 / G;                 // patterns per wave
   constexpr uint32_t RG = G2 ? 4u : (uint32_t)G; // rows of an interval a group can look up in the row tables at once (a pair's lanes take two rows each)
@@ -277,7 +278,7 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
   __shared__ uint32_t s_rows_it[RW ? kSThreads / 64 : 1][RW ? kRowsCap : 1];
   __shared__ uint32_t s_rows_len[RW ? kSThreads / 64 : 1][RW ? kRowsCap : 1];
   uint32_t nrows = 0;               // entries in it (wave-uniform)
-  uint32_t rsteps = 0, rlooks = 0;  // steps taken and row-table words fetched by this LANE in rows phases
+  uint32_t rsteps = 0, rlooks = 0;  // steps taken and row-table words fetched by this LANE in rows phases; rsteps also the steps a lane settles in walk_last (three-step words, level KT + 1 parks): counted for every lane, where `steps` counts for a group's lane 0
   // A pattern's final interval (the lane that holds it calls).  pk_cap != ~0: straight into the 8-byte form (fmx.h) -- word
   // q of sp_out, wide intervals appended to the escape list behind word k -- instead of a pass of k_pack_intervals over
   // both arrays behind the search (every variant of this kernel finishes all of its patterns itself since round 5).
@@ -352,9 +353,36 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
   Tail tail_ahead;
 #pragma unroll
   for (uint32_t i = 0; i < NT; i++) tail_ahead.c[i] = (!kStage && len0 > 4u * i) ? fetch4(pat, end0 - 4ull * i) : 0u;
-  // The parked patterns, P at a time, a lane group each: one-row steps (one rank query + one bit test, as in the step
-  // loop) from the row and step they were parked with until the interval is empty -- or, should one not fail after all,
-  // to its end -- leaving the reference loop's final values in the output arrays and counting its steps.
+  // One one-row step of a walk below, by the lane group: [wsp, wsp + 1) on character c (one rank query + one bit test, as in the
+  // step loop).
+  auto walk_step = [&](uint32_t c, uint64_t &wsp, uint64_t &wep) {
+    const uint4 en = s_tab[c];
+    const uint64_t cfc = ((uint64_t)en.y << 32) | en.x;
+    const uint64_t vb = ((uint64_t)en.w << 32) | en.z;
+    if (vb > 1) {
+      if (LAYOUT == kLayoutBytes) {
+        const ByteRankReq q1 = byte_rank_issue(ix, (uint16_t)(vb - 2), wsp, lc);
+        wsp = cfc + byte_rank_finish(q1, c, lc);
+        wep = wsp + byte_match_bit(q1, c, lc);
+      } else {
+        uint32_t b1, m1;
+        split448(wsp, b1, m1);
+        const Blk w1 = blk_load(vb, b1, m1);
+        wsp = cfc + blk_rank(w1, m1);
+        wep = wsp + blk_bit(w1, m1);
+      }
+      reqs += R * RB;
+    } else {
+      const uint64_t r1 = cfc + ((vb == 1 && wsp > ix.eof) ? 1u : 0u);
+      wep = cfc + ((vb == 1 && wep > ix.eof) ? 1u : 0u);
+      wsp = r1;
+    }
+    steps++;
+  };
+  // The parked patterns, P at a time, a lane group each: one-row steps from the row and step they were parked with until
+  // the interval is empty -- or, should one not fail after all, to its end -- leaving the reference loop's final values in the
+  // output arrays and counting its steps.  This is the walk that makes room INSIDE the batch loop; what is parked when the
+  // wave ends is walk_last's (below), but for the forms named there, which end with this one (kLast).
   auto walk_parked = [&](auto last_tag) {
     constexpr bool kLast = decltype(last_tag)::value;          // the walk before the wave ends (not the one that makes room inside the batch loop)
     while (npark) {                                            // wave-uniform
@@ -373,12 +401,8 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
       if constexpr (R3T && kLast) {
         // ... three of them at a time by the three-step row table: one 8-byte load where the step loop below spends three
         // rank queries (a pattern that misses in the middle of a nine-character entry: 3 dependent requests, not 5).  Only
-        // in the last walk -- where nearly all of them happen: a wave parks ~1.6 patterns per batch of a workload with
-        // 10 % misses and the list holds 64 -- because a second copy of this loop inside the batch loop costs the step
-        // loop a register it does not have (the dictionary's lane address was spilled and re-read at every rank step).
-        // Round 5 also tried the last walk with TWO patterns per lane group, every request of both in flight before either is
-        // waited for (17 parked patterns per wave = one round instead of two): no change at C3 (0.1389-0.1395 against
-        // 0.1373-0.1391 ms on one box) -- the waves' last walks overlap other waves' batches until the very end.
+        // in a last walk: a second copy of this loop inside the batch loop costs the step loop a register it does not have
+        // (the dictionary's lane address was spilled and re-read at every rank step).
         while (__builtin_amdgcn_ballot_w64(actw && wj >= 3u)) {
           const bool go = actw && wj >= 3u;
           if (go) {
@@ -434,31 +458,7 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
         for (uint32_t s8 = 0; s8 < 8; s8++) {
           const bool stepping = actw && wsp < wep && s8 < nst;
           if (!__builtin_amdgcn_ballot_w64(stepping)) break;
-          if (stepping) {
-            const uint32_t c = (uint32_t)(chars >> (8u * s8)) & 0xFFu;
-            const uint4 en = s_tab[c];
-            const uint64_t cfc = ((uint64_t)en.y << 32) | en.x;
-            const uint64_t vb = ((uint64_t)en.w << 32) | en.z;
-            if (vb > 1) {
-              if (LAYOUT == kLayoutBytes) {
-                const ByteRankReq q1 = byte_rank_issue(ix, (uint16_t)(vb - 2), wsp, lc);
-                wsp = cfc + byte_rank_finish(q1, c, lc);
-                wep = wsp + byte_match_bit(q1, c, lc);
-              } else {
-                uint32_t b1, m1;
-                split448(wsp, b1, m1);
-                const Blk w1 = blk_load(vb, b1, m1);
-                wsp = cfc + blk_rank(w1, m1);
-                wep = wsp + blk_bit(w1, m1);
-              }
-              reqs += R * RB;
-            } else {
-              const uint64_t r1 = cfc + ((vb == 1 && wsp > ix.eof) ? 1u : 0u);
-              wep = cfc + ((vb == 1 && wep > ix.eof) ? 1u : 0u);
-              wsp = r1;
-            }
-            steps++;
-          }
+          if (stepping) walk_step((uint32_t)(chars >> (8u * s8)) & 0xFFu, wsp, wep);
         }
         wit += nst;                                            // (meaningless once the interval is empty: the loop ends then)
       }
@@ -534,6 +534,162 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
             if (fail) { s_park_row[wave_in_wg][ps] = row; s_park_pid[wave_in_wg][ps] = rpid; s_park_it[wave_in_wg][ps] = rit; }
             npark += (uint32_t)__builtin_popcountll(fm);
           }
+        }
+      }
+    }
+  };
+  // The LAST walk: what is parked when the wave ends (nearly all of it: a wave parks ~1.6 patterns per batch of a workload with
+  // 10 % misses and flushes its list inside the loop only when 48 or 64 have come together).  It is the end of the critical
+  // path of the waves a launch ends with, on a device that is emptying, so what counts is its DEPENDENT round trips.  Of what an
+  // entry needs, only the chain "three-step words, then rank steps" depends on its predecessor; the pattern's offsets, the
+  // characters the rank steps read and the level-KT decision of a level KT + 1 park depend on the parked entry alone.  So
+  // everything that is not a rank step is done first, 64 entries at a time, by one LANE per entry (64 chains per wave where the
+  // lane groups keep P), every load in flight beside the others:
+  //   trip 1   the first three-step word                | the offsets
+  //   trip 2   the second three-step word               | the characters of the rank steps; KX: the pattern's last KT bytes
+  //   trip 3   (a third word: jump_chars 10 and 11)     | KX: level KT's entry of those bytes
+  // and the lane writes out what needs no rank step: a pattern parked as None, a level KT + 1 park (settled by that entry), a
+  // pattern that ends with its known-good steps.  The others are handed to the lane groups, P at a time -- row and step
+  // through the entry's own slot of the list, up to eight characters through the LDS crossbar (a shuffle: no LDS area of its
+  // own, so the walk does not depend on a form having one free) -- and take their rank steps: at most three when a table
+  // lookup located the miss (what is left of the known-good steps and the failing one).  An entry that has not failed within
+  // its staged characters is put back on the list with nothing known about it and comes round again, eight characters per
+  // pass: in the forms without the three-step table the known-good steps are rank steps, up to jump_chars of them before the
+  // failing one; for every other entry it is the guard the groups' loop was ("should one not fail after all").
+  // (before: per round of P entries and one after the other, each waited for -- up to three three-step words, the offsets,
+  // the KT bytes, level KT's entry, the characters, the rank steps: up to nine dependent trips where DESIGN counted five.)
+  // (Not in the eight single-entry forms of the wide dictionaries by quads or octets -- WIDE, JT = 1, R3T, not G2:
+  // <1,0,KT,1,0,1,0,0> and <1,1,KT,1,0,1,0,0>, KT = 0, 4, 8, 12 -- whose step loop sits at the 80 registers of six waves per
+  // SIMD: with this walk behind it the compiler spills one more loop-invariant register pair there (scratch 8 -> 12 and
+  // 0 -> 12 B per lane).  They end with walk_parked, as before.  Their twins by pairs of lanes, <1,0,KT,1,0,1,1,0>, have 96
+  // registers and take this walk.)
+  // Round 5 had tried the groups' last walk with TWO patterns per lane group, every request of both in flight before either is
+  // waited for (17 parked patterns per wave = one round instead of two): no change at C3 (0.1389-0.1395 against
+  // 0.1373-0.1391 ms on one box) -- the waves' last walks overlap other waves' batches until the very end.  (It halved the
+  // rounds of a wave with more than P parked patterns, not the dependent trips of a round.)
+  constexpr bool kLaneWalk = !(WIDE && JT == 1u && R3T && !G2);
+  auto walk_last = [&]() {
+    while (npark) {                                            // wave-uniform
+      const uint32_t take = npark < 64u ? npark : 64u;
+      const bool on = lane64 < take;
+      const uint32_t slot = npark - take + (on ? lane64 : 0u);
+      npark -= take;
+      const uint32_t wpid = on ? s_park_pid[wave_in_wg][slot] : 0u;
+      const uint32_t wit0 = on ? s_park_it[wave_in_wg][slot] : 0u;
+      uint64_t wsp = on ? s_park_row[wave_in_wg][slot] : 0ull;
+      uint32_t wj = (uint32_t)(wsp >> 56);                       // steps that are known to succeed (the lookup that parked it saw them)
+      const bool wnone = wj == 0xFFu;                            // FMX_SEARCH_MISS_NONE: parked as None -- nothing to walk, (0, 0) to write
+      const bool wkx = KX && on && wj == 0xFEu;                  // level KT + 1 found the pattern's last KT + 1 characters absent
+      wj = (wnone || wkx) ? 0u : wj;
+      wsp &= (1ull << 56) - 1;
+      // ---- trip 1: the first of the entry's wj / 3 three-step words (one 8-byte load where the lane groups would spend three
+      // rank queries) and the offsets.  Every lane loads, an idle one entry 0: a load under a condition is merged with a
+      // default value behind it, and the compiler puts the wait for the load there -- before the loads that follow.
+      const uint32_t n3 = R3T ? wj / 3u : 0u;
+      unsigned long long word = 0;
+      if constexpr (R3T) word = r3tab[n3 >= 1u ? wsp : 0ull];
+      const uint64_t *own = po.at(wpid);
+      const uint64_t o0 = own[0], o1 = own[1];
+      const uint32_t wit = wit0 + 3u * n3;                       // the step the rank steps begin with
+      rsteps += 3u * n3;                                         // (counted by the LANE, like a rows phase's)
+      if constexpr (R3T) {
+        r3l += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(n3 >= 1u)) + (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(n3 >= 2u));
+        // ---- trip 2: the second word
+        if (n3 >= 1u) wsp = word & ((1ull << 40) - 1);
+        word = r3tab[n3 >= 2u ? wsp : 0ull];
+      }
+      const uint64_t wbegin = po.fixed ? (uint64_t)wpid * po.fixed : o0, wend = po.fixed ? ((uint64_t)wpid + 1) * po.fixed : o1;
+      const uint32_t wlen = (uint32_t)(wend - wbegin);
+      const uint32_t wrem = (on && !wnone && !wkx) ? wlen - wit : 0u;
+      const uint32_t nst = wrem < 8u ? wrem : 8u;
+      // ... and the next nst characters, the one of step `wit` in the low byte: the eight bytes that begin nst bytes in front
+      // of where step `wit` reads.  They lie inside the pattern when it has eight or more (nst < 8: then the pattern begins
+      // there, and the 8 - nst bytes behind are characters of steps taken); a shorter pattern is read byte by byte.
+      uint64_t chars = 0;
+      {
+        const uint8_t *src = (nst != 0u && wlen >= 8u) ? pat + (wend - wit - nst) : reinterpret_cast<const uint8_t *>(own);
+        uint32_t lo, hi;
+        __builtin_memcpy(&lo, src, 4);
+        __builtin_memcpy(&hi, src + 4, 4);
+        const uint64_t v = ((uint64_t)__builtin_bswap32(lo) << 32) | __builtin_bswap32(hi);
+        if (nst != 0u && wlen >= 8u) chars = v >> (8u * (8u - nst));
+      }
+      uint64_t wep = wsp;
+      if constexpr (KX) {
+        // Y = the last KT + 1 characters do not occur; wsp = Y's insertion point.  The reference's loop went empty at step KT
+        // (its values: (ins Y, ins Y), KT + 1 steps) if X = the last KT characters occur, else earlier -- where level KT's
+        // entry of X says, with its steps.  One lookup of X decides (here, not in every pattern's batch).  (Such a pattern
+        // has more than KT characters: the dwords below lie inside it.)
+        uint32_t code = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < KT / 4u; i++) {
+          uint32_t d;
+          __builtin_memcpy(&d, wkx ? pat + (wend - 4u * (i + 1u)) : reinterpret_cast<const uint8_t *>(own), 4);
+          d = __builtin_bswap32(d);                              // pat[wend - 4 i - 1 - j] in byte lane j
+#pragma unroll
+          for (uint32_t j = 0; j < 4u; j++) code = code * ksigma + s_dense[(d >> (8u * j)) & 0xFFu];
+        }
+        // ---- trip 3
+        const uint4 xe = ktab[wkx ? code : 0u];
+        ktl += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(wkx));
+        if (wkx) {
+          const uint64_t xsp = (((uint64_t)xe.y << 32) | xe.x) & ((1ull << 56) - 1), xep = ((uint64_t)xe.w << 32) | xe.z;
+          if (xsp < xep) {
+            rsteps += KT + 1u;
+          } else {
+            wsp = xsp;
+            wep = xep;
+            rsteps += xe.y >> 24;
+          }
+        }
+      }
+      if constexpr (R3T) {
+        if (n3 >= 2u) wsp = word & ((1ull << 40) - 1);
+        for (uint32_t lv = 3u; __builtin_amdgcn_ballot_w64(n3 >= lv); lv++) {      // (a row jump entry of ten or eleven characters)
+          if (n3 >= lv) wsp = r3tab[wsp] & ((1ull << 40) - 1);
+          r3l += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(n3 >= lv));
+        }
+      }
+      if (on && nst != 0u && wlen < 8u) {
+        for (uint32_t s8 = 0; s8 < nst; s8++) chars |= (uint64_t)pat[wend - wit - 1 - s8] << (8u * s8);
+      }
+      const bool walks = nst != 0u;                              // (on, not None, not a level KT + 1 park, characters left)
+      if (on && !walks) emit(wpid, wsp, (wnone || wkx) ? wep : wsp + 1u);
+      // ---- the rank steps, P entries at a time: group g takes the entry of lane (base + g).  Its row and step go through the
+      // entry's own slot of the list -- the row's top byte now says how many characters are staged (bit 4: the pattern ends
+      // with them) -- and its characters through the crossbar, so that a lane keeps two registers across the rounds.
+      if (walks) {
+        s_park_row[wave_in_wg][slot] = wsp | ((uint64_t)(nst | (nst == wrem ? 16u : 0u)) << 56);
+        s_park_it[wave_in_wg][slot] = wit;
+      }
+      const unsigned long long wm = __builtin_amdgcn_ballot_w64(walks);
+      const uint32_t slot0 = npark;                              // the first slot of this pass's entries
+      for (uint32_t base = 0; base < take; base += P) {
+        if (((wm >> base) & ((1ull << P) - 1ull)) == 0ull) continue;      // nothing to walk here
+        const bool actw = ((wm >> (base + grp)) & 1ull) != 0ull;
+        const uint32_t gslot = slot0 + base + (actw ? grp : 0u);
+        const uint64_t grow = s_park_row[wave_in_wg][gslot];
+        const uint32_t gpid = s_park_pid[wave_in_wg][gslot], git = s_park_it[wave_in_wg][gslot];
+        const uint32_t gnst = actw ? (uint32_t)(grow >> 56) & 15u : 0u;
+        const bool gfinal = ((uint32_t)(grow >> 60) & 1u) != 0u;
+        const int from = (int)(base + grp);
+        const uint64_t gchars = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(chars >> 32), from, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)chars, from, 64);
+        uint64_t gsp = grow & ((1ull << 56) - 1);
+        uint64_t gep = gsp + 1u;
+        for (uint32_t s8 = 0; s8 < 8; s8++) {
+          const bool stepping = actw && gsp < gep && s8 < gnst;
+          if (!__builtin_amdgcn_ballot_w64(stepping)) break;
+          if (stepping) walk_step((uint32_t)(gchars >> (8u * s8)) & 0xFFu, gsp, gep);
+        }
+        const bool again = actw && gsp < gep && !gfinal;         // it walks on: back on the list, nothing known
+        if (actw && !again && t == 0) emit(gpid, gsp, gep);
+        const unsigned long long am = __builtin_amdgcn_ballot_w64(again && t == 0);
+        if (am) {
+          // (into the slots of this pass's entries, from the first one on: after round r at most (r + 1) P have come back, and
+          // the slots below slot0 + (r + 1) P have been read)
+          const uint32_t ps = npark + (uint32_t)__builtin_popcountll(am & ((1ull << lane64) - 1ull));
+          if (again && t == 0) { s_park_row[wave_in_wg][ps] = gsp; s_park_pid[wave_in_wg][ps] = gpid; s_park_it[wave_in_wg][ps] = git + gnst; }
+          npark += (uint32_t)__builtin_popcountll(am);
         }
       }
     }
@@ -1185,7 +1341,10 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
 #ifdef FMX_SEARCHLOG
   const unsigned long long sl_tw = __builtin_amdgcn_s_memrealtime();      // the last walk begins
 #endif
-  if (kFold) walk_parked(std::true_type{});
+  if constexpr (kFold) {
+    if constexpr (kLaneWalk) walk_last();
+    else walk_parked(std::true_type{});
+  }
 #ifdef FMX_SEARCHLOG
   const unsigned long long sl_t2 = __builtin_amdgcn_s_memrealtime();
 #endif
