@@ -14,6 +14,7 @@ package is the thin host-side mirror of the reference's Scala interface for that
     DirBWTReader(dir) -> one stream, IndexerApp    Corpus.from_dir(dir), HipCorpusSearcher, python -m findex_amd.index --dir
     (beyond the reference)                         HipFMSearcher.match_stats_batch / .mems_batch / .match_stats_text / .mems_text,
                                                    HipCorpusSearcher.shared_passages
+                                                   Corpus.to_stream (the inverse of Corpus.map), corpus.unescape_ranges
 
 There is no CPU fallback: importing works anywhere, but every compute call needs the built
 library and a HIP device and fails loudly otherwise.

@@ -107,6 +107,61 @@ def read_docs(path):
     return doc_start, raw_len, esc_pos, names
 
 
+def stream_positions(doc_start, esc_pos, doc, raw_off):
+    """The inverse of the map, in numpy over the map's tables: where raw byte raw_off of document doc stands in the stream
+    -- the backslash where the byte is escaped; raw_off == raw_len[doc] is the document's separator.
+    stream = doc_start[d] + raw_off + #{escapes of d whose raw offset < raw_off}; the i-th escape of d, at stream position e,
+    has raw offset e - doc_start[d] - i, so with key[j] = esc_pos[j] - j (strictly increasing over all escapes) and lo = the
+    index of d's first escape, the count is #{j >= lo : key[j] < doc_start[d] + raw_off - lo}.
+    Not validated: a doc outside 0 .. n_docs - 1 raises numpy's IndexError, and a raw_off beyond raw_len[doc] silently gives
+    a position in a later document."""
+    ds = np.asarray(doc_start, dtype=np.uint64).astype(np.int64)
+    ep = np.asarray(esc_pos, dtype=np.uint64).astype(np.int64)
+    d = np.asarray(doc, dtype=np.int64).reshape(-1)
+    ro = np.asarray(raw_off, dtype=np.uint64).astype(np.int64).reshape(-1)
+    lo = np.searchsorted(ep, ds[d], side="left")
+    hi = np.searchsorted(ep, ds[d + 1], side="left")
+    key = ep - np.arange(ep.size, dtype=np.int64)
+    upto = np.minimum(np.searchsorted(key, ds[d] + ro - lo, side="left"), hi)
+    return (ds[d] + ro + (upto - lo)).astype(np.uint64)
+
+
+_ESC_CODE = np.zeros(256, dtype=np.uint8)           # the second byte of an escape pair -> the raw byte it stands for
+_ESC_CODE[ord("1")] = 1
+_ESC_CODE[ord("f")] = 255
+_ESC_SECOND = np.zeros(256, dtype=bool)             # ... and which second bytes there are: '0', '1', 'f'
+_ESC_SECOND[[ord("0"), ord("1"), ord("f")]] = True
+
+
+def unescape_ranges(data, off, starts, esc_pos):
+    """The raw bytes of stream ranges (pieces of Corpus.stream() or of X.data), unescaped BY THE MAP: range q is
+    data[off[q]:off[q + 1]], the stream from position starts[q] on; every escape of esc_pos inside it loses its backslash
+    and its second byte becomes the raw byte.  No pattern matching: the reference does not escape the backslash, so a
+    file's own backslash-zero reads like an escape and is none.  The ranges begin and end between pairs (stream_positions
+    gives such positions).  ValueError when the data and esc_pos disagree: no backslash at an escape, or a second byte
+    that is not '0', '1' or 'f'.  -> a list of bytes."""
+    buf = np.array(np.frombuffer(data, dtype=np.uint8))          # the one copy: the second bytes are rewritten in it
+    off = np.asarray(off, dtype=np.uint64).astype(np.int64)
+    st = np.asarray(starts, dtype=np.uint64).astype(np.int64).reshape(-1)
+    ep = np.asarray(esc_pos, dtype=np.uint64).astype(np.int64)
+    lens = np.diff(off)
+    lo = np.searchsorted(ep, st, side="left")
+    cnt = np.searchsorted(ep, st + lens, side="left") - lo
+    which = np.repeat(np.arange(st.size, dtype=np.int64), cnt)
+    j = np.arange(int(cnt.sum()), dtype=np.int64) - np.repeat(np.cumsum(cnt) - cnt, cnt) + np.repeat(lo, cnt)
+    at = ep[j] - st[which] + off[which]                      # the backslashes in `data`
+    if at.size and np.any(at + 1 >= off[which + 1]):
+        raise ValueError("a range ends inside an escape pair")
+    if at.size and (np.any(buf[at] != 0x5C) or not np.all(_ESC_SECOND[buf[at + 1]])):
+        raise ValueError("the data and esc_pos disagree: no escape pair where the map has one")
+    keep = np.ones(buf.size, dtype=bool)
+    keep[at] = False
+    buf[at + 1] = _ESC_CODE[buf[at + 1]]
+    before = np.concatenate([[0], np.cumsum(keep)]).astype(np.int64)
+    raw = buf[keep]
+    return [raw[before[off[q]]:before[off[q + 1]]].tobytes() for q in range(st.size)]
+
+
 class Corpus:
     """fmx_corpus: the stream of a list of documents in HBM (until drop_stream) and the map from stream positions to
     (document, offset).  `names[d]` is document d's path relative to the root, as bytes."""
@@ -224,6 +279,12 @@ class Corpus:
     def map_dev(self, d_pos, k, d_doc, d_esc_off, d_raw_off, stream=0):
         """fmx_corpus_map_dev: device pointers; only enqueues."""
         _lib.check(self._L.fmx_corpus_map_dev(self._c, _dp(d_pos), int(k), _dp(d_doc), _dp(d_esc_off), _dp(d_raw_off), _dp(stream)))
+
+    def to_stream(self, doc, raw_off):
+        """The inverse of map: the stream position (uint64) of raw byte raw_off of document doc (arrays or scalars);
+        raw_off == raw_len[doc] is the separator.  stream_positions over tables()."""
+        ds, _, ep = self.tables()
+        return stream_positions(ds, ep, doc, raw_off)
 
     def save(self, path):
         """X.docs (write_docs) from the device's tables."""
