@@ -15,6 +15,8 @@ package is the thin host-side mirror of the reference's Scala interface for that
     (beyond the reference)                         HipFMSearcher.match_stats_batch / .mems_batch / .match_stats_text / .mems_text,
                                                    HipCorpusSearcher.shared_passages
                                                    Corpus.to_stream (the inverse of Corpus.map), corpus.unescape_ranges
+                                                   HipFMSearcher.extract_text / .extract_text_batch (text by position),
+                                                   HipCorpusSearcher.read / .document / .snippets
 
 There is no CPU fallback: importing works anywhere, but every compute call needs the built
 library and a HIP device and fails loudly otherwise.

@@ -59,6 +59,9 @@ FMX_MSTAT_TILE = 512                  # positions per workgroup tile of the walk
 MSTAT_GROUPS = {"onehot": 16, "bytes": 8}      # lane groups per wave: quads, octets (fmx_device.h, Lay<LAYOUT>::G)
 
 
+FMX_EXTRACT_TILE = 1024               # output bytes per workgroup tile of the extract kernel (fmx.h)
+
+
 class fmx_mstat_opts(ctypes.Structure):
     _fields_ = [("max_len", ctypes.c_uint32), ("min_len", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
 
@@ -161,6 +164,10 @@ SYMBOLS = {
     "fmx_mems_batch": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_mstat_opts), _vp, _vp, _sz, _P(_sz)]),
     "fmx_mems_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _u64, _P(fmx_mstat_opts), _vp, _vp, _sz, _P(_sz), _vp]),
     "fmx_mstat_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(_u64), _P(_u64)]),
+    "fmx_extract_text_batch": (_i32, [_vp, _vp, _vp, _sz, _vp]),
+    "fmx_extract_text_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _u64, _vp, _vp]),
+    "fmx_extract_info": (_i32, [_vp, _P(_u32), _P(_u64), _P(ctypes.c_double)]),
+    "fmx_extract_last": (_i32, [_P(ctypes.c_double), _P(_u64), _P(_u64)]),
     "fmx_corpus_build": (_i32, [_vp, _u64, _vp, _u64, _i32, _P(_vp)]),
     "fmx_corpus_build_dev": (_i32, [_vp, _u64, _vp, _u64, _i32, _vp, _P(_vp)]),
     "fmx_corpus_free": (_i32, [_vp]),

@@ -361,6 +361,38 @@ class HipCorpusSearcher:
             out = out[np.lexsort((out[:, 3], out[:, 2], out[:, 0]))]
         return out
 
+    # ---- the text itself, from the index alone (HipFMSearcher.extract_text_batch): no stream in HBM, no X.data on disk
+    def read(self, doc, raw_off, length):
+        """The raw bytes [raw_off, raw_off + length) of document doc, clipped at the document's end (arrays or scalars) -> a
+        list of bytes.  The map backwards gives the stream range (stream_positions), the index its bytes, the map the raw
+        bytes again (unescape_ranges)."""
+        ds, rl, ep = self.corpus.tables()
+        d = np.asarray(doc, dtype=np.int64).reshape(-1)
+        a = np.asarray(raw_off, dtype=np.uint64).reshape(-1)
+        ln = np.asarray(length, dtype=np.uint64).reshape(-1)
+        d, a, ln = np.broadcast_arrays(d, a, ln)
+        if d.size and (d.min() < 0 or d.max() >= self.corpus.n_docs):
+            raise IndexError("document out of range")
+        a = np.minimum(a, rl[d])
+        b = a + np.minimum(ln, rl[d] - a)
+        s0 = stream_positions(ds, ep, d, a)
+        s1 = stream_positions(ds, ep, d, b)
+        off, data = self.searcher.extract_text_batch(s0, s1 - s0)
+        return unescape_ranges(data, off, s0, ep)
+
+    def document(self, d):
+        """The whole file d, as it was on disk."""
+        _, rl, _ = self.corpus.tables()
+        return self.read(int(d), 0, int(rl[int(d)]))[0]
+
+    def snippets(self, q, before=40, after=40, max_hits=None, max_mismatches=0):
+        """(doc, raw_off, [bytes]): each hit of locate_docs(q, max_hits, max_mismatches) with `before` raw bytes in front of
+        it and `after` behind its len(q) bytes, clipped at the file's ends."""
+        q = bytes(q)
+        doc, raw = self.locate_docs(q, max_hits=max_hits, max_mismatches=max_mismatches)[:2]
+        a = raw - np.minimum(raw, np.uint64(before))
+        return doc, raw, self.read(doc, a, raw - a + np.uint64(len(q) + int(after)))
+
     def _intervals(self, queries):
         esc = [escape(q)[::-1] for q in queries]
         if any(not e for e in esc):

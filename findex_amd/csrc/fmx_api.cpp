@@ -308,6 +308,7 @@ static void destroy(Index *h) {
   if (h->d_loc_marks) (void)hipFree(h->d_loc_marks);
   if (h->d_loc_samples) (void)hipFree(h->d_loc_samples);
   if (h->d_lcp) (void)hipFree(h->d_lcp);
+  if (h->d_ext_isa) (void)hipFree(h->d_ext_isa);
   for (CallCtx *c : h->ctx_pool) free_ctx(c);
   delete h;
 }
@@ -513,7 +514,7 @@ int fmx_index_config_set(fmx_index *idx, const char *key, const char *value) {
   const int pr = policy_set(H(idx)->policy, key, value, &why);
   if (pr == 0) return FMX_OK;
   if (pr == 2) return arg_fail(why);
-  return arg_fail("not a per-handle key (ktab, jump, jump_pairs, search_lanes, jump_chars, tables_after, table_budget, locate_sample)");
+  return arg_fail("not a per-handle key (ktab, jump, jump_pairs, search_lanes, jump_chars, tables_after, table_budget, locate_sample, extract_sample)");
 }
 
 int fmx_host_alloc(size_t bytes, void **out) {
@@ -607,7 +608,7 @@ int fmx_open_block(const uint8_t *bwt, uint64_t n, const int64_t bucket_starts[2
 
 int fmx_prepare(const fmx_index *idx, unsigned what) {
   if (!idx) return arg_fail("null argument");
-  if (what & ~(unsigned)(FMX_PREPARE_KTAB | FMX_PREPARE_SELECT | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_SEARCH | FMX_PREPARE_LOCATE | FMX_PREPARE_LCP)) return arg_fail("unknown fmx_prepare flag");
+  if (what & ~(unsigned)(FMX_PREPARE_KTAB | FMX_PREPARE_SELECT | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_SEARCH | FMX_PREPARE_LOCATE | FMX_PREPARE_LCP | FMX_PREPARE_EXTRACT)) return arg_fail("unknown fmx_prepare flag");
   const Index *h = H(idx);
   if (what & FMX_PREPARE_LOCATE) {
     const int lc = locate_check(h);
@@ -615,6 +616,10 @@ int fmx_prepare(const fmx_index *idx, unsigned what) {
   }
   if (what & FMX_PREPARE_LCP) {
     const int lc = lcp_check(h);
+    if (lc) return lc;
+  }
+  if (what & FMX_PREPARE_EXTRACT) {
+    const int lc = extract_check(h);
     if (lc) return lc;
   }
   int rc = use_device(h);
@@ -646,6 +651,10 @@ int fmx_prepare(const fmx_index *idx, unsigned what) {
     rc = lcp_prepare(h, lease.c->stream);
     if (rc) return rc;
   }
+  if (what & FMX_PREPARE_EXTRACT) {                               // after LOCATE: samples at the same rate are its short cut
+    rc = extract_prepare(h, lease.c->stream);
+    if (rc) return rc;
+  }
   // the literal search kernel this handle's tables select, calibrated here (its residency census: fmx_search.hip) so that no
   // _dev call ever has to read anything back
   if (what & (FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_SEARCH)) HIP_TRY(search_calibrate(h, lease.c->stream), "search calibration");
@@ -663,7 +672,7 @@ int fmx_prepare_ex(fmx_index *idx, unsigned what, uint64_t budget_bytes) {
 
 int fmx_drop_tables(fmx_index *idx, unsigned what) {
   if (!idx) return arg_fail("null argument");
-  if (!what || (what & ~(unsigned)(FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_LOCATE | FMX_PREPARE_LCP))) return arg_fail("fmx_drop_tables frees the k-mer table, the row tables, the locate samples and the LCP array (FMX_PREPARE_KTAB, FMX_PREPARE_JUMP, FMX_PREPARE_FRONTIER, FMX_PREPARE_LOCATE, FMX_PREPARE_LCP)");
+  if (!what || (what & ~(unsigned)(FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_LOCATE | FMX_PREPARE_LCP | FMX_PREPARE_EXTRACT))) return arg_fail("fmx_drop_tables frees the k-mer table, the row tables, the locate samples, the LCP array and the extract samples (FMX_PREPARE_KTAB, FMX_PREPARE_JUMP, FMX_PREPARE_FRONTIER, FMX_PREPARE_LOCATE, FMX_PREPARE_LCP, FMX_PREPARE_EXTRACT)");
   Index *h = H(idx);
   int rc = use_device(h);
   if (rc) return rc;
@@ -1907,6 +1916,83 @@ int fmx_mstat_last(double *walk_ms, double *compact_ms, uint64_t *steps, uint64_
   if (compact_ms) *compact_ms = g_mstat_last.compact_ms;
   if (steps) *steps = g_mstat_last.steps;
   if (requests) *requests = g_mstat_last.requests;
+  return FMX_OK;
+}
+
+// ---------------------------------------------------------------- extract: text by position (fmx_extract.hip)
+static thread_local ExtractInfo g_extract_last;
+
+int fmx_extract_text_batch(const fmx_index *idx, const uint64_t *pos, const uint64_t *off, size_t k, uint8_t *out) {
+  if ((uint64_t)k > (1ull << 26)) return arg_fail("extract: at most 2^26 ranges per call");
+  if (k && (!pos || !off)) return arg_fail("extract: null argument");
+  if (k && off[0] != 0) return arg_fail("extract: off[0] must be 0");
+  if (k && !offsets_monotonic(off, 0, k)) return arg_fail("extract: range offsets must be non-decreasing");
+  const uint64_t n_bytes = k ? off[k] : 0;
+  if (n_bytes >= (1ull << 32)) return arg_fail("extract: n_bytes = off[k] must be below 2^32");
+  if (n_bytes && !out) return arg_fail("extract: null argument (out)");
+  if (!idx) return arg_fail("extract: the handle is null");
+  const Index *h = H(idx);
+  int rc = extract_check(h);
+  if (rc) return rc;
+  const uint64_t len = h->n - 1;
+  for (size_t q = 0; q < k; q++) {
+    const uint64_t l = off[q + 1] - off[q];
+    if (pos[q] > len || l > len - pos[q]) return arg_fail("extract: a range runs past the text (pos + length <= n - 1)");
+  }
+  if (!n_bytes) return FMX_OK;
+  if ((rc = use_device(h))) return rc;
+  if ((rc = ensure_built(h, h->ext_mu, h->ext_ready, extract_prepare, nullptr))) return rc;
+  if ((rc = mstat_room(extract_bytes() + n_bytes + 16 * ((uint64_t)k + 1) + 64, "fmx_extract_text_batch"))) return rc;
+  DevMem mem;
+  StreamGuard own;
+  HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
+  uint64_t *d_pos = nullptr, *d_off = nullptr;
+  uint8_t *d_out = nullptr;
+  DEV_ALLOC(mem, d_pos, 8 * (uint64_t)k, "positions");
+  DEV_ALLOC(mem, d_off, 8 * ((uint64_t)k + 1), "offsets");
+  DEV_ALLOC(mem, d_out, n_bytes, "text");
+  HIP_TRY(hipMemcpyAsync(d_pos, pos, 8 * (uint64_t)k, hipMemcpyHostToDevice, own.s), "H2D(positions)");
+  HIP_TRY(hipMemcpyAsync(d_off, off, 8 * ((uint64_t)k + 1), hipMemcpyHostToDevice, own.s), "H2D(offsets)");
+  HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
+  ExtractInfo info;
+  rc = extract_run(h, d_pos, d_off, k, n_bytes, d_out, own.s, &info);
+  g_extract_last = info;
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(out, d_out, n_bytes, hipMemcpyDeviceToHost, own.s), "D2H(text)");
+  HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
+  return FMX_OK;
+}
+
+int fmx_extract_text_batch_dev(const fmx_index *idx, const void *d_pos, const void *d_off, size_t k, uint64_t n_bytes,
+                               void *d_out, void *stream) {
+  if ((uint64_t)k > (1ull << 26)) return arg_fail("extract: at most 2^26 ranges per call");
+  if (n_bytes >= (1ull << 32)) return arg_fail("extract: n_bytes must be below 2^32");
+  if (k && n_bytes && (!d_pos || !d_off || !d_out)) return arg_fail("extract: null argument");
+  if (!idx) return arg_fail("extract: the handle is null");
+  const Index *h = H(idx);
+  int rc = extract_check(h);
+  if (rc) return rc;
+  if (!k || !n_bytes) return FMX_OK;
+  if ((rc = use_device(h))) return rc;
+  if ((rc = ensure_built(h, h->ext_mu, h->ext_ready, extract_prepare, (hipStream_t)stream))) return rc;
+  HIP_TRY(extract_enqueue(h, d_pos, d_off, k, n_bytes, d_out, nullptr, (hipStream_t)stream), "k_extract");
+  return FMX_OK;
+}
+
+int fmx_extract_info(const fmx_index *idx, uint32_t *rate, uint64_t *bytes, double *build_ms) {
+  if (!idx) return arg_fail("null argument");
+  const Index *h = H(idx);
+  std::lock_guard<std::mutex> lk(h->ext_mu);
+  if (rate) *rate = h->ext_ready ? h->ext_rate : (uint32_t)h->policy.extract_sample.load(std::memory_order_relaxed);
+  if (bytes) *bytes = h->ext_ready ? h->ext_bytes : 0;
+  if (build_ms) *build_ms = h->ext_ready ? h->ext_build_ms : 0.0;
+  return FMX_OK;
+}
+
+int fmx_extract_last(double *ms, uint64_t *steps, uint64_t *requests) {
+  if (ms) *ms = g_extract_last.ms;
+  if (steps) *steps = g_extract_last.steps;
+  if (requests) *requests = g_extract_last.requests;
   return FMX_OK;
 }
 

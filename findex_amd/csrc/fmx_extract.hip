@@ -1,0 +1,377 @@
+// fmx_extract.hip -- text by position from inverse-SA samples.
+//
+// s = reverse(text) + sentinel, n = len + 1 rows; SA[0] = n - 1, SA[LF r] = SA[r] - 1 (fmx_locate.hip).  The row with
+// SA == v (v >= 1) holds the BWT byte s[v - 1] = text[n - 1 - v], so an LF walk from it emits text[n - 1 - v], text[n - v], ..:
+// the text FORWARDS.  A handle keeps ISA SAMPLES at a rate `rate` (the key "extract_sample"): isa[j] = the row with
+// SA == j * rate, j = 0 .. (n - 1) / rate (u32 when n <= 2^32, else u64) -- pass 2 of the locate inversion's tmp, packed; or,
+// when the handle's locate samples exist at the same rate, one scatter pass over their marks (isa[samples[k] / rate] = the
+// k-th marked row), no inversion.
+//
+// To emit from text offset t: v = n - 1 - t, up = ceil(v / rate) * rate; when up <= n - 1 the walk starts at isa[up / rate] and
+// skips up - v steps, otherwise it starts at row 0 (SA n - 1) and skips n - 1 - v.  A range is cut into PIECES at every t with
+// (n - 1 - t) % rate == 0 (and at tile edges): each piece is a walk of its own, at most rate - 1 skipped plus rate emitted
+// steps, a loop on a counter.  A long range is as many independent walks as it has pieces.
+//
+// The batch is k ranges: range q is the off[q + 1] - off[q] text bytes from text offset pos[q], written at out[off[q] ..).  A
+// WORKGROUP takes tiles of kExTile consecutive OUTPUT bytes, grid-strided.  Each thread finds the range that owns its output
+// byte (a search over the offsets, its result clamped to 0 .. k - 1), computes t and decides whether its byte heads a piece:
+// the tile's first byte, a range's first byte, or (n - 1 - t) % rate == 0.  A head computes its piece -- start row, steps to
+// skip, bytes to emit, all clamped -- and appends it to the tile's piece list in LDS.  The lane groups (quads, or octets on the
+// bytes layout) then draw pieces from a cursor in LDS and walk them, one LF step a round, putting their bytes into the tile in
+// LDS; the workgroup writes the tile with 16-byte stores.  A byte with t >= n - 1, or that no range covers, is 0 and costs no
+// walk.  Nothing is written outside out[0 .. n_bytes), and no operand value forms an address outside the index.
+#include <fmx.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <string>
+
+#include "fmx_device.h"
+#include "fmx_host.h"
+
+namespace fmx {
+
+constexpr int kExThreads = 256;
+constexpr uint32_t kExTile = FMX_EXTRACT_TILE;             // output bytes per tile
+constexpr uint32_t kExLineWords = 32;                      // the call's own words: [16] steps, [17] requests
+static_assert(kExTile == 1024, "a piece's start and length are packed into 10 bits each");
+static_assert(kExTile == 4 * kExThreads, "the tile is cleared one dword per thread");
+
+struct ExDev {
+  const void *isa;
+  uint64_t m;          // entries of isa: (n - 1) / rate + 1
+  uint32_t rate;
+  uint32_t wide;       // entries are u64
+};
+
+struct ExShared {
+  uint64_t cf[256];
+  uint16_t slot[256];
+  uint64_t row[kExTile];                                   // per piece: the row its walk starts on
+  uint32_t meta[kExTile];                                  // first byte in the tile | (bytes - 1) << 10 | steps to skip << 20
+  __attribute__((aligned(16))) uint8_t tile[kExTile];
+  uint32_t np, cursor;
+};
+
+__device__ __forceinline__ uint64_t ex_min(uint64_t a, uint64_t b) { return a < b ? a : b; }
+
+template <bool WIDE, uint32_t LAYOUT>
+__global__ __launch_bounds__(kExThreads) void k_extract(DevIndex ix, ExDev xd, const uint64_t *__restrict__ pos,
+                                                        const uint64_t *__restrict__ off, uint64_t k, uint64_t n_bytes,
+                                                        uint8_t *__restrict__ out, unsigned long long *__restrict__ counters) {
+  __shared__ ExShared sh;
+  for (int c = threadIdx.x; c < 256; c += kExThreads) {
+    sh.cf[c] = ix.cf[c];
+    sh.slot[c] = ix.slot[c];
+  }
+  constexpr int G = Lay<LAYOUT>::G;
+  const LaneConst lc = lane_const<G>();
+  const bool lead = lc.t == 0;
+  const uint64_t last = ix.n - 1;                          // the text's length; also the largest row
+  const uint32_t s = xd.rate;
+  unsigned long long steps = 0, reqs = 0;                  // counted by the lane that leads the group
+  const uint64_t ntiles = (n_bytes + kExTile - 1) / kExTile;
+  for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const uint64_t tile_lo = tile * kExTile;
+    const uint32_t tile_n = (uint32_t)ex_min(kExTile, n_bytes - tile_lo);
+    __syncthreads();                                       // the tile before this one is written (and cf / slot are there)
+    if (threadIdx.x == 0) {
+      sh.np = 0;
+      sh.cursor = 0;
+    }
+    reinterpret_cast<uint32_t *>(sh.tile)[threadIdx.x] = 0u;
+    __syncthreads();
+    // ---- heads: one piece per head, its walk fully described
+    for (uint32_t p = threadIdx.x; p < tile_n; p += kExThreads) {
+      const uint64_t j = tile_lo + p;
+      uint64_t lo = 0, hi = k - 1;                         // the largest q in 0 .. k - 1 with off[q] <= j (0 when there is none)
+      while (lo < hi) {
+        const uint64_t mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= j) lo = mid; else hi = mid - 1;
+      }
+      const uint64_t rs = off[lo], re = off[lo + 1];
+      if (j < rs || j >= re) continue;                     // no range covers the byte: 0
+      const uint64_t p0 = pos[lo], d = j - rs;
+      if (p0 >= last || d >= last - p0) continue;          // t >= n - 1: 0, no walk
+      const uint64_t v = last - (p0 + d);                  // 1 .. n - 1
+      const uint64_t vq = v / s;
+      const uint32_t ph = (uint32_t)(v - vq * s);
+      if (!(p == 0 || d == 0 || ph == 0)) continue;
+      // the bytes up to the next cut: the tile's end, the range's end, the next t with (n - 1 - t) % s == 0
+      const uint32_t len = (uint32_t)ex_min(ex_min(tile_n - p, re - j), ph ? ph : s);
+      const uint64_t uj = vq + (ph ? 1u : 0u);             // ceil(v / s)
+      uint64_t row = 0;
+      uint32_t skip;
+      if (uj < xd.m) {                                     // uj * s <= n - 1: a sample
+        row = xd.wide ? static_cast<const uint64_t *>(xd.isa)[uj] : (uint64_t) static_cast<const uint32_t *>(xd.isa)[uj];
+        skip = ph ? s - ph : 0u;
+      } else {                                             // row 0, SA n - 1; fewer than s steps away
+        skip = (uint32_t)(last - v);
+      }
+      const uint32_t at = atomicAdd(&sh.np, 1u);           // at most one piece per byte of the tile
+      sh.row[at] = ex_min(row, last);
+      sh.meta[at] = p | ((len - 1u) << 10) | ((uint32_t)ex_min(skip, s - 1u) << 20);
+    }
+    __syncthreads();
+    // ---- walks: a group draws a piece, steps it skip + len times, draws the next
+    const uint32_t np = sh.np;
+    bool live = false, done = false;                       // the same in all lanes of a group
+    uint32_t wp = 0, left = 0, skip = 0;
+    uint64_t r = 0;
+    for (;;) {
+      if (!live && !done) {
+        const uint32_t idx = group_bcast<G, 0>(lead ? atomicAdd(&sh.cursor, 1u) : 0u);
+        if (idx < np) {
+          const uint32_t m = sh.meta[idx];
+          r = sh.row[idx];
+          wp = m & 1023u;
+          skip = m >> 20;
+          left = ((m >> 10) & 1023u) + 1u + skip;          // <= 2 s - 1
+          live = true;
+        } else {
+          done = true;
+        }
+      }
+      if (!__builtin_amdgcn_ballot_w64(live)) break;
+      if (live) {
+        const uint32_t b = r == ix.eof ? 0u : (uint32_t)ix.bwt[r];
+        const RankReq q = rank_issue<LAYOUT>(ix, sh.slot[b], r, lc);
+        if (skip) {
+          skip--;
+        } else {
+          if (lead) sh.tile[wp] = (uint8_t)b;
+          wp++;
+        }
+        r = ex_min(sh.cf[b] + rank_complete<WIDE, LAYOUT>(q, b, lc), last);
+        if (lead) {
+          steps++;
+          reqs += 1u + (q.kind ? (LAYOUT == kLayoutBytes ? 2u : 1u) : 0u);
+        }
+        left--;
+        live = left != 0;
+      }
+    }
+    __syncthreads();
+    // ---- the tile, 16 bytes per store where the destination allows
+    uint8_t *dst = out + tile_lo;
+    if (((uintptr_t)dst & 15u) == 0) {
+      for (uint32_t c = threadIdx.x * 16u; c < tile_n; c += kExThreads * 16u) {
+        if (c + 16u <= tile_n) {
+          *reinterpret_cast<uint4 *>(dst + c) = *reinterpret_cast<const uint4 *>(sh.tile + c);
+        } else {
+          for (uint32_t e = c; e < tile_n; e++) dst[e] = sh.tile[e];
+        }
+      }
+    } else {
+      for (uint32_t c = threadIdx.x; c < tile_n; c += kExThreads) dst[c] = sh.tile[c];
+    }
+  }
+  counters_add(counters, steps, 0ull, reqs);
+}
+
+// The call's counter slots into the handle's, and their sums into the call's line (the host form).
+__global__ __launch_bounds__(256) void k_extract_fold(const unsigned long long *__restrict__ mine,
+                                                      unsigned long long *__restrict__ counters,
+                                                      unsigned long long *__restrict__ line) {
+  const uint32_t sl = blockIdx.x * 256u + threadIdx.x;
+  unsigned long long v[3] = {0, 0, 0};
+  if (sl < kCounterSlots) {
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      v[j] = mine[(size_t)sl * kCounterStride + j];
+      if (v[j]) atomicAdd(counters + (size_t)sl * kCounterStride + j, v[j]);
+    }
+  }
+  const unsigned long long s0 = wave_sum(v[0]), s2 = wave_sum(v[2]);
+  if ((threadIdx.x & 63u) == 0) {
+    if (s0) atomicAdd(line + 16, s0);
+    if (s2) atomicAdd(line + 17, s2);
+  }
+}
+
+// ---------------------------------------------------------------- the samples
+// isa[j] = tmp[j], a row below n
+__global__ __launch_bounds__(256) void k_isa_pack(const uint64_t *__restrict__ tmp, uint64_t m, uint64_t n, int wide,
+                                                  void *__restrict__ isa) {
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t r = ex_min(tmp[j], n - 1);
+    if (wide) static_cast<uint64_t *>(isa)[j] = r;
+    else static_cast<uint32_t *>(isa)[j] = (uint32_t)r;
+  }
+}
+
+// From the locate samples at the same rate: the k-th set bit of the marks is a row r with SA samples[k]: isa[samples[k] / rate] = r.
+__global__ __launch_bounds__(256) void k_isa_scatter(const uint32_t *__restrict__ marks, uint64_t nb, uint64_t n,
+                                                     const void *__restrict__ samples, int swide, uint32_t rate, uint64_t m,
+                                                     int wide, void *__restrict__ isa) {
+  for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; b < nb; b += (uint64_t)gridDim.x * blockDim.x) {
+    uint64_t rank = *reinterpret_cast<const uint64_t *>(marks + b * 16);
+    for (uint32_t d = 2; d < 16; d++) {
+      uint32_t w = marks[b * 16 + d];
+      for (uint32_t i = 0; i < 32u && w; i++) {            // one round per set bit
+        const uint32_t bit = (uint32_t)__builtin_ctz(w);
+        w &= w - 1u;
+        const uint64_t r = b * kBlockBits + 32u * (d - 2) + bit, kk = rank++;
+        if (kk >= m || r >= n) continue;
+        const uint64_t sa = swide ? static_cast<const uint64_t *>(samples)[kk] : (uint64_t) static_cast<const uint32_t *>(samples)[kk];
+        const uint64_t j = sa / rate;
+        if (j >= m) continue;
+        if (wide) static_cast<uint64_t *>(isa)[j] = r;
+        else static_cast<uint32_t *>(isa)[j] = (uint32_t)r;
+      }
+    }
+  }
+}
+
+static uint32_t ex_grid(uint64_t items) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, 8192)); }
+
+int extract_check(const Index *h) {
+  if (h->block_mode) {
+    set_error("extraction needs the index of one text: fmx_open_block handles (one merge block) have no suffix array");
+    return FMX_ERR_UNSUPPORTED;
+  }
+  if (h->n >= kOneHotMaxN) {
+    set_error("extraction: indexes of 2^37 rows and more are not supported");
+    return FMX_ERR_UNSUPPORTED;
+  }
+  return FMX_OK;
+}
+
+int extract_prepare(const Index *h, hipStream_t st) {
+  int rc = extract_check(h);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(h->ext_mu);
+  if (h->ext_ready) return FMX_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  const uint64_t n = h->n;
+  const uint32_t rate = (uint32_t)h->policy.extract_sample.load(std::memory_order_relaxed);
+  const uint64_t m = (n - 1) / rate + 1, nb = n / kBlockBits + 1;
+  const bool wide = n > (1ull << 32);
+  const uint64_t keep = m * (wide ? 8 : 4);
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  HIP_TRY(hipStreamIsCapturing(st, &cs), "hipStreamIsCapturing");
+  if (cs != hipStreamCaptureStatusNone) {
+    set_error("the extract samples are built by fmx_prepare(FMX_PREPARE_EXTRACT) or a first extract call outside a stream capture");
+    return FMX_ERR_HIP;
+  }
+  // the locate samples at the same rate hold the same pairs (row, SA): no inversion then
+  std::unique_lock<std::mutex> ll(h->loc_mu);
+  const bool from_locate = h->loc_ready && h->loc_rate == rate;
+  if (!from_locate) ll.unlock();
+  const uint64_t need = keep + (from_locate ? 0 : m * 8 + locate_invert_rows_bytes(h));
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
+  if (need > free_b) {
+    set_error("the extract samples need " + std::to_string((unsigned long long)need) + " bytes of device memory, " +
+              std::to_string((unsigned long long)free_b) + " are free");
+    return FMX_ERR_NOMEM;
+  }
+  DevMem mem;                                              // the temporaries, and the samples until they are the handle's
+  void *d_isa = nullptr;
+  DEV_ALLOC(mem, d_isa, keep, "extract samples");
+  if (from_locate) {
+    HIP_TRY(hipMemsetAsync(d_isa, 0, keep, st), "hipMemset(extract samples)");
+    hipLaunchKernelGGL(k_isa_scatter, dim3(ex_grid(nb)), dim3(256), 0, st, static_cast<const uint32_t *>(h->d_loc_marks), nb, n,
+                       static_cast<const void *>(h->d_loc_samples), h->loc_wide ? 1 : 0, rate, m, wide ? 1 : 0, d_isa);
+    HIP_TRY(hipGetLastError(), "k_isa_scatter");
+    HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    ll.unlock();
+  } else {
+    uint64_t *tmp = nullptr;
+    DEV_ALLOC(mem, tmp, m * 8, "extract samples");
+    HIP_TRY(hipMemsetAsync(tmp, 0, m * 8, st), "hipMemset(extract samples)");
+    if ((rc = locate_invert_rows(h, st, rate, tmp))) return rc;
+    hipLaunchKernelGGL(k_isa_pack, dim3(ex_grid(m)), dim3(256), 0, st, static_cast<const uint64_t *>(tmp), m, n, wide ? 1 : 0, d_isa);
+    HIP_TRY(hipGetLastError(), "k_isa_pack");
+    HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+  }
+  mem.ps.erase(std::find(mem.ps.begin(), mem.ps.end(), d_isa));      // kept
+  h->d_ext_isa = d_isa;
+  h->ext_rate = rate;
+  h->ext_wide = wide;
+  h->ext_bytes = keep;
+  h->ext_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  h->ext_ready = true;
+  return FMX_OK;
+}
+
+void extract_drop(Index *h) {
+  std::lock_guard<std::mutex> lk(h->ext_mu);
+  if (h->d_ext_isa) (void)hipFree(h->d_ext_isa);
+  h->d_ext_isa = nullptr;
+  h->ext_bytes = 0;
+  h->ext_rate = 0;
+  h->ext_ready = false;
+}
+
+// ---------------------------------------------------------------- launches
+template <bool WIDE, uint32_t LAYOUT>
+static hipError_t ex_launch(const Index *h, const ExDev &xd, const uint64_t *pos, const uint64_t *off, uint64_t k, uint64_t n_bytes,
+                            uint8_t *out, unsigned long long *counters, hipStream_t st) {
+  static std::atomic<int> cached{0};                       // per instantiation: the query is made once
+  int per_cu = cached.load(std::memory_order_relaxed);
+  if (per_cu <= 0) {
+    const hipError_t he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_extract<WIDE, LAYOUT>, kExThreads, 0);
+    if (he != hipSuccess) return he;
+    per_cu = std::max(per_cu, 1);
+    cached.store(per_cu, std::memory_order_relaxed);
+  }
+  const uint64_t resident = (uint64_t)per_cu * (uint64_t)std::max(h->cu_count, 1);
+  const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(resident, (n_bytes + kExTile - 1) / kExTile));
+  hipLaunchKernelGGL((k_extract<WIDE, LAYOUT>), dim3(grid), dim3(kExThreads), 0, st, h->dev, xd, pos, off, k, n_bytes, out, counters);
+  return hipGetLastError();
+}
+
+hipError_t extract_enqueue(const Index *h, const void *d_pos, const void *d_off, uint64_t k, uint64_t n_bytes, void *d_out,
+                           unsigned long long *counters, hipStream_t st) {
+  if (n_bytes == 0 || k == 0) return hipSuccess;
+  ExDev xd;
+  xd.isa = h->d_ext_isa;
+  xd.rate = h->ext_rate;
+  xd.m = (h->n - 1) / h->ext_rate + 1;
+  xd.wide = h->ext_wide ? 1u : 0u;
+  hipError_t he = hipSuccess;
+#define FMX_EX_CALL(W, L) \
+  he = ex_launch<W, L>(h, xd, static_cast<const uint64_t *>(d_pos), static_cast<const uint64_t *>(d_off), k, n_bytes, \
+                       static_cast<uint8_t *>(d_out), counters ? counters : h->d_counters, st)
+  FMX_LAYOUT_DISPATCH(h, FMX_EX_CALL);
+#undef FMX_EX_CALL
+  return he;
+}
+
+uint64_t extract_bytes() { return kCounterBytes + 8 * kExLineWords; }
+
+int extract_run(const Index *h, const void *d_pos, const void *d_off, uint64_t k, uint64_t n_bytes, void *d_out, hipStream_t st,
+                ExtractInfo *info) {
+  *info = ExtractInfo{};
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 2; i++) if (ev[i]) (void)hipEventDestroy(ev[i]); } } evg{ev};
+  for (int i = 0; i < 2; i++) HIP_TRY(hipEventCreate(&ev[i]), "hipEventCreate");
+  DevMem mem;
+  unsigned long long *line = nullptr, *mine = nullptr;
+  DEV_ALLOC(mem, line, 8 * kExLineWords, "extraction");
+  DEV_ALLOC(mem, mine, kCounterBytes, "extraction");
+  HIP_TRY(hipMemsetAsync(line, 0, 8 * kExLineWords, st), "memset");
+  HIP_TRY(hipMemsetAsync(mine, 0, kCounterBytes, st), "memset");
+  HIP_TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+  HIP_TRY(extract_enqueue(h, d_pos, d_off, k, n_bytes, d_out, mine, st), "k_extract");
+  HIP_TRY(hipEventRecord(ev[1], st), "hipEventRecord");
+  hipLaunchKernelGGL(k_extract_fold, dim3(kCounterSlots / 256), dim3(256), 0, st, mine, h->d_counters, line);
+  HIP_TRY(hipGetLastError(), "k_extract_fold");
+  unsigned long long words[kExLineWords];
+  HIP_TRY(hipMemcpyAsync(words, line, sizeof words, hipMemcpyDeviceToHost, st), "D2H");
+  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");  // the temporaries go when this returns
+  {
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->launches += 1;
+  }
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+  info->ms = ms;
+  info->steps = words[16];
+  info->requests = words[17];
+  return FMX_OK;
+}
+
+}  // namespace fmx

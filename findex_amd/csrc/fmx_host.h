@@ -68,6 +68,7 @@ struct TablePolicy {
   std::atomic<uint64_t> budget_bytes{~0ull};   // ~0: none (what fits beside the margins)
   std::atomic<uint32_t> budget_ppb{0};         // != 0: a fraction (billionths) of the HBM that is free when a table is decided, the handle's own tables counted as free
   std::atomic<int> locate_sample{32};          // "locate_sample": the rate s of the locate samples (rows with SA % s == 0), 1 .. 4096
+  std::atomic<int> extract_sample{32};         // "extract_sample": the rate s of the inverse-SA samples (the row of every SA value j s), 1 .. 4096
   TablePolicy() = default;
   TablePolicy(const TablePolicy &o) { *this = o; }
   TablePolicy &operator=(const TablePolicy &o) {
@@ -76,6 +77,7 @@ struct TablePolicy {
     jump_chars.store(o.jump_chars.load()); tables_after.store(o.tables_after.load());
     budget_bytes.store(o.budget_bytes.load()); budget_ppb.store(o.budget_ppb.load());
     locate_sample.store(o.locate_sample.load());
+    extract_sample.store(o.extract_sample.load());
     return *this;
   }
 };
@@ -181,6 +183,15 @@ struct Index {
   mutable double lcp_build_ms = 0.0;
   mutable uint32_t lcp_max = 0;                 // the largest entry, the first row that holds it, the sum of all entries
   mutable uint64_t lcp_max_row = 0, lcp_sum = 0;
+  // inverse-SA samples for extraction by text position (fmx_extract.hip), built by fmx_prepare(FMX_PREPARE_EXTRACT) or the
+  // first extract call; outside the table budget like the locate samples
+  mutable std::mutex ext_mu;
+  mutable bool ext_ready = false;
+  mutable void *d_ext_isa = nullptr;            // isa[j] = the row with SA == j * ext_rate, j = 0 .. (n - 1) / ext_rate: u32, or u64 when ext_wide
+  mutable uint32_t ext_rate = 0;
+  mutable bool ext_wide = false;
+  mutable uint64_t ext_bytes = 0;
+  mutable double ext_build_ms = 0.0;
   mutable uint64_t launches = 0;
   mutable double last_kernel_ms = 0.0;
   // the handle's host thread for the one-process-several-GPUs entry points (made at the first such call; fmx_hostpar.h)
@@ -236,6 +247,30 @@ hipError_t launch_locate_intervals(const Index *h, const void *d_sp, const void 
 // the sentinel 0 at d_s[n - 1]; locate_invert_text_bytes: the device bytes of its temporaries (the outputs not counted).
 int locate_invert_text(const Index *h, hipStream_t st, uint32_t *d_sa, uint8_t *d_s);
 uint64_t locate_invert_text_bytes(const Index *h);
+
+// pass 2 of the inversion alone (fmx_extract.hip): d_tmp[v / rate] = the row with SA == v for every v % rate == 0, d_tmp of
+// (n - 1) / rate + 1 entries given by the caller; locate_invert_rows_bytes: the device bytes of its temporaries (d_tmp not
+// counted).  Synchronises `st`; the handle's own samples are untouched.
+int locate_invert_rows(const Index *h, hipStream_t st, uint32_t rate, uint64_t *d_tmp);
+uint64_t locate_invert_rows_bytes(const Index *h);
+
+// fmx_extract.hip: text by position from inverse-SA samples.  extract_prepare builds the samples under ext_mu
+// (allocates, synchronises `st`; an FMX_* status with its message).  extract_enqueue: the k ranges' n_bytes bytes into d_out,
+// device pointers throughout; it needs the samples built and only enqueues on `st`; counters == nullptr: the handle's own.
+// extract_run: the same with the call's own counters and timing; allocates, synchronises `st`, frees its temporaries on
+// every path.  extract_bytes: the device bytes extract_run allocates.
+struct ExtractInfo {
+  uint64_t steps = 0, requests = 0;
+  double ms = 0.0;                              // device events around k_extract
+};
+int extract_check(const Index *h);              // FMX_ERR_UNSUPPORTED for handles extraction cannot serve (those of locate)
+int extract_prepare(const Index *h, hipStream_t st);
+void extract_drop(Index *h);
+hipError_t extract_enqueue(const Index *h, const void *d_pos, const void *d_off, uint64_t k, uint64_t n_bytes, void *d_out,
+                           unsigned long long *counters, hipStream_t st);
+uint64_t extract_bytes();
+int extract_run(const Index *h, const void *d_pos, const void *d_off, uint64_t k, uint64_t n_bytes, void *d_out, hipStream_t st,
+                ExtractInfo *info);
 
 // fmx_lcp.hip: the LCP array.  lcp_core: LCP[n] of s from s and its suffix array, all in device memory;
 // d_s is s itself (lcp_text_bytes(n) bytes: s, the sentinel 0 last, and zero padding); allocates 4 n bytes, synchronises `st`, returns an FMX_*

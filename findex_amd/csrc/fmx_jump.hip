@@ -195,6 +195,13 @@ int policy_set(TablePolicy &p, const char *key, const char *value, const char **
     p.locate_sample.store((int)v);
     return 0;
   }
+  if (is("extract_sample")) {
+    char *end = nullptr;
+    const long v = std::strtol(value, &end, 10);
+    if (end == value || *end || v < 1 || v > 4096) { *why = "extract_sample must be an integer 1 .. 4096"; return 2; }
+    p.extract_sample.store((int)v);
+    return 0;
+  }
   if (is("jump_chars")) {
     uint64_t v = 0;
     if (!parse_u64(value, &v) || v < 8 || v > 11) { *why = "jump_chars must be 8, 9, 10 or 11"; return 2; }
@@ -434,6 +441,7 @@ int drop_tables(Index *h, unsigned what) {
   }
   if (what & 32u) locate_drop(h);     // the locate samples (FMX_PREPARE_LOCATE)
   if (what & 64u) lcp_drop(h);        // the LCP array (FMX_PREPARE_LCP)
+  if (what & 128u) extract_drop(h);   // the inverse-SA samples (FMX_PREPARE_EXTRACT)
   return 0;
 }
 

@@ -702,6 +702,16 @@ int locate_invert_text(const Index *h, hipStream_t st, uint32_t *d_sa, uint8_t *
 
 uint64_t locate_invert_text_bytes(const Index *h) { return inv_temp_bytes(h->n, 0); }
 
+// The inverse-SA samples' input (fmx_extract.hip): pass 2's tmp itself, into the caller's array.
+int locate_invert_rows(const Index *h, hipStream_t st, uint32_t rate, uint64_t *d_tmp) {
+  int rc = loc_supported(h);
+  if (rc) return rc;
+  DevMem mem;
+  return invert(h, st, mem, rate, d_tmp, nullptr);
+}
+
+uint64_t locate_invert_rows_bytes(const Index *h) { return inv_temp_bytes(h->n, 0); }
+
 static LocDev loc_dev(const Index *h) {
   LocDev ld;
   ld.marks = (const uint4 *)h->d_loc_marks;

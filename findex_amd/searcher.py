@@ -460,6 +460,41 @@ class HipFMSearcher:
         _lib.check(self._L.fmx_mstat_last(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
         return float(a.value), float(b.value), int(c.value), int(d.value)
 
+    # ---- extract: the text by position, from inverse-SA samples (fmx.h: extract)
+    def extract_text_batch(self, pos, lengths):
+        """fmx_extract_text_batch: (off, data) -- range q, the lengths[q] text bytes from text offset pos[q], is
+        data[off[q]:off[q + 1]] (data a uint8 array); the handle indexes reverse(text) as from_text has it."""
+        pos = np.ascontiguousarray(pos, dtype=np.uint64).reshape(-1)
+        lengths = np.ascontiguousarray(lengths, dtype=np.uint64).reshape(-1)
+        if pos.size != lengths.size:
+            raise ValueError("pos and lengths differ in length")
+        off = np.zeros(pos.size + 1, dtype=np.uint64)
+        np.cumsum(lengths, out=off[1:])
+        out = np.zeros(int(off[-1]), dtype=np.uint8)
+        _lib.check(self._L.fmx_extract_text_batch(self._h, _ptr(pos), off.ctypes.data_as(ctypes.c_void_p), pos.size, _ptr(out)))
+        return off, out
+
+    def extract_text(self, pos, length):
+        """The `length` text bytes from text offset `pos`."""
+        return self.extract_text_batch([int(pos)], [int(length)])[1].tobytes()
+
+    def extract_text_batch_dev(self, d_pos, d_off, k, n_bytes, d_out, stream=0):
+        """fmx_extract_text_batch_dev: device pointers (u64 pos[k], u64 off[k + 1], n_bytes = off[k] bytes out); with the
+        samples prepared it only enqueues."""
+        _lib.check(self._L.fmx_extract_text_batch_dev(self._h, _dp(d_pos), _dp(d_off), int(k), int(n_bytes), _dp(d_out), _dp(stream)))
+
+    def extract_info(self):
+        """fmx_extract_info: (rate, device bytes, build ms) of the inverse-SA samples; 0 bytes when not built."""
+        rate, nbytes, ms = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_double()
+        _lib.check(self._L.fmx_extract_info(self._h, ctypes.byref(rate), ctypes.byref(nbytes), ctypes.byref(ms)))
+        return int(rate.value), int(nbytes.value), float(ms.value)
+
+    def extract_last(self):
+        """fmx_extract_last: (kernel ms, LF steps, memory requests) of this thread's last host-pointer extract call."""
+        a, b, c = ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64()
+        _lib.check(self._L.fmx_extract_last(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return float(a.value), int(b.value), int(c.value)
+
     def match_stats_text(self, q, max_len=None):
         """ms[i] = the length of the longest prefix of q[i:] that occurs in the indexed text (capped at max_len), for a handle
         that indexes reverse(text) as from_text and locate_text have it: the statistics of reverse(q), flipped."""
@@ -630,27 +665,27 @@ class HipFMSearcher:
         return ranks[: text.size], int(done.value)
 
     def prepare(self, ktab=True, select=False, jump=False, frontier=False, search=False, budget_bytes=0, locate=False,
-                lcp=False):
+                lcp=False, extract=False):
         """fmx_prepare[_ex]: build the k-mer jump table / the select directory / the literal search's row tables (J, R3) / the
-        regex frontier's row table / the locate samples / the LCP array now instead of at the threshold or at first use, and calibrate the
+        regex frontier's row table / the locate samples / the LCP array / the extract samples now instead of at the threshold or at first use, and calibrate the
         search kernel they select (`search` alone: only that).  budget_bytes != 0: the handle's "table_budget" first
         (fmx_prepare_ex)."""
         what = (1 if ktab else 0) | (2 if select else 0) | (4 if jump else 0) | (8 if frontier else 0) | (16 if search else 0) \
-            | (32 if locate else 0) | (64 if lcp else 0)
+            | (32 if locate else 0) | (64 if lcp else 0) | (128 if extract else 0)
         if budget_bytes:
             _lib.check(self._L.fmx_prepare_ex(self._h, what, int(budget_bytes)))
         else:
             _lib.check(self._L.fmx_prepare(self._h, what))
 
-    def drop_tables(self, jump=True, frontier=True, ktab=False, locate=False, lcp=False):
+    def drop_tables(self, jump=True, frontier=True, ktab=False, locate=False, lcp=False, extract=False):
         """fmx_drop_tables: free the row jump table and the three-step row table / the frontier's row table / the k-mer table /
-        the locate samples / the LCP array."""
+        the locate samples / the LCP array / the extract samples."""
         _lib.check(self._L.fmx_drop_tables(self._h, (4 if jump else 0) | (8 if frontier else 0) | (1 if ktab else 0)
-                                           | (32 if locate else 0) | (64 if lcp else 0)))
+                                           | (32 if locate else 0) | (64 if lcp else 0) | (128 if extract else 0)))
 
     def config_set(self, key, value):
         """fmx_index_config_set: this handle's own table policy ("ktab", "jump", "jump_pairs", "search_lanes", "jump_chars", "tables_after",
-        "table_budget"); tables that exist stay until drop_tables."""
+        "table_budget", "locate_sample", "extract_sample"); tables that exist stay until drop_tables."""
         _lib.check(self._L.fmx_index_config_set(self._h, key.encode(), str(value).encode()))
 
     # ---- statistics

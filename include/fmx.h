@@ -63,7 +63,8 @@ typedef struct fmx_regex_batch fmx_regex_batch;   /* a set of compiled regexes m
 const char *fmx_last_error(void);
 int fmx_abi_version(void);
 /* Process-wide options.  The table keys ("ktab", "jump", "jump_pairs", "search_lanes", "jump_chars", "tables_after", "table_budget",
- * "locate_sample": the locate samples' rate, fmx_locate_batch) are the
+ * "locate_sample": the locate samples' rate, fmx_locate_batch; "extract_sample": the inverse-SA samples' rate,
+ * fmx_extract_text_batch) are the
  * DEFAULTS a handle copies when it is opened; fmx_index_config_set changes one handle's own copy afterwards, so two handles
  * in one process (one JVM) can differ.  key "layout": "auto" (default: one-hot bit-vectors, one 64-byte block per
  * rank query, when sigma*n/7 bytes fit in free HBM and n < 2^37; else BWT bytes + checkpoints, two
@@ -209,11 +210,12 @@ int fmx_index_config_set(fmx_index *idx, const char *key, const char *value);
  * fmx_prepare_ex: the same under a budget -- budget_bytes != 0 becomes the handle's "table_budget" first. */
 enum { FMX_PREPARE_KTAB = 1, FMX_PREPARE_SELECT = 2, FMX_PREPARE_JUMP = 4, FMX_PREPARE_FRONTIER = 8, FMX_PREPARE_SEARCH = 16,
        FMX_PREPARE_LOCATE = 32 /* the locate samples (fmx_locate_batch below); fmx_drop_tables frees them */,
-       FMX_PREPARE_LCP = 64 /* the LCP array (fmx_lcp_batch below); fmx_drop_tables frees it */ };
+       FMX_PREPARE_LCP = 64 /* the LCP array (fmx_lcp_batch below); fmx_drop_tables frees it */,
+       FMX_PREPARE_EXTRACT = 128 /* the inverse-SA samples (fmx_extract_text_batch below); fmx_drop_tables frees them */ };
 int fmx_prepare(const fmx_index *idx, unsigned what);
 int fmx_prepare_ex(fmx_index *idx, unsigned what, uint64_t budget_bytes);
 /* Frees derived tables again (what = FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_LOCATE |
- * FMX_PREPARE_LCP in any combination: the k-mer table / the row jump table and the three-step row table, 16-32 n + 8 n bytes /
+ * FMX_PREPARE_LCP | FMX_PREPARE_EXTRACT (the inverse-SA samples) in any combination: the k-mer table / the row jump table and the three-step row table, 16-32 n + 8 n bytes /
  * the frontier's row table, 8 n bytes / the locate samples / the LCP array, 4 n bytes) and forgets the handle's pattern count, so that they come back only by fmx_prepare or when the threshold is met
  * anew (under the handle's policy as it is then).  No other call may be using the handle. */
 int fmx_drop_tables(fmx_index *idx, unsigned what);
@@ -450,6 +452,42 @@ int fmx_lcp_info(const fmx_index *idx, uint64_t *bytes, double *build_ms, uint32
                  uint64_t *sum_lcp);
 int fmx_write_lcp(const fmx_index *idx, const char *path);
 int fmx_lcp_last_phases(double *phi_ms, double *plcp_ms, double *gather_ms);
+
+/* ---- extract: the text itself, by text position.  Beyond the reference, whose nextSubstr / prevSubstr start from a row.
+ * DESIGN.md 17.  Definitions: s, n and SA as for locate; the row with SA == v (v >= 1) holds the BWT byte s[v - 1] =
+ * text[n - 1 - v], so an LF walk from it reads the text forwards.  The handle keeps INVERSE-SA SAMPLES: isa[j] = the row with
+ * SA == j * s for j = 0 .. (n - 1) / s (s = the key "extract_sample", 1 .. 4096, default 32; fmx_config_set: the default,
+ * fmx_index_config_set: one handle's own), 4 bytes each, 8 above 2^32 rows.  They are built by
+ * fmx_prepare(FMX_PREPARE_EXTRACT) or else by the first extract call -- which then allocates and synchronises (FMX_ERR_HIP
+ * "... outside a stream capture" under a capture, nothing allocated, the capture left valid): from the handle's locate
+ * samples by one scatter pass when those exist at the same rate, otherwise by the inversion that builds the locate samples
+ * (same array either way).  The need, temporaries included, is checked against the free HBM first (FMX_ERR_NOMEM with the
+ * need in the message); every temporary is freed on every path.  Outside the table budget; no other table changes.
+ * Refusals as locate: fmx_open_block handles and n >= 2^37 FMX_ERR_UNSUPPORTED, an index that is not the BWT of one text
+ * FMX_ERR_FORMAT.  A range is cut at every text offset t with (n - 1 - t) % s == 0 and each piece is a walk of its own from
+ * the next sample (or from row 0): at most s - 1 skipped and s emitted LF steps, about 1.5 steps per byte for ranges shorter
+ * than s and 1 for long ones.  Every step counts as one rank query in fmx_stats_t.rank_queries.
+ * The batch is k ranges: range q is the off[q + 1] - off[q] text bytes from text offset pos[q], written at
+ * out[off[q] .. off[q + 1]); off has k + 1 entries, off[0] == 0.
+ * fmx_extract_text_batch     : host pointers.  FMX_ERR_ARG, decided before the device is touched: a null handle or pointer,
+ *                              off[0] != 0, decreasing offsets, pos[q] + length > n - 1 (the text's length), k > 2^26,
+ *                              off[k] >= 2^32.  k == 0 or only empty ranges: FMX_OK, nothing written.
+ * fmx_extract_text_batch_dev : device pointers, n_bytes = off[k] given by the host.  With the samples prepared it only
+ *                              enqueues (safe inside a stream capture).  IT CANNOT VALIDATE ITS OPERANDS; its kernel clamps
+ *                              them before any address is formed: the range that owns an output byte is searched in
+ *                              d_off[0 .. k] only, a byte that no range covers (offsets that decrease, n_bytes beyond
+ *                              d_off[k]) is written as 0, a byte whose text offset is n - 1 or more is written as 0, rows read
+ *                              from the samples are read as at most n - 1.  Nothing is written outside d_out[0 .. n_bytes).
+ * fmx_extract_info           : the rate, device bytes and build time (ms) of the samples; 0 bytes when they are not built.
+ * fmx_extract_last           : the calling thread's last host-pointer call: device time (ms) of the kernel, LF steps made,
+ *                              memory requests (BWT bytes and rank-dictionary lines); any pointer may be NULL.
+ * FMX_EXTRACT_TILE: the output bytes a workgroup of the kernel takes at a time (what tests aim at). */
+#define FMX_EXTRACT_TILE 1024
+int fmx_extract_text_batch(const fmx_index *idx, const uint64_t *pos, const uint64_t *off, size_t k, uint8_t *out);
+int fmx_extract_text_batch_dev(const fmx_index *idx, const void *d_pos, const void *d_off, size_t k, uint64_t n_bytes,
+                               void *d_out, void *stream);
+int fmx_extract_info(const fmx_index *idx, uint32_t *rate, uint64_t *bytes, double *build_ms);
+int fmx_extract_last(double *ms, uint64_t *steps, uint64_t *requests);
 
 /* ---- approximate search: literal patterns with up to FMX_APPROX_MAX_MISMATCHES substituted bytes (Hamming distance; no
  * insertions or deletions).  Beyond the reference.  DESIGN.md 15.
