@@ -627,7 +627,9 @@ int fmx_mstat_last(double *walk_ms, double *compact_ms, uint64_t *steps, uint64_
  * fmx_corpus_doc_list  : for k row intervals (sp, ep) of `idx` -- the index of this corpus' stream -- found by searching the
  *                        reverse of an escaped pattern of pat_len stream bytes: the distinct documents of each interval's
  *                        first min(ep - sp, max_per) rows (max_per 0: all) with their hit counts, in CSR form: out_off[k + 1],
- *                        out_doc[], out_cnt[]; within an interval the documents ascend.  Nothing is written past entry
+ *                        out_doc[], out_cnt[]; within an interval the documents ascend.  A row whose position
+ *                        stream_len - pat_len - SA is not a stream position (an interval that no such search found, a
+ *                        wrong pat_len) is listed as document UINT32_MAX, after the interval's real documents.  Nothing is written past entry
  *                        cap - 1; the host form returns FMX_ERR_OVERFLOW when out_off[k] > cap (out_off complete, the first
  *                        cap entries written), the _dev form leaves the total in d_out_off[k] for the caller to check.  Locate,
  *                        map, a radix sort of (interval, document) keys, heads and compaction, all on the device.  Both forms

@@ -103,3 +103,25 @@ class RefCorpus:
                 out.append((d, i))
                 i = raw.find(q, i + 1)
         return out
+
+    def doc_counts(self, q):
+        """[(doc, count)] ascending by doc: in which files the raw bytes q occur, and how often (the document listing)."""
+        counts = {}
+        for d, _ in self.occurrences(q):
+            counts[d] = counts.get(d, 0) + 1
+        return sorted(counts.items())
+
+    def list_positions(self, positions):
+        """[(doc, count)] ascending by doc of stream positions looked up in the per-position table; None stands for "no
+        stream position", and those are counted in a last entry (0xFFFFFFFF, count) when there are any."""
+        counts, none = {}, 0
+        for p in positions:
+            if p is None:
+                none += 1
+            else:
+                d = self.table[p][0]
+                counts[d] = counts.get(d, 0) + 1
+        out = sorted(counts.items())
+        if none:
+            out.append((0xFFFFFFFF, none))
+        return out

@@ -1,6 +1,7 @@
 """The corpus index without a GPU: the file order and the binary filter against DirBWTReader's rules, escaping, the checker the
 GPU tests rest on (tests/corpus_ref.py) on the reference's own directories, the X.docs side file, the tool's --dir form, the
-new symbols and their argument errors before any device is touched."""
+new symbols and their argument errors before any device is touched; the listing's reference helpers by hand, and the shapes
+of the generated corpora of tests/corpus_many.py that tests/test_gpu_corpus_many.py relies on."""
 import ctypes
 import os
 import re
@@ -11,6 +12,7 @@ import sys
 import numpy as np
 import pytest
 
+import corpus_many
 import corpus_ref
 import findex_amd
 from conftest import ROOT, TESTDATA
@@ -216,3 +218,121 @@ def test_argument_errors_before_any_device():
         assert b"no CPU fallback" in L.fmx_last_error()
         with pytest.raises(findex_amd.FmxError):
             findex_amd.Corpus.from_documents([b"abc"])
+
+
+# ---- the listing's reference helpers and the corpora of tests/test_gpu_corpus_many.py
+def test_doc_counts_and_list_positions_by_hand():
+    docs = [b"\x00aa\xff", b"", b"aaa", b"b\x01aab", b"\\a"]
+    ref = corpus_ref.RefCorpus(docs)
+    assert ref.stream == b"\\0aa\\f\x01" b"\x01" b"aaa\x01" b"b\\1aab\x01" b"\\a\x01"
+    assert ref.doc_start == [0, 7, 8, 12, 19, 22] and ref.esc_pos == [0, 4, 13]
+    # a query that overlaps itself: "aa" stands twice in "aaa"
+    assert ref.occurrences(b"aa") == [(0, 1), (2, 0), (2, 1), (3, 2)]
+    assert ref.doc_counts(b"aa") == [(0, 1), (2, 2), (3, 1)]
+    assert ref.doc_counts(b"a") == [(0, 2), (2, 3), (3, 2), (4, 1)]
+    assert ref.doc_counts(b"\x00") == [(0, 1)] and ref.doc_counts(b"\xff") == [(0, 1)] and ref.doc_counts(b"\x01a") == [(3, 1)]
+    assert ref.doc_counts(b"\\") == [(4, 1)] and ref.doc_counts(b"zz") == [] and ref.doc_counts(b"ab") == [(3, 1)]
+    # positions: both bytes of the escapes at a document's first and last byte, separators (the empty document's too), None
+    assert ref.list_positions([]) == []
+    assert ref.list_positions([0, 1, 4, 5, 6]) == [(0, 5)]
+    assert ref.list_positions([7]) == [(1, 1)]
+    assert ref.list_positions([21, 7, None, 8, 0, 10, None, 11, 19, 12]) == [(0, 1), (1, 1), (2, 3), (3, 1), (4, 2), (0xFFFFFFFF, 2)]
+    assert ref.list_positions([None]) == [(0xFFFFFFFF, 1)]
+    assert ref.list_positions(range(len(ref.stream))) == [(0, 7), (1, 1), (2, 4), (3, 7), (4, 3)]
+    assert corpus_many.expected_doc_counts(ref, b"\\") == [(0, 2), (3, 1), (4, 1)]
+    assert corpus_many.expected_occurrences(ref, b"\\") == [(0, 0), (0, 3), (3, 1), (4, 0)]
+    off, doc, cnt = corpus_many.csr([[(0, 1), (2, 2)], [], [(4, 7)]])
+    assert off.tolist() == [0, 2, 2, 3] and doc.tolist() == [0, 2, 4] and cnt.tolist() == [1, 2, 7]
+    assert doc.dtype == np.uint32 and cnt.dtype == np.uint32 and off.dtype == np.uint64
+
+
+def _stream_finds(ref, esc):
+    out, i = [], ref.stream.find(esc)
+    while i >= 0:
+        out.append(i)
+        i = ref.stream.find(esc, i + 1)
+    return out
+
+
+@pytest.fixture(scope="module")
+def many():
+    return {name: corpus_ref.RefCorpus(corpus_many.documents(name)) for name in corpus_many.CORPORA}
+
+
+def test_doc_counts_equal_the_listing_of_the_stream_positions(many):
+    """For a query without a backslash the escaped query stands in the stream exactly where the query stands in the files."""
+    for name in ("D256", "D5000"):
+        ref = many[name]
+        for q in corpus_many.QUERIES:
+            if b"\\" in q:
+                continue
+            assert ref.doc_counts(q) == ref.list_positions(_stream_finds(ref, corpus_ref.escape_bytes(q))), (name, q)
+        # the lone backslash: every escape pair begins with one (the union corpus_many states)
+        assert corpus_many.expected_doc_counts(ref, b"\\") == ref.list_positions(_stream_finds(ref, b"\\"))
+
+
+def test_many_document_corpora_have_the_shapes_their_tests_are_for(many):
+    bits = {"D255": 8, "D256": 9, "D257": 9, "D5000": 13, "D65537": 17}
+    for name, ref in many.items():
+        n_docs = corpus_many.CORPORA[name][0]
+        assert len(ref.docs) == n_docs and corpus_many.lib_bits(n_docs) == bits[name]
+        assert len(ref.stream) < 1 << 20
+        for c in (b"0", b"1", b"f"):                              # no raw text reads like an escape pair
+            assert all(c not in d for d in ref.docs)
+        # the documents placed by hand
+        for at, placed in corpus_many.hand_placed(n_docs).items():
+            assert ref.docs[at:at + len(placed)] == placed
+        a, b, c = n_docs // 3, n_docs // 2, (2 * n_docs) // 3
+        assert ref.docs[0] == b"" and ref.docs[-1] == b"" and ref.docs[c:c + 3] == [b"", b"", b""]
+        assert ref.docs[a] in (b"\x00", b"\x01", b"\xff") and len(ref.docs[a + 2]) == 1 and len(ref.docs[a + 3]) == 1
+        assert ref.doc_start[a] in ref.esc_pos and ref.doc_start[a + 2] in ref.esc_pos and ref.doc_start[a + 3] in ref.esc_pos
+        assert ref.doc_start[b] in ref.esc_pos and ref.doc_start[b + 3] - 3 in ref.esc_pos
+        empty = sum(1 for d in ref.docs if not d)
+        mean = sum(ref.raw_len) / n_docs
+        if name == "D65537":
+            assert 0.45 * n_docs < empty < 0.55 * n_docs and 1.5 < mean < 2.5
+        else:
+            assert 0.02 * n_docs < empty < 0.10 * n_docs and 22 < mean < 34
+    # D5000 under the query set: a second radix tile, listings of hundreds of documents, empty documents between hits, misses
+    ref = many["D5000"]
+    per = {q: corpus_many.expected_doc_counts(ref, q) for q in corpus_many.QUERIES}
+    assert max(sum(c for _, c in p) for p in per.values()) > 4096
+    assert max(len(p) for p in per.values()) > 256
+    assert sum(1 for p in per.values() if not p) >= 1 and all(per[q] == [] for q in corpus_many.MISSES)
+    skips = 0
+    for p in per.values():
+        for (d0, _), (d1, _) in zip(p, p[1:]):
+            skips += any(not ref.docs[d] for d in range(d0 + 1, d1))
+    assert skips >= 1
+    assert len(set(corpus_many.QUERIES)) == len(corpus_many.QUERIES) == 4 + 16 + 64 + 6 + 2
+    # the escaped lengths that share a listing call: 1-grams with the backslash, ..., a miss among the 3-grams, a call of misses only
+    by_len = {}
+    for q in corpus_many.QUERIES:
+        by_len.setdefault(len(corpus_ref.escape_bytes(q)), []).append(q)
+    assert sorted(by_len) == [1, 2, 3, 4] and b"azb" in by_len[3] and by_len[4] == [b"abzd"]
+
+
+def test_key_width_cases_reach_their_bits_and_rows(many):
+    for name, k, bits, passes in corpus_many.WIDTH_CASES:
+        ref = many[name]
+        assert corpus_many.lib_bits(len(ref.docs)) + corpus_many.lib_bits(k) == bits and (bits + 7) // 8 == passes
+        g, tokens, rows = corpus_many.width_case(ref, k)
+        assert len(tokens) == k and rows <= corpus_many.MAX_ROWS
+        counts = corpus_many.gram_counts(ref, g)
+        assert rows == sum(counts[w] for kind, w in tokens if kind == "hit")
+        for w in sorted({w for kind, w in tokens if kind == "hit"})[:8]:      # the sizing pass counts what the reference finds
+            assert counts[w] == len(ref.occurrences(w)) > 0
+        if k > 1:
+            kinds = [kind for kind, _ in tokens]
+            assert kinds[0] == "miss" and kinds[-1] == "miss" and "inverted" in kinds and "miss" in kinds[1:-1]
+            hits = {w for kind, w in tokens if kind == "hit"}
+            assert len(hits) >= 4
+            # the top bit of the key is in use unless k is a power of two: the last interval with rows has it set
+            last = max(i for i, (kind, _) in enumerate(tokens) if kind == "hit")
+            assert (corpus_many.lib_bits(last) == corpus_many.lib_bits(k)) == (k & (k - 1) != 0)
+        if name != "D255":
+            assert rows > 4096 * 16                               # many radix tiles, a scan with block totals
+        if name in ("D5000", "D65537"):
+            assert rows >= 1 << 20
+    assert {("D255", 1, 9, 2), ("D256", 127, 16, 2), ("D256", 128, 17, 3), ("D5000", 2047, 24, 3), ("D5000", 2048, 25, 4),
+            ("D5000", 70000, 30, 4), ("D65537", 40000, 33, 5)} <= set(corpus_many.WIDTH_CASES)
