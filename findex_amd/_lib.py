@@ -7,6 +7,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FMX_LIB") or os.path.join(_HERE, "lib", "libfmx.so")     # FMX_LIB: A/B runs of two builds
 
 FMX_OK = 0
+FMX_ERR_OVERFLOW = 9
 ERR_NAMES = {1: "FMX_ERR_IO", 2: "FMX_ERR_FORMAT", 3: "FMX_ERR_ARG", 4: "FMX_ERR_NOMEM", 5: "FMX_ERR_HIP",
              6: "FMX_ERR_UNSUPPORTED", 7: "FMX_ERR_SYNTAX", 8: "FMX_ERR_MATCH", 9: "FMX_ERR_OVERFLOW"}
 

@@ -38,12 +38,12 @@ static std::atomic<int> g_pipeline{0};
 bool validate_device_operands() { return g_validate.load(std::memory_order_relaxed) != 0; }
 bool force_superblocks() { return g_force_superblocks.load(std::memory_order_relaxed) != 0; }
 
-static int arg_fail(const char *msg) {
+int arg_fail(const char *msg) {
   g_err = msg;
   return FMX_ERR_ARG;
 }
 
-static int use_device(const Index *h) {
+int use_device(const Index *h) {
   HIP_TRY(hipSetDevice(h->device), "hipSetDevice");
   return FMX_OK;
 }
@@ -383,9 +383,6 @@ static int open_common(const void *src, bool src_on_device, FILE *src_file, uint
   return FMX_OK;
 }
 
-static inline Index *H(fmx_index *p) { return reinterpret_cast<Index *>(p); }
-static inline const Index *H(const fmx_index *p) { return reinterpret_cast<const Index *>(p); }
-
 // Operands in, kernel, results out.  Where the kernel finds its operands and leaves its results depends on how much travels:
 //   tiny (the single-query forms a per-call adapter makes: getPrevRange / occ / search): in the page-locked staging buffer
 //     itself -- the kernel reads its few operand bytes over the link and writes its results there (the buffer is mapped into
@@ -457,6 +454,36 @@ static int run_io(const Index *h, const HostIn *ins, int nin, const HostOut *out
     o += up16(outs[j].bytes);
   }
   return FMX_OK;
+}
+
+bool offsets_monotonic(const uint64_t *off, size_t a, size_t b) {
+  unsigned bad = 0;
+  for (size_t q = a; q < b; q++) bad |= off[q + 1] < off[q];
+  return bad == 0;
+}
+
+// ---- the host-pointer calls of the metered features (fmx_host.h, HostCall)
+int HostCall::upload(const char *pat_what, const void *pat, uint64_t bytes, const char *off_what, const uint64_t *off, size_t k,
+                     bool rebase, void **d_pat, uint64_t **d_off) {
+  const uint64_t off_bytes = 8 * ((uint64_t)k + 1);
+  int rc;
+  if ((rc = mem.take(d_pat, bytes, pat_what)) || (rc = mem.take((void **)d_off, off_bytes, off_what))) return rc;
+  if (rebase && !k) return FMX_OK;
+  std::vector<uint64_t> rebased;                           // only the bytes in use travel
+  if (rebase) {
+    rebased.resize(k + 1);
+    for (size_t q = 0; q <= k; q++) rebased[q] = off[q] - off[0];
+    off = rebased.data();
+  }
+  if (k) HIP_TRY(hipMemcpyAsync(*d_off, off, off_bytes, hipMemcpyHostToDevice, own.s), "H2D(offsets)");
+  else HIP_TRY(hipMemsetAsync(*d_off, 0, 8, own.s), "memset");
+  if (bytes) HIP_TRY(hipMemcpyAsync(*d_pat, pat, bytes, hipMemcpyHostToDevice, own.s), "H2D(patterns)");
+  return sync();
+}
+
+int csr_overflow(const char *prefix, uint64_t total, size_t cap) {
+  g_err = std::string(prefix) + ": " + std::to_string(total) + " hits, room for " + std::to_string(cap);
+  return FMX_ERR_OVERFLOW;
 }
 
 }  // namespace fmx
@@ -857,12 +884,6 @@ struct HostBatch {
     return launch_search(h, d_pat, off ? d_off : nullptr, d_sp, d_ep, k, st, fixed_len, pack_cap, flags);
   }
 };
-
-static bool offsets_monotonic(const uint64_t *off, size_t a, size_t b) {      // off[a] <= off[a+1] <= .. <= off[b]
-  unsigned bad = 0;
-  for (size_t q = a; q < b; q++) bad |= off[q + 1] < off[q];
-  return bad == 0;
-}
 
 // (i) Whatever refuses a batch before a byte travels, in the order the failures are reported, and the batch as the paths
 // below take it (b->k == 0: an empty one, answered here).  The lean forms (round 4): equal-length patterns travel without
@@ -1658,341 +1679,6 @@ int fmx_write_bwt(const char *bwt_path, const char *aux_path, const uint8_t *bwt
   if (!f) { g_err = std::string("cannot create ") + aux_path; return FMX_ERR_IO; }
   const bool ok = std::fwrite(aux, 1, sizeof aux, f) == sizeof aux;
   if ((std::fclose(f) != 0) || !ok) { g_err = std::string("short write on ") + aux_path; return FMX_ERR_IO; }
-  return FMX_OK;
-}
-
-// ---------------------------------------------------------------- approximate search (fmx_approx.hip)
-static thread_local ApproxInfo g_approx_last;
-
-// What refuses a call before the device is touched; the budget and the range as the kernel takes them.
-static int approx_args(const fmx_index *idx, size_t k, const fmx_approx_opts *opts, const void *out_off, const void *out, size_t cap,
-                       const size_t *n_out, uint32_t *e, uint32_t *lo, uint32_t *hi) {
-  if (!n_out) return arg_fail("approx: n_out is null");
-  *e = 0; *lo = 1; *hi = 255;
-  if (opts) {
-    if (opts->max_mismatches > FMX_APPROX_MAX_MISMATCHES) return arg_fail("fmx_approx_opts.max_mismatches: 0 .. 3");
-    if (opts->reserved != 0) return arg_fail("fmx_approx_opts.reserved must be 0");
-    if ((opts->sub_lo == 0) != (opts->sub_hi == 0)) return arg_fail("fmx_approx_opts: symbol 0 is never substituted (sub_lo >= 1; 0, 0 = the default range)");
-    if (opts->sub_lo > opts->sub_hi) return arg_fail("fmx_approx_opts: sub_lo > sub_hi");
-    *e = opts->max_mismatches;
-    if (opts->sub_lo) { *lo = opts->sub_lo; *hi = opts->sub_hi; }
-  }
-  if ((uint64_t)k > (1ull << 26)) return arg_fail("approx: at most 2^26 patterns per call");
-  if ((uint64_t)cap >= (1ull << 32)) return arg_fail("approx: cap must be below 2^32");
-  if (!out_off || (cap && !out)) return arg_fail("null argument");
-  if (!idx) return arg_fail("approx: the handle is null");
-  return approx_check(H(idx));
-}
-
-static int approx_overflow(const ApproxInfo &info, size_t cap) {
-  g_err = "search_approx: " + std::to_string(info.total) + " hits, room for " + std::to_string(cap);
-  return FMX_ERR_OVERFLOW;
-}
-
-int fmx_search_approx_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k, const fmx_approx_opts *opts,
-                                void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream) {
-  uint32_t e, lo, hi;
-  int rc = approx_args(idx, k, opts, d_out_off, d_out, cap, n_out, &e, &lo, &hi);
-  if (rc) return rc;
-  if (k && !d_off) return arg_fail("null argument");
-  const Index *h = H(idx);
-  if ((rc = use_device(h))) return rc;
-  if ((rc = not_capturing((hipStream_t)stream, "an approximate search"))) return rc;
-  ApproxInfo info;
-  rc = approx_search(h, d_pat, d_off, k, e, lo, hi, d_out_off, d_out, cap, (hipStream_t)stream, &info);
-  g_approx_last = info;
-  if (rc) return rc;
-  *n_out = (size_t)info.total;
-  return info.total > cap ? approx_overflow(info, cap) : FMX_OK;
-}
-
-int fmx_search_approx_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k, const fmx_approx_opts *opts,
-                            uint64_t *out_off, fmx_approx_hit *out, size_t cap, size_t *n_out) {
-  uint32_t e, lo, hi;
-  if (k && (uint64_t)k <= (1ull << 26) && off && !offsets_monotonic(off, 0, k)) return arg_fail("pattern offsets must be non-decreasing");
-  int rc = approx_args(idx, k, opts, out_off, out, cap, n_out, &e, &lo, &hi);
-  if (rc) return rc;
-  if (k && !off) return arg_fail("null argument");
-  const uint64_t lo_off = k ? off[0] : 0, total_bytes = k ? off[k] - lo_off : 0;
-  if (total_bytes && !pat) return arg_fail("pat is null");
-  const Index *h = H(idx);
-  if ((rc = use_device(h))) return rc;
-  DevMem mem;
-  StreamGuard own;
-  HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
-  uint8_t *d_pat = nullptr;
-  uint64_t *d_off = nullptr, *d_out_off = nullptr;
-  fmx_approx_hit *d_out = nullptr;
-  DEV_ALLOC(mem, d_pat, total_bytes, "approx patterns");
-  DEV_ALLOC(mem, d_off, 8 * (k + 1), "approx offsets");
-  DEV_ALLOC(mem, d_out_off, 8 * (k + 1), "approx offsets");
-  DEV_ALLOC(mem, d_out, sizeof(fmx_approx_hit) * cap, "approx hits");
-  if (k) {
-    std::vector<uint64_t> rebased(k + 1);                  // only the bytes in use travel
-    for (size_t q = 0; q <= k; q++) rebased[q] = off[q] - lo_off;
-    HIP_TRY(hipMemcpyAsync(d_off, rebased.data(), 8 * (k + 1), hipMemcpyHostToDevice, own.s), "H2D(offsets)");
-    if (total_bytes) HIP_TRY(hipMemcpyAsync(d_pat, pat + lo_off, total_bytes, hipMemcpyHostToDevice, own.s), "H2D(patterns)");
-    HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
-  }
-  ApproxInfo info;
-  rc = approx_search(h, d_pat, d_off, k, e, lo, hi, d_out_off, d_out, cap, own.s, &info);
-  g_approx_last = info;
-  if (rc) return rc;
-  *n_out = (size_t)info.total;
-  if (info.total > cap) return approx_overflow(info, cap);
-  HIP_TRY(hipMemcpyAsync(out_off, d_out_off, 8 * (k + 1), hipMemcpyDeviceToHost, own.s), "D2H(offsets)");
-  if (info.total) HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(fmx_approx_hit) * info.total, hipMemcpyDeviceToHost, own.s), "D2H(hits)");
-  HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
-  return FMX_OK;
-}
-
-int fmx_approx_last(double *search_ms, double *sort_ms, uint64_t *steps, uint64_t *requests) {
-  if (search_ms) *search_ms = g_approx_last.search_ms;
-  if (sort_ms) *sort_ms = g_approx_last.sort_ms;
-  if (steps) *steps = g_approx_last.steps;
-  if (requests) *requests = g_approx_last.requests;
-  return FMX_OK;
-}
-
-// ---------------------------------------------------------------- matching statistics and MEMs (fmx_mstat.hip)
-static thread_local MstatInfo g_mstat_last;
-
-// What refuses a call before the device is touched; max_len and min_len as the kernels take them.
-static int mstat_args(const fmx_index *idx, size_t k, uint64_t n_bytes, const fmx_mstat_opts *opts, uint32_t *max_len,
-                      uint32_t *min_len) {
-  *max_len = FMX_MSTAT_MAX_LEN;
-  *min_len = 1;
-  if (opts) {
-    if (opts->max_len > FMX_MSTAT_MAX_LEN) return arg_fail("fmx_mstat_opts.max_len: 1 .. 4096 (0 = the maximum)");
-    if (opts->reserved[0] != 0 || opts->reserved[1] != 0) return arg_fail("fmx_mstat_opts.reserved must be 0");
-    if (opts->max_len) *max_len = opts->max_len;
-    if (opts->min_len > *max_len) return arg_fail("fmx_mstat_opts: min_len > max_len");
-    if (opts->min_len) *min_len = opts->min_len;
-  }
-  if ((uint64_t)k > (1ull << 26)) return arg_fail("matching statistics: at most 2^26 patterns per call");
-  if (n_bytes >= (1ull << 32)) return arg_fail("matching statistics: n_bytes must be below 2^32");
-  if (!idx) return arg_fail("matching statistics: the handle is null");
-  return mstat_check(H(idx));
-}
-
-// the host forms' offsets: off[0] == 0, non-decreasing; *n_bytes = off[k]
-static int mstat_host_offsets(const uint64_t *off, size_t k, uint64_t *n_bytes) {
-  *n_bytes = 0;
-  if ((uint64_t)k > (1ull << 26)) return FMX_OK;           // (refused by mstat_args, with its own message)
-  if (k && !off) return arg_fail("null argument");
-  if (k && off[0] != 0) return arg_fail("matching statistics: off[0] must be 0");
-  if (k && !offsets_monotonic(off, 0, k)) return arg_fail("pattern offsets must be non-decreasing");
-  *n_bytes = k ? off[k] : 0;
-  return FMX_OK;
-}
-
-static int mems_overflow(const MstatInfo &info, size_t cap) {
-  g_err = "mems: " + std::to_string(info.total) + " hits, room for " + std::to_string(cap);
-  return FMX_ERR_OVERFLOW;
-}
-
-int fmx_match_stats_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k, uint64_t n_bytes,
-                              const fmx_mstat_opts *opts, void *d_len, void *d_sp, void *d_ep, void *stream) {
-  uint32_t max_len, min_len;
-  if (n_bytes && !d_len) return arg_fail("matching statistics: d_len is null");
-  int rc = mstat_args(idx, k, n_bytes, opts, &max_len, &min_len);
-  if (rc) return rc;
-  if (n_bytes && (!d_pat || !d_off)) return arg_fail("null argument");
-  const Index *h = H(idx);
-  if ((rc = use_device(h))) return rc;
-  HIP_TRY(mstat_enqueue(h, d_pat, d_off, k, n_bytes, max_len, d_len, d_sp, d_ep, nullptr, (hipStream_t)stream), "k_mstat");
-  return FMX_OK;
-}
-
-// the host forms' upload: patterns and offsets into the bag
-static int mstat_upload(DevMem &mem, const uint8_t *pat, const uint64_t *off, size_t k, uint64_t n_bytes, uint8_t **d_pat,
-                        uint64_t **d_off, hipStream_t st) {
-  DEV_ALLOC(mem, *d_pat, n_bytes, "patterns");
-  DEV_ALLOC(mem, *d_off, 8 * ((uint64_t)k + 1), "offsets");
-  if (k) HIP_TRY(hipMemcpyAsync(*d_off, off, 8 * ((uint64_t)k + 1), hipMemcpyHostToDevice, st), "H2D(offsets)");
-  else HIP_TRY(hipMemsetAsync(*d_off, 0, 8, st), "memset");
-  if (n_bytes) HIP_TRY(hipMemcpyAsync(*d_pat, pat, n_bytes, hipMemcpyHostToDevice, st), "H2D(patterns)");
-  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
-  return FMX_OK;
-}
-
-int fmx_match_stats_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k, const fmx_mstat_opts *opts,
-                          uint32_t *out_len, uint64_t *out_sp, uint64_t *out_ep) {
-  uint32_t max_len, min_len;
-  uint64_t n_bytes;
-  int rc = mstat_host_offsets(off, k, &n_bytes);
-  if (rc) return rc;
-  if (n_bytes && n_bytes < (1ull << 32) && (!out_len || !pat)) return arg_fail("matching statistics: null argument");
-  if ((rc = mstat_args(idx, k, n_bytes, opts, &max_len, &min_len))) return rc;
-  const Index *h = H(idx);
-  if ((rc = use_device(h))) return rc;
-  const uint64_t outs = n_bytes * (4 + (out_sp ? 8 : 0) + (out_ep ? 8 : 0));
-  if ((rc = mstat_room(mstat_bytes(n_bytes, false) + n_bytes + 8 * ((uint64_t)k + 1) + outs + 64, "fmx_match_stats_batch"))) return rc;
-  DevMem mem;
-  StreamGuard own;
-  HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
-  uint8_t *d_pat = nullptr;
-  uint64_t *d_off = nullptr, *d_sp = nullptr, *d_ep = nullptr;
-  uint32_t *d_len = nullptr;
-  if ((rc = mstat_upload(mem, pat, off, k, n_bytes, &d_pat, &d_off, own.s))) return rc;
-  DEV_ALLOC(mem, d_len, 4 * n_bytes, "matching statistics");
-  if (out_sp) DEV_ALLOC(mem, d_sp, 8 * n_bytes, "matching statistics");
-  if (out_ep) DEV_ALLOC(mem, d_ep, 8 * n_bytes, "matching statistics");
-  MstatInfo info;
-  rc = mstat_run(h, d_pat, d_off, k, n_bytes, max_len, min_len, d_len, d_sp, d_ep, false, nullptr, nullptr, 0, own.s, &info);
-  g_mstat_last = info;
-  if (rc) return rc;
-  if (n_bytes) {
-    HIP_TRY(hipMemcpyAsync(out_len, d_len, 4 * n_bytes, hipMemcpyDeviceToHost, own.s), "D2H(len)");
-    if (out_sp) HIP_TRY(hipMemcpyAsync(out_sp, d_sp, 8 * n_bytes, hipMemcpyDeviceToHost, own.s), "D2H(sp)");
-    if (out_ep) HIP_TRY(hipMemcpyAsync(out_ep, d_ep, 8 * n_bytes, hipMemcpyDeviceToHost, own.s), "D2H(ep)");
-    HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
-  }
-  return FMX_OK;
-}
-
-static int mems_args(const void *out_off, const void *out, size_t cap, const size_t *n_out) {
-  if (!n_out) return arg_fail("mems: n_out is null");
-  if ((uint64_t)cap >= (1ull << 32)) return arg_fail("mems: cap must be below 2^32");
-  if (!out_off || (cap && !out)) return arg_fail("null argument");
-  return FMX_OK;
-}
-
-int fmx_mems_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k, uint64_t n_bytes,
-                       const fmx_mstat_opts *opts, void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream) {
-  uint32_t max_len, min_len;
-  int rc = mems_args(d_out_off, d_out, cap, n_out);
-  if (rc) return rc;
-  if ((rc = mstat_args(idx, k, n_bytes, opts, &max_len, &min_len))) return rc;
-  if (!d_off || (n_bytes && !d_pat)) return arg_fail("null argument");
-  const Index *h = H(idx);
-  if ((rc = use_device(h))) return rc;
-  if ((rc = not_capturing((hipStream_t)stream, "a MEM call"))) return rc;
-  MstatInfo info;
-  rc = mstat_run(h, d_pat, d_off, k, n_bytes, max_len, min_len, nullptr, nullptr, nullptr, true, d_out_off, d_out, cap,
-                 (hipStream_t)stream, &info);
-  g_mstat_last = info;
-  if (rc) return rc;
-  *n_out = (size_t)info.total;
-  return info.total > cap ? mems_overflow(info, cap) : FMX_OK;
-}
-
-int fmx_mems_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k, const fmx_mstat_opts *opts,
-                   uint64_t *out_off, fmx_mem_hit *out, size_t cap, size_t *n_out) {
-  uint32_t max_len, min_len;
-  uint64_t n_bytes;
-  int rc = mems_args(out_off, out, cap, n_out);
-  if (rc) return rc;
-  if ((rc = mstat_host_offsets(off, k, &n_bytes))) return rc;
-  if (n_bytes && n_bytes < (1ull << 32) && !pat) return arg_fail("pat is null");
-  if ((rc = mstat_args(idx, k, n_bytes, opts, &max_len, &min_len))) return rc;
-  const Index *h = H(idx);
-  if ((rc = use_device(h))) return rc;
-  if ((rc = mstat_room(mstat_bytes(n_bytes, true) + n_bytes + 16 * ((uint64_t)k + 1) + sizeof(fmx_mem_hit) * (uint64_t)cap + 64,
-                       "fmx_mems_batch"))) return rc;
-  DevMem mem;
-  StreamGuard own;
-  HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
-  uint8_t *d_pat = nullptr;
-  uint64_t *d_off = nullptr, *d_out_off = nullptr;
-  fmx_mem_hit *d_out = nullptr;
-  if ((rc = mstat_upload(mem, pat, off, k, n_bytes, &d_pat, &d_off, own.s))) return rc;
-  DEV_ALLOC(mem, d_out_off, 8 * ((uint64_t)k + 1), "MEM offsets");
-  DEV_ALLOC(mem, d_out, sizeof(fmx_mem_hit) * cap, "MEM hits");
-  MstatInfo info;
-  rc = mstat_run(h, d_pat, d_off, k, n_bytes, max_len, min_len, nullptr, nullptr, nullptr, true, d_out_off, d_out, cap, own.s, &info);
-  g_mstat_last = info;
-  if (rc) return rc;
-  *n_out = (size_t)info.total;
-  if (info.total > cap) return mems_overflow(info, cap);
-  HIP_TRY(hipMemcpyAsync(out_off, d_out_off, 8 * ((uint64_t)k + 1), hipMemcpyDeviceToHost, own.s), "D2H(offsets)");
-  if (info.total) HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(fmx_mem_hit) * info.total, hipMemcpyDeviceToHost, own.s), "D2H(hits)");
-  HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
-  return FMX_OK;
-}
-
-int fmx_mstat_last(double *walk_ms, double *compact_ms, uint64_t *steps, uint64_t *requests) {
-  if (walk_ms) *walk_ms = g_mstat_last.walk_ms;
-  if (compact_ms) *compact_ms = g_mstat_last.compact_ms;
-  if (steps) *steps = g_mstat_last.steps;
-  if (requests) *requests = g_mstat_last.requests;
-  return FMX_OK;
-}
-
-// ---------------------------------------------------------------- extract: text by position (fmx_extract.hip)
-static thread_local ExtractInfo g_extract_last;
-
-int fmx_extract_text_batch(const fmx_index *idx, const uint64_t *pos, const uint64_t *off, size_t k, uint8_t *out) {
-  if ((uint64_t)k > (1ull << 26)) return arg_fail("extract: at most 2^26 ranges per call");
-  if (k && (!pos || !off)) return arg_fail("extract: null argument");
-  if (k && off[0] != 0) return arg_fail("extract: off[0] must be 0");
-  if (k && !offsets_monotonic(off, 0, k)) return arg_fail("extract: range offsets must be non-decreasing");
-  const uint64_t n_bytes = k ? off[k] : 0;
-  if (n_bytes >= (1ull << 32)) return arg_fail("extract: n_bytes = off[k] must be below 2^32");
-  if (n_bytes && !out) return arg_fail("extract: null argument (out)");
-  if (!idx) return arg_fail("extract: the handle is null");
-  const Index *h = H(idx);
-  int rc = extract_check(h);
-  if (rc) return rc;
-  const uint64_t len = h->n - 1;
-  for (size_t q = 0; q < k; q++) {
-    const uint64_t l = off[q + 1] - off[q];
-    if (pos[q] > len || l > len - pos[q]) return arg_fail("extract: a range runs past the text (pos + length <= n - 1)");
-  }
-  if (!n_bytes) return FMX_OK;
-  if ((rc = use_device(h))) return rc;
-  if ((rc = ensure_built(h, h->ext_mu, h->ext_ready, extract_prepare, nullptr))) return rc;
-  if ((rc = mstat_room(extract_bytes() + n_bytes + 16 * ((uint64_t)k + 1) + 64, "fmx_extract_text_batch"))) return rc;
-  DevMem mem;
-  StreamGuard own;
-  HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
-  uint64_t *d_pos = nullptr, *d_off = nullptr;
-  uint8_t *d_out = nullptr;
-  DEV_ALLOC(mem, d_pos, 8 * (uint64_t)k, "positions");
-  DEV_ALLOC(mem, d_off, 8 * ((uint64_t)k + 1), "offsets");
-  DEV_ALLOC(mem, d_out, n_bytes, "text");
-  HIP_TRY(hipMemcpyAsync(d_pos, pos, 8 * (uint64_t)k, hipMemcpyHostToDevice, own.s), "H2D(positions)");
-  HIP_TRY(hipMemcpyAsync(d_off, off, 8 * ((uint64_t)k + 1), hipMemcpyHostToDevice, own.s), "H2D(offsets)");
-  HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
-  ExtractInfo info;
-  rc = extract_run(h, d_pos, d_off, k, n_bytes, d_out, own.s, &info);
-  g_extract_last = info;
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(out, d_out, n_bytes, hipMemcpyDeviceToHost, own.s), "D2H(text)");
-  HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
-  return FMX_OK;
-}
-
-int fmx_extract_text_batch_dev(const fmx_index *idx, const void *d_pos, const void *d_off, size_t k, uint64_t n_bytes,
-                               void *d_out, void *stream) {
-  if ((uint64_t)k > (1ull << 26)) return arg_fail("extract: at most 2^26 ranges per call");
-  if (n_bytes >= (1ull << 32)) return arg_fail("extract: n_bytes must be below 2^32");
-  if (k && n_bytes && (!d_pos || !d_off || !d_out)) return arg_fail("extract: null argument");
-  if (!idx) return arg_fail("extract: the handle is null");
-  const Index *h = H(idx);
-  int rc = extract_check(h);
-  if (rc) return rc;
-  if (!k || !n_bytes) return FMX_OK;
-  if ((rc = use_device(h))) return rc;
-  if ((rc = ensure_built(h, h->ext_mu, h->ext_ready, extract_prepare, (hipStream_t)stream))) return rc;
-  HIP_TRY(extract_enqueue(h, d_pos, d_off, k, n_bytes, d_out, nullptr, (hipStream_t)stream), "k_extract");
-  return FMX_OK;
-}
-
-int fmx_extract_info(const fmx_index *idx, uint32_t *rate, uint64_t *bytes, double *build_ms) {
-  if (!idx) return arg_fail("null argument");
-  const Index *h = H(idx);
-  std::lock_guard<std::mutex> lk(h->ext_mu);
-  if (rate) *rate = h->ext_ready ? h->ext_rate : (uint32_t)h->policy.extract_sample.load(std::memory_order_relaxed);
-  if (bytes) *bytes = h->ext_ready ? h->ext_bytes : 0;
-  if (build_ms) *build_ms = h->ext_ready ? h->ext_build_ms : 0.0;
-  return FMX_OK;
-}
-
-int fmx_extract_last(double *ms, uint64_t *steps, uint64_t *requests) {
-  if (ms) *ms = g_extract_last.ms;
-  if (steps) *steps = g_extract_last.steps;
-  if (requests) *requests = g_extract_last.requests;
   return FMX_OK;
 }
 

@@ -32,7 +32,6 @@ constexpr int kApThreads = 256;                // four waves: four patterns per 
 constexpr int kApWaves = kApThreads / 64;
 constexpr uint32_t kApFrames = 2;              // nodes that push have d = 0 .. e - 2
 constexpr int kApRowBits = 38;                 // rows are below 2^38, patterns below 2^26: the sort key
-constexpr uint32_t kApLineWords = 32;          // the call's own words: [0] hits (a 128-byte line of its own), [16] steps, [17] requests
 
 struct ApFrame {
   uint64_t sp, ep, i;                          // the node: its interval and the pattern bytes it has left
@@ -204,28 +203,8 @@ __global__ __launch_bounds__(kApThreads) void k_approx(DevIndex ix, const uint8_
       if (!(sp < ep)) node = false;
     }
   }
-  // the call's own counters: private slots, folded into the handle's afterwards (k_approx_fold)
+  // the call's own counters: private slots, folded into the handle's afterwards (k_counters_fold: fmx_host.h, Metered)
   counters_add(counters, 2ull * steps, steps, reqs);
-}
-
-// The call's counter slots into the handle's, and their sums into the call's line.
-__global__ __launch_bounds__(256) void k_approx_fold(const unsigned long long *__restrict__ mine,
-                                                     unsigned long long *__restrict__ counters,
-                                                     unsigned long long *__restrict__ line) {
-  const uint32_t sl = blockIdx.x * 256u + threadIdx.x;
-  unsigned long long v[3] = {0, 0, 0};
-  if (sl < kCounterSlots) {
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      v[j] = mine[(size_t)sl * kCounterStride + j];
-      if (v[j]) atomicAdd(counters + (size_t)sl * kCounterStride + j, v[j]);
-    }
-  }
-  const unsigned long long s1 = wave_sum(v[1]), s2 = wave_sum(v[2]);
-  if ((threadIdx.x & 63u) == 0) {
-    if (s1) atomicAdd(line + 16, s1);
-    if (s2) atomicAdd(line + 17, s2);
-  }
 }
 
 __global__ __launch_bounds__(256) void k_approx_keys(const unsigned long long *__restrict__ stage, uint64_t rows,
@@ -263,23 +242,19 @@ __global__ __launch_bounds__(256) void k_approx_off(const unsigned long long *__
   }
 }
 
-static uint32_t ap_grid(uint64_t items) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, 4096)); }
-
 template <bool WIDE, uint32_t LAYOUT>
 static hipError_t ap_launch(const Index *h, const uint8_t *pat, const uint64_t *off, uint64_t k, uint32_t e, uint32_t lo,
-                            uint32_t hi, unsigned long long *stage, uint64_t cap, unsigned long long *line,
+                            uint32_t hi, unsigned long long *stage, uint64_t cap, unsigned long long *total,
                             unsigned long long *mine, hipStream_t st) {
-  int per_cu = 0;
-  hipError_t he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_approx<WIDE, LAYOUT>, kApThreads, 0);
+  uint32_t grid = 0;
+  const hipError_t he = resident_grid<k_approx<WIDE, LAYOUT>>(h, kApThreads, k, kApWaves, &grid);
   if (he != hipSuccess) return he;
-  const uint64_t resident = (uint64_t)std::max(per_cu, 1) * (uint64_t)std::max(h->cu_count, 1);
-  const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(resident, (k + kApWaves - 1) / kApWaves));
   hipLaunchKernelGGL((k_approx<WIDE, LAYOUT>), dim3(grid), dim3(kApThreads), 0, st, h->dev, pat, off, k, e, lo, hi, stage, cap,
-                     line, mine);
+                     total, mine);
   return hipGetLastError();
 }
 
-int approx_check(const Index *h) {
+static int approx_check(const Index *h) {
   if (h->block_mode) {
     set_error("approximate search: not for fmx_open_block handles");
     return FMX_ERR_UNSUPPORTED;
@@ -291,48 +266,46 @@ int approx_check(const Index *h) {
   return FMX_OK;
 }
 
-int approx_search(const Index *h, const void *d_pat, const void *d_off, uint64_t k, uint32_t e, uint32_t lo, uint32_t hi,
-                  void *d_out_off, void *d_out, uint64_t cap, hipStream_t st, ApproxInfo *info) {
+struct ApproxInfo {
+  uint64_t total = 0, steps = 0, requests = 0;
+  double search_ms = 0.0, sort_ms = 0.0;      // device events: the search kernel, the ordering step
+};
+
+// The hits of k patterns within e substitutions from [lo, hi], device pointers throughout; allocates, synchronises `st`, frees
+// its temporaries on every path.  info->total is the exact number of hits; when it exceeds cap nothing is ordered and
+// d_out_off / d_out are unspecified.
+static int approx_search(const Index *h, const void *d_pat, const void *d_off, uint64_t k, uint32_t e, uint32_t lo, uint32_t hi,
+                         void *d_out_off, void *d_out, uint64_t cap, hipStream_t st, ApproxInfo *info) {
   *info = ApproxInfo{};
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 3; i++) if (ev[i]) (void)hipEventDestroy(ev[i]); } } evg{ev};
-  for (int i = 0; i < 3; i++) HIP_TRY(hipEventCreate(&ev[i]), "hipEventCreate");
+  Events<3> ev;
+  HIP_TRY(ev.create(), "hipEventCreate");
   DevMem mem;
-  unsigned long long *stage = nullptr, *line = nullptr, *mine = nullptr;
+  unsigned long long *stage = nullptr;
+  Metered own;
+  int rc;
   DEV_ALLOC(mem, stage, 24 * cap, "approx staging");
-  DEV_ALLOC(mem, line, 8 * kApLineWords, "approx");
-  DEV_ALLOC(mem, mine, kCounterBytes, "approx");
-  HIP_TRY(hipMemsetAsync(line, 0, 8 * kApLineWords, st), "memset");
-  HIP_TRY(hipMemsetAsync(mine, 0, kCounterBytes, st), "memset");
-  HIP_TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+  if ((rc = own.alloc(mem, "approx")) || (rc = own.zero(st))) return rc;
+  HIP_TRY(ev.record(0, st), "hipEventRecord");
   if (k) {
 #define FMX_AP_CALL(W, L) \
   HIP_TRY((ap_launch<W, L>(h, static_cast<const uint8_t *>(d_pat), static_cast<const uint64_t *>(d_off), k, e, lo, hi, stage, \
-                           cap, line, mine, st)), "k_approx")
+                           cap, own.line + kLineHits, own.mine, st)), "k_approx")
     FMX_LAYOUT_DISPATCH(h, FMX_AP_CALL);
 #undef FMX_AP_CALL
-    hipLaunchKernelGGL(k_approx_fold, dim3(kCounterSlots / 256), dim3(256), 0, st, mine, h->d_counters, line);
-    HIP_TRY(hipGetLastError(), "k_approx_fold");
+    if ((rc = own.fold(h, 1, st))) return rc;                // counter [1]: the backward steps
   }
-  HIP_TRY(hipEventRecord(ev[1], st), "hipEventRecord");
-  unsigned long long words[kApLineWords];
-  HIP_TRY(hipMemcpyAsync(words, line, sizeof words, hipMemcpyDeviceToHost, st), "D2H");
-  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
-  {
-    std::lock_guard<std::mutex> lk(h->mu);
-    h->launches += k ? 1 : 0;
-  }
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
-  info->search_ms = ms;
-  info->total = words[0];
-  info->steps = words[16];
-  info->requests = words[17];
+  HIP_TRY(ev.record(1, st), "hipEventRecord");
+  MeterCounts cnt;
+  if ((rc = own.finish(h, st, k ? 1 : 0, &cnt))) return rc;
+  info->search_ms = ev.ms(0, 1);
+  info->total = cnt.hits;
+  info->steps = cnt.steps;
+  info->requests = cnt.requests;
   if (info->total > cap) return FMX_OK;                      // the caller reports the overflow; nothing is ordered
   const uint64_t rows = info->total;
   unsigned long long *out_off = static_cast<unsigned long long *>(d_out_off);
   if (rows == 0) {
-    hipLaunchKernelGGL(k_approx_off, dim3(ap_grid(k + 1)), dim3(256), 0, st, nullptr, 0ull, k, out_off);
+    hipLaunchKernelGGL(k_approx_off, dim3(flat_grid(k + 1)), dim3(256), 0, st, nullptr, 0ull, k, out_off);
     HIP_TRY(hipGetLastError(), "k_approx_off");
     HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     return FMX_OK;
@@ -346,7 +319,7 @@ int approx_search(const Index *h, const void *d_pat, const void *d_off, uint64_t
   DEV_ALLOC(mem, v1, 4 * rows, "approx sort");
   DEV_ALLOC(mem, hist, 4 * hist_words, "approx sort");
   DEV_ALLOC(mem, partials, 4 * parts, "approx sort");
-  hipLaunchKernelGGL(k_approx_keys, dim3(ap_grid(rows)), dim3(256), 0, st, stage, rows, k0, v0);
+  hipLaunchKernelGGL(k_approx_keys, dim3(flat_grid(rows)), dim3(256), 0, st, stage, rows, k0, v0);
   HIP_TRY(hipGetLastError(), "k_approx_keys");
   int k_bits = 1;
   while (k_bits < 26 && ((k - 1) >> k_bits) != 0) k_bits++;
@@ -354,16 +327,94 @@ int approx_search(const Index *h, const void *d_pat, const void *d_off, uint64_t
   uint32_t *val = v0, *val_alt = v1;
   int passes = 0;
   HIP_TRY(radix_sort(&key, &val, &key_alt, &val_alt, rows, kApRowBits + k_bits, hist, partials, st, &passes), "radix sort");
-  hipLaunchKernelGGL(k_approx_gather, dim3(ap_grid(rows)), dim3(256), 0, st, stage, val, rows,
+  hipLaunchKernelGGL(k_approx_gather, dim3(flat_grid(rows)), dim3(256), 0, st, stage, val, rows,
                      static_cast<unsigned long long *>(d_out));
   HIP_TRY(hipGetLastError(), "k_approx_gather");
-  hipLaunchKernelGGL(k_approx_off, dim3(ap_grid(k + 1)), dim3(256), 0, st, key, rows, k, out_off);
+  hipLaunchKernelGGL(k_approx_off, dim3(flat_grid(k + 1)), dim3(256), 0, st, key, rows, k, out_off);
   HIP_TRY(hipGetLastError(), "k_approx_off");
-  HIP_TRY(hipEventRecord(ev[2], st), "hipEventRecord");
+  HIP_TRY(ev.record(2, st), "hipEventRecord");
   HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");  // the temporaries go when this returns
-  (void)hipEventElapsedTime(&ms, ev[1], ev[2]);
-  info->sort_ms = ms;
+  info->sort_ms = ev.ms(1, 2);
   return FMX_OK;
 }
 
 }  // namespace fmx
+
+// ---------------------------------------------------------------- the C entry points (fmx.h)
+using namespace fmx;
+
+static thread_local ApproxInfo g_approx_last;
+
+// What refuses a call before the device is touched; the budget and the range as the kernel takes them.
+static int approx_args(const fmx_index *idx, size_t k, const fmx_approx_opts *opts, const void *out_off, const void *out, size_t cap,
+                       const size_t *n_out, uint32_t *e, uint32_t *lo, uint32_t *hi) {
+  if (!n_out) return arg_fail("approx: n_out is null");
+  *e = 0; *lo = 1; *hi = 255;
+  if (opts) {
+    if (opts->max_mismatches > FMX_APPROX_MAX_MISMATCHES) return arg_fail("fmx_approx_opts.max_mismatches: 0 .. 3");
+    if (opts->reserved != 0) return arg_fail("fmx_approx_opts.reserved must be 0");
+    if ((opts->sub_lo == 0) != (opts->sub_hi == 0)) return arg_fail("fmx_approx_opts: symbol 0 is never substituted (sub_lo >= 1; 0, 0 = the default range)");
+    if (opts->sub_lo > opts->sub_hi) return arg_fail("fmx_approx_opts: sub_lo > sub_hi");
+    *e = opts->max_mismatches;
+    if (opts->sub_lo) { *lo = opts->sub_lo; *hi = opts->sub_hi; }
+  }
+  if ((uint64_t)k > (1ull << 26)) return arg_fail("approx: at most 2^26 patterns per call");
+  if ((uint64_t)cap >= (1ull << 32)) return arg_fail("approx: cap must be below 2^32");
+  if (!out_off || (cap && !out)) return arg_fail("null argument");
+  if (!idx) return arg_fail("approx: the handle is null");
+  return approx_check(H(idx));
+}
+
+extern "C" {
+
+int fmx_search_approx_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k, const fmx_approx_opts *opts,
+                                void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream) {
+  uint32_t e, lo, hi;
+  int rc = approx_args(idx, k, opts, d_out_off, d_out, cap, n_out, &e, &lo, &hi);
+  if (rc) return rc;
+  if (k && !d_off) return arg_fail("null argument");
+  const Index *h = H(idx);
+  if ((rc = use_device(h))) return rc;
+  if ((rc = not_capturing((hipStream_t)stream, "an approximate search"))) return rc;
+  rc = approx_search(h, d_pat, d_off, k, e, lo, hi, d_out_off, d_out, cap, (hipStream_t)stream, &g_approx_last);
+  if (rc) return rc;
+  *n_out = (size_t)g_approx_last.total;
+  return g_approx_last.total > cap ? csr_overflow("search_approx", g_approx_last.total, cap) : FMX_OK;
+}
+
+int fmx_search_approx_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k, const fmx_approx_opts *opts,
+                            uint64_t *out_off, fmx_approx_hit *out, size_t cap, size_t *n_out) {
+  uint32_t e, lo, hi;
+  if (k && (uint64_t)k <= (1ull << 26) && off && !offsets_monotonic(off, 0, k)) return arg_fail("pattern offsets must be non-decreasing");
+  int rc = approx_args(idx, k, opts, out_off, out, cap, n_out, &e, &lo, &hi);
+  if (rc) return rc;
+  if (k && !off) return arg_fail("null argument");
+  const uint64_t lo_off = k ? off[0] : 0, total_bytes = k ? off[k] - lo_off : 0;
+  if (total_bytes && !pat) return arg_fail("pat is null");
+  const Index *h = H(idx);
+  if ((rc = use_device(h))) return rc;
+  HostCall hc;
+  void *d_pat = nullptr;
+  uint64_t *d_off = nullptr, *d_out_off = nullptr;
+  fmx_approx_hit *d_out = nullptr;
+  if ((rc = hc.open())) return rc;
+  if ((rc = hc.upload("approx patterns", total_bytes ? pat + lo_off : nullptr, total_bytes, "approx offsets", off, k, true, &d_pat, &d_off))) return rc;
+  DEV_ALLOC(hc.mem, d_out_off, 8 * (k + 1), "approx offsets");
+  DEV_ALLOC(hc.mem, d_out, sizeof(fmx_approx_hit) * cap, "approx hits");
+  rc = approx_search(h, d_pat, d_off, k, e, lo, hi, d_out_off, d_out, cap, hc.own.s, &g_approx_last);
+  if (rc) return rc;
+  const uint64_t total = g_approx_last.total;
+  *n_out = (size_t)total;
+  if (total > cap) return csr_overflow("search_approx", total, cap);
+  return hc.download_csr(out_off, d_out_off, k, out, d_out, total, sizeof(fmx_approx_hit));
+}
+
+int fmx_approx_last(double *search_ms, double *sort_ms, uint64_t *steps, uint64_t *requests) {
+  if (search_ms) *search_ms = g_approx_last.search_ms;
+  if (sort_ms) *sort_ms = g_approx_last.sort_ms;
+  if (steps) *steps = g_approx_last.steps;
+  if (requests) *requests = g_approx_last.requests;
+  return FMX_OK;
+}
+
+}  // extern "C"

@@ -186,7 +186,7 @@ int build_index(Index *h, hipStream_t st, const int64_t *given_counts) {
   const uint64_t nsuper = bytes_layout ? ((h->nblocks >> kSuperShift) + 1) : (h->nblocks + kSuper - 1) / kSuper;
   uint64_t *d_hist = nullptr, *d_tot = nullptr;
   uint16_t *d_sym = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;   // (hist + scan), (fill): kernels only
+  Events<4> ev;                              // 0 .. 1 (hist + scan), 2 .. 3 (fill): kernels only
   int rc = 0;
   hipError_t e = hipSuccess;
   uint64_t tot[256];
@@ -197,20 +197,17 @@ int build_index(Index *h, hipStream_t st, const int64_t *given_counts) {
     break;                                        \
   }
   do {
-    FMX_TRY(hipEventCreate(&ev0), "hipEventCreate");
-    FMX_TRY(hipEventCreate(&ev1), "hipEventCreate");
-    FMX_TRY(hipEventCreate(&ev2), "hipEventCreate");
-    FMX_TRY(hipEventCreate(&ev3), "hipEventCreate");
+    FMX_TRY(ev.create(), "hipEventCreate");
     FMX_TRY(hipMalloc(&d_hist, nsuper * 256 * sizeof(uint64_t)), "hipMalloc(hist)");
     FMX_TRY(hipMalloc(&d_tot, 256 * sizeof(uint64_t)), "hipMalloc(totals)");
     FMX_TRY(hipMalloc(&d_sym, 256 * sizeof(uint16_t)), "hipMalloc(sym)");
-    FMX_TRY(hipEventRecord(ev0, st), "hipEventRecord");
+    FMX_TRY(ev.record(0, st), "hipEventRecord");
     if (bytes_layout) k_hist_bytes<<<(int)nsuper, kBuildThreads, 0, st>>>((const uint8_t *)h->d_bwt, h->n, d_hist);
     else k_hist<<<(int)nsuper, kBuildThreads, 0, st>>>((const uint8_t *)h->d_bwt, h->n, h->eof, d_hist);
     FMX_TRY(hipGetLastError(), "k_hist");
     k_scan<<<256, 256, 0, st>>>(d_hist, nsuper, d_tot);
     FMX_TRY(hipGetLastError(), "k_scan");
-    FMX_TRY(hipEventRecord(ev1, st), "hipEventRecord");
+    FMX_TRY(ev.record(1, st), "hipEventRecord");
     FMX_TRY(hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, st), "copy totals");
     FMX_TRY(hipStreamSynchronize(st), "sync(hist)");
 
@@ -300,7 +297,7 @@ int build_index(Index *h, hipStream_t st, const int64_t *given_counts) {
     }
     FMX_TRY(hipMemcpyAsync((char *)h->d_cf + sizeof h->cf, symtab, sizeof symtab, hipMemcpyHostToDevice, st), "copy symtab");
     FMX_TRY(hipMemcpyAsync(d_sym, sym_of, sizeof sym_of, hipMemcpyHostToDevice, st), "copy sym");
-    FMX_TRY(hipEventRecord(ev2, st), "hipEventRecord");
+    FMX_TRY(ev.record(2, st), "hipEventRecord");
     if (bytes_layout) {
       if (h->nslots) {
         k_fill_bytes<<<(int)nsuper, kBuildThreads, 0, st>>>((const uint8_t *)h->d_bwt, h->nblocks, h->nslots,
@@ -315,11 +312,11 @@ int build_index(Index *h, hipStream_t st, const int64_t *given_counts) {
                                                        (uint32_t *)h->d_bv);
       FMX_TRY(hipGetLastError(), "k_fill");
     }
-    FMX_TRY(hipEventRecord(ev3, st), "hipEventRecord");
+    FMX_TRY(ev.record(3, st), "hipEventRecord");
     FMX_TRY(hipStreamSynchronize(st), "sync(fill)");
     float ms_a = 0, ms_b = 0;                 // the allocations between the two phases are the driver's time, not the build's
-    FMX_TRY(hipEventElapsedTime(&ms_a, ev0, ev1), "hipEventElapsedTime");
-    FMX_TRY(hipEventElapsedTime(&ms_b, ev2, ev3), "hipEventElapsedTime");
+    FMX_TRY(ev.elapsed(0, 1, &ms_a), "hipEventElapsedTime");
+    FMX_TRY(ev.elapsed(2, 3, &ms_b), "hipEventElapsedTime");
     h->build_ms = ms_a + ms_b;
     h->index_bytes = bv_bytes + h->n + sizeof h->cf + sizeof h->slot;
     h->dev.bv = (const uint4 *)h->d_bv;
@@ -338,10 +335,6 @@ int build_index(Index *h, hipStream_t st, const int64_t *given_counts) {
   if (d_hist) (void)hipFree(d_hist);
   if (d_tot) (void)hipFree(d_tot);
   if (d_sym) (void)hipFree(d_sym);
-  if (ev0) (void)hipEventDestroy(ev0);
-  if (ev1) (void)hipEventDestroy(ev1);
-  if (ev2) (void)hipEventDestroy(ev2);
-  if (ev3) (void)hipEventDestroy(ev3);
   return rc;
 }
 

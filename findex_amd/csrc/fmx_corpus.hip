@@ -691,9 +691,8 @@ int fmx_corpus_doc_list_dev(const fmx_corpus *corpus, const fmx_index *idx, cons
   if ((rc = co_use(c))) return rc;
   hipStream_t st = (hipStream_t)stream;
   if ((rc = not_capturing(st, "a document listing"))) return rc;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 5; i++) if (ev[i]) (void)hipEventDestroy(ev[i]); } } evg{ev};
-  for (int i = 0; i < 5; i++) HIP_TRY(hipEventCreate(&ev[i]), "hipEventCreate");
+  Events<5> ev;
+  HIP_TRY(ev.create(), "hipEventCreate");
   DevMem mem;
   unsigned long long *loc_off = nullptr;
   if ((rc = co_room(8 * ((uint64_t)k + 1) + 4096, "a document listing"))) return rc;
@@ -729,18 +728,18 @@ int fmx_corpus_doc_list_dev(const fmx_corpus *corpus, const fmx_index *idx, cons
   DEV_ALLOC(mem, v1, 4 * rows, "corpus");
   DEV_ALLOC(mem, hist, 4 * hist_words, "corpus");
   DEV_ALLOC(mem, partials, 4 * parts, "corpus");
-  HIP_TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+  HIP_TRY(ev.record(0, st), "hipEventRecord");
   if ((rc = fmx_locate_intervals_dev(idx, d_sp, d_ep, k, max_per, loc_off, pos, rows, stream))) return rc;
-  HIP_TRY(hipEventRecord(ev[1], st), "hipEventRecord");
+  HIP_TRY(ev.record(1, st), "hipEventRecord");
   hipLaunchKernelGGL(k_corpus_list_keys, dim3(co_grid(rows)), dim3(kCoThreads), 0, st, c->map(), pos, (uint64_t)rows, loc_off,
                      (uint64_t)k, pat_len, doc_bits, k0, v0);
   HIP_TRY(hipGetLastError(), "k_corpus_list_keys");
-  HIP_TRY(hipEventRecord(ev[2], st), "hipEventRecord");
+  HIP_TRY(ev.record(2, st), "hipEventRecord");
   unsigned long long *key = k0, *key_alt = k1;
   uint32_t *val = v0, *val_alt = v1;
   int passes = 0;
   HIP_TRY(radix_sort(&key, &val, &key_alt, &val_alt, rows, doc_bits + k_bits, hist, partials, st, &passes), "radix sort");
-  HIP_TRY(hipEventRecord(ev[3], st), "hipEventRecord");
+  HIP_TRY(ev.record(3, st), "hipEventRecord");
   uint32_t *head = reinterpret_cast<uint32_t *>(key_alt);           // the free key buffer holds the head flags
   hipLaunchKernelGGL(k_corpus_list_heads, dim3(co_grid(rows)), dim3(kCoThreads), 0, st, key, (uint64_t)rows, head);
   HIP_TRY(hipGetLastError(), "k_corpus_list_heads");
@@ -753,13 +752,9 @@ int fmx_corpus_doc_list_dev(const fmx_corpus *corpus, const fmx_index *idx, cons
                        (uint64_t)cap, static_cast<uint32_t *>(d_out_doc), static_cast<uint32_t *>(d_out_cnt));
     HIP_TRY(hipGetLastError(), "k_corpus_list_emit");
   }
-  HIP_TRY(hipEventRecord(ev[4], st), "hipEventRecord");
+  HIP_TRY(ev.record(4, st), "hipEventRecord");
   HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");        // the temporaries go when this returns
-  for (int i = 0; i < 4; i++) {
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
-    g_list_phases[i] = ms;
-  }
+  for (int i = 0; i < 4; i++) g_list_phases[i] = ev.ms(i, i + 1);
   return FMX_OK;
 }
 

@@ -464,6 +464,13 @@ __device__ __forceinline__ void counters_add(unsigned long long *__restrict__ co
   }
 }
 
+// A metered call's own words (fmx_host.h, Metered): its hits on a 128-byte line of their own, and what the fold
+// sums of the call's private counter slots.
+constexpr uint32_t kLineWords = 32;
+constexpr uint32_t kLineHits = 0, kLineSteps = 16, kLineRequests = 17;
+
+__device__ __forceinline__ uint64_t min_u64(uint64_t a, uint64_t b) { return a < b ? a : b; }
+
 // The frontier kernels' own counters (slots 3..7), same calling rule.
 __device__ __forceinline__ void counters_add_frontier(unsigned long long *__restrict__ counters, unsigned long long reqs,
                                                       unsigned long long pushes, unsigned long long results,

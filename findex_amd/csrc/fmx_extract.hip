@@ -23,7 +23,6 @@
 #include <fmx.h>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <string>
 
@@ -34,7 +33,6 @@ namespace fmx {
 
 constexpr int kExThreads = 256;
 constexpr uint32_t kExTile = FMX_EXTRACT_TILE;             // output bytes per tile
-constexpr uint32_t kExLineWords = 32;                      // the call's own words: [16] steps, [17] requests
 static_assert(kExTile == 1024, "a piece's start and length are packed into 10 bits each");
 static_assert(kExTile == 4 * kExThreads, "the tile is cleared one dword per thread");
 
@@ -54,8 +52,6 @@ struct ExShared {
   uint32_t np, cursor;
 };
 
-__device__ __forceinline__ uint64_t ex_min(uint64_t a, uint64_t b) { return a < b ? a : b; }
-
 template <bool WIDE, uint32_t LAYOUT>
 __global__ __launch_bounds__(kExThreads) void k_extract(DevIndex ix, ExDev xd, const uint64_t *__restrict__ pos,
                                                         const uint64_t *__restrict__ off, uint64_t k, uint64_t n_bytes,
@@ -74,7 +70,7 @@ __global__ __launch_bounds__(kExThreads) void k_extract(DevIndex ix, ExDev xd, c
   const uint64_t ntiles = (n_bytes + kExTile - 1) / kExTile;
   for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const uint64_t tile_lo = tile * kExTile;
-    const uint32_t tile_n = (uint32_t)ex_min(kExTile, n_bytes - tile_lo);
+    const uint32_t tile_n = (uint32_t)min_u64(kExTile, n_bytes - tile_lo);
     __syncthreads();                                       // the tile before this one is written (and cf / slot are there)
     if (threadIdx.x == 0) {
       sh.np = 0;
@@ -99,7 +95,7 @@ __global__ __launch_bounds__(kExThreads) void k_extract(DevIndex ix, ExDev xd, c
       const uint32_t ph = (uint32_t)(v - vq * s);
       if (!(p == 0 || d == 0 || ph == 0)) continue;
       // the bytes up to the next cut: the tile's end, the range's end, the next t with (n - 1 - t) % s == 0
-      const uint32_t len = (uint32_t)ex_min(ex_min(tile_n - p, re - j), ph ? ph : s);
+      const uint32_t len = (uint32_t)min_u64(min_u64(tile_n - p, re - j), ph ? ph : s);
       const uint64_t uj = vq + (ph ? 1u : 0u);             // ceil(v / s)
       uint64_t row = 0;
       uint32_t skip;
@@ -110,8 +106,8 @@ __global__ __launch_bounds__(kExThreads) void k_extract(DevIndex ix, ExDev xd, c
         skip = (uint32_t)(last - v);
       }
       const uint32_t at = atomicAdd(&sh.np, 1u);           // at most one piece per byte of the tile
-      sh.row[at] = ex_min(row, last);
-      sh.meta[at] = p | ((len - 1u) << 10) | ((uint32_t)ex_min(skip, s - 1u) << 20);
+      sh.row[at] = min_u64(row, last);
+      sh.meta[at] = p | ((len - 1u) << 10) | ((uint32_t)min_u64(skip, s - 1u) << 20);
     }
     __syncthreads();
     // ---- walks: a group draws a piece, steps it skip + len times, draws the next
@@ -143,7 +139,7 @@ __global__ __launch_bounds__(kExThreads) void k_extract(DevIndex ix, ExDev xd, c
           if (lead) sh.tile[wp] = (uint8_t)b;
           wp++;
         }
-        r = ex_min(sh.cf[b] + rank_complete<WIDE, LAYOUT>(q, b, lc), last);
+        r = min_u64(sh.cf[b] + rank_complete<WIDE, LAYOUT>(q, b, lc), last);
         if (lead) {
           steps++;
           reqs += 1u + (q.kind ? (LAYOUT == kLayoutBytes ? 2u : 1u) : 0u);
@@ -170,32 +166,12 @@ __global__ __launch_bounds__(kExThreads) void k_extract(DevIndex ix, ExDev xd, c
   counters_add(counters, steps, 0ull, reqs);
 }
 
-// The call's counter slots into the handle's, and their sums into the call's line (the host form).
-__global__ __launch_bounds__(256) void k_extract_fold(const unsigned long long *__restrict__ mine,
-                                                      unsigned long long *__restrict__ counters,
-                                                      unsigned long long *__restrict__ line) {
-  const uint32_t sl = blockIdx.x * 256u + threadIdx.x;
-  unsigned long long v[3] = {0, 0, 0};
-  if (sl < kCounterSlots) {
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      v[j] = mine[(size_t)sl * kCounterStride + j];
-      if (v[j]) atomicAdd(counters + (size_t)sl * kCounterStride + j, v[j]);
-    }
-  }
-  const unsigned long long s0 = wave_sum(v[0]), s2 = wave_sum(v[2]);
-  if ((threadIdx.x & 63u) == 0) {
-    if (s0) atomicAdd(line + 16, s0);
-    if (s2) atomicAdd(line + 17, s2);
-  }
-}
-
 // ---------------------------------------------------------------- the samples
 // isa[j] = tmp[j], a row below n
 __global__ __launch_bounds__(256) void k_isa_pack(const uint64_t *__restrict__ tmp, uint64_t m, uint64_t n, int wide,
                                                   void *__restrict__ isa) {
   for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t r = ex_min(tmp[j], n - 1);
+    const uint64_t r = min_u64(tmp[j], n - 1);
     if (wide) static_cast<uint64_t *>(isa)[j] = r;
     else static_cast<uint32_t *>(isa)[j] = (uint32_t)r;
   }
@@ -223,8 +199,6 @@ __global__ __launch_bounds__(256) void k_isa_scatter(const uint32_t *__restrict_
     }
   }
 }
-
-static uint32_t ex_grid(uint64_t items) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, 8192)); }
 
 int extract_check(const Index *h) {
   if (h->block_mode) {
@@ -272,7 +246,7 @@ int extract_prepare(const Index *h, hipStream_t st) {
   DEV_ALLOC(mem, d_isa, keep, "extract samples");
   if (from_locate) {
     HIP_TRY(hipMemsetAsync(d_isa, 0, keep, st), "hipMemset(extract samples)");
-    hipLaunchKernelGGL(k_isa_scatter, dim3(ex_grid(nb)), dim3(256), 0, st, static_cast<const uint32_t *>(h->d_loc_marks), nb, n,
+    hipLaunchKernelGGL(k_isa_scatter, dim3(flat_grid(nb, 8192)), dim3(256), 0, st, static_cast<const uint32_t *>(h->d_loc_marks), nb, n,
                        static_cast<const void *>(h->d_loc_samples), h->loc_wide ? 1 : 0, rate, m, wide ? 1 : 0, d_isa);
     HIP_TRY(hipGetLastError(), "k_isa_scatter");
     HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
@@ -282,7 +256,7 @@ int extract_prepare(const Index *h, hipStream_t st) {
     DEV_ALLOC(mem, tmp, m * 8, "extract samples");
     HIP_TRY(hipMemsetAsync(tmp, 0, m * 8, st), "hipMemset(extract samples)");
     if ((rc = locate_invert_rows(h, st, rate, tmp))) return rc;
-    hipLaunchKernelGGL(k_isa_pack, dim3(ex_grid(m)), dim3(256), 0, st, static_cast<const uint64_t *>(tmp), m, n, wide ? 1 : 0, d_isa);
+    hipLaunchKernelGGL(k_isa_pack, dim3(flat_grid(m, 8192)), dim3(256), 0, st, static_cast<const uint64_t *>(tmp), m, n, wide ? 1 : 0, d_isa);
     HIP_TRY(hipGetLastError(), "k_isa_pack");
     HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
   }
@@ -309,22 +283,17 @@ void extract_drop(Index *h) {
 template <bool WIDE, uint32_t LAYOUT>
 static hipError_t ex_launch(const Index *h, const ExDev &xd, const uint64_t *pos, const uint64_t *off, uint64_t k, uint64_t n_bytes,
                             uint8_t *out, unsigned long long *counters, hipStream_t st) {
-  static std::atomic<int> cached{0};                       // per instantiation: the query is made once
-  int per_cu = cached.load(std::memory_order_relaxed);
-  if (per_cu <= 0) {
-    const hipError_t he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_extract<WIDE, LAYOUT>, kExThreads, 0);
-    if (he != hipSuccess) return he;
-    per_cu = std::max(per_cu, 1);
-    cached.store(per_cu, std::memory_order_relaxed);
-  }
-  const uint64_t resident = (uint64_t)per_cu * (uint64_t)std::max(h->cu_count, 1);
-  const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(resident, (n_bytes + kExTile - 1) / kExTile));
+  uint32_t grid = 0;
+  const hipError_t he = resident_grid<k_extract<WIDE, LAYOUT>>(h, kExThreads, n_bytes, kExTile, &grid);
+  if (he != hipSuccess) return he;
   hipLaunchKernelGGL((k_extract<WIDE, LAYOUT>), dim3(grid), dim3(kExThreads), 0, st, h->dev, xd, pos, off, k, n_bytes, out, counters);
   return hipGetLastError();
 }
 
-hipError_t extract_enqueue(const Index *h, const void *d_pos, const void *d_off, uint64_t k, uint64_t n_bytes, void *d_out,
-                           unsigned long long *counters, hipStream_t st) {
+// The k ranges' n_bytes bytes into d_out, device pointers throughout; it needs the samples built and only enqueues on `st`;
+// counters == nullptr: the handle's own.
+static hipError_t extract_enqueue(const Index *h, const void *d_pos, const void *d_off, uint64_t k, uint64_t n_bytes, void *d_out,
+                                  unsigned long long *counters, hipStream_t st) {
   if (n_bytes == 0 || k == 0) return hipSuccess;
   ExDev xd;
   xd.isa = h->d_ext_isa;
@@ -340,38 +309,109 @@ hipError_t extract_enqueue(const Index *h, const void *d_pos, const void *d_off,
   return he;
 }
 
-uint64_t extract_bytes() { return kCounterBytes + 8 * kExLineWords; }
+struct ExtractInfo {
+  uint64_t steps = 0, requests = 0;
+  double ms = 0.0;                              // device events around k_extract
+};
 
-int extract_run(const Index *h, const void *d_pos, const void *d_off, uint64_t k, uint64_t n_bytes, void *d_out, hipStream_t st,
-                ExtractInfo *info) {
+static uint64_t extract_bytes() { return kMeteredBytes; }     // the device bytes extract_run allocates
+
+// extract_enqueue with the call's own counters and timing; allocates, synchronises `st`, frees its temporaries on every path.
+static int extract_run(const Index *h, const void *d_pos, const void *d_off, uint64_t k, uint64_t n_bytes, void *d_out,
+                       hipStream_t st, ExtractInfo *info) {
   *info = ExtractInfo{};
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 2; i++) if (ev[i]) (void)hipEventDestroy(ev[i]); } } evg{ev};
-  for (int i = 0; i < 2; i++) HIP_TRY(hipEventCreate(&ev[i]), "hipEventCreate");
+  Events<2> ev;
+  HIP_TRY(ev.create(), "hipEventCreate");
   DevMem mem;
-  unsigned long long *line = nullptr, *mine = nullptr;
-  DEV_ALLOC(mem, line, 8 * kExLineWords, "extraction");
-  DEV_ALLOC(mem, mine, kCounterBytes, "extraction");
-  HIP_TRY(hipMemsetAsync(line, 0, 8 * kExLineWords, st), "memset");
-  HIP_TRY(hipMemsetAsync(mine, 0, kCounterBytes, st), "memset");
-  HIP_TRY(hipEventRecord(ev[0], st), "hipEventRecord");
-  HIP_TRY(extract_enqueue(h, d_pos, d_off, k, n_bytes, d_out, mine, st), "k_extract");
-  HIP_TRY(hipEventRecord(ev[1], st), "hipEventRecord");
-  hipLaunchKernelGGL(k_extract_fold, dim3(kCounterSlots / 256), dim3(256), 0, st, mine, h->d_counters, line);
-  HIP_TRY(hipGetLastError(), "k_extract_fold");
-  unsigned long long words[kExLineWords];
-  HIP_TRY(hipMemcpyAsync(words, line, sizeof words, hipMemcpyDeviceToHost, st), "D2H");
-  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");  // the temporaries go when this returns
-  {
-    std::lock_guard<std::mutex> lk(h->mu);
-    h->launches += 1;
-  }
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
-  info->ms = ms;
-  info->steps = words[16];
-  info->requests = words[17];
+  Metered own;
+  int rc;
+  if ((rc = own.alloc(mem, "extraction")) || (rc = own.zero(st))) return rc;
+  HIP_TRY(ev.record(0, st), "hipEventRecord");
+  HIP_TRY(extract_enqueue(h, d_pos, d_off, k, n_bytes, d_out, own.mine, st), "k_extract");
+  HIP_TRY(ev.record(1, st), "hipEventRecord");
+  if ((rc = own.fold(h, 0, st))) return rc;                  // counter [0]: the rank queries, one per LF step
+  MeterCounts cnt;
+  if ((rc = own.finish(h, st, 1, &cnt))) return rc;
+  info->ms = ev.ms(0, 1);
+  info->steps = cnt.steps;
+  info->requests = cnt.requests;
   return FMX_OK;
 }
 
 }  // namespace fmx
+
+// ---------------------------------------------------------------- the C entry points (fmx.h)
+using namespace fmx;
+
+static thread_local ExtractInfo g_extract_last;
+
+extern "C" {
+
+int fmx_extract_text_batch(const fmx_index *idx, const uint64_t *pos, const uint64_t *off, size_t k, uint8_t *out) {
+  if ((uint64_t)k > (1ull << 26)) return arg_fail("extract: at most 2^26 ranges per call");
+  if (k && (!pos || !off)) return arg_fail("extract: null argument");
+  if (k && off[0] != 0) return arg_fail("extract: off[0] must be 0");
+  if (k && !offsets_monotonic(off, 0, k)) return arg_fail("extract: range offsets must be non-decreasing");
+  const uint64_t n_bytes = k ? off[k] : 0;
+  if (n_bytes >= (1ull << 32)) return arg_fail("extract: n_bytes = off[k] must be below 2^32");
+  if (n_bytes && !out) return arg_fail("extract: null argument (out)");
+  if (!idx) return arg_fail("extract: the handle is null");
+  const Index *h = H(idx);
+  int rc = extract_check(h);
+  if (rc) return rc;
+  const uint64_t len = h->n - 1;
+  for (size_t q = 0; q < k; q++) {
+    const uint64_t l = off[q + 1] - off[q];
+    if (pos[q] > len || l > len - pos[q]) return arg_fail("extract: a range runs past the text (pos + length <= n - 1)");
+  }
+  if (!n_bytes) return FMX_OK;
+  if ((rc = use_device(h))) return rc;
+  if ((rc = ensure_built(h, h->ext_mu, h->ext_ready, extract_prepare, nullptr))) return rc;
+  if ((rc = mstat_room(extract_bytes() + n_bytes + 16 * ((uint64_t)k + 1) + 64, "fmx_extract_text_batch"))) return rc;
+  HostCall hc;
+  void *d_pos = nullptr;
+  uint64_t *d_off = nullptr;
+  uint8_t *d_out = nullptr;
+  if ((rc = hc.open())) return rc;
+  if ((rc = hc.upload("positions", pos, 8 * (uint64_t)k, "offsets", off, k, false, &d_pos, &d_off))) return rc;
+  DEV_ALLOC(hc.mem, d_out, n_bytes, "text");
+  rc = extract_run(h, d_pos, d_off, k, n_bytes, d_out, hc.own.s, &g_extract_last);
+  if (rc) return rc;
+  if ((rc = hc.download(out, d_out, n_bytes, "D2H(text)"))) return rc;
+  return hc.sync();
+}
+
+int fmx_extract_text_batch_dev(const fmx_index *idx, const void *d_pos, const void *d_off, size_t k, uint64_t n_bytes,
+                               void *d_out, void *stream) {
+  if ((uint64_t)k > (1ull << 26)) return arg_fail("extract: at most 2^26 ranges per call");
+  if (n_bytes >= (1ull << 32)) return arg_fail("extract: n_bytes must be below 2^32");
+  if (k && n_bytes && (!d_pos || !d_off || !d_out)) return arg_fail("extract: null argument");
+  if (!idx) return arg_fail("extract: the handle is null");
+  const Index *h = H(idx);
+  int rc = extract_check(h);
+  if (rc) return rc;
+  if (!k || !n_bytes) return FMX_OK;
+  if ((rc = use_device(h))) return rc;
+  if ((rc = ensure_built(h, h->ext_mu, h->ext_ready, extract_prepare, (hipStream_t)stream))) return rc;
+  HIP_TRY(extract_enqueue(h, d_pos, d_off, k, n_bytes, d_out, nullptr, (hipStream_t)stream), "k_extract");
+  return FMX_OK;
+}
+
+int fmx_extract_info(const fmx_index *idx, uint32_t *rate, uint64_t *bytes, double *build_ms) {
+  if (!idx) return arg_fail("null argument");
+  const Index *h = H(idx);
+  std::lock_guard<std::mutex> lk(h->ext_mu);
+  if (rate) *rate = h->ext_ready ? h->ext_rate : (uint32_t)h->policy.extract_sample.load(std::memory_order_relaxed);
+  if (bytes) *bytes = h->ext_ready ? h->ext_bytes : 0;
+  if (build_ms) *build_ms = h->ext_ready ? h->ext_build_ms : 0.0;
+  return FMX_OK;
+}
+
+int fmx_extract_last(double *ms, uint64_t *steps, uint64_t *requests) {
+  if (ms) *ms = g_extract_last.ms;
+  if (steps) *steps = g_extract_last.steps;
+  if (requests) *requests = g_extract_last.requests;
+  return FMX_OK;
+}
+
+}  // extern "C"

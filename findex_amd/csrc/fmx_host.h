@@ -1,8 +1,10 @@
 // fmx_host.h -- host-side handle and the launch entry points shared by the .hip/.cpp units.
 #pragma once
+#include <fmx.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <atomic>
 #include <memory>
 #include <mutex>
@@ -254,23 +256,11 @@ uint64_t locate_invert_text_bytes(const Index *h);
 int locate_invert_rows(const Index *h, hipStream_t st, uint32_t rate, uint64_t *d_tmp);
 uint64_t locate_invert_rows_bytes(const Index *h);
 
-// fmx_extract.hip: text by position from inverse-SA samples.  extract_prepare builds the samples under ext_mu
-// (allocates, synchronises `st`; an FMX_* status with its message).  extract_enqueue: the k ranges' n_bytes bytes into d_out,
-// device pointers throughout; it needs the samples built and only enqueues on `st`; counters == nullptr: the handle's own.
-// extract_run: the same with the call's own counters and timing; allocates, synchronises `st`, frees its temporaries on
-// every path.  extract_bytes: the device bytes extract_run allocates.
-struct ExtractInfo {
-  uint64_t steps = 0, requests = 0;
-  double ms = 0.0;                              // device events around k_extract
-};
+// fmx_extract.hip: text by position from inverse-SA samples, its entry points included.  extract_prepare builds
+// the samples under ext_mu (allocates, synchronises `st`; an FMX_* status with its message).
 int extract_check(const Index *h);              // FMX_ERR_UNSUPPORTED for handles extraction cannot serve (those of locate)
 int extract_prepare(const Index *h, hipStream_t st);
 void extract_drop(Index *h);
-hipError_t extract_enqueue(const Index *h, const void *d_pos, const void *d_off, uint64_t k, uint64_t n_bytes, void *d_out,
-                           unsigned long long *counters, hipStream_t st);
-uint64_t extract_bytes();
-int extract_run(const Index *h, const void *d_pos, const void *d_off, uint64_t k, uint64_t n_bytes, void *d_out, hipStream_t st,
-                ExtractInfo *info);
 
 // fmx_lcp.hip: the LCP array.  lcp_core: LCP[n] of s from s and its suffix array, all in device memory;
 // d_s is s itself (lcp_text_bytes(n) bytes: s, the sentinel 0 last, and zero padding); allocates 4 n bytes, synchronises `st`, returns an FMX_*
@@ -289,37 +279,9 @@ int lcp_prepare(const Index *h, hipStream_t st);   // builds the handle's array 
 void lcp_drop(Index *h);
 hipError_t launch_lcp_gather(const Index *h, const void *d_rows, uint64_t k, void *d_out, hipStream_t st);
 
-// fmx_approx.hip: approximate search.  approx_check: FMX_ERR_UNSUPPORTED for handles it does not serve.
-// approx_search: the hits of k patterns within e substitutions from [lo, hi], device pointers throughout; allocates,
-// synchronises `st`, frees its temporaries on every path.  info->total is the exact number of hits; when it exceeds cap
-// nothing is ordered and d_out_off / d_out are unspecified.
-struct ApproxInfo {
-  uint64_t total = 0, steps = 0, requests = 0;
-  double search_ms = 0.0, sort_ms = 0.0;      // device events: the search kernel, the ordering step
-};
-int approx_check(const Index *h);
-int approx_search(const Index *h, const void *d_pat, const void *d_off, uint64_t k, uint32_t e, uint32_t lo, uint32_t hi,
-                  void *d_out_off, void *d_out, uint64_t cap, hipStream_t st, ApproxInfo *info);
-
-// fmx_mstat.hip: matching statistics and maximal exact matches.  mstat_check: FMX_ERR_UNSUPPORTED for handles
-// they do not serve.  mstat_enqueue: the statistics of the n_bytes pattern bytes, device pointers throughout (d_sp / d_ep may
-// be null); it only enqueues on `st`; counters == nullptr: the handle's own.  mstat_run: the same with the call's own
-// counters and timing, and, with `mems`, the compaction into d_out_off[k + 1] / d_out[cap] (the statistics are then
-// temporaries of the call, d_len / d_sp / d_ep ignored); allocates, synchronises `st`, frees its temporaries on every path.
-// info->total is the exact number of hits; records past cap are not written.  mstat_bytes: the device bytes mstat_run
-// allocates; mstat_room: FMX_ERR_NOMEM with the need in the message when `need` exceeds the free device memory.
-struct MstatInfo {
-  uint64_t total = 0, steps = 0, requests = 0;
-  double walk_ms = 0.0, compact_ms = 0.0;       // device events: k_mstat, the flag / scan / write steps
-};
-int mstat_check(const Index *h);
-hipError_t mstat_enqueue(const Index *h, const void *d_pat, const void *d_off, uint64_t k, uint64_t n_bytes, uint32_t max_len,
-                         void *d_len, void *d_sp, void *d_ep, unsigned long long *counters, hipStream_t st);
-uint64_t mstat_bytes(uint64_t n_bytes, bool mems);
+// fmx_approx.hip and fmx_mstat.hip (§16) hold their entry points themselves.  mstat_room: FMX_ERR_NOMEM with
+// the need in the message when `need` exceeds the free device memory (fmx_extract.hip asks it too).
 int mstat_room(uint64_t need, const char *what);
-int mstat_run(const Index *h, const void *d_pat, const void *d_off, uint64_t k, uint64_t n_bytes, uint32_t max_len,
-              uint32_t min_len, void *d_len, void *d_sp, void *d_ep, bool mems, void *d_out_off, void *d_out, uint64_t cap,
-              hipStream_t st, MstatInfo *info);
 
 // fmx_search.hip: the residency census of the k_search4 instantiation this handle's full-size searches use now, taken with
 // calibration launches on `st` (synchronises it): fmx_prepare's last step, never a _dev call's.
@@ -349,15 +311,17 @@ struct DevMem {                 // the hipMalloc'ed temporaries of one call; fre
   }
   template <class T>
   hipError_t alloc(T **out, size_t count) { return get(reinterpret_cast<void **>(out), count * sizeof(T)); }
+  int take(void **out, size_t bytes, const char *what) {     // get, or "hipMalloc(<what>): .." and FMX_ERR_NOMEM
+    const hipError_t e = get(out, bytes);
+    if (e == hipSuccess) return FMX_OK;
+    set_error(std::string("hipMalloc(") + what + "): " + hipGetErrorString(e));
+    return FMX_ERR_NOMEM;
+  }
 };
 // p = `bytes` of device memory from the bag `mem`, or "hipMalloc(<what>): .." and FMX_ERR_NOMEM
-#define DEV_ALLOC(mem, p, bytes, what)                                                              \
-  do {                                                                                              \
-    const hipError_t e__ = (mem).get((void **)&(p), (bytes));                                       \
-    if (e__ != hipSuccess) {                                                                        \
-      ::fmx::set_error(std::string("hipMalloc(" what "): ") + hipGetErrorString(e__));              \
-      return FMX_ERR_NOMEM;                                                                         \
-    }                                                                                               \
+#define DEV_ALLOC(mem, p, bytes, what)                                           \
+  do {                                                                           \
+    if (const int rc__ = (mem).take((void **)&(p), (bytes), what)) return rc__;  \
   } while (0)
 
 struct StreamGuard {            // a stream the call made for itself
@@ -365,12 +329,102 @@ struct StreamGuard {            // a stream the call made for itself
   ~StreamGuard() { if (s) (void)hipStreamDestroy(s); }
 };
 
+template <int N>
+struct Events {                 // the N timing events of one call; destroyed on every return path
+  hipEvent_t ev[N] = {};
+  Events() = default;
+  Events(const Events &) = delete;
+  Events &operator=(const Events &) = delete;
+  ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+  hipError_t create() {
+    for (hipEvent_t &e : ev) {
+      const hipError_t r = hipEventCreate(&e);
+      if (r != hipSuccess) return r;
+    }
+    return hipSuccess;
+  }
+  hipError_t record(int i, hipStream_t st) { return hipEventRecord(ev[i], st); }
+  hipError_t elapsed(int i, int j, float *ms) const { return hipEventElapsedTime(ms, ev[i], ev[j]); }
+  float ms(int i, int j) const {               // 0 when the runtime has no answer
+    float m = 0;
+    (void)elapsed(i, j, &m);
+    return m;
+  }
+};
+
+// A call's own counters: kernels add to `mine`, private counter slots, and to `line`; fold adds the slots to the
+// handle's and sums counter `steps_counter` and the requests into the line; finish copies the line back, synchronises `st`
+// and adds `launches` to the handle's.  Both buffers belong to the caller's bag, which places its event records itself.
+struct MeterCounts {
+  uint64_t hits = 0, steps = 0, requests = 0;
+};
+struct Metered {
+  unsigned long long *line = nullptr, *mine = nullptr;
+  int alloc(DevMem &mem, const char *what);
+  int zero(hipStream_t st);
+  int fold(const Index *h, uint32_t steps_counter, hipStream_t st);
+  int finish(const Index *h, hipStream_t st, uint64_t launches, MeterCounts *out);
+};
+constexpr uint64_t kMeteredBytes = kCounterBytes + 8 * kLineWords;      // what alloc takes
+
+// Grid of a kernel whose workgroups loop over the work: what is resident on the device at once, at most one workgroup per
+// `per_block` items.  The occupancy query is made once per kernel.
+template <auto Kernel>
+hipError_t resident_grid(const Index *h, int threads, uint64_t work, uint64_t per_block, uint32_t *grid) {
+  static std::atomic<int> cached{0};
+  int per_cu = cached.load(std::memory_order_relaxed);
+  if (per_cu <= 0) {
+    const hipError_t he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, Kernel, threads, 0);
+    if (he != hipSuccess) return he;
+    per_cu = std::max(per_cu, 1);
+    cached.store(per_cu, std::memory_order_relaxed);
+  }
+  const uint64_t resident = (uint64_t)per_cu * (uint64_t)std::max(h->cu_count, 1);
+  *grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(resident, (work + per_block - 1) / per_block));
+  return hipSuccess;
+}
+// Grid of a 256-thread kernel that strides over `items`
+inline uint32_t flat_grid(uint64_t items, uint32_t cap = 4096) {
+  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, cap));
+}
+
 // fmx_api.cpp.  use_device_index: a device there is, `device` names one, hipSetDevice.  not_capturing: "<what> allocates and
 // synchronises: not under a stream capture" when `st` is being captured.  ensure_built: `prepare` (which takes `mu` itself
 // and looks again) on `st`, or on a stream of the handle's when st is null, unless `flag` says it has run.
+int arg_fail(const char *msg);                  // records the message, returns FMX_ERR_ARG
+int use_device(const Index *h);
 int use_device_index(int device);
 int not_capturing(hipStream_t st, const char *what);
 int ensure_built(const Index *h, std::mutex &mu, const bool &flag, int (*prepare)(const Index *, hipStream_t), hipStream_t st);
+bool offsets_monotonic(const uint64_t *off, size_t a, size_t b);      // off[a] <= off[a+1] <= .. <= off[b]
+inline Index *H(fmx_index *p) { return reinterpret_cast<Index *>(p); }
+inline const Index *H(const fmx_index *p) { return reinterpret_cast<const Index *>(p); }
+
+// The device side of one host-pointer call of a metered feature: its temporaries and a non-blocking stream of its own.
+struct HostCall {
+  DevMem mem;
+  StreamGuard own;
+  int open() { HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate"); return FMX_OK; }
+  // `bytes` of pat and the k + 1 offsets into the bag, then a synchronise.  rebase: the offsets travel less off[0] (pat is the
+  // caller's pointer already advanced), and an empty batch copies nothing; otherwise off[0] == 0 and an empty batch gets one
+  // zero offset.  The labels are those of DEV_ALLOC.
+  int upload(const char *pat_what, const void *pat, uint64_t bytes, const char *off_what, const uint64_t *off, size_t k,
+             bool rebase, void **d_pat, uint64_t **d_off);
+  int download(void *dst, const void *src, uint64_t bytes, const char *what) {      // enqueues; dst == nullptr: nothing
+    if (dst) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, own.s), what);
+    return FMX_OK;
+  }
+  int sync() { HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize"); return FMX_OK; }
+  // a CSR result: k + 1 offsets and `total` records of `rec` bytes, then a synchronise
+  int download_csr(uint64_t *out_off, const void *d_out_off, size_t k, void *out, const void *d_out, uint64_t total, size_t rec) {
+    int rc;
+    if ((rc = download(out_off, d_out_off, 8 * ((uint64_t)k + 1), "D2H(offsets)"))) return rc;
+    if (total && (rc = download(out, d_out, rec * total, "D2H(hits)"))) return rc;
+    return sync();
+  }
+};
+// "<prefix>: <total> hits, room for <cap>" and FMX_ERR_OVERFLOW
+int csr_overflow(const char *prefix, uint64_t total, size_t cap);
 
 // fmx_build.hip
 int build_index(Index *h, hipStream_t st, const int64_t *given_counts);   // returns an FMX_* status

@@ -5,6 +5,9 @@
 // lanes (an octet and two lines in the bytes layout; fmx_device.h); C[] and the symbol->slot map
 // are staged in LDS per workgroup.  "group" below = the lanes that serve one query.
 // Reference semantics: SuffixAlgo (findex.scala:9-52), NaiveFMSearcher (bwtmerger.scala:335-421).
+#include <fmx.h>
+
+#include <string>
 #include <type_traits>
 
 #include "fmx_device.h"
@@ -402,6 +405,57 @@ hipError_t launch_fm_fill(const Index *h, void *d_fm, hipStream_t st) {
   FMX_LAYOUT_DISPATCH(h, CALL);
 #undef CALL
   return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- a call's own counters (fmx_host.h, Metered)
+// The call's counter slots into the handle's, and the sums of counter `steps_counter` and of the requests into the call's line.
+__global__ __launch_bounds__(kThreads) void k_counters_fold(const unsigned long long *__restrict__ mine,
+                                                            unsigned long long *__restrict__ counters,
+                                                            unsigned long long *__restrict__ line, uint32_t steps_counter) {
+  const uint32_t sl = blockIdx.x * kThreads + threadIdx.x;
+  unsigned long long v[3] = {0, 0, 0};
+  if (sl < kCounterSlots) {
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+      v[j] = mine[(size_t)sl * kCounterStride + j];
+      if (v[j]) atomicAdd(counters + (size_t)sl * kCounterStride + j, v[j]);
+    }
+  }
+  const unsigned long long ss = wave_sum(steps_counter ? v[1] : v[0]), sr = wave_sum(v[2]);
+  if ((threadIdx.x & 63u) == 0) {
+    if (ss) atomicAdd(line + kLineSteps, ss);
+    if (sr) atomicAdd(line + kLineRequests, sr);
+  }
+}
+
+int Metered::alloc(DevMem &mem, const char *what) {
+  DEV_ALLOC(mem, line, 8 * kLineWords, what);
+  DEV_ALLOC(mem, mine, kCounterBytes, what);
+  return FMX_OK;
+}
+
+int Metered::zero(hipStream_t st) {
+  HIP_TRY(hipMemsetAsync(line, 0, 8 * kLineWords, st), "memset");
+  HIP_TRY(hipMemsetAsync(mine, 0, kCounterBytes, st), "memset");
+  return FMX_OK;
+}
+
+int Metered::fold(const Index *h, uint32_t steps_counter, hipStream_t st) {
+  hipLaunchKernelGGL(k_counters_fold, dim3(kCounterSlots / kThreads), dim3(kThreads), 0, st, mine, h->d_counters, line, steps_counter);
+  HIP_TRY(hipGetLastError(), "k_counters_fold");
+  return FMX_OK;
+}
+
+int Metered::finish(const Index *h, hipStream_t st, uint64_t launches, MeterCounts *out) {
+  unsigned long long words[kLineWords];
+  HIP_TRY(hipMemcpyAsync(words, line, sizeof words, hipMemcpyDeviceToHost, st), "D2H");
+  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");  // the caller's temporaries may go when this returns
+  {
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->launches += launches;
+  }
+  *out = MeterCounts{words[kLineHits], words[kLineSteps], words[kLineRequests]};
+  return FMX_OK;
 }
 
 }  // namespace fmx

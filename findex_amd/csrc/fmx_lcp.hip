@@ -166,11 +166,9 @@ void lcp_reverse_text(const uint8_t *d_text, uint64_t len, uint8_t *d_s, int cu_
 int lcp_core(const uint8_t *d_s, uint64_t n, const uint32_t *d_sa, uint32_t *d_lcp, int cu_count, hipStream_t st, LcpInfo *info) {
   struct Tmp {
     void *phi = nullptr, *res = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     ~Tmp() {
       if (phi) (void)hipFree(phi);
       if (res) (void)hipFree(res);
-      for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     }
   } tmp;
   const uint64_t nruns = (n + kRun - 1) / kRun;
@@ -182,20 +180,21 @@ int lcp_core(const uint8_t *d_s, uint64_t n, const uint32_t *d_sa, uint32_t *d_l
   }
   uint32_t *phi = static_cast<uint32_t *>(tmp.phi);
   unsigned long long *res = static_cast<unsigned long long *>(tmp.res);
-  for (hipEvent_t &ev : tmp.ev) HIP_TRY(hipEventCreate(&ev), "hipEventCreate");
+  Events<4> ev;
+  HIP_TRY(ev.create(), "hipEventCreate");
   HIP_TRY(hipMemsetAsync(res, 0, 64, st), "hipMemsetAsync");
   // the entries no row names (the padding; all of them when d_sa is no permutation) read as "no successor"
   HIP_TRY(hipMemsetAsync(phi, 0xFF, nruns * kRun * 4, st), "hipMemsetAsync");
-  HIP_TRY(hipEventRecord(tmp.ev[0], st), "hipEventRecord");
+  HIP_TRY(ev.record(0, st), "hipEventRecord");
   k_lcp_phi<<<lcp_grid(cu_count, n), kLcpThreads, 0, st>>>(d_sa, n, phi);
   HIP_TRY(hipGetLastError(), "k_lcp_phi");
-  HIP_TRY(hipEventRecord(tmp.ev[1], st), "hipEventRecord");
+  HIP_TRY(ev.record(1, st), "hipEventRecord");
   k_lcp_plcp<<<lcp_grid(cu_count, nruns), kLcpThreads, 0, st>>>(d_s, n, phi, nruns);
   HIP_TRY(hipGetLastError(), "k_lcp_plcp");
-  HIP_TRY(hipEventRecord(tmp.ev[2], st), "hipEventRecord");
+  HIP_TRY(ev.record(2, st), "hipEventRecord");
   k_lcp_gather<<<lcp_grid(cu_count, n), kLcpThreads, 0, st>>>(d_sa, phi, n, d_lcp, res);
   HIP_TRY(hipGetLastError(), "k_lcp_gather");
-  HIP_TRY(hipEventRecord(tmp.ev[3], st), "hipEventRecord");
+  HIP_TRY(ev.record(3, st), "hipEventRecord");
   unsigned long long host[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(host, res, 16, hipMemcpyDeviceToHost, st), "D2H(LCP summary)");
   HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
@@ -203,7 +202,7 @@ int lcp_core(const uint8_t *d_s, uint64_t n, const uint32_t *d_sa, uint32_t *d_l
     info->max = (uint32_t)(host[0] >> 32);
     info->max_row = 0xFFFFFFFFull - (host[0] & 0xFFFFFFFFull);
     info->sum = host[1];
-    for (int i = 0; i < 3; i++) (void)hipEventElapsedTime(&info->phase_ms[i], tmp.ev[i], tmp.ev[i + 1]);
+    for (int i = 0; i < 3; i++) info->phase_ms[i] = ev.ms(i, i + 1);
   }
   return FMX_OK;
 }

@@ -19,7 +19,6 @@
 #include <fmx.h>
 
 #include <algorithm>
-#include <atomic>
 #include <string>
 
 #include "fmx_device.h"
@@ -32,7 +31,6 @@ constexpr int kMsWaves = kMsThreads / 64;
 constexpr uint32_t kMsTile = FMX_MSTAT_TILE;                // positions per tile: four waves of 128
 constexpr uint32_t kMsWaveTile = kMsTile / kMsWaves;
 constexpr uint32_t kMsMaxLen = FMX_MSTAT_MAX_LEN;
-constexpr uint32_t kMsLineWords = 32;                      // the call's own words: [16] steps, [17] requests
 
 struct MsShared {
   uint64_t cf[256];
@@ -40,8 +38,6 @@ struct MsShared {
   uint16_t lim[kMsTile];                                   // per position of the tile: min(e, max_len); 0: no pattern covers it
   uint8_t buf[kMsMaxLen + kMsTile];                        // pat[tile_lo - halo .. tile_hi)
 };
-
-__device__ __forceinline__ uint64_t ms_min(uint64_t a, uint64_t b) { return a < b ? a : b; }
 
 // The pattern that owns position j: the largest q with off[q] <= j, when j < off[q + 1].  Whatever the offsets hold, the
 // search stays inside off[0 .. k] and *start <= j: k (no owner) otherwise.
@@ -79,17 +75,17 @@ __global__ __launch_bounds__(kMsThreads) void k_mstat(DevIndex ix, const uint8_t
   const uint64_t ntiles = (n_bytes + kMsTile - 1) / kMsTile;
   for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const uint64_t tile_lo = tile * kMsTile;
-    const uint32_t tile_n = (uint32_t)ms_min(kMsTile, n_bytes - tile_lo);
-    const uint32_t halo = (uint32_t)ms_min(max_len, tile_lo);
+    const uint32_t tile_n = (uint32_t)min_u64(kMsTile, n_bytes - tile_lo);
+    const uint32_t halo = (uint32_t)min_u64(max_len, tile_lo);
     __syncthreads();                                       // the tile before this one is through (and cf / slot are there)
     for (uint32_t b = threadIdx.x; b < halo + tile_n; b += kMsThreads) sh.buf[b] = pat[tile_lo - halo + b];
     for (uint32_t p = threadIdx.x; p < tile_n; p += kMsThreads) {
       uint64_t start;
       const uint64_t q = ms_owner(off, k, tile_lo + p, &start);
-      sh.lim[p] = q < k ? (uint16_t)ms_min(tile_lo + p - start + 1, max_len) : (uint16_t)0;
+      sh.lim[p] = q < k ? (uint16_t)min_u64(tile_lo + p - start + 1, max_len) : (uint16_t)0;
     }
     __syncthreads();
-    const uint32_t wend = (uint32_t)ms_min(tile_n, (wv + 1) * kMsWaveTile);
+    const uint32_t wend = (uint32_t)min_u64(tile_n, (wv + 1) * kMsWaveTile);
     uint32_t cursor = wv * kMsWaveTile;                    // wave-uniform: the wave's next position that nobody owns
     bool want = true, live = false;                        // both the same in all lanes of a group
     uint32_t p = 0, i = 0, lim = 0;
@@ -109,7 +105,7 @@ __global__ __launch_bounds__(kMsThreads) void k_mstat(DevIndex ix, const uint8_t
             live = true;
           }
         }
-        cursor = (uint32_t)ms_min(wend, cursor + (uint32_t)__popcll(need));
+        cursor = (uint32_t)min_u64(wend, cursor + (uint32_t)__popcll(need));
       }
       if (!__builtin_amdgcn_ballot_w64(live)) break;
       if (live) {
@@ -146,26 +142,6 @@ __global__ __launch_bounds__(kMsThreads) void k_mstat(DevIndex ix, const uint8_t
   counters_add(counters, 2ull * steps, steps, reqs);
 }
 
-// The call's counter slots into the handle's, and their sums into the call's line (the host and MEM forms).
-__global__ __launch_bounds__(256) void k_mstat_fold(const unsigned long long *__restrict__ mine,
-                                                    unsigned long long *__restrict__ counters,
-                                                    unsigned long long *__restrict__ line) {
-  const uint32_t sl = blockIdx.x * 256u + threadIdx.x;
-  unsigned long long v[3] = {0, 0, 0};
-  if (sl < kCounterSlots) {
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      v[j] = mine[(size_t)sl * kCounterStride + j];
-      if (v[j]) atomicAdd(counters + (size_t)sl * kCounterStride + j, v[j]);
-    }
-  }
-  const unsigned long long s1 = wave_sum(v[1]), s2 = wave_sum(v[2]);
-  if ((threadIdx.x & 63u) == 0) {
-    if (s1) atomicAdd(line + 16, s1);
-    if (s2) atomicAdd(line + 17, s2);
-  }
-}
-
 // flag[j] = 1 where byte j ends a reported match: len[j] >= min_len (>= 1) and the match does not go on with byte j + 1.
 // The first byte of a pattern has len <= 1, so len[j + 1] <= len[j] holds at every pattern edge by itself; flag[n_bytes] = 0
 // is the slot the scan leaves the total in.
@@ -199,31 +175,22 @@ __global__ __launch_bounds__(256) void k_mem_write(const uint32_t *__restrict__ 
     out[2 * (uint64_t)at] = make_uint4((uint32_t)q, len[j], (uint32_t)end, (uint32_t)(end >> 32));
     out[2 * (uint64_t)at + 1] = make_uint4((uint32_t)s, (uint32_t)(s >> 32), (uint32_t)e, (uint32_t)(e >> 32));
   }
-  for (uint64_t q = t0; q <= k; q += stride) out_off[q] = slot[ms_min(off[q], n_bytes)];
+  for (uint64_t q = t0; q <= k; q += stride) out_off[q] = slot[min_u64(off[q], n_bytes)];
 }
-
-static uint32_t ms_grid(uint64_t items) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, 4096)); }
 
 template <bool WIDE, uint32_t LAYOUT>
 static hipError_t ms_launch(const Index *h, const uint8_t *pat, const uint64_t *off, uint64_t k, uint64_t n_bytes,
                             uint32_t max_len, uint32_t *len, uint64_t *sp, uint64_t *ep, unsigned long long *counters,
                             hipStream_t st) {
-  static std::atomic<int> cached{0};                       // per instantiation: the query is made once
-  int per_cu = cached.load(std::memory_order_relaxed);
-  if (per_cu <= 0) {
-    const hipError_t he = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_mstat<WIDE, LAYOUT>, kMsThreads, 0);
-    if (he != hipSuccess) return he;
-    per_cu = std::max(per_cu, 1);
-    cached.store(per_cu, std::memory_order_relaxed);
-  }
-  const uint64_t resident = (uint64_t)per_cu * (uint64_t)std::max(h->cu_count, 1);
-  const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(resident, (n_bytes + kMsTile - 1) / kMsTile));
+  uint32_t grid = 0;
+  const hipError_t he = resident_grid<k_mstat<WIDE, LAYOUT>>(h, kMsThreads, n_bytes, kMsTile, &grid);
+  if (he != hipSuccess) return he;
   hipLaunchKernelGGL((k_mstat<WIDE, LAYOUT>), dim3(grid), dim3(kMsThreads), 0, st, h->dev, pat, off, k, n_bytes, max_len, len, sp,
                      ep, counters);
   return hipGetLastError();
 }
 
-int mstat_check(const Index *h) {
+static int mstat_check(const Index *h) {
   if (h->block_mode) {
     set_error("matching statistics: not for fmx_open_block handles");
     return FMX_ERR_UNSUPPORTED;
@@ -231,8 +198,11 @@ int mstat_check(const Index *h) {
   return FMX_OK;
 }
 
-hipError_t mstat_enqueue(const Index *h, const void *d_pat, const void *d_off, uint64_t k, uint64_t n_bytes, uint32_t max_len,
-                         void *d_len, void *d_sp, void *d_ep, unsigned long long *counters, hipStream_t st) {
+// The statistics of the n_bytes pattern bytes, device pointers throughout (d_sp / d_ep may be null); it only enqueues on `st`;
+// counters == nullptr: the handle's own.
+static hipError_t mstat_enqueue(const Index *h, const void *d_pat, const void *d_off, uint64_t k, uint64_t n_bytes,
+                                uint32_t max_len, void *d_len, void *d_sp, void *d_ep, unsigned long long *counters,
+                                hipStream_t st) {
   if (n_bytes == 0) return hipSuccess;
   hipError_t he = hipSuccess;
 #define FMX_MS_CALL(W, L) \
@@ -244,8 +214,9 @@ hipError_t mstat_enqueue(const Index *h, const void *d_pat, const void *d_off, u
   return he;
 }
 
-uint64_t mstat_bytes(uint64_t n_bytes, bool mems) {
-  uint64_t need = kCounterBytes + 8 * kMsLineWords;
+// the device bytes mstat_run allocates
+static uint64_t mstat_bytes(uint64_t n_bytes, bool mems) {
+  uint64_t need = kMeteredBytes;
   if (mems) need += 20 * n_bytes + 4 * (n_bytes + 1) + 4 * scan_partials(n_bytes + 1) + 64;
   return need;
 }
@@ -261,21 +232,27 @@ int mstat_room(uint64_t need, const char *what) {
   return FMX_OK;
 }
 
-int mstat_run(const Index *h, const void *d_pat, const void *d_off, uint64_t k, uint64_t n_bytes, uint32_t max_len,
-              uint32_t min_len, void *d_len, void *d_sp, void *d_ep, bool mems, void *d_out_off, void *d_out, uint64_t cap,
-              hipStream_t st, MstatInfo *info) {
+struct MstatInfo {
+  uint64_t total = 0, steps = 0, requests = 0;
+  double walk_ms = 0.0, compact_ms = 0.0;       // device events: k_mstat, the flag / scan / write steps
+};
+
+// mstat_enqueue with the call's own counters and timing, and, with `mems`, the compaction into d_out_off[k + 1] / d_out[cap]
+// (the statistics are then temporaries of the call, d_len / d_sp / d_ep ignored); allocates, synchronises `st`, frees its
+// temporaries on every path.  info->total is the exact number of hits; records past cap are not written.
+static int mstat_run(const Index *h, const void *d_pat, const void *d_off, uint64_t k, uint64_t n_bytes, uint32_t max_len,
+                     uint32_t min_len, void *d_len, void *d_sp, void *d_ep, bool mems, void *d_out_off, void *d_out,
+                     uint64_t cap, hipStream_t st, MstatInfo *info) {
   *info = MstatInfo{};
   int rc = mstat_room(mstat_bytes(n_bytes, mems), mems ? "fmx_mems_batch" : "fmx_match_stats_batch");
   if (rc) return rc;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 3; i++) if (ev[i]) (void)hipEventDestroy(ev[i]); } } evg{ev};
-  for (int i = 0; i < 3; i++) HIP_TRY(hipEventCreate(&ev[i]), "hipEventCreate");
+  Events<3> ev;
+  HIP_TRY(ev.create(), "hipEventCreate");
   DevMem mem;
-  unsigned long long *line = nullptr, *mine = nullptr;
+  Metered own;
   uint32_t *len = static_cast<uint32_t *>(d_len), *flag = nullptr, *partials = nullptr;
   uint64_t *sp = static_cast<uint64_t *>(d_sp), *ep = static_cast<uint64_t *>(d_ep);
-  DEV_ALLOC(mem, line, 8 * kMsLineWords, "matching statistics");
-  DEV_ALLOC(mem, mine, kCounterBytes, "matching statistics");
+  if ((rc = own.alloc(mem, "matching statistics"))) return rc;
   if (mems) {
     DEV_ALLOC(mem, len, 4 * n_bytes, "MEM statistics");
     DEV_ALLOC(mem, sp, 8 * n_bytes, "MEM statistics");
@@ -283,45 +260,175 @@ int mstat_run(const Index *h, const void *d_pat, const void *d_off, uint64_t k, 
     DEV_ALLOC(mem, flag, 4 * (n_bytes + 1), "MEM flags");
     DEV_ALLOC(mem, partials, 4 * scan_partials(n_bytes + 1), "MEM scan");
   }
-  HIP_TRY(hipMemsetAsync(line, 0, 8 * kMsLineWords, st), "memset");
-  HIP_TRY(hipMemsetAsync(mine, 0, kCounterBytes, st), "memset");
-  HIP_TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+  if ((rc = own.zero(st))) return rc;
+  HIP_TRY(ev.record(0, st), "hipEventRecord");
   if (n_bytes) {
-    HIP_TRY(mstat_enqueue(h, d_pat, d_off, k, n_bytes, max_len, len, sp, ep, mine, st), "k_mstat");
-    hipLaunchKernelGGL(k_mstat_fold, dim3(kCounterSlots / 256), dim3(256), 0, st, mine, h->d_counters, line);
-    HIP_TRY(hipGetLastError(), "k_mstat_fold");
+    HIP_TRY(mstat_enqueue(h, d_pat, d_off, k, n_bytes, max_len, len, sp, ep, own.mine, st), "k_mstat");
+    if ((rc = own.fold(h, 1, st))) return rc;                // counter [1]: the backward steps
   }
-  HIP_TRY(hipEventRecord(ev[1], st), "hipEventRecord");
-  unsigned long long words[kMsLineWords];
+  HIP_TRY(ev.record(1, st), "hipEventRecord");
   uint32_t total = 0;
   if (mems) {
-    hipLaunchKernelGGL(k_mem_flag, dim3(ms_grid(n_bytes + 1)), dim3(256), 0, st, len, n_bytes, min_len, flag);
+    hipLaunchKernelGGL(k_mem_flag, dim3(flat_grid(n_bytes + 1)), dim3(256), 0, st, len, n_bytes, min_len, flag);
     HIP_TRY(hipGetLastError(), "k_mem_flag");
     HIP_TRY(scan_u32(flag, n_bytes + 1, kScanSum, true, partials, st), "scan");
-    hipLaunchKernelGGL(k_mem_write, dim3(ms_grid(std::max<uint64_t>(n_bytes, k + 1))), dim3(256), 0, st, flag, len, sp, ep,
+    hipLaunchKernelGGL(k_mem_write, dim3(flat_grid(std::max<uint64_t>(n_bytes, k + 1))), dim3(256), 0, st, flag, len, sp, ep,
                        static_cast<const uint64_t *>(d_off), k, n_bytes, cap, static_cast<unsigned long long *>(d_out_off),
                        static_cast<uint4 *>(d_out));
     HIP_TRY(hipGetLastError(), "k_mem_write");
-    HIP_TRY(hipEventRecord(ev[2], st), "hipEventRecord");
+    HIP_TRY(ev.record(2, st), "hipEventRecord");
     HIP_TRY(hipMemcpyAsync(&total, flag + n_bytes, 4, hipMemcpyDeviceToHost, st), "D2H");
   }
-  HIP_TRY(hipMemcpyAsync(words, line, sizeof words, hipMemcpyDeviceToHost, st), "D2H");
-  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");  // the temporaries go when this returns
-  {
-    std::lock_guard<std::mutex> lk(h->mu);
-    h->launches += n_bytes ? 1 : 0;
-  }
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
-  info->walk_ms = ms;
-  if (mems) {
-    (void)hipEventElapsedTime(&ms, ev[1], ev[2]);
-    info->compact_ms = ms;
-  }
+  MeterCounts cnt;
+  if ((rc = own.finish(h, st, n_bytes ? 1 : 0, &cnt))) return rc;
+  info->walk_ms = ev.ms(0, 1);
+  if (mems) info->compact_ms = ev.ms(1, 2);
   info->total = total;
-  info->steps = words[16];
-  info->requests = words[17];
+  info->steps = cnt.steps;
+  info->requests = cnt.requests;
   return FMX_OK;
 }
 
 }  // namespace fmx
+
+// ---------------------------------------------------------------- the C entry points (fmx.h)
+using namespace fmx;
+
+static thread_local MstatInfo g_mstat_last;
+
+// What refuses a call before the device is touched; max_len and min_len as the kernels take them.
+static int mstat_args(const fmx_index *idx, size_t k, uint64_t n_bytes, const fmx_mstat_opts *opts, uint32_t *max_len,
+                      uint32_t *min_len) {
+  *max_len = FMX_MSTAT_MAX_LEN;
+  *min_len = 1;
+  if (opts) {
+    if (opts->max_len > FMX_MSTAT_MAX_LEN) return arg_fail("fmx_mstat_opts.max_len: 1 .. 4096 (0 = the maximum)");
+    if (opts->reserved[0] != 0 || opts->reserved[1] != 0) return arg_fail("fmx_mstat_opts.reserved must be 0");
+    if (opts->max_len) *max_len = opts->max_len;
+    if (opts->min_len > *max_len) return arg_fail("fmx_mstat_opts: min_len > max_len");
+    if (opts->min_len) *min_len = opts->min_len;
+  }
+  if ((uint64_t)k > (1ull << 26)) return arg_fail("matching statistics: at most 2^26 patterns per call");
+  if (n_bytes >= (1ull << 32)) return arg_fail("matching statistics: n_bytes must be below 2^32");
+  if (!idx) return arg_fail("matching statistics: the handle is null");
+  return mstat_check(H(idx));
+}
+
+// the host forms' offsets: off[0] == 0, non-decreasing; *n_bytes = off[k]
+static int mstat_host_offsets(const uint64_t *off, size_t k, uint64_t *n_bytes) {
+  *n_bytes = 0;
+  if ((uint64_t)k > (1ull << 26)) return FMX_OK;           // (refused by mstat_args, with its own message)
+  if (k && !off) return arg_fail("null argument");
+  if (k && off[0] != 0) return arg_fail("matching statistics: off[0] must be 0");
+  if (k && !offsets_monotonic(off, 0, k)) return arg_fail("pattern offsets must be non-decreasing");
+  *n_bytes = k ? off[k] : 0;
+  return FMX_OK;
+}
+
+static int mems_args(const void *out_off, const void *out, size_t cap, const size_t *n_out) {
+  if (!n_out) return arg_fail("mems: n_out is null");
+  if ((uint64_t)cap >= (1ull << 32)) return arg_fail("mems: cap must be below 2^32");
+  if (!out_off || (cap && !out)) return arg_fail("null argument");
+  return FMX_OK;
+}
+
+extern "C" {
+
+int fmx_match_stats_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k, uint64_t n_bytes,
+                              const fmx_mstat_opts *opts, void *d_len, void *d_sp, void *d_ep, void *stream) {
+  uint32_t max_len, min_len;
+  if (n_bytes && !d_len) return arg_fail("matching statistics: d_len is null");
+  int rc = mstat_args(idx, k, n_bytes, opts, &max_len, &min_len);
+  if (rc) return rc;
+  if (n_bytes && (!d_pat || !d_off)) return arg_fail("null argument");
+  const Index *h = H(idx);
+  if ((rc = use_device(h))) return rc;
+  HIP_TRY(mstat_enqueue(h, d_pat, d_off, k, n_bytes, max_len, d_len, d_sp, d_ep, nullptr, (hipStream_t)stream), "k_mstat");
+  return FMX_OK;
+}
+
+int fmx_match_stats_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k, const fmx_mstat_opts *opts,
+                          uint32_t *out_len, uint64_t *out_sp, uint64_t *out_ep) {
+  uint32_t max_len, min_len;
+  uint64_t n_bytes;
+  int rc = mstat_host_offsets(off, k, &n_bytes);
+  if (rc) return rc;
+  if (n_bytes && n_bytes < (1ull << 32) && (!out_len || !pat)) return arg_fail("matching statistics: null argument");
+  if ((rc = mstat_args(idx, k, n_bytes, opts, &max_len, &min_len))) return rc;
+  const Index *h = H(idx);
+  if ((rc = use_device(h))) return rc;
+  const uint64_t outs = n_bytes * (4 + (out_sp ? 8 : 0) + (out_ep ? 8 : 0));
+  if ((rc = mstat_room(mstat_bytes(n_bytes, false) + n_bytes + 8 * ((uint64_t)k + 1) + outs + 64, "fmx_match_stats_batch"))) return rc;
+  HostCall hc;
+  void *d_pat = nullptr;
+  uint64_t *d_off = nullptr, *d_sp = nullptr, *d_ep = nullptr;
+  uint32_t *d_len = nullptr;
+  if ((rc = hc.open())) return rc;
+  if ((rc = hc.upload("patterns", pat, n_bytes, "offsets", off, k, false, &d_pat, &d_off))) return rc;
+  DEV_ALLOC(hc.mem, d_len, 4 * n_bytes, "matching statistics");
+  if (out_sp) DEV_ALLOC(hc.mem, d_sp, 8 * n_bytes, "matching statistics");
+  if (out_ep) DEV_ALLOC(hc.mem, d_ep, 8 * n_bytes, "matching statistics");
+  rc = mstat_run(h, d_pat, d_off, k, n_bytes, max_len, min_len, d_len, d_sp, d_ep, false, nullptr, nullptr, 0, hc.own.s, &g_mstat_last);
+  if (rc || !n_bytes) return rc;
+  if ((rc = hc.download(out_len, d_len, 4 * n_bytes, "D2H(len)")) || (rc = hc.download(out_sp, d_sp, 8 * n_bytes, "D2H(sp)")) ||
+      (rc = hc.download(out_ep, d_ep, 8 * n_bytes, "D2H(ep)")))
+    return rc;
+  return hc.sync();
+}
+
+int fmx_mems_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k, uint64_t n_bytes,
+                       const fmx_mstat_opts *opts, void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream) {
+  uint32_t max_len, min_len;
+  int rc = mems_args(d_out_off, d_out, cap, n_out);
+  if (rc) return rc;
+  if ((rc = mstat_args(idx, k, n_bytes, opts, &max_len, &min_len))) return rc;
+  if (!d_off || (n_bytes && !d_pat)) return arg_fail("null argument");
+  const Index *h = H(idx);
+  if ((rc = use_device(h))) return rc;
+  if ((rc = not_capturing((hipStream_t)stream, "a MEM call"))) return rc;
+  rc = mstat_run(h, d_pat, d_off, k, n_bytes, max_len, min_len, nullptr, nullptr, nullptr, true, d_out_off, d_out, cap,
+                 (hipStream_t)stream, &g_mstat_last);
+  if (rc) return rc;
+  *n_out = (size_t)g_mstat_last.total;
+  return g_mstat_last.total > cap ? csr_overflow("mems", g_mstat_last.total, cap) : FMX_OK;
+}
+
+int fmx_mems_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k, const fmx_mstat_opts *opts,
+                   uint64_t *out_off, fmx_mem_hit *out, size_t cap, size_t *n_out) {
+  uint32_t max_len, min_len;
+  uint64_t n_bytes;
+  int rc = mems_args(out_off, out, cap, n_out);
+  if (rc) return rc;
+  if ((rc = mstat_host_offsets(off, k, &n_bytes))) return rc;
+  if (n_bytes && n_bytes < (1ull << 32) && !pat) return arg_fail("pat is null");
+  if ((rc = mstat_args(idx, k, n_bytes, opts, &max_len, &min_len))) return rc;
+  const Index *h = H(idx);
+  if ((rc = use_device(h))) return rc;
+  if ((rc = mstat_room(mstat_bytes(n_bytes, true) + n_bytes + 16 * ((uint64_t)k + 1) + sizeof(fmx_mem_hit) * (uint64_t)cap + 64,
+                       "fmx_mems_batch"))) return rc;
+  HostCall hc;
+  void *d_pat = nullptr;
+  uint64_t *d_off = nullptr, *d_out_off = nullptr;
+  fmx_mem_hit *d_out = nullptr;
+  if ((rc = hc.open())) return rc;
+  if ((rc = hc.upload("patterns", pat, n_bytes, "offsets", off, k, false, &d_pat, &d_off))) return rc;
+  DEV_ALLOC(hc.mem, d_out_off, 8 * ((uint64_t)k + 1), "MEM offsets");
+  DEV_ALLOC(hc.mem, d_out, sizeof(fmx_mem_hit) * cap, "MEM hits");
+  rc = mstat_run(h, d_pat, d_off, k, n_bytes, max_len, min_len, nullptr, nullptr, nullptr, true, d_out_off, d_out, cap, hc.own.s,
+                 &g_mstat_last);
+  if (rc) return rc;
+  const uint64_t total = g_mstat_last.total;
+  *n_out = (size_t)total;
+  if (total > cap) return csr_overflow("mems", total, cap);
+  return hc.download_csr(out_off, d_out_off, k, out, d_out, total, sizeof(fmx_mem_hit));
+}
+
+int fmx_mstat_last(double *walk_ms, double *compact_ms, uint64_t *steps, uint64_t *requests) {
+  if (walk_ms) *walk_ms = g_mstat_last.walk_ms;
+  if (compact_ms) *compact_ms = g_mstat_last.compact_ms;
+  if (steps) *steps = g_mstat_last.steps;
+  if (requests) *requests = g_mstat_last.requests;
+  return FMX_OK;
+}
+
+}  // extern "C"

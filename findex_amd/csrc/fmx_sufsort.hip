@@ -378,12 +378,8 @@ int sufsort_bwt(const void *d_text, uint64_t len, void *d_bwt, void *d_sa_user, 
     hipLaunchKernelGGL(__VA_ARGS__);                                \
     HIP_TRY(hipGetLastError(), "suffix sort kernel launch");        \
   } while (0)
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 2; i++) if (ev[i]) (void)hipEventDestroy(ev[i]); } } evg{ev};
-  if (log_path) {
-    HIP_TRY(hipEventCreate(&ev[0]), "hipEventCreate");
-    HIP_TRY(hipEventCreate(&ev[1]), "hipEventCreate");
-  }
+  Events<2> ev;
+  if (log_path) HIP_TRY(ev.create(), "hipEventCreate");
   std::vector<RoundLog> rounds;
   HIP_TRY(hipMemsetAsync(out, 0, 8 * 257 + 8, st), "hipMemsetAsync");
   SA_LAUNCH(k_sa_reverse, dim3(sa_grid(n + 8)), dim3(kSaThreads), 0, st, static_cast<const uint8_t *>(d_text), len, s, flag);
@@ -398,7 +394,7 @@ int sufsort_bwt(const void *d_text, uint64_t len, void *d_bwt, void *d_sa_user, 
   uint64_t m = n, h = 0;
   uint32_t *list = nullptr;                   // the active list (SA positions); nullptr in round 1: all of them
   while (m > 0) {
-    if (log_path) HIP_TRY(hipEventRecord(ev[0], st), "hipEventRecord");
+    if (log_path) HIP_TRY(ev.record(0, st), "hipEventRecord");
     unsigned long long *k = k0, *ka = k1;
     uint32_t *v = v0, *va = v1;
     if (h == 0) SA_LAUNCH(k_sa_init, dim3(sa_grid(m)), dim3(kSaThreads), 0, st, s, n, k, v);
@@ -416,13 +412,9 @@ int sufsort_bwt(const void *d_text, uint64_t len, void *d_bwt, void *d_sa_user, 
     SA_LAUNCH(k_sa_compact, dim3(sa_grid(m)), dim3(kSaThreads), 0, st, keep, list, m, next);
     uint32_t m_next = 0;
     HIP_TRY(hipMemcpyAsync(&m_next, keep + (m - 1), 4, hipMemcpyDeviceToHost, st), "D2H");
-    if (log_path) HIP_TRY(hipEventRecord(ev[1], st), "hipEventRecord");
+    if (log_path) HIP_TRY(ev.record(1, st), "hipEventRecord");
     HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
-    if (log_path) {
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
-      rounds.push_back({h == 0 ? 8 : 2 * h, m, passes, ms, round_bytes(m, passes, h == 0)});
-    }
+    if (log_path) rounds.push_back({h == 0 ? 8 : 2 * h, m, passes, ev.ms(0, 1), round_bytes(m, passes, h == 0)});
     if ((uint64_t)m_next >= m && h != 0) {    // a round that separates nothing would loop for ever
       set_error("suffix sort made no progress (internal error)");
       return FMX_ERR_HIP;

@@ -326,6 +326,22 @@ class HipFMSearcher:
         """LCPCreator.create (bwtmerger.scala:558-652): write the reference's X.lcp (n - 1 big-endian int32)."""
         _lib.check(self._L.fmx_write_lcp(self._h, str(path).encode()))
 
+    @staticmethod
+    def _csr_hits(entry, args, k, dtype, cap):
+        """entry(*args, out_off, hits, cap, &n_out) -> (out_off[k + 1], hits[:n_out]).  cap=None: a counting call with no room
+        at all first; FMX_ERR_OVERFLOW then leaves the exact total in n_out, which sizes the buffer of the second call."""
+        n_out = ctypes.c_size_t()
+        out_off = np.zeros(k + 1, dtype=np.uint64)
+        if cap is None:
+            rc = entry(*args, _ptr(out_off), None, 0, ctypes.byref(n_out))
+            if rc != _lib.FMX_ERR_OVERFLOW:
+                _lib.check(rc)
+                return out_off, np.zeros(0, dtype=dtype)
+            cap = int(n_out.value)
+        hits = np.zeros(max(int(cap), 1), dtype=dtype)
+        _lib.check(entry(*args, _ptr(out_off), _ptr(hits), int(cap), ctypes.byref(n_out)))
+        return out_off, hits[: int(n_out.value)]
+
     # ---- approximate search: up to three substituted bytes (fmx_search_approx_batch, DESIGN.md 15)
     APPROX_HIT = np.dtype([("pattern", np.uint32), ("mismatches", np.uint32), ("sp", np.uint64), ("ep", np.uint64)])
 
@@ -345,19 +361,8 @@ class HipFMSearcher:
         off = np.ascontiguousarray(off, dtype=np.uint64)
         k = max(off.size - 1, 0)
         opts = self._approx_opts(max_mismatches, sub)
-        n_out = ctypes.c_size_t()
-        out_off = np.zeros(k + 1, dtype=np.uint64)
-        if cap is None:
-            rc = self._L.fmx_search_approx_batch(self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts), _ptr(out_off), None, 0,
-                                                 ctypes.byref(n_out))
-            if rc != 9:                      # FMX_ERR_OVERFLOW: n_out is the exact total
-                _lib.check(rc)
-                return out_off, np.zeros(0, dtype=self.APPROX_HIT)
-            cap = int(n_out.value)
-        hits = np.zeros(max(int(cap), 1), dtype=self.APPROX_HIT)
-        _lib.check(self._L.fmx_search_approx_batch(self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts), _ptr(out_off),
-                                                   _ptr(hits), int(cap), ctypes.byref(n_out)))
-        return out_off, hits[: int(n_out.value)]
+        return self._csr_hits(self._L.fmx_search_approx_batch, (self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts)), k,
+                              self.APPROX_HIT, cap)
 
     def search_approx(self, pat, max_mismatches, sub=(1, 255)):
         """One pattern: the list of (sp, ep, mismatches), by ascending sp."""
@@ -430,19 +435,7 @@ class HipFMSearcher:
         cap that is too small the library's FMX_ERR_OVERFLOW is raised."""
         pat, off, k = self._mstat_batch(pat, off)
         opts = self._mstat_opts(max_len, min_len)
-        n_out = ctypes.c_size_t()
-        out_off = np.zeros(k + 1, dtype=np.uint64)
-        if cap is None:
-            rc = self._L.fmx_mems_batch(self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts), _ptr(out_off), None, 0,
-                                        ctypes.byref(n_out))
-            if rc != 9:                      # FMX_ERR_OVERFLOW: n_out is the exact total
-                _lib.check(rc)
-                return out_off, np.zeros(0, dtype=self.MEM_HIT)
-            cap = int(n_out.value)
-        hits = np.zeros(max(int(cap), 1), dtype=self.MEM_HIT)
-        _lib.check(self._L.fmx_mems_batch(self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts), _ptr(out_off), _ptr(hits),
-                                          int(cap), ctypes.byref(n_out)))
-        return out_off, hits[: int(n_out.value)]
+        return self._csr_hits(self._L.fmx_mems_batch, (self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts)), k, self.MEM_HIT, cap)
 
     def mems_batch_dev(self, d_pat, d_off, k, n_bytes, min_len, d_out_off, d_out, cap, max_len=None, stream=0):
         """fmx_mems_batch_dev: device pointers (u64 out_off[k + 1], 32-byte hit records); allocates and synchronises.  -> the
