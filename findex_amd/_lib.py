@@ -72,6 +72,24 @@ class fmx_mem_hit(ctypes.Structure):
                 ("ep", ctypes.c_uint64)]
 
 
+FMX_REPEATS_ALL, FMX_REPEATS_LATER = 0, 1
+FMX_REPEATS_MAX_LEVELS = 64
+FMX_REPEATS_TILE = 2048               # elements per workgroup of the scans between the repeats passes (fmx.h)
+
+
+class fmx_repeat_opts(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_uint32), ("stop", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3)]
+
+
+class fmx_repeat_range(ctypes.Structure):
+    _fields_ = [("start", ctypes.c_uint64), ("end", ctypes.c_uint64)]
+
+
+class fmx_repeat_summary(ctypes.Structure):
+    _fields_ = [("ranges", ctypes.c_uint64), ("covered_bytes", ctypes.c_uint64), ("classes", ctypes.c_uint64),
+                ("windows", ctypes.c_uint64), ("largest_class", ctypes.c_uint64), ("largest_class_pos", ctypes.c_uint64)]
+
+
 class fmx_stats_t(ctypes.Structure):
     _fields_ = [("rank_queries", ctypes.c_uint64), ("backward_steps", ctypes.c_uint64),
                 ("launches", ctypes.c_uint64), ("last_kernel_ms", ctypes.c_double),
@@ -165,6 +183,9 @@ SYMBOLS = {
     "fmx_mems_batch": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_mstat_opts), _vp, _vp, _sz, _P(_sz)]),
     "fmx_mems_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _u64, _P(fmx_mstat_opts), _vp, _vp, _sz, _P(_sz), _vp]),
     "fmx_mstat_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(_u64), _P(_u64)]),
+    "fmx_repeats": (_i32, [_vp, _vp, _sz, _P(fmx_repeat_opts), _vp, _vp, _sz, _P(_sz), _vp]),
+    "fmx_repeats_dev": (_i32, [_vp, _vp, _sz, _P(fmx_repeat_opts), _vp, _vp, _sz, _P(_sz), _vp, _vp]),
+    "fmx_repeats_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double)]),
     "fmx_extract_text_batch": (_i32, [_vp, _vp, _vp, _sz, _vp]),
     "fmx_extract_text_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _u64, _vp, _vp]),
     "fmx_extract_info": (_i32, [_vp, _P(_u32), _P(_u64), _P(ctypes.c_double)]),

@@ -361,6 +361,31 @@ class HipCorpusSearcher:
             out = out[np.lexsort((out[:, 3], out[:, 2], out[:, 0]))]
         return out
 
+    # ---- the corpus against itself: which passages stand in it more than once (HipFMSearcher.repeats)
+    def duplicate_passages(self, min_len, keep_first=True):
+        """The stretches of the files whose every window of min_len stream bytes occurs more than once in the corpus: rows
+        (doc, raw_start, raw_end) of a uint64 array sorted by (doc, raw_start).  keep_first: the first occurrence of every
+        repeated window (in stream order: the documents' order) is left out, so the rows are what a reader may delete and
+        still find every passage once.  The repeats of the stream with the separator byte 1 as the stop byte, so no row
+        spans two files; the two ends of a range are mapped by the corpus.  min_len is in stream (escaped) bytes.  One known
+        limit: the stream is compared in its escaped form, so a range may begin or end inside an escape pair (the backslash
+        or the digit that stand for a raw 0, 1 or 255); its offsets are then those of the byte the pair stands for."""
+        ranges, _ = self.searcher.repeats(int(min_len), keep_first=keep_first, stop=1)
+        out = np.zeros((ranges.shape[0], 3), dtype=np.uint64)
+        if ranges.shape[0]:
+            doc, _, lo = self.corpus.map(ranges[:, 0])
+            _, _, hi = self.corpus.map(ranges[:, 1] - np.uint64(1))
+            out[:, 0], out[:, 1], out[:, 2] = doc, lo, hi + np.uint64(1)
+            out = out[np.lexsort((out[:, 1], out[:, 0]))]
+        return out
+
+    def duplicate_bytes(self, min_len, keep_first=True):
+        """The raw bytes of every document that duplicate_passages covers (uint64[n_docs])."""
+        rows = self.duplicate_passages(min_len, keep_first)
+        out = np.zeros(self.corpus.n_docs, dtype=np.uint64)
+        np.add.at(out, rows[:, 0].astype(np.int64), rows[:, 2] - rows[:, 1])
+        return out
+
     # ---- the text itself, from the index alone (HipFMSearcher.extract_text_batch): no stream in HBM, no X.data on disk
     def read(self, doc, raw_off, length):
         """The raw bytes [raw_off, raw_off + length) of document doc, clipped at the document's end (arrays or scalars) -> a

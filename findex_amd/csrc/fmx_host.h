@@ -440,6 +440,7 @@ int sufsort_bwt(const void *d_text, uint64_t len, void *d_bwt, void *d_sa_or_nul
 // key's low `bits` bits, 8 per pass; the result is in (*k, *v), the other pair of buffers is free afterwards; hist = 256 *
 // radix_tiles(m) u32, partials = scan_partials(max(m, 256 * radix_tiles(m))) u32; m < 2^32.  Both only enqueue on `st`.
 constexpr int kScanSum = 0, kScanMax = 1;
+constexpr uint32_t kScanTile = 2048;                // elements per scan block: 8 per thread
 uint64_t scan_partials(uint64_t len);
 uint64_t radix_tiles(uint64_t m);
 hipError_t scan_u32(uint32_t *d, uint64_t len, int op, bool exclusive, uint32_t *partials, hipStream_t st);

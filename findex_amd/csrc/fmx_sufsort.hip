@@ -35,7 +35,6 @@ namespace fmx {
 
 constexpr int kSaThreads = 256;
 constexpr uint32_t kSaTile = 4096;                  // keys per radix tile: 16 chunks of 256
-constexpr uint32_t kScanTile = 2048;                // elements per scan block: 8 per thread
 
 __device__ __forceinline__ uint32_t scan_op(int op, uint32_t a, uint32_t b) { return op == kScanMax ? (a > b ? a : b) : a + b; }
 

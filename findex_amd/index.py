@@ -1,5 +1,5 @@
-"""python -m findex_amd.index X.txt [--little-endian] [--device N] [--fm] [--sa] [--lcp]
-python -m findex_amd.index --dir D --out X [--no-filter-binary] [--data] [--little-endian] [--device N] [--fm] [--sa] [--lcp]
+"""python -m findex_amd.index X.txt [--little-endian] [--device N] [--fm] [--sa] [--lcp] [--dups L]
+python -m findex_amd.index --dir D --out X [--no-filter-binary] [--data] [--little-endian] [--device N] [--fm] [--sa] [--lcp] [--dups L]
 
 Writes X.bwt and X.aux next to the input (BWTTempStorage.genBWTFilename / genAuxFilename, bwtmerger.scala:17-24: the
 extension swapped), the files BWTMerger2.merge(FileBWTReader) writes -- the BWT of the reversed file -- big-endian
@@ -9,6 +9,11 @@ findex's readers escape it, and this tool does no escaping.
 --fm, --sa and --lcp add the sibling files the reference's IndexerApp and SACreator write (genFMFilename / genSAFilename /
 genLCPFilename: the extension swapped): X.fm (FMCreator), X.sa (SACreator: n big-endian int32) and X.lcp (LCPCreator:
 n - 1 big-endian int32), through the writers of the handle opened on the two files just written.
+
+--dups L (L >= 1) adds X.dups, the stretches of the input whose every window of L bytes occurs more than once
+(HipFMSearcher.repeats): one line start<TAB>end per range of the file.  With --dir it lists the passages a reader may delete
+and lose nothing -- every copy but the first (HipCorpusSearcher.duplicate_passages) -- as name<TAB>raw_start<TAB>raw_end, by
+document and offset; L is then in stream (escaped) bytes and no passage spans two files.
 
 --dir D --out X indexes a directory the way the reference's IndexerApp does through DirBWTReader (bwtreader.scala:17-173):
 the files of D in a fixed order, binary ones dropped unless --no-filter-binary, bytes 0, 1 and 255 escaped, a separator
@@ -32,6 +37,22 @@ def sibling_names(path):
     return base + ".fm", base + ".sa", base + ".lcp"
 
 
+def dups_threshold(text):
+    """--dups L: an int >= 1 (below 2^32, a threshold of fmx_repeats)."""
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("--dups takes an integer, got %r" % text)
+    if not 1 <= v < 2 ** 32:
+        raise argparse.ArgumentTypeError("--dups takes a length of at least 1")
+    return v
+
+
+def dups_name(a):
+    """X.dups: beside the other outputs."""
+    return a.out + ".dups" if getattr(a, "dir", None) else os.path.splitext(a.text)[0] + ".dups"
+
+
 def parser():
     ap = argparse.ArgumentParser(prog="python -m findex_amd.index", description=__doc__.split("\n\n")[1])
     ap.add_argument("text", nargs="?", help="the file to index (the single-file form)")
@@ -44,18 +65,21 @@ def parser():
     ap.add_argument("--fm", action="store_true", help="also write X.fm (FMCreator)")
     ap.add_argument("--sa", action="store_true", help="also write X.sa (SACreator)")
     ap.add_argument("--lcp", action="store_true", help="also write X.lcp (LCPCreator)")
+    ap.add_argument("--dups", type=dups_threshold, metavar="L", help="also write X.dups: the passages of L bytes and more that occur more than once")
     return ap
 
 
 def planned_outputs(a):
     """The files a run with the parsed arguments `a` writes, in the order it writes them."""
+    dups = getattr(a, "dups", None)
     if getattr(a, "dir", None):
         base = a.out + ".x"             # (the name functions swap an extension: OUT itself is the stem)
         fm, sa, lcp = sibling_names(base)
         return list(output_names(base)) + [a.out + ".docs"] + ([a.out + ".data"] if a.data else []) + \
-            ([fm] if a.fm else []) + ([sa] if a.sa else []) + ([lcp] if a.lcp else [])
+            ([fm] if a.fm else []) + ([sa] if a.sa else []) + ([lcp] if a.lcp else []) + ([dups_name(a)] if dups else [])
     fm, sa, lcp = sibling_names(a.text)
-    return list(output_names(a.text)) + ([fm] if a.fm else []) + ([sa] if a.sa else []) + ([lcp] if a.lcp else [])
+    return list(output_names(a.text)) + ([fm] if a.fm else []) + ([sa] if a.sa else []) + ([lcp] if a.lcp else []) + \
+        ([dups_name(a)] if dups else [])
 
 
 def main_dir(a):
@@ -79,6 +103,18 @@ def main_dir(a):
         if a.data:
             stream.tofile(a.out + ".data")
             print("%s: -> %s" % (a.dir, a.out + ".data"))
+        if getattr(a, "dups", None):
+            from .corpus import HipCorpusSearcher
+            from .searcher import HipFMSearcher
+            hip = HipFMSearcher.from_mem(bwt, eof, counts, device=a.device)
+            try:
+                rows = HipCorpusSearcher(corpus, hip).duplicate_passages(a.dups, keep_first=True)
+            finally:
+                hip.close()
+            with open(dups_name(a), "wb") as f:         # (the names are bytes, as the listing gave them)
+                for d, lo, hi in rows:
+                    f.write(corpus.names[int(d)] + b"\t%d\t%d\n" % (lo, hi))
+            print("%s: %d duplicated passages -> %s" % (a.dir, rows.shape[0], dups_name(a)))
     finally:
         corpus.close()
     if a.fm or a.sa or a.lcp:
@@ -118,7 +154,7 @@ def main(argv=None):
     bwt_path, aux_path = output_names(a.text)
     write_bwt(bwt_path, aux_path, bwt, eof, counts, bigEndian=not a.little_endian)
     print("%s: n = %d, eof = %d -> %s, %s" % (a.text, bwt.size, eof, bwt_path, aux_path))
-    if a.fm or a.sa or a.lcp:
+    if a.fm or a.sa or a.lcp or a.dups:
         from .searcher import HipFMSearcher
         fm_path, sa_path, lcp_path = sibling_names(a.text)
         hip = HipFMSearcher.from_mem(bwt, eof, counts, device=a.device)
@@ -127,6 +163,12 @@ def main(argv=None):
                 if wanted:
                     write(path)
                     print("%s: -> %s" % (a.text, path))
+            if a.dups:
+                ranges, _ = hip.repeats(a.dups)
+                with open(dups_name(a), "w") as f:
+                    for lo, hi in ranges:
+                        f.write("%d\t%d\n" % (lo, hi))
+                print("%s: %d repeated ranges -> %s" % (a.text, ranges.shape[0], dups_name(a)))
         finally:
             hip.close()
     return 0

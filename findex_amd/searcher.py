@@ -488,6 +488,58 @@ class HipFMSearcher:
         _lib.check(self._L.fmx_extract_last(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return float(a.value), int(b.value), int(c.value)
 
+    # ---- repeats: the stretches of the indexed text that occur more than once (fmx_repeats)
+    REPEAT_SUMMARY = ("ranges", "covered_bytes", "classes", "windows", "largest_class", "largest_class_pos")
+
+    @staticmethod
+    def _repeat_args(min_len, keep_first, stop):
+        single = np.ndim(min_len) == 0
+        levels = [int(x) for x in ([min_len] if single else min_len)]
+        if any(not 0 <= x < 2 ** 32 for x in levels) or not 0 <= int(stop) <= 255:
+            raise ValueError("min_len or stop out of range")
+        lv = np.array(levels, dtype=np.uint32)
+        opts = _lib.fmx_repeat_opts(_lib.FMX_REPEATS_LATER if keep_first else _lib.FMX_REPEATS_ALL, int(stop), (0, 0, 0))
+        return single, lv, opts
+
+    def repeats(self, min_len, keep_first=False, stop=0):
+        """fmx_repeats: the stretches of the text whose every window of min_len bytes occurs at least twice ->
+        (ranges, summary): ranges a uint64[r, 2] array of [start, end) text offsets, ascending and maximal, summary a dict
+        (ranges, covered_bytes, classes, windows, largest_class, largest_class_pos).  keep_first: the first occurrence of
+        every repeated window is left out ("every copy but the first").  stop != 0: a window that holds that byte does not
+        count, so no range covers it.  min_len a sequence: one call for all thresholds (the suffix array is made once) and
+        a list of such pairs.  The handle indexes reverse(text) as from_text has it.  A counting call sizes the buffer."""
+        single, lv, opts = self._repeat_args(min_len, keep_first, stop)
+        k = lv.size
+        n_out = ctypes.c_size_t()
+        off = np.zeros(k + 1, dtype=np.uint64)
+        sums = (_lib.fmx_repeat_summary * max(k, 1))()
+        rc = self._L.fmx_repeats(self._h, _ptr(lv), k, ctypes.byref(opts), _ptr(off), None, 0, ctypes.byref(n_out), sums)
+        total = int(n_out.value)
+        out = np.zeros((max(total, 1), 2), dtype=np.uint64)
+        if rc == _lib.FMX_ERR_OVERFLOW:
+            rc = self._L.fmx_repeats(self._h, _ptr(lv), k, ctypes.byref(opts), _ptr(off), _ptr(out), total, ctypes.byref(n_out), sums)
+        _lib.check(rc)
+        res = [(out[int(off[j]):int(off[j + 1])].copy(), {f: int(getattr(sums[j], f)) for f in self.REPEAT_SUMMARY})
+               for j in range(k)]
+        return res[0] if single else res
+
+    def repeats_dev(self, min_len, d_out_off, d_out, cap, keep_first=False, stop=0, stream=0):
+        """fmx_repeats_dev: u64 out_off[k + 1] and 16-byte (start, end) records in device memory; allocates and
+        synchronises.  -> (the exact number of ranges, the list of summaries); FMX_ERR_OVERFLOW is raised when the ranges
+        exceed cap."""
+        _, lv, opts = self._repeat_args(min_len, keep_first, stop)
+        n_out = ctypes.c_size_t()
+        sums = (_lib.fmx_repeat_summary * max(lv.size, 1))()
+        _lib.check(self._L.fmx_repeats_dev(self._h, _ptr(lv), lv.size, ctypes.byref(opts), _dp(d_out_off), _dp(d_out), int(cap),
+                                           ctypes.byref(n_out), sums, _dp(stream)))
+        return int(n_out.value), [{f: int(getattr(sums[j], f)) for f in self.REPEAT_SUMMARY} for j in range(lv.size)]
+
+    def repeats_last(self):
+        """fmx_repeats_last: (inversion ms, class passes ms, coverage passes ms, compaction ms) of this thread's last call."""
+        v = [ctypes.c_double() for _ in range(4)]
+        _lib.check(self._L.fmx_repeats_last(*[ctypes.byref(x) for x in v]))
+        return tuple(float(x.value) for x in v)
+
     def match_stats_text(self, q, max_len=None):
         """ms[i] = the length of the longest prefix of q[i:] that occurs in the indexed text (capped at max_len), for a handle
         that indexes reverse(text) as from_text and locate_text have it: the statistics of reverse(q), flipped."""

@@ -586,6 +586,64 @@ int fmx_mems_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_of
                        const fmx_mstat_opts *opts, void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream);
 int fmx_mstat_last(double *walk_ms, double *compact_ms, uint64_t *steps, uint64_t *requests);
 
+/* ---- repeats: the stretches of the indexed text that occur more than once, from the LCP array.  Beyond the reference, whose
+ * one consumer of the array is an unfinished experiment.  DESIGN.md 18.
+ * Definitions.  T is the text of m = n - 1 bytes, L >= 1 a threshold.  The WINDOW at t (0 <= t <= m - L) is T[t .. t + L).
+ * With a stop byte c != 0 a window that contains c is not ELIGIBLE; with c == 0 every window is (byte 0 never occurs in a
+ * text).  A CLASS is the set of all eligible windows with the same L bytes -- occurrences may overlap: "aaaa" at L = 2 has
+ * one class of three windows -- and it is REPEATED when it has at least two windows.  The MODE decides which windows of a
+ * repeated class are FLAGGED: FMX_REPEATS_ALL every one of them, FMX_REPEATS_LATER every one but the one with the smallest t
+ * ("keep the first copy").  The RESULT is the union of [t, t + L) over the flagged windows, reported as its maximal ranges
+ * [start, end) in text offsets, ascending; two ranges that abut are one range.  A stop byte is never covered, so with a
+ * corpus' separator as the stop byte no range spans two documents.  The SUMMARY of a threshold: the number of ranges, the
+ * covered bytes, the repeated classes, the flagged windows, the size of the largest repeated class and the smallest text
+ * offset of a window of that class (among classes of that size: the smallest such offset); all 0 when nothing repeats.
+ * The same input gives the same bytes on every run.
+ * In the index's terms (s = reverse(T) + sentinel, SA and LCP as for locate and the LCP array): window t is s[p .. p + L)
+ * with p = m - t - L; the windows of one class are a maximal run of rows whose consecutive LCP[r] >= L; a row belongs to a
+ * repeated class iff LCP[r - 1] >= L or LCP[r] >= L; the smallest t is the largest SA value of the run.
+ * One call takes k thresholds (1 .. FMX_REPEATS_MAX_LEVELS) and pays for the suffix array once: one inversion, then one set
+ * of streaming passes per threshold.  Output is CSR: threshold j's ranges are out[out_off[j] .. out_off[j + 1]),
+ * out_off[k] == *n_out.  Capacity: with more than cap ranges the call returns FMX_ERR_OVERFLOW with the exact total in
+ * *n_out, out_off complete and the summaries valid; nothing is written past out[cap - 1]; cap == 0 with out == NULL is the
+ * counting call.  opts == NULL: FMX_REPEATS_ALL and no stop byte.  A threshold above m is valid and has no ranges.
+ * FMX_ERR_ARG, decided before the device is touched: a null handle, min_len, out_off or n_out; k == 0 or k >
+ * FMX_REPEATS_MAX_LEVELS; a threshold of 0; a mode above 1; a reserved byte that is not 0; cap >= 2^32.
+ * The call needs the handle's LCP array and builds it when absent, with its refusals: fmx_open_block handles and n >= 2^32
+ * FMX_ERR_UNSUPPORTED, an index that is not the BWT of one text FMX_ERR_FORMAT.  Both forms ALLOCATE AND SYNCHRONISE (the
+ * _dev form: FMX_ERR_HIP under a stream capture, decided before anything is allocated, the capture left valid).  The need --
+ * about 18 bytes per row beside the LCP array: the suffix array, s, two u32 work arrays, the stop scan and the flags, plus
+ * the inversion's temporaries and the LCP build's when that is still to come -- is checked against the free HBM first
+ * (FMX_ERR_NOMEM with the need in the message); every temporary is freed on every path.  No table and no counter of patterns
+ * seen changes; the launches are added to the handle's.
+ * fmx_repeats_dev : d_out_off (u64[k + 1]) and d_out (16-byte records) in device memory; min_len, n_out and the summaries
+ *                   stay host pointers.
+ * fmx_repeats_last: device time (ms) of the calling thread's last call by phase -- the inversion (with the stop scan), the
+ *                   class passes, the coverage passes, the compaction -- summed over the thresholds; any pointer may be NULL.
+ * FMX_REPEATS_TILE: the elements one workgroup of the scans takes -- where a carry crosses from one workgroup's stretch of
+ * rows or text bytes to the next (what tests aim at). */
+#define FMX_REPEATS_ALL 0u
+#define FMX_REPEATS_LATER 1u
+#define FMX_REPEATS_MAX_LEVELS 64
+#define FMX_REPEATS_TILE 2048
+typedef struct fmx_repeat_opts {
+  uint32_t mode;       /* FMX_REPEATS_ALL | FMX_REPEATS_LATER */
+  uint8_t stop;        /* the stop byte; 0 = none */
+  uint8_t reserved[3]; /* must be 0 */
+} fmx_repeat_opts;
+typedef struct fmx_repeat_range {
+  uint64_t start, end;
+} fmx_repeat_range; /* 16 bytes */
+typedef struct fmx_repeat_summary {
+  uint64_t ranges, covered_bytes, classes, windows, largest_class, largest_class_pos;
+} fmx_repeat_summary; /* 48 bytes */
+int fmx_repeats(const fmx_index *idx, const uint32_t *min_len, size_t k, const fmx_repeat_opts *opts,
+                uint64_t *out_off /* k + 1 */, fmx_repeat_range *out, size_t cap, size_t *n_out,
+                fmx_repeat_summary *summary_or_null /* k */);
+int fmx_repeats_dev(const fmx_index *idx, const uint32_t *min_len, size_t k, const fmx_repeat_opts *opts, void *d_out_off,
+                    void *d_out, size_t cap, size_t *n_out, fmx_repeat_summary *summary_or_null /* k */, void *stream);
+int fmx_repeats_last(double *invert_ms, double *class_ms, double *cover_ms, double *compact_ms);
+
 /* ---- corpus: a directory of files as ONE index -- DirBWTReader (bwtreader.scala:17-173), the input side of the reference's
  * IndexerApp -- and, beyond the reference, the way back from a stream position to (document, offset).
  * The STREAM: the documents in the caller's order; in each, raw byte 0 becomes '\' '0', raw 1 becomes '\' '1' and raw 255
