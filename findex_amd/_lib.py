@@ -55,6 +55,20 @@ class fmx_approx_opts(ctypes.Structure):
                 ("reserved", ctypes.c_uint16)]
 
 
+FMX_EDIT_MAX_EDITS = 2
+FMX_EDIT_MAX_LEN = 255                # pattern bytes of the edit-distance search (fmx.h)
+
+
+class fmx_edit_hit(ctypes.Structure):
+    _fields_ = [("pattern", ctypes.c_uint32), ("edits", ctypes.c_uint16), ("len", ctypes.c_uint16), ("sp", ctypes.c_uint64),
+                ("ep", ctypes.c_uint64)]
+
+
+class fmx_edit_opts(ctypes.Structure):
+    _fields_ = [("max_edits", ctypes.c_uint32), ("sub_lo", ctypes.c_uint8), ("sub_hi", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint16)]
+
+
 FMX_MSTAT_MAX_LEN = 4096
 FMX_MSTAT_TILE = 512                  # positions per workgroup tile of the walk kernel (fmx.h)
 MSTAT_GROUPS = {"onehot": 16, "bytes": 8}      # lane groups per wave: quads, octets (fmx_device.h, Lay<LAYOUT>::G)
@@ -178,6 +192,9 @@ SYMBOLS = {
     "fmx_search_approx_batch": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_approx_opts), _vp, _vp, _sz, _P(_sz)]),
     "fmx_search_approx_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_approx_opts), _vp, _vp, _sz, _P(_sz), _vp]),
     "fmx_approx_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(_u64), _P(_u64)]),
+    "fmx_search_edit_batch": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_edit_opts), _vp, _vp, _sz, _P(_sz)]),
+    "fmx_search_edit_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_edit_opts), _vp, _vp, _sz, _P(_sz), _vp]),
+    "fmx_edit_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(_u64), _P(_u64)]),
     "fmx_match_stats_batch": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_mstat_opts), _vp, _vp, _vp]),
     "fmx_match_stats_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _u64, _P(fmx_mstat_opts), _vp, _vp, _vp, _vp]),
     "fmx_mems_batch": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_mstat_opts), _vp, _vp, _sz, _P(_sz)]),

@@ -337,6 +337,29 @@ class HipCorpusSearcher:
         order = np.lexsort((raw, doc))
         return doc[order], raw[order], mism[order]
 
+    def locate_docs_edits(self, q, max_edits, max_hits=None):
+        """Where strings within max_edits (0 .. 2) substitutions, insertions and deletions of the raw bytes q stand in the
+        files: (doc, raw_off, stream_len, edits) arrays sorted by (doc, raw_off, stream_len).  q is escaped and its reverse
+        searched (HipFMSearcher.search_edit_batch), every hit's rows located with the hit's own length and the positions
+        mapped; stream_len is the length of the string that stands there, in stream (escaped) bytes; max_hits bounds the
+        rows taken of every distinct matching string.  Bytes are substituted and inserted from 2 .. 254 only, so the
+        separator byte 1 is never one of them and no hit spans two files.  One known limit, that of locate_docs: q is compared
+        in its escaped form, so an edit may fall on one half of an escape pair (the backslash or the digit that stand for a
+        raw 0, 1 or 255) -- such a stretch counts one edit although its raw bytes differ otherwise, and a stretch whose raw
+        bytes differ in an escaped byte may be missed."""
+        esc = escape(q)
+        if not esc:
+            raise ValueError("empty pattern")
+        _, hits = self.searcher.search_edit_batch(np.frombuffer(esc[::-1], dtype=np.uint8), np.array([0, len(esc)], dtype=np.uint64),
+                                                  int(max_edits), sub=(2, 254))
+        off, sa = self.searcher.locate_intervals(hits["sp"], hits["ep"], max_per=max_hits)
+        per = np.diff(off).astype(np.int64)
+        ln = np.repeat(hits["len"], per).astype(np.uint64)
+        edits = np.repeat(hits["edits"], per).astype(np.uint32)
+        doc, _, raw = self.corpus.map(np.uint64(self.searcher.n - 1) - ln - sa)
+        order = np.lexsort((ln, raw, doc))
+        return doc[order], raw[order], ln[order], edits[order]
+
     def shared_passages(self, q, min_len, max_len=None, max_per=None):
         """Which stretches of the raw bytes q stand in the corpus, and where: rows (q_off, len, doc, raw_off) of a uint64
         array sorted by (q_off, doc, raw_off) -- the passage that begins at byte q_off of q begins at byte raw_off of

@@ -387,6 +387,67 @@ class HipFMSearcher:
         _lib.check(self._L.fmx_approx_last(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
         return float(a.value), float(b.value), int(c.value), int(d.value)
 
+    # ---- approximate search with insertions and deletions: edit distance up to two (fmx_search_edit_batch)
+    EDIT_HIT = np.dtype([("pattern", np.uint32), ("edits", np.uint16), ("len", np.uint16), ("sp", np.uint64), ("ep", np.uint64)])
+
+    @staticmethod
+    def _edit_opts(max_edits, sub):
+        lo, hi = (int(sub[0]), int(sub[1]))
+        if not (0 <= lo <= 255 and 0 <= hi <= 255 and 0 <= int(max_edits) < 2 ** 32):
+            raise ValueError("max_edits or sub out of range")
+        return _lib.fmx_edit_opts(int(max_edits), lo, hi, 0)
+
+    def search_edit_batch(self, pat, off, max_edits, sub=(1, 255), cap=None):
+        """fmx_search_edit_batch: every string within max_edits (0 .. 2) substitutions, insertions and deletions of each
+        pattern (at most 255 bytes) that occurs, the substituted and inserted bytes taken from sub = (lo, hi).
+        -> (off[k + 1], hits): pattern q's hits are hits[off[q]:off[q + 1]], a structured array (pattern, edits, len, sp,
+        ep) by ascending (sp, len); len is the length of the string that occurs.  cap=None: a counting call sizes the
+        buffer; with a cap that is too small the library's FMX_ERR_OVERFLOW is raised."""
+        pat = np.ascontiguousarray(pat, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        k = max(off.size - 1, 0)
+        opts = self._edit_opts(max_edits, sub)
+        return self._csr_hits(self._L.fmx_search_edit_batch, (self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts)), k,
+                              self.EDIT_HIT, cap)
+
+    def search_edit(self, pat, max_edits, sub=(1, 255)):
+        """One pattern: the list of (sp, ep, len, edits), by ascending (sp, len)."""
+        pat = bytes(pat)
+        _, hits = self.search_edit_batch(np.frombuffer(pat, dtype=np.uint8), np.array([0, len(pat)], dtype=np.uint64),
+                                         max_edits, sub)
+        return [(int(h["sp"]), int(h["ep"]), int(h["len"]), int(h["edits"])) for h in hits]
+
+    def search_edit_batch_dev(self, d_pat, d_off, k, max_edits, d_out_off, d_out, cap, sub=(1, 255), stream=0):
+        """fmx_search_edit_batch_dev: device pointers (u8 patterns, u64 offsets[k + 1], u64 out_off[k + 1], 24-byte hit
+        records); allocates and synchronises.  -> the exact number of hits (FMX_ERR_OVERFLOW is raised when it exceeds cap)."""
+        opts = self._edit_opts(max_edits, sub)
+        n_out = ctypes.c_size_t()
+        _lib.check(self._L.fmx_search_edit_batch_dev(self._h, _dp(d_pat), _dp(d_off), int(k), ctypes.byref(opts), _dp(d_out_off),
+                                                     _dp(d_out), int(cap), ctypes.byref(n_out), _dp(stream)))
+        return int(n_out.value)
+
+    def edit_last(self):
+        """fmx_edit_last: (search kernel ms, ordering ms, backward steps, rank-dictionary requests) of this thread's last
+        edit-distance search."""
+        a, b, c, d = ctypes.c_double(), ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64()
+        _lib.check(self._L.fmx_edit_last(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
+        return float(a.value), float(b.value), int(c.value), int(d.value)
+
+    def locate_text_edits(self, q, max_edits, max_hits=None):
+        """Where strings within max_edits edits of the text string q stand in the indexed text: rows (text offset, len,
+        edits) of a uint64 array sorted by (offset, len) -- the reverse of q is searched and every hit's rows are located
+        with the hit's own len (text_offsets); max_hits bounds the rows taken of every distinct matching string.  A stretch
+        of the text may appear with several lengths."""
+        q = bytes(q)
+        _, hits = self.search_edit_batch(np.frombuffer(q[::-1], dtype=np.uint8), np.array([0, len(q)], dtype=np.uint64), max_edits)
+        off, sa = self.locate_intervals(hits["sp"], hits["ep"], max_per=max_hits)
+        per = np.diff(off).astype(np.int64)
+        out = np.zeros((sa.size, 3), dtype=np.uint64)
+        out[:, 1] = np.repeat(hits["len"], per)
+        out[:, 2] = np.repeat(hits["edits"], per)
+        out[:, 0] = np.uint64(self.n - 1) - out[:, 1] - sa
+        return out[np.lexsort((out[:, 1], out[:, 0]))]
+
     # ---- matching statistics and maximal exact matches (fmx_match_stats_batch, fmx_mems_batch, DESIGN.md 16)
     MEM_HIT = np.dtype([("pattern", np.uint32), ("len", np.uint32), ("end", np.uint64), ("sp", np.uint64), ("ep", np.uint64)])
 

@@ -490,7 +490,7 @@ int fmx_extract_info(const fmx_index *idx, uint32_t *rate, uint64_t *bytes, doub
 int fmx_extract_last(double *ms, uint64_t *steps, uint64_t *requests);
 
 /* ---- approximate search: literal patterns with up to FMX_APPROX_MAX_MISMATCHES substituted bytes (Hamming distance; no
- * insertions or deletions).  Beyond the reference.  DESIGN.md 15.
+ * insertions or deletions: those are fmx_search_edit_batch, below).  Beyond the reference.  DESIGN.md 15.
  * For pattern P of m bytes (matched last byte first, as fmx_search_batch takes it), a budget e = max_mismatches and a
  * substitution range [sub_lo, sub_hi], a HIT is a byte string Q of m bytes that differs from P in d <= e positions, holds a
  * byte of the range at every differing position, and for which the reference's search(Q) loop (findex.scala:15-31) ends with
@@ -533,6 +533,62 @@ int fmx_search_approx_batch_dev(const fmx_index *idx, const void *d_pat, const v
                                 const fmx_approx_opts *opts, void *d_out_off, void *d_out, size_t cap, size_t *n_out,
                                 void *stream);
 int fmx_approx_last(double *search_ms, double *sort_ms, uint64_t *steps, uint64_t *requests);
+
+/* ---- approximate search with insertions and deletions: edit distance up to FMX_EDIT_MAX_EDITS.  Beyond the reference.
+ * DESIGN.md 19.
+ * P is a pattern of m bytes (matched last byte first, as everywhere), e = max_edits the budget, A = [sub_lo, sub_hi] the
+ * symbol range (sub_lo >= 1; 0, 0 = the default 1 .. 255).  d_A(Q, P) is the smallest cost of an alignment of Q with P in which
+ *   - equal bytes cost 0, whatever the byte (0 included);
+ *   - a Q byte of A standing for a different P byte costs 1 (substitution);
+ *   - a Q byte of A standing for nothing costs 1 (insertion);
+ *   - a P byte standing for nothing costs 1, whatever the byte (deletion);
+ *   - a Q byte outside A may only stand for an equal P byte.
+ * With the default range and no byte 0 in the text d_A is the Levenshtein distance.
+ * A HIT is a byte string Q of any length (necessarily m - e .. m + e) with d = d_A(Q, P) <= e for which the reference's
+ * search(Q) loop (findex.scala:15-31) ends with sp < ep.  It is reported as (pattern, d, len = |Q|, sp, ep) with (sp, ep)
+ * exactly what fmx_search_batch returns for Q.  The empty Q is a hit when m <= e (d = m, the interval (0, n), len 0); an empty
+ * P therefore has the hit (0, n) with d = 0 and every occurring string over A of 1 .. e bytes.  With e = 0 the hits are those
+ * of the exact search, with len = m.  The definition rests on cf / occ alone, so it holds for any handle.  Distinct Q of one
+ * length have disjoint intervals; Q of different lengths may share sp.
+ * Results are in CSR form: pattern q's hits are out[out_off[q] .. out_off[q + 1]), by ascending (sp, len) (unique within a
+ * pattern), out_off[k] == *n_out: the same input gives the same bytes on every run.
+ * opts == NULL: e = 0 and the default range.
+ * Capacity, the counting call and the refusals are those of fmx_search_approx_batch: more than cap hits -> nothing is written
+ * past out[cap - 1], FMX_ERR_OVERFLOW with *n_out = the EXACT total (out and out_off then unspecified); cap == 0 with
+ * out == NULL is the counting call.
+ * FMX_ERR_ARG, decided before the device is touched: a null handle, n_out or out_off; max_edits above the maximum;
+ * sub_lo > sub_hi, or exactly one of them 0; reserved != 0; decreasing offsets (host form); k > 2^23; cap >= 2^32; a pattern
+ * of more than FMX_EDIT_MAX_LEN bytes (host form).  The device form cannot see the lengths: its kernel skips such a pattern
+ * and raises a flag, and the call returns FMX_ERR_ARG after the launch with no hits written and *n_out untouched.
+ * FMX_ERR_UNSUPPORTED: fmx_open_block handles (and indexes of 2^38 rows or more).
+ * Both forms ALLOCATE AND SYNCHRONISE (FMX_ERR_HIP under a stream capture) and free every temporary on every path.  The
+ * working set: 24 cap bytes of staging; the walk's stacks, 258 frames of 320 bytes (82 560 bytes) for every wave of the launch,
+ * four waves per workgroup and at most the workgroups the device holds at once (one per four patterns for a small batch; about
+ * 0.6 GB at 1792 workgroups); 24 bytes per hit of sort keys and values; a quarter megabyte of counters.  Staging, stacks and
+ * counters are checked against the free device memory first: FMX_ERR_NOMEM with the need in the message.
+ * The calls use the rank dictionary only, build no derived table and do not count as patterns seen; their steps are added to
+ * the handle's counters (rank_queries, backward_steps, search_requests) and the call to launches.
+ * fmx_edit_last: the calling thread's last call: device time (ms) of the search kernel and of the ordering step, backward
+ * steps executed, rank-dictionary requests issued; any pointer may be NULL. */
+#define FMX_EDIT_MAX_EDITS 2
+#define FMX_EDIT_MAX_LEN 255 /* pattern bytes */
+typedef struct fmx_edit_hit {
+  uint32_t pattern;
+  uint16_t edits;
+  uint16_t len; /* bytes of the string that occurs */
+  uint64_t sp;
+  uint64_t ep;
+} fmx_edit_hit; /* 24 bytes */
+typedef struct fmx_edit_opts {
+  uint32_t max_edits;     /* 0 .. FMX_EDIT_MAX_EDITS */
+  uint8_t sub_lo, sub_hi; /* symbols that may be inserted or substituted, inclusive; 0,0 = the default 1 .. 255 */
+  uint16_t reserved;      /* must be 0 */
+} fmx_edit_opts;
+int fmx_search_edit_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k, const fmx_edit_opts *opts,
+                          uint64_t *out_off /* k + 1 */, fmx_edit_hit *out, size_t cap, size_t *n_out);
+int fmx_search_edit_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k, const fmx_edit_opts *opts,
+                              void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream);
+int fmx_edit_last(double *search_ms, double *sort_ms, uint64_t *steps, uint64_t *requests);
 
 /* ---- matching statistics and maximal exact matches (MEMs) of long queries.  Beyond the reference.  DESIGN.md 16.
  * The batch is k patterns, contiguous in pat: pattern q is pat[off[q] .. off[q + 1]), off[0] == 0, off[k] == n_bytes.  The
