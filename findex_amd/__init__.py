@@ -17,6 +17,8 @@ package is the thin host-side mirror of the reference's Scala interface for that
                                                    Corpus.to_stream (the inverse of Corpus.map), corpus.unescape_ranges
                                                    HipFMSearcher.extract_text / .extract_text_batch (text by position),
                                                    HipCorpusSearcher.read / .document / .snippets
+                                                   HipFMSearcher.occurrences / .finditer (where regexes and hits stand),
+                                                   HipCorpusSearcher.grep, python -m findex_amd.grep
 
 There is no CPU fallback: importing works anywhere, but every compute call needs the built
 library and a HIP device and fails loudly otherwise.

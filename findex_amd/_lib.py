@@ -104,6 +104,19 @@ class fmx_repeat_summary(ctypes.Structure):
                 ("windows", ctypes.c_uint64), ("largest_class", ctypes.c_uint64), ("largest_class_pos", ctypes.c_uint64)]
 
 
+FMX_OCC_ALL, FMX_OCC_LONGEST, FMX_OCC_DISJOINT = 0, 1, 2
+FMX_OCC_MAX_LEN = 65535               # bytes of an occurrence (fmx.h)
+
+
+class fmx_occ_opts(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("max_per", ctypes.c_uint64)]
+
+
+class fmx_occurrence(ctypes.Structure):
+    _fields_ = [("group", ctypes.c_uint32), ("len", ctypes.c_uint32), ("pos", ctypes.c_uint64), ("doc", ctypes.c_uint32),
+                ("raw_len", ctypes.c_uint32), ("raw_off", ctypes.c_uint64)]
+
+
 class fmx_stats_t(ctypes.Structure):
     _fields_ = [("rank_queries", ctypes.c_uint64), ("backward_steps", ctypes.c_uint64),
                 ("launches", ctypes.c_uint64), ("last_kernel_ms", ctypes.c_double),
@@ -239,6 +252,9 @@ SYMBOLS = {
     "fmx_regex_batch_info": (_i32, [_vp, _P(_u64), _P(_u64), _P(_u64), _P(_u64)]),
     "fmx_regex_batch_match": (_i32, [_vp, _vp, _vp, _vp, _sz, _P(_sz), _vp]),
     "fmx_regex_batch_match_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _P(_sz), _vp]),
+    "fmx_occurrences": (_i32, [_vp, _vp, _vp, _sz, _sz, _P(fmx_occ_opts), _vp, _vp, _sz, _P(_sz)]),
+    "fmx_occurrences_dev": (_i32, [_vp, _vp, _vp, _sz, _sz, _P(fmx_occ_opts), _vp, _vp, _sz, _P(_sz), _vp]),
+    "fmx_occurrences_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(_u64)]),
     "fmx_regex_batch_create_multi": (_i32, [_vp, _sz, _vp, _sz, _P(_vp)]),
     "fmx_regex_batch_free_multi": (_i32, [_vp]),
     "fmx_regex_batch_match_multi": (_i32, [_vp, _vp, _vp, _sz, _P(_sz), _vp]),

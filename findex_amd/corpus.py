@@ -441,6 +441,19 @@ class HipCorpusSearcher:
         a = raw - np.minimum(raw, np.uint64(before))
         return doc, raw, self.read(doc, a, raw - a + np.uint64(len(q) + int(after)))
 
+    # ---- regexes over the files (HipFMSearcher.finditer)
+    def grep(self, regexes, mode="disjoint", max_steps=0, max_per=None, text=False, lineOnly=False):
+        """Where a batch of regexes matches inside the files: (off, occ, truncated) as HipFMSearcher.finditer gives them, with
+        the corpus -- a match that does not lie inside one file is dropped before the reduction, and every occurrence carries
+        doc, raw_off and raw_len (offset and length in the file on disk).  text=True: a fourth value, the matched raw bytes
+        of every occurrence (read).  The regexes are matched against the escaped stream: a raw 0, 1 or 255 stands there as its
+        escape pair, and an end that falls inside a pair maps to the byte the pair stands for."""
+        off, occ, truncated = self.searcher.finditer(regexes, mode=mode, max_steps=max_steps, max_per=max_per, lineOnly=lineOnly,
+                                                     corpus=self.corpus)
+        if not text:
+            return off, occ, truncated
+        return off, occ, truncated, self.read(occ["doc"], occ["raw_off"], occ["raw_len"]) if occ.size else []
+
     def _intervals(self, queries):
         esc = [escape(q)[::-1] for q in queries]
         if any(not e for e in esc):

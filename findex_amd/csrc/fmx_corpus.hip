@@ -32,6 +32,7 @@
 #include <string>
 #include <vector>
 
+#include "fmx_corpus_dev.h"
 #include "fmx_host.h"
 
 namespace fmx {
@@ -44,26 +45,6 @@ constexpr uint32_t kCoPad = 0x61616161u;             // what a lane's bytes past
 
 __device__ __forceinline__ bool co_esc(uint32_t c) { return ((c + 1u) & 255u) <= 2u; }      // 0, 1, 255
 __device__ __forceinline__ uint32_t co_letter(uint32_t c) { return c == 255u ? 'f' : '0' + c; }
-
-template <typename T>
-__device__ __forceinline__ uint64_t co_lower(const T *__restrict__ a, uint64_t lo, uint64_t hi, uint64_t v) {   // first i: a[i] >= v
-  while (lo < hi) {
-    const uint64_t mid = lo + ((hi - lo) >> 1);
-    if ((uint64_t)a[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-template <typename T>
-__device__ __forceinline__ uint64_t co_upper(const T *__restrict__ a, uint64_t lo, uint64_t hi, uint64_t v) {   // first i: a[i] > v
-  while (lo < hi) {
-    const uint64_t mid = lo + ((hi - lo) >> 1);
-    if ((uint64_t)a[mid] <= v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
 
 // A lane's 16 raw bytes from `base` on: one 16-byte load where the text and the pointer allow it.  Returns how many are real.
 __device__ __forceinline__ uint32_t co_load16(const uint8_t *__restrict__ raw, uint64_t base, uint64_t raw_len, int aligned,
@@ -228,22 +209,6 @@ __global__ __launch_bounds__(kCoThreads) void k_corpus_doc_esc(const uint32_t *_
     doc_esc[d] = (uint32_t)co_lower(esc_pos, 0, n_esc, doc_start[d]);
 }
 
-struct CoMap {
-  const uint32_t *doc_start, *doc_esc, *esc_pos;
-  uint64_t n_docs, n_esc, stream_len;
-};
-
-// (doc, esc_off, raw_off) of stream position p; false at or past the end of the stream
-__device__ __forceinline__ bool co_map(const CoMap &m, uint64_t p, uint32_t &doc, uint64_t &esc_off, uint64_t &raw_off) {
-  if (p >= m.stream_len) return false;
-  const uint64_t d = co_upper(m.doc_start, 0, m.n_docs, p) - 1;       // doc_start[0] = 0 <= p
-  const uint64_t e = co_lower(m.esc_pos, 0, m.n_esc, p);
-  doc = (uint32_t)d;
-  esc_off = p - m.doc_start[d];
-  raw_off = esc_off - (e - m.doc_esc[d]);
-  return true;
-}
-
 __global__ __launch_bounds__(kCoThreads) void k_corpus_map(CoMap m, const unsigned long long *__restrict__ pos, uint64_t k,
                                                            uint32_t *__restrict__ doc, unsigned long long *__restrict__ esc_off,
                                                            unsigned long long *__restrict__ raw_off) {
@@ -315,20 +280,6 @@ __global__ __launch_bounds__(kCoThreads) void k_corpus_list_emit(const unsigned 
 }
 
 // ---------------------------------------------------------------- host side
-struct Corpus {
-  int device = 0;
-  uint64_t n_docs = 0, stream_len = 0, n_esc = 0;
-  uint8_t *d_stream = nullptr;                      // until fmx_corpus_drop_stream
-  uint32_t *d_doc_start = nullptr, *d_doc_esc = nullptr, *d_esc_pos = nullptr;
-  double build_ms = 0.0;
-  ~Corpus() {
-    for (void *p : {(void *)d_stream, (void *)d_doc_start, (void *)d_doc_esc, (void *)d_esc_pos})
-      if (p) (void)hipFree(p);
-  }
-  uint64_t bytes() const { return (d_stream ? stream_len : 0) + 8 * (n_docs + 1) + 4 * std::max<uint64_t>(n_esc, 1); }
-  CoMap map() const { return CoMap{d_doc_start, d_doc_esc, d_esc_pos, n_docs, n_esc, stream_len}; }
-};
-
 namespace {
 
 int co_arg(const char *msg) {

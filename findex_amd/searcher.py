@@ -448,8 +448,106 @@ class HipFMSearcher:
         out[:, 0] = np.uint64(self.n - 1) - out[:, 1] - sa
         return out[np.lexsort((out[:, 1], out[:, 0]))]
 
+    # ---- occurrences: (group, len, sp, ep) intervals as text positions (fmx_occurrences)
+    RESULT = np.dtype([("regex", np.uint32), ("len", np.uint32), ("sp", np.uint64), ("ep", np.uint64)])
+    OCCURRENCE = np.dtype([("group", np.uint32), ("len", np.uint32), ("pos", np.uint64), ("doc", np.uint32), ("raw_len", np.uint32),
+                           ("raw_off", np.uint64)])
+    OCC_MODES = {"all": _lib.FMX_OCC_ALL, "longest": _lib.FMX_OCC_LONGEST, "disjoint": _lib.FMX_OCC_DISJOINT}
+
+    @classmethod
+    def _occ_opts(cls, mode, max_per):
+        if mode not in cls.OCC_MODES:
+            raise ValueError("mode: all, longest or disjoint")
+        if max_per is not None and not 0 < int(max_per) < 2 ** 64:
+            raise ValueError("max_per out of range")
+        return _lib.fmx_occ_opts(cls.OCC_MODES[mode], 0, int(max_per or 0))
+
+    @classmethod
+    def pack_records(cls, group, length, sp, ep):
+        """The record array fmx_occurrences takes, from four arrays (or scalars for the first two)."""
+        sp = np.asarray(sp, dtype=np.uint64).reshape(-1)
+        rec = np.zeros(sp.size, dtype=cls.RESULT)
+        rec["regex"], rec["len"], rec["sp"], rec["ep"] = group, length, sp, ep
+        return rec
+
+    def occurrences(self, records, n_groups=None, mode="all", max_per=None, corpus=None, cap=None):
+        """fmx_occurrences: the text occurrences of (group, len, sp, ep) records (a RESULT array: what RegexBatch.match_raw
+        returns, or pack_records of other hits), at most max_per rows of each, reduced by mode ("all": every distinct (pos,
+        len) of a group, "longest": the longest at every pos, "disjoint": the leftmost non-overlapping reading of those).
+        -> (off[n_groups + 1], occ): group g's occurrences are occ[off[g]:off[g + 1]], an OCCURRENCE array ascending by
+        (pos, len).  corpus (a Corpus whose stream this index is of): occurrences that do not lie inside one document are
+        dropped and the others carry doc, raw_off and raw_len.  n_groups=None: the largest group + 1.  cap=None: a counting
+        call sizes the buffer; with a cap that is too small the library's FMX_ERR_OVERFLOW is raised."""
+        rec = np.ascontiguousarray(records, dtype=self.RESULT).reshape(-1)
+        if n_groups is None:
+            n_groups = int(rec["regex"].max()) + 1 if rec.size else 1
+        opts = self._occ_opts(mode, max_per)
+        args = (self._h, corpus.handle if corpus is not None else None, _ptr(rec), rec.size, int(n_groups), ctypes.byref(opts))
+        return self._csr_hits(self._L.fmx_occurrences, args, int(n_groups), self.OCCURRENCE, cap)
+
+    def occurrences_dev(self, d_rec, k, n_groups, d_out_off, d_out, cap, mode="all", max_per=None, corpus=None, stream=0, grow=False):
+        """fmx_occurrences_dev: device pointers (24-byte records, u64 out_off[n_groups + 1], 32-byte occurrences); allocates and
+        synchronises.  -> the exact number of occurrences.  cap = 0 is the counting call; with any other cap that is too
+        small FMX_ERR_OVERFLOW is raised -- unless grow is set: then the total comes back all the same, for the caller to
+        compare with cap and call again."""
+        opts = self._occ_opts(mode, max_per)
+        n_out = ctypes.c_size_t()
+        rc = self._L.fmx_occurrences_dev(self._h, corpus.handle if corpus is not None else None, _dp(d_rec), int(k), int(n_groups),
+                                         ctypes.byref(opts), _dp(d_out_off), _dp(d_out), int(cap), ctypes.byref(n_out), _dp(stream))
+        if not (rc == _lib.FMX_ERR_OVERFLOW and (int(cap) == 0 or grow)):
+            _lib.check(rc)
+        return int(n_out.value)
+
+    def occurrences_last(self):
+        """fmx_occurrences_last: (locate ms, keys and sort ms, selection ms, compaction ms, rows located) of this thread's
+        last occurrences call."""
+        t = [ctypes.c_double() for _ in range(4)]
+        rows = ctypes.c_uint64()
+        _lib.check(self._L.fmx_occurrences_last(*[ctypes.byref(x) for x in t], ctypes.byref(rows)))
+        return tuple(float(x.value) for x in t) + (int(rows.value),)
+
+    def finditer(self, regexes, mode="disjoint", max_steps=0, max_per=None, lineOnly=False, corpus=None, match_cap=1 << 20,
+                 occ_cap=1 << 20):
+        """Where a batch of regexes matches the indexed text: (off, occ, truncated) -- regex i's matches are
+        occ[off[i]:off[i + 1]] (an OCCURRENCE array ascending by (pos, len)), truncated = the match was cut at max_steps
+        (FMX_TRUNCATED).  regexes: strings (compiled here; lineOnly as ReTree.compile_batch), a CompiledRegexes set or a
+        resident RegexBatch of this searcher.  The batch is matched into device memory (fmx_regex_batch_match_dev; match_cap
+        records to begin with, four times as many after every overflow), fmx_occurrences_dev reads the results there (with room for
+        occ_cap occurrences, and once more with the exact room when that was too little), and offsets and occurrences come down
+        in one copy each: between the two calls only counts cross the link.  The device
+        buffers are torch tensors."""
+        import torch
+        from .regex import CompiledRegexes, RegexBatch, ReTree
+        if isinstance(regexes, RegexBatch):
+            batch = regexes
+        else:
+            batch = RegexBatch(self, regexes if isinstance(regexes, CompiledRegexes) else ReTree.compile_batch(list(regexes), lineOnly))
+        dev = ctypes.c_int()
+        _lib.check(self._L.fmx_device(self._h, ctypes.byref(dev)))
+        dev = torch.device("cuda", dev.value)
+        k, cap = max(batch.k, 1), int(match_cap)
+        while True:
+            d_res = torch.empty(3 * cap, dtype=torch.int64, device=dev)
+            try:
+                n_res = batch.match_dev(d_res.data_ptr(), cap, max_steps=max_steps)
+                break
+            except _lib.FmxError as e:
+                if e.code != _lib.FMX_ERR_OVERFLOW or "result buffer" not in str(e) or cap >= 1 << 28:
+                    raise
+                cap *= 4
+        d_off = torch.empty(k + 1, dtype=torch.int64, device=dev)
+        room = int(occ_cap)
+        d_occ = torch.empty(4 * max(room, 1), dtype=torch.int64, device=dev)
+        total = self.occurrences_dev(d_res.data_ptr(), n_res, k, d_off.data_ptr(), d_occ.data_ptr(), room, mode, max_per, corpus, grow=True)
+        if total > room:                                 # too little room: the call said how much it takes
+            d_occ = torch.empty(4 * total, dtype=torch.int64, device=dev)
+            self.occurrences_dev(d_res.data_ptr(), n_res, k, d_off.data_ptr(), d_occ.data_ptr(), total, mode, max_per, corpus)
+        off = d_off.cpu().numpy().view(np.uint64)
+        occ = d_occ[: 4 * total].cpu().numpy().view(self.OCCURRENCE)
+        return off, occ, bool(batch.truncated)
+
     # ---- matching statistics and maximal exact matches (fmx_match_stats_batch, fmx_mems_batch, DESIGN.md 16)
-    MEM_HIT = np.dtype([("pattern", np.uint32), ("len", np.uint32), ("end", np.uint64), ("sp", np.uint64), ("ep", np.uint64)])
+    MEM_HIT =np.dtype([("pattern", np.uint32), ("len", np.uint32), ("end", np.uint64), ("sp", np.uint64), ("ep", np.uint64)])
 
     @staticmethod
     def _mstat_opts(max_len, min_len=0):

@@ -892,6 +892,75 @@ int fmx_regex_batch_match(const fmx_index *idx, fmx_regex_batch *batch, const fm
 int fmx_regex_batch_match_dev(const fmx_index *idx, fmx_regex_batch *batch, const fmx_limits *lim, void *d_out,
                               size_t cap, size_t *n_out, void *d_per_regex_count);
 
+/* ---- occurrences: where the strings of (group, len, sp, ep) intervals stand in the text, reduced and in CSR order.  Beyond
+ * the reference, whose SAResult can only print one row's string.  DESIGN.md 20.
+ * s, n and SA are as for locate; the text has n - 1 bytes.  The input is k records fmx_result {regex, len, sp, ep} with
+ * `regex` read as a GROUP number < n_groups: the results a regex batch leaves in HBM (fmx_regex_batch_match_dev) have that form
+ * already, edit, mismatch and exact hits after a repack.
+ * The OCCURRENCES OF ONE RECORD: its first min(ep - sp, max_per) rows r (max_per == 0: all) give (group, pos, len) with
+ * pos = n - 1 - len - SA[r] -- the string begins at text offset pos and is len bytes long (locate_text's arithmetic with the
+ * record's own length).  A record with ep <= sp or len == 0 has none; a row with SA[r] + len > n - 1 is dropped (no real
+ * result has one).
+ * WITH A CORPUS (corpus != NULL, idx the index of its stream; n - 1 != stream length is FMX_ERR_ARG) the document is d =
+ * doc(pos) and an occurrence is kept only if pos + len <= doc_start[d + 1] - 1: it lies inside one document and does not touch
+ * its separator.  That happens BEFORE the reduction, so a shorter match at the same start that fits its file can still win.  A
+ * kept occurrence carries doc, raw_off = the raw offset of pos and raw_len = the raw offset of (pos + len - 1) + 1 - raw_off,
+ * both by fmx_corpus_map's rules.  Without a corpus doc = UINT32_MAX, raw_off = pos, raw_len = len.  One known limit, as
+ * elsewhere in the corpus code: the stream is compared in its escaped form, so an end may fall inside an escape pair; its raw
+ * offset is then that of the byte the pair stands for.
+ * MODES (fmx_occ_opts.mode), per group:
+ *   FMX_OCC_ALL      every distinct (pos, len): records that repeat give occurrences that repeat, and those are merged (the
+ *                    frontier keeps multiplicity);
+ *   FMX_OCC_LONGEST  for every pos the occurrence with the largest len;
+ *   FMX_OCC_DISJOINT the LONGEST set by ascending pos: its first element, and after an element (pos, len) the first one with
+ *                    pos' >= pos + len -- the leftmost non-overlapping reading, what finditer or grep -o show.
+ * OUTPUT is CSR over groups: group g's records are out[out_off[g] .. out_off[g + 1]), ascending by (pos, len), and
+ * out_off[n_groups] == *n_out.  The same input gives the same bytes on every run.  opts == NULL: FMX_OCC_ALL, no limit.
+ * Capacity: more than cap occurrences -> FMX_ERR_OVERFLOW with the EXACT total in *n_out (out and, in the host form, out_off
+ * then unspecified); nothing is written past out[cap - 1]; cap == 0 with out == NULL is the counting call.
+ * FMX_ERR_ARG, decided before the device is touched: a null handle, out_off or n_out; mode > 2; reserved != 0; k > 2^26;
+ * n_groups == 0 or > 2^26; cap >= 2^32; a record with group >= n_groups, len > FMX_OCC_MAX_LEN or sp > ep (host form).  The
+ * device form cannot see the records: its kernels read ep > n as n, skip a bad record and raise a flag, and the call returns
+ * FMX_ERR_ARG after the launch with nothing reported (outputs and *n_out untouched).  No record value leads outside the index
+ * or the outputs.
+ * Both forms ALLOCATE AND SYNCHRONISE (FMX_ERR_HIP under a stream capture, decided before anything is allocated, the capture
+ * left valid) and free every temporary on every path.  They need the locate samples and build them when absent, with locate's
+ * refusals: fmx_open_block handles FMX_ERR_UNSUPPORTED, an index that is not the BWT of one text FMX_ERR_FORMAT.  Limit:
+ * n >= 2^32 is FMX_ERR_UNSUPPORTED (positions are 32 bits in the sort key; a corpus stream has that limit anyway).  The rows to
+ * locate, R = the sum of min(ep - sp, max_per), must be < 2^32: FMX_ERR_OVERFLOW otherwise, with a message that says to lower
+ * max_per -- known after the scan and before anything row-sized is allocated.  The need -- 36 bytes per row (the SA values, two
+ * key and two value buffers of the radix sort, the flags), 24 more with FMX_OCC_DISJOINT (the compacted set, two jump buffers,
+ * the marks), 4 more when group, pos and len do not fit one 64-bit key, plus 24 bytes per record, the sort's histograms and
+ * the scans' block totals -- is checked against the free HBM first: FMX_ERR_NOMEM with the need in the message.
+ * No derived search table and no count of patterns seen changes; the launches are added to the handle's.
+ * fmx_occurrences_dev : d_rec (24-byte records), d_out_off (u64[n_groups + 1]) and d_out (32-byte records) in device memory;
+ *                       n_out stays a host pointer.
+ * fmx_occurrences_last: the calling thread's last call: device time (ms) of the locate walks, of the keys and the sort, of the
+ *                       selection, of the compaction, and the rows located; any pointer may be NULL. */
+#define FMX_OCC_ALL 0u
+#define FMX_OCC_LONGEST 1u
+#define FMX_OCC_DISJOINT 2u
+#define FMX_OCC_MAX_LEN 65535
+typedef struct fmx_occ_opts {
+  uint32_t mode;     /* FMX_OCC_ALL | FMX_OCC_LONGEST | FMX_OCC_DISJOINT */
+  uint32_t reserved; /* must be 0 */
+  uint64_t max_per;  /* rows taken of every record; 0 = all */
+} fmx_occ_opts;      /* 16 bytes */
+typedef struct fmx_occurrence {
+  uint32_t group;
+  uint32_t len;
+  uint64_t pos;
+  uint32_t doc;     /* UINT32_MAX without a corpus */
+  uint32_t raw_len;
+  uint64_t raw_off;
+} fmx_occurrence; /* 32 bytes */
+int fmx_occurrences(const fmx_index *idx, const fmx_corpus *corpus_or_null, const fmx_result *rec, size_t k, size_t n_groups,
+                    const fmx_occ_opts *opts, uint64_t *out_off /* n_groups + 1 */, fmx_occurrence *out, size_t cap,
+                    size_t *n_out);
+int fmx_occurrences_dev(const fmx_index *idx, const fmx_corpus *corpus_or_null, const void *d_rec, size_t k, size_t n_groups,
+                        const fmx_occ_opts *opts, void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream);
+int fmx_occurrences_last(double *locate_ms, double *sort_ms, double *select_ms, double *compact_ms, uint64_t *rows);
+
 /* One process, several GPUs (the single-process form of SURVEY.md 8e for regexes; one process per GPU uses
  * findex_amd/distributed.py and an RCCL gather instead): the batch is cut into contiguous slices of about equal
  * estimated frontier work (start elements, states and follow entries of each regex), slice r is made resident on
