@@ -10,6 +10,8 @@ package is the thin host-side mirror of the reference's Scala interface for that
     ReTree(postfix).matchSA(sa)                    ReTree(postfix).matchSA(sa)
     SAResult(sa,len,sp,ep)                         SAResult
     BWTMerger2.merge(FileBWTReader) -> X.bwt/.aux  bwt_from_text(text) + write_bwt(...), python -m findex_amd.index
+    BWTMerger2.merge onto an existing index        HipFMSearcher.append_text, .from_text(chunk=), bwt_from_text_chunked,
+                                                   HipCorpusSearcher.append_documents, python -m findex_amd.index --append / --chunk
     LCPSuffixWalkingAlgo.getLCP, LCPCreator        HipFMSearcher.getLCP / .lcp / .write_lcp, lcp_from_text(text)
     DirBWTReader(dir) -> one stream, IndexerApp    Corpus.from_dir(dir), HipCorpusSearcher, python -m findex_amd.index --dir
     (beyond the reference)                         HipFMSearcher.match_stats_batch / .mems_batch / .match_stats_text / .mems_text,
@@ -25,7 +27,7 @@ library and a HIP device and fails loudly otherwise.
 """
 from ._lib import FmxError, MatchError, Re2PostSyntax, LIB_PATH, load  # noqa: F401
 from .searcher import HipFMSearcher  # noqa: F401
-from .construct import bwt_from_text, bwt_from_text_dev, lcp_from_text, lcp_from_text_dev, write_bwt  # noqa: F401
+from .construct import bwt_from_text, bwt_from_text_chunked, bwt_from_text_dev, lcp_from_text, lcp_from_text_dev, write_bwt  # noqa: F401
 from .corpus import Corpus, HipCorpusSearcher, escape, is_binary, list_files  # noqa: F401
 from .regex import DFA, NFA, REParser, ReTree, SAResult, CompiledRegexes  # noqa: F401
 

@@ -117,6 +117,22 @@ class fmx_occurrence(ctypes.Structure):
                 ("raw_len", ctypes.c_uint32), ("raw_off", ctypes.c_uint64)]
 
 
+FMX_MERGE_SEGMENT, FMX_MERGE_WARMUP, FMX_MERGE_TILE, FMX_MERGE_CONTEXT = 256, 32, 4096, 4096      # fmx.h
+MAX_TEXT_LEN = (1 << 32) - 2          # bytes one suffix sort takes (u32 suffix indices)
+
+
+class fmx_merge_opts(ctypes.Structure):
+    _fields_ = [("context", ctypes.c_uint64), ("max_context", ctypes.c_uint64), ("segment", ctypes.c_uint32),
+                ("warmup", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 4)]
+
+
+class fmx_merge_stats(ctypes.Structure):
+    _fields_ = [("piece_ms", ctypes.c_double), ("walk_ms", ctypes.c_double), ("fixup_ms", ctypes.c_double),
+                ("emit_ms", ctypes.c_double), ("walk_steps", ctypes.c_uint64), ("fixup_steps", ctypes.c_uint64),
+                ("longest_run", ctypes.c_uint64), ("runs", ctypes.c_uint64), ("context", ctypes.c_uint64),
+                ("rounds", ctypes.c_uint64), ("need_bytes", ctypes.c_uint64)]
+
+
 class fmx_stats_t(ctypes.Structure):
     _fields_ = [("rank_queries", ctypes.c_uint64), ("backward_steps", ctypes.c_uint64),
                 ("launches", ctypes.c_uint64), ("last_kernel_ms", ctypes.c_double),
@@ -154,6 +170,9 @@ SYMBOLS = {
     "fmx_bwt_from_text_dev": (_i32, [_vp, _u64, _vp, _vp, _P(_u64), _vp, _i32, _vp]),
     "fmx_open_text": (_i32, [_vp, _u64, _i32, _P(_vp)]),
     "fmx_write_bwt": (_i32, [_cp, _cp, _vp, _u64, _u64, _vp, _i32]),
+    "fmx_append_text": (_i32, [_vp, _vp, _u64, _P(fmx_merge_opts), _P(_vp)]),
+    "fmx_append_text_dev": (_i32, [_vp, _vp, _u64, _P(fmx_merge_opts), _vp, _P(_u64), _vp, _vp]),
+    "fmx_merge_last": (_i32, [_P(fmx_merge_stats)]),
     "fmx_index_config_set": (_i32, [_vp, _cp, _cp]),
     "fmx_prepare": (_i32, [_vp, _u32]),
     "fmx_prepare_ex": (_i32, [_vp, _u32, _u64]),

@@ -30,6 +30,17 @@ def bwt_from_text(text, device=0):
     return bwt, int(eof.value), counts
 
 
+def bwt_from_text_chunked(text, chunk, device=0):
+    """The same (bwt, eof, counts) as bwt_from_text, built `chunk` bytes at a time: the first chunk by the suffix sort, every
+    further one appended to the index on the device (fmx_append_text) -- the way to a text beyond 2^32 - 2 bytes."""
+    from .searcher import HipFMSearcher
+    hip = HipFMSearcher.from_text(_text_array(text), device=device, chunk=int(chunk))
+    try:
+        return hip.bwt_bytes(), hip.eof, hip.counts()
+    finally:
+        hip.close()
+
+
 def bwt_from_text_dev(d_text, length, d_bwt, d_sa=0, device=0, stream=0):
     """fmx_bwt_from_text_dev: device pointers (e.g. tensor.data_ptr()) -- text[length] in, bwt[length + 1] out, and
     the suffix array of reverse(text) + sentinel (u32[length + 1]) into d_sa when it is not 0.  Synchronises `stream`.

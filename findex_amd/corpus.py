@@ -286,6 +286,26 @@ class Corpus:
         ds, _, ep = self.tables()
         return stream_positions(ds, ep, doc, raw_off)
 
+    @classmethod
+    def from_tables(cls, doc_start, raw_len, esc_pos, names, device=0):
+        """The map alone from its three tables (fmx_corpus_from_tables), as load() makes it from an X.docs file."""
+        L = _lib.load()
+        doc_start, raw_len, esc_pos = (np.ascontiguousarray(a, dtype=np.uint64).reshape(-1) for a in (doc_start, raw_len, esc_pos))
+        h = ctypes.c_void_p()
+        _lib.check(L.fmx_corpus_from_tables(_ptr(doc_start), _ptr(raw_len), _ptr(esc_pos), raw_len.size, esc_pos.size,
+                                            int(device), ctypes.byref(h)))
+        return cls(h, names, device)
+
+    def extended(self, more):
+        """The map of this corpus followed by the documents of the corpus `more`: the tables concatenated, the new documents'
+        starts and escapes shifted by this stream's length (every document ends with its separator, so the streams simply
+        follow each other).  No stream."""
+        ds, rl, ep = self.tables()
+        ds2, rl2, ep2 = more.tables()
+        shift = np.uint64(self.stream_len)
+        return Corpus.from_tables(np.concatenate([ds, ds2[1:] + shift]), np.concatenate([rl, rl2]),
+                                  np.concatenate([ep, ep2 + shift]), self.names + more.names, self.device)
+
     def save(self, path):
         """X.docs (write_docs) from the device's tables."""
         ds, rl, ep = self.tables()
@@ -310,6 +330,29 @@ class HipCorpusSearcher:
     def close(self):
         self.searcher.close()
         self.corpus.close()
+
+    def append_documents(self, docs, names=None, context=None):
+        """A NEW HipCorpusSearcher over this corpus followed by the raw documents `docs`: their stream (fmx_corpus_build) is
+        appended to the index on the device (HipFMSearcher.append_text) and the document tables are concatenated -- what
+        Corpus.from_documents of all the documents and its index would be, without sorting the old stream again.  This
+        searcher is untouched; the caller closes both.  Default names go on counting from this corpus's documents."""
+        docs = [bytes(d) for d in docs]
+        if not docs:
+            raise ValueError("no documents to append")
+        if names is None:
+            names = [b"%d" % (self.corpus.n_docs + d) for d in range(len(docs))]
+        more = Corpus.from_documents(docs, names, self.corpus.device)
+        try:
+            stream = more.stream()
+            more.drop_stream()
+            searcher = self.searcher.append_text(stream, context=context)
+            try:
+                return HipCorpusSearcher(self.corpus.extended(more), searcher)
+            except Exception:
+                searcher.close()
+                raise
+        finally:
+            more.close()
 
     def locate_docs(self, q, max_hits=None, max_mismatches=0):
         """(doc, raw_off) arrays of the occurrences of the raw bytes q, sorted by (doc, raw_off): q is escaped, its reverse

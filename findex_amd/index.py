@@ -1,5 +1,6 @@
-"""python -m findex_amd.index X.txt [--little-endian] [--device N] [--fm] [--sa] [--lcp] [--dups L]
+"""python -m findex_amd.index X.txt [--chunk BYTES] [--little-endian] [--device N] [--fm] [--sa] [--lcp] [--dups L]
 python -m findex_amd.index --dir D --out X [--no-filter-binary] [--data] [--little-endian] [--device N] [--fm] [--sa] [--lcp] [--dups L]
+python -m findex_amd.index --append BASE (FILE | --dir D) [--no-filter-binary] [--little-endian] [--device N] [--fm] [--sa] [--lcp] [--dups L]
 
 Writes X.bwt and X.aux next to the input (BWTTempStorage.genBWTFilename / genAuxFilename, bwtmerger.scala:17-24: the
 extension swapped), the files BWTMerger2.merge(FileBWTReader) writes -- the BWT of the reversed file -- big-endian
@@ -19,7 +20,16 @@ document and offset; L is then in stream (escaped) bytes and no passage spans tw
 the files of D in a fixed order, binary ones dropped unless --no-filter-binary, bytes 0, 1 and 255 escaped, a separator
 byte 1 after every file (findex_amd/corpus.py).  It writes X.bwt and X.aux of that stream, X.docs (this project's own side
 file: which stream positions belong to which file), and with --data X.data, the stream itself -- what
-DirBWTReader(caching = true) leaves at genDataFilename.  Escaping and the suffix sort run on the device."""
+DirBWTReader(caching = true) leaves at genDataFilename.  Escaping and the suffix sort run on the device.
+
+--chunk BYTES builds X.bwt / X.aux chunk by chunk: the first BYTES bytes by the suffix sort, the rest appended to that
+index on the device (HipFMSearcher.append_text) -- the same files, and the way to a text beyond 2^32 - 2 bytes.
+
+--append BASE merges new text into the index BASE.bwt / BASE.aux without rebuilding it and rewrites both.  With a
+BASE.docs beside them the index is a corpus: FILE (named by its base name) or the files of --dir D become further documents
+and BASE.docs is rewritten too; without one FILE's bytes are appended to the indexed text.  Side files of the old index
+(BASE.fm, .sa, .lcp, .dups) are rewritten when their flags are given and removed otherwise, with a line on stderr: they are
+never left stale.  --little-endian must be given as it was when BASE was written."""
 import argparse
 import os
 import sys
@@ -48,8 +58,27 @@ def dups_threshold(text):
     return v
 
 
+def chunk_bytes(text):
+    """--chunk BYTES: an int >= 1."""
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("--chunk takes a number of bytes, got %r" % text)
+    if v < 1:
+        raise argparse.ArgumentTypeError("--chunk takes at least 1 byte")
+    return v
+
+
+def append_outputs(a):
+    """--append BASE: (BASE.bwt, BASE.aux, BASE.docs) and the side files (BASE.fm, .sa, .lcp, .dups), in that order."""
+    b = a.append
+    return (b + ".bwt", b + ".aux", b + ".docs"), (b + ".fm", b + ".sa", b + ".lcp", b + ".dups")
+
+
 def dups_name(a):
     """X.dups: beside the other outputs."""
+    if getattr(a, "append", None):
+        return a.append + ".dups"
     return a.out + ".dups" if getattr(a, "dir", None) else os.path.splitext(a.text)[0] + ".dups"
 
 
@@ -65,6 +94,8 @@ def parser():
     ap.add_argument("--fm", action="store_true", help="also write X.fm (FMCreator)")
     ap.add_argument("--sa", action="store_true", help="also write X.sa (SACreator)")
     ap.add_argument("--lcp", action="store_true", help="also write X.lcp (LCPCreator)")
+    ap.add_argument("--chunk", type=chunk_bytes, metavar="BYTES", help="build in chunks of BYTES bytes: the first by the suffix sort, the rest appended")
+    ap.add_argument("--append", metavar="BASE", help="append FILE, or the files of --dir D, to the index BASE.bwt / BASE.aux [/ BASE.docs]")
     ap.add_argument("--dups", type=dups_threshold, metavar="L", help="also write X.dups: the passages of L bytes and more that occur more than once")
     return ap
 
@@ -131,9 +162,91 @@ def main_dir(a):
     return 0
 
 
+def main_append(a):
+    """The --append form: BASE.bwt / BASE.aux (and BASE.docs) rewritten, the side files rewritten or removed."""
+    from .construct import write_bwt
+    from .corpus import Corpus, HipCorpusSearcher, list_files
+    from .searcher import HipFMSearcher
+    (bwt_path, aux_path, docs_path), (fm_path, sa_path, lcp_path, dups_path) = append_outputs(a)
+    be = not a.little_endian
+    is_corpus = os.path.exists(docs_path)
+    if a.dir and not is_corpus:
+        print("%s: no %s -- --append --dir needs a corpus index (one written with --dir)" % (a.append, docs_path), file=sys.stderr)
+        return 2
+    if a.dir:
+        names, docs = [], []
+        for rel in list_files(a.dir, filter_binary=not a.no_filter_binary):
+            try:
+                with open(os.path.join(os.fsencode(a.dir), *rel.split(b"/")), "rb") as f:
+                    docs.append(f.read())
+                names.append(rel)
+            except OSError:
+                continue
+        if not docs:
+            print("%s: no files to index" % a.dir, file=sys.stderr)
+            return 2
+    else:
+        with open(a.text, "rb") as f:
+            data = f.read()
+        if not data and not is_corpus:
+            print("%s: empty file, nothing to append" % a.text, file=sys.stderr)
+            return 2
+        if b"\0" in data and not is_corpus:
+            print("%s: contains byte 0 at offset %d; findex's readers escape byte 0 and this tool does not -- refused"
+                  % (a.text, data.index(b"\0")), file=sys.stderr)
+            return 2
+        names, docs = [os.fsencode(os.path.basename(a.text))], [data]
+    old = new = corpus = None
+    try:
+        if is_corpus:
+            old = HipCorpusSearcher.open(a.append, bigEndian=be, device=a.device)
+            new = old.append_documents(docs, names)
+            hip, corpus = new.searcher, new.corpus
+        else:
+            old = HipFMSearcher(bwt_path, bigEndian=be, device=a.device)
+            hip = new = old.append_text(data)
+        old.close()
+        old = None
+        write_bwt(bwt_path, aux_path, hip.bwt_bytes(), hip.eof, hip.counts(), bigEndian=be)
+        if corpus is not None:
+            corpus.save(docs_path)
+        print("%s: n = %d, eof = %d -> %s, %s%s" % (a.append, hip.n, hip.eof, bwt_path, aux_path, ", " + docs_path if corpus is not None else ""))
+        for wanted, write, path in ((a.fm, hip.write_fm, fm_path), (a.sa, hip.write_sa, sa_path), (a.lcp, hip.write_lcp, lcp_path)):
+            if wanted:
+                write(path)
+                print("%s: -> %s" % (a.append, path))
+        if a.dups and corpus is not None:
+            rows = new.duplicate_passages(a.dups, keep_first=True)
+            with open(dups_path, "wb") as f:
+                for d, lo, hi in rows:
+                    f.write(corpus.names[int(d)] + b"\t%d\t%d\n" % (lo, hi))
+            print("%s: %d duplicated passages -> %s" % (a.append, rows.shape[0], dups_path))
+        elif a.dups:
+            ranges, _ = hip.repeats(a.dups)
+            with open(dups_path, "w") as f:
+                for lo, hi in ranges:
+                    f.write("%d\t%d\n" % (lo, hi))
+            print("%s: %d repeated ranges -> %s" % (a.append, ranges.shape[0], dups_path))
+    finally:
+        for h in (old, new):
+            if h is not None:
+                h.close()
+    for wanted, path in ((a.fm, fm_path), (a.sa, sa_path), (a.lcp, lcp_path), (a.dups, dups_path)):
+        if not wanted and os.path.exists(path):
+            os.remove(path)
+            print("%s: described the index before the append -- removed" % path, file=sys.stderr)
+    return 0
+
+
 def main(argv=None):
     ap = parser()
     a = ap.parse_args(argv)
+    if a.append:
+        if a.out or a.data or a.chunk or bool(a.text) == bool(a.dir):
+            ap.error("--append BASE takes FILE or --dir D (and no --out, --data or --chunk)")
+        return main_append(a)
+    if a.chunk and a.dir:
+        ap.error("--chunk builds a single text file in chunks")
     if a.dir:
         if a.text or not a.out:
             ap.error("--dir takes --out X and no text file")
@@ -149,8 +262,11 @@ def main(argv=None):
         print("%s: contains byte 0 at offset %d; findex's readers escape byte 0 and this tool does not -- refused"
               % (a.text, data.index(b"\0")), file=sys.stderr)
         return 2
-    from .construct import bwt_from_text, write_bwt
-    bwt, eof, counts = bwt_from_text(data, device=a.device)
+    from .construct import bwt_from_text, bwt_from_text_chunked, write_bwt
+    if a.chunk or len(data) > (1 << 32) - 2:        # (beyond one suffix sort: chunks are forced)
+        bwt, eof, counts = bwt_from_text_chunked(data, a.chunk or 1 << 30, device=a.device)
+    else:
+        bwt, eof, counts = bwt_from_text(data, device=a.device)
     bwt_path, aux_path = output_names(a.text)
     write_bwt(bwt_path, aux_path, bwt, eof, counts, bigEndian=not a.little_endian)
     print("%s: n = %d, eof = %d -> %s, %s" % (a.text, bwt.size, eof, bwt_path, aux_path))

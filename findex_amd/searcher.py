@@ -97,15 +97,96 @@ class HipFMSearcher:
         return cls(_handle=h)
 
     @classmethod
-    def from_text(cls, text, device=0):
+    def from_text(cls, text, device=0, chunk=None):
         """fmx_open_text: the index BWTMerger2.merge(FileBWTReader) would write for this text (the BWT of the reversed
-        text, so that search(reversed pattern) counts the pattern's occurrences), built on the device."""
+        text, so that search(reversed pattern) counts the pattern's occurrences), built on the device.  With `chunk` the
+        first `chunk` bytes are built that way and the rest is appended chunk by chunk (append_text): the same index, and
+        the way to a text beyond the suffix sort's 2^32 - 2 bytes, for which chunking is forced."""
         L = _lib.load()
         t = np.frombuffer(bytes(text), dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else \
             np.ascontiguousarray(text, dtype=np.uint8).reshape(-1)
+        if chunk is None and t.size > _lib.MAX_TEXT_LEN:
+            chunk = 1 << 30
+        if chunk is not None:
+            chunk = int(chunk)
+            if chunk < 1:
+                raise ValueError("chunk must be at least 1 byte")
+        if chunk is None or chunk >= t.size:
+            h = ctypes.c_void_p()
+            _lib.check(L.fmx_open_text(_ptr(t), t.size, int(device), ctypes.byref(h)))
+            return cls(_handle=h)
+        cur = cls.from_text(t[:chunk], device=device)
+        # a piece is not made much longer than what it appends: the first context follows the chunk (a retry doubles it)
+        context = min(_lib.FMX_MERGE_CONTEXT, max(64, chunk))
+        for lo in range(chunk, t.size, chunk):
+            nxt = cur.append_text(t[lo: lo + chunk], context=context)
+            cur.close()
+            cur = nxt
+        return cur
+
+    # ---- append (fmx.h, "append"; DESIGN.md 21)
+    @staticmethod
+    def _merge_opts(context=None, max_context=None, segment=None, warmup=None):
+        if context is None and max_context is None and segment is None and warmup is None:
+            return None
+        o = _lib.fmx_merge_opts()
+        o.context = int(context or 0)
+        o.max_context = int(max_context or 0)
+        if segment is not None or warmup is not None:
+            o.segment = int(_lib.FMX_MERGE_SEGMENT if segment is None else segment)
+            o.warmup = int(_lib.FMX_MERGE_WARMUP if warmup is None else warmup)
+            if o.segment < 1:
+                raise ValueError("segment must be at least 1")
+        return o
+
+    def append_text(self, text, context=None, max_context=None, segment=None, warmup=None):
+        """fmx_append_text: a NEW searcher over (this index's text) + text, byte for byte the index from_text of the
+        whole would give, merged on the device without rebuilding this one.  This searcher is untouched and stays valid.
+        `context`: bytes of the indexed text's tail sorted together with the new text (doubled while the new text
+        repeats them, up to `max_context`); `segment`, `warmup`: the rank walk's cut (fmx.h)."""
+        t = np.frombuffer(bytes(text), dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else \
+            np.ascontiguousarray(text, dtype=np.uint8).reshape(-1)
+        o = self._merge_opts(context, max_context, segment, warmup)
         h = ctypes.c_void_p()
-        _lib.check(L.fmx_open_text(_ptr(t), t.size, int(device), ctypes.byref(h)))
-        return cls(_handle=h)
+        _lib.check(self._L.fmx_append_text(self._h, _ptr(t), t.size, ctypes.byref(o) if o is not None else None,
+                                           ctypes.byref(h)))
+        return type(self)(_handle=h)
+
+    def append_text_dev(self, d_text, length, d_bwt_out, context=None, max_context=None, segment=None, warmup=None, stream=0):
+        """fmx_append_text_dev: device pointers -- text[length] in, the merged BWT (n + length bytes) out, ready for
+        from_device.  Synchronises `stream`.  Returns (eof, counts int64[256])."""
+        o = self._merge_opts(context, max_context, segment, warmup)
+        counts = np.zeros(256, dtype=np.int64)
+        eof = ctypes.c_uint64()
+        _lib.check(self._L.fmx_append_text_dev(self._h, _dp(d_text), int(length), ctypes.byref(o) if o is not None else None,
+                                               _dp(d_bwt_out), ctypes.byref(eof), _ptr(counts), _dp(stream)))
+        return int(eof.value), counts
+
+    @staticmethod
+    def merge_last():
+        """fmx_merge_last: this thread's last append -- device ms of its phases, the steps of the segment walk, steps,
+        number and longest of the fix-up runs, the context that passed and the pieces built."""
+        st = _lib.fmx_merge_stats()
+        _lib.check(_lib.load().fmx_merge_last(ctypes.byref(st)))
+        return {name: getattr(st, name) for name, _ in st._fields_}
+
+    def bwt_bytes(self, batch=1 << 22):
+        """The index's BWT as fmx_bwt_from_text writes it: BWTLoader.read of every row, and at the eof slot the filler
+        of sa2BWT (bwtmerger.scala:799-806: the byte of the row above, of the row below for eof == 0)."""
+        out = np.empty(self.n, dtype=np.uint8)
+        for lo in range(0, self.n, batch):
+            rows = np.arange(lo, min(lo + batch, self.n), dtype=np.uint64)
+            b, _ = self.lf_walk_batch(rows, 1)
+            out[lo: lo + rows.size] = np.asarray(b, dtype=np.uint8).reshape(-1)
+        if self.n > 1:
+            out[self.eof] = out[self.eof - 1] if self.eof else out[1]
+        return out
+
+    def counts(self):
+        """fmx_counts: the .aux counts (occurrences of every byte in the text)."""
+        c = np.zeros(256, dtype=np.int64)
+        _lib.check(self._L.fmx_counts(self._h, _ptr(c)))
+        return c
 
     @classmethod
     def from_block(cls, bwt, bucketStarts, rk0, device=0):

@@ -187,6 +187,64 @@ int fmx_bwt_from_text_dev(const void *d_text, uint64_t len, void *d_bwt, void *d
 int fmx_open_text(const uint8_t *text, uint64_t len, int device, fmx_index **out);
 int fmx_write_bwt(const char *bwt_path, const char *aux_path, const uint8_t *bwt, uint64_t n, uint64_t eof,
                   const int64_t counts[256], int big_endian);
+
+/* ---- append: new text merged into an index without rebuilding it (BWTMerger2's way to a large index) ----
+ * A = the indexed text (a bytes, n = a + 1 rows), B = the new text (len bytes, no 0 byte).  The result is byte for byte what
+ * fmx_bwt_from_text(A + B) gives: eof, counts and the filler at the eof slot included.  With R = reverse(B) the new string
+ * is R . s_A: the rows of A keep their order and their bytes (A's eof row takes R's last byte), and the len new suffixes
+ * are placed among them --
+ *   gap ranks : how many rows of A lie before each new suffix.  One chain of len dependent rank steps, cut into segments
+ *               of `segment` positions: a lane group starts `warmup` positions to the right of its segment with the full
+ *               row range and walks left; once its interval is empty the rank is exact.  Positions whose interval is
+ *               still not empty inside the segment (B shares a stretch with A there) are walked again as the plain chain,
+ *               one walker per maximal run: correct for every B, slow where B repeats A (B == A is one run of len steps).
+ *   order     : the new suffixes among themselves, from the suffix sort of tail(A, M) + B with M = min(a, context); the
+ *               piece's LCP array tells whether a comparison reached the piece's end, and then context doubles and the
+ *               piece is rebuilt, until M == a or context passes max_context (FMX_ERR_UNSUPPORTED, the context that
+ *               would be tried next in the message).  tail(A, M) comes from the handle by one Psi walk from the eof row
+ *               (it builds the handle's select directory, as fmx_next_substr does).
+ *   emit      : per tile of FMX_MERGE_TILE output rows, the new bytes and the next rows of A, 16 bytes per store.
+ * Rows and ranks are 64-bit: n + len may exceed 2^32 (len itself, with the context, stays within the suffix sort's limit).
+ * fmx_merge_opts: NULL = all defaults.  context 0 = FMX_MERGE_CONTEXT; max_context 0 = no limit; segment 0 = the header's
+ *   FMX_MERGE_SEGMENT and FMX_MERGE_WARMUP, segment != 0 = segment and warmup both as given (warmup 0 is a valid choice);
+ *   reserved must be 0.
+ * fmx_append_text     : host text in, a NEW handle out; idx is untouched, stays valid, and the caller closes both.
+ * fmx_append_text_dev : device text in, the merged BWT (n + len bytes) into the caller's device buffer, eof and counts to
+ *                       host pointers: ready for fmx_open_dev.  Enqueued on `stream` and synchronised.
+ * fmx_merge_last      : the calling thread's last append: device-event times (ms) of its phases, the backward steps of the
+ *                       segment walk, the steps, number and longest of the fix-up runs, the context used and the number of
+ *                       pieces built.
+ * Like construction these calls ALLOCATE AND SYNCHRONISE: FMX_ERR_HIP under a stream capture, decided before anything is
+ * allocated, the capture left valid.  The need in device memory -- the piece's temporaries (~47 bytes per piece byte), 17
+ * bytes per new byte for ranks, rows and bytes, and in the host form the text, the n + len output bytes and the new
+ * handle's rank dictionary -- is checked against the free HBM before each piece: FMX_ERR_NOMEM with the need in the
+ * message.  Every temporary is freed on every path; the same inputs give the same bytes on every run.
+ * Refusals, decided before the device is touched, in this order: a NULL text or output, len == 0, a non-zero reserved
+ * word: FMX_ERR_ARG; len + context > 2^32 - 2, a 0 byte in a host text: FMX_ERR_UNSUPPORTED; a NULL handle: FMX_ERR_ARG; an
+ * fmx_open_block handle, n + len >= 2^38: FMX_ERR_UNSUPPORTED.  (A 0 byte in a device text is found by the piece's first
+ * kernel: FMX_ERR_UNSUPPORTED then too.) */
+#define FMX_MERGE_SEGMENT 256      /* positions of B per lane group of the rank walk */
+#define FMX_MERGE_WARMUP 32        /* positions a group starts to the right of its segment */
+#define FMX_MERGE_TILE 4096        /* output rows per workgroup tile of the emit kernel */
+#define FMX_MERGE_CONTEXT 4096     /* bytes of A's tail in the first piece */
+typedef struct fmx_merge_opts {
+  uint64_t context;
+  uint64_t max_context;
+  uint32_t segment;
+  uint32_t warmup;
+  uint32_t reserved[4];
+} fmx_merge_opts;
+typedef struct fmx_merge_stats {
+  double piece_ms, walk_ms, fixup_ms, emit_ms;
+  uint64_t walk_steps, fixup_steps, longest_run, runs;
+  uint64_t context;                /* M of the piece that passed: min(a, context after the retries) */
+  uint64_t rounds;                 /* pieces built */
+  uint64_t need_bytes;             /* the device memory need that was checked before the last piece */
+} fmx_merge_stats;
+int fmx_append_text(const fmx_index *idx, const uint8_t *text, uint64_t len, const fmx_merge_opts *opts, fmx_index **out);
+int fmx_append_text_dev(const fmx_index *idx, const void *d_text, uint64_t len, const fmx_merge_opts *opts, void *d_bwt_out,
+                        uint64_t *eof, int64_t counts[256], void *stream);
+int fmx_merge_last(fmx_merge_stats *out);
 /* One handle's own table policy (the keys fmx_config_set lists as table keys; FMX_ERR_ARG for any other key or a bad value).
  * Tables that exist are not touched: fmx_drop_tables + fmx_prepare rebuild under the new policy. */
 int fmx_index_config_set(fmx_index *idx, const char *key, const char *value);
