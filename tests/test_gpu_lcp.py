@@ -128,9 +128,11 @@ def _core_on_device(torch, text, sa):
     return lcp
 
 
-def _verify_on_device(torch, text, sa32, lcp32, chunk=1 << 26):
+def _verify_on_device(torch, text, sa32, lcp32, chunk=1 << 26, cap=None):
     """Every row r < n - 1, with a = SA[r], b = SA[r + 1], L = LCP[r]: a + L <= n - 1, b + L <= n - 1, s[a + L] != s[b + L]
-    and s[a + t] == s[b + t] for all t < L; LCP[n - 1] == 0.  Returns (max, sum) of the array by torch."""
+    and s[a + t] == s[b + t] for all t < L; LCP[n - 1] == 0.  Returns (max, sum) of the array by torch.  With a cap the
+    bytes are compared for t < min(L, cap) only: a row with L <= cap is checked whole, and what a longer entry should be
+    is the caller's to know."""
     dev = text.device
     n = text.numel() + 1
     s = torch.cat([torch.flip(text, dims=[0]), torch.zeros(1, dtype=torch.uint8, device=dev)])
@@ -146,7 +148,7 @@ def _verify_on_device(torch, text, sa32, lcp32, chunk=1 << 26):
         mx = max(mx, int(L.max().item()))
         total += int(L.sum().item())
         t = 0
-        while True:
+        while cap is None or t < cap:
             live = L > t
             if not bool(live.any().item()):
                 break
