@@ -21,6 +21,8 @@ package is the thin host-side mirror of the reference's Scala interface for that
                                                    HipCorpusSearcher.read / .document / .snippets
                                                    HipFMSearcher.occurrences / .finditer (where regexes and hits stand),
                                                    HipCorpusSearcher.grep, python -m findex_amd.grep
+                                                   HipFMSearcher.ngrams / .ngram_texts (which strings of L bytes occur, how often),
+                                                   HipCorpusSearcher.frequent_phrases, python -m findex_amd.index --ngrams
 
 There is no CPU fallback: importing works anywhere, but every compute call needs the built
 library and a HIP device and fails loudly otherwise.

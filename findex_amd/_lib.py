@@ -104,6 +104,28 @@ class fmx_repeat_summary(ctypes.Structure):
                 ("windows", ctypes.c_uint64), ("largest_class", ctypes.c_uint64), ("largest_class_pos", ctypes.c_uint64)]
 
 
+FMX_NGRAMS_BY_ROW, FMX_NGRAMS_BY_COUNT = 0, 1
+FMX_NGRAMS_NO_POS = 1
+FMX_NGRAMS_MAX_LEVELS = 64
+FMX_NGRAMS_MAX_BINS = 65536
+FMX_NGRAMS_LDS_BINS = 1024            # counts below it are histogrammed in LDS, the others in global memory (fmx.h)
+
+
+class fmx_ngram_opts(ctypes.Structure):
+    _fields_ = [("order", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("min_count", ctypes.c_uint64), ("top", ctypes.c_uint64),
+                ("spectrum_bins", ctypes.c_uint32), ("stop", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3)]
+
+
+class fmx_ngram(ctypes.Structure):
+    _fields_ = [("sp", ctypes.c_uint64), ("count", ctypes.c_uint64), ("first_pos", ctypes.c_uint64)]
+
+
+class fmx_ngram_summary(ctypes.Structure):
+    _fields_ = [("records", ctypes.c_uint64), ("selected", ctypes.c_uint64), ("distinct", ctypes.c_uint64),
+                ("windows", ctypes.c_uint64), ("singletons", ctypes.c_uint64), ("largest_count", ctypes.c_uint64),
+                ("largest_sp", ctypes.c_uint64), ("largest_pos", ctypes.c_uint64)]
+
+
 FMX_OCC_ALL, FMX_OCC_LONGEST, FMX_OCC_DISJOINT = 0, 1, 2
 FMX_OCC_MAX_LEN = 65535               # bytes of an occurrence (fmx.h)
 
@@ -235,6 +257,9 @@ SYMBOLS = {
     "fmx_repeats": (_i32, [_vp, _vp, _sz, _P(fmx_repeat_opts), _vp, _vp, _sz, _P(_sz), _vp]),
     "fmx_repeats_dev": (_i32, [_vp, _vp, _sz, _P(fmx_repeat_opts), _vp, _vp, _sz, _P(_sz), _vp, _vp]),
     "fmx_repeats_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double)]),
+    "fmx_ngrams": (_i32, [_vp, _vp, _sz, _P(fmx_ngram_opts), _vp, _vp, _sz, _P(_sz), _vp, _vp]),
+    "fmx_ngrams_dev": (_i32, [_vp, _vp, _sz, _P(fmx_ngram_opts), _vp, _vp, _sz, _P(_sz), _vp, _vp, _vp]),
+    "fmx_ngrams_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double)]),
     "fmx_extract_text_batch": (_i32, [_vp, _vp, _vp, _sz, _vp]),
     "fmx_extract_text_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _u64, _vp, _vp]),
     "fmx_extract_info": (_i32, [_vp, _P(_u32), _P(_u64), _P(ctypes.c_double)]),

@@ -452,6 +452,36 @@ class HipCorpusSearcher:
         np.add.at(out, rows[:, 0].astype(np.int64), rows[:, 2] - rows[:, 1])
         return out
 
+    # ---- the most frequent phrases of the corpus (HipFMSearcher.ngrams)
+    def frequent_phrases(self, length, min_count=2, top=100):
+        """The windows of `length` stream bytes that occur min_count times and more in the corpus, the `top` most frequent
+        of them: a list of rows (text, count, n_docs, first_doc, first_raw_off) by descending count -- the phrase's raw
+        bytes, how often it occurs, in how many documents, and the document and raw offset of its first occurrence (in
+        stream order: the documents' order).  The n-grams of the stream with the separator byte 1 as the stop byte, so no
+        phrase spans two files; the bytes come from the index (extract_text_batch) and are unescaped by the map, the
+        documents from fmx_corpus_doc_list over the phrase's interval, the first occurrence from the map.  `length` is in
+        stream (escaped) bytes.  One known limit: the stream is compared in its escaped form, so a window may begin or end
+        inside an escape pair (the backslash or the digit that stand for a raw 0, 1 or 255); its text is then that of the raw
+        bytes the first occurrence touches, and its offset that of the byte the pair stands for."""
+        length = int(length)
+        rec, _ = self.searcher.ngrams(length, min_count=min_count, top=top, order="count", stop=1)
+        if not rec.size:
+            return []
+        _, _, ep = self.corpus.tables()
+        lo = rec["first_pos"].copy()
+        hi = lo + np.uint64(length)
+        if ep.size:                      # a window that begins on a pair's second byte or ends on its backslash: the whole pair
+            at = np.minimum(np.searchsorted(ep, lo - np.uint64(1)), ep.size - 1)
+            lo = np.where((lo > 0) & (ep[at] == lo - np.uint64(1)), lo - np.uint64(1), lo)
+            at = np.minimum(np.searchsorted(ep, hi - np.uint64(1)), ep.size - 1)
+            hi = np.where(ep[at] == hi - np.uint64(1), hi + np.uint64(1), hi)
+        off, data = self.searcher.extract_text_batch(lo, hi - lo)
+        texts = unescape_ranges(data, off, lo, ep)
+        doc_off, _, _ = self._doc_list(rec["sp"], rec["sp"] + rec["count"], length)
+        n_docs = np.diff(doc_off.astype(np.int64))
+        doc, _, raw = self.corpus.map(rec["first_pos"])
+        return [(texts[i], int(rec["count"][i]), int(n_docs[i]), int(doc[i]), int(raw[i])) for i in range(rec.size)]
+
     # ---- the text itself, from the index alone (HipFMSearcher.extract_text_batch): no stream in HBM, no X.data on disk
     def read(self, doc, raw_off, length):
         """The raw bytes [raw_off, raw_off + length) of document doc, clipped at the document's end (arrays or scalars) -> a

@@ -1,5 +1,5 @@
-"""python -m findex_amd.index X.txt [--chunk BYTES] [--little-endian] [--device N] [--fm] [--sa] [--lcp] [--dups L]
-python -m findex_amd.index --dir D --out X [--no-filter-binary] [--data] [--little-endian] [--device N] [--fm] [--sa] [--lcp] [--dups L]
+"""python -m findex_amd.index X.txt [--chunk BYTES] [--little-endian] [--device N] [--fm] [--sa] [--lcp] [--dups L] [--ngrams L[,L..] [--min-count C] [--top K]]
+python -m findex_amd.index --dir D --out X [--no-filter-binary] [--data] [--little-endian] [--device N] [--fm] [--sa] [--lcp] [--dups L] [--ngrams L[,L..] [--min-count C] [--top K]]
 python -m findex_amd.index --append BASE (FILE | --dir D) [--no-filter-binary] [--little-endian] [--device N] [--fm] [--sa] [--lcp] [--dups L]
 
 Writes X.bwt and X.aux next to the input (BWTTempStorage.genBWTFilename / genAuxFilename, bwtmerger.scala:17-24: the
@@ -16,6 +16,13 @@ n - 1 big-endian int32), through the writers of the handle opened on the two fil
 and lose nothing -- every copy but the first (HipCorpusSearcher.duplicate_passages) -- as name<TAB>raw_start<TAB>raw_end, by
 document and offset; L is then in stream (escaped) bytes and no passage spans two files.
 
+--ngrams L[,L..] adds X.ngrams, the strings of L bytes that occur --min-count times and more (default 2), the --top most
+frequent of every length (default 100; 0: all), most frequent first (HipFMSearcher.ngrams): one line
+L<TAB>count<TAB>first offset<TAB>bytes per string.  With --dir the lines are the rows of HipCorpusSearcher.frequent_phrases,
+L<TAB>count<TAB>files<TAB>name<TAB>raw offset<TAB>bytes -- in how many files the phrase stands, and the file and offset of
+its first occurrence; L is then in stream (escaped) bytes and no phrase spans two files.  In the bytes everything outside
+0x21 .. 0x7e, and the backslash, is written as a backslash, an x and two hex digits.
+
 --dir D --out X indexes a directory the way the reference's IndexerApp does through DirBWTReader (bwtreader.scala:17-173):
 the files of D in a fixed order, binary ones dropped unless --no-filter-binary, bytes 0, 1 and 255 escaped, a separator
 byte 1 after every file (findex_amd/corpus.py).  It writes X.bwt and X.aux of that stream, X.docs (this project's own side
@@ -29,7 +36,7 @@ index on the device (HipFMSearcher.append_text) -- the same files, and the way t
 BASE.docs beside them the index is a corpus: FILE (named by its base name) or the files of --dir D become further documents
 and BASE.docs is rewritten too; without one FILE's bytes are appended to the indexed text.  Side files of the old index
 (BASE.fm, .sa, .lcp, .dups) are rewritten when their flags are given and removed otherwise, with a line on stderr: they are
-never left stale.  --little-endian must be given as it was when BASE was written."""
+never left stale.  --ngrams is not taken here, and a BASE.ngrams is removed likewise.  --little-endian must be given as it was when BASE was written."""
 import argparse
 import os
 import sys
@@ -56,6 +63,59 @@ def dups_threshold(text):
     if not 1 <= v < 2 ** 32:
         raise argparse.ArgumentTypeError("--dups takes a length of at least 1")
     return v
+
+
+def ngram_lengths(text):
+    """--ngrams L[,L..]: 1 .. 64 ints >= 1 (below 2^32, the lengths of one fmx_ngrams call)."""
+    try:
+        v = [int(x) for x in text.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError("--ngrams takes integers separated by commas, got %r" % text)
+    if not 1 <= len(v) <= 64 or any(not 1 <= x < 2 ** 32 for x in v):
+        raise argparse.ArgumentTypeError("--ngrams takes 1 to 64 lengths of at least 1")
+    return v
+
+
+def count_arg(least):
+    """--min-count C (C >= 1), --top K (K >= 0)"""
+    def parse(text):
+        try:
+            v = int(text)
+        except ValueError:
+            raise argparse.ArgumentTypeError("an integer is expected, got %r" % text)
+        if not least <= v < 2 ** 63:
+            raise argparse.ArgumentTypeError("at least %d is expected" % least)
+        return v
+    return parse
+
+
+def printable(b):
+    """The bytes of an X.ngrams line: 0x21 .. 0x7e as they are, the backslash and everything else as \\xHH."""
+    return b"".join(bytes([c]) if 0x21 <= c <= 0x7E and c != 0x5C else b"\\x%02X" % c for c in bytes(b))
+
+
+def ngrams_name(a):
+    """X.ngrams: beside the other outputs."""
+    return a.out + ".ngrams" if getattr(a, "dir", None) else os.path.splitext(a.text)[0] + ".ngrams"
+
+
+def write_ngrams(a, hip, corpus=None):
+    """X.ngrams of the parsed arguments `a` from the searcher `hip` (of `corpus`' stream) -> the number of lines."""
+    lines = 0
+    with open(ngrams_name(a), "wb") as f:
+        if corpus is not None:
+            from .corpus import HipCorpusSearcher
+            cs = HipCorpusSearcher(corpus, hip)
+            for L in a.ngrams:
+                for text, count, n_docs, doc, raw_off in cs.frequent_phrases(L, min_count=a.min_count, top=a.top):
+                    f.write(b"%d\t%d\t%d\t" % (L, count, n_docs) + corpus.names[doc] + b"\t%d\t" % raw_off + printable(text) + b"\n")
+                    lines += 1
+        else:
+            for L, (rec, _) in zip(a.ngrams, hip.ngrams(a.ngrams, min_count=a.min_count, top=a.top, order="count")):
+                for r, text in zip(rec, hip.ngram_texts(rec, L)):
+                    f.write(b"%d\t%d\t%d\t" % (L, int(r["count"]), int(r["first_pos"])) + printable(text) + b"\n")
+                    lines += 1
+    return lines
 
 
 def chunk_bytes(text):
@@ -97,12 +157,19 @@ def parser():
     ap.add_argument("--chunk", type=chunk_bytes, metavar="BYTES", help="build in chunks of BYTES bytes: the first by the suffix sort, the rest appended")
     ap.add_argument("--append", metavar="BASE", help="append FILE, or the files of --dir D, to the index BASE.bwt / BASE.aux [/ BASE.docs]")
     ap.add_argument("--dups", type=dups_threshold, metavar="L", help="also write X.dups: the passages of L bytes and more that occur more than once")
+    ap.add_argument("--ngrams", type=ngram_lengths, metavar="L[,L..]", help="also write X.ngrams: the most frequent strings of L bytes")
+    ap.add_argument("--min-count", type=count_arg(1), default=2, metavar="C", help="with --ngrams: strings that occur C times and more (default 2)")
+    ap.add_argument("--top", type=count_arg(0), default=100, metavar="K", help="with --ngrams: the K most frequent of every length (default 100; 0: all)")
     return ap
 
 
 def planned_outputs(a):
     """The files a run with the parsed arguments `a` writes, in the order it writes them."""
     dups = getattr(a, "dups", None)
+    if getattr(a, "ngrams", None):
+        b = argparse.Namespace(**vars(a))
+        b.ngrams = None
+        return planned_outputs(b) + [ngrams_name(a)]
     if getattr(a, "dir", None):
         base = a.out + ".x"             # (the name functions swap an extension: OUT itself is the stem)
         fm, sa, lcp = sibling_names(base)
@@ -146,6 +213,13 @@ def main_dir(a):
                 for d, lo, hi in rows:
                     f.write(corpus.names[int(d)] + b"\t%d\t%d\n" % (lo, hi))
             print("%s: %d duplicated passages -> %s" % (a.dir, rows.shape[0], dups_name(a)))
+        if getattr(a, "ngrams", None):
+            from .searcher import HipFMSearcher
+            hip = HipFMSearcher.from_mem(bwt, eof, counts, device=a.device)
+            try:
+                print("%s: %d frequent phrases -> %s" % (a.dir, write_ngrams(a, hip, corpus), ngrams_name(a)))
+            finally:
+                hip.close()
     finally:
         corpus.close()
     if a.fm or a.sa or a.lcp:
@@ -231,7 +305,7 @@ def main_append(a):
         for h in (old, new):
             if h is not None:
                 h.close()
-    for wanted, path in ((a.fm, fm_path), (a.sa, sa_path), (a.lcp, lcp_path), (a.dups, dups_path)):
+    for wanted, path in ((a.fm, fm_path), (a.sa, sa_path), (a.lcp, lcp_path), (a.dups, dups_path), (False, a.append + ".ngrams")):
         if not wanted and os.path.exists(path):
             os.remove(path)
             print("%s: described the index before the append -- removed" % path, file=sys.stderr)
@@ -242,8 +316,8 @@ def main(argv=None):
     ap = parser()
     a = ap.parse_args(argv)
     if a.append:
-        if a.out or a.data or a.chunk or bool(a.text) == bool(a.dir):
-            ap.error("--append BASE takes FILE or --dir D (and no --out, --data or --chunk)")
+        if a.out or a.data or a.chunk or a.ngrams or bool(a.text) == bool(a.dir):
+            ap.error("--append BASE takes FILE or --dir D (and no --out, --data, --chunk or --ngrams)")
         return main_append(a)
     if a.chunk and a.dir:
         ap.error("--chunk builds a single text file in chunks")
@@ -270,7 +344,7 @@ def main(argv=None):
     bwt_path, aux_path = output_names(a.text)
     write_bwt(bwt_path, aux_path, bwt, eof, counts, bigEndian=not a.little_endian)
     print("%s: n = %d, eof = %d -> %s, %s" % (a.text, bwt.size, eof, bwt_path, aux_path))
-    if a.fm or a.sa or a.lcp or a.dups:
+    if a.fm or a.sa or a.lcp or a.dups or a.ngrams:
         from .searcher import HipFMSearcher
         fm_path, sa_path, lcp_path = sibling_names(a.text)
         hip = HipFMSearcher.from_mem(bwt, eof, counts, device=a.device)
@@ -285,6 +359,8 @@ def main(argv=None):
                     for lo, hi in ranges:
                         f.write("%d\t%d\n" % (lo, hi))
                 print("%s: %d repeated ranges -> %s" % (a.text, ranges.shape[0], dups_name(a)))
+            if a.ngrams:
+                print("%s: %d frequent strings -> %s" % (a.text, write_ngrams(a, hip), ngrams_name(a)))
         finally:
             hip.close()
     return 0

@@ -780,6 +780,91 @@ class HipFMSearcher:
         _lib.check(self._L.fmx_repeats_last(*[ctypes.byref(x) for x in v]))
         return tuple(float(x.value) for x in v)
 
+    # ---- n-grams: the distinct windows of a length, their counts and the spectrum of the counts (fmx_ngrams)
+    NGRAM = np.dtype([("sp", np.uint64), ("count", np.uint64), ("first_pos", np.uint64)])
+    NGRAM_SUMMARY = ("records", "selected", "distinct", "windows", "singletons", "largest_count", "largest_sp", "largest_pos")
+    NO_POS = 2 ** 64 - 1                # first_pos and largest_pos of a call without positions
+
+    @staticmethod
+    def _ngram_args(length, min_count, top, order, stop, spectrum, positions):
+        single = np.ndim(length) == 0
+        levels = [int(x) for x in ([length] if single else length)]
+        if order not in ("row", "count"):
+            raise ValueError("order: 'row' or 'count'")
+        top, spectrum = int(top or 0), int(spectrum or 0)
+        if any(not 0 <= x < 2 ** 32 for x in levels) or not 0 <= int(stop) <= 255 or not 0 <= int(min_count) < 2 ** 64 or \
+                not 0 <= top < 2 ** 64 or not 0 <= spectrum < 2 ** 32:
+            raise ValueError("length, min_count, top, stop or spectrum out of range")
+        lv = np.array(levels, dtype=np.uint32)
+        opts = _lib.fmx_ngram_opts(_lib.FMX_NGRAMS_BY_COUNT if order == "count" else _lib.FMX_NGRAMS_BY_ROW,
+                                   0 if positions else _lib.FMX_NGRAMS_NO_POS, int(min_count), top, spectrum, int(stop), (0, 0, 0))
+        return single, lv, opts
+
+    def _ngram_summaries(self, sums, spec, k, bins):
+        out = []
+        for j in range(k):
+            s = {f: int(getattr(sums[j], f)) for f in self.NGRAM_SUMMARY}
+            if bins:
+                s["spectrum"] = spec[j * bins:(j + 1) * bins].copy()
+            out.append(s)
+        return out
+
+    def ngrams(self, length, min_count=2, top=None, order="count", stop=0, spectrum=0, positions=True):
+        """fmx_ngrams: the distinct windows of `length` bytes that occur min_count times and more -> (records, summary):
+        records a structured array (sp, count, first_pos) -- the window's interval is [sp, sp + count), what
+        search(reverse(window)) returns, first_pos its first text offset -- by descending count (ties by sp; order="row":
+        by sp), the first `top` of them; summary a dict (records, selected, distinct, windows, singletons, largest_count,
+        largest_sp, largest_pos) and, with spectrum=B, "spectrum": a uint64[B] array, entry c the number of windows'
+        classes of count c, entry 0 those of count >= B.  stop != 0: a window that holds that byte does not count.
+        positions=False: first_pos and largest_pos are NO_POS and no suffix array is made (min_count >= 2, no stop byte).
+        length a sequence: one call for all lengths and a list of such pairs.  The handle indexes reverse(text) as
+        from_text has it.  A counting call sizes the buffer."""
+        single, lv, opts = self._ngram_args(length, min_count, top, order, stop, spectrum, positions)
+        k, bins = lv.size, int(opts.spectrum_bins)
+        n_out = ctypes.c_size_t()
+        off = np.zeros(k + 1, dtype=np.uint64)
+        sums = (_lib.fmx_ngram_summary * max(k, 1))()
+        spec = np.zeros(max(k * bins, 1), dtype=np.uint64)
+        rc = self._L.fmx_ngrams(self._h, _ptr(lv), k, ctypes.byref(opts), _ptr(off), None, 0, ctypes.byref(n_out), sums, _ptr(spec))
+        total = int(n_out.value)
+        out = np.zeros(max(total, 1), dtype=self.NGRAM)
+        if rc == _lib.FMX_ERR_OVERFLOW:
+            rc = self._L.fmx_ngrams(self._h, _ptr(lv), k, ctypes.byref(opts), _ptr(off), _ptr(out), total, ctypes.byref(n_out), sums,
+                                    _ptr(spec))
+        _lib.check(rc)
+        summaries = self._ngram_summaries(sums, spec, k, bins)
+        res = [(out[int(off[j]):int(off[j + 1])].copy(), summaries[j]) for j in range(k)]
+        return res[0] if single else res
+
+    def ngrams_dev(self, length, d_out_off, d_out, cap, min_count=2, top=None, order="count", stop=0, spectrum=0, positions=True,
+                   stream=0):
+        """fmx_ngrams_dev: u64 out_off[k + 1] and 24-byte (sp, count, first_pos) records in device memory; allocates and
+        synchronises.  -> (the exact number of records, the list of summaries); FMX_ERR_OVERFLOW is raised when the records
+        exceed cap."""
+        _, lv, opts = self._ngram_args(length, min_count, top, order, stop, spectrum, positions)
+        bins = int(opts.spectrum_bins)
+        n_out = ctypes.c_size_t()
+        sums = (_lib.fmx_ngram_summary * max(lv.size, 1))()
+        spec = np.zeros(max(lv.size * bins, 1), dtype=np.uint64)
+        _lib.check(self._L.fmx_ngrams_dev(self._h, _ptr(lv), lv.size, ctypes.byref(opts), _dp(d_out_off), _dp(d_out), int(cap),
+                                          ctypes.byref(n_out), sums, _ptr(spec), _dp(stream)))
+        return int(n_out.value), self._ngram_summaries(sums, spec, lv.size, bins)
+
+    def ngrams_last(self):
+        """fmx_ngrams_last: (inversion ms, class passes ms, selection ms, sort ms) of this thread's last call."""
+        v = [ctypes.c_double() for _ in range(4)]
+        _lib.check(self._L.fmx_ngrams_last(*[ctypes.byref(x) for x in v]))
+        return tuple(float(x.value) for x in v)
+
+    def ngram_texts(self, records, length):
+        """The bytes of the windows of `records` (as ngrams gave them for `length`, with positions) -> a list of bytes:
+        extract_text_batch(first_pos, length)."""
+        rec = np.ascontiguousarray(records, dtype=self.NGRAM).reshape(-1)
+        if rec.size and (rec["first_pos"] == np.uint64(self.NO_POS)).any():
+            raise ValueError("the records carry no positions (positions=False)")
+        off, data = self.extract_text_batch(rec["first_pos"], np.full(rec.size, int(length), dtype=np.uint64))
+        return [data[int(off[q]):int(off[q + 1])].tobytes() for q in range(rec.size)]
+
     def match_stats_text(self, q, max_len=None):
         """ms[i] = the length of the longest prefix of q[i:] that occurs in the indexed text (capped at max_len), for a handle
         that indexes reverse(text) as from_text and locate_text have it: the statistics of reverse(q), flipped."""

@@ -758,6 +758,80 @@ int fmx_repeats_dev(const fmx_index *idx, const uint32_t *min_len, size_t k, con
                     void *d_out, size_t cap, size_t *n_out, fmx_repeat_summary *summary_or_null /* k */, void *stream);
 int fmx_repeats_last(double *invert_ms, double *class_ms, double *cover_ms, double *compact_ms);
 
+/* ---- n-grams: which strings of L bytes occur in the indexed text, and how often -- the k-mer table, its multiplicity
+ * spectrum and the most frequent phrases, from the LCP array.  Beyond the reference.  DESIGN.md 22.
+ * Definitions.  WINDOW, ELIGIBLE (a stop byte c != 0: a window that contains c is not) and CLASS are those of the repeats
+ * section: a class is the set of all eligible windows with the same L bytes.  The COUNT of a class is its number of windows
+ * (overlapping windows count: "aaaa" at L = 2 is one class of count 3), its FIRST position the smallest t.
+ * In the index's terms: a class is a maximal run of rows whose consecutive LCP[r] >= L; its interval [sp, sp + count) is the
+ * one search(reverse(window)) returns, its first position m - L - (the largest SA value of the run).  Exactly min(L, n)
+ * rows have fewer than L bytes in front of the sentinel; each is a run of one row and no window.
+ * One call takes k lengths (1 .. FMX_NGRAMS_MAX_LEVELS) and returns per length
+ *   RECORDS  fmx_ngram (sp, count, first_pos), one per eligible class with count >= min_count.  FMX_NGRAMS_BY_ROW: ascending
+ *            by sp (the lexicographic order of reverse(window)); FMX_NGRAMS_BY_COUNT: descending by count, ties ascending by
+ *            sp -- a total order.  top != 0 keeps the first `top` records of that order.  CSR as in repeats: length j's
+ *            records are out[out_off[j] .. out_off[j + 1]), out_off[k] == *n_out.
+ *   SUMMARY  fmx_ngram_summary: records (after top), selected (classes with count >= min_count, before top), distinct
+ *            (eligible classes of every count), windows (eligible windows), singletons, largest_count, largest_sp (the
+ *            smallest sp among the classes of that count) and largest_pos (its first position); all 0 without a class.
+ *   SPECTRUM (spectrum_bins = B in 1 .. FMX_NGRAMS_MAX_BINS; 0: none) uint64 spectrum[k * B]: entry c (1 <= c < B) of a length
+ *            is the number of eligible classes of count c, entry 0 the number with count >= B.
+ * opts == NULL: BY_ROW, min_count 2, no top, no spectrum, no stop byte.
+ * FMX_NGRAMS_NO_POS (a flag): first_pos and largest_pos come back as UINT64_MAX and NO INVERSION IS RUN -- counts, intervals,
+ * order, summary and spectrum come from the LCP array alone, the rows that are no windows by the closed form above.  Valid
+ * only with stop == 0 and min_count >= 2 (eligibility needs text positions, and a listed singleton has to be told from a short
+ * row); every other field equals the call with positions bit for bit.
+ * Capacity, the counting call (cap == 0, out == NULL), FMX_ERR_OVERFLOW with the exact total and out_off and the summaries
+ * complete, "nothing written past out[cap - 1]" and determinism: as in repeats.  A length above m is valid, has no records
+ * and runs no pass.
+ * FMX_ERR_ARG, decided before the device is touched: a null handle, lengths, out_off or n_out; k == 0 or k >
+ * FMX_NGRAMS_MAX_LEVELS; a length of 0; order > 1; an unknown flag; min_count == 0; FMX_NGRAMS_NO_POS with a stop byte or with
+ * min_count == 1; spectrum_bins > FMX_NGRAMS_MAX_BINS; spectrum_bins != 0 with a null spectrum; a reserved byte that is not 0;
+ * cap >= 2^32.
+ * The call needs the handle's LCP array and builds it when absent, with its refusals: fmx_open_block handles and n >= 2^32
+ * FMX_ERR_UNSUPPORTED before the device is touched, an index that is not the BWT of one text FMX_ERR_FORMAT.  Both forms
+ * ALLOCATE AND SYNCHRONISE (the _dev form: FMX_ERR_HIP under a stream capture, decided before anything is allocated, the
+ * capture left valid).  The need -- with positions about 17 bytes per row beside the LCP array (the suffix array, s, three u32
+ * work arrays) and 4 more with a stop byte, plus the inversion's temporaries; without positions 8 bytes per row; the LCP
+ * build's when that is still to come -- is checked against the free HBM first, the sort's buffers (28 bytes per selected class)
+ * once a length's selected classes are counted (FMX_ERR_NOMEM with the need in the message); every temporary is freed on every
+ * path.  No table and no counter of patterns seen changes; the launches are added to the handle's.
+ * fmx_ngrams_dev : d_out_off (u64[k + 1]) and d_out (24-byte records) in device memory; lengths, n_out, the summaries and
+ *                  the spectrum stay host pointers.
+ * fmx_ngrams_last: device time (ms) of the calling thread's last call by phase -- the inversion (with the stop scan; 0 for a
+ *                  FMX_NGRAMS_NO_POS call), the class passes, the selection (slot scan, keys, records), the sort -- summed over
+ *                  the lengths; any pointer may be NULL.
+ * FMX_NGRAMS_LDS_BINS: counts below it are histogrammed in LDS, counts at or above it go to global memory one by one (what
+ * tests stand on both sides of). */
+#define FMX_NGRAMS_BY_ROW 0u
+#define FMX_NGRAMS_BY_COUNT 1u
+#define FMX_NGRAMS_NO_POS 1u
+#define FMX_NGRAMS_MAX_LEVELS 64
+#define FMX_NGRAMS_MAX_BINS 65536u
+#define FMX_NGRAMS_LDS_BINS 1024
+typedef struct fmx_ngram_opts {
+  uint32_t order;         /* FMX_NGRAMS_BY_ROW | FMX_NGRAMS_BY_COUNT */
+  uint32_t flags;         /* FMX_NGRAMS_NO_POS or 0 */
+  uint64_t min_count;     /* >= 1 */
+  uint64_t top;           /* 0 = all */
+  uint32_t spectrum_bins; /* 0 .. FMX_NGRAMS_MAX_BINS */
+  uint8_t stop;           /* the stop byte; 0 = none */
+  uint8_t reserved[3];    /* must be 0 */
+} fmx_ngram_opts; /* 32 bytes */
+typedef struct fmx_ngram {
+  uint64_t sp, count, first_pos;
+} fmx_ngram; /* 24 bytes */
+typedef struct fmx_ngram_summary {
+  uint64_t records, selected, distinct, windows, singletons, largest_count, largest_sp, largest_pos;
+} fmx_ngram_summary; /* 64 bytes */
+int fmx_ngrams(const fmx_index *idx, const uint32_t *lengths, size_t k, const fmx_ngram_opts *opts,
+               uint64_t *out_off /* k + 1 */, fmx_ngram *out, size_t cap, size_t *n_out,
+               fmx_ngram_summary *summary_or_null /* k */, uint64_t *spectrum_or_null /* k * spectrum_bins */);
+int fmx_ngrams_dev(const fmx_index *idx, const uint32_t *lengths, size_t k, const fmx_ngram_opts *opts, void *d_out_off,
+                   void *d_out, size_t cap, size_t *n_out, fmx_ngram_summary *summary_or_null /* k */,
+                   uint64_t *spectrum_or_null /* k * spectrum_bins */, void *stream);
+int fmx_ngrams_last(double *invert_ms, double *class_ms, double *select_ms, double *sort_ms);
+
 /* ---- corpus: a directory of files as ONE index -- DirBWTReader (bwtreader.scala:17-173), the input side of the reference's
  * IndexerApp -- and, beyond the reference, the way back from a stream position to (document, offset).
  * The STREAM: the documents in the caller's order; in each, raw byte 0 becomes '\' '0', raw 1 becomes '\' '1' and raw 255
