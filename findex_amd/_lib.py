@@ -139,6 +139,20 @@ class fmx_occurrence(ctypes.Structure):
                 ("raw_len", ctypes.c_uint32), ("raw_off", ctypes.c_uint64)]
 
 
+FMX_PREPARE_LINES = 256               # fmx_prepare / fmx_drop_tables: the line table (fmx.h)
+
+
+class fmx_line_hit(ctypes.Structure):
+    _fields_ = [("group", ctypes.c_uint32), ("doc", ctypes.c_uint32), ("line_no", ctypes.c_uint64), ("start", ctypes.c_uint64),
+                ("len", ctypes.c_uint32), ("n_hits", ctypes.c_uint32), ("raw_off", ctypes.c_uint64), ("raw_len", ctypes.c_uint32),
+                ("first", ctypes.c_uint32)]
+
+
+# the same record as a numpy dtype (48 bytes)
+LINE_HIT = [("group", "<u4"), ("doc", "<u4"), ("line_no", "<u8"), ("start", "<u8"), ("len", "<u4"), ("n_hits", "<u4"),
+            ("raw_off", "<u8"), ("raw_len", "<u4"), ("first", "<u4")]
+
+
 FMX_MERGE_SEGMENT, FMX_MERGE_WARMUP, FMX_MERGE_TILE, FMX_MERGE_CONTEXT = 256, 32, 4096, 4096      # fmx.h
 MAX_TEXT_LEN = (1 << 32) - 2          # bytes one suffix sort takes (u32 suffix indices)
 
@@ -299,6 +313,15 @@ SYMBOLS = {
     "fmx_occurrences": (_i32, [_vp, _vp, _vp, _sz, _sz, _P(fmx_occ_opts), _vp, _vp, _sz, _P(_sz)]),
     "fmx_occurrences_dev": (_i32, [_vp, _vp, _vp, _sz, _sz, _P(fmx_occ_opts), _vp, _vp, _sz, _P(_sz), _vp]),
     "fmx_occurrences_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(_u64)]),
+    "fmx_lines_prepare": (_i32, [_vp, _vp, _sz]),
+    "fmx_lines_info": (_i32, [_vp, _P(_u64), _vp, _P(_u32), _P(_u32), _P(_u64), _P(ctypes.c_double)]),
+    "fmx_lines_batch": (_i32, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    "fmx_lines_batch_dev": (_i32, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "fmx_line_spans": (_i32, [_vp, _vp, _sz, _vp, _vp]),
+    "fmx_line_spans_dev": (_i32, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    "fmx_occurrence_lines": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _P(_sz)]),
+    "fmx_occurrence_lines_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, _P(_sz), _vp]),
+    "fmx_lines_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double)]),
     "fmx_regex_batch_create_multi": (_i32, [_vp, _sz, _vp, _sz, _P(_vp)]),
     "fmx_regex_batch_free_multi": (_i32, [_vp]),
     "fmx_regex_batch_match_multi": (_i32, [_vp, _vp, _vp, _sz, _P(_sz), _vp]),

@@ -321,6 +321,7 @@ class HipCorpusSearcher:
         if self.searcher.n != corpus.stream_len + 1:
             raise ValueError("the index has %d rows, the corpus stream %d bytes" % (self.searcher.n, corpus.stream_len))
         self._L = _lib.load()
+        self._doc_start = None                  # doc_start[n_docs + 1], fetched by the first lines call
 
     @classmethod
     def open(cls, base, bigEndian=True, device=0):
@@ -526,6 +527,91 @@ class HipCorpusSearcher:
         if not text:
             return off, occ, truncated
         return off, occ, truncated, self.read(occ["doc"], occ["raw_off"], occ["raw_len"]) if occ.size else []
+
+    # ---- lines (HipFMSearcher.line_of / occurrence_lines): the break set holds 10 and 1, so no line spans two files
+    def _lines_table(self):
+        """The searcher's line table with the separator in its set: {10, 1} is built unless the handle has a table whose set
+        holds byte 1 already (a call on the bare searcher would build {10}, under which a line runs across files)."""
+        _, bset, _, nbytes, _ = self.searcher.lines_info()
+        if not nbytes or 1 not in bset:
+            self.searcher.lines_prepare(b"\n\x01")
+
+    def _doc_lines(self, docs=None):
+        """(g0, count) of the documents `docs` (all when None): the global index of a document's first line and its number of
+        lines as `wc -l` counts them, the last unterminated line counted.  Two lookups per document asked for: at its first
+        position and at its separator."""
+        self._lines_table()
+        if self._doc_start is None:
+            self._doc_start = self.corpus.tables()[0]        # (a corpus never changes: extended() makes a new one)
+        ds = self._doc_start
+        d = np.arange(self.corpus.n_docs) if docs is None else np.asarray(docs, dtype=np.int64).reshape(-1)
+        if d.size and (d.min() < 0 or d.max() >= self.corpus.n_docs):
+            raise IndexError("document out of range")
+        sep = ds[d + 1] - np.uint64(1)
+        line, start, _ = self.searcher.line_of(np.concatenate([ds[d], sep]))
+        g0 = line[:d.size].astype(np.int64)
+        count = line[d.size:].astype(np.int64) - g0 + (start[d.size:] < sep)
+        return g0, count
+
+    def line_count(self, doc=None):
+        """The lines of document doc (an int64 array over all documents when None): its newlines, plus one when the file does
+        not end in one."""
+        if doc is None:
+            return self._doc_lines()[1]
+        return int(self._doc_lines([int(doc)])[1][0])
+
+    def _span_texts(self, start, end):
+        """The raw bytes of the stream ranges [start, end) -- whole lines, so both ends map exactly -> a list of bytes."""
+        start = np.asarray(start, dtype=np.uint64).reshape(-1)
+        if not start.size:
+            return []
+        doc, _, ro = self.corpus.map(start)
+        ro2 = self.corpus.map(end)[2]
+        return self.read(doc, ro, ro2 - ro)
+
+    def line(self, doc, line_no):
+        """Line line_no (1-based) of document doc, without its newline."""
+        g0, count = self._doc_lines([int(doc)])
+        if not 1 <= int(line_no) <= int(count[0]):
+            raise IndexError("document %d has %d lines" % (int(doc), int(count[0])))
+        start, end = self.searcher.line_spans([int(g0[0]) + int(line_no) - 1])
+        return self._span_texts(start, end)[0]
+
+    def grep_lines(self, regexes, mode="disjoint", max_steps=0, max_per=None, text=False, before=0, after=0, lineOnly=False,
+                   max_line=None):
+        """grep, reduced to lines: (off, hits, truncated) -- regex i's matching lines are hits[off[i]:off[i + 1]], a
+        HipFMSearcher.LINE_HIT array in (file, line) order, each with its 1-based line_no in the file, its raw_off / raw_len
+        there and n_hits, the matches that begin on it.  text=True (or any context): a fourth value, the lines' raw bytes; a
+        line longer than max_line (when given) is cut to that many bytes around its first match.  before / after > 0: a
+        fifth value, per hit ([lines before], [lines after]), at most that many, clipped to the file."""
+        self._lines_table()
+        off, occ, truncated = self.grep(regexes, mode=mode, max_steps=max_steps, max_per=max_per, lineOnly=lineOnly)
+        loff, hits = self.searcher.occurrence_lines(off, occ, corpus=self.corpus)
+        before, after = int(before), int(after)
+        if not (text or before or after):
+            return loff, hits, truncated
+        a, ln = hits["raw_off"].copy(), hits["raw_len"].astype(np.uint64)
+        if max_line is not None and hits.size:
+            first = occ["raw_off"][off[hits["group"]].astype(np.int64) + hits["first"].astype(np.int64)]
+            cut = ln > np.uint64(max_line)
+            lead = np.minimum(first - a, np.uint64(int(max_line) // 2))
+            a = np.where(cut, first - lead, a)
+            ln = np.where(cut, np.minimum(np.uint64(max_line), hits["raw_off"] + ln - a), ln)
+        lines = self.read(hits["doc"], a, ln) if hits.size else []
+        if not (before or after):
+            return loff, hits, truncated, lines
+        docs, d = np.unique(hits["doc"].astype(np.int64), return_inverse=True)      # the documents with hits alone
+        g0, count = self._doc_lines(docs)
+        no = hits["line_no"].astype(np.int64)
+        nb = np.minimum(no - 1, before)
+        na = np.maximum(np.minimum(count[d] - no, after), 0)
+        want = [np.arange(g - b, g + 1 + x) for g, b, x in zip((g0[d] + no - 1).tolist(), nb.tolist(), na.tolist())]
+        texts = self._span_texts(*self.searcher.line_spans(np.concatenate(want))) if want else []
+        context, at = [], 0
+        for b, x in zip(nb.tolist(), na.tolist()):
+            context.append((texts[at:at + b], texts[at + b + 1:at + b + 1 + x]))
+            at += b + 1 + x
+        return loff, hits, truncated, lines, context
 
     def _intervals(self, queries):
         esc = [escape(q)[::-1] for q in queries]

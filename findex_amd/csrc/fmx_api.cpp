@@ -309,6 +309,8 @@ static void destroy(Index *h) {
   if (h->d_loc_samples) (void)hipFree(h->d_loc_samples);
   if (h->d_lcp) (void)hipFree(h->d_lcp);
   if (h->d_ext_isa) (void)hipFree(h->d_ext_isa);
+  if (h->d_lin_brk) (void)hipFree(h->d_lin_brk);
+  if (h->d_lin_dir) (void)hipFree(h->d_lin_dir);
   for (CallCtx *c : h->ctx_pool) free_ctx(c);
   delete h;
 }
@@ -541,7 +543,7 @@ int fmx_index_config_set(fmx_index *idx, const char *key, const char *value) {
   const int pr = policy_set(H(idx)->policy, key, value, &why);
   if (pr == 0) return FMX_OK;
   if (pr == 2) return arg_fail(why);
-  return arg_fail("not a per-handle key (ktab, jump, jump_pairs, search_lanes, jump_chars, tables_after, table_budget, locate_sample, extract_sample)");
+  return arg_fail("not a per-handle key (ktab, jump, jump_pairs, search_lanes, jump_chars, tables_after, table_budget, locate_sample, extract_sample, lines_shift)");
 }
 
 int fmx_host_alloc(size_t bytes, void **out) {
@@ -635,7 +637,7 @@ int fmx_open_block(const uint8_t *bwt, uint64_t n, const int64_t bucket_starts[2
 
 int fmx_prepare(const fmx_index *idx, unsigned what) {
   if (!idx) return arg_fail("null argument");
-  if (what & ~(unsigned)(FMX_PREPARE_KTAB | FMX_PREPARE_SELECT | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_SEARCH | FMX_PREPARE_LOCATE | FMX_PREPARE_LCP | FMX_PREPARE_EXTRACT)) return arg_fail("unknown fmx_prepare flag");
+  if (what & ~(unsigned)(FMX_PREPARE_KTAB | FMX_PREPARE_SELECT | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_SEARCH | FMX_PREPARE_LOCATE | FMX_PREPARE_LCP | FMX_PREPARE_EXTRACT | FMX_PREPARE_LINES)) return arg_fail("unknown fmx_prepare flag");
   const Index *h = H(idx);
   if (what & FMX_PREPARE_LOCATE) {
     const int lc = locate_check(h);
@@ -647,6 +649,10 @@ int fmx_prepare(const fmx_index *idx, unsigned what) {
   }
   if (what & FMX_PREPARE_EXTRACT) {
     const int lc = extract_check(h);
+    if (lc) return lc;
+  }
+  if (what & FMX_PREPARE_LINES) {
+    const int lc = lines_check(h);
     if (lc) return lc;
   }
   int rc = use_device(h);
@@ -682,6 +688,10 @@ int fmx_prepare(const fmx_index *idx, unsigned what) {
     rc = extract_prepare(h, lease.c->stream);
     if (rc) return rc;
   }
+  if (what & FMX_PREPARE_LINES) {                                 // after LOCATE: its build reads the samples
+    rc = lines_prepare(h, lease.c->stream);
+    if (rc) return rc;
+  }
   // the literal search kernel this handle's tables select, calibrated here (its residency census: fmx_search.hip) so that no
   // _dev call ever has to read anything back
   if (what & (FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_SEARCH)) HIP_TRY(search_calibrate(h, lease.c->stream), "search calibration");
@@ -699,7 +709,7 @@ int fmx_prepare_ex(fmx_index *idx, unsigned what, uint64_t budget_bytes) {
 
 int fmx_drop_tables(fmx_index *idx, unsigned what) {
   if (!idx) return arg_fail("null argument");
-  if (!what || (what & ~(unsigned)(FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_LOCATE | FMX_PREPARE_LCP | FMX_PREPARE_EXTRACT))) return arg_fail("fmx_drop_tables frees the k-mer table, the row tables, the locate samples, the LCP array and the extract samples (FMX_PREPARE_KTAB, FMX_PREPARE_JUMP, FMX_PREPARE_FRONTIER, FMX_PREPARE_LOCATE, FMX_PREPARE_LCP, FMX_PREPARE_EXTRACT)");
+  if (!what || (what & ~(unsigned)(FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_LOCATE | FMX_PREPARE_LCP | FMX_PREPARE_EXTRACT | FMX_PREPARE_LINES))) return arg_fail("fmx_drop_tables frees the k-mer table, the row tables, the locate samples, the LCP array, the extract samples and the line table (FMX_PREPARE_KTAB, FMX_PREPARE_JUMP, FMX_PREPARE_FRONTIER, FMX_PREPARE_LOCATE, FMX_PREPARE_LCP, FMX_PREPARE_EXTRACT, FMX_PREPARE_LINES)");
   Index *h = H(idx);
   int rc = use_device(h);
   if (rc) return rc;

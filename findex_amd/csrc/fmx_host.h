@@ -71,6 +71,7 @@ struct TablePolicy {
   std::atomic<uint32_t> budget_ppb{0};         // != 0: a fraction (billionths) of the HBM that is free when a table is decided, the handle's own tables counted as free
   std::atomic<int> locate_sample{32};          // "locate_sample": the rate s of the locate samples (rows with SA % s == 0), 1 .. 4096
   std::atomic<int> extract_sample{32};         // "extract_sample": the rate s of the inverse-SA samples (the row of every SA value j s), 1 .. 4096
+  std::atomic<int> lines_shift{6};             // "lines_shift": the line table's directory step 2^S (fmx_lines.hip), 4 .. 16
   TablePolicy() = default;
   TablePolicy(const TablePolicy &o) { *this = o; }
   TablePolicy &operator=(const TablePolicy &o) {
@@ -80,6 +81,7 @@ struct TablePolicy {
     budget_bytes.store(o.budget_bytes.load()); budget_ppb.store(o.budget_ppb.load());
     locate_sample.store(o.locate_sample.load());
     extract_sample.store(o.extract_sample.load());
+    lines_shift.store(o.lines_shift.load());
     return *this;
   }
 };
@@ -194,6 +196,18 @@ struct Index {
   mutable bool ext_wide = false;
   mutable uint64_t ext_bytes = 0;
   mutable double ext_build_ms = 0.0;
+  // line table (fmx_lines.hip), built by fmx_prepare(FMX_PREPARE_LINES), fmx_lines_prepare or the first lines call; outside the
+  // table budget like the locate samples
+  mutable std::mutex lin_mu;
+  mutable bool lin_ready = false;
+  mutable void *d_lin_brk = nullptr;            // u32[max(n_brk, 1)]: the positions of the break bytes, ascending
+  mutable void *d_lin_dir = nullptr;            // u32[((n - 1) >> lin_shift) + 2]: dir[i] = the breaks before position i << lin_shift
+  mutable uint64_t lin_n_brk = 0;
+  mutable uint32_t lin_shift = 0;
+  mutable uint8_t lin_set[4] = {0, 0, 0, 0};    // the break set, ascending
+  mutable uint32_t lin_n_set = 0;
+  mutable uint64_t lin_bytes = 0;
+  mutable double lin_build_ms = 0.0;
   mutable uint64_t launches = 0;
   mutable double last_kernel_ms = 0.0;
   // the handle's host thread for the one-process-several-GPUs entry points (made at the first such call; fmx_hostpar.h)
@@ -261,6 +275,12 @@ uint64_t locate_invert_rows_bytes(const Index *h);
 int extract_check(const Index *h);              // FMX_ERR_UNSUPPORTED for handles extraction cannot serve (those of locate)
 int extract_prepare(const Index *h, hipStream_t st);
 void extract_drop(Index *h);
+
+// fmx_lines.hip: the line table.  lines_prepare builds it for the set {10} under lin_mu unless one exists
+// (allocates, synchronises `st`; an FMX_* status with its message); its entry points are in the unit.
+int lines_check(const Index *h);                // FMX_ERR_UNSUPPORTED for handles the line table cannot serve (locate's, n >= 2^32)
+int lines_prepare(const Index *h, hipStream_t st);
+void lines_drop(Index *h);
 
 // fmx_lcp.hip: the LCP array.  lcp_core: LCP[n] of s from s and its suffix array, all in device memory;
 // d_s is s itself (lcp_text_bytes(n) bytes: s, the sentinel 0 last, and zero padding); allocates 4 n bytes, synchronises `st`, returns an FMX_*

@@ -202,6 +202,13 @@ int policy_set(TablePolicy &p, const char *key, const char *value, const char **
     p.extract_sample.store((int)v);
     return 0;
   }
+  if (is("lines_shift")) {
+    char *end = nullptr;
+    const long v = std::strtol(value, &end, 10);
+    if (end == value || *end || v < 4 || v > 16) { *why = "lines_shift must be an integer 4 .. 16"; return 2; }
+    p.lines_shift.store((int)v);
+    return 0;
+  }
   if (is("jump_chars")) {
     uint64_t v = 0;
     if (!parse_u64(value, &v) || v < 8 || v > 11) { *why = "jump_chars must be 8, 9, 10 or 11"; return 2; }
@@ -442,6 +449,7 @@ int drop_tables(Index *h, unsigned what) {
   if (what & 32u) locate_drop(h);     // the locate samples (FMX_PREPARE_LOCATE)
   if (what & 64u) lcp_drop(h);        // the LCP array (FMX_PREPARE_LCP)
   if (what & 128u) extract_drop(h);   // the inverse-SA samples (FMX_PREPARE_EXTRACT)
+  if (what & 256u) lines_drop(h);     // the line table (FMX_PREPARE_LINES)
   return 0;
 }
 

@@ -1,11 +1,17 @@
 """grep over a corpus index: where do these regexes match, in which files?
 
     python -m findex_amd.grep BASE REGEX [REGEX ..] [--mode all|longest|disjoint] [--max-per N] [--max-steps N] [-C BYTES] [--count]
+                                                    [-n] [-A N] [-B N] [--context-lines N] [-c] [-l] [--max-line BYTES]
 
 BASE names BASE.bwt / BASE.aux / BASE.docs as `python -m findex_amd.index --dir D --out BASE` writes them.  One line per
 match, `name:raw_off:text`, regex by regex in (file, offset) order; -C BYTES shows that many bytes of the file around the
 match, cut at newlines; --count prints one count per regex instead.  The regexes are the reference's (REParser.re2post) and are
 matched against the escaped stream (HipCorpusSearcher.grep).
+
+By lines (HipCorpusSearcher.grep_lines; any of the flags below): -n prints `name:line_no:line`, one line of output per matching
+line, regex by regex in (file, line) order; -A N / -B N / --context-lines N add that many lines after / before / around, as
+`name-line_no-line`, with grep's `--` between groups that do not touch; -c prints `name:count` per file with matching lines,
+-l the names of those files.  A line longer than --max-line BYTES is cut to that many bytes around its first match.
 """
 import argparse
 import sys
@@ -22,6 +28,13 @@ def parser():
     ap.add_argument("--max-steps", type=int, default=0, help="longest match explored (0: the library's default)")
     ap.add_argument("-C", dest="context", type=int, default=0, metavar="BYTES")
     ap.add_argument("--count", action="store_true")
+    ap.add_argument("-n", "--line-number", action="store_true", help="whole matching lines with their numbers")
+    ap.add_argument("-A", dest="after", type=int, default=None, metavar="N", help="lines of context after a matching line")
+    ap.add_argument("-B", dest="before", type=int, default=None, metavar="N", help="lines of context before a matching line")
+    ap.add_argument("--context-lines", type=int, default=None, metavar="N", help="lines of context on both sides")
+    ap.add_argument("-c", "--count-lines", action="store_true", help="matching lines per file")
+    ap.add_argument("-l", "--files-with-matches", action="store_true", help="the files with a matching line")
+    ap.add_argument("--max-line", type=int, default=4096, metavar="BYTES", help="longer lines are cut around their first match")
     ap.add_argument("--little-endian", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     return ap
@@ -40,11 +53,90 @@ def with_context(cs, occ, context):
     return out
 
 
+def by_lines(a):
+    """Do the arguments ask for output by lines?"""
+    return bool(a.line_number or a.count_lines or a.files_with_matches or a.after is not None or a.before is not None
+                or a.context_lines is not None)
+
+
+def context_of(a):
+    """(before, after) in lines: -B / -A, each falling back to --context-lines."""
+    both = a.context_lines or 0
+    return (a.before if a.before is not None else both), (a.after if a.after is not None else both)
+
+
+def format_lines(names, hits, lines, number=True):
+    """`name:line_no:line` (`name:line` without numbers) for every hit, in order."""
+    return [names[int(h["doc"])] + (b":%d:" % int(h["line_no"]) if number else b":") + t for h, t in zip(hits, lines)]
+
+
+def format_context(names, hits, lines, context, number=True):
+    """The hits of ONE regex with their context lines (grep_lines' fifth value), as grep -A / -B prints them: a matching
+    line as `name:line_no:line`, a context line as `name-line_no-line`, every line once, `--` between two groups that neither
+    overlap nor touch."""
+    matching = {(int(h["doc"]), int(h["line_no"])): t for h, t in zip(hits, lines)}      # (a hit's text may be cut: --max-line)
+    out, last = [], None
+    for h, t, (bf, af) in zip(hits, lines, context):
+        d, no = int(h["doc"]), int(h["line_no"])
+        group = [(no - len(bf) + i, x) for i, x in enumerate(bf)] + [(no, t)] + [(no + 1 + i, x) for i, x in enumerate(af)]
+        if last is not None and (last[0] != d or group[0][0] > last[1] + 1):
+            out.append(b"--")
+        for k, x in group:
+            if last is not None and last[0] == d and k <= last[1]:
+                continue
+            sep = b":" if (d, k) in matching else b"-"
+            out.append(names[d] + sep + (b"%d" % k + sep if number else b"") + matching.get((d, k), x))
+            last = (d, k)
+    return out
+
+
+def format_counts(names, hits):
+    """`name:count` per file with matching lines, in file order."""
+    docs, counts = np.unique(hits["doc"], return_counts=True)
+    return [names[int(d)] + b":%d" % int(c) for d, c in zip(docs, counts)]
+
+
+def format_files(names, hits):
+    """The names of the files with matching lines, in file order."""
+    return [names[int(d)] for d in np.unique(hits["doc"])]
+
+
+def main_lines(cs, a, out):
+    before, after = context_of(a)
+    names = cs.corpus.names
+    if a.count_lines or a.files_with_matches:
+        off, hits, truncated = cs.grep_lines(a.regex, mode=a.mode, max_steps=a.max_steps, max_per=a.max_per)
+        fmt = format_counts if a.count_lines else format_files
+        for i in range(len(a.regex)):
+            for row in fmt(names, hits[int(off[i]):int(off[i + 1])]):
+                out.write(row + b"\n")
+        return truncated
+    res = cs.grep_lines(a.regex, mode=a.mode, max_steps=a.max_steps, max_per=a.max_per, text=True, before=before, after=after,
+                        max_line=a.max_line)
+    off, hits, truncated, lines = res[:4]
+    for i in range(len(a.regex)):
+        lo, hi = int(off[i]), int(off[i + 1])
+        if before or after:
+            rows = format_context(names, hits[lo:hi], lines[lo:hi], res[4][lo:hi], a.line_number)
+        else:
+            rows = format_lines(names, hits[lo:hi], lines[lo:hi], a.line_number)
+        for row in rows:
+            out.write(row + b"\n")
+    return truncated
+
+
 def main(argv=None):
     a = parser().parse_args(argv)
     from .corpus import HipCorpusSearcher
     cs = HipCorpusSearcher.open(a.base, bigEndian=not a.little_endian, device=a.device)
     try:
+        if by_lines(a):
+            out = sys.stdout.buffer
+            truncated = main_lines(cs, a, out)
+            out.flush()
+            if truncated:
+                print("matches longer than --max-steps were cut", file=sys.stderr)
+            return 0
         off, occ, truncated = cs.grep(a.regex, mode=a.mode, max_steps=a.max_steps, max_per=a.max_per)
         out = sys.stdout.buffer
         if a.count:

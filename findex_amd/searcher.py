@@ -627,6 +627,78 @@ class HipFMSearcher:
         occ = d_occ[: 4 * total].cpu().numpy().view(self.OCCURRENCE)
         return off, occ, bool(batch.truncated)
 
+    # ---- lines: text position -> line, occurrences -> the distinct lines that hold them (fmx_lines_batch)
+    LINE_HIT = np.dtype(_lib.LINE_HIT)
+    NO_LINE = (1 << 64) - 1
+
+    def lines_prepare(self, breaks=b"\n"):
+        """fmx_lines_prepare: build the line table for the break set `breaks` (1 .. 4 distinct non-zero bytes); an equal set
+        does nothing, another set rebuilds."""
+        b = np.frombuffer(bytes(breaks), dtype=np.uint8)
+        _lib.check(self._L.fmx_lines_prepare(self._h, _ptr(b) if b.size else None, b.size))
+
+    def lines_info(self):
+        """fmx_lines_info: (breaks found, break set as bytes, shift S, device bytes, build ms) of the line table; 0 breaks,
+        0 bytes and the default set when not built."""
+        nb, ns, sh, by, ms = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_double()
+        st = (ctypes.c_uint8 * 4)()
+        _lib.check(self._L.fmx_lines_info(self._h, ctypes.byref(nb), ctypes.cast(st, ctypes.c_void_p), ctypes.byref(ns), ctypes.byref(sh),
+                                          ctypes.byref(by), ctypes.byref(ms)))
+        return int(nb.value), bytes(st[: ns.value]), int(sh.value), int(by.value), float(ms.value)
+
+    def line_of(self, pos):
+        """fmx_lines_batch: (line, start, end) arrays for text positions: the 0-based global line index and the line's
+        [start, end) without its break byte; NO_LINE in all three for a position at or past the text's end."""
+        pos = np.ascontiguousarray(pos, dtype=np.uint64).reshape(-1)
+        out = [np.zeros(pos.size, dtype=np.uint64) for _ in range(3)]
+        _lib.check(self._L.fmx_lines_batch(self._h, _ptr(pos), pos.size, *[_ptr(o) for o in out]))
+        return tuple(out)
+
+    def line_of_dev(self, d_pos, k, d_line=0, d_start=0, d_end=0, stream=0):
+        """fmx_lines_batch_dev: device pointers (u64 throughout; an output of 0 is left out); with the table built it only
+        enqueues."""
+        _lib.check(self._L.fmx_lines_batch_dev(self._h, _dp(d_pos), int(k), _dp(d_line), _dp(d_start), _dp(d_end), _dp(stream)))
+
+    def line_spans(self, lines):
+        """fmx_line_spans: (start, end) arrays for global line indices; NO_LINE past the last line."""
+        lines = np.ascontiguousarray(lines, dtype=np.uint64).reshape(-1)
+        out = [np.zeros(lines.size, dtype=np.uint64) for _ in range(2)]
+        _lib.check(self._L.fmx_line_spans(self._h, _ptr(lines), lines.size, *[_ptr(o) for o in out]))
+        return tuple(out)
+
+    def line_spans_dev(self, d_line, k, d_start=0, d_end=0, stream=0):
+        """fmx_line_spans_dev: device pointers; with the table built it only enqueues."""
+        _lib.check(self._L.fmx_line_spans_dev(self._h, _dp(d_line), int(k), _dp(d_start), _dp(d_end), _dp(stream)))
+
+    def occurrence_lines(self, off, occ, corpus=None, cap=None):
+        """fmx_occurrence_lines: (off, occ) as occurrences or finditer return them -> (line_off[n_groups + 1], hits): group
+        g's distinct lines are hits[line_off[g]:line_off[g + 1]], a LINE_HIT array ascending by line, each with the number
+        of occurrences that begin on it.  cap=None: a counting call sizes the buffer."""
+        off = np.ascontiguousarray(off, dtype=np.uint64).reshape(-1)
+        occ = np.ascontiguousarray(occ, dtype=self.OCCURRENCE).reshape(-1)
+        if off.size < 2 or int(off[-1]) > occ.size:
+            raise ValueError("off: n_groups + 1 offsets into occ")
+        args = (self._h, corpus.handle if corpus is not None else None, _ptr(off), _ptr(occ) if occ.size else None, off.size - 1)
+        return self._csr_hits(self._L.fmx_occurrence_lines, args, off.size - 1, self.LINE_HIT, cap)
+
+    def occurrence_lines_dev(self, d_occ_off, d_occ, n_occ, n_groups, d_out_off, d_out, cap, corpus=None, stream=0, grow=False):
+        """fmx_occurrence_lines_dev: device pointers (u64 offsets, 32-byte occurrences in, 48-byte line hits out); allocates
+        and synchronises.  -> the exact number of lines; cap = 0 is the counting call, grow as occurrences_dev."""
+        n_out = ctypes.c_size_t()
+        rc = self._L.fmx_occurrence_lines_dev(self._h, corpus.handle if corpus is not None else None, _dp(d_occ_off), _dp(d_occ),
+                                              int(n_occ), int(n_groups), _dp(d_out_off), _dp(d_out), int(cap), ctypes.byref(n_out),
+                                              _dp(stream))
+        if not (rc == _lib.FMX_ERR_OVERFLOW and (int(cap) == 0 or grow)):
+            _lib.check(rc)
+        return int(n_out.value)
+
+    def lines_last(self):
+        """fmx_lines_last: (locate ms, keys + sort + directory ms) of this thread's last table build, (lookup ms, compaction
+        ms) of its last lookup or occurrence-lines call."""
+        t = [ctypes.c_double() for _ in range(4)]
+        _lib.check(self._L.fmx_lines_last(*[ctypes.byref(x) for x in t]))
+        return tuple(float(x.value) for x in t)
+
     # ---- matching statistics and maximal exact matches (fmx_match_stats_batch, fmx_mems_batch, DESIGN.md 16)
     MEM_HIT =np.dtype([("pattern", np.uint32), ("len", np.uint32), ("end", np.uint64), ("sp", np.uint64), ("ep", np.uint64)])
 
@@ -1035,27 +1107,27 @@ class HipFMSearcher:
         return ranks[: text.size], int(done.value)
 
     def prepare(self, ktab=True, select=False, jump=False, frontier=False, search=False, budget_bytes=0, locate=False,
-                lcp=False, extract=False):
+                lcp=False, extract=False, lines=False):
         """fmx_prepare[_ex]: build the k-mer jump table / the select directory / the literal search's row tables (J, R3) / the
-        regex frontier's row table / the locate samples / the LCP array / the extract samples now instead of at the threshold or at first use, and calibrate the
+        regex frontier's row table / the locate samples / the LCP array / the extract samples / the line table (break set {10}) now instead of at the threshold or at first use, and calibrate the
         search kernel they select (`search` alone: only that).  budget_bytes != 0: the handle's "table_budget" first
         (fmx_prepare_ex)."""
         what = (1 if ktab else 0) | (2 if select else 0) | (4 if jump else 0) | (8 if frontier else 0) | (16 if search else 0) \
-            | (32 if locate else 0) | (64 if lcp else 0) | (128 if extract else 0)
+            | (32 if locate else 0) | (64 if lcp else 0) | (128 if extract else 0) | (256 if lines else 0)
         if budget_bytes:
             _lib.check(self._L.fmx_prepare_ex(self._h, what, int(budget_bytes)))
         else:
             _lib.check(self._L.fmx_prepare(self._h, what))
 
-    def drop_tables(self, jump=True, frontier=True, ktab=False, locate=False, lcp=False, extract=False):
+    def drop_tables(self, jump=True, frontier=True, ktab=False, locate=False, lcp=False, extract=False, lines=False):
         """fmx_drop_tables: free the row jump table and the three-step row table / the frontier's row table / the k-mer table /
-        the locate samples / the LCP array / the extract samples."""
+        the locate samples / the LCP array / the extract samples / the line table."""
         _lib.check(self._L.fmx_drop_tables(self._h, (4 if jump else 0) | (8 if frontier else 0) | (1 if ktab else 0)
-                                           | (32 if locate else 0) | (64 if lcp else 0) | (128 if extract else 0)))
+                                           | (32 if locate else 0) | (64 if lcp else 0) | (128 if extract else 0) | (256 if lines else 0)))
 
     def config_set(self, key, value):
         """fmx_index_config_set: this handle's own table policy ("ktab", "jump", "jump_pairs", "search_lanes", "jump_chars", "tables_after",
-        "table_budget", "locate_sample", "extract_sample"); tables that exist stay until drop_tables."""
+        "table_budget", "locate_sample", "extract_sample", "lines_shift"); tables that exist stay until drop_tables."""
         _lib.check(self._L.fmx_index_config_set(self._h, key.encode(), str(value).encode()))
 
     # ---- statistics

@@ -64,7 +64,7 @@ const char *fmx_last_error(void);
 int fmx_abi_version(void);
 /* Process-wide options.  The table keys ("ktab", "jump", "jump_pairs", "search_lanes", "jump_chars", "tables_after", "table_budget",
  * "locate_sample": the locate samples' rate, fmx_locate_batch; "extract_sample": the inverse-SA samples' rate,
- * fmx_extract_text_batch) are the
+ * fmx_extract_text_batch; "lines_shift": the line table's directory step 2^S, 4 .. 16, fmx_lines_batch) are the
  * DEFAULTS a handle copies when it is opened; fmx_index_config_set changes one handle's own copy afterwards, so two handles
  * in one process (one JVM) can differ.  key "layout": "auto" (default: one-hot bit-vectors, one 64-byte block per
  * rank query, when sigma*n/7 bytes fit in free HBM and n < 2^37; else BWT bytes + checkpoints, two
@@ -269,11 +269,13 @@ int fmx_index_config_set(fmx_index *idx, const char *key, const char *value);
 enum { FMX_PREPARE_KTAB = 1, FMX_PREPARE_SELECT = 2, FMX_PREPARE_JUMP = 4, FMX_PREPARE_FRONTIER = 8, FMX_PREPARE_SEARCH = 16,
        FMX_PREPARE_LOCATE = 32 /* the locate samples (fmx_locate_batch below); fmx_drop_tables frees them */,
        FMX_PREPARE_LCP = 64 /* the LCP array (fmx_lcp_batch below); fmx_drop_tables frees it */,
-       FMX_PREPARE_EXTRACT = 128 /* the inverse-SA samples (fmx_extract_text_batch below); fmx_drop_tables frees them */ };
+       FMX_PREPARE_EXTRACT = 128 /* the inverse-SA samples (fmx_extract_text_batch below); fmx_drop_tables frees them */,
+       FMX_PREPARE_LINES = 256 /* the line table (fmx_lines_batch below), with the default break set {10} unless the handle has
+                                  one already, whatever its set; fmx_drop_tables frees it */ };
 int fmx_prepare(const fmx_index *idx, unsigned what);
 int fmx_prepare_ex(fmx_index *idx, unsigned what, uint64_t budget_bytes);
 /* Frees derived tables again (what = FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_LOCATE |
- * FMX_PREPARE_LCP | FMX_PREPARE_EXTRACT (the inverse-SA samples) in any combination: the k-mer table / the row jump table and the three-step row table, 16-32 n + 8 n bytes /
+ * FMX_PREPARE_LCP | FMX_PREPARE_EXTRACT (the inverse-SA samples) | FMX_PREPARE_LINES (the line table) in any combination: the k-mer table / the row jump table and the three-step row table, 16-32 n + 8 n bytes /
  * the frontier's row table, 8 n bytes / the locate samples / the LCP array, 4 n bytes) and forgets the handle's pattern count, so that they come back only by fmx_prepare or when the threshold is met
  * anew (under the handle's policy as it is then).  No other call may be using the handle. */
 int fmx_drop_tables(fmx_index *idx, unsigned what);
@@ -1092,6 +1094,92 @@ int fmx_occurrences(const fmx_index *idx, const fmx_corpus *corpus_or_null, cons
 int fmx_occurrences_dev(const fmx_index *idx, const fmx_corpus *corpus_or_null, const void *d_rec, size_t k, size_t n_groups,
                         const fmx_occ_opts *opts, void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream);
 int fmx_occurrences_last(double *locate_ms, double *sort_ms, double *select_ms, double *compact_ms, uint64_t *rows);
+
+/* ---- lines: the map from a text position to its line, and occurrences reduced to the distinct lines that hold them (grep -n
+ * over an index).  Beyond the reference.  DESIGN.md 23.
+ * t is the indexed text of n - 1 bytes; positions are the `pos` of fmx_occurrence, so the occurrence of a one-byte string at
+ * row r stands at n - 2 - SA[r].  A BREAK SET B holds 1 .. 4 distinct byte values (none of them 0); brk[0 .. n_brk) are the
+ * positions p with t[p] in B, ascending.
+ *   line(p)  = #{ j : brk[j] < p }: a 0-based GLOBAL line index; a break byte belongs to the line it ends.
+ *   start(L) = 0 for L == 0, else brk[L - 1] + 1.
+ *   end(L)   = brk[L] for L < n_brk, else n - 1: exclusive, the break byte is not part of the line.
+ * There are n_brk + 1 lines; the last may be empty.  B is {10} for a plain text and {10, 1} for a corpus stream: byte 1 is the
+ * separator behind every document (the corpus section above), so no line spans two files, and the 1-based line number of p in
+ * its document d is line(p) - line(doc_start[d]) + 1.  Escape pairs never contain a break byte, so the raw offsets of starts
+ * and ends follow fmx_corpus_map's rules unchanged.
+ * THE TABLE is derived from the index alone, like the locate samples: the breaks are the rows of the buckets [cf(c), cf(c + 1))
+ * of the c in B, located, turned into positions and sorted (no atomics: the same input gives the same bytes on every run).  It
+ * holds brk[] as u32 and a directory dir[i] = #{ j : brk[j] < i 2^S }, i = 0 .. ((n - 1) >> S) + 1, as u32; S is the key
+ * "lines_shift", 4 .. 16, default 6 (fmx_config_set: the default; fmx_index_config_set: one handle's).  A lookup reads
+ * dir[p >> S] and dir[(p >> S) + 1] and takes a lower bound among at most 2^S consecutive entries of brk.  Size: 4 n_brk +
+ * 4 (n >> S) bytes, outside the table budget.  The build needs the locate samples and builds them when absent, with locate's
+ * refusals (fmx_open_block handles FMX_ERR_UNSUPPORTED, an index that is not the BWT of one text FMX_ERR_FORMAT); it allocates
+ * and synchronises (FMX_ERR_HIP under a stream capture, decided before anything is allocated, the capture left valid), checks
+ * its need -- the SA values, two key and two value buffers, the histograms and the table itself -- against the free HBM first
+ * (FMX_ERR_NOMEM with the need in the message) and frees every temporary on every path.  Limit: n >= 2^32 is
+ * FMX_ERR_UNSUPPORTED (fmx_occurrences and the corpus stream have that limit anyway); positions and line indices are uint64_t
+ * in every signature so that lifting it changes no ABI.
+ * A call that finds no table builds one: with the set {10} without a corpus and {10, 1} with one.  A table whose set lacks
+ * byte 1, combined with a corpus, is FMX_ERR_ARG.
+ * fmx_lines_prepare   : builds the table for `breaks` (NULL / 0: {10}); an equal set (in any order): nothing to do; another
+ *                       set: the table is rebuilt.  FMX_ERR_ARG before the device is touched: a null handle, n_breaks > 4, a
+ *                       repeated break byte, break byte 0.
+ * fmx_lines_info      : the breaks found, the set, S, the table's bytes and its build time (0 breaks / bytes / ms and the
+ *                       default set while there is none); any pointer may be NULL.
+ * fmx_lines_batch     : for k positions line, start(line) and end(line); any output may be NULL; a position p >= n - 1 gives
+ *                       UINT64_MAX in all three.
+ * fmx_line_spans      : for k global line indices start and end; an index L > n_brk gives UINT64_MAX in both.
+ * The _dev forms of both take device pointers (u64 throughout) and, with a table present, ONLY ENQUEUE on `stream`; without
+ * one they build it first, and under a stream capture return FMX_ERR_HIP before anything is allocated.  k == 0 does nothing
+ * in the _dev forms: no table is built for it.
+ * fmx_occurrence_lines: reduces occurrence records to the distinct lines their `pos` fall on.  The input is what
+ *                       fmx_occurrences leaves: CSR offsets occ_off[n_groups + 1] over n_occ = occ_off[n_groups] records, the
+ *                       records of a group ascending by (pos, len).  OUTPUT is CSR over the same groups: one fmx_line_hit per
+ *                       distinct line of a group, ascending by line, out_off[n_groups] == *n_out.  A match that contains a
+ *                       break byte counts on the line it BEGINS on.  With a corpus `doc` and raw_off are fmx_corpus_map's of
+ *                       the line's start (the record's own `doc` and `group` fields are not read: a line begins in the
+ *                       document its hits lie in, and the CSR offsets say the group), raw_len is the raw offset of the end
+ *                       less raw_off, line_no is relative to doc_start[doc];
+ *                       without one doc = UINT32_MAX, line_no = line + 1, raw_off = start, raw_len = len.
+ *                       Capacity as fmx_occurrences: more than cap lines -> FMX_ERR_OVERFLOW with the EXACT total in *n_out,
+ *                       nothing written past out[cap - 1]; cap == 0 with out == NULL is the counting call.
+ *                       FMX_ERR_ARG, decided before the device is touched: a null handle, occ_off / d_occ_off, out_off or
+ *                       n_out; records missing while there are some; n_groups == 0 or > 2^26; n_occ > 2^26; cap >= 2^32; in
+ *                       the host form occ_off not non-decreasing or a pos >= n - 1; a corpus whose stream length != n - 1.
+ *                       The device form cannot see the records: it reads a pos >= n - 1 as "no line", skips the record and
+ *                       raises a flag, and the call returns FMX_ERR_ARG after the launch with nothing reported.  No record
+ *                       value leads outside the table or the outputs.  Both forms ALLOCATE AND SYNCHRONISE (FMX_ERR_HIP under
+ *                       a stream capture) and free every temporary on every path; the need (16 bytes per record and the
+ *                       scan's block totals) is checked against the free HBM first.
+ * fmx_lines_last      : the calling thread's last build (device ms of the locate walks, of the keys, the sort and the
+ *                       directory) and its last lookup and occurrence-lines call (ms of the lookups, of the compaction); any
+ *                       pointer may be NULL. */
+typedef struct fmx_line_hit {
+  uint32_t group;
+  uint32_t doc;     /* UINT32_MAX without a corpus */
+  uint64_t line_no; /* 1-based: in the document, or in the text without a corpus */
+  uint64_t start;   /* position of the line's first byte */
+  uint32_t len;     /* end - start: the line without its break byte, in stream bytes */
+  uint32_t n_hits;  /* occurrences that begin on this line */
+  uint64_t raw_off; /* raw offset of start in the file; == start without a corpus */
+  uint32_t raw_len; /* the line's length in the file; == len without a corpus */
+  uint32_t first;   /* index, within the group's occurrence records, of the first hit on this line */
+} fmx_line_hit;     /* 48 bytes */
+int fmx_lines_prepare(const fmx_index *idx, const uint8_t *breaks, size_t n_breaks);
+int fmx_lines_info(const fmx_index *idx, uint64_t *n_breaks_found, uint8_t set[4], uint32_t *n_set, uint32_t *shift,
+                   uint64_t *bytes, double *build_ms);
+int fmx_lines_batch(const fmx_index *idx, const uint64_t *pos, size_t k, uint64_t *line, uint64_t *start, uint64_t *end);
+int fmx_lines_batch_dev(const fmx_index *idx, const void *d_pos, size_t k, void *d_line, void *d_start, void *d_end,
+                        void *stream);
+int fmx_line_spans(const fmx_index *idx, const uint64_t *line, size_t k, uint64_t *start, uint64_t *end);
+int fmx_line_spans_dev(const fmx_index *idx, const void *d_line, size_t k, void *d_start, void *d_end, void *stream);
+int fmx_occurrence_lines(const fmx_index *idx, const fmx_corpus *corpus_or_null, const uint64_t *occ_off /* n_groups + 1 */,
+                         const fmx_occurrence *occ, size_t n_groups, uint64_t *out_off /* n_groups + 1 */, fmx_line_hit *out,
+                         size_t cap, size_t *n_out);
+int fmx_occurrence_lines_dev(const fmx_index *idx, const fmx_corpus *corpus_or_null, const void *d_occ_off, const void *d_occ,
+                             size_t n_occ, size_t n_groups, void *d_out_off, void *d_out, size_t cap, size_t *n_out,
+                             void *stream);
+int fmx_lines_last(double *locate_ms, double *sort_ms, double *lookup_ms, double *compact_ms);
 
 /* One process, several GPUs (the single-process form of SURVEY.md 8e for regexes; one process per GPU uses
  * findex_amd/distributed.py and an RCCL gather instead): the batch is cut into contiguous slices of about equal
