@@ -30,6 +30,7 @@
 #pragma once
 #include <type_traits>
 #include "fmx_device.h"
+#include "fmx_pool_deal.h"
 
 namespace fmx {
 
@@ -1280,22 +1281,21 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
       fix_off((uint64_t)batch + 2ull * nwaves, raw2a, raw2b, end1, len1);
     }
     // ---- the pool: batches nstatic .. nbatch - 1 by ticket, from kTixShards counters: the waves of eight consecutive workgroups
-    // (one per XCD) share a counter, wave w draws from counter (w / 32) mod 64, and ticket j of counter c is pool batch c + 64 j
-    // (fewer counters when the grid has fewer than 64 such groups).
+    // (one per XCD) share a counter, wave w draws from counter (w / 32) mod 64 (fewer counters when the grid has fewer than 64
+    // such groups).  The counters have UNEQUAL numbers of drawers whenever the groups are no multiple of 64 -- C3's 160 groups are
+    // three for counters 0..31 and two for the others -- so a counter owns a contiguous share of the pool in proportion to its
+    // drawers (fmx_pool_deal.h), and ticket j of it is that share's batch j.  (Equal shares, until then, gave the waves of the
+    // short-handed counters 2.6 drawn batches each and the others 1.75: the launch ended with them, a batch behind --
+    // profiles/pool_c3_ab.md.)
     // Every wave draws until its ticket is past its counter's share -- one failing draw each -- so a counter ends at its share
     // + its waves, and the wave that drew the last of those sets it back to zero for the stream's next launch (every other
     // draw from it has returned by then: the counter serialises them).
     if constexpr (kPool) {
     if (nstatic != nbatch) {
-      const uint32_t groups = (nwaves + 31u) >> 5;                                                      // of 32 waves (the last may be short)
-      const uint32_t nshards = groups < kTixShards ? groups : kTixShards;
-      const uint32_t shard = (wave >> 5) % nshards;
+      static_assert(kPoolShards == kTixShards, "fmx_pool_deal.h deals to the counters of a ticket area");
+      const uint32_t shard = pool_shard_of((uint32_t)__builtin_amdgcn_readfirstlane((int)wave), nwaves);      // (scalar arithmetic from here on)
       unsigned long long *tix = counters + (kCounterBytes + kCensusBytes + kCalibScratchBytes) / 8 +
                                 ((size_t)(tix_area - 1u) * kTixShards + shard) * kTixStride;
-      const uint32_t npool = nbatch - nstatic;
-      const uint32_t pool = npool > shard ? (npool - shard + nshards - 1u) / nshards : 0u;               // this counter's batches
-      const uint32_t mine = groups > shard ? (groups - shard + nshards - 1u) / nshards : 0u;             // ... its groups of waves
-      const uint32_t drawers = mine * 32u - ((groups - 1u) % nshards == shard ? groups * 32u - nwaves : 0u);
       // (tried: this first draw at the start of the wave's last strided batch, so that the first drawn batch does not begin
       // with the atomic's round trip -- one more value through the strided loop: the C3 form 42 -> 44 spilled scalar and 4 -> 8
       // spilled vector registers, the bytes layout's RW = 3 forms 73 -> 77 vector registers; not measured, not kept)
@@ -1304,14 +1304,22 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
       sl_draw = __builtin_amdgcn_s_memrealtime();
 #endif
       if (lane64 == 0) drawn = (uint32_t)atomicAdd(tix, 1ull);
+      // the counter's share, worked out while the first ticket is on its way: the loop keeps its first batch and its two ends
+      // (the divisor as a value the compiler knows nothing about: it shares the reciprocal of a plain `nwaves` with the division
+      // at the kernel's top, one more value through the strided loop -- the bytes layout's RW = 3 form 71 -> 73 vector registers,
+      // seven waves per SIMD -> six; the C3 form a spilled vector register)
+      uint32_t ndraw = nwaves;
+      asm volatile("" : "+s"(ndraw));
+      const PoolDeal deal = pool_deal(ndraw, shard, nbatch - nstatic);
+      const uint32_t first = nstatic + deal.first, pool = deal.count, last_draw = deal.count + deal.drawers - 1u;
       for (;;) {
         const uint32_t tk = (uint32_t)__builtin_amdgcn_readfirstlane((int)drawn);
         if (tk >= pool) {
-          if (tk == pool + drawers - 1u && lane64 == 0) atomicExch(tix, 0ull);
+          if (tk == last_draw && lane64 == 0) atomicExch(tix, 0ull);
           break;
         }
         if (lane64 == 0) drawn = (uint32_t)atomicAdd(tix, 1ull);      // the next one, looked at when this batch is done
-        batch = nstatic + shard + nshards * tk;
+        batch = first + tk;
 #ifdef FMX_SEARCHLOG
         sl_batches++;
 #endif

@@ -4,7 +4,9 @@ patched with the same log):
     tools/build_variant.sh slog -DFMX_SEARCHLOG && FMX_LIB=findex_amd/lib/variants/libfmx_slog.so python tools/search_wave_timeline.py c5
 Prints the launch's span on the device's 100 MHz clock, when the waves began / entered their batch loop / issued their first
 table lookup / drew their first ticket / left the loop / ended (percentiles), how long a batch took, and how many waves were
-alive at tenths of the span.  A second argument 4 reads the log of a build from before the two marks (four words per wave)."""
+alive at tenths of the span, and per class of ticket counter (by its number of drawers) what its waves drew from the pool and
+when they ended.  A second argument 4 reads the log of a build from before the two marks (four words per wave); a third is
+the number of full rounds the build draws (2)."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -13,6 +15,7 @@ import bench, findex_amd
 from findex_amd import _lib
 wl = sys.argv[1] if len(sys.argv) > 1 else "c5"
 words = int(sys.argv[2]) if len(sys.argv) > 2 else 6
+pooled_rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 2      # full rounds the build draws with the partial one (fmx_search.hip, kPoolRounds)
 log2n, sigma, k, m, seed = bench.LITERAL[wl]
 n = 1 << log2n
 dev = torch.device("cuda", 0)
@@ -69,6 +72,24 @@ for b in sorted(set(nb.tolist())):
     sel = nb == b
     print("waves with %d batches: %5d; batch loop ends p50 %6.1f p99 %6.1f, wave ends p50 %6.1f p99 %6.1f max %6.1f us" % (b, sel.sum(), np.percentile((tw[sel] - z) * T, 50), np.percentile((tw[sel] - z) * T, 99), np.percentile((t3[sel] - z) * T, 50), np.percentile((t3[sel] - z) * T, 99), ((t3[sel] - z) * T).max()))
 print("batches per wave: min %d max %d" % (nb.min(), nb.max()))
+# The pool by class of ticket counter (fmx_pool_deal.h): wave w draws from counter (w / 32) mod min(groups, 64), so the counters
+# have unequal numbers of drawers whenever the groups are no multiple of 64; a counter's share of the pool should be in
+# proportion.  What its waves drew is measured: their batches beyond the strided rounds.
+if words >= 6 and (draw != 0).any():
+    wv = np.nonzero(live)[0]
+    nw, total = int(wv.max()) + 1, int(nb.sum())
+    strided = total // nw - pooled_rounds                    # full rounds every wave takes by stride
+    nsh = min((nw + 31) // 32, 64)
+    shard = (wv >> 5) % nsh
+    drawers = np.bincount(shard, minlength=nsh)
+    took = np.bincount(shard, weights=nb - strided, minlength=nsh)
+    print("the pool: %d batches behind %d strided rounds, %d counters" % (total - strided * nw, strided, nsh))
+    for d in sorted(set(drawers.tolist()), reverse=True):
+        cs = drawers == d
+        sel = cs[shard]
+        print("  counters with %3d drawers: %2d (%5d waves); pool batches per counter %6.1f (a share in proportion: %6.1f), batches per wave %d + %.2f; waves end p50 %6.1f max %6.1f us"
+              % (d, cs.sum(), sel.sum(), took[cs].mean(), (total - strided * nw) * d / nw, strided, took[cs].sum() / sel.sum(),
+                 np.percentile((t3[sel] - z) * T, 50), ((t3[sel] - z) * T).max()))
 for f in range(0, 11):
     at = z + int(f / 10 * (t3.max() - z))
     print("  at %3d %% of the span: %5d waves alive, %5d not begun, %5d ended" % (10 * f, int(((t0 <= at) & (t3 > at)).sum()), int((t0 > at).sum()), int((t3 <= at).sum())))
