@@ -101,7 +101,9 @@ __device__ __forceinline__ uint32_t pat_chunk(const uint8_t *__restrict__ pat, c
 #ifdef FMX_SEARCHLOG
 // Diagnostic build only (tools/search_wave_timeline.py): begin and end of every wave of the last k_search4 launch on
 // the constant 100 MHz clock, the batches it searched, and when it issued its first table lookup and drew its first ticket.
-static __device__ unsigned long long g_searchlog[1u << 15][6];      // (each unit that instantiates k_search4 has its own)
+// Words 6 and 7: when the wave issued its last draw that gave it a batch (0: none did), and how many draws it made beside a
+// row-jump lookup (low half) and behind a batch's loop (high half) -- the pool's claim, below.
+static __device__ unsigned long long g_searchlog[1u << 15][8];      // (each unit that instantiates k_search4 has its own)
 #endif
 // G2 (round 5, one-hot layout only): a pattern is served by a PAIR of lanes instead of a quad -- 32 patterns per wave, the
 // dictionary's 64-byte block fetched as two 32-byte halves (fmx_device.h, Blk2).  tools/c3_halfbatch.py: with the same 1M
@@ -134,7 +136,8 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
 #ifdef FMX_SEARCHLOG
   const unsigned long long sl_t0 = __builtin_amdgcn_s_memrealtime();
   unsigned long long sl_t1 = 0, sl_look = 0, sl_draw = 0;      // sl_look: the first table lookup goes out; sl_draw: the first ticket is drawn (0: never)
-  uint32_t sl_batches = 0;
+  uint32_t sl_claim = 0, sl_last = 0;                          // the newest draw goes out; the newest one that gave a batch did (ticks from sl_t0)
+  uint32_t sl_batches = 0, sl_claims = 0;                      // sl_claims: draws beside a lookup (low half) and behind a batch's loop
 #endif
   // the residency census (fmx_device.h): when this workgroup began
   if (threadIdx.x == 0 && blockIdx.x < kCensusBlocks) {
@@ -215,8 +218,9 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
   // (C2 83-110 us, C5 244-294 us p10-p99).  So when the host hands the launch a ticket area (bits 16-23 of `spin`; fmx_device.h,
   // kTixAreas) and there are four rounds or more, all rounds but the last two full ones are strided as before and the rest --
   // two to three rounds' worth -- is a pool: a wave that has done its share draws batch after batch from it (one returning
-  // atomic each, issued a batch ahead) until it is empty.  A drawn batch starts cold (its offsets, then its bytes: two
-  // round trips the strided ones have behind them), which is why only the end is drawn; the strided part keeps its code
+  // atomic each, issued a round trip before the batch it is in ends, or a batch ahead: "the pool", below) until it is empty.
+  // A drawn batch starts cold (its offsets, then its bytes: two round trips the strided ones have behind them), which is
+  // why only the end is drawn; the strided part keeps its code
   // and its registers (tools/r05_tickets.patch drew every batch: +2.5-4 % for the drawing, -6-7 % for its state in the loop).
   // (not in the quads' kernels with a row jump table: the second copy of the batch body costs them 4 vector and 9 scalar
   // registers spilled at six waves per SIMD -- C3 by quads 0.137-0.140 -> 0.143 ms; their large batches go to the pairs)
@@ -706,6 +710,13 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
     // ever a merge with the result of a global load -- the compiler waits for ALL outstanding loads (`vmcnt(0)`) where it
     // meets such a value, and the next batch's loads issued below would be among them.
     // AHEAD: a strided batch, which requests the next one's bytes and the offsets of the one after it; a drawn one does not
+    // The pool's claim (the pool, below): a drawn batch of a kernel with a row jump table draws the wave's next ticket itself,
+    // beside its last row-jump lookup.  The state is the drawn copy's alone: the counter, the ticket (lane 0's) and whether the
+    // batch being searched has drawn.
+    constexpr bool kClaimBeside = kPool && JT != 0u;
+    [[maybe_unused]] unsigned long long *tix = nullptr;
+    [[maybe_unused]] uint32_t drawn = 0;
+    [[maybe_unused]] bool claimed = false;
     auto search_one_batch = [&](auto staged_tag, auto ahead_tag) {
     constexpr bool STAGED = decltype(staged_tag)::value;
     constexpr bool AHEAD = decltype(ahead_tag)::value;
@@ -1003,6 +1014,24 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
           bool jumped = false, pair_both = false, pair_then_miss = false;
           uint64_t rowj = 0;
           uint32_t nrows = 1;
+          // A drawn batch claims the wave's next one here (the pool, below): when no live group will have characters left
+          // behind the steps this lookup can give it (jc, or 2 jc by a pair; a group that cannot look up has some left), this is
+          // the batch's last lookup and the next ticket is wanted one round trip from now.  The draw goes out BEHIND the entry's
+          // load; the compiler aggregates it over the wave and waits for the ticket at once, with the entry (profiles/claim_c3_ab.md).
+          bool claim_now = false;
+          if constexpr (!AHEAD && kClaimBeside) claim_now = !claimed && !__builtin_amdgcn_ballot_w64(alive && (!can || rem > (can2 ? 2u * jc : jc)));
+          auto claim_beside = [&]() {
+            if constexpr (!AHEAD && kClaimBeside) {
+              if (claim_now) {
+                if (lane64 == 0) drawn = (uint32_t)atomicAdd(tix, 1ull);
+                claimed = true;
+#ifdef FMX_SEARCHLOG
+                sl_claim = (uint32_t)(__builtin_amdgcn_s_memrealtime() - sl_t0);
+                sl_claims++;
+#endif
+              }
+            }
+          };
           // ONE 16-byte load per row, everything taken out of it unconditionally: with the row used only under `if (hit)`,
           // the compiler sank that half of the load behind the comparison -- two dependent loads per lookup (round 4,
           // profiles/r04_c3_bound.md)
@@ -1010,6 +1039,7 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
             // one row per group: every lane of the group loads the same entry, the row comes straight out of it
             uint4 je = make_uint4(0, 0, 0, 0);
             if (can) je = jtab[(JT == 2u ? 2ull * sp : sp) + (half && can2 ? 1u : 0u)];
+            claim_beside();
             const uint32_t d0 = je.x ^ p0, d1 = je.y ^ p1, d2 = (je.z ^ p2) & m2;
             jumped = can && (d0 | d1 | d2) == 0u;
             // (an entry's character of step s is its byte s: the first byte that differs is the step that fails)
@@ -1041,6 +1071,7 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
               uint4 j0 = make_uint4(0, 0, 0, 0), j1 = make_uint4(0, 0, 0, 0);
               if (mn0) j0 = jtab[JT == 2u ? 2ull * (sp + t) : sp + t];
               if (mn1) j1 = jtab[JT == 2u ? 2ull * (sp + 2u + t) : sp + 2u + t];
+              claim_beside();
               const uint32_t d0 = j0.x ^ p0, d1 = j0.y ^ p1, d2 = (j0.z ^ p2) & m2;
               const bool hit0 = mn0 && (d0 | d1 | d2) == 0u;
               const bool hit1 = mn1 && ((j1.x ^ p0) | (j1.y ^ p1) | ((j1.z ^ p2) & m2)) == 0u;
@@ -1260,6 +1291,17 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
       } else {
         search_one_batch(std::false_type{}, ahead_tag);
       }
+      if constexpr (!decltype(ahead_tag)::value && kClaimBeside) {
+        // a drawn batch that did not claim beside a lookup (it ended on a three-step word, a rank step or a miss, or had no
+        // loop at all) draws here, in front of the walk of its parked patterns: the round trip is paid, which costs only time
+        if (!claimed) {
+          if (lane64 == 0) drawn = (uint32_t)atomicAdd(tix, 1ull);
+#ifdef FMX_SEARCHLOG
+          sl_claim = (uint32_t)(__builtin_amdgcn_s_memrealtime() - sl_t0);
+          sl_claims += 1u << 16;
+#endif
+        }
+      }
       if constexpr (RW != 0u) {
         if (nrows >= 64u) {
           if (npark > kParkCap - 64u) walk_parked(std::false_type{});         // room for all a rows phase may hand over
@@ -1294,14 +1336,14 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
     if (nstatic != nbatch) {
       static_assert(kPoolShards == kTixShards, "fmx_pool_deal.h deals to the counters of a ticket area");
       const uint32_t shard = pool_shard_of((uint32_t)__builtin_amdgcn_readfirstlane((int)wave), nwaves);      // (scalar arithmetic from here on)
-      unsigned long long *tix = counters + (kCounterBytes + kCensusBytes + kCalibScratchBytes) / 8 +
-                                ((size_t)(tix_area - 1u) * kTixShards + shard) * kTixStride;
+      tix = counters + (kCounterBytes + kCensusBytes + kCalibScratchBytes) / 8 +
+            ((size_t)(tix_area - 1u) * kTixShards + shard) * kTixStride;
       // (tried: this first draw at the start of the wave's last strided batch, so that the first drawn batch does not begin
       // with the atomic's round trip -- one more value through the strided loop: the C3 form 42 -> 44 spilled scalar and 4 -> 8
       // spilled vector registers, the bytes layout's RW = 3 forms 73 -> 77 vector registers; not measured, not kept)
-      uint32_t drawn = 0;
 #ifdef FMX_SEARCHLOG
       sl_draw = __builtin_amdgcn_s_memrealtime();
+      sl_claim = (uint32_t)(sl_draw - sl_t0);
 #endif
       if (lane64 == 0) drawn = (uint32_t)atomicAdd(tix, 1ull);
       // the counter's share, worked out while the first ticket is on its way: the loop keeps its first batch and its two ends
@@ -1318,11 +1360,28 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
           if (tk == last_draw && lane64 == 0) atomicExch(tix, 0ull);
           break;
         }
-        if (lane64 == 0) drawn = (uint32_t)atomicAdd(tix, 1ull);      // the next one, looked at when this batch is done
-        batch = first + tk;
 #ifdef FMX_SEARCHLOG
         sl_batches++;
+        sl_last = sl_claim;
 #endif
+        // The next one, looked at when this batch is done.  Drawn HERE, a wave holds two claimed batches within a round trip of
+        // arriving at the pool, and 95 % of C3's pool (2.1 batches per wave) was dealt in order of arrival, before any wave's pace
+        // could be seen: dry 38 us before the launch ended, the early waves with three drawn batches ending last and the late ones
+        // idle (profiles/claim_c3_before_wave_timeline.txt).  The draw only has to hide the atomic's round trip, so a kernel
+        // with a row jump table makes it beside the batch's last lookup (search_one_batch, claim_beside: 99.97 % of C3's claims;
+        // behind the loop, in one_batch, where there was no lookup to stand beside) and a wave is committed one batch ahead, not
+        // two: the pool is dry 25 us before the end, C3 0.1028 -> 0.1004 ms (profiles/claim_c3_ab.md; the draw behind EVERY
+        // batch, its round trip in the open: 0.1007, simpler and the same within the spread; the lookup's side is never behind).
+        // The kernels without a row jump table (RW: C5, the bytes layout) have no lookup in their loop to stand beside -- the
+        // bytes form sits one register under a lost wave per SIMD -- and keep the draw here.
+        if constexpr (!kClaimBeside) {
+          if (lane64 == 0) drawn = (uint32_t)atomicAdd(tix, 1ull);
+#ifdef FMX_SEARCHLOG
+          sl_claim = (uint32_t)(__builtin_amdgcn_s_memrealtime() - sl_t0);
+#endif
+        }
+        claimed = false;
+        batch = first + tk;
         {
           uint64_t a0, a1;
           load_off_raw(batch, a0, a1);
@@ -1366,6 +1425,7 @@ __global__ __launch_bounds__(kSThreads) __attribute__((amdgpu_waves_per_eu(G2 ? 
     unsigned long long *e = g_searchlog[wave];
     e[0] = sl_t0; e[1] = ((sl_t1 - sl_t0) & 0xFFFFFFFFull) | ((sl_tw - sl_t0) << 32); e[2] = sl_t2; e[3] = __builtin_amdgcn_s_memrealtime() | ((unsigned long long)sl_batches << 48);
     e[4] = sl_look; e[5] = sl_draw;
+    e[6] = sl_last ? sl_t0 + sl_last : 0ull; e[7] = (unsigned long long)(sl_claims & 0xFFFFu) | ((unsigned long long)(sl_claims >> 16) << 32);
   }
 #endif
   if (threadIdx.x == 0 && blockIdx.x < kCensusBlocks)       // ... and when its first wave ended
