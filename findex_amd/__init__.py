@@ -23,6 +23,8 @@ package is the thin host-side mirror of the reference's Scala interface for that
                                                    HipCorpusSearcher.grep, python -m findex_amd.grep
                                                    HipFMSearcher.ngrams / .ngram_texts (which strings of L bytes occur, how often),
                                                    HipCorpusSearcher.frequent_phrases, python -m findex_amd.index --ngrams
+                                                   HipFMSearcher.line_query (lines with A and B, A not C, A near B, grep -v),
+                                                   HipCorpusSearcher.grep_lines_where / .grep_lines_inverted, grep -v / --and / --not
 
 There is no CPU fallback: importing works anywhere, but every compute call needs the built
 library and a HIP device and fails loudly otherwise.

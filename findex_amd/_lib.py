@@ -153,6 +153,13 @@ LINE_HIT = [("group", "<u4"), ("doc", "<u4"), ("line_no", "<u8"), ("start", "<u8
             ("raw_off", "<u8"), ("raw_len", "<u4"), ("first", "<u4")]
 
 
+FMX_LQ_ALL_LINES, FMX_LQ_NOT = 0xFFFFFFFF, 1      # fmx_line_query: the anchor "every real line", a negated term (fmx.h)
+
+
+class fmx_line_term(ctypes.Structure):
+    _fields_ = [("group", ctypes.c_uint32), ("window", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 FMX_MERGE_SEGMENT, FMX_MERGE_WARMUP, FMX_MERGE_TILE, FMX_MERGE_CONTEXT = 256, 32, 4096, 4096      # fmx.h
 MAX_TEXT_LEN = (1 << 32) - 2          # bytes one suffix sort takes (u32 suffix indices)
 
@@ -322,6 +329,10 @@ SYMBOLS = {
     "fmx_occurrence_lines": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _P(_sz)]),
     "fmx_occurrence_lines_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, _P(_sz), _vp]),
     "fmx_lines_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double)]),
+    "fmx_line_query": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _P(_sz)]),
+    "fmx_line_query_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _P(_sz), _vp]),
+    "fmx_line_query_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_uint64),
+                                   _P(ctypes.c_uint64)]),
     "fmx_regex_batch_create_multi": (_i32, [_vp, _sz, _vp, _sz, _P(_vp)]),
     "fmx_regex_batch_free_multi": (_i32, [_vp]),
     "fmx_regex_batch_match_multi": (_i32, [_vp, _vp, _vp, _sz, _P(_sz), _vp]),

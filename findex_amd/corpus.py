@@ -587,12 +587,20 @@ class HipCorpusSearcher:
         self._lines_table()
         off, occ, truncated = self.grep(regexes, mode=mode, max_steps=max_steps, max_per=max_per, lineOnly=lineOnly)
         loff, hits = self.searcher.occurrence_lines(off, occ, corpus=self.corpus)
+        return self._lines_result(loff, hits, truncated, off, occ, hits["group"], text, before, after, max_line)
+
+    def _lines_result(self, loff, hits, truncated, off, occ, occ_group, text, before, after, max_line):
+        """What grep_lines returns for the line hits (loff, hits): the texts and the context when asked for.  occ_group: per
+        hit the group of (off, occ) its `first` counts in; a hit without a first match (first == UINT32_MAX) is cut from
+        the line's beginning."""
         before, after = int(before), int(after)
         if not (text or before or after):
             return loff, hits, truncated
         a, ln = hits["raw_off"].copy(), hits["raw_len"].astype(np.uint64)
         if max_line is not None and hits.size:
-            first = occ["raw_off"][off[hits["group"]].astype(np.int64) + hits["first"].astype(np.int64)]
+            has = hits["first"] != np.uint32(0xFFFFFFFF)
+            at = np.where(has, off[np.where(has, occ_group, 0)].astype(np.int64) + hits["first"].astype(np.int64), 0)
+            first = np.where(has, occ["raw_off"][at] if occ.size else a, a)
             cut = ln > np.uint64(max_line)
             lead = np.minimum(first - a, np.uint64(int(max_line) // 2))
             a = np.where(cut, first - lead, a)
@@ -612,6 +620,39 @@ class HipCorpusSearcher:
             context.append((texts[at:at + b], texts[at + b + 1:at + b + 1 + x]))
             at += b + 1 + x
         return loff, hits, truncated, lines, context
+
+    def grep_lines_where(self, queries, mode="disjoint", max_steps=0, max_per=None, text=False, before=0, after=0, lineOnly=False,
+                         max_line=None):
+        """Line queries over regexes (HipFMSearcher.line_query): queries = [(anchor_regex_or_None, [(regex,
+        window, negate), ..]), ..] -> what grep_lines returns, with groups equal to query indices.  Query q's lines are the
+        lines that hold its anchor regex (every line of every file when None) and satisfy all its terms: a term asks for a
+        line with `regex` within `window` lines in the same file (0: the same line, "file": anywhere in the file), or with
+        negate for none.  The distinct regexes of all queries are matched in one grep and reduced to lines once; the algebra
+        runs on the device.  A line "holds" a regex when a match begins on it (lineOnly, or mode "all" / "longest", for
+        grep's strict sense)."""
+        queries = [(a, list(terms)) for a, terms in queries]
+        regexes, number = [], {}
+        for r in [a for a, _ in queries if a is not None] + [t[0] for _, terms in queries for t in terms]:
+            if r not in number:
+                number[r] = len(regexes)
+                regexes.append(r)
+        self._lines_table()
+        if regexes:
+            off, occ, truncated = self.grep(regexes, mode=mode, max_steps=max_steps, max_per=max_per, lineOnly=lineOnly)
+            loff, hits = self.searcher.occurrence_lines(off, occ, corpus=self.corpus)
+        else:                                                # only anchors without terms: one empty group
+            off, occ, truncated = np.zeros(2, dtype=np.uint64), np.zeros(0, dtype=self.searcher.OCCURRENCE), False
+            loff, hits = np.zeros(2, dtype=np.uint64), np.zeros(0, dtype=self.searcher.LINE_HIT)
+        lq = [(None if a is None else number[a], [(number[r], w, neg) for r, w, neg in terms]) for a, terms in queries]
+        qoff, out = self.searcher.line_query(loff, hits, lq, corpus=self.corpus)
+        anchors = np.array([0 if a is None else a for a, _ in lq], dtype=np.int64)
+        return self._lines_result(qoff, out, truncated, off, occ, anchors[out["group"].astype(np.int64)], text, before, after, max_line)
+
+    def grep_lines_inverted(self, regexes, mode="disjoint", max_steps=0, max_per=None, text=False, before=0, after=0, lineOnly=False,
+                            max_line=None):
+        """grep -v: per regex the lines of all files on which no match of it begins; returns what grep_lines returns."""
+        return self.grep_lines_where([(None, [(r, 0, True)]) for r in regexes], mode=mode, max_steps=max_steps, max_per=max_per,
+                                     text=text, before=before, after=after, lineOnly=lineOnly, max_line=max_line)
 
     def _intervals(self, queries):
         esc = [escape(q)[::-1] for q in queries]

@@ -529,6 +529,12 @@ int fmx_config_set(const char *key, const char *value) {
     set_host_threads((unsigned)v);
     return FMX_OK;
   }
+  {
+    const char *lq_why = nullptr;
+    const int lr = lq_config(key, value, &lq_why);
+    if (lr == 0) return FMX_OK;
+    if (lr == 2) return arg_fail(lq_why);
+  }
   // the table policy's keys: the defaults a handle copies when it is opened (fmx_index_config_set: one handle's own)
   const char *why = nullptr;
   const int pr = policy_set(default_policy(), key, value, &why);

@@ -281,6 +281,13 @@ void extract_drop(Index *h);
 int lines_check(const Index *h);                // FMX_ERR_UNSUPPORTED for handles the line table cannot serve (locate's, n >= 2^32)
 int lines_prepare(const Index *h, hipStream_t st);
 void lines_drop(Index *h);
+// a table for a call that needs one: the handle's, or {10} / {10, 1} (with a corpus) built on `st` (a stream of the handle's
+// when null); FMX_ERR_ARG for a table that lacks byte 1 combined with a corpus
+int lines_ensure(const Index *h, bool with_corpus, hipStream_t st);
+
+// fmx_linequery.hip: the query algebra over line-hit lists, its entry points included.  lq_config: the
+// process-wide key "lq_narrow" = on | off (default off); 0 ok, 1 not this unit's key, 2 bad value (*why says which values there are)
+int lq_config(const char *key, const char *value, const char **why);
 
 // fmx_lcp.hip: the LCP array.  lcp_core: LCP[n] of s from s and its suffix array, all in device memory;
 // d_s is s itself (lcp_text_bytes(n) bytes: s, the sentinel 0 last, and zero padding); allocates 4 n bytes, synchronises `st`, returns an FMX_*

@@ -23,6 +23,7 @@
 
 #include "fmx_corpus_dev.h"
 #include "fmx_host.h"
+#include "fmx_lines_dev.h"
 
 namespace fmx {
 
@@ -30,22 +31,6 @@ constexpr int kLinThreads = 256;
 constexpr uint32_t kLinNone = 0xffffffffu;           // a record without a line
 constexpr uint64_t kLinMaxK = 1ull << 26;            // occurrence records and groups per call
 static_assert(sizeof(fmx_line_hit) == 48 && sizeof(fmx_occurrence) == 32, "record sizes are ABI");
-
-struct LinesDev {
-  const uint32_t *brk, *dir;
-  uint64_t n_brk, len;                               // len = n - 1, the bytes of the text
-  uint32_t shift;
-};
-
-__device__ __forceinline__ uint64_t lin_line(const LinesDev &L, uint64_t p) {      // p < len
-  const uint64_t b = p >> L.shift;
-  uint64_t lo = L.dir[b], hi = L.dir[b + 1];
-  hi = hi < L.n_brk ? hi : L.n_brk;
-  lo = lo < hi ? lo : hi;
-  return co_lower(L.brk, lo, hi, p);
-}
-__device__ __forceinline__ uint64_t lin_start(const LinesDev &L, uint64_t line) { return line ? (uint64_t)L.brk[line - 1] + 1 : 0; }
-__device__ __forceinline__ uint64_t lin_end(const LinesDev &L, uint64_t line) { return line < L.n_brk ? (uint64_t)L.brk[line] : L.len; }
 
 __global__ __launch_bounds__(kLinThreads) void k_lines_keys(const unsigned long long *__restrict__ sa, uint64_t m, uint64_t n,
                                                             unsigned long long sentinel, unsigned long long *__restrict__ key,
@@ -155,31 +140,11 @@ __global__ __launch_bounds__(kLinThreads) void k_ol_emit(LinesDev L, const unsig
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < lim; t += stride) {
     const uint64_t i = hidx[t], next = t + 1 < total ? (uint64_t)hidx[t + 1] : n_occ;
-    const uint64_t l = line[i], s = lin_start(L, l), e = lin_end(L, l);
     const uint32_t g = grp[i];
-    fmx_line_hit o;
+    fmx_line_hit o = lin_record(L, line[i], has_map, m);
     o.group = g;
-    o.doc = 0xffffffffu;
-    o.line_no = l + 1;
-    o.start = s;
-    o.len = (uint32_t)(e - s);
     o.n_hits = (uint32_t)(next - i);
-    o.raw_off = s;
-    o.raw_len = o.len;
     o.first = (uint32_t)(i - occ_off[g]);
-    if (has_map) {
-      // the line begins in the document its hits lie in (the separator before it is a break), and ends on a break byte of
-      // that document, which no escape pair contains
-      uint32_t d = 0xffffffffu, d2;
-      uint64_t eo, ro = ~0ull, ro2 = ~0ull;
-      if (co_map(m, s, d, eo, ro)) {
-        o.line_no = l - lin_line(L, m.doc_start[d]) + 1;
-        if (!co_map(m, e, d2, eo, ro2)) ro2 = ro + (e - s);
-      }
-      o.doc = d;
-      o.raw_off = ro;
-      o.raw_len = (uint32_t)(ro2 - ro);
-    }
     out[t] = o;
   }
 }
@@ -207,11 +172,6 @@ int bits_for(uint64_t v) {                           // the bits that hold 0 .. 
   int b = 1;
   while (b < 64 && (v >> b) != 0) b++;
   return b;
-}
-
-LinesDev lines_dev(const Index *h) {
-  return LinesDev{static_cast<const uint32_t *>(h->d_lin_brk), static_cast<const uint32_t *>(h->d_lin_dir), h->lin_n_brk, h->n - 1,
-                  h->lin_shift};
 }
 
 void add_launches(const Index *h, uint64_t launches) {
@@ -354,6 +314,8 @@ int lines_build(const Index *h, const uint8_t *set, uint32_t n_set, hipStream_t 
   return FMX_OK;
 }
 
+}  // namespace
+
 // A table for a call that needs one: the handle's, or {10} / {10, 1} built on `st` (a stream of the handle's when null).
 // With a corpus the set must hold byte 1.
 int lines_ensure(const Index *h, bool with_corpus, hipStream_t st) {
@@ -373,6 +335,8 @@ int lines_ensure(const Index *h, bool with_corpus, hipStream_t st) {
   if (!lease.c) return FMX_ERR_HIP;
   return lines_build(h, set, n_set, lease.c->stream);
 }
+
+namespace {
 
 hipError_t lookup_enqueue(const Index *h, const void *d_pos, uint64_t k, void *d_line, void *d_start, void *d_end, hipStream_t st) {
   if (!k) return hipSuccess;

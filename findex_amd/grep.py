@@ -2,6 +2,7 @@
 
     python -m findex_amd.grep BASE REGEX [REGEX ..] [--mode all|longest|disjoint] [--max-per N] [--max-steps N] [-C BYTES] [--count]
                                                     [-n] [-A N] [-B N] [--context-lines N] [-c] [-l] [--max-line BYTES]
+                                                    [-v] [--and REGEX ..] [--not REGEX ..] [--near N | --same-file]
 
 BASE names BASE.bwt / BASE.aux / BASE.docs as `python -m findex_amd.index --dir D --out BASE` writes them.  One line per
 match, `name:raw_off:text`, regex by regex in (file, offset) order; -C BYTES shows that many bytes of the file around the
@@ -12,11 +13,25 @@ By lines (HipCorpusSearcher.grep_lines; any of the flags below): -n prints `name
 line, regex by regex in (file, line) order; -A N / -B N / --context-lines N add that many lines after / before / around, as
 `name-line_no-line`, with grep's `--` between groups that do not touch; -c prints `name:count` per file with matching lines,
 -l the names of those files.  A line longer than --max-line BYTES is cut to that many bytes around its first match.
+
+Line queries (HipCorpusSearcher.grep_lines_where, evaluated on the device; each implies output by lines and combines with the
+flags above): every REGEX is one query's anchor; --and X / --not X (repeatable) keep the anchor's lines that also hold / do not
+hold X -- on the same line, within --near N lines, or anywhere in the file with --same-file; -v prints the lines on which no
+match of REGEX begins.  A line holds a regex when a match BEGINS on it (use --mode all or longest for grep's strict sense of -v
+where matches run over line breaks).
 """
 import argparse
 import sys
 
 import numpy as np
+
+
+def line_count(s):
+    """argparse type of --near: a number of lines, 0 or more."""
+    v = int(s)
+    if not 0 <= v < 2 ** 32:
+        raise argparse.ArgumentTypeError("a number of lines, 0 .. 2^32 - 1")
+    return v
 
 
 def parser():
@@ -35,6 +50,12 @@ def parser():
     ap.add_argument("-c", "--count-lines", action="store_true", help="matching lines per file")
     ap.add_argument("-l", "--files-with-matches", action="store_true", help="the files with a matching line")
     ap.add_argument("--max-line", type=int, default=4096, metavar="BYTES", help="longer lines are cut around their first match")
+    ap.add_argument("-v", "--invert-match", action="store_true", help="the lines on which no match begins")
+    ap.add_argument("--and", dest="and_", action="append", default=[], metavar="REGEX", help="only lines that also hold REGEX (repeatable)")
+    ap.add_argument("--not", dest="not_", action="append", default=[], metavar="REGEX", help="only lines that do not hold REGEX (repeatable)")
+    near = ap.add_mutually_exclusive_group()
+    near.add_argument("--near", type=line_count, default=None, metavar="N", help="--and / --not look N lines to either side (default 0: the same line)")
+    near.add_argument("--same-file", action="store_true", help="--and / --not look at the whole file")
     ap.add_argument("--little-endian", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     return ap
@@ -56,7 +77,23 @@ def with_context(cs, occ, context):
 def by_lines(a):
     """Do the arguments ask for output by lines?"""
     return bool(a.line_number or a.count_lines or a.files_with_matches or a.after is not None or a.before is not None
-                or a.context_lines is not None)
+                or a.context_lines is not None or where(a))
+
+
+def where(a):
+    """Do the arguments ask for a line query (-v, --and, --not, --near, --same-file)?"""
+    return bool(a.invert_match or a.and_ or a.not_ or a.near is not None or a.same_file)
+
+
+def queries_of(a):
+    """The line queries of the arguments, as HipCorpusSearcher.grep_lines_where takes them: one per positional regex, which
+    is the query's anchor -- or, with -v, a negative term on the same line under the anchor "all lines"; every --and / --not
+    adds a positive / negative term with the window of --near N (default 0) or --same-file to every query."""
+    window = "file" if a.same_file else (a.near or 0)
+    extra = [(r, window, False) for r in a.and_] + [(r, window, True) for r in a.not_]
+    if a.invert_match:
+        return [(None, [(r, 0, True)] + extra) for r in a.regex]
+    return [(r, list(extra)) for r in a.regex]
 
 
 def context_of(a):
@@ -104,15 +141,20 @@ def format_files(names, hits):
 def main_lines(cs, a, out):
     before, after = context_of(a)
     names = cs.corpus.names
+    if where(a):
+        queries = queries_of(a)
+        grep_lines = lambda _regexes, **kw: cs.grep_lines_where(queries, **kw)
+    else:
+        grep_lines = cs.grep_lines
     if a.count_lines or a.files_with_matches:
-        off, hits, truncated = cs.grep_lines(a.regex, mode=a.mode, max_steps=a.max_steps, max_per=a.max_per)
+        off, hits, truncated = grep_lines(a.regex, mode=a.mode, max_steps=a.max_steps, max_per=a.max_per)
         fmt = format_counts if a.count_lines else format_files
         for i in range(len(a.regex)):
             for row in fmt(names, hits[int(off[i]):int(off[i + 1])]):
                 out.write(row + b"\n")
         return truncated
-    res = cs.grep_lines(a.regex, mode=a.mode, max_steps=a.max_steps, max_per=a.max_per, text=True, before=before, after=after,
-                        max_line=a.max_line)
+    res = grep_lines(a.regex, mode=a.mode, max_steps=a.max_steps, max_per=a.max_per, text=True, before=before, after=after,
+                     max_line=a.max_line)
     off, hits, truncated, lines = res[:4]
     for i in range(len(a.regex)):
         lo, hi = int(off[i]), int(off[i + 1])

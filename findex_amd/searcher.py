@@ -699,6 +699,65 @@ class HipFMSearcher:
         _lib.check(self._L.fmx_lines_last(*[ctypes.byref(x) for x in t]))
         return tuple(float(x.value) for x in t)
 
+    # ---- line queries: all-of, none-of, near and inverted matches over line-hit lists (fmx_line_query, DESIGN.md 24)
+    ALL_LINES = None                # the anchor "every real line of the text"
+    LINE_TERM = np.dtype([("group", "<u4"), ("window", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+
+    @classmethod
+    def _line_queries(cls, queries):
+        """[(anchor, [(group, window, negate), ..]), ..] -> (q_off, anchor, terms) as fmx_line_query takes them."""
+        queries = list(queries)
+        q_off = np.zeros(len(queries) + 1, dtype=np.uint64)
+        anchor = np.zeros(len(queries), dtype=np.uint32)
+        rows = []
+        for i, (a, terms) in enumerate(queries):
+            if a is not None and not 0 <= int(a) < _lib.FMX_LQ_ALL_LINES:
+                raise ValueError("anchor: a group number, or None for all lines")
+            anchor[i] = _lib.FMX_LQ_ALL_LINES if a is None else int(a)
+            for g, w, neg in terms:
+                w = _lib.FMX_LQ_ALL_LINES if isinstance(w, str) and w == "file" else int(w)
+                if not (0 <= int(g) < 2 ** 32 and 0 <= w < 2 ** 32):
+                    raise ValueError("term: (group, window, negate), window an int below 2^32 or 'file'")
+                rows.append((int(g), w, _lib.FMX_LQ_NOT if neg else 0, 0))
+            q_off[i + 1] = len(rows)
+        return q_off, anchor, np.array(rows, dtype=cls.LINE_TERM).reshape(-1)
+
+    def line_query(self, off, hits, queries, corpus=None, cap=None):
+        """fmx_line_query: (off, hits) as occurrence_lines returns them, queries = [(anchor, terms), ..] -> (out_off[n_queries
+        + 1], records): query q's lines are records[out_off[q]:out_off[q + 1]], a LINE_HIT array with group == q.  anchor: a
+        group number, or None (ALL_LINES) for every real line of the text; terms: [(group, window, negate), ..], window an
+        int (lines on either side, 0 = the same line) or "file" (anywhere in the same document).  The result is the anchor's
+        records that satisfy every term, in order.  cap=None: a counting call sizes the buffer."""
+        off = np.ascontiguousarray(off, dtype=np.uint64).reshape(-1)
+        hits = np.ascontiguousarray(hits, dtype=self.LINE_HIT).reshape(-1)
+        if off.size < 2 or int(off[-1]) > hits.size:
+            raise ValueError("off: n_groups + 1 offsets into hits")
+        q_off, anchor, terms = self._line_queries(queries)
+        args = (self._h, corpus.handle if corpus is not None else None, _ptr(off), _ptr(hits) if hits.size else None, off.size - 1,
+                _ptr(q_off), _ptr(anchor) if anchor.size else None, _ptr(terms) if terms.size else None, anchor.size)
+        return self._csr_hits(self._L.fmx_line_query, args, anchor.size, self.LINE_HIT, cap)
+
+    def line_query_dev(self, d_hit_off, d_hits, n_hits, n_groups, queries, d_out_off, d_out, cap, corpus=None, stream=0, grow=False):
+        """fmx_line_query_dev: device pointers (u64 offsets, 48-byte line hits in and out), the queries from the host;
+        allocates and synchronises.  -> the exact number of records; cap = 0 is the counting call, grow as occurrences_dev."""
+        q_off, anchor, terms = self._line_queries(queries)
+        n_out = ctypes.c_size_t()
+        rc = self._L.fmx_line_query_dev(self._h, corpus.handle if corpus is not None else None, _dp(d_hit_off), _dp(d_hits), int(n_hits),
+                                        int(n_groups), _ptr(q_off), _ptr(anchor) if anchor.size else None,
+                                        _ptr(terms) if terms.size else None, anchor.size, _dp(d_out_off), _dp(d_out), int(cap),
+                                        ctypes.byref(n_out), _dp(stream))
+        if not (rc == _lib.FMX_ERR_OVERFLOW and (int(cap) == 0 or grow)):
+            _lib.check(rc)
+        return int(n_out.value)
+
+    def line_query_last(self):
+        """fmx_line_query_last: (key packing ms, flags ms, scan + emit + offsets ms, candidates, keys probed) of this thread's
+        last line query."""
+        t = [ctypes.c_double() for _ in range(3)]
+        n = [ctypes.c_uint64() for _ in range(2)]
+        _lib.check(self._L.fmx_line_query_last(*[ctypes.byref(x) for x in t + n]))
+        return tuple(float(x.value) for x in t) + tuple(int(x.value) for x in n)
+
     # ---- matching statistics and maximal exact matches (fmx_match_stats_batch, fmx_mems_batch, DESIGN.md 16)
     MEM_HIT =np.dtype([("pattern", np.uint32), ("len", np.uint32), ("end", np.uint64), ("sp", np.uint64), ("ep", np.uint64)])
 

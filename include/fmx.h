@@ -1181,6 +1181,72 @@ int fmx_occurrence_lines_dev(const fmx_index *idx, const fmx_corpus *corpus_or_n
                              void *stream);
 int fmx_lines_last(double *locate_ms, double *sort_ms, double *lookup_ms, double *compact_ms);
 
+/* ---- line queries: all-of, none-of, near and inverted matches over line-hit lists, evaluated on the device.  Beyond the
+ * reference.  DESIGN.md 24.
+ * INPUT.  hit_off[n_groups + 1] and hits[] are exactly what fmx_occurrence_lines leaves: CSR over groups, the records of a
+ * group ascending by line.  The KEY of a record is (doc, line_no), compared as the 64-bit value doc << 32 | line_no (line_no <
+ * 2^32 because n < 2^32; without a corpus doc is UINT32_MAX in every record, so the key orders by line_no alone).  Within a
+ * group the keys are strictly ascending.
+ * A TERM is (group, window, flags).  A line X with key (d, i) SATISFIES a positive term if group `group` holds a record (d, j)
+ * with max(1, i - window) <= j <= i + window; the upper end saturates, so a window of UINT32_MAX means "anywhere in the same
+ * document" (without a corpus: anywhere in the text).  window == 0 means the same line.  A term with FMX_LQ_NOT set is
+ * satisfied when no such record exists.  A window never reaches into another document, because the document is part of the
+ * key.
+ * A QUERY is an ANCHOR and a list of terms.  The anchor is a group number, or FMX_LQ_ALL_LINES (UINT32_MAX).  The query's
+ * CANDIDATES are the anchor group's records, in order; for FMX_LQ_ALL_LINES they are the REAL LINES of the text, in order.  A
+ * global line L of the line table (0 <= L <= n_brk) is real unless it is the empty piece behind a final break: without a
+ * corpus L is not real if start(L) == n - 1; with a corpus L is not real if start(L) is the position of a document's
+ * separator (start(L) == doc_start[d + 1] - 1).  An empty file therefore has no lines, a file that ends in "\n" has as many
+ * lines as `wc -l` says, and an unterminated last line counts.  The query's RESULT is the candidates that satisfy every term,
+ * in candidate order; a query without terms returns its candidates.
+ * OUTPUT is CSR over QUERIES: out_off[n_queries + 1], out_off[n_queries] == *n_out, and fmx_line_hit records.  An output
+ * record is the candidate's record with `group` set to the query's index.  For an FMX_LQ_ALL_LINES candidate the record is
+ * built from the line table (and the corpus map when given): doc, line_no, start, len, raw_off and raw_len exactly as
+ * fmx_occurrence_lines fills them for a hit on that line, n_hits = 0 and first = UINT32_MAX.  The same input gives the same
+ * bytes on every run: no atomics decide an order.
+ * `grep -v A` is the query (FMX_LQ_ALL_LINES, [(A, 0, FMX_LQ_NOT)]).  The algebra is over the hit lists it is given: a line
+ * "holds a match" when a match BEGINS on it, and in mode `disjoint` a match that runs over a line break can hide a later one;
+ * a caller who wants -v in grep's strict sense asks for the lists with lineOnly, or in mode `all` / `longest`.
+ * q_off[n_queries + 1] is CSR over `terms`; q_off, anchor and terms are HOST memory in both forms (the call uploads them).
+ * Capacity as fmx_occurrence_lines: more than cap results -> FMX_ERR_OVERFLOW with the EXACT total in *n_out, nothing written
+ * past out[cap - 1]; cap == 0 with out == NULL is the counting call.
+ * FMX_ERR_ARG, decided before the device is touched: null hit_off / out_off / n_out / q_off / anchor; terms null while there
+ * are some; n_groups == 0 or > 2^26; n_queries == 0 or > 2^16; more than 64 terms in one query; q_off not non-decreasing from
+ * 0; an anchor or term group >= n_groups (the anchor may be FMX_LQ_ALL_LINES); flags & ~1 or reserved != 0; cap >= 2^32;
+ * n_hits > 2^26; a null handle (refused last); a corpus whose stream length != n - 1; in the host form also hit_off not
+ * non-decreasing from 0, or keys not strictly ascending inside a group.  The device form cannot see the records: it downloads
+ * hit_off (which must begin at 0, be non-decreasing and end at n_hits), its key kernel raises a flag for a group whose keys
+ * do not ascend, and the call returns FMX_ERR_ARG after the launch with nothing reported.  No record value leads outside the
+ * inputs, the table or the outputs.  The candidates of all queries together must be < 2^32, otherwise FMX_ERR_OVERFLOW with a
+ * message, known on the host before anything candidate-sized is allocated.
+ * Both forms ALLOCATE AND SYNCHRONISE (FMX_ERR_HIP under a stream capture, decided before anything is allocated, the capture
+ * left valid) and free every temporary on every path; the need -- 8 bytes per hit, 4 per candidate, the scan's block totals,
+ * the query tables -- is checked against the free HBM first (FMX_ERR_NOMEM).  Only a query with FMX_LQ_ALL_LINES needs the
+ * line table: such a call builds one when absent, with fmx_occurrence_lines's rules ({10} without a corpus, {10, 1} with one;
+ * a table that lacks byte 1 combined with a corpus is FMX_ERR_ARG; locate's refusals pass through, so an fmx_open_block
+ * handle is FMX_ERR_UNSUPPORTED).  A call without such a query builds no table and changes none.
+ * The process-wide key "lq_narrow" (fmx_config_set: on | off, default off: the plain per-lane search measured
+ * faster) selects whether a wave whose candidates belong to
+ * one query narrows each term's key range by the bounds of its first and last candidate before every lane searches.
+ * fmx_line_query_last: the calling thread's last call: device ms of the key packing, of the flags and of scan + emit +
+ * offsets, the candidates and the keys probed; any pointer may be NULL. */
+#define FMX_LQ_ALL_LINES 0xffffffffu
+#define FMX_LQ_NOT 1u
+typedef struct fmx_line_term {
+  uint32_t group;
+  uint32_t window; /* lines on either side; 0: the same line; UINT32_MAX: the same document */
+  uint32_t flags;  /* FMX_LQ_NOT */
+  uint32_t reserved;
+} fmx_line_term;    /* 16 bytes */
+int fmx_line_query(const fmx_index *idx, const fmx_corpus *corpus_or_null, const uint64_t *hit_off /* n_groups + 1 */,
+                   const fmx_line_hit *hits, size_t n_groups, const uint64_t *q_off /* n_queries + 1 */,
+                   const uint32_t *anchor /* n_queries */, const fmx_line_term *terms, size_t n_queries,
+                   uint64_t *out_off /* n_queries + 1 */, fmx_line_hit *out, size_t cap, size_t *n_out);
+int fmx_line_query_dev(const fmx_index *idx, const fmx_corpus *corpus_or_null, const void *d_hit_off, const void *d_hits,
+                       size_t n_hits, size_t n_groups, const uint64_t *q_off, const uint32_t *anchor, const fmx_line_term *terms,
+                       size_t n_queries, void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream);
+int fmx_line_query_last(double *keys_ms, double *flags_ms, double *emit_ms, uint64_t *candidates, uint64_t *probes);
+
 /* One process, several GPUs (the single-process form of SURVEY.md 8e for regexes; one process per GPU uses
  * findex_amd/distributed.py and an RCCL gather instead): the batch is cut into contiguous slices of about equal
  * estimated frontier work (start elements, states and follow entries of each regex), slice r is made resident on
