@@ -56,21 +56,35 @@ int use_device_index(int device) {
   return FMX_OK;
 }
 
-int not_capturing(hipStream_t st, const char *what) {
+int no_capture(hipStream_t st, const char *text) {
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   HIP_TRY(hipStreamIsCapturing(st, &cs), "hipStreamIsCapturing");
   if (cs != hipStreamCaptureStatusNone) {
-    g_err = std::string(what) + " allocates and synchronises: not under a stream capture";
+    g_err = text;
     return FMX_ERR_HIP;
   }
   return FMX_OK;
 }
 
-// What a handle builds at first use (the locate samples, the LCP array) is built here when a call finds none.
-int ensure_built(const Index *h, std::mutex &mu, const bool &flag, int (*prepare)(const Index *, hipStream_t), hipStream_t st) {
+int not_capturing(hipStream_t st, const char *what) {
+  return no_capture(st, (std::string(what) + " allocates and synchronises: not under a stream capture").c_str());
+}
+
+int device_room(uint64_t need, const std::string &what, const char *verb) {
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
+  if (need > free_b) {
+    g_err = what + " " + verb + " " + std::to_string(need) + " bytes of device memory, " + std::to_string(free_b) + " are free";
+    return FMX_ERR_NOMEM;
+  }
+  return FMX_OK;
+}
+
+// What a handle builds at first use (the locate samples, the LCP array, ..) is built here when a call finds none.
+int ensure_built(const Index *h, Side &side, int (*prepare)(const Index *, hipStream_t), hipStream_t st) {
   {
-    std::lock_guard<std::mutex> lk(mu);
-    if (flag) return FMX_OK;
+    std::lock_guard<std::mutex> lk(side.mu);
+    if (side.ready) return FMX_OK;
   }
   if (st) return prepare(h, st);
   CtxLease lease(h);
@@ -283,10 +297,39 @@ Worker *worker_of(const Index *h) {
   return h->worker.get();
 }
 
+// What a handle derives outside the table budget, by its fmx_prepare / fmx_drop_tables flag.  In this order: the extract
+// samples take a short cut through locate samples at the same rate, and the line table's build reads the locate samples.
+static const struct DerivedFlag {
+  unsigned flag;
+  int (*check)(const Index *);
+  int (*prepare)(const Index *, hipStream_t);
+  void (*drop)(Index *);
+} kDerived[] = {
+    {FMX_PREPARE_LOCATE, locate_check, locate_prepare, [](Index *h) { h->loc.drop(); }},
+    {FMX_PREPARE_LCP, lcp_check, lcp_prepare, [](Index *h) { h->lcp.drop(); }},
+    {FMX_PREPARE_EXTRACT, extract_check, extract_prepare, [](Index *h) { h->ext.drop(); }},
+    {FMX_PREPARE_LINES, lines_check, lines_prepare, [](Index *h) { h->lin.drop(); }},
+};
+static unsigned derived_flags() {
+  unsigned all = 0;
+  for (const DerivedFlag &d : kDerived) all |= d.flag;
+  return all;
+}
+static constexpr unsigned kDroppableTables = FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER;      // those of the budget
+
+// fmx_drop_tables and fmx_close: the budgeted tables (fmx_jump.hip), then the rest by the table above
+static int drop_derived(Index *h, unsigned what) {
+  const int rc = drop_tables(h, what & kDroppableTables);
+  for (const DerivedFlag &d : kDerived)
+    if (what & d.flag) d.drop(h);
+  return rc;
+}
+
 static void destroy(Index *h) {
   if (!h) return;
   h->worker.reset();                  // finishes what was submitted, joins
   (void)hipSetDevice(h->device);
+  (void)drop_derived(h, kDroppableTables | derived_flags());
   if (h->d_bv) (void)hipFree(h->d_bv);
   if (h->d_chk) (void)hipFree(h->d_chk);
   if (h->d_sup) (void)hipFree(h->d_sup);
@@ -294,23 +337,9 @@ static void destroy(Index *h) {
   if (h->d_cf) (void)hipFree(h->d_cf);
   if (h->d_slot) (void)hipFree(h->d_slot);
   if (h->d_counters) (void)hipFree(h->d_counters);
-  if (h->d_ktab) (void)hipFree(h->d_ktab);
-  if (h->d_kt_dense) (void)hipFree(h->d_kt_dense);
-  if (h->d_kt_levels) (void)hipFree(h->d_kt_levels);
-  if (h->d_kt_ext) (void)hipFree(h->d_kt_ext);
-  if (h->d_kt_ovf) (void)hipFree(h->d_kt_ovf);
-  if (h->d_jump) (void)hipFree(h->d_jump);
-  if (h->d_row1) (void)hipFree(h->d_row1);
-  if (h->d_row3) (void)hipFree(h->d_row3);
   if (h->d_sel_dir) (void)hipFree(h->d_sel_dir);
   if (h->d_sel_off) (void)hipFree(h->d_sel_off);
   if (h->d_sel_shift) (void)hipFree(h->d_sel_shift);
-  if (h->d_loc_marks) (void)hipFree(h->d_loc_marks);
-  if (h->d_loc_samples) (void)hipFree(h->d_loc_samples);
-  if (h->d_lcp) (void)hipFree(h->d_lcp);
-  if (h->d_ext_isa) (void)hipFree(h->d_ext_isa);
-  if (h->d_lin_brk) (void)hipFree(h->d_lin_brk);
-  if (h->d_lin_dir) (void)hipFree(h->d_lin_dir);
   for (CallCtx *c : h->ctx_pool) free_ctx(c);
   delete h;
 }
@@ -643,26 +672,12 @@ int fmx_open_block(const uint8_t *bwt, uint64_t n, const int64_t bucket_starts[2
 
 int fmx_prepare(const fmx_index *idx, unsigned what) {
   if (!idx) return arg_fail("null argument");
-  if (what & ~(unsigned)(FMX_PREPARE_KTAB | FMX_PREPARE_SELECT | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_SEARCH | FMX_PREPARE_LOCATE | FMX_PREPARE_LCP | FMX_PREPARE_EXTRACT | FMX_PREPARE_LINES)) return arg_fail("unknown fmx_prepare flag");
+  if (what & ~(kDroppableTables | FMX_PREPARE_SELECT | FMX_PREPARE_SEARCH | derived_flags())) return arg_fail("unknown fmx_prepare flag");
   const Index *h = H(idx);
-  if (what & FMX_PREPARE_LOCATE) {
-    const int lc = locate_check(h);
-    if (lc) return lc;
-  }
-  if (what & FMX_PREPARE_LCP) {
-    const int lc = lcp_check(h);
-    if (lc) return lc;
-  }
-  if (what & FMX_PREPARE_EXTRACT) {
-    const int lc = extract_check(h);
-    if (lc) return lc;
-  }
-  if (what & FMX_PREPARE_LINES) {
-    const int lc = lines_check(h);
-    if (lc) return lc;
-  }
-  int rc = use_device(h);
-  if (rc) return rc;
+  int rc;
+  for (const DerivedFlag &d : kDerived)
+    if ((what & d.flag) && (rc = d.check(h))) return rc;
+  if ((rc = use_device(h))) return rc;
   CtxLease lease(h);
   if (!lease.c) return FMX_ERR_HIP;
   if (what & FMX_PREPARE_KTAB) {
@@ -682,22 +697,8 @@ int fmx_prepare(const fmx_index *idx, unsigned what) {
     const unsigned long long *r1 = nullptr;
     HIP_TRY(row1_get(h, lease.c->stream, &r1), "row table");
   }
-  if (what & FMX_PREPARE_LOCATE) {
-    rc = locate_prepare(h, lease.c->stream);
-    if (rc) return rc;
-  }
-  if (what & FMX_PREPARE_LCP) {
-    rc = lcp_prepare(h, lease.c->stream);
-    if (rc) return rc;
-  }
-  if (what & FMX_PREPARE_EXTRACT) {                               // after LOCATE: samples at the same rate are its short cut
-    rc = extract_prepare(h, lease.c->stream);
-    if (rc) return rc;
-  }
-  if (what & FMX_PREPARE_LINES) {                                 // after LOCATE: its build reads the samples
-    rc = lines_prepare(h, lease.c->stream);
-    if (rc) return rc;
-  }
+  for (const DerivedFlag &d : kDerived)
+    if ((what & d.flag) && (rc = d.prepare(h, lease.c->stream))) return rc;
   // the literal search kernel this handle's tables select, calibrated here (its residency census: fmx_search.hip) so that no
   // _dev call ever has to read anything back
   if (what & (FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_SEARCH)) HIP_TRY(search_calibrate(h, lease.c->stream), "search calibration");
@@ -715,12 +716,12 @@ int fmx_prepare_ex(fmx_index *idx, unsigned what, uint64_t budget_bytes) {
 
 int fmx_drop_tables(fmx_index *idx, unsigned what) {
   if (!idx) return arg_fail("null argument");
-  if (!what || (what & ~(unsigned)(FMX_PREPARE_KTAB | FMX_PREPARE_JUMP | FMX_PREPARE_FRONTIER | FMX_PREPARE_LOCATE | FMX_PREPARE_LCP | FMX_PREPARE_EXTRACT | FMX_PREPARE_LINES))) return arg_fail("fmx_drop_tables frees the k-mer table, the row tables, the locate samples, the LCP array, the extract samples and the line table (FMX_PREPARE_KTAB, FMX_PREPARE_JUMP, FMX_PREPARE_FRONTIER, FMX_PREPARE_LOCATE, FMX_PREPARE_LCP, FMX_PREPARE_EXTRACT, FMX_PREPARE_LINES)");
+  if (!what || (what & ~(kDroppableTables | derived_flags()))) return arg_fail("fmx_drop_tables frees the k-mer table, the row tables, the locate samples, the LCP array, the extract samples and the line table (FMX_PREPARE_KTAB, FMX_PREPARE_JUMP, FMX_PREPARE_FRONTIER, FMX_PREPARE_LOCATE, FMX_PREPARE_LCP, FMX_PREPARE_EXTRACT, FMX_PREPARE_LINES)");
   Index *h = H(idx);
   int rc = use_device(h);
   if (rc) return rc;
   HIP_TRY(hipDeviceSynchronize(), "hipDeviceSynchronize");
-  return drop_tables(h, what);
+  return drop_derived(h, what);
 }
 
 int fmx_close(fmx_index *idx) {
@@ -1311,7 +1312,7 @@ int fmx_locate_batch(const fmx_index *idx, const uint64_t *rows, size_t k, uint6
   for (size_t q = 0; q < k; q++)
     if (rows[q] >= h->n) return arg_fail("row out of range (reference: SALoader reads past X.sa)");
   if ((rc = use_device(h)) || !k) return rc;
-  if ((rc = ensure_built(h, h->loc_mu, h->loc_ready, locate_prepare, nullptr))) return rc;
+  if ((rc = ensure_built(h, h->loc, locate_prepare, nullptr))) return rc;
   const HostIn ins[] = {{rows, k * 8}};
   const HostOut outs[] = {{out_pos, k * 8}};
   return run_io(h, ins, 1, outs, 1, [&](hipStream_t st, const void *const *di, void *const *dout) {
@@ -1325,7 +1326,7 @@ int fmx_locate_batch_dev(const fmx_index *idx, const void *d_rows, size_t k, voi
   int rc = locate_check(h);
   if (rc) return rc;
   if ((rc = use_device(h)) || !k) return rc;
-  if ((rc = ensure_built(h, h->loc_mu, h->loc_ready, locate_prepare, (hipStream_t)stream))) return rc;
+  if ((rc = ensure_built(h, h->loc, locate_prepare, (hipStream_t)stream))) return rc;
   HIP_TRY(launch_locate(h, d_rows, k, d_out_pos, (hipStream_t)stream), "k_locate");
   return FMX_OK;
 }
@@ -1363,7 +1364,7 @@ int fmx_locate_intervals_dev(const fmx_index *idx, const void *d_sp, const void 
   int rc = locate_check(h);
   if (rc) return rc;
   if ((rc = use_device(h))) return rc;
-  if ((rc = ensure_built(h, h->loc_mu, h->loc_ready, locate_prepare, (hipStream_t)stream))) return rc;
+  if ((rc = ensure_built(h, h->loc, locate_prepare, (hipStream_t)stream))) return rc;
   HIP_TRY(launch_locate_intervals(h, d_sp, d_ep, k, max_per, d_out_off, d_out_pos, cap, (hipStream_t)stream), "k_locate");
   return FMX_OK;
 }
@@ -1371,10 +1372,10 @@ int fmx_locate_intervals_dev(const fmx_index *idx, const void *d_sp, const void 
 int fmx_locate_info(const fmx_index *idx, uint32_t *rate, uint64_t *bytes, double *build_ms) {
   if (!idx) return arg_fail("null argument");
   const Index *h = H(idx);
-  std::lock_guard<std::mutex> lk(h->loc_mu);
-  if (rate) *rate = h->loc_ready ? h->loc_rate : (uint32_t)h->policy.locate_sample.load(std::memory_order_relaxed);
-  if (bytes) *bytes = h->loc_ready ? h->loc_bytes : 0;
-  if (build_ms) *build_ms = h->loc_ready ? h->loc_build_ms : 0.0;
+  std::lock_guard<std::mutex> lk(h->loc.mu);
+  if (rate) *rate = h->loc.ready ? h->loc.rate : (uint32_t)h->policy.locate_sample.load(std::memory_order_relaxed);
+  if (bytes) *bytes = h->loc.ready ? h->loc.bytes : 0;
+  if (build_ms) *build_ms = h->loc.ready ? h->loc.build_ms : 0.0;
   return FMX_OK;
 }
 
@@ -1388,14 +1389,7 @@ int fmx_write_sa(const fmx_index *idx, const char *path) {
   FILE *f = std::fopen(path, "wb");
   if (!f) { g_err = std::string("cannot create ") + path; return FMX_ERR_IO; }
   std::unique_ptr<FILE, int (*)(FILE *)> guard(f, std::fclose);
-  if ((rc = use_device(h))) return rc;
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
-  const uint64_t need = locate_write_sa_bytes(h);
-  if (need > free_b) {
-    g_err = "fmx_write_sa needs " + std::to_string(need) + " bytes of device memory, " + std::to_string((unsigned long long)free_b) + " are free";
-    return FMX_ERR_NOMEM;
-  }
+  if ((rc = use_device(h)) || (rc = device_room(locate_write_sa_bytes(h), "fmx_write_sa"))) return rc;
   DevMem mem;
   void *d_sa = nullptr;
   HIP_TRY(mem.get(&d_sa, h->n * 4), "hipMalloc(sa)");
@@ -1423,7 +1417,7 @@ int fmx_lcp_batch(const fmx_index *idx, const uint64_t *rows, size_t k, uint32_t
   for (size_t q = 0; q < k; q++)
     if (rows[q] >= h->n) return arg_fail("row out of range (reference: LCPLoader reads past X.lcp)");
   if ((rc = use_device(h)) || !k) return rc;
-  if ((rc = ensure_built(h, h->lcp_mu, h->lcp_ready, lcp_prepare, nullptr))) return rc;
+  if ((rc = ensure_built(h, h->lcp, lcp_prepare, nullptr))) return rc;
   const HostIn ins[] = {{rows, k * 8}};
   const HostOut outs[] = {{out, k * 4}};
   return run_io(h, ins, 1, outs, 1, [&](hipStream_t st, const void *const *di, void *const *dout) {
@@ -1437,7 +1431,7 @@ int fmx_lcp_batch_dev(const fmx_index *idx, const void *d_rows, size_t k, void *
   int rc = lcp_check(h);
   if (rc) return rc;
   if ((rc = use_device(h)) || !k) return rc;
-  if ((rc = ensure_built(h, h->lcp_mu, h->lcp_ready, lcp_prepare, (hipStream_t)stream))) return rc;
+  if ((rc = ensure_built(h, h->lcp, lcp_prepare, (hipStream_t)stream))) return rc;
   HIP_TRY(launch_lcp_gather(h, d_rows, k, d_out, (hipStream_t)stream), "k_lcp_rows");
   return FMX_OK;
 }
@@ -1456,8 +1450,8 @@ int fmx_lcp_range(const fmx_index *idx, uint64_t first, uint64_t count, uint32_t
   if (rc) return rc;
   const Index *h = H(idx);
   if ((rc = use_device(h)) || !count) return rc;
-  if ((rc = ensure_built(h, h->lcp_mu, h->lcp_ready, lcp_prepare, nullptr))) return rc;
-  HIP_TRY(hipMemcpy(out, static_cast<const uint32_t *>(h->d_lcp) + first, count * 4, hipMemcpyDeviceToHost), "D2H(lcp)");
+  if ((rc = ensure_built(h, h->lcp, lcp_prepare, nullptr))) return rc;
+  HIP_TRY(hipMemcpy(out, static_cast<const uint32_t *>(h->lcp.lcp) + first, count * 4, hipMemcpyDeviceToHost), "D2H(lcp)");
   return FMX_OK;
 }
 
@@ -1466,8 +1460,8 @@ int fmx_lcp_range_dev(const fmx_index *idx, uint64_t first, uint64_t count, void
   if (rc) return rc;
   const Index *h = H(idx);
   if ((rc = use_device(h)) || !count) return rc;
-  if ((rc = ensure_built(h, h->lcp_mu, h->lcp_ready, lcp_prepare, (hipStream_t)stream))) return rc;
-  HIP_TRY(hipMemcpyAsync(d_out, static_cast<const uint32_t *>(h->d_lcp) + first, count * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream),
+  if ((rc = ensure_built(h, h->lcp, lcp_prepare, (hipStream_t)stream))) return rc;
+  HIP_TRY(hipMemcpyAsync(d_out, static_cast<const uint32_t *>(h->lcp.lcp) + first, count * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream),
           "D2D(lcp)");
   return FMX_OK;
 }
@@ -1475,12 +1469,12 @@ int fmx_lcp_range_dev(const fmx_index *idx, uint64_t first, uint64_t count, void
 int fmx_lcp_info(const fmx_index *idx, uint64_t *bytes, double *build_ms, uint32_t *max_lcp, uint64_t *max_row, uint64_t *sum_lcp) {
   if (!idx) return arg_fail("null argument");
   const Index *h = H(idx);
-  std::lock_guard<std::mutex> lk(h->lcp_mu);
-  if (bytes) *bytes = h->lcp_ready ? h->lcp_bytes : 0;
-  if (build_ms) *build_ms = h->lcp_ready ? h->lcp_build_ms : 0.0;
-  if (max_lcp) *max_lcp = h->lcp_ready ? h->lcp_max : 0;
-  if (max_row) *max_row = h->lcp_ready ? h->lcp_max_row : 0;
-  if (sum_lcp) *sum_lcp = h->lcp_ready ? h->lcp_sum : 0;
+  std::lock_guard<std::mutex> lk(h->lcp.mu);
+  if (bytes) *bytes = h->lcp.ready ? h->lcp.bytes : 0;
+  if (build_ms) *build_ms = h->lcp.ready ? h->lcp.build_ms : 0.0;
+  if (max_lcp) *max_lcp = h->lcp.ready ? h->lcp.max : 0;
+  if (max_row) *max_row = h->lcp.ready ? h->lcp.max_row : 0;
+  if (sum_lcp) *sum_lcp = h->lcp.ready ? h->lcp.sum : 0;
   return FMX_OK;
 }
 
@@ -1492,7 +1486,7 @@ int fmx_write_lcp(const fmx_index *idx, const char *path) {
   int rc = lcp_check(h);
   if (rc) return rc;
   if ((rc = use_device(h))) return rc;
-  if ((rc = ensure_built(h, h->lcp_mu, h->lcp_ready, lcp_prepare, nullptr))) return rc;
+  if ((rc = ensure_built(h, h->lcp, lcp_prepare, nullptr))) return rc;
   FILE *f = std::fopen(path, "wb");
   if (!f) { g_err = std::string("cannot create ") + path; return FMX_ERR_IO; }
   std::unique_ptr<FILE, int (*)(FILE *)> guard(f, std::fclose);
@@ -1500,7 +1494,7 @@ int fmx_write_lcp(const fmx_index *idx, const char *path) {
   std::vector<uint32_t> buf((size_t)std::min<uint64_t>(chunk, entries));
   for (uint64_t o = 0; o < entries; o += chunk) {
     const size_t len = (size_t)std::min<uint64_t>(chunk, entries - o);
-    HIP_TRY(hipMemcpy(buf.data(), static_cast<const uint32_t *>(h->d_lcp) + o, len * 4, hipMemcpyDeviceToHost), "D2H(lcp)");
+    HIP_TRY(hipMemcpy(buf.data(), static_cast<const uint32_t *>(h->lcp.lcp) + o, len * 4, hipMemcpyDeviceToHost), "D2H(lcp)");
     for (size_t i = 0; i < len; i++) buf[i] = __builtin_bswap32(buf[i]);
     if (std::fwrite(buf.data(), 4, len, f) != len) { g_err = "short write"; return FMX_ERR_IO; }
   }
@@ -1538,34 +1532,23 @@ static int text_to_device_bwt(const uint8_t *text, uint64_t len, int device, uin
   int rc = use_device_index(device);
   if (rc) return rc;
   const uint64_t n = len + 1;
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
-  const uint64_t need = sufsort_peak_bytes(len, false) + len + n;
-  if (need > free_b) {
-    g_err = "suffix sort of " + std::to_string(len) + " bytes needs " + std::to_string(need) + " bytes of device memory, " +
-            std::to_string((unsigned long long)free_b) + " are free";
-    return FMX_ERR_NOMEM;
-  }
-  struct Bufs {
-    void *text = nullptr, *bwt = nullptr;
-    ~Bufs() { if (text) (void)hipFree(text); if (bwt) (void)hipFree(bwt); }
-  } b;
+  if ((rc = device_room(sufsort_peak_bytes(len, false) + len + n, "suffix sort of " + std::to_string(len) + " bytes"))) return rc;
+  DevMem mem;
+  void *d_text = nullptr, *d_bwt = nullptr;
   StreamGuard own;
   HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
-  hipError_t e = hipMalloc(&b.text, len);
-  if (e == hipSuccess) e = hipMalloc(&b.bwt, n);
-  if (e != hipSuccess) { g_err = std::string("hipMalloc(text, bwt): ") + hipGetErrorString(e); return FMX_ERR_NOMEM; }
-  HIP_TRY(hipMemcpyAsync(b.text, text, len, hipMemcpyHostToDevice, own.s), "H2D(text)");
-  rc = sufsort_bwt(b.text, len, b.bwt, nullptr, eof, counts, own.s, 0);
+  DEV_ALLOC(mem, d_text, len, "text, bwt");
+  DEV_ALLOC(mem, d_bwt, n, "text, bwt");
+  HIP_TRY(hipMemcpyAsync(d_text, text, len, hipMemcpyHostToDevice, own.s), "H2D(text)");
+  rc = sufsort_bwt(d_text, len, d_bwt, nullptr, eof, counts, own.s, 0);
   if (rc) return rc;
-  (void)hipFree(b.text);
-  b.text = nullptr;
+  mem.free_now(d_text);               // before the handle's dictionary is built
   if (bwt_out) {
-    HIP_TRY(hipMemcpyAsync(bwt_out, b.bwt, n, hipMemcpyDeviceToHost, own.s), "D2H(bwt)");
+    HIP_TRY(hipMemcpyAsync(bwt_out, d_bwt, n, hipMemcpyDeviceToHost, own.s), "D2H(bwt)");
     HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
     return FMX_OK;
   }
-  return open_common(b.bwt, true, nullptr, n, *eof, counts, device, own.s, idx_out);
+  return open_common(d_bwt, true, nullptr, n, *eof, counts, device, own.s, idx_out);
 }
 
 int fmx_bwt_from_text(const uint8_t *text, uint64_t len, uint8_t *bwt, uint64_t *eof, int64_t counts[256], int device) {
@@ -1590,14 +1573,8 @@ int fmx_bwt_from_text_dev(const void *d_text, uint64_t len, void *d_bwt, void *d
 static int lcp_from_device_text(const void *d_text, uint64_t len, const void *d_sa, void *d_lcp, int device, hipStream_t st,
                                 uint64_t extra) {
   const uint64_t n = len + 1;
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
-  const uint64_t need = lcp_text_bytes(n) + lcp_core_bytes(n) + extra;
-  if (need > free_b) {
-    g_err = "the LCP array of " + std::to_string(len) + " bytes needs " + std::to_string(need) + " bytes of device memory, " +
-            std::to_string((unsigned long long)free_b) + " are free";
-    return FMX_ERR_NOMEM;
-  }
+  int rc = device_room(lcp_text_bytes(n) + lcp_core_bytes(n) + extra, "the LCP array of " + std::to_string(len) + " bytes");
+  if (rc) return rc;
   DevMem mem;
   uint8_t *s = nullptr;
   DEV_ALLOC(mem, s, lcp_text_bytes(n), "LCP");
@@ -1606,8 +1583,7 @@ static int lcp_from_device_text(const void *d_text, uint64_t len, const void *d_
   lcp_reverse_text(static_cast<const uint8_t *>(d_text), len, s, cus, st);
   HIP_TRY(hipGetLastError(), "k_lcp_reverse");
   LcpInfo info;
-  const int rc = lcp_core(s, n, static_cast<const uint32_t *>(d_sa), static_cast<uint32_t *>(d_lcp), cus, st,
-                          &info);
+  rc = lcp_core(s, n, static_cast<const uint32_t *>(d_sa), static_cast<uint32_t *>(d_lcp), cus, st, &info);
   if (rc) return rc;
   for (int i = 0; i < 3; i++) g_lcp_phases[i] = info.phase_ms[i];
   return FMX_OK;
@@ -1629,31 +1605,22 @@ int fmx_lcp_from_text(const uint8_t *text, uint64_t len, uint32_t *lcp, int devi
   if (rc) return rc;
   if ((rc = use_device_index(device))) return rc;
   const uint64_t n = len + 1;
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
   // the sort's temporaries are gone when the LCP's come; text, BWT / LCP (one buffer, 4 n) and the suffix array stay throughout
   const uint64_t need = len + 4 * n + 4 * n + std::max<uint64_t>(sufsort_peak_bytes(len, true), lcp_text_bytes(n) + lcp_core_bytes(n));
-  if (need > free_b) {
-    g_err = "suffix sort and LCP array of " + std::to_string(len) + " bytes need " + std::to_string(need) + " bytes of device memory, " +
-            std::to_string((unsigned long long)free_b) + " are free";
-    return FMX_ERR_NOMEM;
-  }
-  struct Bufs {
-    void *text = nullptr, *sa = nullptr, *out = nullptr;
-    ~Bufs() { if (text) (void)hipFree(text); if (sa) (void)hipFree(sa); if (out) (void)hipFree(out); }
-  } b;
+  if ((rc = device_room(need, "suffix sort and LCP array of " + std::to_string(len) + " bytes", "need"))) return rc;
+  DevMem mem;
+  void *d_text = nullptr, *d_sa = nullptr, *d_out = nullptr;
   StreamGuard own;
   HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
-  hipError_t e = hipMalloc(&b.text, len);
-  if (e == hipSuccess) e = hipMalloc(&b.sa, 4 * n);
-  if (e == hipSuccess) e = hipMalloc(&b.out, 4 * n);          // the BWT first (n bytes of it), then the LCP array
-  if (e != hipSuccess) { g_err = std::string("hipMalloc(text, sa, lcp): ") + hipGetErrorString(e); return FMX_ERR_NOMEM; }
-  HIP_TRY(hipMemcpyAsync(b.text, text, len, hipMemcpyHostToDevice, own.s), "H2D(text)");
+  DEV_ALLOC(mem, d_text, len, "text, sa, lcp");
+  DEV_ALLOC(mem, d_sa, 4 * n, "text, sa, lcp");
+  DEV_ALLOC(mem, d_out, 4 * n, "text, sa, lcp");              // the BWT first (n bytes of it), then the LCP array
+  HIP_TRY(hipMemcpyAsync(d_text, text, len, hipMemcpyHostToDevice, own.s), "H2D(text)");
   uint64_t eof = 0;
   int64_t counts[256];
-  if ((rc = sufsort_bwt(b.text, len, b.out, b.sa, &eof, counts, own.s, 0))) return rc;
-  if ((rc = lcp_from_device_text(b.text, len, b.sa, b.out, device, own.s, 0))) return rc;
-  HIP_TRY(hipMemcpyAsync(lcp, b.out, 4 * n, hipMemcpyDeviceToHost, own.s), "D2H(lcp)");
+  if ((rc = sufsort_bwt(d_text, len, d_out, d_sa, &eof, counts, own.s, 0))) return rc;
+  if ((rc = lcp_from_device_text(d_text, len, d_sa, d_out, device, own.s, 0))) return rc;
+  HIP_TRY(hipMemcpyAsync(lcp, d_out, 4 * n, hipMemcpyDeviceToHost, own.s), "D2H(lcp)");
   HIP_TRY(hipStreamSynchronize(own.s), "hipStreamSynchronize");
   return FMX_OK;
 }

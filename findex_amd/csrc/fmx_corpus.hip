@@ -292,18 +292,6 @@ unsigned co_grid(uint64_t m) {
   return (unsigned)(b < 1 ? 1 : b > 8192 ? 8192 : b);
 }
 
-int co_room(uint64_t need, const char *what) {
-  size_t free_b = 0, total_b = 0;
-  const hipError_t e = hipMemGetInfo(&free_b, &total_b);
-  if (e != hipSuccess) return hip_fail(e, "hipMemGetInfo");
-  if (need > free_b) {
-    set_error(std::string(what) + " needs " + std::to_string(need) + " bytes of device memory, " +
-              std::to_string((unsigned long long)free_b) + " are free");
-    return FMX_ERR_NOMEM;
-  }
-  return FMX_OK;
-}
-
 int co_check_ends(const uint64_t *ends, uint64_t n_docs, uint64_t raw_len) {
   if (n_docs < 1) return co_arg("a corpus has at least one document");
   if (!ends) return co_arg("null argument");
@@ -338,7 +326,7 @@ int co_build(const uint8_t *d_raw, uint64_t raw_len, const uint64_t *ends, uint6
   const uint64_t parts = scan_partials(ntiles + 1);
   const uint64_t tmp = 8 * n_docs + 4 * (ntiles + 1) + 4 * ntiles + 4 * parts;
   // the stream is raw_len + n_docs + escapes bytes: what is known before the count pass is checked now, the rest after it
-  int rc = co_room(tmp + raw_len + n_docs + 8 * (n_docs + 1) + 4096, "the corpus stream");
+  int rc = device_room(tmp + raw_len + n_docs + 8 * (n_docs + 1) + 4096, "the corpus stream");
   if (rc) return rc;
   DevMem mem;
   unsigned long long *d_ends = nullptr;
@@ -362,7 +350,7 @@ int co_build(const uint8_t *d_raw, uint64_t raw_len, const uint64_t *ends, uint6
     set_error("the corpus stream would be " + std::to_string(stream_len) + " bytes: at most 2^32 - 2 (the suffix sort's limit)");
     return FMX_ERR_UNSUPPORTED;
   }
-  if ((rc = co_room(stream_len + 8 * (n_docs + 1) + 4 * (uint64_t)n_esc + 4096, "the corpus stream"))) return rc;
+  if ((rc = device_room(stream_len + 8 * (n_docs + 1) + 4 * (uint64_t)n_esc + 4096, "the corpus stream"))) return rc;
   std::unique_ptr<Corpus> c(new Corpus);
   c->device = device;
   c->n_docs = n_docs;
@@ -424,7 +412,7 @@ int fmx_corpus_build(const uint8_t *raw, uint64_t raw_len, const uint64_t *doc_e
   int rc = co_check_ends(doc_ends, n_docs, raw_len);
   if (rc) return rc;
   if ((rc = use_device_index(device))) return rc;
-  if ((rc = co_room(2 * raw_len + 9 * n_docs + 4096, "the corpus stream"))) return rc;
+  if ((rc = device_room(2 * raw_len + 9 * n_docs + 4096, "the corpus stream"))) return rc;
   DevMem mem;
   StreamGuard own;
   HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
@@ -504,7 +492,7 @@ int fmx_corpus_open_index(const fmx_corpus *corpus, void *stream, fmx_index **ou
   hipStream_t st = (hipStream_t)stream;
   if ((rc = not_capturing(st, "index construction"))) return rc;
   const uint64_t n = c->stream_len + 1;
-  if ((rc = co_room(sufsort_peak_bytes(c->stream_len, false) + n, "the index of the corpus stream"))) return rc;
+  if ((rc = device_room(sufsort_peak_bytes(c->stream_len, false) + n, "the index of the corpus stream"))) return rc;
   DevMem mem;
   uint8_t *d_bwt = nullptr;
   DEV_ALLOC(mem, d_bwt, n, "corpus");
@@ -564,7 +552,7 @@ int fmx_corpus_from_tables(const uint64_t *doc_start, const uint64_t *raw_len, c
   ds[n_docs] = (uint32_t)doc_start[n_docs];
   int rc = use_device_index(device);
   if (rc) return rc;
-  if ((rc = co_room(8 * (n_docs + 1) + 4 * n_esc + 4096, "the corpus map"))) return rc;
+  if ((rc = device_room(8 * (n_docs + 1) + 4 * n_esc + 4096, "the corpus map"))) return rc;
   std::unique_ptr<Corpus> c(new Corpus);
   c->device = device;
   c->n_docs = n_docs;
@@ -602,7 +590,7 @@ int fmx_corpus_map(const fmx_corpus *corpus, const uint64_t *pos, size_t k, uint
   const Corpus *c = C(corpus);
   int rc = co_use(c);
   if (rc || !k) return rc;
-  if ((rc = co_room(28 * (uint64_t)k + 4096, "a corpus map call"))) return rc;
+  if ((rc = device_room(28 * (uint64_t)k + 4096, "a corpus map call"))) return rc;
   DevMem mem;
   unsigned long long *d_pos = nullptr, *d_eo = nullptr, *d_ro = nullptr;
   uint32_t *d_doc = nullptr;
@@ -646,7 +634,7 @@ int fmx_corpus_doc_list_dev(const fmx_corpus *corpus, const fmx_index *idx, cons
   HIP_TRY(ev.create(), "hipEventCreate");
   DevMem mem;
   unsigned long long *loc_off = nullptr;
-  if ((rc = co_room(8 * ((uint64_t)k + 1) + 4096, "a document listing"))) return rc;
+  if ((rc = device_room(8 * ((uint64_t)k + 1) + 4096, "a document listing"))) return rc;
   DEV_ALLOC(mem, loc_off, 8 * ((uint64_t)k + 1), "corpus");
   // the row counts first (no positions: cap 0), then room for exactly that many
   if ((rc = fmx_locate_intervals_dev(idx, d_sp, d_ep, k, max_per, loc_off, nullptr, 0, stream))) return rc;
@@ -669,7 +657,7 @@ int fmx_corpus_doc_list_dev(const fmx_corpus *corpus, const fmx_index *idx, cons
     return FMX_OK;
   }
   const uint64_t nt = radix_tiles(rows), hist_words = 256 * nt, parts = scan_partials(std::max<uint64_t>(rows, hist_words));
-  if ((rc = co_room(8 * rows + 16 * rows + 8 * rows + 4 * hist_words + 4 * parts + 8192, "a document listing"))) return rc;
+  if ((rc = device_room(8 * rows + 16 * rows + 8 * rows + 4 * hist_words + 4 * parts + 8192, "a document listing"))) return rc;
   unsigned long long *pos = nullptr, *k0 = nullptr, *k1 = nullptr;
   uint32_t *v0 = nullptr, *v1 = nullptr, *hist = nullptr, *partials = nullptr;
   DEV_ALLOC(mem, pos, 8 * rows, "corpus");
@@ -719,7 +707,7 @@ int fmx_corpus_doc_list(const fmx_corpus *corpus, const fmx_index *idx, const ui
   for (size_t i = 0; i < k; i++)
     if (sp[i] > n || ep[i] > n) return co_arg("interval out of range (sp, ep <= n)");
   if ((rc = co_use(c))) return rc;
-  if ((rc = co_room(24 * (uint64_t)k + 8 * (uint64_t)cap + 8192, "a document listing"))) return rc;
+  if ((rc = device_room(24 * (uint64_t)k + 8 * (uint64_t)cap + 8192, "a document listing"))) return rc;
   DevMem mem;
   StreamGuard own;
   HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");

@@ -346,7 +346,7 @@ static int edit_search(const Index *h, const void *d_pat, const void *d_off, uin
   }
   const uint64_t stack_bytes = k ? (uint64_t)grid * kEdWaves * kEdFrames * sizeof(EdFrame) : 0;
   int rc;
-  if ((rc = mstat_room(24 * cap + stack_bytes + kMeteredBytes + 8, "the edit search"))) return rc;
+  if ((rc = device_room(24 * cap + stack_bytes + kMeteredBytes + 8, "the edit search"))) return rc;
   Events<3> ev;
   HIP_TRY(ev.create(), "hipEventCreate");
   DevMem mem;

@@ -212,42 +212,25 @@ int extract_check(const Index *h) {
   return FMX_OK;
 }
 
-int extract_prepare(const Index *h, hipStream_t st) {
-  int rc = extract_check(h);
-  if (rc) return rc;
-  std::lock_guard<std::mutex> lk(h->ext_mu);
-  if (h->ext_ready) return FMX_OK;
-  const auto t0 = std::chrono::steady_clock::now();
+// The samples at the handle's rate into h->ext.
+static int extract_build(const Index *h, hipStream_t st, DevMem &mem) {
   const uint64_t n = h->n;
   const uint32_t rate = (uint32_t)h->policy.extract_sample.load(std::memory_order_relaxed);
   const uint64_t m = (n - 1) / rate + 1, nb = n / kBlockBits + 1;
   const bool wide = n > (1ull << 32);
   const uint64_t keep = m * (wide ? 8 : 4);
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  HIP_TRY(hipStreamIsCapturing(st, &cs), "hipStreamIsCapturing");
-  if (cs != hipStreamCaptureStatusNone) {
-    set_error("the extract samples are built by fmx_prepare(FMX_PREPARE_EXTRACT) or a first extract call outside a stream capture");
-    return FMX_ERR_HIP;
-  }
   // the locate samples at the same rate hold the same pairs (row, SA): no inversion then
-  std::unique_lock<std::mutex> ll(h->loc_mu);
-  const bool from_locate = h->loc_ready && h->loc_rate == rate;
+  std::unique_lock<std::mutex> ll(h->loc.mu);
+  const bool from_locate = h->loc.ready && h->loc.rate == rate;
   if (!from_locate) ll.unlock();
-  const uint64_t need = keep + (from_locate ? 0 : m * 8 + locate_invert_rows_bytes(h));
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
-  if (need > free_b) {
-    set_error("the extract samples need " + std::to_string((unsigned long long)need) + " bytes of device memory, " +
-              std::to_string((unsigned long long)free_b) + " are free");
-    return FMX_ERR_NOMEM;
-  }
-  DevMem mem;                                              // the temporaries, and the samples until they are the handle's
+  int rc = device_room(keep + (from_locate ? 0 : m * 8 + locate_invert_rows_bytes(h)), "the extract samples", "need");
+  if (rc) return rc;
   void *d_isa = nullptr;
   DEV_ALLOC(mem, d_isa, keep, "extract samples");
   if (from_locate) {
     HIP_TRY(hipMemsetAsync(d_isa, 0, keep, st), "hipMemset(extract samples)");
-    hipLaunchKernelGGL(k_isa_scatter, dim3(flat_grid(nb, 8192)), dim3(256), 0, st, static_cast<const uint32_t *>(h->d_loc_marks), nb, n,
-                       static_cast<const void *>(h->d_loc_samples), h->loc_wide ? 1 : 0, rate, m, wide ? 1 : 0, d_isa);
+    hipLaunchKernelGGL(k_isa_scatter, dim3(flat_grid(nb, 8192)), dim3(256), 0, st, static_cast<const uint32_t *>(h->loc.marks), nb, n,
+                       static_cast<const void *>(h->loc.samples), h->loc.wide ? 1 : 0, rate, m, wide ? 1 : 0, d_isa);
     HIP_TRY(hipGetLastError(), "k_isa_scatter");
     HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     ll.unlock();
@@ -260,23 +243,18 @@ int extract_prepare(const Index *h, hipStream_t st) {
     HIP_TRY(hipGetLastError(), "k_isa_pack");
     HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
   }
-  mem.ps.erase(std::find(mem.ps.begin(), mem.ps.end(), d_isa));      // kept
-  h->d_ext_isa = d_isa;
-  h->ext_rate = rate;
-  h->ext_wide = wide;
-  h->ext_bytes = keep;
-  h->ext_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  h->ext_ready = true;
+  mem.keep(d_isa);
+  h->ext.isa = d_isa;
+  h->ext.rate = rate;
+  h->ext.wide = wide;
+  h->ext.bytes = keep;
   return FMX_OK;
 }
 
-void extract_drop(Index *h) {
-  std::lock_guard<std::mutex> lk(h->ext_mu);
-  if (h->d_ext_isa) (void)hipFree(h->d_ext_isa);
-  h->d_ext_isa = nullptr;
-  h->ext_bytes = 0;
-  h->ext_rate = 0;
-  h->ext_ready = false;
+int extract_prepare(const Index *h, hipStream_t st) {
+  if (const int rc = extract_check(h)) return rc;
+  return build_locked(h->ext, st, "the extract samples are built by fmx_prepare(FMX_PREPARE_EXTRACT) or a first extract call outside a stream capture",
+                      [&](DevMem &mem) { return extract_build(h, st, mem); });
 }
 
 // ---------------------------------------------------------------- launches
@@ -296,10 +274,10 @@ static hipError_t extract_enqueue(const Index *h, const void *d_pos, const void 
                                   unsigned long long *counters, hipStream_t st) {
   if (n_bytes == 0 || k == 0) return hipSuccess;
   ExDev xd;
-  xd.isa = h->d_ext_isa;
-  xd.rate = h->ext_rate;
-  xd.m = (h->n - 1) / h->ext_rate + 1;
-  xd.wide = h->ext_wide ? 1u : 0u;
+  xd.isa = h->ext.isa;
+  xd.rate = h->ext.rate;
+  xd.m = (h->n - 1) / h->ext.rate + 1;
+  xd.wide = h->ext.wide ? 1u : 0u;
   hipError_t he = hipSuccess;
 #define FMX_EX_CALL(W, L) \
   he = ex_launch<W, L>(h, xd, static_cast<const uint64_t *>(d_pos), static_cast<const uint64_t *>(d_off), k, n_bytes, \
@@ -366,8 +344,8 @@ int fmx_extract_text_batch(const fmx_index *idx, const uint64_t *pos, const uint
   }
   if (!n_bytes) return FMX_OK;
   if ((rc = use_device(h))) return rc;
-  if ((rc = ensure_built(h, h->ext_mu, h->ext_ready, extract_prepare, nullptr))) return rc;
-  if ((rc = mstat_room(extract_bytes() + n_bytes + 16 * ((uint64_t)k + 1) + 64, "fmx_extract_text_batch"))) return rc;
+  if ((rc = ensure_built(h, h->ext, extract_prepare, nullptr))) return rc;
+  if ((rc = device_room(extract_bytes() + n_bytes + 16 * ((uint64_t)k + 1) + 64, "fmx_extract_text_batch"))) return rc;
   HostCall hc;
   void *d_pos = nullptr;
   uint64_t *d_off = nullptr;
@@ -392,7 +370,7 @@ int fmx_extract_text_batch_dev(const fmx_index *idx, const void *d_pos, const vo
   if (rc) return rc;
   if (!k || !n_bytes) return FMX_OK;
   if ((rc = use_device(h))) return rc;
-  if ((rc = ensure_built(h, h->ext_mu, h->ext_ready, extract_prepare, (hipStream_t)stream))) return rc;
+  if ((rc = ensure_built(h, h->ext, extract_prepare, (hipStream_t)stream))) return rc;
   HIP_TRY(extract_enqueue(h, d_pos, d_off, k, n_bytes, d_out, nullptr, (hipStream_t)stream), "k_extract");
   return FMX_OK;
 }
@@ -400,10 +378,10 @@ int fmx_extract_text_batch_dev(const fmx_index *idx, const void *d_pos, const vo
 int fmx_extract_info(const fmx_index *idx, uint32_t *rate, uint64_t *bytes, double *build_ms) {
   if (!idx) return arg_fail("null argument");
   const Index *h = H(idx);
-  std::lock_guard<std::mutex> lk(h->ext_mu);
-  if (rate) *rate = h->ext_ready ? h->ext_rate : (uint32_t)h->policy.extract_sample.load(std::memory_order_relaxed);
-  if (bytes) *bytes = h->ext_ready ? h->ext_bytes : 0;
-  if (build_ms) *build_ms = h->ext_ready ? h->ext_build_ms : 0.0;
+  std::lock_guard<std::mutex> lk(h->ext.mu);
+  if (rate) *rate = h->ext.ready ? h->ext.rate : (uint32_t)h->policy.extract_sample.load(std::memory_order_relaxed);
+  if (bytes) *bytes = h->ext.ready ? h->ext.bytes : 0;
+  if (build_ms) *build_ms = h->ext.ready ? h->ext.build_ms : 0.0;
   return FMX_OK;
 }
 

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -89,6 +90,58 @@ TablePolicy &default_policy();          // fmx_jump.hip: what fmx_config_set wri
 // One policy key = value into `p`: 0 ok, 1 unknown key (not a table key), 2 bad value (*why says which values there are)
 int policy_set(TablePolicy &p, const char *key, const char *value, const char **why);
 
+// A structure a handle derives from its index at first use and keeps until fmx_drop_tables: the lock its build and its drop
+// take, and what every *_info call reports.  Derived<F> adds the feature's own fields F; free_locked is the one place that
+// frees F's buffers, and it puts every field back to its default (the info calls report 0 while `ready` is false).
+struct Side {
+  std::mutex mu;
+  bool ready = false;
+  uint64_t bytes = 0;                           // device bytes held
+  double build_ms = 0.0;                        // host time of the build
+};
+template <class F>
+struct Derived : Side, F {
+  void free_locked() {                          // under mu
+    F::free_buffers();
+    static_cast<F &>(*this) = F{};
+    ready = false;
+    bytes = 0;
+    build_ms = 0.0;
+  }
+  void drop() {
+    std::lock_guard<std::mutex> lk(mu);
+    free_locked();
+  }
+};
+struct LocateSamples {                          // the sampled suffix array
+  void *marks = nullptr;                        // one-hot rank blocks over the rows: bit r set <=> SA[r] % rate == 0
+  void *samples = nullptr;                      // SA of the marked rows in row order: u32, or u64 when wide
+  uint32_t rate = 0;
+  bool wide = false;
+  void free_buffers() { (void)hipFree(marks); (void)hipFree(samples); }
+};
+struct LcpArray {                               // u32[n]
+  void *lcp = nullptr;
+  uint32_t max = 0;                             // the largest entry, the first row that holds it, the sum of all entries
+  uint64_t max_row = 0, sum = 0;
+  void free_buffers() { (void)hipFree(lcp); }
+};
+struct ExtractSamples {                         // the inverse-SA samples for extraction by text position
+  void *isa = nullptr;                          // isa[j] = the row with SA == j * rate, j = 0 .. (n - 1) / rate: u32, or u64 when wide
+  uint32_t rate = 0;
+  bool wide = false;
+  void free_buffers() { (void)hipFree(isa); }
+};
+struct LineTable {
+  void *brk = nullptr;                          // u32[max(n_brk, 1)]: the positions of the break bytes, ascending
+  void *dir = nullptr;                          // u32[((n - 1) >> shift) + 2]: dir[i] = the breaks before position i << shift
+  uint64_t n_brk = 0;
+  uint32_t shift = 0;
+  uint8_t set[4] = {0, 0, 0, 0};                // the break set, ascending
+  uint32_t n_set = 0;
+  void free_buffers() { (void)hipFree(brk); (void)hipFree(dir); }
+};
+
 struct Index {
   uint64_t serial = 0;          // unique per open in this process: what a resident regex batch remembers of its index
   int device = 0;
@@ -168,46 +221,12 @@ struct Index {
   mutable bool sel_ready = false;
   mutable void *d_sel_dir = nullptr, *d_sel_off = nullptr, *d_sel_shift = nullptr;
   mutable uint64_t sel_bytes = 0;
-  // sampled suffix array for locate (fmx_locate.hip), built by fmx_prepare(FMX_PREPARE_LOCATE) or the first locate call;
-  // outside the table budget (the search tables never see it)
-  mutable std::mutex loc_mu;
-  mutable bool loc_ready = false;
-  mutable void *d_loc_marks = nullptr;          // one-hot rank blocks over the rows: bit r set <=> SA[r] % loc_rate == 0
-  mutable void *d_loc_samples = nullptr;        // SA of the marked rows in row order: u32, or u64 when loc_wide
-  mutable uint32_t loc_rate = 0;
-  mutable bool loc_wide = false;
-  mutable uint64_t loc_bytes = 0;
-  mutable double loc_build_ms = 0.0;
-  // LCP array (fmx_lcp.hip), built by fmx_prepare(FMX_PREPARE_LCP) or the first LCP call; u32[n], outside the table
-  // budget like the locate samples
-  mutable std::mutex lcp_mu;
-  mutable bool lcp_ready = false;
-  mutable void *d_lcp = nullptr;
-  mutable uint64_t lcp_bytes = 0;
-  mutable double lcp_build_ms = 0.0;
-  mutable uint32_t lcp_max = 0;                 // the largest entry, the first row that holds it, the sum of all entries
-  mutable uint64_t lcp_max_row = 0, lcp_sum = 0;
-  // inverse-SA samples for extraction by text position (fmx_extract.hip), built by fmx_prepare(FMX_PREPARE_EXTRACT) or the
-  // first extract call; outside the table budget like the locate samples
-  mutable std::mutex ext_mu;
-  mutable bool ext_ready = false;
-  mutable void *d_ext_isa = nullptr;            // isa[j] = the row with SA == j * ext_rate, j = 0 .. (n - 1) / ext_rate: u32, or u64 when ext_wide
-  mutable uint32_t ext_rate = 0;
-  mutable bool ext_wide = false;
-  mutable uint64_t ext_bytes = 0;
-  mutable double ext_build_ms = 0.0;
-  // line table (fmx_lines.hip), built by fmx_prepare(FMX_PREPARE_LINES), fmx_lines_prepare or the first lines call; outside the
-  // table budget like the locate samples
-  mutable std::mutex lin_mu;
-  mutable bool lin_ready = false;
-  mutable void *d_lin_brk = nullptr;            // u32[max(n_brk, 1)]: the positions of the break bytes, ascending
-  mutable void *d_lin_dir = nullptr;            // u32[((n - 1) >> lin_shift) + 2]: dir[i] = the breaks before position i << lin_shift
-  mutable uint64_t lin_n_brk = 0;
-  mutable uint32_t lin_shift = 0;
-  mutable uint8_t lin_set[4] = {0, 0, 0, 0};    // the break set, ascending
-  mutable uint32_t lin_n_set = 0;
-  mutable uint64_t lin_bytes = 0;
-  mutable double lin_build_ms = 0.0;
+  // what is built at first use outside the table budget (the search tables never see it): by fmx_prepare(FMX_PREPARE_LOCATE |
+  // _LCP | _EXTRACT | _LINES), fmx_lines_prepare or the first call that needs it
+  mutable Derived<LocateSamples> loc;           // fmx_locate.hip
+  mutable Derived<LcpArray> lcp;                // fmx_lcp.hip
+  mutable Derived<ExtractSamples> ext;          // fmx_extract.hip
+  mutable Derived<LineTable> lin;               // fmx_lines.hip
   mutable uint64_t launches = 0;
   mutable double last_kernel_ms = 0.0;
   // the handle's host thread for the one-process-several-GPUs entry points (made at the first such call; fmx_hostpar.h)
@@ -246,14 +265,13 @@ hipError_t select_prepare(const Index *h, hipStream_t st);          // fmx_selec
 hipError_t jump_get(const Index *h, hipStream_t st, const uint4 **out, bool build = true);   // fmx_jump.hip (nullptr: the handle has none)
 hipError_t row1_get(const Index *h, hipStream_t st, const unsigned long long **out, bool build = true);   // fmx_jump.hip (nullptr: none)
 hipError_t row3_get(const Index *h, hipStream_t st, const unsigned long long **out, bool build = true);   // fmx_jump.hip (nullptr: none)
-int drop_tables(Index *h, unsigned what);       // fmx_jump.hip: fmx_drop_tables
+int drop_tables(Index *h, unsigned what);       // fmx_jump.hip: frees the budgeted tables `what` names (FMX_PREPARE_KTAB | _JUMP | _FRONTIER)
 
-// fmx_locate.hip: the locate samples.  locate_prepare builds them under loc_mu (allocates, synchronises `st`; an FMX_*
+// fmx_locate.hip: the locate samples.  locate_prepare builds them under loc.mu (allocates, synchronises `st`; an FMX_*
 // status with its message); launch_locate* need them built.  locate_write_sa: every row's SA as big-endian u32 into
 // d_sa_be (n < 2^32), the handle's own samples untouched; locate_write_sa_bytes: the device bytes that takes, d_sa_be included.
 int locate_check(const Index *h);               // FMX_ERR_UNSUPPORTED for handles locate cannot serve
 int locate_prepare(const Index *h, hipStream_t st);
-void locate_drop(Index *h);
 int locate_write_sa(const Index *h, hipStream_t st, uint32_t *d_sa_be);
 uint64_t locate_write_sa_bytes(const Index *h);
 hipError_t launch_locate(const Index *h, const void *d_rows, uint64_t k, void *d_out, hipStream_t st);
@@ -271,16 +289,14 @@ int locate_invert_rows(const Index *h, hipStream_t st, uint32_t rate, uint64_t *
 uint64_t locate_invert_rows_bytes(const Index *h);
 
 // fmx_extract.hip: text by position from inverse-SA samples, its entry points included.  extract_prepare builds
-// the samples under ext_mu (allocates, synchronises `st`; an FMX_* status with its message).
+// the samples under ext.mu (allocates, synchronises `st`; an FMX_* status with its message).
 int extract_check(const Index *h);              // FMX_ERR_UNSUPPORTED for handles extraction cannot serve (those of locate)
 int extract_prepare(const Index *h, hipStream_t st);
-void extract_drop(Index *h);
 
-// fmx_lines.hip: the line table.  lines_prepare builds it for the set {10} under lin_mu unless one exists
+// fmx_lines.hip: the line table.  lines_prepare builds it for the set {10} under lin.mu unless one exists
 // (allocates, synchronises `st`; an FMX_* status with its message); its entry points are in the unit.
 int lines_check(const Index *h);                // FMX_ERR_UNSUPPORTED for handles the line table cannot serve (locate's, n >= 2^32)
 int lines_prepare(const Index *h, hipStream_t st);
-void lines_drop(Index *h);
 // a table for a call that needs one: the handle's, or {10} / {10, 1} (with a corpus) built on `st` (a stream of the handle's
 // when null); FMX_ERR_ARG for a table that lacks byte 1 combined with a corpus
 int lines_ensure(const Index *h, bool with_corpus, hipStream_t st);
@@ -302,13 +318,10 @@ uint64_t lcp_text_bytes(uint64_t n);            // device bytes of s with the pa
 int lcp_core(const uint8_t *d_s, uint64_t n, const uint32_t *d_sa, uint32_t *d_lcp, int cu_count, hipStream_t st, LcpInfo *info);
 void lcp_reverse_text(const uint8_t *d_text, uint64_t len, uint8_t *d_s, int cu_count, hipStream_t st);   // s = reverse(text) + 0
 int lcp_check(const Index *h);                  // FMX_ERR_UNSUPPORTED for handles that have no LCP array
-int lcp_prepare(const Index *h, hipStream_t st);   // builds the handle's array under lcp_mu (allocates, synchronises `st`)
-void lcp_drop(Index *h);
+int lcp_prepare(const Index *h, hipStream_t st);   // builds the handle's array under lcp.mu (allocates, synchronises `st`)
 hipError_t launch_lcp_gather(const Index *h, const void *d_rows, uint64_t k, void *d_out, hipStream_t st);
 
-// fmx_approx.hip and fmx_mstat.hip (§16) hold their entry points themselves.  mstat_room: FMX_ERR_NOMEM with
-// the need in the message when `need` exceeds the free device memory (fmx_extract.hip asks it too).
-int mstat_room(uint64_t need, const char *what);
+// fmx_approx.hip and fmx_mstat.hip (§16) hold their entry points themselves.
 
 // fmx_search.hip: the residency census of the k_search4 instantiation this handle's full-size searches use now, taken with
 // calibration launches on `st` (synchronises it): fmx_prepare's last step, never a _dev call's.
@@ -338,6 +351,11 @@ struct DevMem {                 // the hipMalloc'ed temporaries of one call; fre
   }
   template <class T>
   hipError_t alloc(T **out, size_t count) { return get(reinterpret_cast<void **>(out), count * sizeof(T)); }
+  void keep(const void *p) {                    // p outlives the call: it is the caller's now
+    const auto it = std::find(ps.begin(), ps.end(), p);
+    if (it != ps.end()) ps.erase(it);
+  }
+  void free_now(void *p) { keep(p); (void)hipFree(p); }      // a temporary that goes before the call ends
   int take(void **out, size_t bytes, const char *what) {     // get, or "hipMalloc(<what>): .." and FMX_ERR_NOMEM
     const hipError_t e = get(out, bytes);
     if (e == hipSuccess) return FMX_OK;
@@ -415,14 +433,39 @@ inline uint32_t flat_grid(uint64_t items, uint32_t cap = 4096) {
   return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + 255) / 256, cap));
 }
 
-// fmx_api.cpp.  use_device_index: a device there is, `device` names one, hipSetDevice.  not_capturing: "<what> allocates and
-// synchronises: not under a stream capture" when `st` is being captured.  ensure_built: `prepare` (which takes `mu` itself
-// and looks again) on `st`, or on a stream of the handle's when st is null, unless `flag` says it has run.
+// fmx_api.cpp.  use_device_index: a device there is, `device` names one, hipSetDevice.  no_capture: FMX_ERR_HIP with `text`
+// when `st` is being captured; not_capturing: the same with "<what> allocates and synchronises: not under a stream capture".
+// device_room: FMX_ERR_NOMEM with "<what> <verb> <need> bytes of device memory, <free> are free" when `need` exceeds the
+// free device memory.  ensure_built: `prepare` (which takes side.mu itself and looks again) on `st`, or on a stream of the
+// handle's when st is null, unless the side is ready.
 int arg_fail(const char *msg);                  // records the message, returns FMX_ERR_ARG
 int use_device(const Index *h);
 int use_device_index(int device);
+int no_capture(hipStream_t st, const char *text);
 int not_capturing(hipStream_t st, const char *what);
-int ensure_built(const Index *h, std::mutex &mu, const bool &flag, int (*prepare)(const Index *, hipStream_t), hipStream_t st);
+int device_room(uint64_t need, const std::string &what, const char *verb = "needs");
+int ensure_built(const Index *h, Side &side, int (*prepare)(const Index *, hipStream_t), hipStream_t st);
+// The build of a derived structure under its lock: nothing when `ready` says it is there; not under a stream capture
+// (`capture_text` is the feature's refusal); `first`, what the build needs built before it (its time is not the structure's);
+// then `body`, which checks the room, allocates from `mem` (what it keeps it takes out of the bag), builds and, as its last
+// step, fills the record; then the build time and the ready flag, and only then the temporaries go.
+template <class Body, class Ready, class First>
+int build_locked(Side &side, hipStream_t st, const char *capture_text, Body body, Ready ready, First first) {
+  std::lock_guard<std::mutex> lk(side.mu);
+  if (ready()) return FMX_OK;
+  int rc = no_capture(st, capture_text);
+  if (rc || (rc = first())) return rc;
+  DevMem mem;
+  const auto t0 = std::chrono::steady_clock::now();
+  if ((rc = body(mem))) return rc;
+  side.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  side.ready = true;
+  return FMX_OK;
+}
+template <class Body>
+int build_locked(Side &side, hipStream_t st, const char *capture_text, Body body) {      // unless side.ready; nothing first
+  return build_locked(side, st, capture_text, body, [&] { return side.ready; }, [] { return (int)FMX_OK; });
+}
 bool offsets_monotonic(const uint64_t *off, size_t a, size_t b);      // off[a] <= off[a+1] <= .. <= off[b]
 inline Index *H(fmx_index *p) { return reinterpret_cast<Index *>(p); }
 inline const Index *H(const fmx_index *p) { return reinterpret_cast<const Index *>(p); }

@@ -416,10 +416,10 @@ hipError_t jump_get(const Index *h, hipStream_t st, const uint4 **out, bool buil
   return hipSuccess;
 }
 
-// fmx_drop_tables: frees derived tables (the caller guarantees that no call is using the handle).  They are built
+// fmx_drop_tables: frees the tables of the budget (the caller guarantees that no call is using the handle).  They are built
 // again by fmx_prepare or when the threshold is met anew.
 int drop_tables(Index *h, unsigned what) {
-  if (what & 1u) {      // the k-mer table
+  if (what & FMX_PREPARE_KTAB) {
     std::lock_guard<std::mutex> lk(h->kt_mu);
     if (h->d_ktab) (void)hipFree(h->d_ktab);
     if (h->d_kt_dense) (void)hipFree(h->d_kt_dense);
@@ -434,22 +434,18 @@ int drop_tables(Index *h, unsigned what) {
     h->kt_ready = false;
     h->prepared_ktab.store(false, std::memory_order_relaxed);
   }
-  if (what & 4u) {
+  if (what & FMX_PREPARE_JUMP) {
     { std::lock_guard<std::mutex> lk(h->jt_mu); if (h->d_jump) (void)hipFree(h->d_jump); tables_account(h, -(int64_t)h->jump_bytes); h->d_jump = nullptr; h->jump_bytes = 0; h->jump_pairs = false; h->jt_ready = false; }
     { std::lock_guard<std::mutex> lk(h->r3_mu); if (h->d_row3) (void)hipFree(h->d_row3); tables_account(h, -(int64_t)h->row3_bytes); h->d_row3 = nullptr; h->row3_bytes = 0; h->r3_ready = false; }
     h->prepared_rows.store(false, std::memory_order_relaxed);
   }
-  if (what & 5u) h->patterns_seen.store(0, std::memory_order_relaxed);
-  if (what & 8u) {
+  if (what & (FMX_PREPARE_KTAB | FMX_PREPARE_JUMP)) h->patterns_seen.store(0, std::memory_order_relaxed);
+  if (what & FMX_PREPARE_FRONTIER) {
     std::lock_guard<std::mutex> lk(h->r1_mu);
     if (h->d_row1) (void)hipFree(h->d_row1);
     tables_account(h, -(int64_t)h->row1_bytes);
     h->d_row1 = nullptr; h->row1_bytes = 0; h->r1_ready = false;
   }
-  if (what & 32u) locate_drop(h);     // the locate samples (FMX_PREPARE_LOCATE)
-  if (what & 64u) lcp_drop(h);        // the LCP array (FMX_PREPARE_LCP)
-  if (what & 128u) extract_drop(h);   // the inverse-SA samples (FMX_PREPARE_EXTRACT)
-  if (what & 256u) lines_drop(h);     // the line table (FMX_PREPARE_LINES)
   return 0;
 }
 

@@ -220,72 +220,38 @@ int lcp_check(const Index *h) {
   return FMX_OK;
 }
 
-int lcp_prepare(const Index *h, hipStream_t st) {
-  int rc = lcp_check(h);
-  if (rc) return rc;
-  std::lock_guard<std::mutex> lk(h->lcp_mu);
-  if (h->lcp_ready) return FMX_OK;
-  const auto t0 = std::chrono::steady_clock::now();
+// The handle's array into h->lcp: s and the suffix array by the inversion (fmx_locate.hip), then the core.
+static int lcp_build(const Index *h, hipStream_t st, DevMem &mem) {
   const uint64_t n = h->n;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  hipError_t e = hipStreamIsCapturing(st, &cs);
-  if (e != hipSuccess) return hip_fail(e, "hipStreamIsCapturing");
-  if (cs != hipStreamCaptureStatusNone) {
-    set_error("the LCP array is built by fmx_prepare(FMX_PREPARE_LCP) or a first LCP call outside a stream capture");
-    return FMX_ERR_HIP;
-  }
-  const uint64_t need = 4 * n + 4 * n + lcp_text_bytes(n) + lcp_core_bytes(n) + locate_invert_text_bytes(h);
-  size_t free_b = 0, total_b = 0;
-  if ((e = hipMemGetInfo(&free_b, &total_b)) != hipSuccess) return hip_fail(e, "hipMemGetInfo");
-  if (need > free_b) {
-    set_error("the LCP array needs " + std::to_string(need) + " bytes of device memory, " +
-              std::to_string((unsigned long long)free_b) + " are free");
-    return FMX_ERR_NOMEM;
-  }
-  struct Bufs {
-    void *lcp = nullptr, *sa = nullptr, *s = nullptr;
-    ~Bufs() {
-      if (lcp) (void)hipFree(lcp);
-      if (sa) (void)hipFree(sa);
-      if (s) (void)hipFree(s);
-    }
-  } b;
-  if ((e = hipMalloc(&b.lcp, 4 * n)) != hipSuccess || (e = hipMalloc(&b.sa, 4 * n)) != hipSuccess ||
-      (e = hipMalloc(&b.s, lcp_text_bytes(n))) != hipSuccess) {
-    set_error(std::string("hipMalloc(LCP): ") + hipGetErrorString(e));
-    return FMX_ERR_NOMEM;
-  }
-  if ((e = hipMemsetAsync(b.s, 0, lcp_text_bytes(n), st)) != hipSuccess) return hip_fail(e, "hipMemsetAsync");
-  if ((rc = locate_invert_text(h, st, static_cast<uint32_t *>(b.sa), static_cast<uint8_t *>(b.s)))) return rc;
+  int rc = device_room(4 * n + 4 * n + lcp_text_bytes(n) + lcp_core_bytes(n) + locate_invert_text_bytes(h), "the LCP array");
+  if (rc) return rc;
+  uint32_t *lcp = nullptr, *sa = nullptr;
+  uint8_t *s = nullptr;
+  DEV_ALLOC(mem, lcp, 4 * n, "LCP");
+  DEV_ALLOC(mem, sa, 4 * n, "LCP");
+  DEV_ALLOC(mem, s, lcp_text_bytes(n), "LCP");
+  HIP_TRY(hipMemsetAsync(s, 0, lcp_text_bytes(n), st), "hipMemsetAsync");
+  if ((rc = locate_invert_text(h, st, sa, s))) return rc;
   LcpInfo info;
-  if ((rc = lcp_core(static_cast<const uint8_t *>(b.s), n, static_cast<const uint32_t *>(b.sa), static_cast<uint32_t *>(b.lcp),
-                     h->cu_count, st, &info)))
-    return rc;
-  h->d_lcp = b.lcp;
-  b.lcp = nullptr;
-  h->lcp_bytes = 4 * n;
-  h->lcp_max = info.max;
-  h->lcp_max_row = info.max_row;
-  h->lcp_sum = info.sum;
-  h->lcp_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  h->lcp_ready = true;
+  if ((rc = lcp_core(s, n, sa, lcp, h->cu_count, st, &info))) return rc;
+  mem.keep(lcp);
+  h->lcp.lcp = lcp;
+  h->lcp.bytes = 4 * n;
+  h->lcp.max = info.max;
+  h->lcp.max_row = info.max_row;
+  h->lcp.sum = info.sum;
   return FMX_OK;
 }
 
-void lcp_drop(Index *h) {
-  std::lock_guard<std::mutex> lk(h->lcp_mu);
-  if (h->d_lcp) (void)hipFree(h->d_lcp);
-  h->d_lcp = nullptr;
-  h->lcp_bytes = 0;
-  h->lcp_max = 0;
-  h->lcp_max_row = h->lcp_sum = 0;
-  h->lcp_build_ms = 0.0;
-  h->lcp_ready = false;
+int lcp_prepare(const Index *h, hipStream_t st) {
+  if (const int rc = lcp_check(h)) return rc;
+  return build_locked(h->lcp, st, "the LCP array is built by fmx_prepare(FMX_PREPARE_LCP) or a first LCP call outside a stream capture",
+                      [&](DevMem &mem) { return lcp_build(h, st, mem); });
 }
 
 hipError_t launch_lcp_gather(const Index *h, const void *d_rows, uint64_t k, void *d_out, hipStream_t st) {
   if (!k) return hipSuccess;
-  k_lcp_rows<<<lcp_grid(h->cu_count, k), kLcpThreads, 0, st>>>(static_cast<const uint32_t *>(h->d_lcp), h->n,
+  k_lcp_rows<<<lcp_grid(h->cu_count, k), kLcpThreads, 0, st>>>(static_cast<const uint32_t *>(h->lcp.lcp), h->n,
                                                               static_cast<const uint64_t *>(d_rows), k, static_cast<uint32_t *>(d_out));
   return hipGetLastError();
 }

@@ -282,7 +282,7 @@ int lq_run(const Index *h, const Corpus *c, const uint64_t *hit_off, const unsig
   if (n_terms) std::memcpy(tm, terms, sizeof(fmx_line_term) * n_terms);
   const uint64_t parts = scan_partials(std::max<uint64_t>(n_cand, 1)), tab_bytes = 8 * (uint64_t)tab.size();
   // 8 bytes per hit, 4 per candidate, the scan's block totals, the query tables
-  if ((rc = mstat_room(8 * n_hits + 4 * n_cand + 4 * parts + tab_bytes + kMeteredBytes + 4096, "fmx_line_query"))) return rc;
+  if ((rc = device_room(8 * n_hits + 4 * n_cand + 4 * parts + tab_bytes + kMeteredBytes + 4096, "fmx_line_query"))) return rc;
   const CoMap map = c ? c->map() : CoMap{nullptr, nullptr, nullptr, 0, 0, 0};
   Events<5> ev;
   HIP_TRY(ev.create(), "hipEventCreate");
@@ -415,7 +415,7 @@ int fmx_line_query(const fmx_index *idx, const fmx_corpus *corpus, const uint64_
   if ((rc = use_device(h))) return rc;
   HostCall hc;
   if ((rc = hc.open())) return rc;
-  if ((rc = mstat_room(48 * n_hits + 16 * ((uint64_t)n_groups + 1) + 8 * ((uint64_t)n_queries + 1) + 48 * (uint64_t)cap + 4096, "fmx_line_query")))
+  if ((rc = device_room(48 * n_hits + 16 * ((uint64_t)n_groups + 1) + 8 * ((uint64_t)n_queries + 1) + 48 * (uint64_t)cap + 4096, "fmx_line_query")))
     return rc;
   unsigned long long *d_in_off = nullptr, *d_off = nullptr;
   fmx_line_hit *d_hits = nullptr, *d_out = nullptr;

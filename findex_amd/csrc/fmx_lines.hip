@@ -198,33 +198,9 @@ int lines_set_args(const uint8_t *breaks, size_t n_breaks, uint8_t set[4], uint3
   return FMX_OK;
 }
 
-void lines_free_locked(const Index *h) {
-  if (h->d_lin_brk) (void)hipFree(h->d_lin_brk);
-  if (h->d_lin_dir) (void)hipFree(h->d_lin_dir);
-  h->d_lin_brk = h->d_lin_dir = nullptr;
-  h->lin_n_brk = 0;
-  h->lin_bytes = 0;
-  h->lin_shift = 0;
-  h->lin_n_set = 0;
-  h->lin_build_ms = 0.0;
-  h->lin_ready = false;
-}
-
-// The table for `set` (ascending) on `st`, under lin_mu: nothing to do when the handle has it for that set, rebuilt when it
-// has it for another.  Allocates, synchronises `st`, frees its temporaries on every path.
-int lines_build(const Index *h, const uint8_t *set, uint32_t n_set, hipStream_t st) {
-  int rc = lines_check(h);
-  if (rc) return rc;
-  std::lock_guard<std::mutex> lk(h->lin_mu);
-  if (h->lin_ready && h->lin_n_set == n_set && std::equal(set, set + n_set, h->lin_set)) return FMX_OK;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  HIP_TRY(hipStreamIsCapturing(st, &cs), "hipStreamIsCapturing");
-  if (cs != hipStreamCaptureStatusNone) {
-    set_error("the line table is built by fmx_prepare(FMX_PREPARE_LINES), fmx_lines_prepare or a first lines call outside a stream capture");
-    return FMX_ERR_HIP;
-  }
-  if ((rc = ensure_built(h, h->loc_mu, h->loc_ready, locate_prepare, st))) return rc;
-  const auto t0 = std::chrono::steady_clock::now();
+// The table for `set` into h->lin, in place of one for another set; the locate samples are built.
+int lines_table(const Index *h, const uint8_t *set, uint32_t n_set, hipStream_t st, DevMem &mem) {
+  int rc;
   const uint64_t n = h->n, len = n - 1;
   const uint32_t shift = (uint32_t)h->policy.lines_shift.load(std::memory_order_relaxed);
   unsigned long long sp[4] = {0, 0, 0, 0}, ep[4] = {0, 0, 0, 0};
@@ -242,10 +218,9 @@ int lines_build(const Index *h, const uint8_t *set, uint32_t n_set, hipStream_t 
   const uint64_t nt = radix_tiles(std::max<uint64_t>(m, 1)), hist_words = 256 * nt;
   const uint64_t parts = scan_partials(std::max<uint64_t>(m, hist_words));
   // the SA values, two key and two value buffers, the histograms and the scan's block totals, the table itself
-  if ((rc = mstat_room(keep + 32 * m + 4 * hist_words + 4 * parts + 8192, "the line table"))) return rc;
+  if ((rc = device_room(keep + 32 * m + 4 * hist_words + 4 * parts + 8192, "the line table"))) return rc;
   Events<4> ev;
   HIP_TRY(ev.create(), "hipEventCreate");
-  DevMem mem;                                        // the temporaries, and the table until it is the handle's
   uint32_t *brk = nullptr, *dir = nullptr, *bad = nullptr;
   DEV_ALLOC(mem, brk, 4 * std::max<uint64_t>(m, 1), "line table");
   DEV_ALLOC(mem, dir, 4 * entries, "line table");
@@ -299,19 +274,28 @@ int lines_build(const Index *h, const uint8_t *set, uint32_t n_set, hipStream_t 
   }
   g_lines_last.locate_ms = ev.ms(0, 1);
   g_lines_last.sort_ms = ev.ms(1, 3);
-  lines_free_locked(h);
-  mem.ps.erase(std::find(mem.ps.begin(), mem.ps.end(), (void *)brk));      // kept
-  mem.ps.erase(std::find(mem.ps.begin(), mem.ps.end(), (void *)dir));
-  h->d_lin_brk = brk;
-  h->d_lin_dir = dir;
-  h->lin_n_brk = m;
-  h->lin_shift = shift;
-  std::copy(set, set + n_set, h->lin_set);
-  h->lin_n_set = n_set;
-  h->lin_bytes = keep;
-  h->lin_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  h->lin_ready = true;
+  h->lin.free_locked();                                    // a table for another set
+  mem.keep(brk);
+  mem.keep(dir);
+  h->lin.brk = brk;
+  h->lin.dir = dir;
+  h->lin.n_brk = m;
+  h->lin.shift = shift;
+  std::copy(set, set + n_set, h->lin.set);
+  h->lin.n_set = n_set;
+  h->lin.bytes = keep;
   return FMX_OK;
+}
+
+// The table for `set` (ascending) on `st`, under lin.mu: nothing to do when the handle has it for that set, rebuilt when it
+// has it for another.  Allocates, synchronises `st`, frees its temporaries on every path.
+int lines_build(const Index *h, const uint8_t *set, uint32_t n_set, hipStream_t st) {
+  if (const int rc = lines_check(h)) return rc;
+  return build_locked(
+      h->lin, st, "the line table is built by fmx_prepare(FMX_PREPARE_LINES), fmx_lines_prepare or a first lines call outside a stream capture",
+      [&](DevMem &mem) { return lines_table(h, set, n_set, st, mem); },
+      [&] { return h->lin.ready && h->lin.n_set == n_set && std::equal(set, set + n_set, h->lin.set); },
+      [&] { return ensure_built(h, h->loc, locate_prepare, st); });      // the table is made from the locate samples
 }
 
 }  // namespace
@@ -320,9 +304,9 @@ int lines_build(const Index *h, const uint8_t *set, uint32_t n_set, hipStream_t 
 // With a corpus the set must hold byte 1.
 int lines_ensure(const Index *h, bool with_corpus, hipStream_t st) {
   {
-    std::lock_guard<std::mutex> lk(h->lin_mu);
-    if (h->lin_ready) {
-      if (with_corpus && !std::count(h->lin_set, h->lin_set + h->lin_n_set, (uint8_t)1))
+    std::lock_guard<std::mutex> lk(h->lin.mu);
+    if (h->lin.ready) {
+      if (with_corpus && !std::count(h->lin.set, h->lin.set + h->lin.n_set, (uint8_t)1))
         return arg_fail("lines: the line table's break set lacks byte 1, the corpus separator: fmx_lines_prepare with {10, 1}");
       return FMX_OK;
     }
@@ -360,7 +344,7 @@ int lookup_host(const Index *h, bool spans, const uint64_t *in, size_t k, uint64
   if (rc || (rc = lines_ensure(h, false, nullptr))) return rc;
   g_lines_last.lookup_ms = 0;
   if (!k) return FMX_OK;
-  if ((rc = mstat_room(32 * (uint64_t)k + 4096, spans ? "fmx_line_spans" : "fmx_lines_batch"))) return rc;
+  if ((rc = device_room(32 * (uint64_t)k + 4096, spans ? "fmx_line_spans" : "fmx_lines_batch"))) return rc;
   HostCall hc;
   if ((rc = hc.open())) return rc;
   Events<2> ev;
@@ -425,7 +409,7 @@ int ol_run(const Index *h, const Corpus *c, const unsigned long long *d_occ_off,
     return FMX_OK;
   }
   const uint64_t parts = scan_partials(n_occ);
-  if ((rc = mstat_room(16 * n_occ + 4 * parts + 4096, "fmx_occurrence_lines"))) return rc;
+  if ((rc = device_room(16 * n_occ + 4 * parts + 4096, "fmx_occurrence_lines"))) return rc;
   const CoMap map = c ? c->map() : CoMap{nullptr, nullptr, nullptr, 0, 0, 0};
   const LinesDev L = lines_dev(h);
   Events<3> ev;
@@ -488,16 +472,11 @@ int lines_check(const Index *h) {
 
 int lines_prepare(const Index *h, hipStream_t st) {
   {
-    std::lock_guard<std::mutex> lk(h->lin_mu);
-    if (h->lin_ready) return FMX_OK;
+    std::lock_guard<std::mutex> lk(h->lin.mu);
+    if (h->lin.ready) return FMX_OK;
   }
   const uint8_t set[1] = {10};
   return lines_build(h, set, 1, st);
-}
-
-void lines_drop(Index *h) {
-  std::lock_guard<std::mutex> lk(h->lin_mu);
-  lines_free_locked(h);
 }
 
 }  // namespace fmx
@@ -523,16 +502,16 @@ int fmx_lines_info(const fmx_index *idx, uint64_t *n_breaks_found, uint8_t set[4
                    double *build_ms) {
   if (!idx) return arg_fail("null argument");
   const Index *h = H(idx);
-  std::lock_guard<std::mutex> lk(h->lin_mu);
-  if (n_breaks_found) *n_breaks_found = h->lin_ready ? h->lin_n_brk : 0;
+  std::lock_guard<std::mutex> lk(h->lin.mu);
+  if (n_breaks_found) *n_breaks_found = h->lin.ready ? h->lin.n_brk : 0;
   if (set) {
-    for (int i = 0; i < 4; i++) set[i] = h->lin_ready && (uint32_t)i < h->lin_n_set ? h->lin_set[i] : 0;
-    if (!h->lin_ready) set[0] = 10;
+    for (int i = 0; i < 4; i++) set[i] = h->lin.ready && (uint32_t)i < h->lin.n_set ? h->lin.set[i] : 0;
+    if (!h->lin.ready) set[0] = 10;
   }
-  if (n_set) *n_set = h->lin_ready ? h->lin_n_set : 1;
-  if (shift) *shift = h->lin_ready ? h->lin_shift : (uint32_t)h->policy.lines_shift.load(std::memory_order_relaxed);
-  if (bytes) *bytes = h->lin_ready ? h->lin_bytes : 0;
-  if (build_ms) *build_ms = h->lin_ready ? h->lin_build_ms : 0.0;
+  if (n_set) *n_set = h->lin.ready ? h->lin.n_set : 1;
+  if (shift) *shift = h->lin.ready ? h->lin.shift : (uint32_t)h->policy.lines_shift.load(std::memory_order_relaxed);
+  if (bytes) *bytes = h->lin.ready ? h->lin.bytes : 0;
+  if (build_ms) *build_ms = h->lin.ready ? h->lin.build_ms : 0.0;
   return FMX_OK;
 }
 
@@ -607,7 +586,7 @@ int fmx_occurrence_lines(const fmx_index *idx, const fmx_corpus *corpus, const u
   if ((rc = use_device(h))) return rc;
   HostCall hc;
   if ((rc = hc.open())) return rc;
-  if ((rc = mstat_room(32 * n_occ + 16 * ((uint64_t)n_groups + 1) + 48 * (uint64_t)cap + 4096, "fmx_occurrence_lines"))) return rc;
+  if ((rc = device_room(32 * n_occ + 16 * ((uint64_t)n_groups + 1) + 48 * (uint64_t)cap + 4096, "fmx_occurrence_lines"))) return rc;
   unsigned long long *d_in_off = nullptr, *d_off = nullptr;
   fmx_occurrence *d_occ = nullptr;
   fmx_line_hit *d_out = nullptr;

@@ -15,8 +15,8 @@ struct LinesDev {
 };
 
 inline LinesDev lines_dev(const Index *h) {
-  return LinesDev{static_cast<const uint32_t *>(h->d_lin_brk), static_cast<const uint32_t *>(h->d_lin_dir), h->lin_n_brk, h->n - 1,
-                  h->lin_shift};
+  return LinesDev{static_cast<const uint32_t *>(h->lin.brk), static_cast<const uint32_t *>(h->lin.dir), h->lin.n_brk, h->n - 1,
+                  h->lin.shift};
 }
 
 __device__ __forceinline__ uint64_t lin_line(const LinesDev &L, uint64_t p) {      // p < len

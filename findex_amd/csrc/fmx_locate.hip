@@ -574,18 +574,6 @@ static int invert(const Index *h, hipStream_t st, DevMem &mem, uint32_t rate, ui
   return FMX_OK;
 }
 
-static int check_room(uint64_t need, const char *what) {
-  size_t free_b = 0, total_b = 0;
-  hipError_t e = hipMemGetInfo(&free_b, &total_b);
-  if (e != hipSuccess) return hip_fail(e, "hipMemGetInfo");
-  if (need > free_b) {
-    set_error(std::string(what) + " needs " + std::to_string(need) + " bytes of device memory, " +
-              std::to_string((unsigned long long)free_b) + " are free");
-    return FMX_ERR_NOMEM;
-  }
-  return FMX_OK;
-}
-
 static int loc_supported(const Index *h) {
   if (h->block_mode) {
     set_error("locate needs the index of one text: fmx_open_block handles (one merge block) have no suffix array");
@@ -600,86 +588,57 @@ static int loc_supported(const Index *h) {
 
 int locate_check(const Index *h) { return loc_supported(h); }
 
-int locate_prepare(const Index *h, hipStream_t st) {
-  int rc = loc_supported(h);
-  if (rc) return rc;
-  std::lock_guard<std::mutex> lk(h->loc_mu);
-  if (h->loc_ready) return FMX_OK;
-  const auto t0 = std::chrono::steady_clock::now();
+// The samples at the handle's rate into h->loc: the inversion, the marks as rank blocks, the samples in row order.
+static int locate_build(const Index *h, hipStream_t st, DevMem &mem) {
   const uint64_t n = h->n;
   const uint32_t rate = (uint32_t)h->policy.locate_sample.load(std::memory_order_relaxed);
   const uint64_t m = (n - 1) / rate + 1, nb = n / kBlockBits + 1;
   const bool wide = n > (1ull << 32);
   const uint64_t keep = sample_bytes(n, rate);
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  hipError_t e = hipStreamIsCapturing(st, &cs);
-  if (e != hipSuccess) return hip_fail(e, "hipStreamIsCapturing");
-  if (cs != hipStreamCaptureStatusNone) {
-    set_error("the locate samples are built by fmx_prepare(FMX_PREPARE_LOCATE) or a first locate call outside a stream capture");
-    return FMX_ERR_HIP;
-  }
-  if ((rc = check_room(inv_temp_bytes(n, rate) + keep, "the locate samples"))) return rc;
+  int rc = device_room(inv_temp_bytes(n, rate) + keep, "the locate samples");
+  if (rc) return rc;
   void *d_marks = nullptr, *d_samples = nullptr;
-  if ((e = hipMalloc(&d_marks, nb * kBlockBytes)) != hipSuccess || (e = hipMalloc(&d_samples, m * (wide ? 8 : 4))) != hipSuccess) {
-    if (d_marks) (void)hipFree(d_marks);
-    set_error(std::string("hipMalloc(locate samples): ") + hipGetErrorString(e));
-    return FMX_ERR_NOMEM;
+  uint64_t *tmp = nullptr, *d_pre = nullptr;
+  uint32_t *d_cnt = nullptr;
+  DEV_ALLOC(mem, d_marks, nb * kBlockBytes, "locate samples");
+  DEV_ALLOC(mem, d_samples, m * (wide ? 8 : 4), "locate samples");
+  DEV_ALLOC(mem, tmp, m * 8, "locate samples");
+  DEV_ALLOC(mem, d_cnt, nb * 4, "locate samples");
+  DEV_ALLOC(mem, d_pre, nb * 8, "locate samples");
+  if ((rc = invert(h, st, mem, rate, tmp, nullptr))) return rc;
+  HIP_TRY(hipMemsetAsync(d_marks, 0, nb * kBlockBytes, st), "hipMemset(marks)");
+  k_mark_set<<<flat_grid(h, m), kLocThreads, 0, st>>>(tmp, m, (uint32_t *)d_marks);
+  k_mark_count<<<flat_grid(h, nb), kLocThreads, 0, st>>>((const uint32_t *)d_marks, nb, d_cnt);
+  HIP_TRY(hipGetLastError(), "k_mark_count");
+  std::vector<uint32_t> cnt(nb);
+  std::vector<uint64_t> pre(nb);
+  HIP_TRY(hipMemcpyAsync(cnt.data(), d_cnt, nb * 4, hipMemcpyDeviceToHost, st), "D2H(mark counts)");
+  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+  uint64_t acc = 0;
+  for (uint64_t b = 0; b < nb; b++) { pre[b] = acc; acc += cnt[b]; }
+  if (acc != m) {
+    set_error("locate: " + std::to_string(acc) + " rows marked, " + std::to_string(m) + " expected -- not the BWT of one text");
+    return FMX_ERR_FORMAT;
   }
-  struct Guard {
-    void **a, **b;
-    bool keep = false;
-    ~Guard() { if (!keep) { (void)hipFree(*a); (void)hipFree(*b); } }
-  } guard{&d_marks, &d_samples};
-  {
-    DevMem mem;
-    uint64_t *tmp = nullptr;
-    uint32_t *d_cnt = nullptr;
-    uint64_t *d_pre = nullptr;
-    if ((e = mem.get((void **)&tmp, m * 8)) != hipSuccess || (e = mem.get((void **)&d_cnt, nb * 4)) != hipSuccess ||
-        (e = mem.get((void **)&d_pre, nb * 8)) != hipSuccess) {
-      set_error(std::string("hipMalloc(locate samples): ") + hipGetErrorString(e));
-      return FMX_ERR_NOMEM;
-    }
-    if ((rc = invert(h, st, mem, rate, tmp, nullptr))) return rc;
-    if ((e = hipMemsetAsync(d_marks, 0, nb * kBlockBytes, st)) != hipSuccess) return hip_fail(e, "hipMemset(marks)");
-    k_mark_set<<<flat_grid(h, m), kLocThreads, 0, st>>>(tmp, m, (uint32_t *)d_marks);
-    k_mark_count<<<flat_grid(h, nb), kLocThreads, 0, st>>>((const uint32_t *)d_marks, nb, d_cnt);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_mark_count");
-    std::vector<uint32_t> cnt(nb);
-    std::vector<uint64_t> pre(nb);
-    if ((e = hipMemcpyAsync(cnt.data(), d_cnt, nb * 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return hip_fail(e, "D2H(mark counts)");
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-    uint64_t acc = 0;
-    for (uint64_t b = 0; b < nb; b++) { pre[b] = acc; acc += cnt[b]; }
-    if (acc != m) {
-      set_error("locate: " + std::to_string(acc) + " rows marked, " + std::to_string(m) + " expected -- not the BWT of one text");
-      return FMX_ERR_FORMAT;
-    }
-    if ((e = hipMemcpyAsync(d_pre, pre.data(), nb * 8, hipMemcpyHostToDevice, st)) != hipSuccess) return hip_fail(e, "H2D(mark counts)");
-    k_mark_headers<<<flat_grid(h, nb), kLocThreads, 0, st>>>(d_pre, nb, (uint64_t *)d_marks);
-    k_mark_samples<<<flat_grid(h, m), kLocThreads, 0, st>>>(tmp, m, (const uint32_t *)d_marks, rate, wide ? 1 : 0, d_samples);
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "k_mark_samples");
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
-  }
-  guard.keep = true;
-  h->d_loc_marks = d_marks;
-  h->d_loc_samples = d_samples;
-  h->loc_rate = rate;
-  h->loc_wide = wide;
-  h->loc_bytes = keep;
-  h->loc_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  h->loc_ready = true;
+  HIP_TRY(hipMemcpyAsync(d_pre, pre.data(), nb * 8, hipMemcpyHostToDevice, st), "H2D(mark counts)");
+  k_mark_headers<<<flat_grid(h, nb), kLocThreads, 0, st>>>(d_pre, nb, (uint64_t *)d_marks);
+  k_mark_samples<<<flat_grid(h, m), kLocThreads, 0, st>>>(tmp, m, (const uint32_t *)d_marks, rate, wide ? 1 : 0, d_samples);
+  HIP_TRY(hipGetLastError(), "k_mark_samples");
+  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+  mem.keep(d_marks);
+  mem.keep(d_samples);
+  h->loc.marks = d_marks;
+  h->loc.samples = d_samples;
+  h->loc.rate = rate;
+  h->loc.wide = wide;
+  h->loc.bytes = keep;
   return FMX_OK;
 }
 
-void locate_drop(Index *h) {
-  std::lock_guard<std::mutex> lk(h->loc_mu);
-  if (h->d_loc_marks) (void)hipFree(h->d_loc_marks);
-  if (h->d_loc_samples) (void)hipFree(h->d_loc_samples);
-  h->d_loc_marks = h->d_loc_samples = nullptr;
-  h->loc_bytes = 0;
-  h->loc_rate = 0;
-  h->loc_ready = false;
+int locate_prepare(const Index *h, hipStream_t st) {
+  if (const int rc = loc_supported(h)) return rc;
+  return build_locked(h->loc, st, "the locate samples are built by fmx_prepare(FMX_PREPARE_LOCATE) or a first locate call outside a stream capture",
+                      [&](DevMem &mem) { return locate_build(h, st, mem); });
 }
 
 int locate_write_sa(const Index *h, hipStream_t st, uint32_t *d_sa_be) {
@@ -714,9 +673,9 @@ uint64_t locate_invert_rows_bytes(const Index *h) { return inv_temp_bytes(h->n, 
 
 static LocDev loc_dev(const Index *h) {
   LocDev ld;
-  ld.marks = (const uint4 *)h->d_loc_marks;
-  ld.samples = h->d_loc_samples;
-  ld.wide = h->loc_wide ? 1u : 0u;
+  ld.marks = (const uint4 *)h->loc.marks;
+  ld.samples = h->loc.samples;
+  ld.wide = h->loc.wide ? 1u : 0u;
   return ld;
 }
 

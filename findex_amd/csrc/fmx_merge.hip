@@ -404,13 +404,7 @@ int merge_core(const Index *h, const uint8_t *d_text, uint64_t b, const MergeOpt
     piece = nullptr;
     const uint64_t need = piece_hold_bytes(M, b) + piece_temp_bytes(M, b) + place_bytes(b, nseg) + extra;
     stats.need_bytes = need;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
-    if (need > free_b) {
-      set_error("append of " + std::to_string(b) + " bytes with a context of " + std::to_string(M) + " needs " +
-                std::to_string(need) + " bytes of device memory, " + std::to_string((unsigned long long)free_b) + " are free");
-      return FMX_ERR_NOMEM;
-    }
+    if (const int rc = device_room(need, "append of " + std::to_string(b) + " bytes with a context of " + std::to_string(M))) return rc;
     if (first) {
       DEV_ALLOC(mem, res, 8 * kResWords, "append");
       DEV_ALLOC(mem, d_sps, 8, "append");
@@ -590,13 +584,7 @@ int fmx_append_text(const fmx_index *idx, const uint8_t *text, uint64_t len, con
   StreamGuard own;
   HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking), "hipStreamCreate");
   const uint64_t extra = len + n_t + handle_bytes_floor(n_t, nslots);
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
-  if (extra > free_b) {
-    set_error("append: the merged index of " + std::to_string(n_t) + " rows needs " + std::to_string(extra) +
-              " bytes of device memory, " + std::to_string((unsigned long long)free_b) + " are free");
-    return FMX_ERR_NOMEM;
-  }
+  if ((rc = device_room(extra, "append: the merged index of " + std::to_string(n_t) + " rows"))) return rc;
   uint8_t *d_text = nullptr, *d_out = nullptr;
   DEV_ALLOC(mem, d_text, len, "append text");
   DEV_ALLOC(mem, d_out, n_t, "append output");

@@ -221,17 +221,6 @@ static uint64_t mstat_bytes(uint64_t n_bytes, bool mems) {
   return need;
 }
 
-int mstat_room(uint64_t need, const char *what) {
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
-  if (need > free_b) {
-    set_error(std::string(what) + " needs " + std::to_string((unsigned long long)need) + " bytes of device memory, " +
-              std::to_string((unsigned long long)free_b) + " are free");
-    return FMX_ERR_NOMEM;
-  }
-  return FMX_OK;
-}
-
 struct MstatInfo {
   uint64_t total = 0, steps = 0, requests = 0;
   double walk_ms = 0.0, compact_ms = 0.0;       // device events: k_mstat, the flag / scan / write steps
@@ -244,7 +233,7 @@ static int mstat_run(const Index *h, const void *d_pat, const void *d_off, uint6
                      uint32_t min_len, void *d_len, void *d_sp, void *d_ep, bool mems, void *d_out_off, void *d_out,
                      uint64_t cap, hipStream_t st, MstatInfo *info) {
   *info = MstatInfo{};
-  int rc = mstat_room(mstat_bytes(n_bytes, mems), mems ? "fmx_mems_batch" : "fmx_match_stats_batch");
+  int rc = device_room(mstat_bytes(n_bytes, mems), mems ? "fmx_mems_batch" : "fmx_match_stats_batch");
   if (rc) return rc;
   Events<3> ev;
   HIP_TRY(ev.create(), "hipEventCreate");
@@ -358,7 +347,7 @@ int fmx_match_stats_batch(const fmx_index *idx, const uint8_t *pat, const uint64
   const Index *h = H(idx);
   if ((rc = use_device(h))) return rc;
   const uint64_t outs = n_bytes * (4 + (out_sp ? 8 : 0) + (out_ep ? 8 : 0));
-  if ((rc = mstat_room(mstat_bytes(n_bytes, false) + n_bytes + 8 * ((uint64_t)k + 1) + outs + 64, "fmx_match_stats_batch"))) return rc;
+  if ((rc = device_room(mstat_bytes(n_bytes, false) + n_bytes + 8 * ((uint64_t)k + 1) + outs + 64, "fmx_match_stats_batch"))) return rc;
   HostCall hc;
   void *d_pat = nullptr;
   uint64_t *d_off = nullptr, *d_sp = nullptr, *d_ep = nullptr;
@@ -404,8 +393,8 @@ int fmx_mems_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off
   if ((rc = mstat_args(idx, k, n_bytes, opts, &max_len, &min_len))) return rc;
   const Index *h = H(idx);
   if ((rc = use_device(h))) return rc;
-  if ((rc = mstat_room(mstat_bytes(n_bytes, true) + n_bytes + 16 * ((uint64_t)k + 1) + sizeof(fmx_mem_hit) * (uint64_t)cap + 64,
-                       "fmx_mems_batch"))) return rc;
+  if ((rc = device_room(mstat_bytes(n_bytes, true) + n_bytes + 16 * ((uint64_t)k + 1) + sizeof(fmx_mem_hit) * (uint64_t)cap + 64,
+                        "fmx_mems_batch"))) return rc;
   HostCall hc;
   void *d_pat = nullptr;
   uint64_t *d_off = nullptr, *d_out_off = nullptr;

@@ -296,8 +296,8 @@ static uint64_t ngrams_need(const Index *h, const NgOpts &o) {
   const uint64_t own = ngrams_bytes(h, o);
   bool built;
   {
-    std::lock_guard<std::mutex> lk(h->lcp_mu);
-    built = h->lcp_ready;
+    std::lock_guard<std::mutex> lk(h->lcp.mu);
+    built = h->lcp.ready;
   }
   return built ? own : std::max(own + 4 * h->n, ng_lcp_build_bytes(h));
 }
@@ -309,7 +309,7 @@ static int ngrams_first_long_row(const Index *h, uint64_t L, hipStream_t st, uin
   uint64_t c = 1;
   while (c * c < L) c++;
   const uint64_t nchk = (L + c - 1) / c;
-  int rc = mstat_room(8 * c * nchk + L + 1 + 8, "fmx_ngrams");
+  int rc = device_room(8 * c * nchk + L + 1 + 8, "fmx_ngrams");
   if (rc) return rc;
   DevMem mem;
   uint64_t *M = nullptr;
@@ -358,10 +358,10 @@ static int ngrams_run(const Index *h, const uint32_t *lengths, size_t k, const N
     }
     return FMX_OK;
   }
-  int rc = mstat_room(ngrams_need(h, o), "fmx_ngrams");
+  int rc = device_room(ngrams_need(h, o), "fmx_ngrams");
   if (rc) return rc;
-  if ((rc = ensure_built(h, h->lcp_mu, h->lcp_ready, lcp_prepare, st))) return rc;
-  const uint32_t *lcp = static_cast<const uint32_t *>(h->d_lcp);
+  if ((rc = ensure_built(h, h->lcp, lcp_prepare, st))) return rc;
+  const uint32_t *lcp = static_cast<const uint32_t *>(h->lcp.lcp);
   Events<8> ev;
   HIP_TRY(ev.create(), "hipEventCreate");
   DevMem mem;
@@ -465,7 +465,7 @@ static int ngrams_run(const Index *h, const uint32_t *lengths, size_t k, const N
         info->select_ms += ev.ms(5, 6);
       } else if (writes) {
         const uint64_t sel = selected, hist_words = 256 * radix_tiles(sel);
-        if ((rc = mstat_room(ngrams_sort_bytes(sel, o.pos), "fmx_ngrams (the sort)"))) return rc;
+        if ((rc = device_room(ngrams_sort_bytes(sel, o.pos), "fmx_ngrams (the sort)"))) return rc;
         DevMem sortmem;
         unsigned long long *k0 = nullptr, *k1 = nullptr;
         uint32_t *v0 = nullptr, *v1 = nullptr, *hist = nullptr, *sort_partials = nullptr, *F = nullptr;
@@ -571,7 +571,7 @@ int fmx_ngrams(const fmx_index *idx, const uint32_t *lengths, size_t k, const fm
   fmx_ngram *d_out = nullptr;
   if ((rc = hc.open())) return rc;
   const uint64_t outs = sizeof(fmx_ngram) * (uint64_t)cap + 16;
-  if ((rc = mstat_room(outs + ngrams_need(h, o), "fmx_ngrams"))) return rc;
+  if ((rc = device_room(outs + ngrams_need(h, o), "fmx_ngrams"))) return rc;
   DEV_ALLOC(hc.mem, d_out, outs, "ngram records");
   uint64_t off[FMX_NGRAMS_MAX_LEVELS + 1];
   if ((rc = ngrams_run(h, lengths, k, o, d_out, cap, hc.own.s, off, summary, spectrum, &g_ngrams_last))) return rc;

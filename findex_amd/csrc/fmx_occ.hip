@@ -300,9 +300,9 @@ int occ_run(const Index *h, const Corpus *c, const fmx_result *d_rec, uint64_t k
             int len_bits, unsigned long long *d_out_off, fmx_occurrence *d_out, uint64_t cap, hipStream_t st, uint64_t *total) {
   g_occ_last = OccInfo{};
   const uint64_t n = h->n;
-  int rc = mstat_room(24 * k + 4096, "fmx_occurrences");
+  int rc = device_room(24 * k + 4096, "fmx_occurrences");
   if (rc) return rc;
-  if ((rc = ensure_built(h, h->loc_mu, h->loc_ready, locate_prepare, st))) return rc;
+  if ((rc = ensure_built(h, h->loc, locate_prepare, st))) return rc;
   const CoMap map = c ? c->map() : CoMap{nullptr, nullptr, nullptr, 0, 0, 0};
   const int has_map = c ? 1 : 0;
   Events<5> ev;
@@ -359,7 +359,7 @@ int occ_run(const Index *h, const Corpus *c, const fmx_result *d_rec, uint64_t k
   const int gb = bits_for(n_groups);                 // groups 0 .. n_groups (n_groups: a dropped row)
   f.wide = f.pb + f.lb + gb > 64 ? 1 : 0;
   const uint64_t nt = radix_tiles(rows), hist_words = 256 * nt, parts = scan_partials(std::max<uint64_t>(rows, hist_words));
-  if ((rc = mstat_room(occ_row_bytes(mode, f.wide) * rows + 4 * hist_words + 4 * parts + 8192, "fmx_occurrences"))) {
+  if ((rc = device_room(occ_row_bytes(mode, f.wide) * rows + 4 * hist_words + 4 * parts + 8192, "fmx_occurrences"))) {
     done();
     return rc;
   }
@@ -503,7 +503,7 @@ int fmx_occurrences(const fmx_index *idx, const fmx_corpus *corpus, const fmx_re
   if ((rc = use_device(h))) return rc;
   HostCall hc;
   if ((rc = hc.open())) return rc;
-  if ((rc = mstat_room(24 * (uint64_t)k + 8 * ((uint64_t)n_groups + 1) + 32 * (uint64_t)cap + 4096, "fmx_occurrences"))) return rc;
+  if ((rc = device_room(24 * (uint64_t)k + 8 * ((uint64_t)n_groups + 1) + 32 * (uint64_t)cap + 4096, "fmx_occurrences"))) return rc;
   fmx_result *d_rec = nullptr;
   unsigned long long *d_off = nullptr;
   fmx_occurrence *d_out = nullptr;

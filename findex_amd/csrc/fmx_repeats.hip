@@ -200,8 +200,8 @@ static uint64_t repeats_bytes(const Index *h, bool stop) {
 }
 
 static bool lcp_built(const Index *h) {
-  std::lock_guard<std::mutex> lk(h->lcp_mu);
-  return h->lcp_ready;
+  std::lock_guard<std::mutex> lk(h->lcp.mu);
+  return h->lcp.ready;
 }
 
 // the free device bytes a call needs: its own, beside the LCP array when that is still to be built, or that build's
@@ -226,10 +226,10 @@ static int repeats_run(const Index *h, const uint32_t *min_len, size_t k, uint32
     }
     return FMX_OK;
   }
-  int rc = mstat_room(repeats_need(h, stop != 0), "fmx_repeats");
+  int rc = device_room(repeats_need(h, stop != 0), "fmx_repeats");
   if (rc) return rc;
-  if ((rc = ensure_built(h, h->lcp_mu, h->lcp_ready, lcp_prepare, st))) return rc;
-  const uint32_t *lcp = static_cast<const uint32_t *>(h->d_lcp);
+  if ((rc = ensure_built(h, h->lcp, lcp_prepare, st))) return rc;
+  const uint32_t *lcp = static_cast<const uint32_t *>(h->lcp.lcp);
   Events<6> ev;
   HIP_TRY(ev.create(), "hipEventCreate");
   DevMem mem;
@@ -366,7 +366,7 @@ int fmx_repeats(const fmx_index *idx, const uint32_t *min_len, size_t k, const f
   fmx_repeat_range *d_out = nullptr;
   if ((rc = hc.open())) return rc;
   const uint64_t outs = sizeof(fmx_repeat_range) * (uint64_t)cap + 16;
-  if ((rc = mstat_room(outs + repeats_need(h, stop != 0), "fmx_repeats"))) return rc;
+  if ((rc = device_room(outs + repeats_need(h, stop != 0), "fmx_repeats"))) return rc;
   DEV_ALLOC(hc.mem, d_out, outs, "repeat ranges");
   uint64_t off[FMX_REPEATS_MAX_LEVELS + 1];
   if ((rc = repeats_run(h, min_len, k, later, stop, d_out, cap, hc.own.s, off, summary, &g_repeats_last))) return rc;

@@ -342,13 +342,7 @@ int sufsort_bwt(const void *d_text, uint64_t len, void *d_bwt, void *d_sa_user, 
                 hipStream_t st, uint64_t extra) {
   const uint64_t n = len + 1;
   const uint64_t peak = sufsort_peak_bytes(len, d_sa_user != nullptr);
-  size_t free_b = 0, total_b = 0;
-  HIP_TRY(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
-  if (peak + extra > free_b) {
-    set_error("suffix sort of " + std::to_string(len) + " bytes needs " + std::to_string(peak + extra) +
-              " bytes of device memory, " + std::to_string((unsigned long long)free_b) + " are free");
-    return FMX_ERR_NOMEM;
-  }
+  if (const int rc = device_room(peak + extra, "suffix sort of " + std::to_string(len) + " bytes")) return rc;
   const char *log_path = std::getenv("FMX_SUFSORT_LOG");
   const auto t0 = std::chrono::steady_clock::now();
   DevMem mem;

@@ -188,6 +188,33 @@ def test_break_sets():
         hip.close()
 
 
+@ends_at_a_fault
+def test_dropping_locate_leaves_lines_and_extract_alone():
+    """The line table and the extract samples are built from the locate samples and keep nothing of them."""
+    T = occ_ref.word_text()
+    hip = H.from_text(T)
+    try:
+        hip.prepare(ktab=False, locate=True, extract=True, lines=True)
+        rows = np.arange(0, hip.n, 7, dtype=np.uint64)
+        pos = np.arange(len(T) + 1, dtype=np.uint64)
+        loc, lin, ext = hip.locate_info(), hip.lines_info(), hip.extract_info()
+        assert loc[1] > 0 and lin[3] > 0 and ext[1] > 0
+        sa, lines, text = hip.locate(rows), hip.line_of(pos), hip.extract_text(0, len(T))
+        assert text == T
+        hip.drop_tables(jump=False, frontier=False, locate=True)
+        assert hip.locate_info()[1] == 0
+        assert hip.lines_info() == lin and hip.extract_info() == ext
+        for g, w in zip(hip.line_of(pos), lines):
+            assert np.array_equal(g, w)
+        assert hip.extract_text(0, len(T)) == T and hip.extract_text(len(T) // 3, 100) == T[len(T) // 3:len(T) // 3 + 100]
+        assert hip.locate_info()[1] == 0                      # neither of them asked for the samples again
+        assert np.array_equal(hip.locate(rows), sa)           # the next locate call builds them
+        assert hip.locate_info()[:2] == loc[:2]
+        assert hip.lines_info() == lin and hip.extract_info() == ext
+    finally:
+        hip.close()
+
+
 # ---------------------------------------------------------------- 5. the corpus
 LONG = b"ab" + b"c" * 2996 + b"ab"
 DOCS = [b"", b"ab\ncab", b"ab\nxab\n", b"\n\n\n", b"x\x00ab\x01y\xffab\nab", b"ab\r\ncd ab\r\nend\r\n", LONG + b"\nab\n", b"", b"b",
