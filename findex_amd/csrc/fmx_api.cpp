@@ -319,7 +319,7 @@ static constexpr unsigned kDroppableTables = FMX_PREPARE_KTAB | FMX_PREPARE_JUMP
 
 // fmx_drop_tables and fmx_close: the budgeted tables (fmx_jump.hip), then the rest by the table above
 static int drop_derived(Index *h, unsigned what) {
-  const int rc = drop_tables(h, what & kDroppableTables);
+  const int rc = drop_tables(h, what);
   for (const DerivedFlag &d : kDerived)
     if (what & d.flag) d.drop(h);
   return rc;
@@ -329,7 +329,7 @@ static void destroy(Index *h) {
   if (!h) return;
   h->worker.reset();                  // finishes what was submitted, joins
   (void)hipSetDevice(h->device);
-  (void)drop_derived(h, kDroppableTables | derived_flags());
+  (void)drop_derived(h, kDroppableTables | FMX_PREPARE_SELECT | derived_flags());      // (the select directory goes only here)
   if (h->d_bv) (void)hipFree(h->d_bv);
   if (h->d_chk) (void)hipFree(h->d_chk);
   if (h->d_sup) (void)hipFree(h->d_sup);
@@ -337,9 +337,6 @@ static void destroy(Index *h) {
   if (h->d_cf) (void)hipFree(h->d_cf);
   if (h->d_slot) (void)hipFree(h->d_slot);
   if (h->d_counters) (void)hipFree(h->d_counters);
-  if (h->d_sel_dir) (void)hipFree(h->d_sel_dir);
-  if (h->d_sel_off) (void)hipFree(h->d_sel_off);
-  if (h->d_sel_shift) (void)hipFree(h->d_sel_shift);
   for (CallCtx *c : h->ctx_pool) free_ctx(c);
   delete h;
 }
@@ -688,7 +685,7 @@ int fmx_prepare(const fmx_index *idx, unsigned what) {
   if (what & FMX_PREPARE_SELECT) HIP_TRY(select_prepare(h, lease.c->stream), "select directory");
   if (what & FMX_PREPARE_JUMP) {
     h->prepared_rows.store(true, std::memory_order_relaxed);      // from now on searches use (and may build) the row tables
-    const uint4 *jt = nullptr;
+    JumpView jt;
     HIP_TRY(jump_get(h, lease.c->stream, &jt), "jump table");
     const unsigned long long *r3 = nullptr;
     HIP_TRY(row3_get(h, lease.c->stream, &r3), "three-step row table");      // beside the jump table, or instead of it
@@ -1680,16 +1677,17 @@ int fmx_stats(const fmx_index *idx, fmx_stats_t *out) {
     for (uint32_t sl = 0; sl < kCounterSlots; sl++)
       for (int j = 0; j < 12; j++) cnt[j] += slots[(size_t)sl * kCounterStride + j];
   }
+  const TablesSnapshot tab = tables_snapshot(h);      // (before h->mu: each table's own lock, one at a time)
   std::lock_guard<std::mutex> lk(h->mu);
   out->rank_queries = cnt[0];
   out->backward_steps = cnt[1];
   out->launches = h->launches;
   out->last_kernel_ms = h->last_kernel_ms;
-  out->index_bytes = h->index_bytes + h->sel_bytes + h->kt_bytes + h->jump_bytes + h->row1_bytes + h->row3_bytes;
+  out->index_bytes = h->index_bytes + tab.sel_held + tab.kmer_held + tab.jump_held + tab.row1_held + tab.row3_held;
   out->jump_lookups = cnt[10];
-  out->jump_bytes = h->jump_bytes;
+  out->jump_bytes = tab.jump_held;
   out->row_lookups = cnt[11];
-  out->row_bytes = h->row1_bytes + h->row3_bytes;
+  out->row_bytes = tab.row1_held + tab.row3_held;
   out->n_blocks = h->nblocks;
   out->n_symbols = h->nslots;
   out->block_bytes = h->layout == kLayoutBytes ? kByteBlock + 4 : kBlockBytes;
@@ -1702,11 +1700,11 @@ int fmx_stats(const fmx_index *idx, fmx_stats_t *out) {
   out->frontier_queue_reads = cnt[7];
   out->frontier_records = cnt[8];
   out->ktab_lookups = cnt[9];
-  out->ktab_k = h->kt.k;
+  out->ktab_k = tab.kmer_k;
   out->search_residency = h->search_residency.load();
-  out->jump_chars = h->jump_bytes ? h->jump_chars : 0;
+  out->jump_chars = tab.jump_jc;      // (0 while there is no J)
   out->build_ms = h->build_ms;
-  out->tables_build_ms = h->tables_ms;
+  out->tables_build_ms = h->tables_ms.load(std::memory_order_relaxed);
   out->tables_alloc_ms = (double)h->tables_alloc_us.load(std::memory_order_relaxed) * 1e-3;
   out->peak_table_build_bytes = h->peak_table_build_bytes.load(std::memory_order_relaxed);
   out->patterns_seen = h->patterns_seen.load(std::memory_order_relaxed);

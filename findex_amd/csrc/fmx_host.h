@@ -96,8 +96,9 @@ int policy_set(TablePolicy &p, const char *key, const char *value, const char **
 struct Side {
   std::mutex mu;
   bool ready = false;
-  uint64_t bytes = 0;                           // device bytes held
-  double build_ms = 0.0;                        // host time of the build
+  uint64_t bytes = 0;                           // device bytes held (the budgeted tables: the bytes fmx_stats reports for them)
+  double build_ms = 0.0;                        // host time of the build (the budgeted tables keep theirs in Index::tables_ms)
+  bool decided() { std::lock_guard<std::mutex> lk(mu); return ready; }      // `ready`, for a caller that only asks
 };
 template <class F>
 struct Derived : Side, F {
@@ -142,6 +143,37 @@ struct LineTable {
   void free_buffers() { (void)hipFree(brk); (void)hipFree(dir); }
 };
 
+// The five tables under the handle's table budget (TablePolicy::budget_*), records of the same shape.  For them `ready` means
+// DECIDED, not built: a table that is switched off, does not fit the budget or failed to build is decided and holds nothing,
+// and the question is not asked again until a drop (the four structures above are asked for again at every call until they
+// are built).  table_get builds them, table_publish counts them, table_drop frees them (below).
+struct KmerTable {                              // fmx_ktab.hip
+  KTab kt;                                      // what the kernels see (sigma is filled in when it is copied out)
+  void *all = nullptr, *dense = nullptr, *levels = nullptr;      // the levels in one allocation, KTab::dense, KTab::level_dev
+  void *ext = nullptr, *ovf = nullptr;          // level K+1 and its overflow lists (KTab::ext, ::ovf)
+  void free_buffers() { for (void *p : {all, dense, levels, ext, ovf}) if (p) (void)hipFree(p); }
+};
+struct JumpTable {                              // fmx_jump.hip: the row jump table J
+  void *tab = nullptr;
+  bool pairs = false;                           // the table holds pairs J[r] | J[LF^jc r] (32 bytes per row): up to 2 jc steps per request
+  uint32_t chars = 0;                           // characters (backward steps) one entry stands for: 8 .. 11
+  void free_buffers() { if (tab) (void)hipFree(tab); }
+};
+struct RowWords {                               // fmx_jump.hip: one 8-byte word per row (R1, R3)
+  void *words = nullptr;
+  void free_buffers() { if (words) (void)hipFree(words); }
+};
+struct SelectDir {                              // fmx_select.hip: the select directory for Psi
+  void *dir = nullptr, *off = nullptr, *shift = nullptr;
+  void free_buffers() { for (void *p : {dir, off, shift}) if (p) (void)hipFree(p); }
+};
+// The row jump table as a search sees it: copied under the record's lock, as KTab is
+struct JumpView {
+  const uint4 *tab = nullptr;                   // nullptr: the handle has none
+  bool pairs = false;
+  uint32_t chars = 0;
+};
+
 struct Index {
   uint64_t serial = 0;          // unique per open in this process: what a resident regex batch remembers of its index
   int device = 0;
@@ -172,32 +204,16 @@ struct Index {
   // host-call bookkeeping
   mutable std::mutex mu;
   mutable std::vector<CallCtx *> ctx_pool;      // idle call contexts (guarded by mu)
-  // k-mer jump table (fmx_ktab.hip), built on first use
-  mutable std::mutex kt_mu;
-  mutable bool kt_ready = false;
-  mutable KTab kt;
-  mutable void *d_ktab = nullptr, *d_kt_dense = nullptr, *d_kt_levels = nullptr;
-  mutable void *d_kt_ext = nullptr, *d_kt_ovf = nullptr;      // level K+1 and its overflow lists (KTab::ext, ::ovf)
-  mutable uint64_t kt_bytes = 0;                              // (all of the above)
-  // row jump table (fmx_jump.hip), built at the first literal search
-  mutable std::mutex jt_mu;
-  mutable bool jt_ready = false;
-  mutable void *d_jump = nullptr;
-  mutable uint64_t jump_bytes = 0;
-  mutable bool jump_pairs = false;              // the table holds pairs J[r] | J[LF^jc r] (32 bytes per row): up to 2 jc steps per request
-  mutable uint32_t jump_chars = 0;              // characters (backward steps) one entry of the row jump table stands for: 8 .. 11
-  // row table of the regex frontier (fmx_jump.hip): (BWT'[r], LF r) per row, 8 bytes; built at the first regex match
-  mutable std::mutex r1_mu;
-  mutable bool r1_ready = false;
-  mutable void *d_row1 = nullptr;
-  mutable uint64_t row1_bytes = 0;
-  // three-step row table (fmx_jump.hip): (BWT'[r], BWT'[LF r], BWT'[LF^2 r]; LF^3 r) per row, 8 bytes; built at the first
-  // literal search of a handle whose row jump table does not fit
-  mutable std::mutex r3_mu;
-  mutable bool r3_ready = false;
-  mutable void *d_row3 = nullptr;
-  mutable uint64_t row3_bytes = 0;
-  mutable double tables_ms = 0.0;             // host time spent building the k-mer table and the select directory (under their mutexes)
+  // the tables of the budget, each decided at first use: the k-mer jump table (at a search, or by fmx_prepare), the row jump
+  // table J and the three-step row table R3 = (BWT'[r], BWT'[LF r], BWT'[LF^2 r]; LF^3 r) (at the first literal search that
+  // finds them due), the regex frontier's row table R1 = (BWT'[r], LF r) (at the first regex match) and the select directory
+  // (at the first Psi / nextSubstr call).  LOCK ORDER: jump.mu before row3.mu (J is built from R3, inside J's build); no other
+  // two of these locks are ever held together, and none is held while Index::mu is taken.
+  mutable Derived<KmerTable> kmer;
+  mutable Derived<JumpTable> jump;
+  mutable Derived<RowWords> row1, row3;
+  mutable Derived<SelectDir> sel;
+  mutable std::atomic<double> tables_ms{0.0};   // host time spent deciding and building the five (TableSpan)
   // when the derived tables are built (fmx_jump.hip, tables_due): patterns searched so far, fmx_prepare seen
   // ticket areas of the literal search kernel (fmx_device.h, kTixAreas): which stream owns which.  A launch draws its last
   // batches from the area of the stream it is enqueued on; launches on ONE stream follow each other, so an area serves one
@@ -216,11 +232,6 @@ struct Index {
   mutable std::atomic<uint64_t> tables_alloc_us{0};             // of tables_ms: microseconds spent inside hipMalloc for the tables (the driver wiping memory somebody released: profiles/r05_alloc.md)
   mutable std::atomic<uint64_t> hbm_free_after_tables{0};       // hipMemGetInfo's free bytes right after the last table build (0: none built)
   mutable std::atomic<uint64_t> peak_table_build_bytes{0};      // most device memory a table build held at once (table + its scratch)
-  // select directory for Psi (fmx_select.hip), built on first use
-  mutable std::mutex sel_mu;
-  mutable bool sel_ready = false;
-  mutable void *d_sel_dir = nullptr, *d_sel_off = nullptr, *d_sel_shift = nullptr;
-  mutable uint64_t sel_bytes = 0;
   // what is built at first use outside the table budget (the search tables never see it): by fmx_prepare(FMX_PREPARE_LOCATE |
   // _LCP | _EXTRACT | _LINES), fmx_lines_prepare or the first call that needs it
   mutable Derived<LocateSamples> loc;           // fmx_locate.hip
@@ -258,14 +269,68 @@ bool tables_due(const Index *h, uint64_t k, bool small_table);      // fmx_jump.
 void note_table_build(const Index *h, uint64_t bytes_held);
 // Room for one more derived table of this handle: min(free HBM - margin, what the handle's budget leaves); 0 when hipMemGetInfo fails.
 uint64_t table_room(const Index *h, uint64_t margin);
-void tables_account(const Index *h, int64_t delta);
-hipError_t table_malloc(const Index *h, void **p, size_t bytes);    // hipMalloc for a derived table, its time added to tables_alloc_us                 // a table of |delta| bytes was built (+) or freed (-)
+void tables_account(const Index *h, int64_t delta);                 // a table of |delta| bytes was built (+) or freed (-)
+struct DevMem;
+hipError_t table_malloc(const Index *h, DevMem &mem, void **p, size_t bytes);      // mem.get for a derived table, its time added to tables_alloc_us
+// A budgeted table is there: `bytes` more on its record and on the handle's count, `peak_bytes` = what its build held at once
+void table_publish(const Index *h, Side &t, uint64_t bytes, uint64_t peak_bytes);
+// The host time of a table build, for Index::tables_ms.  Builds nest (J's contains R3's): only a thread's outermost span adds.
+struct TableSpan {
+  const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  TableSpan();
+  ~TableSpan();
+  TableSpan(const TableSpan &) = delete;
+  void add_to(const Index *h) const;
+};
+template <class F>
+void table_drop_locked(const Index *h, Derived<F> &t) {             // under t.mu: undecided again, nothing held
+  tables_account(h, -(int64_t)t.bytes);
+  t.free_locked();
+}
+template <class F>
+void table_drop(const Index *h, Derived<F> &t) {
+  std::lock_guard<std::mutex> lk(t.mu);
+  table_drop_locked(h, t);
+}
+// The one way to a budgeted table: under its lock, `body` decides and builds it unless it is decided or the caller only looks
+// (`build` false), then `out` copies what the caller needs.  body allocates from a DevMem of its own, keeps what it fills
+// the record with and calls table_publish last.  A body that fails leaves the record empty; `optional`: that is "no table,
+// no error" -- decided, the HIP last-error slot cleared -- else the error comes back and the next call asks again.
+template <class F, class Body, class Out>
+hipError_t table_get(const Index *h, Derived<F> &t, bool build, bool optional, Body body, Out out) {
+  std::lock_guard<std::mutex> lk(t.mu);
+  if (!t.ready && build) {
+    const TableSpan span;
+    const hipError_t e = body();
+    if (e != hipSuccess) {
+      table_drop_locked(h, t);
+      if (!optional) return e;
+      (void)hipGetLastError();
+    }
+    span.add_to(h);
+    t.ready = true;
+  }
+  out();
+  return hipSuccess;
+}
+// Grid of a table build whose lane groups (8 lanes in the bytes layout, 4 in the one-hot) each walk from one of `items` rows
+inline int row_walk_grid(const Index *h, uint64_t items, int threads) {
+  const uint64_t per_wg = (uint64_t)threads / (h->layout == kLayoutBytes ? 8 : 4);
+  return (int)std::min<uint64_t>((items + per_wg - 1) / per_wg, (uint64_t)h->cu_count * 8);
+}
+// What fmx_stats reports of the five tables, each read under its own lock (fmx_jump.hip)
+struct TablesSnapshot {
+  uint64_t kmer_held = 0, jump_held = 0, row1_held = 0, row3_held = 0, sel_held = 0;      // the records' bytes
+  uint32_t kmer_k = 0, jump_jc = 0;
+};
+TablesSnapshot tables_snapshot(const Index *h);
 hipError_t ktab_get(const Index *h, hipStream_t st, KTab *out, bool build = true);     // fmx_ktab.hip
 hipError_t select_prepare(const Index *h, hipStream_t st);          // fmx_select.hip: builds the select directory now
-hipError_t jump_get(const Index *h, hipStream_t st, const uint4 **out, bool build = true);   // fmx_jump.hip (nullptr: the handle has none)
+hipError_t jump_get(const Index *h, hipStream_t st, JumpView *out, bool build = true);   // fmx_jump.hip (tab == nullptr: the handle has none)
 hipError_t row1_get(const Index *h, hipStream_t st, const unsigned long long **out, bool build = true);   // fmx_jump.hip (nullptr: none)
 hipError_t row3_get(const Index *h, hipStream_t st, const unsigned long long **out, bool build = true);   // fmx_jump.hip (nullptr: none)
-int drop_tables(Index *h, unsigned what);       // fmx_jump.hip: frees the budgeted tables `what` names (FMX_PREPARE_KTAB | _JUMP | _FRONTIER)
+// fmx_jump.hip: frees the budgeted tables `what` names (FMX_PREPARE_KTAB | _JUMP | _FRONTIER; fmx_close adds _SELECT)
+int drop_tables(Index *h, unsigned what);
 
 // fmx_locate.hip: the locate samples.  locate_prepare builds them under loc.mu (allocates, synchronises `st`; an FMX_*
 // status with its message); launch_locate* need them built.  locate_write_sa: every row's SA as big-endian u32 into

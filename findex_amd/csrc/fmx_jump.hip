@@ -25,7 +25,9 @@
 // floor(jc / 3) lookups of R3 and jc mod 3 rank queries per entry, twice that per pair (k_jump_build).  (Round 3 built J by
 // doubling, J1 -> J2 -> J4 -> J8 through a second 16 n-byte buffer: 0.45 s of kernels and 3.5-4 s for two 64 GiB hipMallocs.)
 // A table that does not fit the free memory or the handle's budget is simply not there.  Not for fmx_open_block handles
-// (their skipped row and first-byte rule are not properties of an LF walk).
+// (their skipped row and first-byte rule are not properties of an LF walk).  J, R3 and R1 are the handle's records jump,
+// row3 and row1 (fmx_host.h), each decided once under its own lock by table_get; this unit also holds what all five
+// budgeted records share (table_malloc, table_publish, TableSpan, tables_snapshot, drop_tables).
 #include "fmx_device.h"
 #include "fmx_host.h"
 
@@ -152,19 +154,27 @@ static bool parse_u64(const char *v, uint64_t *out) {
 int policy_set(TablePolicy &p, const char *key, const char *value, const char **why) {
   auto is = [&](const char *k) { return std::strcmp(key, k) == 0; };
   auto val = [&](const char *v) { return std::strcmp(value, v) == 0; };
+  auto tri_state = [&](std::atomic<int> &a, const char *bad) {      // auto | on | off
+    if (val("auto")) a.store(-1);
+    else if (val("on")) a.store(1);
+    else if (val("off")) a.store(0);
+    else { *why = bad; return 2; }
+    return 0;
+  };
+  auto bounded = [&](std::atomic<int> &a, long lo, long hi, const char *bad) {      // an integer lo .. hi
+    char *end = nullptr;
+    const long v = std::strtol(value, &end, 10);
+    if (end == value || *end || v < lo || v > hi) { *why = bad; return 2; }
+    a.store((int)v);
+    return 0;
+  };
   if (is("ktab")) {
     if (val("auto")) p.ktab.store(1);
     else if (val("off")) p.ktab.store(0);
     else { *why = "ktab must be auto or off"; return 2; }
     return 0;
   }
-  if (is("ktab_ext")) {
-    if (val("auto")) p.ktab_ext.store(-1);
-    else if (val("on")) p.ktab_ext.store(1);
-    else if (val("off")) p.ktab_ext.store(0);
-    else { *why = "ktab_ext must be auto, on or off"; return 2; }
-    return 0;
-  }
+  if (is("ktab_ext")) return tri_state(p.ktab_ext, "ktab_ext must be auto, on or off");
   if (is("jump")) {
     if (val("auto")) p.jump_mode.store(7);
     else if (val("off")) p.jump_mode.store(0);
@@ -174,13 +184,7 @@ int policy_set(TablePolicy &p, const char *key, const char *value, const char **
     else { *why = "jump must be auto, rows, rows3, jumps or off"; return 2; }
     return 0;
   }
-  if (is("jump_pairs")) {
-    if (val("auto")) p.jump_pairs.store(-1);
-    else if (val("on")) p.jump_pairs.store(1);
-    else if (val("off")) p.jump_pairs.store(0);
-    else { *why = "jump_pairs must be auto, on or off"; return 2; }
-    return 0;
-  }
+  if (is("jump_pairs")) return tri_state(p.jump_pairs, "jump_pairs must be auto, on or off");
   if (is("search_lanes")) {
     if (val("auto")) p.search_lanes.store(-1);
     else if (val("quads")) p.search_lanes.store(0);
@@ -188,27 +192,9 @@ int policy_set(TablePolicy &p, const char *key, const char *value, const char **
     else { *why = "search_lanes must be auto, quads or pairs"; return 2; }
     return 0;
   }
-  if (is("locate_sample")) {
-    char *end = nullptr;
-    const long v = std::strtol(value, &end, 10);
-    if (end == value || *end || v < 1 || v > 4096) { *why = "locate_sample must be an integer 1 .. 4096"; return 2; }
-    p.locate_sample.store((int)v);
-    return 0;
-  }
-  if (is("extract_sample")) {
-    char *end = nullptr;
-    const long v = std::strtol(value, &end, 10);
-    if (end == value || *end || v < 1 || v > 4096) { *why = "extract_sample must be an integer 1 .. 4096"; return 2; }
-    p.extract_sample.store((int)v);
-    return 0;
-  }
-  if (is("lines_shift")) {
-    char *end = nullptr;
-    const long v = std::strtol(value, &end, 10);
-    if (end == value || *end || v < 4 || v > 16) { *why = "lines_shift must be an integer 4 .. 16"; return 2; }
-    p.lines_shift.store((int)v);
-    return 0;
-  }
+  if (is("locate_sample")) return bounded(p.locate_sample, 1, 4096, "locate_sample must be an integer 1 .. 4096");
+  if (is("extract_sample")) return bounded(p.extract_sample, 1, 4096, "extract_sample must be an integer 1 .. 4096");
+  if (is("lines_shift")) return bounded(p.lines_shift, 4, 16, "lines_shift must be an integer 4 .. 16");
   if (is("jump_chars")) {
     uint64_t v = 0;
     if (!parse_u64(value, &v) || v < 8 || v > 11) { *why = "jump_chars must be 8, 9, 10 or 11"; return 2; }
@@ -272,11 +258,25 @@ void tables_account(const Index *h, int64_t delta) {
   if (delta > 0 && hipMemGetInfo(&free_b, &total_b) == hipSuccess) h->hbm_free_after_tables.store(free_b, std::memory_order_relaxed);
   else if (delta > 0) (void)hipGetLastError();
 }
-hipError_t table_malloc(const Index *h, void **p, size_t bytes) {
+hipError_t table_malloc(const Index *h, DevMem &mem, void **p, size_t bytes) {
   const auto t0 = std::chrono::steady_clock::now();
-  const hipError_t e = hipMalloc(p, bytes);
+  const hipError_t e = mem.get(p, bytes);
   h->tables_alloc_us.fetch_add((uint64_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(), std::memory_order_relaxed);
   return e;
+}
+void table_publish(const Index *h, Side &t, uint64_t bytes, uint64_t peak_bytes) {
+  t.bytes += bytes;
+  note_table_build(h, peak_bytes);
+  tables_account(h, (int64_t)bytes);
+}
+static thread_local int t_table_spans = 0;      // TableSpans open on this thread
+TableSpan::TableSpan() { t_table_spans++; }
+TableSpan::~TableSpan() { t_table_spans--; }
+void TableSpan::add_to(const Index *h) const {
+  if (t_table_spans != 1) return;
+  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  double cur = h->tables_ms.load(std::memory_order_relaxed);
+  while (!h->tables_ms.compare_exchange_weak(cur, cur + ms, std::memory_order_relaxed)) {}
 }
 uint64_t table_room(const Index *h, uint64_t margin) {
   size_t free_b = 0, total_b = 0;
@@ -290,65 +290,50 @@ uint64_t table_room(const Index *h, uint64_t margin) {
   return room;
 }
 
-// 8 n bytes of row words by `launch`; leaves *slot null when the table is not wanted or does not fit (no error).
-template <class Launch>
-static void build_row_words(const Index *h, hipStream_t st, uint64_t margin, void **slot, uint64_t *slot_bytes, Launch launch) {
-  const uint64_t bytes = h->n * 8;
-  if (bytes > table_room(h, margin)) return;
-  void *p = nullptr;
-  hipError_t e = table_malloc(h, &p, bytes);
-  if (e == hipSuccess) {
-    const uint64_t per_wg = kJThreads / (h->layout == kLayoutBytes ? 8 : 4);
-    const int grid = (int)std::min<uint64_t>((h->n + per_wg - 1) / per_wg, (uint64_t)h->cu_count * 8);
-    launch(grid, static_cast<unsigned long long *>(p));
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) { *slot = p; *slot_bytes = bytes; note_table_build(h, bytes); tables_account(h, (int64_t)bytes); }
-    else (void)hipFree(p);
-  }
-  if (e != hipSuccess) (void)hipGetLastError();
-}
-
 static bool rows_eligible(const Index *h) { return !h->block_mode && h->n >= 2 && h->nslots >= 1; }
+
+// 8 n bytes of row words by `launch` into t, if `wanted`, eligible and inside the room `margin` leaves
+template <class Launch>
+static hipError_t row_words_get(const Index *h, hipStream_t st, Derived<RowWords> &t, bool build, bool wanted, uint64_t margin,
+                                Launch launch, const unsigned long long **out) {
+  return table_get(h, t, build, true, [&]() -> hipError_t {
+    const uint64_t bytes = h->n * 8;
+    if (!wanted || !rows_eligible(h) || bytes > table_room(h, margin)) return hipSuccess;
+    DevMem mem;
+    void *p = nullptr;
+    hipError_t e = table_malloc(h, mem, &p, bytes);
+    if (e != hipSuccess) return e;
+    launch(row_walk_grid(h, h->n, kJThreads), static_cast<unsigned long long *>(p));
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess) return e;
+    mem.keep(p);
+    t.words = p;
+    table_publish(h, t, bytes, bytes);
+    return hipSuccess;
+  }, [&] { *out = static_cast<const unsigned long long *>(t.words); });
+}
 
 // The three-step row table of a handle (nullptr: none yet / none at all): 8 n bytes.
 hipError_t row3_get(const Index *h, hipStream_t st, const unsigned long long **out, bool build) {
-  std::lock_guard<std::mutex> lk(h->r3_mu);
-  if (!h->r3_ready && build) {
-    const auto t0 = std::chrono::steady_clock::now();
-    if ((h->policy.jump_mode.load(std::memory_order_relaxed) & 4) && rows_eligible(h))
-      build_row_words(h, st, 8ull << 30, &h->d_row3, &h->row3_bytes, [&](int grid, unsigned long long *p) {
+  const bool wanted = (h->policy.jump_mode.load(std::memory_order_relaxed) & 4) != 0;
+  return row_words_get(h, st, h->row3, build, wanted, 8ull << 30, [&](int grid, unsigned long long *p) {
 #define CALL(W, L) k_row3_init<W, L><<<grid, kJThreads, 0, st>>>(h->dev, p)
-        FMX_LAYOUT_DISPATCH(h, CALL);
+    FMX_LAYOUT_DISPATCH(h, CALL);
 #undef CALL
-      });
-    h->tables_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    h->r3_ready = true;
-  }
-  *out = static_cast<const unsigned long long *>(h->d_row3);
-  return hipSuccess;
+  }, out);
 }
 
 // The frontier's row table of a handle (nullptr: none), built at the first regex match: 8 n bytes.
 hipError_t row1_get(const Index *h, hipStream_t st, const unsigned long long **out, bool build) {
-  std::lock_guard<std::mutex> lk(h->r1_mu);
-  if (!h->r1_ready && build) {
-    const auto t0 = std::chrono::steady_clock::now();
-    static const int forced = getenv("FMX_ROW1") ? atoi(getenv("FMX_ROW1")) : -1;      // 0 = off
-    if (forced != 0 && (h->policy.jump_mode.load(std::memory_order_relaxed) & 1) && rows_eligible(h))
-      build_row_words(h, st, 4ull << 30, &h->d_row1, &h->row1_bytes, [&](int grid, unsigned long long *p) {
+  static const int forced = getenv("FMX_ROW1") ? atoi(getenv("FMX_ROW1")) : -1;      // 0 = off
+  const bool wanted = forced != 0 && (h->policy.jump_mode.load(std::memory_order_relaxed) & 1);
+  return row_words_get(h, st, h->row1, build, wanted, 4ull << 30, [&](int grid, unsigned long long *p) {
 #define CALL(W, L) k_row1_init<W, L><<<grid, kJThreads, 0, st>>>(h->dev, p)
-        FMX_LAYOUT_DISPATCH(h, CALL);
+    FMX_LAYOUT_DISPATCH(h, CALL);
 #undef CALL
-      });
-    h->tables_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    h->r1_ready = true;
-  }
-  *out = static_cast<const unsigned long long *>(h->d_row1);
-  return hipSuccess;
+  }, out);
 }
 
-// Called under h->jt_mu by jump_get.  Leaves h->d_jump null when the table is not wanted or does not fit.
+// The body of jump_get, under jump.mu.  Leaves the record empty when the table is not wanted or does not fit.
 static hipError_t build_jump(const Index *h, hipStream_t st) {
   static const int forced = getenv("FMX_JUMP") ? atoi(getenv("FMX_JUMP")) : -1;      // 0 = off, 1 = whenever it fits
   if (forced == 0 || (forced < 0 && !(h->policy.jump_mode.load(std::memory_order_relaxed) & 2))) return hipSuccess;
@@ -369,83 +354,65 @@ static hipError_t build_jump(const Index *h, hipStream_t st) {
   const bool pairs = want_pairs && 2 * bytes <= room;
   if (pairs) bytes *= 2;
   if (bytes > room && !(forced == 1 && bytes <= table_room(h, 1ull << 28))) return hipSuccess;
-  hipError_t e = hipSuccess;
   static const bool trace = getenv("FMX_TRACE") != nullptr;
   const auto t0 = std::chrono::steady_clock::now();
   auto mark = [&](const char *what) {
     if (trace) { (void)hipStreamSynchronize(st); fprintf(stderr, "[fmx] jump table %-12s +%.1f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); }
   };
   const uint32_t jc = (uint32_t)std::min(11, std::max(8, h->policy.jump_chars.load(std::memory_order_relaxed)));
+  DevMem mem;
   void *a = nullptr;
-  e = table_malloc(h, &a, bytes);
-  if (e != hipSuccess) { (void)hipGetLastError(); return hipSuccess; }      // no table, no error
+  hipError_t e = table_malloc(h, mem, &a, bytes);
+  if (e != hipSuccess) return e;
   mark("allocated");
-  {
-    const uint64_t per_wg = kJThreads / (h->layout == kLayoutBytes ? 8 : 4);
-    const int grid = (int)std::min<uint64_t>((h->n + per_wg - 1) / per_wg, (uint64_t)h->cu_count * 8);
-#define CALL(W, L) k_jump_build<W, L><<<grid, kJThreads, 0, st>>>(h->dev, r3, (uint4 *)a, jc, pairs ? 1u : 0u)
-    FMX_LAYOUT_DISPATCH(h, CALL);
+#define CALL(W, L) k_jump_build<W, L><<<row_walk_grid(h, h->n, kJThreads), kJThreads, 0, st>>>(h->dev, r3, (uint4 *)a, jc, pairs ? 1u : 0u)
+  FMX_LAYOUT_DISPATCH(h, CALL);
 #undef CALL
-    e = hipGetLastError();
-  }
+  e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   mark(r3 ? "built (R3)" : "built (walk)");
-  if (e != hipSuccess) { (void)hipFree(a); return e; }
-  h->d_jump = a;
-  h->jump_bytes = bytes;
-  h->jump_pairs = pairs;
-  h->jump_chars = jc;
-  note_table_build(h, bytes);
-  tables_account(h, (int64_t)bytes);
+  if (e != hipSuccess) return e;
+  mem.keep(a);
+  h->jump.tab = a;
+  h->jump.pairs = pairs;
+  h->jump.chars = jc;
+  table_publish(h, h->jump, bytes, bytes);
   return hipSuccess;
 }
 
-// The jump table of a handle (nullptr: none yet / none at all).
-hipError_t jump_get(const Index *h, hipStream_t st, const uint4 **out, bool build) {
-  std::lock_guard<std::mutex> lk(h->jt_mu);
-  if (!h->jt_ready && build) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const double ms_before = h->tables_ms;
-    const hipError_t e = build_jump(h, st);
-    if (e != hipSuccess) { (void)hipGetLastError(); h->d_jump = nullptr; h->jump_bytes = 0; }      // searches walk every step
-    // (row3_get, called inside build_jump, has added its share already: the whole span counts once)
-    h->tables_ms = ms_before + std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    h->jt_ready = true;
-  }
-  *out = static_cast<const uint4 *>(h->d_jump);
-  return hipSuccess;
+// The jump table of a handle (tab == nullptr: none yet / none at all; searches then walk every step).
+hipError_t jump_get(const Index *h, hipStream_t st, JumpView *out, bool build) {
+  Derived<JumpTable> &t = h->jump;
+  return table_get(h, t, build, true, [&] { return build_jump(h, st); },
+                   [&] { *out = JumpView{static_cast<const uint4 *>(t.tab), t.pairs, t.chars}; });
 }
 
-// fmx_drop_tables: frees the tables of the budget (the caller guarantees that no call is using the handle).  They are built
-// again by fmx_prepare or when the threshold is met anew.
+TablesSnapshot tables_snapshot(const Index *h) {
+  TablesSnapshot s;
+  auto under = [](Side &t, auto read) { std::lock_guard<std::mutex> lk(t.mu); read(); };
+  under(h->kmer, [&] { s.kmer_held = h->kmer.bytes; s.kmer_k = h->kmer.kt.k; });
+  under(h->jump, [&] { s.jump_held = h->jump.bytes; s.jump_jc = h->jump.chars; });
+  under(h->row1, [&] { s.row1_held = h->row1.bytes; });
+  under(h->row3, [&] { s.row3_held = h->row3.bytes; });
+  under(h->sel, [&] { s.sel_held = h->sel.bytes; });
+  return s;
+}
+
+// fmx_drop_tables and fmx_close: frees the tables of the budget by their flags, in this order (the caller guarantees that no
+// call is using the handle).  They are built again by fmx_prepare or when the threshold is met anew.
+static const struct BudgetedFlag {
+  unsigned flags;
+  void (*drop)(Index *);
+} kBudgeted[] = {
+    {FMX_PREPARE_KTAB, [](Index *h) { table_drop(h, h->kmer); h->prepared_ktab.store(false, std::memory_order_relaxed); }},
+    {FMX_PREPARE_JUMP, [](Index *h) { table_drop(h, h->jump); table_drop(h, h->row3); h->prepared_rows.store(false, std::memory_order_relaxed); }},
+    {FMX_PREPARE_KTAB | FMX_PREPARE_JUMP, [](Index *h) { h->patterns_seen.store(0, std::memory_order_relaxed); }},
+    {FMX_PREPARE_FRONTIER, [](Index *h) { table_drop(h, h->row1); }},
+    {FMX_PREPARE_SELECT, [](Index *h) { table_drop(h, h->sel); }},      // (fmx_close only: fmx_drop_tables does not take the flag)
+};
 int drop_tables(Index *h, unsigned what) {
-  if (what & FMX_PREPARE_KTAB) {
-    std::lock_guard<std::mutex> lk(h->kt_mu);
-    if (h->d_ktab) (void)hipFree(h->d_ktab);
-    if (h->d_kt_dense) (void)hipFree(h->d_kt_dense);
-    if (h->d_kt_levels) (void)hipFree(h->d_kt_levels);
-    if (h->d_kt_ext) (void)hipFree(h->d_kt_ext);
-    if (h->d_kt_ovf) (void)hipFree(h->d_kt_ovf);
-    h->d_ktab = h->d_kt_dense = h->d_kt_levels = h->d_kt_ext = h->d_kt_ovf = nullptr;
-    tables_account(h, -(int64_t)h->kt_bytes);
-    h->kt_bytes = 0;
-    h->kt = KTab{};
-    h->kt.sigma = h->nslots;
-    h->kt_ready = false;
-    h->prepared_ktab.store(false, std::memory_order_relaxed);
-  }
-  if (what & FMX_PREPARE_JUMP) {
-    { std::lock_guard<std::mutex> lk(h->jt_mu); if (h->d_jump) (void)hipFree(h->d_jump); tables_account(h, -(int64_t)h->jump_bytes); h->d_jump = nullptr; h->jump_bytes = 0; h->jump_pairs = false; h->jt_ready = false; }
-    { std::lock_guard<std::mutex> lk(h->r3_mu); if (h->d_row3) (void)hipFree(h->d_row3); tables_account(h, -(int64_t)h->row3_bytes); h->d_row3 = nullptr; h->row3_bytes = 0; h->r3_ready = false; }
-    h->prepared_rows.store(false, std::memory_order_relaxed);
-  }
-  if (what & (FMX_PREPARE_KTAB | FMX_PREPARE_JUMP)) h->patterns_seen.store(0, std::memory_order_relaxed);
-  if (what & FMX_PREPARE_FRONTIER) {
-    std::lock_guard<std::mutex> lk(h->r1_mu);
-    if (h->d_row1) (void)hipFree(h->d_row1);
-    tables_account(h, -(int64_t)h->row1_bytes);
-    h->d_row1 = nullptr; h->row1_bytes = 0; h->r1_ready = false;
-  }
+  for (const BudgetedFlag &b : kBudgeted)
+    if (what & b.flags) b.drop(h);
   return 0;
 }
 

@@ -160,7 +160,7 @@ __global__ __launch_bounds__(kKtThreads) void k_kext_fill(DevIndex ix, const uin
 // It serves the kernels with a row jump table of pairs (k_search4<.., KX>) and is built where they will run ("auto": a
 // one-hot index for which "jump_pairs" asks for pairs, when the 32-byte entries, the 8 n bytes of the three-step table and
 // the 32 n bytes of the pairs all fit beside each other and the margins -- it never takes the pairs' place), or whenever it
-// fits ("on").  Leaves h->kt.ext null when it is not built; a failure is no error (the kernels without the level serve).
+// fits ("on").  Leaves the record's kt.ext null when it is not built; a failure is no error (the kernels without the level serve).
 static void build_kext(const Index *h, hipStream_t st, uint32_t KE, const uint8_t *d_sym, const uint8_t *d_dense) {
   const int mode = h->policy.ktab_ext.load(std::memory_order_relaxed);
   if (mode == 0 || KE == 0 || h->layout != kLayoutOneHot || h->block_mode || h->n > (1ull << 32)) return;      // (the kernels that use it are not WIDE)
@@ -176,73 +176,62 @@ static void build_kext(const Index *h, hipStream_t st, uint32_t KE, const uint8_
   } else if (ext_bytes + ovf_reserve > table_room(h, 1ull << 30)) {
     return;
   }
-  const uint64_t per_wg = kKtThreads / 4;
-  auto grid_for = [&](uint64_t items) { return (int)std::min<uint64_t>((items + per_wg - 1) / per_wg, (uint64_t)h->cu_count * 8); };
   uint64_t tmp_entries = 0;
   for (uint64_t j = 1, c = sigma; j < KE; j++, c *= sigma) tmp_entries += c;      // levels 1 .. KE-1, every step taken
-  void *d_ext = nullptr, *d_ovf = nullptr, *d_tmp = nullptr, *d_units = nullptr;
-  hipError_t e = table_malloc(h, &d_ext, ext_bytes);
-  if (e == hipSuccess) e = hipMalloc(&d_tmp, std::max<uint64_t>(tmp_entries, 1) * 16 + 256);
-  if (e == hipSuccess) { d_units = static_cast<uint8_t *>(d_tmp) + std::max<uint64_t>(tmp_entries, 1) * 16; e = hipMemsetAsync(d_units, 0, 16, st); }
-  uint64_t off = 0, n_prev = 1;
-  const uint4 *prev = nullptr;
-  for (uint32_t lv = 0; lv + 1 < KE && e == hipSuccess; lv++) {
-    uint4 *next = static_cast<uint4 *>(d_tmp) + off;
-    const uint64_t n_next = n_prev * sigma;
-    const int grid = grid_for(n_next);
-#define CALL(W, L) k_ktab_level<W, L><<<grid, kKtThreads, 0, st>>>(h->dev, prev, next, n_prev, sigma, lv, d_sym, 1u)
+  DevMem mem;
+  void *d_ext = nullptr, *d_ovf = nullptr, *d_tmp = nullptr;
+  uint64_t ovf_bytes = 0;
+  const hipError_t built = [&]() -> hipError_t {
+    hipError_t e = table_malloc(h, mem, &d_ext, ext_bytes);
+    if (e != hipSuccess || (e = mem.get(&d_tmp, std::max<uint64_t>(tmp_entries, 1) * 16 + 256)) != hipSuccess) return e;
+    void *d_units = static_cast<uint8_t *>(d_tmp) + std::max<uint64_t>(tmp_entries, 1) * 16;
+    if ((e = hipMemsetAsync(d_units, 0, 16, st)) != hipSuccess) return e;
+    uint64_t off = 0, n_prev = 1;
+    const uint4 *prev = nullptr;
+    for (uint32_t lv = 0; lv + 1 < KE; lv++) {
+      uint4 *next = static_cast<uint4 *>(d_tmp) + off;
+      const uint64_t n_next = n_prev * sigma;
+#define CALL(W, L) k_ktab_level<W, L><<<row_walk_grid(h, n_next, kKtThreads), kKtThreads, 0, st>>>(h->dev, prev, next, n_prev, sigma, lv, d_sym, 1u)
+      FMX_LAYOUT_DISPATCH(h, CALL);
+#undef CALL
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+      prev = next;
+      off += n_next;
+      n_prev = n_next;
+    }
+#define CALL(W, L) k_kext_head<W, L><<<row_walk_grid(h, codes, kKtThreads), kKtThreads, 0, st>>>(h->dev, prev, static_cast<uint4 *>(d_ext), n_prev, sigma, d_sym, static_cast<unsigned long long *>(d_units))
     FMX_LAYOUT_DISPATCH(h, CALL);
 #undef CALL
-    e = hipGetLastError();
-    prev = next;
-    off += n_next;
-    n_prev = n_next;
-  }
-  if (e == hipSuccess) {
-    const int grid = grid_for(codes);
-#define CALL(W, L) k_kext_head<W, L><<<grid, kKtThreads, 0, st>>>(h->dev, prev, static_cast<uint4 *>(d_ext), n_prev, sigma, d_sym, static_cast<unsigned long long *>(d_units))
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    unsigned long long units[2] = {0, 0};
+    if ((e = hipMemcpyAsync(units, d_units, 16, hipMemcpyDeviceToHost, st)) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess) return e;
+    if (units[1] > kExtMaxList) return hipErrorNotSupported;      // (not an error: no level)
+    ovf_bytes = std::max<uint64_t>(units[0], 1) * 16;
+    if (ovf_bytes > table_room(h, mode < 0 ? 40 * h->n + (8ull << 30) : (1ull << 30))) return hipErrorOutOfMemory;      // (a skewed text)
+    if ((e = table_malloc(h, mem, &d_ovf, ovf_bytes)) != hipSuccess || (e = hipMemsetAsync(d_ovf, 0xFF, ovf_bytes, st)) != hipSuccess) return e;
+#define CALL(W, L) k_kext_fill<W, L><<<row_walk_grid(h, h->n, kKtThreads), kKtThreads, 0, st>>>(h->dev, static_cast<const uint4 *>(d_ext), static_cast<uint8_t *>(d_ext), static_cast<uint8_t *>(d_ovf), d_dense, sigma, KE)
     FMX_LAYOUT_DISPATCH(h, CALL);
 #undef CALL
-    e = hipGetLastError();
-  }
-  unsigned long long units[2] = {0, 0};
-  if (e == hipSuccess) e = hipMemcpyAsync(units, d_units, 16, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e == hipSuccess && units[1] > kExtMaxList) e = hipErrorNotSupported;      // (not an error: no level)
-  const uint64_t ovf_bytes = std::max<uint64_t>(units[0], 1) * 16;
-  if (e == hipSuccess && ovf_bytes > table_room(h, mode < 0 ? 40 * h->n + (8ull << 30) : (1ull << 30))) e = hipErrorOutOfMemory;      // (a skewed text)
-  if (e == hipSuccess) e = table_malloc(h, &d_ovf, ovf_bytes);
-  if (e == hipSuccess) e = hipMemsetAsync(d_ovf, 0xFF, ovf_bytes, st);
-  if (e == hipSuccess) {
-    const int grid = grid_for(h->n);
-#define CALL(W, L) k_kext_fill<W, L><<<grid, kKtThreads, 0, st>>>(h->dev, static_cast<const uint4 *>(d_ext), static_cast<uint8_t *>(d_ext), static_cast<uint8_t *>(d_ovf), d_dense, sigma, KE)
-    FMX_LAYOUT_DISPATCH(h, CALL);
-#undef CALL
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (d_tmp) (void)hipFree(d_tmp);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    if (d_ext) (void)hipFree(d_ext);
-    if (d_ovf) (void)hipFree(d_ovf);
-    return;
-  }
-  h->d_kt_ext = d_ext;
-  h->d_kt_ovf = d_ovf;
-  h->kt.ext = static_cast<const uint4 *>(d_ext);
-  h->kt.ovf = static_cast<const uint4 *>(d_ovf);
-  h->kt.ext_k = KE;
-  h->kt_bytes += ext_bytes + ovf_bytes;
-  note_table_build(h, ext_bytes + ovf_bytes + tmp_entries * 16);
-  tables_account(h, (int64_t)(ext_bytes + ovf_bytes));
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    return hipStreamSynchronize(st);
+  }();
+  if (built != hipSuccess) { (void)hipGetLastError(); return; }
+  Derived<KmerTable> &t = h->kmer;
+  mem.free_now(d_tmp);
+  mem.keep(d_ext);
+  mem.keep(d_ovf);
+  t.ext = d_ext;
+  t.ovf = d_ovf;
+  t.kt.ext = static_cast<const uint4 *>(d_ext);
+  t.kt.ovf = static_cast<const uint4 *>(d_ovf);
+  t.kt.ext_k = KE;
+  table_publish(h, t, ext_bytes + ovf_bytes, ext_bytes + ovf_bytes + tmp_entries * 16);
 }
 
-// Chooses K, allocates and fills the levels.  Called under h->kt_mu by ktab_get.
+// The body of ktab_get, under kmer.mu: chooses K, allocates and fills the levels, then level K+1.
 static hipError_t build_ktab(const Index *h, hipStream_t st) {
+  Derived<KmerTable> &t = h->kmer;
   const uint32_t sigma = h->nslots;
-  h->kt.k = 0;
-  h->kt.sigma = sigma;
   static const int forced = getenv("FMX_KTAB") ? atoi(getenv("FMX_KTAB")) : -1;      // 0 = off, k > 0 = exactly k levels
   if (sigma < 2 || forced == 0 || !h->policy.ktab.load(std::memory_order_relaxed)) return hipSuccess;
   size_t free_b = 0, total_b = 0;
@@ -270,79 +259,54 @@ static hipError_t build_ktab(const Index *h, hipStream_t st) {
     dense[c] = 0xFF;
     if (h->slot[c] < kSlotEof) { dense[c] = (uint8_t)h->slot[c]; sym_of[h->slot[c]] = (uint8_t)c; }    // slots number the present symbols densely
   }
-  void *d_all = nullptr, *d_dense = nullptr, *d_sym = nullptr;
-  e = table_malloc(h, &d_all, all * 16);
-  if (e == hipSuccess) e = hipMalloc(&d_dense, 256);
-  if (e == hipSuccess) e = hipMalloc(&d_sym, 256);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_dense, dense, 256, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_sym, sym_of, 256, hipMemcpyHostToDevice, st);
+  DevMem mem;
+  void *d_all = nullptr, *d_dense = nullptr, *d_sym = nullptr, *d_levels = nullptr;
+  if ((e = table_malloc(h, mem, &d_all, all * 16)) != hipSuccess || (e = mem.get(&d_dense, 256)) != hipSuccess ||
+      (e = mem.get(&d_sym, 256)) != hipSuccess ||
+      (e = hipMemcpyAsync(d_dense, dense, 256, hipMemcpyHostToDevice, st)) != hipSuccess ||
+      (e = hipMemcpyAsync(d_sym, sym_of, 256, hipMemcpyHostToDevice, st)) != hipSuccess)
+    return e;
   uint64_t off = 0, n_prev = 1;
   const uint4 *prev = nullptr;
-  for (uint32_t lv = 0; lv < k && e == hipSuccess; lv++) {
+  for (uint32_t lv = 0; lv < k; lv++) {
     uint4 *next = static_cast<uint4 *>(d_all) + off;
     const uint64_t n_next = n_prev * sigma;
-    const uint64_t per_wg = kKtThreads / (h->layout == kLayoutBytes ? 8 : 4);
-    const int grid = (int)std::min<uint64_t>((n_next + per_wg - 1) / per_wg, (uint64_t)h->cu_count * 8);
-#define CALL(W, L) k_ktab_level<W, L><<<grid, kKtThreads, 0, st>>>(h->dev, prev, next, n_prev, sigma, lv, (const uint8_t *)d_sym, 0u)
+#define CALL(W, L) k_ktab_level<W, L><<<row_walk_grid(h, n_next, kKtThreads), kKtThreads, 0, st>>>(h->dev, prev, next, n_prev, sigma, lv, (const uint8_t *)d_sym, 0u)
     FMX_LAYOUT_DISPATCH(h, CALL);
 #undef CALL
-    e = hipGetLastError();
-    h->kt.level[lv] = next;
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    t.kt.level[lv] = next;
     prev = next;
     off += n_next;
     n_prev = n_next;
   }
-  void *d_levels = nullptr;
-  if (e == hipSuccess) e = hipMalloc(&d_levels, sizeof h->kt.level);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_levels, h->kt.level, sizeof h->kt.level, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);      // `dense` / `sym_of` go out of scope
-  if (e != hipSuccess) {
-    if (d_sym) (void)hipFree(d_sym);
-    if (d_all) (void)hipFree(d_all);
-    if (d_dense) (void)hipFree(d_dense);
-    if (d_levels) (void)hipFree(d_levels);
-    h->kt.k = 0;
+  if ((e = mem.get(&d_levels, sizeof t.kt.level)) != hipSuccess ||
+      (e = hipMemcpyAsync(d_levels, t.kt.level, sizeof t.kt.level, hipMemcpyHostToDevice, st)) != hipSuccess ||
+      (e = hipStreamSynchronize(st)) != hipSuccess)      // `dense` / `sym_of` go out of scope
     return e;
-  }
-  h->d_ktab = d_all;
-  h->d_kt_dense = d_dense;
-  h->d_kt_levels = d_levels;
-  h->kt.level_dev = static_cast<const uint4 *const *>(d_levels);
-  h->kt.k = k;
-  h->kt.tab = h->kt.level[k - 1];
-  h->kt.dense = static_cast<const uint8_t *>(d_dense);
-  h->kt_bytes = all * 16 + 256;
-  note_table_build(h, h->kt_bytes);
-  tables_account(h, (int64_t)h->kt_bytes);
-  // level K+1 over the K-mers of the level a search uses (plan_of: 12, 8 or 4)
+  for (void *p : {d_all, d_dense, d_levels}) mem.keep(p);
+  t.all = d_all;
+  t.dense = d_dense;
+  t.levels = d_levels;
+  t.kt.level_dev = static_cast<const uint4 *const *>(d_levels);
+  t.kt.k = k;
+  t.kt.tab = t.kt.level[k - 1];
+  t.kt.dense = static_cast<const uint8_t *>(d_dense);
+  table_publish(h, t, all * 16 + 256, all * 16 + 256);
+  // level K+1 over the K-mers of the level a search uses (plan_of: 12, 8 or 4); d_sym goes with `mem` (build_kext has
+  // synchronised the stream)
   build_kext(h, st, k >= 12 ? 12u : k >= 8 ? 8u : k >= 4 ? 4u : 0u, static_cast<const uint8_t *>(d_sym), static_cast<const uint8_t *>(d_dense));
-  (void)hipFree(d_sym);      // (build_kext has synchronised the stream)
   return hipSuccess;
 }
 
-// The table of a handle (k == 0: none), built on first use.
+// The table of a handle (k == 0: none, or not yet: the search walks its first steps on the rank dictionary), built on first
+// use.  A build that fails (out of memory for the table, usually) is no table: every step on the rank dictionary is always
+// correct, and the failure must not stick to the handle -- or to the HIP runtime's last-error slot.
 hipError_t ktab_get(const Index *h, hipStream_t st, KTab *out, bool build) {
-  std::lock_guard<std::mutex> lk(h->kt_mu);
-  if (!h->kt_ready && !build) {      // not yet: this search walks its first steps on the rank dictionary
-    *out = KTab{};
+  return table_get(h, h->kmer, build, true, [&] { return build_ktab(h, st); }, [&] {
+    *out = h->kmer.kt;
     out->sigma = h->nslots;
-    return hipSuccess;
-  }
-  if (!h->kt_ready) {
-    const auto t0 = std::chrono::steady_clock::now();
-    const hipError_t e = build_ktab(h, st);
-    if (e != hipSuccess) {
-      // No table (out of memory for it, usually): searches walk every step on the rank dictionary, which is always
-      // correct.  The failure must not stick to the handle -- or to the HIP runtime's last-error slot.
-      (void)hipGetLastError();
-      h->kt = KTab{};
-      h->kt.sigma = h->nslots;
-    }
-    h->tables_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    h->kt_ready = true;
-  }
-  *out = h->kt;
-  return hipSuccess;
+  });
 }
 
 }  // namespace fmx

@@ -95,7 +95,7 @@ constexpr uint32_t kPoolRounds = 2;
 // The handle's tables as a search finds them.
 struct SearchTables {
   KTab kt;
-  const uint4 *jt = nullptr;                       // the row jump table
+  JumpView jt;                                     // the row jump table
   const unsigned long long *r3 = nullptr;          // the three-step row table
   const unsigned long long *r1 = nullptr;          // the frontier's row table (asked for only where there is neither of the two)
 };
@@ -109,7 +109,7 @@ static hipError_t search_tables(const Index *h, uint32_t k, hipStream_t st, bool
   if (e != hipSuccess) return e;
   bool built_now = false;
   const bool due = !cal && tables_due(h, k, false);
-  if (due) { std::lock_guard<std::mutex> lk(h->jt_mu); built_now = !h->jt_ready; }
+  if (due) built_now = !h->jump.decided();
   if ((e = jump_get(h, st, &t->jt, due)) != hipSuccess) return e;
   if (built_now) {
     const unsigned long long *r3b = nullptr;
@@ -118,10 +118,10 @@ static hipError_t search_tables(const Index *h, uint32_t k, hipStream_t st, bool
   }
   // beside the jump table, the three-step table serves the steps no aligned jump covers; without it, the three-step table or,
   // where the handle has that one already, the regex frontier's row table
-  bool have1 = false;
-  if (!t->jt) { std::lock_guard<std::mutex> lk(h->r1_mu); have1 = h->d_row1 != nullptr; }
+  const unsigned long long *have1 = nullptr;
+  if (!t->jt.tab) (void)row1_get(h, st, &have1, false);      // (only looks)
   if (!have1 && (e = row3_get(h, st, &t->r3, due)) != hipSuccess) return e;
-  if (!t->jt && !t->r3 && (e = row1_get(h, st, &t->r1, due)) != hipSuccess) return e;
+  if (!t->jt.tab && !t->r3 && (e = row1_get(h, st, &t->r1, due)) != hipSuccess) return e;
   return hipSuccess;
 }
 
@@ -144,8 +144,8 @@ static SearchPlan plan_of(const Index *h, const SearchTables &t, bool g2) {
   SearchPlan p{h->layout == kLayoutBytes || h->n > (1ull << 32), h->layout, 0u, 0u, 0u, false, false, false};      // (FMX_LAYOUT_DISPATCH)
   // the search uses the k-mer table's levels in steps of four characters (all levels are kept: fmx_ktab.hip)
   p.kt = t.kt.k >= 12 ? 12u : t.kt.k >= 8 ? 8u : t.kt.k >= 4 ? 4u : 0u;
-  if (t.jt) {
-    p.jt = h->jump_pairs ? 2u : 1u;      // (pairs are built from the three-step table: it is there)
+  if (t.jt.tab) {
+    p.jt = t.jt.pairs ? 2u : 1u;      // (pairs are built from the three-step table: it is there)
     p.r3t = t.r3 != nullptr;
     p.g2 = g2;
     // level KT + 1 of the k-mer table (fmx_ktab.hip, build_kext) serves the kernels with pairs of row jump entries; "ktab_ext" =
@@ -159,7 +159,7 @@ static SearchPlan plan_of(const Index *h, const SearchTables &t, bool g2) {
 
 // Pairs of lanes serve the one-hot layout with a row jump table (single entries or pairs of them) and the three-step table.
 static bool can_pair_lanes(const Index *h, const SearchTables &t) {
-  return h->layout == kLayoutOneHot && t.jt && t.r3 && h->policy.search_lanes.load(std::memory_order_relaxed) != 0;
+  return h->layout == kLayoutOneHot && t.jt.tab && t.r3 && h->policy.search_lanes.load(std::memory_order_relaxed) != 0;
 }
 
 // Large batches on the one-hot layout: a PAIR of lanes per pattern, 32 patterns per wave (k_search4<.., G2>) -- half the
@@ -228,8 +228,8 @@ static Search4Args form_args(const Index *h, const SearchPlan &p, const SearchTa
   a.ksigma = t.kt.sigma;
   a.kext = p.kx ? t.kt.ext : nullptr;
   a.kovf = p.kx ? t.kt.ovf : nullptr;
-  a.jtab = t.jt;
-  a.jc = h->jump_chars;
+  a.jtab = t.jt.tab;
+  a.jc = t.jt.chars;
   a.r3tab = p.rw == 1u ? t.r1 : (p.r3t || p.rw == 3u) ? t.r3 : nullptr;      // (the one-step table is passed in the same argument)
   a.counters = h->d_counters;
   return a;

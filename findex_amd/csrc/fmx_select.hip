@@ -223,69 +223,65 @@ __global__ __launch_bounds__(kSelThreads) void k_next_substr(DevIndex ix, SelDir
 
 // ---------------------------------------------------------------- host side
 // Builds the directory on first use (most handles never extract text; C3's costs 4 GiB and a pass over the block
-// headers).  Guarded by the handle's mutex; the pointers never change afterwards.  The build allocates and synchronises
-// `st`, so it is refused while `st` is capturing (as the locate samples and the LCP array are): the message is recorded
-// here and hipErrorStreamCaptureUnsupported tells the entry point to keep it.  A build that fails leaves nothing allocated.
-static hipError_t ensure_select(const Index *h, hipStream_t st, SelDir *out) {
-  std::lock_guard<std::mutex> lk(h->sel_mu);
-  if (!h->sel_ready) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    hipError_t ec = hipStreamIsCapturing(st, &cs);
-    if (ec != hipSuccess) return ec;
-    if (cs != hipStreamCaptureStatusNone) {
-      set_error("the select directory is built by fmx_prepare(FMX_PREPARE_SELECT) or a first Psi / nextSubstr call outside a stream capture");
-      return hipErrorStreamCaptureUnsupported;
-    }
-    const auto t_build = std::chrono::steady_clock::now();
-    std::vector<uint64_t> off(h->nslots + 1, 0), totals(h->nslots ? h->nslots : 1, 0);
-    std::vector<uint8_t> shift(h->nslots ? h->nslots : 1, 0);
-    const double rows_per_block = h->layout == kLayoutBytes ? (double)kByteBlock : (double)kBlockBits;
-    for (int c = 1; c < 256; c++) {
-      const uint16_t s = h->slot[c];
-      if (s >= kSlotEof) continue;
-      const uint64_t cnt = (uint64_t)h->counts[c];
-      totals[s] = cnt;
-      // S occurrences span about two blocks (four in the bytes layout, whose blocks are small): S ~ 2 * density * block
-      const double want = (h->layout == kLayoutBytes ? 4.0 : 2.0) * rows_per_block * (double)cnt / (double)h->n;
-      uint32_t k = 0;
-      while (k < 8 && (double)(2u << k) <= want) k++;
-      shift[s] = (uint8_t)k;
-    }
-    for (uint32_t s = 0; s < h->nslots; s++) off[s + 1] = off[s] + ((totals[s] + ((1ull << shift[s]) - 1)) >> shift[s]) + 1;
-    const uint64_t entries = off[h->nslots];
-    hipError_t e = table_malloc(h, &h->d_sel_dir, (entries ? entries : 1) * 4 + 16);
-    if (e == hipSuccess) e = hipMalloc(&h->d_sel_off, off.size() * 8);
-    if (e == hipSuccess) e = hipMalloc(&h->d_sel_shift, shift.size());
-    uint64_t *d_tot = nullptr;
-    if (e == hipSuccess) e = hipMalloc((void **)&d_tot, totals.size() * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->d_sel_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->d_sel_shift, shift.data(), shift.size(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tot, totals.data(), totals.size() * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && h->nslots) {
-      const uint64_t work = (uint64_t)h->nslots * h->nblocks;
-      const int grid = (int)std::min<uint64_t>((work + 255) / 256, (uint64_t)h->cu_count * 32);
-      k_sel_build<<<grid, 256, 0, st>>>(h->dev, d_tot, (const uint64_t *)h->d_sel_off, (const uint8_t *)h->d_sel_shift,
-                                         (uint32_t *)h->d_sel_dir);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);           // the host vectors go out of scope
-    if (d_tot) (void)hipFree(d_tot);
-    if (e != hipSuccess) {
-      for (void **p : {&h->d_sel_dir, &h->d_sel_off, &h->d_sel_shift}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-      }
-      return e;
-    }
-    h->sel_bytes = entries * 4;
-    tables_account(h, (int64_t)h->sel_bytes);      // (Psi cannot do without it: counted against the budget, never refused by it)
-    h->sel_ready = true;
-    h->tables_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build).count();
+// headers), under the lock of its record h->sel (table_get); the pointers never change until the handle is closed.  The
+// build allocates and synchronises `st`, so it is refused while `st` is capturing (as the locate samples and the LCP array
+// are): the message is recorded here and hipErrorStreamCaptureUnsupported tells the entry point to keep it.  Unlike the
+// search tables the directory is not optional: a build that fails returns its error, leaves nothing allocated and is tried
+// again by the next call.
+static hipError_t build_select(const Index *h, hipStream_t st) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  hipError_t e = hipStreamIsCapturing(st, &cs);
+  if (e != hipSuccess) return e;
+  if (cs != hipStreamCaptureStatusNone) {
+    set_error("the select directory is built by fmx_prepare(FMX_PREPARE_SELECT) or a first Psi / nextSubstr call outside a stream capture");
+    return hipErrorStreamCaptureUnsupported;
   }
-  out->dir = (const uint32_t *)h->d_sel_dir;
-  out->off = (const uint64_t *)h->d_sel_off;
-  out->shift = (const uint8_t *)h->d_sel_shift;
+  std::vector<uint64_t> off(h->nslots + 1, 0), totals(h->nslots ? h->nslots : 1, 0);
+  std::vector<uint8_t> shift(h->nslots ? h->nslots : 1, 0);
+  const double rows_per_block = h->layout == kLayoutBytes ? (double)kByteBlock : (double)kBlockBits;
+  for (int c = 1; c < 256; c++) {
+    const uint16_t s = h->slot[c];
+    if (s >= kSlotEof) continue;
+    const uint64_t cnt = (uint64_t)h->counts[c];
+    totals[s] = cnt;
+    // S occurrences span about two blocks (four in the bytes layout, whose blocks are small): S ~ 2 * density * block
+    const double want = (h->layout == kLayoutBytes ? 4.0 : 2.0) * rows_per_block * (double)cnt / (double)h->n;
+    uint32_t k = 0;
+    while (k < 8 && (double)(2u << k) <= want) k++;
+    shift[s] = (uint8_t)k;
+  }
+  for (uint32_t s = 0; s < h->nslots; s++) off[s + 1] = off[s] + ((totals[s] + ((1ull << shift[s]) - 1)) >> shift[s]) + 1;
+  const uint64_t entries = off[h->nslots];
+  DevMem mem;
+  void *d_dir = nullptr, *d_off = nullptr, *d_shift = nullptr, *d_tot = nullptr;
+  if ((e = table_malloc(h, mem, &d_dir, (entries ? entries : 1) * 4 + 16)) != hipSuccess || (e = mem.get(&d_off, off.size() * 8)) != hipSuccess ||
+      (e = mem.get(&d_shift, shift.size())) != hipSuccess || (e = mem.get(&d_tot, totals.size() * 8)) != hipSuccess ||
+      (e = hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, st)) != hipSuccess ||
+      (e = hipMemcpyAsync(d_shift, shift.data(), shift.size(), hipMemcpyHostToDevice, st)) != hipSuccess ||
+      (e = hipMemcpyAsync(d_tot, totals.data(), totals.size() * 8, hipMemcpyHostToDevice, st)) != hipSuccess)
+    return e;
+  if (h->nslots) {
+    const uint64_t work = (uint64_t)h->nslots * h->nblocks;
+    const int grid = (int)std::min<uint64_t>((work + 255) / 256, (uint64_t)h->cu_count * 32);
+    k_sel_build<<<grid, 256, 0, st>>>(h->dev, (const uint64_t *)d_tot, (const uint64_t *)d_off, (const uint8_t *)d_shift, (uint32_t *)d_dir);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;      // the host vectors go out of scope
+  mem.free_now(d_tot);
+  for (void *p : {d_dir, d_off, d_shift}) mem.keep(p);
+  h->sel.dir = d_dir;
+  h->sel.off = d_off;
+  h->sel.shift = d_shift;
+  table_publish(h, h->sel, entries * 4, 0);      // (Psi cannot do without it: counted against the budget, never refused by it; no peak noted)
   return hipSuccess;
+}
+
+static hipError_t ensure_select(const Index *h, hipStream_t st, SelDir *out) {
+  return table_get(h, h->sel, true, false, [&] { return build_select(h, st); }, [&] {
+    out->dir = (const uint32_t *)h->sel.dir;
+    out->off = (const uint64_t *)h->sel.off;
+    out->shift = (const uint8_t *)h->sel.shift;
+  });
 }
 
 hipError_t select_prepare(const Index *h, hipStream_t st) {

@@ -764,6 +764,87 @@ def test_table_budget_decides_what_is_built():
     hip.close()
 
 
+def test_dropping_one_budgeted_table_leaves_the_others_alone():
+    """fmx_drop_tables with ONE flag of the table budget at a time -- FRONTIER, then JUMP, then KTAB: the table named goes
+    (its bytes leave row_bytes / jump_bytes / ktab_k and tables_held_bytes, which stays index_bytes less the dictionary),
+    the others stay as they were, JUMP and KTAB reset patterns_seen and FRONTIER does not, and the select directory, which
+    no drop takes, is all that is held at the end.  After each step literal searches, nextSubstr and a frontier regex match
+    answer like the oracle; the same fmx_prepare then brings back every stats field that is neither a time, a counter nor a
+    reading of one launch or of the free memory; the handle closes and a second one on the same arrays serves."""
+    bwt, eof, counts = synth_bwt(300_000, 1, 20, 5)
+    hip, orc = pair_from_mem(bwt, eof, counts)
+    n = orc.n
+    rng = np.random.default_rng(21)
+    pats = lf_walk_patterns(orc, rng, 1000, 30, 0.2, alphabet=list(range(1, 21)))
+    rows = rng.integers(0, n, 200).astype(np.uint64)
+    want_sub = [orc.nextSubstr(int(r), 9) for r in rows]
+    regexes = ("\x01\x02(\x03|\x04)*\x05", "\x01[\x02-\x04]+\x06\x07")
+    trees = [findex_amd.ReTree(findex_amd.REParser.re2post(re)) for re in regexes]
+    want_re = [oracle_results(orc, re)[0] for re in regexes]
+    assert any(want_re)
+
+    def serves(h):
+        check_search(h, orc, pats)
+        assert h.nextSubstr_batch(rows, 9) == want_sub
+        got = findex_amd.ReTree.matchSA_batch(h, trees, mode="frontier", maxBranching=1 << 20, maxIterations=0)
+        assert [[r.key() for r in g] for g in got] == want_re
+
+    fresh = findex_amd.HipFMSearcher.from_mem(bwt, eof, counts)       # what the select directory alone holds
+    assert fresh.stats()["tables_held_bytes"] == 0
+    fresh.nextSubstr_batch(rows[:5], 9)
+    sel_held = fresh.stats()["tables_held_bytes"]
+    fresh.close()
+    assert sel_held > 0
+
+    base = hip.stats()["index_bytes"]
+    hip.prepare(ktab=True, select=True, jump=True, frontier=True)
+    st0 = hip.stats()
+    assert st0["row_bytes"] == 16 * n and st0["jump_bytes"] == jump_row_bytes() * n and st0["ktab_k"] > 0
+    assert st0["tables_held_bytes"] == st0["index_bytes"] - base
+
+    hip.drop_tables(jump=False, frontier=True, ktab=False)            # R1 alone
+    st1 = hip.stats()
+    assert st1["row_bytes"] == st0["row_bytes"] - 8 * n
+    assert st1["jump_bytes"] == st0["jump_bytes"] and st1["ktab_k"] == st0["ktab_k"] and st1["patterns_seen"] == st0["patterns_seen"]
+    assert st1["tables_held_bytes"] == st0["tables_held_bytes"] - 8 * n == st1["index_bytes"] - base
+    serves(hip)                                                       # (the regex match builds R1 again: 8 n)
+
+    before = hip.stats()
+    assert before["row_bytes"] == 16 * n and before["patterns_seen"] > 0
+    hip.drop_tables(jump=True, frontier=False, ktab=False)            # J and R3 alone
+    st2 = hip.stats()
+    assert st2["jump_bytes"] == 0 and st2["jump_chars"] == 0 and st2["row_bytes"] == before["row_bytes"] - 8 * n      # what R1 left
+    assert st2["ktab_k"] == st0["ktab_k"] and st2["patterns_seen"] == 0
+    assert st2["tables_held_bytes"] == before["tables_held_bytes"] - before["jump_bytes"] - 8 * n == st2["index_bytes"] - base
+    serves(hip)                                                       # (this search builds J and R3 again: "tables_after" is 0 here)
+
+    before = hip.stats()
+    hip.drop_tables(jump=False, frontier=False, ktab=True)            # the k-mer table alone
+    st3 = hip.stats()
+    assert st3["ktab_k"] == 0 and st3["patterns_seen"] == 0
+    assert st3["jump_bytes"] == before["jump_bytes"] and st3["row_bytes"] == before["row_bytes"]
+    assert sel_held < st3["tables_held_bytes"] < before["tables_held_bytes"]
+    assert st3["tables_held_bytes"] == st3["index_bytes"] - base
+    serves(hip)
+    hip.drop_tables(jump=True, frontier=True, ktab=True)              # all three gone: what is held is the select directory
+    st3 = hip.stats()
+    assert st3["ktab_k"] == 0 and st3["jump_bytes"] == 0 and st3["row_bytes"] == 0
+    assert st3["tables_held_bytes"] == sel_held == st3["index_bytes"] - base
+
+    hip.prepare(ktab=True, select=True, jump=True, frontier=True)
+    st4 = hip.stats()
+    moving = {"rank_queries", "backward_steps", "launches", "last_kernel_ms", "search_requests", "frontier_requests",
+              "frontier_elements", "frontier_queue_reads", "frontier_queue_writes", "frontier_results", "frontier_records",
+              "ktab_lookups", "jump_lookups", "row_lookups", "patterns_seen",                  # counters
+              "build_ms", "tables_build_ms", "tables_alloc_ms",                                # times
+              "search_residency", "hbm_free_after_tables"}                                     # readings of a launch / of the free memory
+    assert {f: v for f, v in st4.items() if f not in moving} == {f: v for f, v in st0.items() if f not in moving}
+    hip.close()
+    hip2 = findex_amd.HipFMSearcher.from_mem(bwt, eof, counts)
+    check_search(hip2, orc, pats)
+    hip2.close()
+
+
 def test_pipelined_host_batch_pageable_and_pinned():
     """Host-pointer batches of 128k patterns or more travel as whole arrays or, with the "pipeline" setting on and
     page-locked buffers, as chunks over three streams (fmx_api.cpp): ragged
