@@ -10,7 +10,7 @@
 //                  of every escape's backslash, ascending).
 //                  k_corpus_count : per tile of kCoTile raw bytes the number of escapes, and the first document whose end
 //                                   lies at or behind the tile's first byte (a search in the end offsets).
-//                  scan_u32       : the exclusive sum of the escape counts (fmx_sufsort.hip's scan).
+//                  scan           : the exclusive sum of the escape counts (fmx_order.h, ScanSpace).
 //                  k_corpus_emit  : a raw byte i goes to stream position i + #escapes before i + #documents ended at or
 //                                   before i.  The escapes before i = the tile's scanned count + the lanes' counts scanned
 //                                   over the wave and the block; the documents = a search per lane, then comparisons with
@@ -21,7 +21,7 @@
 //   position map : k_corpus_map, two binary searches per position (doc_start, esc_pos); the escapes before each document's
 //                  start are kept per document (k_corpus_doc_esc), so a document's own escapes are a difference.
 //   doc listing  : rows of k intervals -> SA (fmx_locate_intervals_dev) -> text offsets -> documents (k_corpus_list_keys)
-//                  -> radix sort of interval << bits | doc (fmx_sufsort.hip's radix_sort) -> heads, scan, compact.
+//                  -> radix sort of interval << bits | doc (fmx_order.h, SortSpace) -> heads, scan, compact.
 //
 // Positions are u32 on the device (a stream has at most 2^32 - 2 bytes, the suffix sort's limit) and u64 at the ABI.
 #include <fmx.h>
@@ -33,7 +33,7 @@
 #include <vector>
 
 #include "fmx_corpus_dev.h"
-#include "fmx_host.h"
+#include "fmx_order.h"
 
 namespace fmx {
 
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(kCoThreads) void k_corpus_count(const uint8_t *__re
     __syncthreads();
     if (tid == 0) {
       esc_cnt[t] = ws[0] + ws[1] + ws[2] + ws[3];
-      tile_doc[t] = (uint32_t)co_lower(ends, 0, n_docs, a);
+      tile_doc[t] = (uint32_t)lower_bound(ends, 0, n_docs, a);
       if (t == ntiles - 1) esc_cnt[ntiles] = 0;
     }
     __syncthreads();
@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kCoThreads) void k_corpus_emit(const uint8_t *__res
     const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
     uint32_t lp[16];
     {
-      uint64_t d = nb ? co_upper(ends, d_lo, d_hi, base) : d_hi;
+      uint64_t d = nb ? upper_bound(ends, d_lo, d_hi, base) : d_hi;
       uint64_t next_end = d < d_hi ? (uint64_t)ends[d] : ~0ull;
       uint32_t run = (uint32_t)(base - a) + before, ne = 0;
 #pragma unroll
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(kCoThreads) void k_corpus_emit(const uint8_t *__res
         if ((uint32_t)j < nb) {
           const uint64_t i = base + j;
           if (next_end <= i) {
-            d = co_upper(ends, d, d_hi, i);
+            d = upper_bound(ends, d, d_hi, i);
             next_end = d < d_hi ? (uint64_t)ends[d] : ~0ull;
           }
           const uint32_t c = (w4[j >> 2] >> (8 * (j & 3))) & 255u;
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(kCoThreads) void k_corpus_doc_esc(const uint32_t *_
                                                                uint32_t *__restrict__ doc_esc) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t d = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; d <= n_docs; d += stride)
-    doc_esc[d] = (uint32_t)co_lower(esc_pos, 0, n_esc, doc_start[d]);
+    doc_esc[d] = (uint32_t)lower_bound(esc_pos, 0, n_esc, doc_start[d]);
 }
 
 __global__ __launch_bounds__(kCoThreads) void k_corpus_map(CoMap m, const unsigned long long *__restrict__ pos, uint64_t k,
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(kCoThreads) void k_corpus_list_keys(CoMap m, const 
                                                                  unsigned long long *__restrict__ key, uint32_t *__restrict__ val) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < rows; j += stride) {
-    const uint64_t i = co_upper(off, 0, k + 1, j) - 1;
+    const uint64_t i = upper_bound(off, 0, k + 1, j) - 1;
     const uint64_t s = sa[j];
     uint32_t d = (uint32_t)m.n_docs;
     uint64_t eo, ro;
@@ -245,20 +245,13 @@ __global__ __launch_bounds__(kCoThreads) void k_corpus_list_keys(CoMap m, const 
   }
 }
 
-__global__ __launch_bounds__(kCoThreads) void k_corpus_list_heads(const unsigned long long *__restrict__ key, uint64_t rows,
-                                                                  uint32_t *__restrict__ head) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < rows; j += stride)
-    head[j] = j == 0 || key[j] != key[j - 1] ? 1u : 0u;
-}
-
 // incl = the inclusive sum of head.  out_off[i] = distinct (interval, document) pairs of the intervals before i
 __global__ __launch_bounds__(kCoThreads) void k_corpus_list_off(const unsigned long long *__restrict__ key, uint64_t rows,
                                                                 const uint32_t *__restrict__ incl, uint64_t k, int doc_bits,
                                                                 unsigned long long *__restrict__ out_off) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= k; i += stride) {
-    const uint64_t j = co_lower(key, 0, rows, i << doc_bits);
+    const uint64_t j = lower_bound(key, 0, rows, i << doc_bits);
     out_off[i] = j ? incl[j - 1] : 0u;
   }
 }
@@ -275,7 +268,7 @@ __global__ __launch_bounds__(kCoThreads) void k_corpus_list_emit(const unsigned 
     if (slot >= cap) continue;
     const uint64_t d = kj & ((1ull << doc_bits) - 1);
     out_doc[slot] = d >= n_docs ? 0xffffffffu : (uint32_t)d;
-    out_cnt[slot] = (uint32_t)(co_upper(key, j, rows, kj) - j);
+    out_cnt[slot] = (uint32_t)(upper_bound(key, j, rows, kj) - j);
   }
 }
 
@@ -311,9 +304,8 @@ int co_check_ends(const uint64_t *ends, uint64_t n_docs, uint64_t raw_len) {
 
 // The map's own tables from doc_start / esc_pos in device memory: takes ownership on success.
 int co_finish(Corpus *c, hipStream_t st) {
-  hipLaunchKernelGGL(k_corpus_doc_esc, dim3(co_grid(c->n_docs + 1)), dim3(kCoThreads), 0, st, c->d_doc_start, c->n_docs,
-                     c->d_esc_pos, c->n_esc, c->d_doc_esc);
-  HIP_TRY(hipGetLastError(), "k_corpus_doc_esc");
+  LAUNCH("k_corpus_doc_esc", k_corpus_doc_esc, dim3(co_grid(c->n_docs + 1)), dim3(kCoThreads), st, c->d_doc_start, c->n_docs, c->d_esc_pos,
+         c->n_esc, c->d_doc_esc);
   HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
   return FMX_OK;
 }
@@ -323,25 +315,24 @@ int co_build(const uint8_t *d_raw, uint64_t raw_len, const uint64_t *ends, uint6
              Corpus **out) {
   const auto t0 = std::chrono::steady_clock::now();
   const uint64_t ntiles = std::max<uint64_t>(1, (raw_len + kCoTile - 1) / kCoTile);
-  const uint64_t parts = scan_partials(ntiles + 1);
-  const uint64_t tmp = 8 * n_docs + 4 * (ntiles + 1) + 4 * ntiles + 4 * parts;
+  const uint64_t tmp = 8 * n_docs + 4 * (ntiles + 1) + 4 * ntiles + ScanSpace::bytes(ntiles + 1);
   // the stream is raw_len + n_docs + escapes bytes: what is known before the count pass is checked now, the rest after it
   int rc = device_room(tmp + raw_len + n_docs + 8 * (n_docs + 1) + 4096, "the corpus stream");
   if (rc) return rc;
   DevMem mem;
   unsigned long long *d_ends = nullptr;
-  uint32_t *esc_cnt = nullptr, *tile_doc = nullptr, *partials = nullptr;
+  uint32_t *esc_cnt = nullptr, *tile_doc = nullptr;
+  ScanSpace scan;
   DEV_ALLOC(mem, d_ends, 8 * n_docs, "corpus");
   DEV_ALLOC(mem, esc_cnt, 4 * (ntiles + 1), "corpus");
   DEV_ALLOC(mem, tile_doc, 4 * ntiles, "corpus");
-  DEV_ALLOC(mem, partials, 4 * parts, "corpus");
+  if ((rc = scan.alloc(mem, ntiles + 1, "corpus"))) return rc;
   HIP_TRY(hipMemcpyAsync(d_ends, ends, 8 * n_docs, hipMemcpyHostToDevice, st), "H2D(ends)");
   const int aligned = (reinterpret_cast<uintptr_t>(d_raw) & 15u) == 0 ? 1 : 0;
   const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, 4096);
-  hipLaunchKernelGGL(k_corpus_count, dim3(grid), dim3(kCoThreads), 0, st, d_raw, raw_len, aligned, d_ends, n_docs, ntiles, esc_cnt,
-                     tile_doc);
-  HIP_TRY(hipGetLastError(), "k_corpus_count");
-  HIP_TRY(scan_u32(esc_cnt, ntiles + 1, kScanSum, true, partials, st), "scan");
+  LAUNCH("k_corpus_count", k_corpus_count, dim3(grid), dim3(kCoThreads), st, d_raw, raw_len, aligned, d_ends, n_docs, ntiles, esc_cnt,
+         tile_doc);
+  HIP_TRY(scan.sum(esc_cnt, ntiles + 1, true, st), "scan");
   uint32_t n_esc = 0;
   HIP_TRY(hipMemcpyAsync(&n_esc, esc_cnt + ntiles, 4, hipMemcpyDeviceToHost, st), "D2H");
   HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
@@ -364,9 +355,8 @@ int co_build(const uint8_t *d_raw, uint64_t raw_len, const uint64_t *ends, uint6
     set_error(std::string("hipMalloc(corpus): ") + hipGetErrorString(e));
     return FMX_ERR_NOMEM;
   }
-  hipLaunchKernelGGL(k_corpus_emit, dim3(grid), dim3(kCoThreads), 0, st, d_raw, raw_len, aligned, d_ends, n_docs, ntiles, esc_cnt,
-                     tile_doc, c->d_stream, c->d_doc_start, c->d_esc_pos);
-  HIP_TRY(hipGetLastError(), "k_corpus_emit");
+  LAUNCH("k_corpus_emit", k_corpus_emit, dim3(grid), dim3(kCoThreads), st, d_raw, raw_len, aligned, d_ends, n_docs, ntiles, esc_cnt,
+         tile_doc, c->d_stream, c->d_doc_start, c->d_esc_pos);
   if ((rc = co_finish(c.get(), st))) return rc;
   c->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   *out = c.release();
@@ -578,10 +568,9 @@ int fmx_corpus_map_dev(const fmx_corpus *corpus, const void *d_pos, size_t k, vo
   const Corpus *c = C(corpus);
   int rc = co_use(c);
   if (rc || !k) return rc;
-  hipLaunchKernelGGL(k_corpus_map, dim3(co_grid(k)), dim3(kCoThreads), 0, (hipStream_t)stream, c->map(),
-                     static_cast<const unsigned long long *>(d_pos), (uint64_t)k, static_cast<uint32_t *>(d_doc),
-                     static_cast<unsigned long long *>(d_esc_off), static_cast<unsigned long long *>(d_raw_off));
-  HIP_TRY(hipGetLastError(), "k_corpus_map");
+  LAUNCH("k_corpus_map", k_corpus_map, dim3(co_grid(k)), dim3(kCoThreads), (hipStream_t)stream, c->map(),
+         static_cast<const unsigned long long *>(d_pos), (uint64_t)k, static_cast<uint32_t *>(d_doc),
+         static_cast<unsigned long long *>(d_esc_off), static_cast<unsigned long long *>(d_raw_off));
   return FMX_OK;
 }
 
@@ -645,51 +634,35 @@ int fmx_corpus_doc_list_dev(const fmx_corpus *corpus, const fmx_index *idx, cons
     set_error("document listing of " + std::to_string(rows) + " rows: at most 2^32 - 2 per call (use max_per)");
     return FMX_ERR_UNSUPPORTED;
   }
-  int doc_bits = 1;
-  while ((c->n_docs >> doc_bits) != 0) doc_bits++;                 // documents 0 .. n_docs (n_docs: no document) fit
-  int k_bits = 1;
-  while (((uint64_t)k >> k_bits) != 0) k_bits++;
+  const int doc_bits = bits_for(c->n_docs), k_bits = bits_for(k);      // documents 0 .. n_docs (n_docs: no document) fit
   if (rows == 0) {
-    hipLaunchKernelGGL(k_corpus_list_off, dim3(co_grid(k + 1)), dim3(kCoThreads), 0, st, nullptr, 0ull, nullptr, (uint64_t)k,
-                       doc_bits, static_cast<unsigned long long *>(d_out_off));
-    HIP_TRY(hipGetLastError(), "k_corpus_list_off");
+    LAUNCH("k_corpus_list_off", k_corpus_list_off, dim3(co_grid(k + 1)), dim3(kCoThreads), st, nullptr, 0ull, nullptr, (uint64_t)k,
+           doc_bits, static_cast<unsigned long long *>(d_out_off));
     for (double &p : g_list_phases) p = 0.0;
     return FMX_OK;
   }
-  const uint64_t nt = radix_tiles(rows), hist_words = 256 * nt, parts = scan_partials(std::max<uint64_t>(rows, hist_words));
-  if ((rc = device_room(8 * rows + 16 * rows + 8 * rows + 4 * hist_words + 4 * parts + 8192, "a document listing"))) return rc;
-  unsigned long long *pos = nullptr, *k0 = nullptr, *k1 = nullptr;
-  uint32_t *v0 = nullptr, *v1 = nullptr, *hist = nullptr, *partials = nullptr;
+  if ((rc = device_room(8 * rows + SortSpace::bytes(rows) + 8192, "a document listing"))) return rc;
+  unsigned long long *pos = nullptr;
+  SortSpace ws;
   DEV_ALLOC(mem, pos, 8 * rows, "corpus");
-  DEV_ALLOC(mem, k0, 8 * rows, "corpus");
-  DEV_ALLOC(mem, k1, 8 * rows, "corpus");
-  DEV_ALLOC(mem, v0, 4 * rows, "corpus");
-  DEV_ALLOC(mem, v1, 4 * rows, "corpus");
-  DEV_ALLOC(mem, hist, 4 * hist_words, "corpus");
-  DEV_ALLOC(mem, partials, 4 * parts, "corpus");
+  if ((rc = ws.alloc(mem, rows, "corpus"))) return rc;
   HIP_TRY(ev.record(0, st), "hipEventRecord");
   if ((rc = fmx_locate_intervals_dev(idx, d_sp, d_ep, k, max_per, loc_off, pos, rows, stream))) return rc;
   HIP_TRY(ev.record(1, st), "hipEventRecord");
-  hipLaunchKernelGGL(k_corpus_list_keys, dim3(co_grid(rows)), dim3(kCoThreads), 0, st, c->map(), pos, (uint64_t)rows, loc_off,
-                     (uint64_t)k, pat_len, doc_bits, k0, v0);
-  HIP_TRY(hipGetLastError(), "k_corpus_list_keys");
+  LAUNCH("k_corpus_list_keys", k_corpus_list_keys, dim3(co_grid(rows)), dim3(kCoThreads), st, c->map(), pos, (uint64_t)rows, loc_off,
+         (uint64_t)k, pat_len, doc_bits, ws.keys(), ws.vals());
   HIP_TRY(ev.record(2, st), "hipEventRecord");
-  unsigned long long *key = k0, *key_alt = k1;
-  uint32_t *val = v0, *val_alt = v1;
-  int passes = 0;
-  HIP_TRY(radix_sort(&key, &val, &key_alt, &val_alt, rows, doc_bits + k_bits, hist, partials, st, &passes), "radix sort");
+  HIP_TRY(ws.sort(rows, doc_bits + k_bits, st), "radix sort");
   HIP_TRY(ev.record(3, st), "hipEventRecord");
-  uint32_t *head = reinterpret_cast<uint32_t *>(key_alt);           // the free key buffer holds the head flags
-  hipLaunchKernelGGL(k_corpus_list_heads, dim3(co_grid(rows)), dim3(kCoThreads), 0, st, key, (uint64_t)rows, head);
-  HIP_TRY(hipGetLastError(), "k_corpus_list_heads");
-  HIP_TRY(scan_u32(head, rows, kScanSum, false, partials, st), "scan");
-  hipLaunchKernelGGL(k_corpus_list_off, dim3(co_grid(k + 1)), dim3(kCoThreads), 0, st, key, (uint64_t)rows, head, (uint64_t)k, doc_bits,
-                     static_cast<unsigned long long *>(d_out_off));
-  HIP_TRY(hipGetLastError(), "k_corpus_list_off");
+  const unsigned long long *key = ws.keys();
+  uint32_t *head = reinterpret_cast<uint32_t *>(ws.free_keys());    // the free key buffer holds the head flags
+  HIP_TRY(launch_heads(key, rows, head, st), "k_corpus_list_heads");
+  HIP_TRY(ws.scan().sum(head, rows, false, st), "scan");
+  LAUNCH("k_corpus_list_off", k_corpus_list_off, dim3(co_grid(k + 1)), dim3(kCoThreads), st, key, (uint64_t)rows, head, (uint64_t)k,
+         doc_bits, static_cast<unsigned long long *>(d_out_off));
   if (cap) {
-    hipLaunchKernelGGL(k_corpus_list_emit, dim3(co_grid(rows)), dim3(kCoThreads), 0, st, key, (uint64_t)rows, head, doc_bits, c->n_docs,
-                       (uint64_t)cap, static_cast<uint32_t *>(d_out_doc), static_cast<uint32_t *>(d_out_cnt));
-    HIP_TRY(hipGetLastError(), "k_corpus_list_emit");
+    LAUNCH("k_corpus_list_emit", k_corpus_list_emit, dim3(co_grid(rows)), dim3(kCoThreads), st, key, (uint64_t)rows, head, doc_bits,
+           c->n_docs, (uint64_t)cap, static_cast<uint32_t *>(d_out_doc), static_cast<uint32_t *>(d_out_cnt));
   }
   HIP_TRY(ev.record(4, st), "hipEventRecord");
   HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");        // the temporaries go when this returns

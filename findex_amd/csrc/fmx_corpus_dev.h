@@ -1,32 +1,15 @@
 // fmx_corpus_dev.h -- the corpus map as the units that need it see it (fmx_corpus.hip builds and owns it, fmx_occ.hip reads
-// it): the handle's host side, the map's device view, and the searches that turn a stream position into (document, offset).
+// it): the handle's host side, the map's device view, and the searches (fmx_order.h's lower_bound / upper_bound) that turn a
+// stream position into (document, offset).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 
+#include "fmx_order.h"
+
 namespace fmx {
-
-template <typename T>
-__device__ __forceinline__ uint64_t co_lower(const T *__restrict__ a, uint64_t lo, uint64_t hi, uint64_t v) {   // first i: a[i] >= v
-  while (lo < hi) {
-    const uint64_t mid = lo + ((hi - lo) >> 1);
-    if ((uint64_t)a[mid] < v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-template <typename T>
-__device__ __forceinline__ uint64_t co_upper(const T *__restrict__ a, uint64_t lo, uint64_t hi, uint64_t v) {   // first i: a[i] > v
-  while (lo < hi) {
-    const uint64_t mid = lo + ((hi - lo) >> 1);
-    if ((uint64_t)a[mid] <= v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
 
 struct CoMap {
   const uint32_t *doc_start, *doc_esc, *esc_pos;
@@ -36,8 +19,8 @@ struct CoMap {
 // (doc, esc_off, raw_off) of stream position p; false at or past the end of the stream
 __device__ __forceinline__ bool co_map(const CoMap &m, uint64_t p, uint32_t &doc, uint64_t &esc_off, uint64_t &raw_off) {
   if (p >= m.stream_len) return false;
-  const uint64_t d = co_upper(m.doc_start, 0, m.n_docs, p) - 1;       // doc_start[0] = 0 <= p
-  const uint64_t e = co_lower(m.esc_pos, 0, m.n_esc, p);
+  const uint64_t d = upper_bound(m.doc_start, 0, m.n_docs, p) - 1;       // doc_start[0] = 0 <= p
+  const uint64_t e = lower_bound(m.esc_pos, 0, m.n_esc, p);
   doc = (uint32_t)d;
   esc_off = p - m.doc_start[d];
   raw_off = esc_off - (e - m.doc_esc[d]);

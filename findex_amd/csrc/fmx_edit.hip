@@ -29,7 +29,7 @@
 
 #include "fmx_approx.h"
 #include "fmx_device.h"
-#include "fmx_host.h"
+#include "fmx_order.h"
 
 namespace fmx {
 
@@ -283,32 +283,6 @@ __global__ __launch_bounds__(256) void k_edit_keys(const unsigned long long *__r
   }
 }
 
-__global__ __launch_bounds__(256) void k_edit_gather(const unsigned long long *__restrict__ stage,
-                                                     const uint32_t *__restrict__ val, uint64_t rows,
-                                                     unsigned long long *__restrict__ out) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < rows; j += stride) {
-    const uint64_t s = val[j] < rows ? val[j] : rows - 1;
-#pragma unroll
-    for (int w = 0; w < 3; w++) out[3 * j + w] = stage[3 * s + w];
-  }
-}
-
-// out_off[i] = hits of the patterns before i: the first sorted key that is not below i << 41 (key == nullptr: none at all)
-__global__ __launch_bounds__(256) void k_edit_off(const unsigned long long *__restrict__ key, uint64_t rows, uint64_t k,
-                                                  unsigned long long *__restrict__ out_off) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= k; i += stride) {
-    const unsigned long long want = (unsigned long long)i << (kEdRowBits + kEdLenBits);
-    uint64_t lo = i < k ? 0 : rows, hi = rows;               // (k = 2^23: k << 41 does not fit)
-    while (lo < hi) {
-      const uint64_t mid = (lo + hi) >> 1;
-      if (key[mid] < want) lo = mid + 1; else hi = mid;
-    }
-    out_off[i] = lo;
-  }
-}
-
 template <bool WIDE, uint32_t LAYOUT>
 static hipError_t ed_grid(const Index *h, uint64_t k, uint32_t *grid) {
   return resident_grid<k_edit<WIDE, LAYOUT>>(h, kEdThreads, k, kEdWaves, grid);
@@ -386,35 +360,17 @@ static int edit_search(const Index *h, const void *d_pat, const void *d_off, uin
   const uint64_t rows = info->total;
   unsigned long long *out_off = static_cast<unsigned long long *>(d_out_off);
   if (rows == 0) {
-    hipLaunchKernelGGL(k_edit_off, dim3(flat_grid(k + 1)), dim3(256), 0, st, nullptr, 0ull, k, out_off);
-    HIP_TRY(hipGetLastError(), "k_edit_off");
+    HIP_TRY(launch_csr_off(nullptr, 0, k, kEdRowBits + kEdLenBits, out_off, st), "k_edit_off");
     HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     return FMX_OK;
   }
-  const uint64_t nt = radix_tiles(rows), hist_words = 256 * nt, parts = scan_partials(std::max<uint64_t>(rows, hist_words));
-  unsigned long long *k0 = nullptr, *k1 = nullptr;
-  uint32_t *v0 = nullptr, *v1 = nullptr, *hist = nullptr, *partials = nullptr;
-  DEV_ALLOC(mem, k0, 8 * rows, "edit sort");
-  DEV_ALLOC(mem, k1, 8 * rows, "edit sort");
-  DEV_ALLOC(mem, v0, 4 * rows, "edit sort");
-  DEV_ALLOC(mem, v1, 4 * rows, "edit sort");
-  DEV_ALLOC(mem, hist, 4 * hist_words, "edit sort");
-  DEV_ALLOC(mem, partials, 4 * parts, "edit sort");
-  hipLaunchKernelGGL(k_edit_keys, dim3(flat_grid(rows)), dim3(256), 0, st, stage, rows, static_cast<const uint64_t *>(d_off), e,
-                     k0, v0);
-  HIP_TRY(hipGetLastError(), "k_edit_keys");
-  int k_bits = 1;
-  while (k_bits < 23 && ((k - 1) >> k_bits) != 0) k_bits++;
-  unsigned long long *key = k0, *key_alt = k1;
-  uint32_t *val = v0, *val_alt = v1;
-  int passes = 0;
-  HIP_TRY(radix_sort(&key, &val, &key_alt, &val_alt, rows, kEdRowBits + kEdLenBits + k_bits, hist, partials, st, &passes),
-          "radix sort");
-  hipLaunchKernelGGL(k_edit_gather, dim3(flat_grid(rows)), dim3(256), 0, st, stage, val, rows,
-                     static_cast<unsigned long long *>(d_out));
-  HIP_TRY(hipGetLastError(), "k_edit_gather");
-  hipLaunchKernelGGL(k_edit_off, dim3(flat_grid(k + 1)), dim3(256), 0, st, key, rows, k, out_off);
-  HIP_TRY(hipGetLastError(), "k_edit_off");
+  SortSpace ws;
+  if ((rc = ws.alloc(mem, rows, "edit sort"))) return rc;
+  LAUNCH("k_edit_keys", k_edit_keys, dim3(flat_grid(rows)), dim3(256), st, stage, rows, static_cast<const uint64_t *>(d_off), e, ws.keys(),
+         ws.vals());
+  HIP_TRY(ws.sort(rows, kEdRowBits + kEdLenBits + std::min(23, bits_for(k - 1)), st), "radix sort");      // pattern ids 0 .. k - 1
+  HIP_TRY(launch_gather3(stage, ws.vals(), rows, static_cast<unsigned long long *>(d_out), st), "k_edit_gather");
+  HIP_TRY(launch_csr_off(ws.keys(), rows, k, kEdRowBits + kEdLenBits, out_off, st), "k_edit_off");
   HIP_TRY(ev.record(2, st), "hipEventRecord");
   HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");  // the temporaries go when this returns
   info->sort_ms = ev.ms(1, 2);

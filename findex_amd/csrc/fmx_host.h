@@ -14,6 +14,7 @@
 
 #include "fmx_device.h"
 #include "fmx_hostpar.h"
+#include "fmx_order_math.h"
 
 namespace fmx {
 
@@ -401,6 +402,12 @@ int hip_fail(hipError_t e, const char *what);   // records the message, returns 
     const hipError_t e__ = (call);                            \
     if (e__ != hipSuccess) return ::fmx::hip_fail(e__, what); \
   } while (0)
+// One kernel launch on `st` (no dynamic LDS) and its error check
+#define LAUNCH(what, kernel, grid, block, st, ...)                    \
+  do {                                                                \
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, __VA_ARGS__);      \
+    HIP_TRY(hipGetLastError(), what);                                 \
+  } while (0)
 
 struct DevMem {                 // the hipMalloc'ed temporaries of one call; freed on every return path
   std::vector<void *> ps;
@@ -570,17 +577,7 @@ uint64_t sufsort_peak_bytes(uint64_t len, bool sa_given);
 int sufsort_bwt(const void *d_text, uint64_t len, void *d_bwt, void *d_sa_or_null, uint64_t *eof, int64_t counts[256],
                 hipStream_t st, uint64_t extra);
 
-// fmx_sufsort.hip's scan and sort, for the other units that need one (fmx_corpus.hip).  scan_u32: in place over len u32 (sum or
-// max, inclusive or exclusive), partials = scan_partials(len) u32 of scratch.  radix_sort: m (u64 key, u32 value) pairs by the
-// key's low `bits` bits, 8 per pass; the result is in (*k, *v), the other pair of buffers is free afterwards; hist = 256 *
-// radix_tiles(m) u32, partials = scan_partials(max(m, 256 * radix_tiles(m))) u32; m < 2^32.  Both only enqueue on `st`.
-constexpr int kScanSum = 0, kScanMax = 1;
-constexpr uint32_t kScanTile = 2048;                // elements per scan block: 8 per thread
-uint64_t scan_partials(uint64_t len);
-uint64_t radix_tiles(uint64_t m);
-hipError_t scan_u32(uint32_t *d, uint64_t len, int op, bool exclusive, uint32_t *partials, hipStream_t st);
-hipError_t radix_sort(unsigned long long **k, uint32_t **v, unsigned long long **k_alt, uint32_t **v_alt, uint64_t m,
-                      int bits, uint32_t *hist, uint32_t *partials, hipStream_t st, int *passes);
+// The scan, the radix sort and the shared order kernels: fmx_order.h (bits_for and the workspace sizes: fmx_order_math.h).
 
 // fmx_kernels.hip (launch_psi, launch_next_substr: fmx_select.hip)
 hipError_t launch_occ(const Index *h, const void *d_c, const void *d_i, void *d_out, uint64_t k, hipStream_t st);

@@ -9,7 +9,7 @@
 //                        the line table with the realness test), per term a lower bound of (d, max(1, i - w)) in the term's
 //                        key range compared with (d, i + w); with "lq_narrow" on a wave whose lanes share a query narrows
 //                        the range first by the bounds of its first and last lane (off by default: it measured slower)
-//   scan   : scan_u32 (fmx_sufsort.hip) over the flags
+//   scan   : ScanSpace (fmx_order.h) over the flags
 //   emit   : k_lq_emit   one record per kept candidate: the anchor's with `group` = the query, or lin_record's from the table
 //   offsets: k_lq_off    out_off[q] = the inclusive sum in front of the query's first candidate
 // No atomics decide an order: the same input gives the same bytes on every run.
@@ -21,7 +21,7 @@
 #include <vector>
 
 #include "fmx_corpus_dev.h"
-#include "fmx_host.h"
+#include "fmx_order.h"
 #include "fmx_lines_dev.h"
 
 namespace fmx {
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(kLqThreads) void k_lq_keys(const unsigned long long
     const unsigned long long k = lq_key(hits[i].doc, ln);
     bool ok = ln >= 1 && ln < (1ull << 32);
     if (i) {
-      const uint64_t u = co_upper(hit_off, 0, n_groups + 1, i);      // hit_off[u - 1] <= i: the group's first record, or not
+      const uint64_t u = upper_bound(hit_off, 0, n_groups + 1, i);      // hit_off[u - 1] <= i: the group's first record, or not
       if (hit_off[u - 1] != i && lq_key(hits[i - 1].doc, hits[i - 1].line_no) >= k) ok = false;
     }
     if (!ok) *bad = 1u;
@@ -94,7 +94,7 @@ __device__ __forceinline__ unsigned long long lq_line_key(const LinesDev &L, int
     real = false;
     return ~0ull;
   }
-  const uint64_t d = co_upper(m.doc_start, 0, m.n_docs, s) - 1;       // doc_start[0] = 0 <= s
+  const uint64_t d = upper_bound(m.doc_start, 0, m.n_docs, s) - 1;       // doc_start[0] = 0 <= s
   real = s + 1 != (uint64_t)m.doc_start[d + 1];
   return lq_key((uint32_t)d, j - lin_line(L, m.doc_start[d]) + 1);
 }
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(kLqThreads) void k_lq_flags(LinesDev L, int has_map
   const uint32_t lane = threadIdx.x & 63u;
   for (uint64_t c0 = (uint64_t)blockIdx.x * kLqThreads; c0 < n_cand; c0 += (uint64_t)gridDim.x * kLqThreads) {
     const uint64_t c = c0 + threadIdx.x, cc = c < n_cand ? c : n_cand - 1;
-    const uint64_t q = co_upper(T.cand_off, 0, T.n_queries + 1, cc) - 1;      // cand_off[0] = 0 <= cc < cand_off[n_queries]
+    const uint64_t q = upper_bound(T.cand_off, 0, T.n_queries + 1, cc) - 1;      // cand_off[0] = 0 <= cc < cand_off[n_queries]
     const uint64_t j = cc - T.cand_off[q];
     const uint32_t a = T.anchor[q];
     bool real = true;
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(kLqThreads) void k_lq_emit(LinesDev L, int has_map,
   for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_cand; c += stride) {
     const uint32_t after = incl[c], before = c ? incl[c - 1] : 0u;
     if (after == before || (uint64_t)before >= cap) continue;
-    const uint64_t q = co_upper(T.cand_off, 0, T.n_queries + 1, c) - 1, j = c - T.cand_off[q];
+    const uint64_t q = upper_bound(T.cand_off, 0, T.n_queries + 1, c) - 1, j = c - T.cand_off[q];
     const uint32_t a = T.anchor[q];
     fmx_line_hit o;
     if (a == FMX_LQ_ALL_LINES) o = lin_record(L, j, has_map, m);
@@ -280,20 +280,21 @@ int lq_run(const Index *h, const Corpus *c, const uint64_t *hit_off, const unsig
   cand_off[n_queries] = n_cand;
   qo[n_queries] = n_terms;
   if (n_terms) std::memcpy(tm, terms, sizeof(fmx_line_term) * n_terms);
-  const uint64_t parts = scan_partials(std::max<uint64_t>(n_cand, 1)), tab_bytes = 8 * (uint64_t)tab.size();
+  const uint64_t tab_bytes = 8 * (uint64_t)tab.size();
   // 8 bytes per hit, 4 per candidate, the scan's block totals, the query tables
-  if ((rc = device_room(8 * n_hits + 4 * n_cand + 4 * parts + tab_bytes + kMeteredBytes + 4096, "fmx_line_query"))) return rc;
+  if ((rc = device_room(8 * n_hits + 4 * n_cand + ScanSpace::bytes(n_cand) + tab_bytes + kMeteredBytes + 4096, "fmx_line_query"))) return rc;
   const CoMap map = c ? c->map() : CoMap{nullptr, nullptr, nullptr, 0, 0, 0};
   Events<5> ev;
   HIP_TRY(ev.create(), "hipEventCreate");
   DevMem mem;
   Metered own;
   unsigned long long *d_tab = nullptr, *keys = nullptr;
-  uint32_t *flag = nullptr, *partials = nullptr, *bad = nullptr;
+  uint32_t *flag = nullptr, *bad = nullptr;
+  ScanSpace scan;
   DEV_ALLOC(mem, d_tab, tab_bytes, "line query");
   DEV_ALLOC(mem, keys, 8 * n_hits, "line query");
   DEV_ALLOC(mem, flag, 4 * n_cand, "line query");
-  DEV_ALLOC(mem, partials, 4 * parts, "line query");
+  if ((rc = scan.alloc(mem, n_cand, "line query"))) return rc;
   DEV_ALLOC(mem, bad, 16, "line query");
   if ((rc = own.alloc(mem, "line query")) || (rc = own.zero(st))) return rc;
   HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, st), "H2D(queries)");
@@ -304,8 +305,7 @@ int lq_run(const Index *h, const Corpus *c, const uint64_t *hit_off, const unsig
   uint64_t launches = 0;
   HIP_TRY(ev.record(0, st), "hipEventRecord");
   if (n_hits) {
-    hipLaunchKernelGGL(k_lq_keys, dim3(flat_grid(n_hits)), block, 0, st, d_hit_off, n_groups, d_hits, n_hits, keys, bad);
-    HIP_TRY(hipGetLastError(), "k_lq_keys");
+    LAUNCH("k_lq_keys", k_lq_keys, dim3(flat_grid(n_hits)), block, st, d_hit_off, n_groups, d_hits, n_hits, keys, bad);
     launches++;
   }
   HIP_TRY(ev.record(1, st), "hipEventRecord");
@@ -318,25 +318,20 @@ int lq_run(const Index *h, const Corpus *c, const uint64_t *hit_off, const unsig
   }
   HIP_TRY(ev.record(2, st), "hipEventRecord");
   if (n_cand) {
-    hipLaunchKernelGGL(k_lq_flags, dim3(flat_grid(n_cand)), block, 0, st, L, c ? 1 : 0, map, d_hit_off, keys, T, n_cand,
-                       g_lq_narrow.load(std::memory_order_relaxed), flag, own.mine);
-    HIP_TRY(hipGetLastError(), "k_lq_flags");
+    LAUNCH("k_lq_flags", k_lq_flags, dim3(flat_grid(n_cand)), block, st, L, c ? 1 : 0, map, d_hit_off, keys, T, n_cand,
+           g_lq_narrow.load(std::memory_order_relaxed), flag, own.mine);
     HIP_TRY(ev.record(3, st), "hipEventRecord");
-    HIP_TRY(scan_u32(flag, n_cand, kScanSum, false, partials, st), "scan");
+    HIP_TRY(scan.sum(flag, n_cand, false, st), "scan");
     if (cap) {
-      hipLaunchKernelGGL(k_lq_emit, dim3(flat_grid(n_cand)), block, 0, st, L, c ? 1 : 0, map, d_hit_off, d_hits, T, flag, n_cand, cap,
-                         d_out);
-      HIP_TRY(hipGetLastError(), "k_lq_emit");
+      LAUNCH("k_lq_emit", k_lq_emit, dim3(flat_grid(n_cand)), block, st, L, c ? 1 : 0, map, d_hit_off, d_hits, T, flag, n_cand, cap, d_out);
     }
     launches += 5;
   } else {
     HIP_TRY(ev.record(3, st), "hipEventRecord");
   }
-  hipLaunchKernelGGL(k_lq_off, dim3(flat_grid(n_queries + 1)), block, 0, st, T, flag, n_cand, d_out_off);
-  HIP_TRY(hipGetLastError(), "k_lq_off");
+  LAUNCH("k_lq_off", k_lq_off, dim3(flat_grid(n_queries + 1)), block, st, T, flag, n_cand, d_out_off);
   HIP_TRY(ev.record(4, st), "hipEventRecord");
-  hipLaunchKernelGGL(k_lq_sum, dim3(1), block, 0, st, own.mine, own.line);
-  HIP_TRY(hipGetLastError(), "k_lq_sum");
+  LAUNCH("k_lq_sum", k_lq_sum, dim3(1), block, st, own.mine, own.line);
   uint32_t tot = 0;
   if (n_cand) HIP_TRY(hipMemcpyAsync(&tot, flag + (n_cand - 1), 4, hipMemcpyDeviceToHost, st), "D2H(total)");
   MeterCounts cnt;

@@ -4,13 +4,13 @@
 //   rows    : the buckets [cf(c), cf(c) + counts(c)) of the break bytes c -- the occurrences of the one-byte strings
 //   locate  : launch_locate_intervals (fmx_locate.hip) for their SA values
 //   keys    : k_lines_keys    pos = n - 2 - SA (a value outside the text raises a flag and sorts last)
-//   sort    : radix_sort (fmx_sufsort.hip) over the bits n needs
+//   sort    : SortSpace (fmx_order.h) over the bits n needs
 //   table   : k_lines_pack    brk[j] as u32 (a repeated position raises the flag); k_lines_dir  dir[i] = the breaks before
 //                             position i << S, a lower bound per directory entry
 //   lookup  : k_lines_lookup  p -> dir[p >> S], dir[(p >> S) + 1], a lower bound among at most 2^S entries of brk
 //             k_lines_spans   L -> brk[L - 1] + 1, brk[L]
 //   reduce  : k_ol_lines      every record's group (a search in the CSR offsets) and line; a pos outside the text raises a flag
-//             k_ol_heads      1 where (group, line) differs from the record before; scan_u32 over the flags
+//             k_ol_heads      1 where (group, line) differs from the record before; a scan (fmx_order.h) over the flags
 //             k_ol_pick       head t's record index side by side; k_ol_emit one fmx_line_hit per head, n_hits from the next
 //                             head's index; k_ol_off  out_off[g] = the heads before the group's first record
 // No atomics anywhere: the same input gives the same bytes on every run.  Positions are u32 in the table (n < 2^32).
@@ -22,7 +22,7 @@
 #include <vector>
 
 #include "fmx_corpus_dev.h"
-#include "fmx_host.h"
+#include "fmx_order.h"
 #include "fmx_lines_dev.h"
 
 namespace fmx {
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(kLinThreads) void k_lines_dir(const uint32_t *__res
                                                            uint32_t shift, uint32_t *__restrict__ dir) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < entries; i += stride)
-    dir[i] = (uint32_t)co_lower(brk, 0, m, i << shift);
+    dir[i] = (uint32_t)lower_bound(brk, 0, m, i << shift);
 }
 
 __global__ __launch_bounds__(kLinThreads) void k_lines_lookup(LinesDev L, const unsigned long long *__restrict__ pos, uint64_t k,
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(kLinThreads) void k_ol_lines(LinesDev L, const unsi
                                                           uint32_t *__restrict__ bad) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_occ; i += stride) {
-    const uint64_t u = co_upper(occ_off, 0, n_groups + 1, i), p = occ[i].pos;
+    const uint64_t u = upper_bound(occ_off, 0, n_groups + 1, i), p = occ[i].pos;
     uint32_t g = kLinNone, l = kLinNone;
     if (u >= 1 && u <= n_groups && p < L.len) {
       g = (uint32_t)(u - 1);
@@ -168,12 +168,6 @@ struct LinesInfo {
 };
 thread_local LinesInfo g_lines_last;
 
-int bits_for(uint64_t v) {                           // the bits that hold 0 .. v
-  int b = 1;
-  while (b < 64 && (v >> b) != 0) b++;
-  return b;
-}
-
 void add_launches(const Index *h, uint64_t launches) {
   std::lock_guard<std::mutex> lk(h->mu);
   h->launches += launches;
@@ -215,10 +209,8 @@ int lines_table(const Index *h, const uint8_t *set, uint32_t n_set, hipStream_t 
     return FMX_ERR_FORMAT;
   }
   const uint64_t entries = (len >> shift) + 2, keep = 4 * std::max<uint64_t>(m, 1) + 4 * entries;
-  const uint64_t nt = radix_tiles(std::max<uint64_t>(m, 1)), hist_words = 256 * nt;
-  const uint64_t parts = scan_partials(std::max<uint64_t>(m, hist_words));
-  // the SA values, two key and two value buffers, the histograms and the scan's block totals, the table itself
-  if ((rc = device_room(keep + 32 * m + 4 * hist_words + 4 * parts + 8192, "the line table"))) return rc;
+  // the table itself; where there are breaks, their SA values and the sort's workspace
+  if ((rc = device_room(keep + (m ? 8 * m + SortSpace::bytes(m) : 0) + 8192, "the line table"))) return rc;
   Events<4> ev;
   HIP_TRY(ev.create(), "hipEventCreate");
   uint32_t *brk = nullptr, *dir = nullptr, *bad = nullptr;
@@ -229,17 +221,12 @@ int lines_table(const Index *h, const uint8_t *set, uint32_t n_set, hipStream_t 
   uint64_t launches = 0;
   uint32_t bad_h = 0;
   if (m) {
-    unsigned long long *d_iv = nullptr, *off = nullptr, *sa = nullptr, *k0 = nullptr, *k1 = nullptr;
-    uint32_t *v0 = nullptr, *v1 = nullptr, *hist = nullptr, *partials = nullptr;
+    unsigned long long *d_iv = nullptr, *off = nullptr, *sa = nullptr;
+    SortSpace ws;
     DEV_ALLOC(mem, d_iv, 64, "line table");
     DEV_ALLOC(mem, off, 64, "line table");
     DEV_ALLOC(mem, sa, 8 * m, "line table");
-    DEV_ALLOC(mem, k0, 8 * m, "line table");
-    DEV_ALLOC(mem, k1, 8 * m, "line table");
-    DEV_ALLOC(mem, v0, 4 * m, "line table");
-    DEV_ALLOC(mem, v1, 4 * m, "line table");
-    DEV_ALLOC(mem, hist, 4 * hist_words, "line table");
-    DEV_ALLOC(mem, partials, 4 * parts, "line table");
+    if ((rc = ws.alloc(mem, m, "line table"))) return rc;
     HIP_TRY(hipMemcpyAsync(d_iv, sp, 32, hipMemcpyHostToDevice, st), "H2D(intervals)");
     HIP_TRY(hipMemcpyAsync(d_iv + 4, ep, 32, hipMemcpyHostToDevice, st), "H2D(intervals)");
     HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");       // sp and ep are this frame's
@@ -248,21 +235,15 @@ int lines_table(const Index *h, const uint8_t *set, uint32_t n_set, hipStream_t 
     HIP_TRY(launch_locate_intervals(h, d_iv, d_iv + 4, n_set, 0, off, sa, m, st), "k_locate");
     HIP_TRY(ev.record(1, st), "hipEventRecord");
     const int pb = bits_for(n);
-    hipLaunchKernelGGL(k_lines_keys, grid, block, 0, st, sa, m, n, (1ull << pb) - 1, k0, v0, bad);
-    HIP_TRY(hipGetLastError(), "k_lines_keys");
-    unsigned long long *key = k0, *key_alt = k1;
-    uint32_t *val = v0, *val_alt = v1;
-    int passes = 0;
-    HIP_TRY(radix_sort(&key, &val, &key_alt, &val_alt, m, pb, hist, partials, st, &passes), "radix sort");
-    hipLaunchKernelGGL(k_lines_pack, grid, block, 0, st, key, m, len, brk, bad);
-    HIP_TRY(hipGetLastError(), "k_lines_pack");
+    LAUNCH("k_lines_keys", k_lines_keys, grid, block, st, sa, m, n, (1ull << pb) - 1, ws.keys(), ws.vals(), bad);
+    HIP_TRY(ws.sort(m, pb, st), "radix sort");
+    LAUNCH("k_lines_pack", k_lines_pack, grid, block, st, ws.keys(), m, len, brk, bad);
     HIP_TRY(ev.record(2, st), "hipEventRecord");
-    launches += 5 + 3 * (uint64_t)passes;
+    launches += 5 + 3 * (uint64_t)ws.passes;
   } else {
     for (int i = 0; i < 3; i++) HIP_TRY(ev.record(i, st), "hipEventRecord");
   }
-  hipLaunchKernelGGL(k_lines_dir, dim3(flat_grid(entries)), dim3(kLinThreads), 0, st, brk, m, entries, shift, dir);
-  HIP_TRY(hipGetLastError(), "k_lines_dir");
+  LAUNCH("k_lines_dir", k_lines_dir, dim3(flat_grid(entries)), dim3(kLinThreads), st, brk, m, entries, shift, dir);
   HIP_TRY(ev.record(3, st), "hipEventRecord");
   launches++;
   HIP_TRY(hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, st), "D2H(flag)");
@@ -401,32 +382,30 @@ int ol_run(const Index *h, const Corpus *c, const unsigned long long *d_occ_off,
   if (rc) return rc;
   const dim3 block(kLinThreads);
   if (!n_occ) {
-    hipLaunchKernelGGL(k_ol_off, dim3(flat_grid(n_groups + 1)), block, 0, st, d_occ_off, n_groups, nullptr, 0ull, d_out_off);
-    HIP_TRY(hipGetLastError(), "k_ol_off");
+    LAUNCH("k_ol_off", k_ol_off, dim3(flat_grid(n_groups + 1)), block, st, d_occ_off, n_groups, nullptr, 0ull, d_out_off);
     HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     add_launches(h, 1);
     *total = 0;
     return FMX_OK;
   }
-  const uint64_t parts = scan_partials(n_occ);
-  if ((rc = device_room(16 * n_occ + 4 * parts + 4096, "fmx_occurrence_lines"))) return rc;
+  if ((rc = device_room(16 * n_occ + ScanSpace::bytes(n_occ) + 4096, "fmx_occurrence_lines"))) return rc;
   const CoMap map = c ? c->map() : CoMap{nullptr, nullptr, nullptr, 0, 0, 0};
   const LinesDev L = lines_dev(h);
   Events<3> ev;
   HIP_TRY(ev.create(), "hipEventCreate");
   DevMem mem;
-  uint32_t *grp = nullptr, *line = nullptr, *flag = nullptr, *hidx = nullptr, *partials = nullptr, *bad = nullptr;
+  uint32_t *grp = nullptr, *line = nullptr, *flag = nullptr, *hidx = nullptr, *bad = nullptr;
+  ScanSpace scan;
   DEV_ALLOC(mem, grp, 4 * n_occ, "occurrence lines");
   DEV_ALLOC(mem, line, 4 * n_occ, "occurrence lines");
   DEV_ALLOC(mem, flag, 4 * n_occ, "occurrence lines");
   DEV_ALLOC(mem, hidx, 4 * n_occ, "occurrence lines");
-  DEV_ALLOC(mem, partials, 4 * parts, "occurrence lines");
+  if ((rc = scan.alloc(mem, n_occ, "occurrence lines"))) return rc;
   DEV_ALLOC(mem, bad, 16, "occurrence lines");
   const dim3 grid(flat_grid(n_occ));
   HIP_TRY(hipMemsetAsync(bad, 0, 16, st), "hipMemsetAsync");
   HIP_TRY(ev.record(0, st), "hipEventRecord");
-  hipLaunchKernelGGL(k_ol_lines, grid, block, 0, st, L, d_occ_off, n_groups, d_occ, n_occ, grp, line, bad);
-  HIP_TRY(hipGetLastError(), "k_ol_lines");
+  LAUNCH("k_ol_lines", k_ol_lines, grid, block, st, L, d_occ_off, n_groups, d_occ, n_occ, grp, line, bad);
   HIP_TRY(ev.record(1, st), "hipEventRecord");
   uint32_t bad_h = 0;
   HIP_TRY(hipMemcpyAsync(&bad_h, bad, 4, hipMemcpyDeviceToHost, st), "D2H(flag)");
@@ -435,17 +414,13 @@ int ol_run(const Index *h, const Corpus *c, const unsigned long long *d_occ_off,
     add_launches(h, 1);
     return arg_fail("occurrence lines: a record with pos >= n - 1, or offsets that do not cover the records");
   }
-  hipLaunchKernelGGL(k_ol_heads, grid, block, 0, st, grp, line, n_occ, flag);
-  HIP_TRY(hipGetLastError(), "k_ol_heads");
-  HIP_TRY(scan_u32(flag, n_occ, kScanSum, false, partials, st), "scan");
-  hipLaunchKernelGGL(k_ol_off, dim3(flat_grid(n_groups + 1)), block, 0, st, d_occ_off, n_groups, flag, n_occ, d_out_off);
-  HIP_TRY(hipGetLastError(), "k_ol_off");
+  LAUNCH("k_ol_heads", k_ol_heads, grid, block, st, grp, line, n_occ, flag);
+  HIP_TRY(scan.sum(flag, n_occ, false, st), "scan");
+  LAUNCH("k_ol_off", k_ol_off, dim3(flat_grid(n_groups + 1)), block, st, d_occ_off, n_groups, flag, n_occ, d_out_off);
   if (cap) {
-    hipLaunchKernelGGL(k_ol_pick, grid, block, 0, st, flag, n_occ, hidx);
-    HIP_TRY(hipGetLastError(), "k_ol_pick");
-    hipLaunchKernelGGL(k_ol_emit, dim3(flat_grid(std::min(n_occ, cap))), block, 0, st, L, d_occ_off, grp, line, flag, hidx, n_occ,
-                       c ? 1 : 0, map, cap, d_out);
-    HIP_TRY(hipGetLastError(), "k_ol_emit");
+    LAUNCH("k_ol_pick", k_ol_pick, grid, block, st, flag, n_occ, hidx);
+    LAUNCH("k_ol_emit", k_ol_emit, dim3(flat_grid(std::min(n_occ, cap))), block, st, L, d_occ_off, grp, line, flag, hidx, n_occ, c ? 1 : 0,
+           map, cap, d_out);
   }
   HIP_TRY(ev.record(2, st), "hipEventRecord");
   uint32_t tot = 0;

@@ -24,7 +24,7 @@ __device__ __forceinline__ uint64_t lin_line(const LinesDev &L, uint64_t p) {   
   uint64_t lo = L.dir[b], hi = L.dir[b + 1];
   hi = hi < L.n_brk ? hi : L.n_brk;
   lo = lo < hi ? lo : hi;
-  return co_lower(L.brk, lo, hi, p);
+  return lower_bound(L.brk, lo, hi, p);
 }
 __device__ __forceinline__ uint64_t lin_start(const LinesDev &L, uint64_t line) { return line ? (uint64_t)L.brk[line - 1] + 1 : 0; }
 __device__ __forceinline__ uint64_t lin_end(const LinesDev &L, uint64_t line) { return line < L.n_brk ? (uint64_t)L.brk[line] : L.len; }

@@ -28,7 +28,7 @@
 #include <string>
 
 #include "fmx_device.h"
-#include "fmx_host.h"
+#include "fmx_order.h"
 
 namespace fmx {
 
@@ -353,7 +353,7 @@ uint64_t piece_hold_bytes(uint64_t M, uint64_t b) {          // what a piece kee
 }
 uint64_t piece_temp_bytes(uint64_t M, uint64_t b) {          // the largest of its temporaries
   const uint64_t np = M + b + 1;
-  return std::max<uint64_t>({sufsort_peak_bytes(M + b, true), lcp_text_bytes(np) + lcp_core_bytes(np), 4 * scan_partials(np)});
+  return std::max<uint64_t>({sufsort_peak_bytes(M + b, true), lcp_text_bytes(np) + lcp_core_bytes(np), ScanSpace::bytes(np)});
 }
 uint64_t place_bytes(uint64_t b, uint64_t nseg) { return 8 * b + 8 * b + b + 4 * nseg + 8 * kResWords + 256; }
 
@@ -470,13 +470,14 @@ int merge_core(const Index *h, const uint8_t *d_text, uint64_t b, const MergeOpt
   const uint64_t np = M + b + 1;
   // ---- gap ranks
   uint64_t *rank = nullptr, *pos = nullptr;
-  uint32_t *nun = nullptr, *partials = nullptr;
+  uint32_t *nun = nullptr;
+  ScanSpace scan;
   uint8_t *nb = nullptr;
   DEV_ALLOC(mem, rank, 8 * b, "append ranks");
   DEV_ALLOC(mem, pos, 8 * b, "append rows");
   DEV_ALLOC(mem, nb, b, "append bytes");
   DEV_ALLOC(mem, nun, 4 * nseg, "append segments");
-  DEV_ALLOC(mem, partials, 4 * scan_partials(np), "append scan");
+  if (const int arc = scan.alloc(mem, np, "append scan")) return arc;
   hipError_t he = hipSuccess;
 #define MRG_WALKS(WIDE, LAYOUT) he = launch_walks<WIDE, LAYOUT>(h, d_text, b, mo, nseg, rank, nun, res, ev, st)
   FMX_LAYOUT_DISPATCH(h, MRG_WALKS);
@@ -498,7 +499,7 @@ int merge_core(const Index *h, const uint8_t *d_text, uint64_t b, const MergeOpt
   uint32_t *keep = piece->lcp;                     // (the check is done: the LCP buffer holds the keep flags and their sum)
   k_mrg_keep<<<mrg_grid(np, h->cu_count), kMrgThreads, 0, st>>>(piece->sa, np, b, keep);
   HIP_TRY(hipGetLastError(), "k_mrg_keep");
-  HIP_TRY(scan_u32(keep, np, kScanSum, true, partials, st), "scan");
+  HIP_TRY(scan.sum(keep, np, true, st), "scan");
   k_mrg_place<<<mrg_grid(np, h->cu_count), kMrgThreads, 0, st>>>(piece->sa, keep, np, d_text, b, rank, pos, nb, res);
   HIP_TRY(hipGetLastError(), "k_mrg_place");
   k_mrg_mono<<<mrg_grid(b, h->cu_count), kMrgThreads, 0, st>>>(pos, b, n_t, res);

@@ -22,7 +22,7 @@
 #include <string>
 
 #include "fmx_device.h"
-#include "fmx_host.h"
+#include "fmx_order.h"
 
 namespace fmx {
 
@@ -217,7 +217,7 @@ static hipError_t mstat_enqueue(const Index *h, const void *d_pat, const void *d
 // the device bytes mstat_run allocates
 static uint64_t mstat_bytes(uint64_t n_bytes, bool mems) {
   uint64_t need = kMeteredBytes;
-  if (mems) need += 20 * n_bytes + 4 * (n_bytes + 1) + 4 * scan_partials(n_bytes + 1) + 64;
+  if (mems) need += 20 * n_bytes + 4 * (n_bytes + 1) + ScanSpace::bytes(n_bytes + 1) + 64;
   return need;
 }
 
@@ -239,7 +239,8 @@ static int mstat_run(const Index *h, const void *d_pat, const void *d_off, uint6
   HIP_TRY(ev.create(), "hipEventCreate");
   DevMem mem;
   Metered own;
-  uint32_t *len = static_cast<uint32_t *>(d_len), *flag = nullptr, *partials = nullptr;
+  uint32_t *len = static_cast<uint32_t *>(d_len), *flag = nullptr;
+  ScanSpace scan;
   uint64_t *sp = static_cast<uint64_t *>(d_sp), *ep = static_cast<uint64_t *>(d_ep);
   if ((rc = own.alloc(mem, "matching statistics"))) return rc;
   if (mems) {
@@ -247,7 +248,7 @@ static int mstat_run(const Index *h, const void *d_pat, const void *d_off, uint6
     DEV_ALLOC(mem, sp, 8 * n_bytes, "MEM statistics");
     DEV_ALLOC(mem, ep, 8 * n_bytes, "MEM statistics");
     DEV_ALLOC(mem, flag, 4 * (n_bytes + 1), "MEM flags");
-    DEV_ALLOC(mem, partials, 4 * scan_partials(n_bytes + 1), "MEM scan");
+    if ((rc = scan.alloc(mem, n_bytes + 1, "MEM scan"))) return rc;
   }
   if ((rc = own.zero(st))) return rc;
   HIP_TRY(ev.record(0, st), "hipEventRecord");
@@ -258,13 +259,11 @@ static int mstat_run(const Index *h, const void *d_pat, const void *d_off, uint6
   HIP_TRY(ev.record(1, st), "hipEventRecord");
   uint32_t total = 0;
   if (mems) {
-    hipLaunchKernelGGL(k_mem_flag, dim3(flat_grid(n_bytes + 1)), dim3(256), 0, st, len, n_bytes, min_len, flag);
-    HIP_TRY(hipGetLastError(), "k_mem_flag");
-    HIP_TRY(scan_u32(flag, n_bytes + 1, kScanSum, true, partials, st), "scan");
-    hipLaunchKernelGGL(k_mem_write, dim3(flat_grid(std::max<uint64_t>(n_bytes, k + 1))), dim3(256), 0, st, flag, len, sp, ep,
-                       static_cast<const uint64_t *>(d_off), k, n_bytes, cap, static_cast<unsigned long long *>(d_out_off),
-                       static_cast<uint4 *>(d_out));
-    HIP_TRY(hipGetLastError(), "k_mem_write");
+    LAUNCH("k_mem_flag", k_mem_flag, dim3(flat_grid(n_bytes + 1)), dim3(256), st, len, n_bytes, min_len, flag);
+    HIP_TRY(scan.sum(flag, n_bytes + 1, true, st), "scan");
+    LAUNCH("k_mem_write", k_mem_write, dim3(flat_grid(std::max<uint64_t>(n_bytes, k + 1))), dim3(256), st, flag, len, sp, ep,
+           static_cast<const uint64_t *>(d_off), k, n_bytes, cap, static_cast<unsigned long long *>(d_out_off),
+           static_cast<uint4 *>(d_out));
     HIP_TRY(ev.record(2, st), "hipEventRecord");
     HIP_TRY(hipMemcpyAsync(&total, flag + n_bytes, 4, hipMemcpyDeviceToHost, st), "D2H");
   }

@@ -7,11 +7,12 @@
 // window only when its suffix has L bytes in front of the sentinel (p + L <= m); exactly min(L, n) rows have not, and each
 // of them is a run of its own.
 //
-// One call: with positions the inversion (SA and s) and, with a stop byte, the stop scan; then per length L
+// One call: with positions the inversion (SA and s) and, with a stop byte, the stop scan; then per length L (the stops, the
+// class heads and the class maxima are fmx_order.h's kernels, shared with fmx_repeats.hip)
 //
-//   k_ng_heads    : A[r] = r + 1 where a run begins (r == 0 or LCP[r - 1] < L), else 0; B[r] = 0.  A max-scan turns A into
+//   class heads   : A[r] = r + 1 where a run begins (r == 0 or LCP[r - 1] < L), else 0; B[r] = 0.  A max-scan turns A into
 //                   (head row of r's run) + 1.
-//   k_ng_classmax : (positions only) B[head] = the largest SA of the run, over the runs of two rows and more: a segmented
+//   class maxima  : (positions only) B[head] = the largest SA of the run, over the runs of two rows and more: a segmented
 //                   max over the wave, then one atomicMax per run and wave.  A run of one row has its own SA.
 //   k_ng_class    : the last row of a run (LCP[r] < L) knows the size r - head + 1.  It decides whether the run is a window
 //                   (p + L <= m; without positions every run passes and the host takes the min(L, n) short rows off the
@@ -33,7 +34,7 @@
 
 #include <string>
 
-#include "fmx_host.h"
+#include "fmx_order.h"
 
 namespace fmx {
 
@@ -43,46 +44,6 @@ static_assert(FMX_NGRAMS_LDS_BINS >= 2 && FMX_NGRAMS_LDS_BINS <= 4096, "the hist
 constexpr int kNgThreads = 256;
 constexpr uint32_t kNgLdsBins = FMX_NGRAMS_LDS_BINS;
 constexpr uint64_t kNgNone = ~0ull;
-
-// P[t] = t + 1 where T[t] is the stop byte, else 0 (T[t] = s[m - 1 - t])
-__global__ __launch_bounds__(kNgThreads) void k_ng_stops(const uint8_t *__restrict__ s, uint64_t m, uint32_t stop,
-                                                         uint32_t *__restrict__ P) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < m; t += stride)
-    P[t] = s[m - 1 - t] == stop ? (uint32_t)t + 1u : 0u;
-}
-
-// B may be null (no positions: no class maximum)
-__global__ __launch_bounds__(kNgThreads) void k_ng_heads(const uint32_t *__restrict__ lcp, uint64_t n, uint32_t L,
-                                                         uint32_t *__restrict__ A, uint32_t *__restrict__ B) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += stride) {
-    A[r] = (r == 0 || lcp[r - 1] < L) ? (uint32_t)r + 1u : 0u;
-    if (B) B[r] = 0u;
-  }
-}
-
-// A: the scanned heads.  The loop's trip count is the same for every lane of a workgroup: all 64 lanes shuffle.
-__global__ __launch_bounds__(kNgThreads) void k_ng_classmax(const uint32_t *__restrict__ lcp, const uint32_t *__restrict__ sa,
-                                                            const uint32_t *__restrict__ A, uint64_t n, uint32_t L,
-                                                            uint32_t *__restrict__ B) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  const int lane = threadIdx.x & 63;
-  const uint32_t last = (uint32_t)(n - 1);
-  for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x; b < n; b += stride) {
-    const uint64_t r = b + threadIdx.x;
-    const bool rep = r < n && ((r > 0 && lcp[r - 1] >= L) || (r < n - 1 && lcp[r] >= L));
-    const uint32_t key = rep ? A[r] : 0u;                     // >= 1 for a row of a run of two rows and more
-    uint32_t val = rep ? min(sa[r], last) : 0u;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t ok = __shfl_up(key, d, 64), ov = __shfl_up(val, d, 64);
-      if (lane >= d && ok == key) val = max(val, ov);
-    }
-    const uint32_t next = __shfl_down(key, 1, 64);
-    if (rep && (lane == 63 || next != key)) atomicMax(&B[min(key - 1u, last)], val);
-  }
-}
 
 // What the last row of a run knows of its class
 struct NgClass {
@@ -270,8 +231,6 @@ struct NgOpts {
   uint64_t min_count = 2, top = 0;
 };
 
-static int bit_width(uint64_t v) { return v ? 64 - __builtin_clzll((unsigned long long)v) : 0; }
-
 // the device bytes a build of the LCP array takes while it runs (lcp_prepare's own sum)
 static uint64_t ng_lcp_build_bytes(const Index *h) {
   const uint64_t n = h->n;
@@ -281,16 +240,13 @@ static uint64_t ng_lcp_build_bytes(const Index *h) {
 // the device bytes ngrams_run allocates before a length's selected classes are known, the inversion's temporaries included
 static uint64_t ngrams_bytes(const Index *h, const NgOpts &o) {
   const uint64_t n = h->n;
-  uint64_t b = 8 * n + 4 * scan_partials(n) + 64 + 8 * (uint64_t)o.bins;               // A, S, the scan, the summary, the spectrum
+  uint64_t b = 8 * n + ScanSpace::bytes(n) + 64 + 8 * (uint64_t)o.bins;               // A, S, the scan, the summary, the spectrum
   if (o.pos) b += 4 * n + lcp_text_bytes(n) + 4 * n + (o.stop ? 4 * n : 0) + locate_invert_text_bytes(h);   // SA, s, B, P
   return b;
 }
 
 // ... and the sort's, for `sel` selected classes
-static uint64_t ngrams_sort_bytes(uint64_t sel, bool pos) {
-  const uint64_t hist_words = 256 * radix_tiles(sel);
-  return 2 * 12 * sel + 4 * hist_words + 4 * scan_partials(std::max(sel, hist_words)) + (pos ? 4 * sel : 0);
-}
+static uint64_t ngrams_sort_bytes(uint64_t sel, bool pos) { return SortSpace::bytes(sel) + (pos ? 4 * sel : 0); }
 
 static uint64_t ngrams_need(const Index *h, const NgOpts &o) {
   const uint64_t own = ngrams_bytes(h, o);
@@ -326,10 +282,8 @@ static int ngrams_first_long_row(const Index *h, uint64_t L, hipStream_t st, uin
     const uint64_t walks = (L - j - 1 + c - 1) / c;             // the starts i with i c + j + 1 < L
     HIP_TRY(launch_lf_walk(h, M + j * nchk, walks, 1, nullptr, M + (j + 1) * nchk, st), "k_lf_walk");
   }
-  hipLaunchKernelGGL(k_ng_short_mark, dim3(flat_grid(c * nchk)), dim3(kNgThreads), 0, st, M, L, c, nchk, flag);
-  HIP_TRY(hipGetLastError(), "k_ng_short_mark");
-  hipLaunchKernelGGL(k_ng_short_mex, dim3(flat_grid(L + 1)), dim3(kNgThreads), 0, st, flag, L, best);
-  HIP_TRY(hipGetLastError(), "k_ng_short_mex");
+  LAUNCH("k_ng_short_mark", k_ng_short_mark, dim3(flat_grid(c * nchk)), dim3(kNgThreads), st, M, L, c, nchk, flag);
+  LAUNCH("k_ng_short_mex", k_ng_short_mex, dim3(flat_grid(L + 1)), dim3(kNgThreads), st, flag, L, best);
   unsigned long long got = 0;
   HIP_TRY(hipMemcpyAsync(&got, best, 8, hipMemcpyDeviceToHost, st), "D2H(short rows)");
   HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
@@ -365,12 +319,13 @@ static int ngrams_run(const Index *h, const uint32_t *lengths, size_t k, const N
   Events<8> ev;
   HIP_TRY(ev.create(), "hipEventCreate");
   DevMem mem;
-  uint32_t *sa = nullptr, *A = nullptr, *B = nullptr, *S = nullptr, *P = nullptr, *partials = nullptr;
+  uint32_t *sa = nullptr, *A = nullptr, *B = nullptr, *S = nullptr, *P = nullptr;
+  ScanSpace scan;
   uint8_t *s = nullptr;
   unsigned long long *res = nullptr, *spec = nullptr;
   DEV_ALLOC(mem, A, 4 * n, "ngrams classes");
   DEV_ALLOC(mem, S, 4 * n, "ngrams slots");
-  DEV_ALLOC(mem, partials, 4 * scan_partials(n), "ngrams scan");
+  if ((rc = scan.alloc(mem, n, "ngrams scan"))) return rc;
   DEV_ALLOC(mem, res, 64, "ngrams summary");
   if (o.bins) DEV_ALLOC(mem, spec, 8 * (uint64_t)o.bins, "ngrams spectrum");
   uint64_t launches = 0;
@@ -383,9 +338,8 @@ static int ngrams_run(const Index *h, const uint32_t *lengths, size_t k, const N
     HIP_TRY(hipMemsetAsync(s, 0, lcp_text_bytes(n), st), "hipMemsetAsync");
     if ((rc = locate_invert_text(h, st, sa, s))) return rc;
     if (o.stop) {
-      hipLaunchKernelGGL(k_ng_stops, dim3(flat_grid(m)), dim3(kNgThreads), 0, st, s, m, o.stop, P);
-      HIP_TRY(hipGetLastError(), "k_ng_stops");
-      HIP_TRY(scan_u32(P, m, kScanMax, false, partials, st), "scan");
+      HIP_TRY(launch_stops(s, m, o.stop, P, st), "k_ng_stops");
+      HIP_TRY(scan.max(P, m, false, st), "scan");
       launches++;
     }
     HIP_TRY(ev.record(1, st), "hipEventRecord");
@@ -393,7 +347,7 @@ static int ngrams_run(const Index *h, const uint32_t *lengths, size_t k, const N
     info->invert_ms = ev.ms(0, 1);
   }
   const unsigned grid_n = flat_grid(n);
-  const int sp_bits = std::max(1, bit_width(n - 1));
+  const int sp_bits = bits_for(n - 1);
   unsigned long long *out = static_cast<unsigned long long *>(d_out);
   for (size_t j = 0; j < k; j++) {
     const uint32_t L = lengths[j];
@@ -405,21 +359,16 @@ static int ngrams_run(const Index *h, const uint32_t *lengths, size_t k, const N
       HIP_TRY(hipMemsetAsync(res, 0, 64, st), "hipMemsetAsync");
       if (o.bins) HIP_TRY(hipMemsetAsync(spec, 0, 8 * (uint64_t)o.bins, st), "hipMemsetAsync");
       HIP_TRY(ev.record(2, st), "hipEventRecord");
-      hipLaunchKernelGGL(k_ng_heads, dim3(grid_n), dim3(kNgThreads), 0, st, lcp, n, L, A, B);
-      HIP_TRY(hipGetLastError(), "k_ng_heads");
-      HIP_TRY(scan_u32(A, n, kScanMax, false, partials, st), "scan");
+      HIP_TRY(launch_class_heads(lcp, n, L, A, B, st), "k_ng_heads");
+      HIP_TRY(scan.max(A, n, false, st), "scan");
       if (o.pos) {
-        hipLaunchKernelGGL(k_ng_classmax, dim3(grid_n), dim3(kNgThreads), 0, st, lcp, sa, A, n, L, B);
-        HIP_TRY(hipGetLastError(), "k_ng_classmax");
-        hipLaunchKernelGGL(k_ng_class<true>, dim3(grid_n), dim3(kNgThreads), 0, st, lcp, sa, A, B, P, n, L, o.min_count, o.bins, S, spec,
-                           res);
+        HIP_TRY(launch_class_max(lcp, sa, A, n, L, B, st), "k_ng_classmax");
+        LAUNCH("k_ng_class", k_ng_class<true>, dim3(grid_n), dim3(kNgThreads), st, lcp, sa, A, B, P, n, L, o.min_count, o.bins, S, spec, res);
       } else {
-        hipLaunchKernelGGL(k_ng_class<false>, dim3(grid_n), dim3(kNgThreads), 0, st, lcp, sa, A, B, P, n, L, o.min_count, o.bins, S, spec,
-                           res);
+        LAUNCH("k_ng_class", k_ng_class<false>, dim3(grid_n), dim3(kNgThreads), st, lcp, sa, A, B, P, n, L, o.min_count, o.bins, S, spec, res);
       }
-      HIP_TRY(hipGetLastError(), "k_ng_class");
       HIP_TRY(ev.record(3, st), "hipEventRecord");
-      HIP_TRY(scan_u32(S, n, kScanSum, false, partials, st), "scan");
+      HIP_TRY(scan.sum(S, n, false, st), "scan");
       HIP_TRY(ev.record(4, st), "hipEventRecord");
       HIP_TRY(hipMemcpyAsync(&selected, S + (n - 1), 4, hipMemcpyDeviceToHost, st), "D2H(selected)");
       HIP_TRY(hipMemcpyAsync(host, res, 32, hipMemcpyDeviceToHost, st), "D2H(summary)");
@@ -456,42 +405,32 @@ static int ngrams_run(const Index *h, const uint32_t *lengths, size_t k, const N
       const uint64_t room = cap > base ? cap - base : 0, writes = std::min(sm.records, room);
       if (writes && o.order == FMX_NGRAMS_BY_ROW) {
         HIP_TRY(ev.record(5, st), "hipEventRecord");
-        if (o.pos) hipLaunchKernelGGL(k_ng_write<true>, dim3(grid_n), dim3(kNgThreads), 0, st, sa, A, B, S, n, L, sm.records, base, cap, out);
-        else hipLaunchKernelGGL(k_ng_write<false>, dim3(grid_n), dim3(kNgThreads), 0, st, sa, A, B, S, n, L, sm.records, base, cap, out);
-        HIP_TRY(hipGetLastError(), "k_ng_write");
+        if (o.pos) LAUNCH("k_ng_write", k_ng_write<true>, dim3(grid_n), dim3(kNgThreads), st, sa, A, B, S, n, L, sm.records, base, cap, out);
+        else LAUNCH("k_ng_write", k_ng_write<false>, dim3(grid_n), dim3(kNgThreads), st, sa, A, B, S, n, L, sm.records, base, cap, out);
         HIP_TRY(ev.record(6, st), "hipEventRecord");
         HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
         launches++;
         info->select_ms += ev.ms(5, 6);
       } else if (writes) {
-        const uint64_t sel = selected, hist_words = 256 * radix_tiles(sel);
+        const uint64_t sel = selected;
         if ((rc = device_room(ngrams_sort_bytes(sel, o.pos), "fmx_ngrams (the sort)"))) return rc;
         DevMem sortmem;
-        unsigned long long *k0 = nullptr, *k1 = nullptr;
-        uint32_t *v0 = nullptr, *v1 = nullptr, *hist = nullptr, *sort_partials = nullptr, *F = nullptr;
-        DEV_ALLOC(sortmem, k0, 8 * sel, "ngrams sort");
-        DEV_ALLOC(sortmem, k1, 8 * sel, "ngrams sort");
-        DEV_ALLOC(sortmem, v0, 4 * sel, "ngrams sort");
-        DEV_ALLOC(sortmem, v1, 4 * sel, "ngrams sort");
-        DEV_ALLOC(sortmem, hist, 4 * hist_words, "ngrams sort");
-        DEV_ALLOC(sortmem, sort_partials, 4 * scan_partials(std::max(sel, hist_words)), "ngrams sort");
+        SortSpace ws;
+        uint32_t *F = nullptr;
+        if ((rc = ws.alloc(sortmem, sel, "ngrams sort"))) return rc;
         if (o.pos) DEV_ALLOC(sortmem, F, 4 * sel, "ngrams first positions");
         HIP_TRY(ev.record(5, st), "hipEventRecord");
-        if (o.pos) hipLaunchKernelGGL(k_ng_keys<true>, dim3(grid_n), dim3(kNgThreads), 0, st, sa, A, B, S, n, L, sel, largest, sp_bits, k0, v0, F);
-        else hipLaunchKernelGGL(k_ng_keys<false>, dim3(grid_n), dim3(kNgThreads), 0, st, sa, A, B, S, n, L, sel, largest, sp_bits, k0, v0, F);
-        HIP_TRY(hipGetLastError(), "k_ng_keys");
+        if (o.pos) LAUNCH("k_ng_keys", k_ng_keys<true>, dim3(grid_n), dim3(kNgThreads), st, sa, A, B, S, n, L, sel, largest, sp_bits, ws.keys(), ws.vals(), F);
+        else LAUNCH("k_ng_keys", k_ng_keys<false>, dim3(grid_n), dim3(kNgThreads), st, sa, A, B, S, n, L, sel, largest, sp_bits, ws.keys(), ws.vals(), F);
         HIP_TRY(ev.record(6, st), "hipEventRecord");
-        unsigned long long *key = k0, *key_alt = k1;
-        uint32_t *val = v0, *val_alt = v1;
-        int passes = 0;
-        const int bits = sp_bits + std::max(1, bit_width(largest - std::min<uint64_t>(o.min_count, largest)));
-        HIP_TRY(radix_sort(&key, &val, &key_alt, &val_alt, sel, bits, hist, sort_partials, st, &passes), "radix sort");
+        const int bits = sp_bits + bits_for(largest - std::min<uint64_t>(o.min_count, largest));
+        HIP_TRY(ws.sort(sel, bits, st), "radix sort");
         HIP_TRY(ev.record(7, st), "hipEventRecord");
-        hipLaunchKernelGGL(k_ng_emit, dim3(flat_grid(writes)), dim3(kNgThreads), 0, st, key, val, F, writes, sel, largest, sp_bits, base, out);
-        HIP_TRY(hipGetLastError(), "k_ng_emit");
+        LAUNCH("k_ng_emit", k_ng_emit, dim3(flat_grid(writes)), dim3(kNgThreads), st, ws.keys(), ws.vals(), F, writes, sel, largest,
+               sp_bits, base, out);
         HIP_TRY(ev.record(0, st), "hipEventRecord");                    // (the inversion's pair of events is free by now)
         HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");      // the sort's buffers go with this block
-        launches += 2 + 3 * (uint64_t)passes;
+        launches += 2 + 3 * (uint64_t)ws.passes;
         info->select_ms += ev.ms(5, 6) + ev.ms(7, 0);
         info->sort_ms += ev.ms(6, 7);
       }

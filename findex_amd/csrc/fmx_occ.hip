@@ -6,14 +6,14 @@
 //   locate  : launch_locate_intervals (fmx_locate.hip): the scan of min(ep - sp, max_per), the expansion, the LF walks
 //   keys    : k_occ_keys     row j finds its record by a search in the offsets, forms pos = n - 1 - len - SA, applies the corpus
 //                            rule and writes a sort key over (group, pos, len); a dropped row sorts behind everything
-//   sort    : radix_sort (fmx_sufsort.hip) over the bits the call needs; when group, pos and len do not fit 64 bits, two stable
+//   sort    : SortSpace (fmx_order.h) over the bits the call needs; when group, pos and len do not fit 64 bits, two stable
 //             sorts: (pos, len) first, then the group gathered through the permutation (k_occ_regroup)
 //   select  : k_occ_spread   the sorted keys as G[] (group) and PL[] (pos << 16 | len)
 //             k_occ_heads    ALL: the first of each equal (group, pos, len); LONGEST: the last of each (group, pos) run
 //             DISJOINT       the LONGEST set compacted (k_occ_pick), next[] by a lower bound of (group, pos + len)
 //                            (k_occ_next), then ceil(log2(rows + 1)) rounds of mark[jump[i]] = 1 for marked i, jump = jump o jump
 //                            (k_occ_round): plain stores of the value 1, jump double-buffered
-//   compact : scan_u32 over the flags, k_occ_emit (32-byte records, the corpus map's raw offsets), k_occ_off (a lower bound
+//   compact : a scan (fmx_order.h) over the flags, k_occ_emit (32-byte records, the corpus map's raw offsets), k_occ_off (a lower bound
 //             per group)
 // No atomics anywhere: the same input gives the same bytes on every run.  Positions are u32 in the keys (n < 2^32).
 #include <fmx.h>
@@ -23,7 +23,7 @@
 #include <vector>
 
 #include "fmx_corpus_dev.h"
-#include "fmx_host.h"
+#include "fmx_order.h"
 
 namespace fmx {
 
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(kOccThreads) void k_occ_keys(const unsigned long lo
                                                           uint32_t *__restrict__ grp) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < rows; j += stride) {
-    const uint64_t i = co_upper(off, 0, k + 1, j) - 1;
+    const uint64_t i = upper_bound(off, 0, k + 1, j) - 1;
     const uint64_t s = sa[j], len = rec[i].len;
     uint64_t g = n_groups, pos = 0, ln = 0;
     if (s < n && s + len <= n - 1) {
@@ -236,7 +236,7 @@ __global__ __launch_bounds__(kOccThreads) void k_occ_off(const uint32_t *__restr
   if (len_dev) len = *len_dev;
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g <= n_groups; g += stride) {
-    const uint64_t j = len ? co_lower(G, 0, len, g) : 0;
+    const uint64_t j = len ? lower_bound(G, 0, len, g) : 0;
     out_off[g] = j ? incl[j - 1] : 0u;
   }
 }
@@ -249,16 +249,10 @@ struct OccInfo {
 };
 thread_local OccInfo g_occ_last;
 
-int bits_for(uint64_t v) {                           // the bits that hold 0 .. v
-  int b = 1;
-  while (b < 64 && (v >> b) != 0) b++;
-  return b;
-}
-
-// Device bytes of a call: per row the SA values (8), two key and two value buffers of the sort (24), the flags (4), and
-// with DISJOINT the compacted set, two jump buffers and the marks (24); the group array of the two-sort form (4); per
-// record the two interval ends and the offset (24); the sort's histograms and the scans' block totals.
-uint64_t occ_row_bytes(uint32_t mode, bool wide) { return 36 + (mode == FMX_OCC_DISJOINT ? 24 : 0) + (wide ? 4 : 0); }
+// Device bytes of a call beside the sort's workspace: per row the SA values (8), the flags (4), and with DISJOINT the
+// compacted set, two jump buffers and the marks (24); the group array of the two-sort form (4); per record the two interval
+// ends and the offset (24).
+uint64_t occ_row_bytes(uint32_t mode, bool wide) { return 12 + (mode == FMX_OCC_DISJOINT ? 24 : 0) + (wide ? 4 : 0); }
 
 // What the arguments alone decide (both forms), before a handle is looked at.
 int occ_args(const void *rec, size_t k, size_t n_groups, const fmx_occ_opts *opts, const void *out_off, const void *out, size_t cap,
@@ -317,8 +311,7 @@ int occ_run(const Index *h, const Corpus *c, const fmx_result *d_rec, uint64_t k
   uint64_t launches = 0;
   HIP_TRY(hipMemsetAsync(bad, 0, 16, st), "hipMemsetAsync");
   if (k) {
-    hipLaunchKernelGGL(k_occ_unpack, dim3(flat_grid(k)), dim3(kOccThreads), 0, st, d_rec, k, n, n_groups, sp, ep, bad);
-    HIP_TRY(hipGetLastError(), "k_occ_unpack");
+    LAUNCH("k_occ_unpack", k_occ_unpack, dim3(flat_grid(k)), dim3(kOccThreads), st, d_rec, k, n, n_groups, sp, ep, bad);
     launches++;
   }
   // the row counts first (no positions: cap 0), then room for exactly that many
@@ -344,9 +337,8 @@ int occ_run(const Index *h, const Corpus *c, const fmx_result *d_rec, uint64_t k
     return FMX_ERR_OVERFLOW;
   }
   if (rows == 0) {
-    hipLaunchKernelGGL(k_occ_off, dim3(flat_grid(n_groups + 1)), dim3(kOccThreads), 0, st, nullptr, nullptr, 0ull, nullptr, n_groups,
-                       d_out_off);
-    HIP_TRY(hipGetLastError(), "k_occ_off");
+    LAUNCH("k_occ_off", k_occ_off, dim3(flat_grid(n_groups + 1)), dim3(kOccThreads), st, nullptr, nullptr, 0ull, nullptr, n_groups,
+           d_out_off);
     HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     launches++;
     done();
@@ -358,23 +350,17 @@ int occ_run(const Index *h, const Corpus *c, const fmx_result *d_rec, uint64_t k
   f.lb = len_bits;
   const int gb = bits_for(n_groups);                 // groups 0 .. n_groups (n_groups: a dropped row)
   f.wide = f.pb + f.lb + gb > 64 ? 1 : 0;
-  const uint64_t nt = radix_tiles(rows), hist_words = 256 * nt, parts = scan_partials(std::max<uint64_t>(rows, hist_words));
-  if ((rc = device_room(occ_row_bytes(mode, f.wide) * rows + 4 * hist_words + 4 * parts + 8192, "fmx_occurrences"))) {
+  if ((rc = device_room(occ_row_bytes(mode, f.wide) * rows + SortSpace::bytes(rows) + 8192, "fmx_occurrences"))) {
     done();
     return rc;
   }
-  unsigned long long *pos = nullptr, *k0 = nullptr, *k1 = nullptr, *cPL = nullptr;
-  uint32_t *v0 = nullptr, *v1 = nullptr, *flag = nullptr, *grp = nullptr, *hist = nullptr, *partials = nullptr;
-  uint32_t *cG = nullptr, *ja = nullptr, *jb = nullptr, *mark = nullptr;
+  unsigned long long *pos = nullptr, *cPL = nullptr;
+  uint32_t *flag = nullptr, *grp = nullptr, *cG = nullptr, *ja = nullptr, *jb = nullptr, *mark = nullptr;
+  SortSpace ws;
   DEV_ALLOC(mem, pos, 8 * rows, "occurrences");
-  DEV_ALLOC(mem, k0, 8 * rows, "occurrences");
-  DEV_ALLOC(mem, k1, 8 * rows, "occurrences");
-  DEV_ALLOC(mem, v0, 4 * rows, "occurrences");
-  DEV_ALLOC(mem, v1, 4 * rows, "occurrences");
+  if ((rc = ws.alloc(mem, rows, "occurrences"))) return rc;
   DEV_ALLOC(mem, flag, 4 * rows, "occurrences");
   if (f.wide) DEV_ALLOC(mem, grp, 4 * rows, "occurrences");
-  DEV_ALLOC(mem, hist, 4 * hist_words, "occurrences");
-  DEV_ALLOC(mem, partials, 4 * parts, "occurrences");
   if (mode == FMX_OCC_DISJOINT) {
     DEV_ALLOC(mem, cPL, 8 * rows, "occurrences");
     DEV_ALLOC(mem, cG, 4 * rows, "occurrences");
@@ -389,46 +375,37 @@ int occ_run(const Index *h, const Corpus *c, const fmx_result *d_rec, uint64_t k
   launches += 3;
   HIP_TRY(ev.record(1, st), "hipEventRecord");
   // ---- keys and sort
-  hipLaunchKernelGGL(k_occ_keys, grid, block, 0, st, pos, (uint64_t)rows, off, k, d_rec, n, n_groups, has_map, map, f, k0, v0, grp);
-  HIP_TRY(hipGetLastError(), "k_occ_keys");
+  LAUNCH("k_occ_keys", k_occ_keys, grid, block, st, pos, (uint64_t)rows, off, k, d_rec, n, n_groups, has_map, map, f, ws.keys(), ws.vals(),
+         grp);
   launches++;
-  unsigned long long *key = k0, *key_alt = k1;
-  uint32_t *val = v0, *val_alt = v1;
-  int passes = 0;
   const unsigned long long *pl_in = nullptr;
   if (f.wide) {
-    HIP_TRY(radix_sort(&key, &val, &key_alt, &val_alt, rows, f.pb + kOccLenBits, hist, partials, st, &passes), "radix sort");
-    launches += 3 * (uint64_t)passes;
-    hipLaunchKernelGGL(k_occ_regroup, grid, block, 0, st, key, val, grp, (uint64_t)rows, pos, key_alt, val_alt);
-    HIP_TRY(hipGetLastError(), "k_occ_regroup");
+    HIP_TRY(ws.sort(rows, f.pb + kOccLenBits, st), "radix sort");
+    launches += 3 * (uint64_t)ws.passes;
+    LAUNCH("k_occ_regroup", k_occ_regroup, grid, block, st, ws.keys(), ws.vals(), grp, (uint64_t)rows, pos, ws.free_keys(), ws.free_vals());
     launches++;
-    std::swap(key, key_alt);
-    std::swap(val, val_alt);
-    HIP_TRY(radix_sort(&key, &val, &key_alt, &val_alt, rows, gb, hist, partials, st, &passes), "radix sort");
-    launches += 3 * (uint64_t)passes;
+    ws.swap();
+    HIP_TRY(ws.sort(rows, gb, st), "radix sort");
+    launches += 3 * (uint64_t)ws.passes;
     pl_in = pos;
   } else {
-    HIP_TRY(radix_sort(&key, &val, &key_alt, &val_alt, rows, f.pb + f.lb + gb, hist, partials, st, &passes), "radix sort");
-    launches += 3 * (uint64_t)passes;
+    HIP_TRY(ws.sort(rows, f.pb + f.lb + gb, st), "radix sort");
+    launches += 3 * (uint64_t)ws.passes;
   }
   HIP_TRY(ev.record(2, st), "hipEventRecord");
   // ---- select: G in the free value buffer; PL in the free key buffer
-  uint32_t *G = val_alt;
-  unsigned long long *PL = key_alt;
-  hipLaunchKernelGGL(k_occ_spread, grid, block, 0, st, key, val, pl_in, (uint64_t)rows, f, G, PL);
-  HIP_TRY(hipGetLastError(), "k_occ_spread");
-  hipLaunchKernelGGL(k_occ_heads, grid, block, 0, st, G, PL, (uint64_t)rows, (uint32_t)n_groups, mode == FMX_OCC_ALL ? 0 : 1, flag);
-  HIP_TRY(hipGetLastError(), "k_occ_heads");
+  uint32_t *G = ws.free_vals();
+  unsigned long long *PL = ws.free_keys();
+  LAUNCH("k_occ_spread", k_occ_spread, grid, block, st, ws.keys(), ws.vals(), pl_in, (uint64_t)rows, f, G, PL);
+  LAUNCH("k_occ_heads", k_occ_heads, grid, block, st, G, PL, (uint64_t)rows, (uint32_t)n_groups, mode == FMX_OCC_ALL ? 0 : 1, flag);
   launches += 2;
   const uint32_t *len_dev = nullptr;
   if (mode == FMX_OCC_DISJOINT) {
-    HIP_TRY(scan_u32(flag, rows, kScanSum, false, partials, st), "scan");
-    hipLaunchKernelGGL(k_occ_pick, grid, block, 0, st, G, PL, flag, (uint64_t)rows, cG, cPL);
-    HIP_TRY(hipGetLastError(), "k_occ_pick");
+    HIP_TRY(ws.scan().sum(flag, rows, false, st), "scan");
+    LAUNCH("k_occ_pick", k_occ_pick, grid, block, st, G, PL, flag, (uint64_t)rows, cG, cPL);
     uint32_t *m_dev = reinterpret_cast<uint32_t *>(bad) + 1;         // the size of the compacted set stays on the device
     HIP_TRY(hipMemcpyAsync(m_dev, flag + (rows - 1), 4, hipMemcpyDeviceToDevice, st), "D2D");
-    hipLaunchKernelGGL(k_occ_next, grid, block, 0, st, cG, cPL, m_dev, ja, mark);
-    HIP_TRY(hipGetLastError(), "k_occ_next");
+    LAUNCH("k_occ_next", k_occ_next, grid, block, st, cG, cPL, m_dev, ja, mark);
     int rounds = 1;
     while ((1ull << rounds) < rows + 1) rounds++;
     for (int r = 0; r < rounds; r++) {
@@ -436,8 +413,7 @@ int occ_run(const Index *h, const Corpus *c, const fmx_result *d_rec, uint64_t k
       std::swap(ja, jb);
     }
     HIP_TRY(hipGetLastError(), "k_occ_round");
-    hipLaunchKernelGGL(k_occ_marks, grid, block, 0, st, m_dev, mark, (uint64_t)rows, flag);
-    HIP_TRY(hipGetLastError(), "k_occ_marks");
+    LAUNCH("k_occ_marks", k_occ_marks, grid, block, st, m_dev, mark, (uint64_t)rows, flag);
     launches += 6 + (uint64_t)rounds;
     G = cG;
     PL = cPL;
@@ -445,12 +421,10 @@ int occ_run(const Index *h, const Corpus *c, const fmx_result *d_rec, uint64_t k
   }
   HIP_TRY(ev.record(3, st), "hipEventRecord");
   // ---- compact
-  HIP_TRY(scan_u32(flag, rows, kScanSum, false, partials, st), "scan");
-  hipLaunchKernelGGL(k_occ_off, dim3(flat_grid(n_groups + 1)), block, 0, st, G, flag, (uint64_t)rows, len_dev, n_groups, d_out_off);
-  HIP_TRY(hipGetLastError(), "k_occ_off");
+  HIP_TRY(ws.scan().sum(flag, rows, false, st), "scan");
+  LAUNCH("k_occ_off", k_occ_off, dim3(flat_grid(n_groups + 1)), block, st, G, flag, (uint64_t)rows, len_dev, n_groups, d_out_off);
   if (cap) {
-    hipLaunchKernelGGL(k_occ_emit, grid, block, 0, st, G, PL, flag, (uint64_t)rows, len_dev, has_map, map, cap, d_out);
-    HIP_TRY(hipGetLastError(), "k_occ_emit");
+    LAUNCH("k_occ_emit", k_occ_emit, grid, block, st, G, PL, flag, (uint64_t)rows, len_dev, has_map, map, cap, d_out);
   }
   launches += 4;
   HIP_TRY(ev.record(4, st), "hipEventRecord");

@@ -5,11 +5,12 @@
 // suffixes share their first L bytes are a maximal run of rows with LCP[r] >= L between neighbours: a CLASS; LCP[r] >= L
 // implies that both suffixes have L bytes in front of the sentinel, so every row of such a run is a window.
 //
-// One call: the inversion (SA and s), the stop scan when there is a stop byte, then per threshold L
+// One call: the inversion (SA and s), the stop scan when there is a stop byte, then per threshold L (the stops, the class
+// heads and the class maxima are fmx_order.h's kernels, shared with fmx_ngrams.hip)
 //
-//   k_rep_heads    : A[r] = r + 1 where a class begins (r == 0 or LCP[r - 1] < L), else 0; B[r] = 0.  A max-scan turns A
+//   class heads    : A[r] = r + 1 where a class begins (r == 0 or LCP[r - 1] < L), else 0; B[r] = 0.  A max-scan turns A
 //                    into (head row of r's class) + 1: the class id.
-//   k_rep_classmax : B[head] = the largest SA of the class, over the rows of repeated classes only (LCP[r - 1] >= L or
+//   class maxima   : B[head] = the largest SA of the class, over the rows of repeated classes only (LCP[r - 1] >= L or
 //                    LCP[r] >= L).  The lanes of a wave hold consecutive rows, so a class is a stretch of lanes: a segmented
 //                    max over the wave first, one atomicMax per class and wave -- a run of one letter is ONE class of n rows.
 //   k_rep_scatter  : flag8[t] = 1 for the rows to flag (all of a repeated class, or all but the one with the largest SA: the
@@ -31,7 +32,7 @@
 
 #include <string>
 
-#include "fmx_host.h"
+#include "fmx_order.h"
 
 namespace fmx {
 
@@ -39,45 +40,6 @@ static_assert(FMX_REPEATS_TILE == kScanTile, "FMX_REPEATS_TILE is the scan's blo
 static_assert(sizeof(fmx_repeat_opts) == 8 && sizeof(fmx_repeat_range) == 16 && sizeof(fmx_repeat_summary) == 48, "fmx.h");
 
 constexpr int kRepThreads = 256;
-
-// P[t] = t + 1 where T[t] is the stop byte, else 0 (T[t] = s[m - 1 - t])
-__global__ __launch_bounds__(kRepThreads) void k_rep_stops(const uint8_t *__restrict__ s, uint64_t m, uint32_t stop,
-                                                           uint32_t *__restrict__ P) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < m; t += stride)
-    P[t] = s[m - 1 - t] == stop ? (uint32_t)t + 1u : 0u;
-}
-
-__global__ __launch_bounds__(kRepThreads) void k_rep_heads(const uint32_t *__restrict__ lcp, uint64_t n, uint32_t L,
-                                                           uint32_t *__restrict__ A, uint32_t *__restrict__ B) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += stride) {
-    A[r] = (r == 0 || lcp[r - 1] < L) ? (uint32_t)r + 1u : 0u;
-    B[r] = 0u;
-  }
-}
-
-// A: the scanned heads.  The loop's trip count is the same for every lane of a workgroup: all 64 lanes shuffle.
-__global__ __launch_bounds__(kRepThreads) void k_rep_classmax(const uint32_t *__restrict__ lcp, const uint32_t *__restrict__ sa,
-                                                              const uint32_t *__restrict__ A, uint64_t n, uint32_t L,
-                                                              uint32_t *__restrict__ B) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  const int lane = threadIdx.x & 63;
-  const uint32_t last = (uint32_t)(n - 1);
-  for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x; b < n; b += stride) {
-    const uint64_t r = b + threadIdx.x;
-    const bool rep = r < n && ((r > 0 && lcp[r - 1] >= L) || lcp[r] >= L);
-    const uint32_t key = rep ? A[r] : 0u;                     // >= 1 for a row of a repeated class
-    uint32_t val = rep ? min(sa[r], last) : 0u;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint32_t ok = __shfl_up(key, d, 64), ov = __shfl_up(val, d, 64);
-      if (lane >= d && ok == key) val = max(val, ov);
-    }
-    const uint32_t next = __shfl_down(key, 1, 64);
-    if (rep && (lane == 63 || next != key)) atomicMax(&B[min(key - 1u, last)], val);
-  }
-}
 
 // res[0] classes, res[1] flagged windows, res[2] max of size << 32 | (0xFFFFFFFF - smallest t)
 __global__ __launch_bounds__(kRepThreads) void k_rep_scatter(const uint32_t *__restrict__ lcp, const uint32_t *__restrict__ sa,
@@ -196,7 +158,7 @@ static uint64_t lcp_build_bytes(const Index *h) {
 // the device bytes repeats_run allocates, the inversion's temporaries included
 static uint64_t repeats_bytes(const Index *h, bool stop) {
   const uint64_t n = h->n;
-  return 4 * n + lcp_text_bytes(n) + 8 * n + (stop ? 4 * n : 0) + n + 4 * scan_partials(n) + 64 + locate_invert_text_bytes(h);
+  return 4 * n + lcp_text_bytes(n) + 8 * n + (stop ? 4 * n : 0) + n + ScanSpace::bytes(n) + 64 + locate_invert_text_bytes(h);
 }
 
 static bool lcp_built(const Index *h) {
@@ -233,7 +195,8 @@ static int repeats_run(const Index *h, const uint32_t *min_len, size_t k, uint32
   Events<6> ev;
   HIP_TRY(ev.create(), "hipEventCreate");
   DevMem mem;
-  uint32_t *sa = nullptr, *A = nullptr, *B = nullptr, *P = nullptr, *partials = nullptr;
+  uint32_t *sa = nullptr, *A = nullptr, *B = nullptr, *P = nullptr;
+  ScanSpace scan;
   uint8_t *s = nullptr, *flag8 = nullptr;
   unsigned long long *res = nullptr;
   DEV_ALLOC(mem, sa, 4 * n, "repeats suffix array");
@@ -242,16 +205,15 @@ static int repeats_run(const Index *h, const uint32_t *min_len, size_t k, uint32
   DEV_ALLOC(mem, B, 4 * n, "repeats classes");
   if (stop) DEV_ALLOC(mem, P, 4 * n, "repeats stop scan");
   DEV_ALLOC(mem, flag8, n, "repeats flags");
-  DEV_ALLOC(mem, partials, 4 * scan_partials(n), "repeats scan");
+  if ((rc = scan.alloc(mem, n, "repeats scan"))) return rc;
   DEV_ALLOC(mem, res, 64, "repeats summary");
   uint64_t launches = 0;
   HIP_TRY(ev.record(0, st), "hipEventRecord");
   HIP_TRY(hipMemsetAsync(s, 0, lcp_text_bytes(n), st), "hipMemsetAsync");
   if ((rc = locate_invert_text(h, st, sa, s))) return rc;
   if (stop) {
-    hipLaunchKernelGGL(k_rep_stops, dim3(flat_grid(m)), dim3(kRepThreads), 0, st, s, m, stop, P);
-    HIP_TRY(hipGetLastError(), "k_rep_stops");
-    HIP_TRY(scan_u32(P, m, kScanMax, false, partials, st), "scan");
+    HIP_TRY(launch_stops(s, m, stop, P, st), "k_rep_stops");
+    HIP_TRY(scan.max(P, m, false, st), "scan");
     launches++;
   }
   HIP_TRY(ev.record(1, st), "hipEventRecord");
@@ -267,24 +229,18 @@ static int repeats_run(const Index *h, const uint32_t *min_len, size_t k, uint32
       HIP_TRY(hipMemsetAsync(res, 0, 64, st), "hipMemsetAsync");
       HIP_TRY(hipMemsetAsync(flag8, 0, n, st), "hipMemsetAsync");
       HIP_TRY(ev.record(2, st), "hipEventRecord");
-      hipLaunchKernelGGL(k_rep_heads, dim3(grid_n), dim3(kRepThreads), 0, st, lcp, n, L, A, B);
-      HIP_TRY(hipGetLastError(), "k_rep_heads");
-      HIP_TRY(scan_u32(A, n, kScanMax, false, partials, st), "scan");
-      hipLaunchKernelGGL(k_rep_classmax, dim3(grid_n), dim3(kRepThreads), 0, st, lcp, sa, A, n, L, B);
-      HIP_TRY(hipGetLastError(), "k_rep_classmax");
-      hipLaunchKernelGGL(k_rep_scatter, dim3(grid_n), dim3(kRepThreads), 0, st, lcp, sa, A, B, P, n, L, later, flag8, res);
-      HIP_TRY(hipGetLastError(), "k_rep_scatter");
+      HIP_TRY(launch_class_heads(lcp, n, L, A, B, st), "k_rep_heads");
+      HIP_TRY(scan.max(A, n, false, st), "scan");
+      HIP_TRY(launch_class_max(lcp, sa, A, n, L, B, st), "k_rep_classmax");
+      LAUNCH("k_rep_scatter", k_rep_scatter, dim3(grid_n), dim3(kRepThreads), st, lcp, sa, A, B, P, n, L, later, flag8, res);
       HIP_TRY(ev.record(3, st), "hipEventRecord");
-      hipLaunchKernelGGL(k_rep_seed, dim3(grid_m), dim3(kRepThreads), 0, st, flag8, P, m, L, B);
-      HIP_TRY(hipGetLastError(), "k_rep_seed");
-      HIP_TRY(scan_u32(B, m, kScanMax, false, partials, st), "scan");
-      hipLaunchKernelGGL(k_rep_bounds, dim3(grid_m), dim3(kRepThreads), 0, st, B, m, L, A, res);
-      HIP_TRY(hipGetLastError(), "k_rep_bounds");
+      LAUNCH("k_rep_seed", k_rep_seed, dim3(grid_m), dim3(kRepThreads), st, flag8, P, m, L, B);
+      HIP_TRY(scan.max(B, m, false, st), "scan");
+      LAUNCH("k_rep_bounds", k_rep_bounds, dim3(grid_m), dim3(kRepThreads), st, B, m, L, A, res);
       HIP_TRY(ev.record(4, st), "hipEventRecord");
-      HIP_TRY(scan_u32(A, m, kScanSum, false, partials, st), "scan");
-      hipLaunchKernelGGL(k_rep_write, dim3(grid_m), dim3(kRepThreads), 0, st, B, A, m, L, off[j], cap,
-                         static_cast<unsigned long long *>(d_out));
-      HIP_TRY(hipGetLastError(), "k_rep_write");
+      HIP_TRY(scan.sum(A, m, false, st), "scan");
+      LAUNCH("k_rep_write", k_rep_write, dim3(grid_m), dim3(kRepThreads), st, B, A, m, L, off[j], cap,
+             static_cast<unsigned long long *>(d_out));
       HIP_TRY(ev.record(5, st), "hipEventRecord");
       HIP_TRY(hipMemcpyAsync(&total, A + (m - 1), 4, hipMemcpyDeviceToHost, st), "D2H(ranges)");
       HIP_TRY(hipMemcpyAsync(host, res, 32, hipMemcpyDeviceToHost, st), "D2H(summary)");

@@ -13,9 +13,8 @@
 //              Then the new group heads are flagged, max-scanned and scattered into rank[], singletons leave the list.
 //   emit     : bwt[j] = s[sa[j] - 1]; the row with sa[j] == 0 is eof; the 256-entry histogram of the text.
 //
-// Radix sort: 8-bit digits, one pass = k_sa_hist (per 4096-key tile histogram, digit-major) + exclusive scan +
-// k_sa_scatter (stable: a tile goes through in 256-key chunks, each key's place among its digit's keys from eight
-// wave ballots).  Everything is u32 index / u64 key; a loop index is u64, so positions >= 2^31 stay unsigned throughout.
+// The radix sort and the scans are fmx_order.h's (SortSpace).  Everything is u32 index / u64 key; a loop index is u64, so
+// positions >= 2^31 stay unsigned throughout.
 //
 // Working set (bytes per suffix, n = len + 1): s (1) + sa (4) + rank (4) + two key buffers (16) + two value buffers (8)
 // + the active list (4) = 37, plus the digit histograms (1/4) and the scan partials (< 1/500).  The host-pointer entry
@@ -29,14 +28,11 @@
 #include <string>
 #include <vector>
 
-#include "fmx_host.h"
+#include "fmx_order.h"
 
 namespace fmx {
 
 constexpr int kSaThreads = 256;
-constexpr uint32_t kSaTile = 4096;                  // keys per radix tile: 16 chunks of 256
-
-__device__ __forceinline__ uint32_t scan_op(int op, uint32_t a, uint32_t b) { return op == kScanMax ? (a > b ? a : b) : a + b; }
 
 static unsigned sa_grid(uint64_t m) {
   const uint64_t b = (m + kSaThreads - 1) / kSaThreads;
@@ -87,101 +83,6 @@ __global__ __launch_bounds__(kSaThreads) void k_sa_keys(const uint32_t *__restri
     key[k] = ((unsigned long long)rank[i] << bits) | r2;
     val[k] = i;
   }
-}
-
-// ---- LSD radix sort of (u64 key, u32 value), 8 bits per pass
-__global__ __launch_bounds__(kSaThreads) void k_sa_hist(const unsigned long long *__restrict__ key, uint64_t m, int shift,
-                                                        uint32_t *__restrict__ hist /* [256][ntiles] */, uint64_t ntiles) {
-  __shared__ uint32_t h[256];
-  h[threadIdx.x] = 0;
-  __syncthreads();
-  const uint64_t base = (uint64_t)blockIdx.x * kSaTile;
-  for (uint32_t c = 0; c < kSaTile; c += kSaThreads) {
-    const uint64_t idx = base + c + threadIdx.x;
-    if (idx < m) atomicAdd(&h[(key[idx] >> shift) & 255u], 1u);
-  }
-  __syncthreads();
-  hist[(uint64_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
-}
-
-// hist: the exclusive scan of k_sa_hist's output = where this tile's first key of each digit goes.  Stable: inside a
-// 256-key chunk a key's place is its lane rank among the wave's keys of its digit (eight ballots) plus the counts of
-// the waves before it; chunks follow each other through base[].
-__global__ __launch_bounds__(kSaThreads) void k_sa_scatter(const unsigned long long *__restrict__ kin,
-                                                           const uint32_t *__restrict__ vin,
-                                                           unsigned long long *__restrict__ kout,
-                                                           uint32_t *__restrict__ vout, uint64_t m, int shift,
-                                                           const uint32_t *__restrict__ hist, uint64_t ntiles) {
-  __shared__ uint32_t base[256];
-  __shared__ uint32_t wc[kSaThreads / 64][256];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const unsigned long long lt = (1ull << lane) - 1;
-  base[tid] = hist[(uint64_t)tid * ntiles + blockIdx.x];
-  const uint64_t tile = (uint64_t)blockIdx.x * kSaTile;
-  for (uint32_t c = 0; c < kSaTile; c += kSaThreads) {
-    const uint64_t idx = tile + c + tid;
-    const bool valid = idx < m;
-    const unsigned long long k = valid ? kin[idx] : 0ull;
-    const uint32_t v = valid ? vin[idx] : 0u;
-    const uint32_t d = (uint32_t)(k >> shift) & 255u;
-    for (int w = 0; w < kSaThreads / 64; w++) wc[w][tid] = 0;
-    __syncthreads();
-    unsigned long long mm = __ballot(valid);
-    for (int b = 0; b < 8; b++) {
-      const bool bit = (d >> b) & 1u;
-      const unsigned long long bb = __ballot(bit);
-      mm &= bit ? bb : ~bb;
-    }
-    const uint32_t r = (uint32_t)__popcll(mm & lt);
-    if (valid && r == 0) wc[wave][d] = (uint32_t)__popcll(mm);
-    __syncthreads();
-    if (valid) {
-      uint32_t dst = base[d] + r;
-      for (int w = 0; w < wave; w++) dst += wc[w][d];
-      kout[dst] = k;
-      vout[dst] = v;
-    }
-    __syncthreads();
-    uint32_t add = 0;
-    for (int w = 0; w < kSaThreads / 64; w++) add += wc[w][tid];
-    base[tid] += add;
-    __syncthreads();
-  }
-}
-
-// ---- scans of u32 (sum or max; inclusive or exclusive), 2048 elements per block, block totals scanned recursively
-__global__ __launch_bounds__(kSaThreads) void k_sa_scan_tile(uint32_t *__restrict__ d, uint64_t len,
-                                                             uint32_t *__restrict__ sums, int op, int exclusive) {
-  __shared__ uint32_t t[kSaThreads];
-  const uint64_t base = (uint64_t)blockIdx.x * kScanTile + (uint64_t)threadIdx.x * 8;
-  uint32_t x[8], acc = 0;                   // 0 is the identity of both operators
-  for (int e = 0; e < 8; e++) {
-    x[e] = base + e < len ? d[base + e] : 0u;
-    acc = scan_op(op, acc, x[e]);
-  }
-  t[threadIdx.x] = acc;
-  __syncthreads();
-  for (int off = 1; off < kSaThreads; off <<= 1) {
-    const uint32_t y = (int)threadIdx.x >= off ? t[threadIdx.x - off] : 0u;
-    __syncthreads();
-    t[threadIdx.x] = scan_op(op, t[threadIdx.x], y);
-    __syncthreads();
-  }
-  uint32_t run = threadIdx.x ? t[threadIdx.x - 1] : 0u;
-  for (int e = 0; e < 8; e++) {
-    const uint32_t before = run;
-    run = scan_op(op, run, x[e]);
-    if (base + e < len) d[base + e] = exclusive ? before : run;
-  }
-  if (threadIdx.x == kSaThreads - 1) sums[blockIdx.x] = t[kSaThreads - 1];
-}
-
-__global__ __launch_bounds__(kSaThreads) void k_sa_scan_add(uint32_t *__restrict__ d, uint64_t len,
-                                                            const uint32_t *__restrict__ sums, int op) {
-  const uint32_t carry = sums[blockIdx.x];
-  const uint64_t base = (uint64_t)blockIdx.x * kScanTile;
-  for (uint32_t e = threadIdx.x; e < kScanTile; e += kSaThreads)
-    if (base + e < len) d[base + e] = scan_op(op, carry, d[base + e]);
 }
 
 // ---- group heads and ranks
@@ -256,52 +157,6 @@ __global__ void k_sa_eof_fill(const uint8_t *__restrict__ s, const uint32_t *__r
 // ---- host side
 namespace {
 
-uint64_t ntiles_of(uint64_t m) { return (m + kSaTile - 1) / kSaTile; }
-
-}  // namespace
-
-// (scan_partials, scan_u32, radix_tiles and radix_sort are declared in fmx_host.h: fmx_corpus.hip sorts and scans with them too)
-uint64_t radix_tiles(uint64_t m) { return ntiles_of(m); }
-
-uint64_t scan_partials(uint64_t len) {         // u32 slots the recursive scan of len elements needs for its block totals
-  uint64_t t = 0;
-  while (len > 1) { len = (len + kScanTile - 1) / kScanTile; t += len; }
-  return t + 1;
-}
-
-hipError_t scan_u32(uint32_t *d, uint64_t len, int op, bool exclusive, uint32_t *partials, hipStream_t st) {
-  if (len == 0) return hipSuccess;
-  const uint64_t nb = (len + kScanTile - 1) / kScanTile;
-  hipLaunchKernelGGL(k_sa_scan_tile, dim3((unsigned)nb), dim3(kSaThreads), 0, st, d, len, partials, op, exclusive ? 1 : 0);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || nb == 1) return e;
-  // the block totals: their exclusive scan (a max's exclusive prefix is the max of the blocks before)
-  if ((e = scan_u32(partials, nb, op, true, partials + nb, st)) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_sa_scan_add, dim3((unsigned)nb), dim3(kSaThreads), 0, st, d, len, partials, op);
-  return hipGetLastError();
-}
-
-// Sorts m (key, value) pairs by the key's low `bits` bits; the result is in (*k, *v), the other pair of buffers is free.
-hipError_t radix_sort(unsigned long long **k, uint32_t **v, unsigned long long **k_alt, uint32_t **v_alt, uint64_t m,
-                      int bits, uint32_t *hist, uint32_t *partials, hipStream_t st, int *passes) {
-  const uint64_t nt = ntiles_of(m);
-  *passes = 0;
-  for (int shift = 0; shift < bits; shift += 8) {
-    hipLaunchKernelGGL(k_sa_hist, dim3((unsigned)nt), dim3(kSaThreads), 0, st, *k, m, shift, hist, nt);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if ((e = scan_u32(hist, 256 * nt, kScanSum, true, partials, st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(k_sa_scatter, dim3((unsigned)nt), dim3(kSaThreads), 0, st, *k, *v, *k_alt, *v_alt, m, shift, hist, nt);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    std::swap(*k, *k_alt);
-    std::swap(*v, *v_alt);
-    ++*passes;
-  }
-  return hipSuccess;
-}
-
-namespace {
-
 // FMX_SUFSORT_LOG=<file>: one JSON line per construction appended to the file (tools/build_text_bench.py reads it)
 struct RoundLog { uint64_t h, active; int passes; float ms; double bytes; };
 
@@ -329,10 +184,8 @@ double round_bytes(uint64_t m, int passes, bool first) {
 
 uint64_t sufsort_peak_bytes(uint64_t len, bool sa_given) {
   const uint64_t n = len + 1;
-  const uint64_t nt = ntiles_of(n);
-  const uint64_t scan_len = std::max<uint64_t>(n, 256 * nt);
-  return (n + 8) + (sa_given ? 0 : 4 * n) + 4 * n + 16 * n + 12 * n + 4 * 256 * nt + 4 * scan_partials(scan_len) +
-         8 * 257 + 4096;
+  // s, sa, rank, the active list, the sort's workspace, the results
+  return (n + 8) + (sa_given ? 0 : 4 * n) + 4 * n + 4 * n + SortSpace::bytes(n) + 8 * 257 + 4096;
 }
 
 // The construction proper (include/fmx.h, fmx_bwt_from_text_dev): d_text[len] -> d_bwt[len + 1], eof, counts, and the
@@ -347,35 +200,25 @@ int sufsort_bwt(const void *d_text, uint64_t len, void *d_bwt, void *d_sa_user, 
   const auto t0 = std::chrono::steady_clock::now();
   DevMem mem;
   uint8_t *s = nullptr;
-  uint32_t *sa = nullptr, *rank = nullptr, *ap = nullptr, *hist = nullptr, *partials = nullptr, *v0 = nullptr, *v1 = nullptr,
-           *flag = nullptr;
-  unsigned long long *k0 = nullptr, *k1 = nullptr, *out = nullptr;
-  const uint64_t nt = ntiles_of(n);
-  const uint64_t scan_len = std::max<uint64_t>(n, 256 * nt);
+  uint32_t *sa = nullptr, *rank = nullptr, *ap = nullptr, *flag = nullptr;
+  unsigned long long *out = nullptr;
+  SortSpace ws;
   DEV_ALLOC(mem, s, n + 8, "suffix sort");
   if (d_sa_user) sa = static_cast<uint32_t *>(d_sa_user);
   else DEV_ALLOC(mem, sa, 4 * n, "suffix sort");
   DEV_ALLOC(mem, rank, 4 * n, "suffix sort");
-  DEV_ALLOC(mem, k0, 8 * n, "suffix sort");
-  DEV_ALLOC(mem, k1, 8 * n, "suffix sort");
-  DEV_ALLOC(mem, v0, 4 * n, "suffix sort");
-  DEV_ALLOC(mem, v1, 4 * n, "suffix sort");
   DEV_ALLOC(mem, ap, 4 * n, "suffix sort");
-  DEV_ALLOC(mem, hist, 4 * 256 * nt, "suffix sort");
-  DEV_ALLOC(mem, partials, 4 * scan_partials(scan_len), "suffix sort");
+  if (const int rc = ws.alloc(mem, n, "suffix sort")) return rc;
   DEV_ALLOC(mem, out, 8 * 257 + 8, "suffix sort");
   flag = reinterpret_cast<uint32_t *>(out + 257);
   const double alloc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-#define SA_LAUNCH(...)                                              \
-  do {                                                              \
-    hipLaunchKernelGGL(__VA_ARGS__);                                \
-    HIP_TRY(hipGetLastError(), "suffix sort kernel launch");        \
-  } while (0)
+  const char *const launch = "suffix sort kernel launch";
+  const dim3 block(kSaThreads);
   Events<2> ev;
   if (log_path) HIP_TRY(ev.create(), "hipEventCreate");
   std::vector<RoundLog> rounds;
   HIP_TRY(hipMemsetAsync(out, 0, 8 * 257 + 8, st), "hipMemsetAsync");
-  SA_LAUNCH(k_sa_reverse, dim3(sa_grid(n + 8)), dim3(kSaThreads), 0, st, static_cast<const uint8_t *>(d_text), len, s, flag);
+  LAUNCH(launch, k_sa_reverse, dim3(sa_grid(n + 8)), block, st, static_cast<const uint8_t *>(d_text), len, s, flag);
   uint32_t zero = 0;
   HIP_TRY(hipMemcpyAsync(&zero, flag, 4, hipMemcpyDeviceToHost, st), "D2H");
   HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
@@ -383,48 +226,43 @@ int sufsort_bwt(const void *d_text, uint64_t len, void *d_bwt, void *d_sa_user, 
     set_error("the text contains byte 0 (findex's readers escape it; counts[0] must be 0)");
     return FMX_ERR_UNSUPPORTED;
   }
-  const int bits = 64 - __builtin_clzll((unsigned long long)(n - 1));      // significant bits of a rank (n >= 2)
+  const int bits = bits_for(n - 1);           // significant bits of a rank
   uint64_t m = n, h = 0;
   uint32_t *list = nullptr;                   // the active list (SA positions); nullptr in round 1: all of them
   while (m > 0) {
     if (log_path) HIP_TRY(ev.record(0, st), "hipEventRecord");
-    unsigned long long *k = k0, *ka = k1;
-    uint32_t *v = v0, *va = v1;
-    if (h == 0) SA_LAUNCH(k_sa_init, dim3(sa_grid(m)), dim3(kSaThreads), 0, st, s, n, k, v);
-    else SA_LAUNCH(k_sa_keys, dim3(sa_grid(m)), dim3(kSaThreads), 0, st, list, m, sa, rank, n, h, bits, k, v);
-    int passes = 0;
-    HIP_TRY(radix_sort(&k, &v, &ka, &va, m, h == 0 ? 64 : 2 * bits, hist, partials, st, &passes), "radix sort");
+    const dim3 grid(sa_grid(m));
+    if (h == 0) LAUNCH(launch, k_sa_init, grid, block, st, s, n, ws.keys(), ws.vals());
+    else LAUNCH(launch, k_sa_keys, grid, block, st, list, m, sa, rank, n, h, bits, ws.keys(), ws.vals());
+    HIP_TRY(ws.sort(m, h == 0 ? 64 : 2 * bits, st), "radix sort");
     // the free key buffer holds the heads (first m u32) and the keep flags (next m u32)
-    uint32_t *hp = reinterpret_cast<uint32_t *>(ka), *keep = hp + m;
-    SA_LAUNCH(k_sa_heads, dim3(sa_grid(m)), dim3(kSaThreads), 0, st, k, m, hp);
-    HIP_TRY(scan_u32(hp, m, kScanMax, false, partials, st), "scan");
-    SA_LAUNCH(k_sa_rank, dim3(sa_grid(m)), dim3(kSaThreads), 0, st, k, v, hp, list, m, sa, rank, keep);
-    HIP_TRY(scan_u32(keep, m, kScanSum, false, partials, st), "scan");
-    // the next list goes to the free value buffer; the old list's buffer becomes a value buffer
-    uint32_t *next = va;
-    SA_LAUNCH(k_sa_compact, dim3(sa_grid(m)), dim3(kSaThreads), 0, st, keep, list, m, next);
+    uint32_t *hp = reinterpret_cast<uint32_t *>(ws.free_keys()), *keep = hp + m;
+    LAUNCH(launch, k_sa_heads, grid, block, st, ws.keys(), m, hp);
+    HIP_TRY(ws.scan().max(hp, m, false, st), "scan");
+    LAUNCH(launch, k_sa_rank, grid, block, st, ws.keys(), ws.vals(), hp, list, m, sa, rank, keep);
+    HIP_TRY(ws.scan().sum(keep, m, false, st), "scan");
+    // the next list goes to the free value buffer
+    uint32_t *next = ws.free_vals();
+    LAUNCH(launch, k_sa_compact, grid, block, st, keep, list, m, next);
     uint32_t m_next = 0;
     HIP_TRY(hipMemcpyAsync(&m_next, keep + (m - 1), 4, hipMemcpyDeviceToHost, st), "D2H");
     if (log_path) HIP_TRY(ev.record(1, st), "hipEventRecord");
     HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
-    if (log_path) rounds.push_back({h == 0 ? 8 : 2 * h, m, passes, ev.ms(0, 1), round_bytes(m, passes, h == 0)});
+    if (log_path) rounds.push_back({h == 0 ? 8 : 2 * h, m, ws.passes, ev.ms(0, 1), round_bytes(m, ws.passes, h == 0)});
     if ((uint64_t)m_next >= m && h != 0) {    // a round that separates nothing would loop for ever
       set_error("suffix sort made no progress (internal error)");
       return FMX_ERR_HIP;
     }
-    // buffers: v0/v1 are the value buffers, ap the list; rotate so that the list lives in `next`
-    if (next == v0) { v0 = ap; } else { v1 = ap; }
-    ap = next;
-    list = ap;
+    // ... and the old list's buffer becomes a value buffer in its place
+    list = ap = ws.trade_free_vals(ap);
     m = m_next;
     h = h == 0 ? 8 : 2 * h;
   }
-  SA_LAUNCH(k_sa_emit, dim3(sa_grid(n)), dim3(kSaThreads), 0, st, s, sa, n, static_cast<uint8_t *>(d_bwt), out);
-  SA_LAUNCH(k_sa_eof_fill, dim3(1), dim3(1), 0, st, s, sa, n, static_cast<uint8_t *>(d_bwt), out);
+  LAUNCH(launch, k_sa_emit, dim3(sa_grid(n)), block, st, s, sa, n, static_cast<uint8_t *>(d_bwt), out);
+  LAUNCH(launch, k_sa_eof_fill, dim3(1), dim3(1), st, s, sa, n, static_cast<uint8_t *>(d_bwt), out);
   unsigned long long host_out[257];
   HIP_TRY(hipMemcpyAsync(host_out, out, sizeof host_out, hipMemcpyDeviceToHost, st), "D2H");
   HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
-#undef SA_LAUNCH
   *eof = host_out[0];
   for (int c = 0; c < 256; c++) counts[c] = (int64_t)host_out[1 + c];
   if (log_path)

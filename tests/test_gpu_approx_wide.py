@@ -4,7 +4,7 @@ in both layouts.
 fmx_search_approx_batch starts k_approx<true, kLayoutOneHot> only when n > 2^32; k_approx<true, kLayoutBytes> runs for every
 bytes-layout handle, but below this size none of its row fields ever held a value of 2^32 or more.  Here rows on both sides
 of 2^32 pass through all of them: the sort key pattern << 38 | sp and the radix sort over 38 + ceil(log2 k) bits, the binary
-search of k_approx_off, the csp[] / cep[] slots of a frame in LDS, ix.bwt[sp] and sp == ix.eof under the one-row rule (the
+search of k_ord_csr_off, the csp[] / cep[] slots of a frame in LDS, ix.bwt[sp] and sp == ix.eof under the one-row rule (the
 EOF slot lies above 2^32), and the 24-byte records.
 
 Every expectation comes from oracle.SampledFMSearcher (held to the inverted lists by tests/test_oracle_kat.py): the hits from

@@ -2,7 +2,7 @@
 tests/test_gpu_approx_wide.py -- 2^32 + 2^29 + 12345 rows over a..d, the EOF row above 2^32 -- in both layouts.
 
 k_edit<true, kLayoutOneHot> runs only when n > 2^32, and what holds a row there needs 33 bits and more: sp and ep in a frame's
-csp[] / cep[], sp << 3 in the sort key, ix.bwt[sp] and sp == ix.eof under the one-row rule, the binary search of k_edit_off.
+csp[] / cep[], sp << 3 in the sort key, ix.bwt[sp] and sp == ix.eof under the one-row rule, the binary search of k_ord_csr_off.
 The patterns are prefixes of the suffixes of the rows 2^32 - 1, 2^32 and the EOF row (from cf / occ: helpers.forward_string),
 plain and with one byte deleted or inserted; e = 0 .. 2.  The expectation is edit_ref.dfs_hits over oracle.SampledFMSearcher,
 the steps are edit_ref.walk's.  The index, both handles and the oracle are made once for the module.
