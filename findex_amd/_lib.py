@@ -176,6 +176,15 @@ class fmx_merge_stats(ctypes.Structure):
                 ("rounds", ctypes.c_uint64), ("need_bytes", ctypes.c_uint64)]
 
 
+FMX_RANK_ALL = 1
+FMX_RANK_MAX_TOP, FMX_RANK_MAX_SLOTS = 1024, 64      # results per query, term slots per query (fmx.h)
+
+
+class fmx_rank_params(ctypes.Structure):
+    _fields_ = [("k1", ctypes.c_double), ("b", ctypes.c_double), ("max_per", ctypes.c_uint64), ("top", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32)]
+
+
 class fmx_stats_t(ctypes.Structure):
     _fields_ = [("rank_queries", ctypes.c_uint64), ("backward_steps", ctypes.c_uint64),
                 ("launches", ctypes.c_uint64), ("last_kernel_ms", ctypes.c_double),
@@ -301,6 +310,10 @@ SYMBOLS = {
     "fmx_corpus_doc_list_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _u64, _u64, _vp, _vp, _vp, _sz, _vp]),
     "fmx_corpus_doc_list_phases": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double)]),
     "fmx_corpus_escape": (_i32, [_vp, _sz, _vp, _sz, _P(_sz)]),
+    "fmx_corpus_rank": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _P(fmx_rank_params), _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "fmx_corpus_rank_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _P(fmx_rank_params), _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "fmx_corpus_rank_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(_u64),
+                                    _P(_u64), _P(_u64)]),
     "fmx_occ_host": (_i32, [_vp, _i32, ctypes.c_int64, _P(_u64)]),
     "fmx_calc_gaps_chain": (_i32, [_vp, _vp, _sz, _u64, _i32, _u64, _vp, _P(_sz)]),
     "fmx_regex_compile": (_i32, [_cp, _i32, _P(_vp)]),

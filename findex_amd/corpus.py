@@ -700,3 +700,61 @@ class HipCorpusSearcher:
         """In how many documents q occurs."""
         off, _, _ = self.list_docs([q])
         return int(off[1])
+
+    # ---- ranked retrieval (fmx_corpus_rank, DESIGN.md 26)
+    def rank(self, queries, top=10, k1=1.2, b=0.75, match="any", weights=None, max_per=None):
+        """fmx_corpus_rank: the `top` best files of every query by BM25.  `queries` is a list of lists of raw byte strings
+        (terms; substrings, as everywhere in this index), escaped and searched here.  match="any": a file that holds at
+        least one term of a query is a candidate; "all": only a file that holds every term.  weights: one float per term in
+        the order given (default: the BM25 idf from the document frequencies).  -> (off, doc, score, df, weight): query i's
+        files are doc[off[i]:off[i + 1]], best first (equal scores by document number), with their scores; df and weight per
+        term.  Terms of any lengths share the one call."""
+        if match not in ("any", "all"):
+            raise ValueError("match is 'any' or 'all'")
+        queries = [[bytes(t) for t in q] for q in queries]
+        terms = [t for q in queries for t in q]
+        q_off = np.zeros(len(queries) + 1, dtype=np.uint64)
+        q_off[1:] = np.cumsum([len(q) for q in queries])
+        if terms:
+            _, sp, ep = self._intervals(terms)
+        else:
+            sp = ep = np.zeros(0, dtype=np.uint64)
+        return self.rank_intervals(sp, ep, q_off, top=top, k1=k1, b=b, match=match, weights=weights, max_per=max_per)
+
+    def rank_intervals(self, sp, ep, q_off, top=10, k1=1.2, b=0.75, match="any", weights=None, max_per=None, cap=None):
+        """rank() for term slots given as row intervals of the index; q_off[n_queries + 1] cuts them into queries."""
+        sp = np.ascontiguousarray(sp, dtype=np.uint64).reshape(-1)
+        ep = np.ascontiguousarray(ep, dtype=np.uint64).reshape(-1)
+        q_off = np.ascontiguousarray(q_off, dtype=np.uint64).reshape(-1)
+        n_queries = q_off.size - 1
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+            if weights.size != sp.size:
+                raise ValueError("%d weights for %d terms" % (weights.size, sp.size))
+        prm = _lib.fmx_rank_params(float(k1), float(b), int(max_per or 0), int(top), _lib.FMX_RANK_ALL if match == "all" else 0)
+        if cap is None:
+            cap = max(n_queries, 0) * max(int(top), 0)
+        off = np.zeros(max(n_queries, 0) + 1, dtype=np.uint64)
+        doc = np.zeros(max(cap, 1), dtype=np.uint32)
+        score = np.zeros(max(cap, 1), dtype=np.float64)
+        df = np.zeros(max(sp.size, 1), dtype=np.uint32)
+        w = np.zeros(max(sp.size, 1), dtype=np.float64)
+        _lib.check(self._L.fmx_corpus_rank(self.corpus.handle, self.searcher.handle, _ptr(sp), _ptr(ep), sp.size, _ptr(q_off),
+                                           n_queries, ctypes.byref(prm), _ptr(weights) if weights is not None else None,
+                                           _ptr(off), _ptr(doc), _ptr(score), int(cap), _ptr(df), _ptr(w)))
+        m = int(off[-1])
+        return off, doc[:m], score[:m], df[:sp.size], w[:sp.size]
+
+    def rank_files(self, query_terms, top=10, k1=1.2, b=0.75, match="any", weights=None, max_per=None):
+        """The `top` best files of ONE query (a list of raw byte strings): [(name, score)], best first."""
+        _, doc, score, _, _ = self.rank([list(query_terms)], top=top, k1=k1, b=b, match=match, weights=weights, max_per=max_per)
+        return [(self.corpus.names[int(d)], float(s)) for d, s in zip(doc, score)]
+
+    def rank_last(self):
+        """fmx_corpus_rank_last: {locate_ms, postings_ms, score_ms, select_ms, rows, postings, candidates} of this thread's
+        last ranking."""
+        ms = [ctypes.c_double() for _ in range(4)]
+        n = [ctypes.c_uint64() for _ in range(3)]
+        _lib.check(self._L.fmx_corpus_rank_last(*[ctypes.byref(x) for x in ms + n]))
+        keys = ("locate_ms", "postings_ms", "score_ms", "select_ms", "rows", "postings", "candidates")
+        return dict(zip(keys, [float(x.value) for x in ms] + [int(x.value) for x in n]))

@@ -21,7 +21,8 @@
 //   position map : k_corpus_map, two binary searches per position (doc_start, esc_pos); the escapes before each document's
 //                  start are kept per document (k_corpus_doc_esc), so a document's own escapes are a difference.
 //   doc listing  : rows of k intervals -> SA (fmx_locate_intervals_dev) -> text offsets -> documents (k_corpus_list_keys)
-//                  -> radix sort of interval << bits | doc (fmx_order.h, SortSpace) -> heads, scan, compact.
+//                  -> radix sort of interval << bits | doc (fmx_order.h, SortSpace) -> heads, scan, compact.  Everything up
+//                  to the scan is corpus_doc_keys (fmx_corpus_dev.h), which the ranking (fmx_rank.hip) calls too.
 //
 // Positions are u32 on the device (a stream has at most 2^32 - 2 bytes, the suffix sort's limit) and u64 at the ABI.
 #include <fmx.h>
@@ -372,6 +373,57 @@ int co_use(const Corpus *c) {
 }
 
 }  // namespace
+
+int corpus_index_check(const Corpus *c, const fmx_index *idx, size_t k, hipStream_t st, const char *noun) {
+  uint64_t n = 0;
+  int dev = -1, rc;
+  if ((rc = fmx_n(idx, &n)) || (rc = fmx_device(idx, &dev))) return rc;
+  if (n != c->stream_len + 1) return co_arg("the index is not the index of this corpus (n != stream length + 1)");
+  if (dev != c->device) return co_arg("the index and the corpus live on different devices");
+  if ((uint64_t)k >= 0xffffffffull) return co_arg("too many intervals");
+  if ((rc = co_use(c))) return rc;
+  return not_capturing(st, (std::string("a ") + noun).c_str());
+}
+
+int corpus_doc_keys(const Corpus *c, const fmx_index *idx, const void *d_sp, const void *d_ep, size_t k, uint64_t pat_len,
+                    uint64_t max_per, hipStream_t st, const char *noun, DevMem &mem, Events<5> &ev, DocKeys &out) {
+  const std::string what = std::string("a ") + noun;
+  int rc;
+  if ((rc = device_room(8 * ((uint64_t)k + 1) + 4096, what))) return rc;
+  DEV_ALLOC(mem, out.loc_off, 8 * ((uint64_t)k + 1), "corpus");
+  // the row counts first (no positions: cap 0), then room for exactly that many
+  if ((rc = fmx_locate_intervals_dev(idx, d_sp, d_ep, k, max_per, out.loc_off, nullptr, 0, st))) return rc;
+  unsigned long long rows = 0;
+  HIP_TRY(hipMemcpyAsync(&rows, out.loc_off + k, 8, hipMemcpyDeviceToHost, st), "D2H");
+  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+  if (rows >= 0xffffffffull) {
+    set_error(std::string(noun) + " of " + std::to_string(rows) + " rows: at most 2^32 - 2 per call (use max_per)");
+    return FMX_ERR_UNSUPPORTED;
+  }
+  out.doc_bits = bits_for(c->n_docs);                               // documents 0 .. n_docs (n_docs: no document) fit
+  out.rows = rows;
+  if (rows == 0) return FMX_OK;
+  const int k_bits = bits_for(k);
+  if ((rc = device_room(8 * rows + SortSpace::bytes(rows) + 8192, what))) return rc;
+  unsigned long long *pos = nullptr;
+  SortSpace &ws = out.ws;
+  DEV_ALLOC(mem, pos, 8 * rows, "corpus");
+  if ((rc = ws.alloc(mem, rows, "corpus"))) return rc;
+  HIP_TRY(ev.record(0, st), "hipEventRecord");
+  if ((rc = fmx_locate_intervals_dev(idx, d_sp, d_ep, k, max_per, out.loc_off, pos, rows, st))) return rc;
+  HIP_TRY(ev.record(1, st), "hipEventRecord");
+  LAUNCH("k_corpus_list_keys", k_corpus_list_keys, dim3(co_grid(rows)), dim3(kCoThreads), st, c->map(), pos, (uint64_t)rows, out.loc_off,
+         (uint64_t)k, pat_len, out.doc_bits, ws.keys(), ws.vals());
+  HIP_TRY(ev.record(2, st), "hipEventRecord");
+  HIP_TRY(ws.sort(rows, out.doc_bits + k_bits, st), "radix sort");
+  HIP_TRY(ev.record(3, st), "hipEventRecord");
+  uint32_t *head = reinterpret_cast<uint32_t *>(ws.free_keys());    // the free key buffer holds the head flags
+  HIP_TRY(launch_heads(ws.keys(), rows, head, st), "k_corpus_list_heads");
+  HIP_TRY(ws.scan().sum(head, rows, false, st), "scan");
+  out.incl = head;
+  return FMX_OK;
+}
+
 }  // namespace fmx
 
 using namespace fmx;
@@ -610,58 +662,26 @@ int fmx_corpus_doc_list_dev(const fmx_corpus *corpus, const fmx_index *idx, cons
                             void *stream) {
   if (!corpus || !idx || !d_out_off || (k && (!d_sp || !d_ep)) || (cap && (!d_out_doc || !d_out_cnt))) return co_arg("null argument");
   const Corpus *c = C(corpus);
-  uint64_t n = 0;
-  int dev = -1, rc;
-  if ((rc = fmx_n(idx, &n)) || (rc = fmx_device(idx, &dev))) return rc;
-  if (n != c->stream_len + 1) return co_arg("the index is not the index of this corpus (n != stream length + 1)");
-  if (dev != c->device) return co_arg("the index and the corpus live on different devices");
-  if ((uint64_t)k >= 0xffffffffull) return co_arg("too many intervals");
-  if ((rc = co_use(c))) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if ((rc = not_capturing(st, "a document listing"))) return rc;
+  int rc;
+  if ((rc = corpus_index_check(c, idx, k, st, "document listing"))) return rc;
   Events<5> ev;
   HIP_TRY(ev.create(), "hipEventCreate");
   DevMem mem;
-  unsigned long long *loc_off = nullptr;
-  if ((rc = device_room(8 * ((uint64_t)k + 1) + 4096, "a document listing"))) return rc;
-  DEV_ALLOC(mem, loc_off, 8 * ((uint64_t)k + 1), "corpus");
-  // the row counts first (no positions: cap 0), then room for exactly that many
-  if ((rc = fmx_locate_intervals_dev(idx, d_sp, d_ep, k, max_per, loc_off, nullptr, 0, stream))) return rc;
-  unsigned long long rows = 0;
-  HIP_TRY(hipMemcpyAsync(&rows, loc_off + k, 8, hipMemcpyDeviceToHost, st), "D2H");
-  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
-  if (rows >= 0xffffffffull) {
-    set_error("document listing of " + std::to_string(rows) + " rows: at most 2^32 - 2 per call (use max_per)");
-    return FMX_ERR_UNSUPPORTED;
-  }
-  const int doc_bits = bits_for(c->n_docs), k_bits = bits_for(k);      // documents 0 .. n_docs (n_docs: no document) fit
+  DocKeys dk;
+  if ((rc = corpus_doc_keys(c, idx, d_sp, d_ep, k, pat_len, max_per, st, "document listing", mem, ev, dk))) return rc;
+  const uint64_t rows = dk.rows;
   if (rows == 0) {
     LAUNCH("k_corpus_list_off", k_corpus_list_off, dim3(co_grid(k + 1)), dim3(kCoThreads), st, nullptr, 0ull, nullptr, (uint64_t)k,
-           doc_bits, static_cast<unsigned long long *>(d_out_off));
+           dk.doc_bits, static_cast<unsigned long long *>(d_out_off));
     for (double &p : g_list_phases) p = 0.0;
     return FMX_OK;
   }
-  if ((rc = device_room(8 * rows + SortSpace::bytes(rows) + 8192, "a document listing"))) return rc;
-  unsigned long long *pos = nullptr;
-  SortSpace ws;
-  DEV_ALLOC(mem, pos, 8 * rows, "corpus");
-  if ((rc = ws.alloc(mem, rows, "corpus"))) return rc;
-  HIP_TRY(ev.record(0, st), "hipEventRecord");
-  if ((rc = fmx_locate_intervals_dev(idx, d_sp, d_ep, k, max_per, loc_off, pos, rows, stream))) return rc;
-  HIP_TRY(ev.record(1, st), "hipEventRecord");
-  LAUNCH("k_corpus_list_keys", k_corpus_list_keys, dim3(co_grid(rows)), dim3(kCoThreads), st, c->map(), pos, (uint64_t)rows, loc_off,
-         (uint64_t)k, pat_len, doc_bits, ws.keys(), ws.vals());
-  HIP_TRY(ev.record(2, st), "hipEventRecord");
-  HIP_TRY(ws.sort(rows, doc_bits + k_bits, st), "radix sort");
-  HIP_TRY(ev.record(3, st), "hipEventRecord");
-  const unsigned long long *key = ws.keys();
-  uint32_t *head = reinterpret_cast<uint32_t *>(ws.free_keys());    // the free key buffer holds the head flags
-  HIP_TRY(launch_heads(key, rows, head, st), "k_corpus_list_heads");
-  HIP_TRY(ws.scan().sum(head, rows, false, st), "scan");
-  LAUNCH("k_corpus_list_off", k_corpus_list_off, dim3(co_grid(k + 1)), dim3(kCoThreads), st, key, (uint64_t)rows, head, (uint64_t)k,
-         doc_bits, static_cast<unsigned long long *>(d_out_off));
+  const unsigned long long *key = dk.ws.keys();
+  LAUNCH("k_corpus_list_off", k_corpus_list_off, dim3(co_grid(k + 1)), dim3(kCoThreads), st, key, (uint64_t)rows, dk.incl, (uint64_t)k,
+         dk.doc_bits, static_cast<unsigned long long *>(d_out_off));
   if (cap) {
-    LAUNCH("k_corpus_list_emit", k_corpus_list_emit, dim3(co_grid(rows)), dim3(kCoThreads), st, key, (uint64_t)rows, head, doc_bits,
+    LAUNCH("k_corpus_list_emit", k_corpus_list_emit, dim3(co_grid(rows)), dim3(kCoThreads), st, key, (uint64_t)rows, dk.incl, dk.doc_bits,
            c->n_docs, (uint64_t)cap, static_cast<uint32_t *>(d_out_doc), static_cast<uint32_t *>(d_out_cnt));
   }
   HIP_TRY(ev.record(4, st), "hipEventRecord");

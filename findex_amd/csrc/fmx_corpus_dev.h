@@ -41,4 +41,23 @@ struct Corpus {
   CoMap map() const { return CoMap{d_doc_start, d_doc_esc, d_esc_pos, n_docs, n_esc, stream_len}; }
 };
 
+// ---- the part the document listing and the ranking share (fmx_corpus.hip): the rows of k intervals as sorted
+// (interval, document) keys.  corpus_index_check: `idx` is the index of this corpus' stream, on its device, k fits, and
+// `st` is not being captured (`noun`: "document listing", "ranking" -- what the messages call the call).
+// corpus_doc_keys: locate (the counts, then the rows), the key interval << doc_bits | document of every row -- the document
+// of stream position stream_len - pat_len - SA, n_docs where that is no stream position --, the radix sort over exactly
+// the significant bits, the head flags and their inclusive sum.  Allocates from `mem`, checks the room first and
+// synchronises `st` once, for the row count; records ev[0] before the locate, ev[1] after it, ev[2] after the key kernel
+// and ev[3] after the sort.  rows == 0: nothing but loc_off is allocated and no event is recorded.
+struct DocKeys {
+  unsigned long long *loc_off = nullptr;            // [k + 1]: the located rows of the intervals before i
+  SortSpace ws;                                     // keys(): the sorted keys
+  const uint32_t *incl = nullptr;                   // [rows]: distinct keys up to and including row j (in ws.free_keys())
+  uint64_t rows = 0;
+  int doc_bits = 0;                                 // documents 0 .. n_docs (n_docs: no document) fit
+};
+int corpus_index_check(const Corpus *c, const fmx_index *idx, size_t k, hipStream_t st, const char *noun);
+int corpus_doc_keys(const Corpus *c, const fmx_index *idx, const void *d_sp, const void *d_ep, size_t k, uint64_t pat_len,
+                    uint64_t max_per, hipStream_t st, const char *noun, DevMem &mem, Events<5> &ev, DocKeys &out);
+
 }  // namespace fmx

@@ -1,0 +1,67 @@
+"""Ranked retrieval over a corpus index: which files are the best matches for these words?
+
+    python -m findex_amd.rank BASE "words of a query" ["another query" ..] [--top K] [--all] [--k1 X] [--b X] [--device D]
+                                                                            [--little-endian]
+
+BASE names BASE.bwt / BASE.aux / BASE.docs as `python -m findex_amd.index --dir D --out BASE` writes them.  Every positional
+argument is one query, split on white space into its terms.  Terms are SUBSTRINGS, as everywhere in this index: `cat` counts
+in `concatenate` too; there is no whole-word matching.  A file is scored by BM25 over its terms' occurrence counts
+(HipCorpusSearcher.rank, fmx_corpus_rank: scored and cut to the best K on the device).  Output: one line per hit,
+`score<TAB>file`, best first; the queries' blocks are separated by a blank line.  --all keeps only files that hold every term of
+the query.
+"""
+import argparse
+import sys
+
+
+def parser():
+    ap = argparse.ArgumentParser(prog="python -m findex_amd.rank", description=__doc__.split("\n\n")[0],
+                                 epilog="Terms are substrings, as everywhere in this index: there is no whole-word matching.")
+    ap.add_argument("base")
+    ap.add_argument("query", nargs="+", help="the words of one query, split on white space; every word is matched as a substring")
+    ap.add_argument("--top", type=int, default=10, metavar="K", help="files per query, 1 .. 1024 (default 10)")
+    ap.add_argument("--all", dest="all_", action="store_true", help="only files that hold every term of the query")
+    ap.add_argument("--k1", type=float, default=1.2)
+    ap.add_argument("--b", type=float, default=0.75)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--little-endian", action="store_true")
+    return ap
+
+
+def split_queries(queries):
+    """Each query string split on white space into its terms, as bytes (the file system's encoding, like the names)."""
+    import os
+    return [[os.fsencode(w) for w in q.split()] for q in queries]
+
+
+def render(names, off, doc, score):
+    """The output lines (bytes, without newlines): `score<TAB>file` per hit, a blank line between two queries."""
+    rows = []
+    for i in range(len(off) - 1):
+        if i:
+            rows.append(b"")
+        for j in range(int(off[i]), int(off[i + 1])):
+            rows.append(repr(float(score[j])).encode() + b"\t" + names[int(doc[j])])
+    return rows
+
+
+def main(argv=None):
+    a = parser().parse_args(argv)
+    if not 1 <= a.top <= 1024:
+        parser().error("--top is 1 .. 1024")
+    queries = split_queries(a.query)
+    from .corpus import HipCorpusSearcher
+    cs = HipCorpusSearcher.open(a.base, bigEndian=not a.little_endian, device=a.device)
+    try:
+        off, doc, score, _, _ = cs.rank(queries, top=a.top, k1=a.k1, b=a.b, match="all" if a.all_ else "any")
+        out = sys.stdout.buffer
+        for row in render(cs.corpus.names, off, doc, score):
+            out.write(row + b"\n")
+        out.flush()
+    finally:
+        cs.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -914,6 +914,67 @@ int fmx_corpus_doc_list_dev(const fmx_corpus *corpus, const fmx_index *idx, cons
 int fmx_corpus_doc_list_phases(double *locate_ms, double *map_ms, double *sort_ms, double *compact_ms);
 int fmx_corpus_escape(const uint8_t *in, size_t len, uint8_t *out, size_t cap, size_t *out_len);
 
+/* ---- ranked retrieval: the top-K documents of multi-term queries by BM25.  Beyond the reference.  DESIGN.md 26.
+ * The definition is exact, not "BM25 up to rounding": a result can be compared bit for bit.
+ * INPUTS.  A call takes n_terms term slots.  Slot t is a row interval (sp[t], ep[t]) of `idx`, the index of this corpus'
+ * stream, as a search for the reverse of the escaped term finds it.  q_off[n_queries + 1] cuts the slots into queries
+ * (q_off[0] == 0, non-decreasing, q_off[n_queries] == n_terms): slots are never shared between queries, and a term given
+ * twice in a query is two slots and counts twice.
+ * DOCUMENT OF A ROW.  The document that holds stream position stream_len - 1 - SA, the LAST byte of the occurrence.  It does
+ * not depend on the term's length, so terms of any lengths share one call (fmx_corpus_doc_list needs one call per length);
+ * an escaped term never holds the separator byte 1, so its first and last byte lie in one document.  A row with
+ * SA > stream_len - 1 belongs to no document and is dropped.
+ * TERM FREQUENCY.  tf(t, d) = the rows of slot t in document d; overlapping occurrences count.  With max_per != 0 only the
+ * first min(ep - sp, max_per) rows of every slot are taken, as fmx_locate_intervals takes them.  df(t) = the documents with
+ * tf(t, d) > 0.
+ * CORPUS CONSTANTS.  N = n_docs (empty documents count); len(d) = the RAW length of d = doc_start[d + 1] - doc_start[d] - 1
+ * - (the escapes of d); avglen = (double)(stream_len - n_docs - n_esc) / (double)n_docs.
+ * WEIGHTS.  `weights` (n_terms doubles, all finite, else FMX_ERR_ARG; negative ones allowed) are used as they are; NULL:
+ * w(t) = log(1.0 + ((double)(N - df) + 0.5) / ((double)df + 0.5)), computed on the HOST in double (std::log) from the df the
+ * call reads back.  The weights used and the df come back through out_weight and out_df; either may be NULL.
+ * SCORE.  IEEE double on the device, every operation rounded once and none contracted into an FMA, in this order:
+ *   r     = avglen == 0 ? 0.0 : (double)len(d) / avglen
+ *   nd    = k1 * ((1.0 - b) + b * r)
+ *   c(t)  = w(t) * (((double)tf * (k1 + 1.0)) / ((double)tf + nd))
+ *   score = (((0.0 + c(t0)) + c(t1)) + ..) over the query's slots with tf > 0, in ascending slot order
+ * with k1 >= 0 and 0 <= b <= 1, both finite (FMX_ERR_ARG otherwise).
+ * CANDIDATES of a query: the documents with tf > 0 for at least one of its slots; with FMX_RANK_ALL only those with
+ * tf > 0 for every one of its slots.
+ * OUTPUT.  CSR over the queries: out_off[n_queries + 1], out_doc[], out_score[].  Query i gets its min(top, candidates) best
+ * by score descending, equal scores (plain == on the doubles; a score is never -0.0) by document ascending.  A query with no
+ * slots or no candidates gets nothing.  Nothing is written past entry cap - 1; the host form returns FMX_ERR_OVERFLOW when
+ * out_off[n_queries] > cap (out_off complete, the first cap entries written), the _dev form leaves the total in
+ * d_out_off[n_queries] for the caller to check.
+ * LIMITS, each refused with a message that names it: 1 <= top <= 1024 and at most 64 slots per query (FMX_ERR_ARG); fewer
+ * than 2^32 - 1 located rows per call, and bits_for(n_queries) + bits_for(n_docs) + bits_for(slots of the longest query) <=
+ * 64, bits_for(v) being the bits that hold 0 .. v (FMX_ERR_UNSUPPORTED); the handles locate refuses.
+ * The host form decides every FMX_ERR_ARG above before a handle or the device is touched.  fmx_corpus_rank_dev: the same with
+ * every array a device pointer (u64 sp / ep / q_off / out_off, f64 weights / out_score / out_weight, u32 out_doc / out_df).
+ * Both forms ALLOCATE AND SYNCHRONISE (FMX_ERR_HIP under a stream capture, decided before anything is allocated); the need is
+ * checked against the free HBM before every allocation (FMX_ERR_NOMEM with the need in the message) and every temporary is
+ * freed on every path.  Locate, the listing's key sort, a second sort over the postings, one lane per candidate for the
+ * score and one workgroup per query for the selection (a radix select above 1024 candidates, a bitonic sort in LDS); no
+ * atomic decides an order: the same input gives the same bytes.
+ * fmx_corpus_rank_last: device time (ms) of the calling thread's last ranking in its four phases, and the rows located,
+ * the (slot, document) postings and the (query, document) candidates it went through. */
+#define FMX_RANK_ALL 1u
+typedef struct fmx_rank_params {
+  double k1, b;
+  uint64_t max_per; /* rows taken of every slot; 0 = all */
+  uint32_t top;     /* results per query, 1 .. 1024 */
+  uint32_t flags;   /* FMX_RANK_ALL or 0 */
+} fmx_rank_params;  /* 32 bytes */
+int fmx_corpus_rank(const fmx_corpus *corpus, const fmx_index *idx, const uint64_t *sp, const uint64_t *ep, size_t n_terms,
+                    const uint64_t *q_off, size_t n_queries, const fmx_rank_params *params, const double *weights,
+                    uint64_t *out_off, uint32_t *out_doc, double *out_score, size_t cap, uint32_t *out_df,
+                    double *out_weight);
+int fmx_corpus_rank_dev(const fmx_corpus *corpus, const fmx_index *idx, const void *d_sp, const void *d_ep, size_t n_terms,
+                        const void *d_q_off, size_t n_queries, const fmx_rank_params *params, const void *d_weights,
+                        void *d_out_off, void *d_out_doc, void *d_out_score, size_t cap, void *d_out_df,
+                        void *d_out_weight, void *stream);
+int fmx_corpus_rank_last(double *locate_ms, double *postings_ms, double *score_ms, double *select_ms, uint64_t *rows,
+                         uint64_t *postings, uint64_t *candidates);
+
 /* ---- regex: REParser.re2post (re2/re2.scala:50-185) + ReTree.apply (re2/retree.scala:156-370).
  * Bytes of `re` are Latin-1 characters.  FMX_ERR_SYNTAX / FMX_ERR_MATCH mirror the reference's
  * "re2post syntax" exception and scala.MatchError. */
