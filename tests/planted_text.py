@@ -254,6 +254,93 @@ def occurrence_pairs(plan, b, lo, hi):
     return [t + lo for t in b.copies]
 
 
+# ---------------------------------------------------------------- n-grams
+NGRAM_CLASS = np.dtype([("block", np.int64), ("offset", np.int64), ("count", np.int64), ("first_pos", np.int64)])
+NGRAM_RECORD = np.dtype([("sp", np.uint64), ("count", np.uint64), ("first_pos", np.uint64)])
+NGRAM_FIELDS = ("records", "selected", "distinct", "windows", "singletons", "largest_count", "largest_sp", "largest_pos")
+
+
+def stop_positions(plan, stop):
+    """The text positions of the stop byte, ascending: the background and the flanks hold none."""
+    return sorted(t + o for b in plan.blocks for t in b.copies for o, x in enumerate(b.data) if stop and x == stop)
+
+
+def eligible_windows(plan, L, stop=0):
+    """How many of the m - L + 1 windows of L bytes hold no stop byte: the windows that hold position p begin in
+    [p - L + 1, p]; the union of these stretches, cut at the text's two ends, is taken off."""
+    if L > plan.m:
+        return 0
+    held, reach = 0, -1                                           # reach: the last window start already taken off
+    for p in stop_positions(plan, stop):
+        lo, hi = max(p - L + 1, 0, reach + 1), min(p, plan.m - L)
+        if hi >= lo:
+            held, reach = held + hi - lo + 1, hi
+    return plan.m - L + 1 - held
+
+
+def ngram_classes(plan, L, stop=0):
+    """The windows of L >= L0 bytes that occur twice or more, and the closed forms of the n-gram summary.
+
+    -> (classes, summary).  classes: a NGRAM_CLASS array, one entry per distinct repeated window -- by (1)-(3) of the
+    module's docstring the windows that lie inside one copy of a block with two or more copies, once per copy -- as (index
+    of the block in plan.blocks, offset in the block, count = the block's copies, first position = first copy + offset),
+    eligibility as eligible() has it.  The entries stand in the order of their rows: the suffix array of
+    s = reverse(T) + sentinel lists the windows by their reversed bytes, and no two classes share them.
+    summary: windows (the eligible ones), distinct = windows - sum(count - 1), singletons = windows - sum(count),
+    largest_count and largest_pos (the first position of the first class, in row order, of that count).  Without a class
+    every eligible window is a singleton: largest_count is 1 and largest_pos None -- the window of the smallest row, which
+    the plan does not name."""
+    assert L >= plan.L0
+    rows = []
+    for k, b in enumerate(plan.blocks):
+        if len(b.copies) >= 2:
+            rows += [(b.data[o:o + L][::-1], k, int(o), len(b.copies), b.copies[0] + int(o)) for o in eligible(b, L, stop).tolist()]
+    rows.sort()
+    assert all(x[0] != y[0] for x, y in zip(rows, rows[1:]))
+    classes = np.array([r[1:] for r in rows], dtype=np.int64).reshape(-1, 4)
+    out = np.zeros(len(rows), dtype=NGRAM_CLASS)
+    for j, f in enumerate(NGRAM_CLASS.names):
+        out[f] = classes[:, j]
+    windows = eligible_windows(plan, L, stop)
+    total = int(out["count"].sum())
+    summary = dict(windows=windows, distinct=windows - total + out.size, singletons=windows - total,
+                   largest_count=int(out["count"].max()) if out.size else int(windows > 0), largest_pos=None if windows else 0)
+    if out.size:
+        summary["largest_pos"] = int(out["first_pos"][np.argmax(out["count"])])      # argmax: the first of the largest
+    return out, summary
+
+
+def ngram_occurrences(plan, classes, L):
+    """int64[classes, copies as a ragged list]: per class the positions in s = reverse(T) + sentinel of its windows,
+    m - t - L for every copy t + offset -- whose rows must be consecutive, the smallest of them the class's sp."""
+    return [plan.m - (np.array(plan.blocks[int(c["block"])].copies, dtype=np.int64) + int(c["offset"])) - L for c in classes]
+
+
+def ngram_result(classes, summary, sp, order="count", top=0, lone=None):
+    """(records, summary) as fmx_ngrams defines them at min_count = 2, from ngram_classes' pair and the classes' sp (int64,
+    in their order; ascending, as that is the row order).  lone: (sp, first_pos) of the eligible window in the smallest row,
+    for a length without a class."""
+    sp = np.asarray(sp, dtype=np.int64).reshape(-1)
+    assert sp.size == classes.size and (np.diff(sp) > 0).all()
+    pick = np.arange(sp.size) if order == "row" else np.lexsort((sp, -classes["count"]))
+    kept = pick[:top] if top else pick
+    rec = np.zeros(kept.size, dtype=NGRAM_RECORD)
+    rec["sp"], rec["count"], rec["first_pos"] = sp[kept], classes["count"][kept], classes["first_pos"][kept]
+    full = dict(summary, records=int(kept.size), selected=int(sp.size), largest_sp=0)
+    if sp.size:
+        full["largest_sp"] = int(sp[np.argmax(classes["count"])])
+    elif summary["windows"]:
+        full["largest_sp"], full["largest_pos"] = int(lone[0]), int(lone[1])
+    return rec, {f: full[f] for f in NGRAM_FIELDS}
+
+
+def ngram_spectrum(classes, summary, bins):
+    """uint64[bins]: entry c the classes of count c, singletons included, entry 0 those of count >= bins."""
+    spec = np.bincount(np.where(classes["count"] < bins, classes["count"], 0), minlength=bins).astype(np.uint64)
+    spec[1 if bins > 1 else 0] += np.uint64(summary["singletons"])
+    return spec
+
+
 # ---------------------------------------------------------------- LCP
 def row_order(plan, b):
     """The copies of b in the order their suffixes stand in the suffix array of s = reverse(T) + sentinel: a suffix that

@@ -1,10 +1,15 @@
-"""The three features with 32-bit positions -- the LCP array on a handle, fmx_repeats (18) and
-fmx_occurrences (20) -- on a text of m = 3 * 2^30 + 4099 bytes, in both layouts.  All three refuse n >= 2^32, so their hard
-zone is 2^31 <= n < 2^32: here a third of the rows, of the SA values and of the text positions carry their top bit, and with
-them every `row + 1` class id, every `pos << lb` key field (pb = 32) and every u32 sample that locate reads.
+"""The features with 32-bit positions -- the LCP array on a handle, fmx_repeats (18), fmx_occurrences (20),
+fmx_ngrams (22), the line table and its lookups (23) and fmx_line_query (24) -- on a text of m = 3 * 2^30 + 4099 bytes, in both
+layouts.  All of them refuse n >= 2^32, so their hard zone is 2^31 <= n < 2^32: here a third of the rows, of the SA values and
+of the text positions carry their top bit, and with them every `row + 1` class id, every `pos << lb` key field (pb = 32) and
+every u32 sample that locate reads; with the break set {10, a, b, c} the text has more than 2^31 lines, so line indices, line
+numbers and the candidates of an all-lines query carry it too.
 
 The text is tests/planted_text.py's plan written over i.i.d. a..d bytes on the device; every expectation is a closed form of
-the plan (held to the from-the-definition references by tests/test_planted_text_cpu.py on the same geometry scaled down).
+the plan (held to the from-the-definition references by tests/test_planted_text_cpu.py on the same geometry scaled down) or,
+where the background counts -- the lines of a break set, the windows of one to three bytes -- plain torch over the fixture's
+text tensor and the inverse of the sort's SA (tests/top_bit_ref.py, held to lines_ref, linequery_ref and ngrams_ref.brute by
+tests/test_top_bit_ref_cpu.py).
 Nothing of the library produces an expectation: its suffix sort and its search supply inputs only -- the rows and intervals
 to ask about -- and their sizes and SA values are asserted against the plan.  The conditions the inputs must meet are
 computed from the plan alone, printed and asserted by the fixture before any comparison.  A natural repeat of 64 bytes in the
@@ -12,7 +17,9 @@ background (chance below 2^-66) would fail the first LCP test.
 
 The module prints the seconds of the fixture and of every case (DESIGN.md 6 has one run's figures).  Every repeats call
 inverts the index once (HipFMSearcher.repeats twice: the counting call and the sized one), every first occurrences call of a
-handle builds its locate samples by one more inversion: that is where the seconds of those cases go.
+handle builds its locate samples by one more inversion: that is where the seconds of those cases go.  An n-grams call with
+positions inverts once as well; the line table of 2.4 * 10^9 breaks is built once, by a fixture of its own that prints its
+seconds, and dropped when the module ends.
 """
 import ctypes
 import functools
@@ -23,8 +30,12 @@ import numpy as np
 import pytest
 
 import findex_amd
+import linequery_ref
+import lines_ref
+import ngrams_ref
 import occ_ref
 import planted_text as pt
+import top_bit_ref as tb
 from findex_amd import _lib
 from helpers import ends_at_a_fault
 from test_gpu_lcp import _sort_on_device, _verify_on_device
@@ -117,7 +128,7 @@ def top():
         r = torch.arange(lo, hi, dtype=torch.int64, device="cuda")
         row_of[sa[lo:hi].to(torch.int64) & M32] = torch.where(r >= LINE, r - (1 << 32), r).to(torch.int32)
     del r
-    w.text, w.sa, w.row_of = text, sa, row_of
+    w.text, w.sa, w.row_of, w.counts = text, sa, row_of, counts
     # what the LCP test asks about, from the plan; the rows from the sort, held to the plan: the suffixes of one class stand
     # in consecutive rows in the order the plan says
     v, nxt, val = pt.lcp_planted(plan)
@@ -130,12 +141,13 @@ def top():
                   "seconds_handles_and_inverse": round(time.time() - t2, 1)})
     print("top bit inputs:", w.fig)
     assert w.fig["lcp_rows_below"] > 0 and w.fig["lcp_rows_above"] > 0
-    w.lcp = {}
+    w.lcp, w.cache = {}, {}
     torch.cuda.synchronize()
     print("top bit: fixture %.1f s" % (time.time() - t0))
     yield w
     for h in w.hip.values():
         h.close()
+    w.cache.clear()
     del w.text, w.sa, w.row_of, w.lcp, text, sa, row_of
     gc.collect()
     torch.cuda.empty_cache()
@@ -407,3 +419,459 @@ def test_occurrences_device_form_one_record_short(top):
     assert ei.value.code == OVERFLOW and str(T) in str(ei.value)
     torch.cuda.synchronize()
     assert (d_out.cpu().numpy()[(T - 1) * 32:] == 0xCD).all()      # (fmx.h leaves what lies in front of it unspecified)
+
+
+# ---------------------------------------------------------------- 4. n-grams
+LB = _lib.FMX_NGRAMS_LDS_BINS
+NO_POS = H.NO_POS
+
+
+def timed(top, key, make):
+    """top.cache[key], made once and its seconds printed: a reference that several cases share."""
+    if key not in top.cache:
+        t0 = time.time()
+        top.cache[key] = make()
+        top.torch.cuda.synchronize()
+        print("top bit: reference %s %.1f s" % (key, time.time() - t0))
+    return top.cache[key]
+
+
+def lone_window(top, L, stop):
+    """(row, first position) of the eligible window of L bytes in the smallest row, from the sort's SA: the window of row r
+    begins at t = m - L - SA[r]."""
+    t = top.m - L - u32(top.sa[:1 << 20])
+    ok = t >= 0
+    for p in pt.stop_positions(top.plan, stop):
+        ok &= ~((t <= p) & (p < t + L))
+    r = int(top.torch.nonzero(ok)[0].item())
+    return r, int(t[r].item())
+
+
+def planted_ngrams(top, L, stop):
+    """(classes, summary, sp, lone) of a planted threshold: ngram_classes from the plan, sp from the inverse of the sort's
+    SA -- the rows of a class's copies, which must be consecutive."""
+    def make():
+        torch, plan = top.torch, top.plan
+        classes, summary = pt.ngram_classes(plan, L, stop)
+        at = pt.ngram_occurrences(plan, classes, L)
+        sp = np.zeros(classes.size, dtype=np.int64)
+        if classes.size:
+            rows = u32(top.row_of[torch.from_numpy(np.concatenate(at)).cuda()]).cpu().numpy()
+            lo = 0
+            for j, a in enumerate(at):
+                r = np.sort(rows[lo:lo + a.size])
+                assert np.array_equal(r, r[0] + np.arange(a.size)), (L, stop, j)
+                sp[j], lo = r[0], lo + a.size
+        lone = None if classes.size or not summary["windows"] else lone_window(top, L, stop)
+        return classes, summary, sp, lone
+    return timed(top, ("planted n-grams", L, stop), make)
+
+
+def ngrams_dev_call(w, hip, levels, cap, room, **kw):
+    """One fmx_ngrams_dev with `cap`, the buffer `room` records and 8 guard records -> (n or the FmxError, out_off, the first
+    min(cap, room) records, summaries); what lies behind out[cap - 1] must be untouched.  (w: the fixture.)"""
+    torch = w.torch
+    d_off = torch.zeros(len(levels) + 1, dtype=torch.int64, device="cuda")
+    d_out = torch.full((3 * (room + 8),), -1, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    try:
+        n, sums = hip.ngrams_dev(levels, d_off.data_ptr(), d_out.data_ptr(), cap, **kw)
+    except findex_amd.FmxError as e:
+        if e.code != OVERFLOW:
+            raise
+        n, sums = e, None
+    torch.cuda.synchronize()
+    raw = d_out.cpu().numpy().view(np.uint64)
+    assert (raw[3 * cap:] == np.uint64(M32 << 32 | M32)).all()
+    return n, d_off.cpu().numpy().view(np.uint64), raw[:3 * cap].copy().view(H.NGRAM), sums
+
+
+def same_summary(got, want, what, positions=True):
+    assert list(ngrams_ref.FIELDS) == list(pt.NGRAM_FIELDS)
+    for f in ngrams_ref.FIELDS:
+        assert got[f] == (NO_POS if f == "largest_pos" and not positions else want[f]), (what, f, got, want)
+
+
+@pytest.mark.parametrize("stop", (0, pt.STOP))
+@pytest.mark.parametrize("layout", LAYOUTS)
+@case
+def test_ngrams_planted_thresholds(top, layout, stop):
+    """Every threshold in one call per order, min_count 2, with positions: records byte for byte, every summary field and a
+    spectrum of 6 bins (Y's seven copies are its overflow) against ngram_classes.  One inversion per call."""
+    plan, hip = top.plan, top.hip[layout]
+    levels = plan.thresholds
+    want = [planted_ngrams(top, L, stop) for L in levels]
+    sp = np.concatenate([w[2] for w in want])
+    pos = np.concatenate([w[0]["first_pos"] for w in want])
+    fig = {"classes": int(sp.size), "sp_below": int((sp < LINE).sum()), "sp_above": int((sp >= LINE).sum()),
+           "first_pos_below": int((pos < LINE).sum()), "first_pos_above": int((pos >= LINE).sum()),
+           "lengths_without_a_class": sum(1 for w in want if not w[0].size)}
+    print("top bit: planted n-grams, stop %d:" % stop, fig)
+    assert min(fig.values()) > 0
+    for order in ("row", "count"):
+        exp = [pt.ngram_result(c, s, r, order, 0, lone) for c, s, r, lone in want]
+        total = sum(r.size for r, _ in exp)
+        n, off, rec, sums = ngrams_dev_call(top, hip, levels, total, total, min_count=2, order=order, stop=stop, spectrum=6)
+        assert n == total and np.array_equal(off, np.cumsum([0] + [r.size for r, _ in exp]).astype(np.uint64)), (order, n, total)
+        assert rec.tobytes() == np.concatenate([r for r, _ in exp]).tobytes(), order
+        for L, (c, s, _, _), (_, ws), g in zip(levels, want, exp, sums):
+            same_summary(g, ws, (L, order, stop))
+            assert np.array_equal(g["spectrum"], pt.ngram_spectrum(c, s, 6)), (L, order, stop)
+    assert all(x >= 0 for x in hip.ngrams_last()) and hip.ngrams_last()[0] > 0
+
+
+def gram_tables(top):
+    """tb.gram_table of 1, 2 and 3 bytes over the fixture's text with the inverse of the sort's SA, as numpy (sp, count, first)
+    triples by L; what every small-L case must reach is asserted here."""
+    def make():
+        out = {}
+        for L in (1, 2, 3):
+            g = tb.gram_table(top.text, L, top.row_of)
+            out[L] = tuple(g[k].cpu().numpy() for k in ("sp", "count", "first"))
+            sp, cnt, first = out[L]
+            assert int(cnt.sum()) == top.m - L + 1
+            big = cnt >= 2
+            fig = {"distinct": int(cnt.size), "largest_count": int(cnt.max()), "sp_below": int((sp[big] < LINE).sum()),
+                   "sp_above": int((sp[big] >= LINE).sum()), "first_pos_above": int((first >= LINE).sum()),
+                   "counts_from_%d_on" % LB: int((cnt >= LB).sum()), "singletons": int((cnt == 1).sum())}
+            print("top bit: windows of %d bytes:" % L, fig)
+            assert fig["largest_count"] > 1 << 29 if L == 1 else fig["largest_count"] > 1 << 25
+            assert fig["sp_below"] > 0 and fig["sp_above"] > 0 and fig["counts_from_%d_on" % LB] >= 4 ** L
+        return out
+    return timed(top, "gram tables", make)
+
+
+def small_expected(top, L, min_count, order, k, bins):
+    """(records, summary with the spectrum) from the gram table: the selection by ngrams_ref.result, the bins a
+    torch.bincount of the counts with those at or above the bound in bin 0."""
+    torch = top.torch
+    sp, cnt, first = gram_tables(top)[L]
+    rec, s = ngrams_ref.result((sp, cnt, first), min_count, order, k, 0)
+    c = torch.from_numpy(cnt).cuda()
+    s["spectrum"] = torch.bincount(torch.where(c < bins, c, torch.zeros_like(c)), minlength=bins).cpu().numpy().astype(np.uint64)
+    return rec, s
+
+
+SMALL = [(1, "count", 10, LB - 24), (1, "count", 0, 5000), (2, "count", 10, 5000), (2, "count", 0, LB - 24), (1, "row", 0, LB - 24),
+         (2, "row", 0, 5000)]
+
+
+@pytest.mark.parametrize("min_count,order,k,bins", SMALL)
+@case
+def test_ngrams_windows_of_one_two_and_three_bytes(top, min_count, order, k, bins):
+    """L = 1, 2, 3 in one call: counts near 2^30 (the largest class covers more than 2^29 rows, and the count-ordered key
+    (largest - count) << 32 | sp uses all 32 position bits), a spectrum bound below and above the LDS histogram."""
+    hip = top.hip["bytes"]
+    exp = [small_expected(top, L, min_count, order, k, bins) for L in (1, 2, 3)]
+    total = sum(r.size for r, _ in exp)
+    assert bins != LB and all(s["largest_count"] >= bins for _, s in exp)
+    assert any((r["sp"] >= LINE).any() and (r["sp"] < LINE).any() for r, _ in exp)
+    n, off, rec, sums = ngrams_dev_call(top, hip, [1, 2, 3], total, total, min_count=min_count, order=order, top=k, spectrum=bins)
+    assert n == total and np.array_equal(off, np.cumsum([0] + [r.size for r, _ in exp]).astype(np.uint64)), (n, total)
+    for L, (wr, ws), g, a, e in zip((1, 2, 3), exp, sums, off, off[1:]):
+        assert rec[int(a):int(e)].tobytes() == wr.tobytes(), (L, rec[int(a):int(e)][:5], wr[:5])
+        same_summary(g, ws, L)
+        assert g["spectrum"].dtype == np.uint64 and np.array_equal(g["spectrum"], ws["spectrum"]), (L, np.nonzero(g["spectrum"] != ws["spectrum"]))
+        assert int(ws["spectrum"][0]) >= 4 ** L and int(ws["spectrum"].sum()) == ws["distinct"]
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+@case
+def test_ngrams_without_positions(top, layout):
+    """One planted length and L = 2 without positions: every field of the call with positions but first_pos and largest_pos
+    -- the text's last min(L, n) rows, which are no windows, taken off by the closed form -- and no inversion."""
+    plan, hip = top.plan, top.hip[layout]
+    c, s, sp, lone = planted_ngrams(top, plan.L0, 0)
+    want = [pt.ngram_result(c, s, sp, "count", 0, lone), small_expected(top, 2, 2, "count", 0, 7)]
+    spectra = [pt.ngram_spectrum(c, s, 7), want[1][1]["spectrum"]]
+    assert (want[1][0]["count"] > 1 << 25).any() and int(want[0][0]["count"].max()) == 7
+    got = hip.ngrams([plan.L0, 2], min_count=2, order="count", spectrum=7, positions=False)
+    assert hip.ngrams_last()[0] == 0
+    for (rec, summary), (wrec, ws), spec in zip(got, want, spectra):
+        assert rec.dtype == ngrams_ref.RECORD and rec.shape == wrec.shape
+        assert np.array_equal(rec["sp"], wrec["sp"]) and np.array_equal(rec["count"], wrec["count"])
+        assert (rec["first_pos"] == np.uint64(NO_POS)).all()
+        same_summary(summary, ws, layout, positions=False)
+        assert np.array_equal(summary["spectrum"], spec)
+
+
+@case
+def test_ngrams_device_form_one_record_short(top):
+    """fmx_ngrams_dev with room for all records, twice, and with cap one short: equal bytes, the exact total, complete offsets,
+    the guard records behind out[cap - 1] untouched.  Three inversions."""
+    hip = top.hip["onehot"]
+    exp = [pt.ngram_result(*planted_ngrams(top, L, pt.STOP)[:3], "count", 0, planted_ngrams(top, L, pt.STOP)[3]) for L in FIVE]
+    total = sum(r.size for r, _ in exp)
+    want_off = np.cumsum([0] + [r.size for r, _ in exp]).astype(np.uint64)
+    want = np.concatenate([r for r, _ in exp])
+    kw = dict(min_count=2, order="count", stop=pt.STOP)
+    assert total > 4000 and exp[2][0].size == 0
+    runs = [ngrams_dev_call(top, hip, FIVE, total, total, **kw) for _ in range(2)]
+    for n, off, rec, sums in runs:
+        assert n == total and np.array_equal(off, want_off) and rec.tobytes() == want.tobytes()
+        for L, g, (_, ws) in zip(FIVE, sums, exp):
+            same_summary(g, ws, L)
+    assert runs[0][2].tobytes() == runs[1][2].tobytes()
+    err, off, rec, _ = ngrams_dev_call(top, hip, FIVE, total - 1, total, **kw)
+    assert isinstance(err, findex_amd.FmxError) and err.code == OVERFLOW and str(total) in str(err)
+    assert np.array_equal(off, want_off) and rec.tobytes() == want[:total - 1].tobytes()
+
+
+# ---------------------------------------------------------------- 5. lines
+BIG = bytes([10, 97, 98, 99])
+NO_LINE = H.NO_LINE
+
+
+def same_u64(got, want):
+    for g, w in zip(got, want):
+        assert g.dtype == np.uint64 and np.array_equal(g, w), (g[:8], w[:8])
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+@case
+def test_lines_six_lines_of_a_gigabyte(top, layout):
+    """The break set {10}: five breaks, X's stop byte in each of its five copies."""
+    plan, hip, m = top.plan, top.hip[layout], top.m
+    ref = timed(top, "lines {10}", lambda: tb.Lines(top.text, b"\n"))
+    brk = ref.brk.tolist()
+    assert brk == pt.stop_positions(plan, pt.STOP) and len(brk) == 5 and brk[1] < LINE - 2 and brk[2] > LINE + 2 and brk[0] > 1
+    assert max(b - a for a, b in zip([0] + brk, brk + [m])) > 1 << 30
+    hip.lines_prepare(b"\n")
+    info = hip.lines_info()
+    assert info[0] == 5 and info[1] == b"\n"
+    pos = [0, m - 1] + [b + d for b in brk for d in (-1, 0, 1)] + [LINE - 1, LINE, m, 1 << 63]
+    pos = np.array(pos, dtype=np.uint64)
+    want = ref.lookup(pos)
+    assert want[0][:-2].tolist() == [0, 5] + [k + d for k in range(5) for d in (0, 0, 1)] + [2, 2] and (want[0][-2:] == np.uint64(NO_LINE)).all()
+    assert (want[1][:-2] >= np.uint64(LINE)).any() and (want[2][:-2] >= np.uint64(LINE)).any() and (want[2] < np.uint64(LINE)).any()
+    same_u64(hip.line_of(pos), want)
+    lines = np.arange(8, dtype=np.uint64)
+    spans = ref.spans(lines)
+    assert spans[0][:6].tolist() == [0] + [b + 1 for b in brk] and spans[1][:6].tolist() == brk + [m] and (spans[0][6:] == np.uint64(NO_LINE)).all()
+    same_u64(hip.line_spans(lines), spans)
+
+
+def sort_space_bytes(m):
+    """fmx_order_math.h: two key and two value buffers, a histogram of 256 digits per tile of 4096 keys, and the block totals
+    (one u32 per 2048 elements, level by level, and one) of the longer of the scans over the histograms and over m elements."""
+    hist = 256 * ((m + 4095) // 4096)
+    length, partials = max(m, hist), 0
+    while length > 1:
+        length = (length + 2047) // 2048
+        partials += length
+    return 2 * 8 * m + 2 * 4 * m + 4 * hist + 4 * (partials + 1)
+
+
+class Big:
+    pass
+
+
+@pytest.fixture(scope="module")
+def big(top):
+    """The line table of the break set {10, a, b, c} on the one-hot handle -- three bytes of four are breaks, more than 2^31 of
+    them -- and the stand-in over the same set; the build's seconds are printed on their own.  Afterwards the table is
+    dropped."""
+    torch, hip, m = top.torch, top.hip["onehot"], top.m
+    w = Big()
+    w.hip = hip
+    w.n_brk = sum(int(top.counts[c]) for c in BIG)
+    if w.n_brk <= LINE:
+        pytest.fail("the break bytes 10, a, b, c occur %d times, not more than 2^31: no line index would carry its top bit" % w.n_brk)
+    shift = hip.lines_info()[2]
+    keep = 4 * w.n_brk + 4 * ((m >> shift) + 2)
+    need = keep + 8 * w.n_brk + sort_space_bytes(w.n_brk) + 8192
+    gc.collect()
+    torch.cuda.empty_cache()
+    t0 = time.time()
+    w.ref = tb.Lines(top.text, BIG)
+    torch.cuda.synchronize()
+    t1 = time.time()
+    free = torch.cuda.mem_get_info()[0]
+    if free < need:
+        pytest.fail("%.0f GB of HBM are free, the line table of %d breaks needs %.0f GB while it is built: no line ran above 2^31"
+                    % (free / 1e9, w.n_brk, need / 1e9))
+    ends_at_a_fault(hip.lines_prepare)(BIG)
+    t2 = time.time()
+    info = hip.lines_info()
+    w.shift = info[2]
+    print("top bit: the line table of %d breaks: reference %.1f s, build %.1f s (locate %.0f ms, sort and directory %.0f ms), %d bytes, shift %d"
+          % (w.n_brk, t1 - t0, t2 - t1, hip.lines_last()[0], hip.lines_last()[1], info[3], info[2]))
+    assert info[0] == w.n_brk == w.ref.n_brk and info[1] == BIG and info[3] == keep and w.shift == shift
+    yield w
+    hip.drop_tables(jump=False, frontier=False, lines=True)
+    assert hip.lines_info()[0] == 0 and hip.lines_info()[3] == 0
+    del w.ref
+    gc.collect()
+    torch.cuda.empty_cache()
+
+
+@case
+def test_lines_lookups_above_2_31_breaks(top, big):
+    """fmx_lines_batch_dev and fmx_line_spans_dev on device arrays, all outputs against the stand-in on the device."""
+    torch, hip, ref, m = top.torch, big.hip, big.ref, top.m
+    g = torch.Generator(device="cuda")
+    g.manual_seed(2032)
+    at = [int(ref.brk[j].item()) for j in (LINE - 1, LINE)]
+    special = [0, m - 1, LINE - 2, LINE - 1, LINE, LINE + 1, LINE + 2] + [b + d for b in at for d in (-1, 0, 1)]
+    special += ref.directory_crossings(big.shift) + [m, m + 1]
+    pos = torch.cat([torch.randint(0, m, (1 << 20,), generator=g, device="cuda"), torch.tensor(special, dtype=torch.int64, device="cuda")])
+    want = ref.lookup(pos)
+    fig = {"lines_below": int(((want[0] >= 0) & (want[0] < LINE)).sum()), "lines_above": int((want[0] >= LINE).sum()),
+           "starts_above": int((want[1] >= LINE).sum()), "no_line": int((want[0] < 0).sum())}
+    print("top bit: line lookups", fig)
+    assert fig["lines_below"] > 1000 and fig["lines_above"] > 1000 and fig["starts_above"] > 1000 and fig["no_line"] == 2
+    k = LINE - 1                                                  # brk[2^31 - 1] and brk[2^31], each - 1, 0, + 1: lines 2^31 - 1 .. 2^31 + 1
+    assert want[0][-12:-6].tolist()[1:3] == [k, k + 1] and want[0][-12:-6].tolist()[4:] == [k + 1, k + 2]
+    cross = want[0][-6:-2].tolist()
+    assert cross[0] < LINE <= cross[3] and cross[1] <= cross[2]
+    out = [torch.full((pos.numel(),), 7, dtype=torch.int64, device="cuda") for _ in range(3)]
+    torch.cuda.synchronize()
+    hip.line_of_dev(pos.data_ptr(), pos.numel(), *[o.data_ptr() for o in out], stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    for name, o, wv in zip(("line", "start", "end"), out, want):
+        bad = torch.nonzero(o != wv).reshape(-1)
+        assert bad.numel() == 0, (name, bad.numel(), pos[bad[:4]].tolist(), o[bad[:4]].tolist(), wv[bad[:4]].tolist())
+    # spans
+    nb = big.n_brk
+    lines = torch.cat([torch.randint(0, nb + 1, (1 << 20,), generator=g, device="cuda"),
+                       torch.tensor([0, 1, LINE - 1, LINE, nb - 1, nb, nb + 1], dtype=torch.int64, device="cuda")])
+    want = ref.spans(lines)
+    assert int((lines >= LINE).sum()) > 1000 and int((lines < LINE).sum()) > 1000 and want[0][-1].item() == -1 and want[1][-2].item() == m
+    out = [torch.full((lines.numel(),), 7, dtype=torch.int64, device="cuda") for _ in range(2)]
+    torch.cuda.synchronize()
+    hip.line_spans_dev(lines.data_ptr(), lines.numel(), *[o.data_ptr() for o in out], stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    for name, o, wv in zip(("start", "end"), out, want):
+        bad = torch.nonzero(o != wv).reshape(-1)
+        assert bad.numel() == 0, (name, bad.numel(), lines[bad[:4]].tolist(), o[bad[:4]].tolist(), wv[bad[:4]].tolist())
+
+
+def planted_hits(top, big):
+    """(off, occ) of three groups from the plan -- the chain of 199 slices of X, Y whole, none -- and their line hits by
+    lines_ref.occurrence_lines over the stand-in."""
+    def make():
+        plan = top.plan
+        y = plan.block["Y"]
+        per = {0: [(p, hi - lo) for _, b, lo, hi in chain(plan) for p in pt.occurrence_pairs(plan, b, lo, hi)],
+               1: [(p, len(y)) for p in pt.occurrence_pairs(plan, y, 0, len(y))]}
+        off, occ = expected_csr(per, 3, "all")
+        assert off.tolist() == [0, 995, 1002, 1002] and all((np.diff(occ["pos"][int(a):int(b)].astype(np.int64)) >= 0).all() for a, b in zip(off, off[1:]))
+        hoff, hits = lines_ref.occurrence_lines(big.ref, off, occ)
+        fig = {"lines": int(hits.size), "line_no_below": int((hits["line_no"] < LINE).sum()), "line_no_above": int((hits["line_no"] > LINE).sum()),
+               "of_them_Y": int((hits["line_no"][int(hoff[1]):] > LINE).sum())}
+        print("top bit: occurrence lines", fig)
+        assert fig["line_no_below"] > 100 and fig["line_no_above"] > 100 and fig["of_them_Y"] >= 2 and hoff[2] == hoff[3]
+        return off, occ, hoff, hits
+    return timed(top, "occurrence lines", make)
+
+
+@case
+def test_occurrence_lines_above_2_31_lines(top, big):
+    torch, hip = top.torch, big.hip
+    off, occ, hoff, hits = planted_hits(top, big)
+    got = hip.occurrence_lines(off, occ)
+    assert np.array_equal(got[0], hoff) and got[1].dtype == lines_ref.LINE_HIT and got[1].tobytes() == hits.tobytes(), (got[1][:3], hits[:3])
+    T = hits.size
+    d_off = torch.from_numpy(off.view(np.int64)).cuda()
+    d_occ = torch.from_numpy(occ.view(np.int64)).cuda()
+    d_loff = torch.full((4,), 7, dtype=torch.int64, device="cuda")
+    d_out = torch.full((T * 48 + 256,), 0xCD, dtype=torch.uint8, device="cuda")
+    args = (d_off.data_ptr(), d_occ.data_ptr(), occ.size, 3, d_loff.data_ptr())
+    assert hip.occurrence_lines_dev(*args, d_out.data_ptr(), T) == T
+    torch.cuda.synchronize()
+    raw = d_out.cpu().numpy()
+    assert raw[:T * 48].tobytes() == hits.tobytes() and (raw[T * 48:] == 0xCD).all() and np.array_equal(d_loff.cpu().numpy().view(np.uint64), hoff)
+    d_out.fill_(0xCD)
+    with pytest.raises(findex_amd.FmxError) as ei:
+        hip.occurrence_lines_dev(*args, d_out.data_ptr(), T - 1)
+    assert ei.value.code == OVERFLOW and str(T) in str(ei.value)
+    torch.cuda.synchronize()
+    raw = d_out.cpu().numpy()
+    assert raw[:(T - 1) * 48].tobytes() == hits[:T - 1].tobytes() and (raw[(T - 1) * 48:] == 0xCD).all()
+
+
+# ---------------------------------------------------------------- 6. line queries
+def same_hits(got, want):
+    assert np.array_equal(got[0], want[0]), (got[0], want[0])
+    assert got[1].dtype == lines_ref.LINE_HIT and got[1].tobytes() == want[1].tobytes(), (got[1][:3], want[1][:3])
+
+
+def bridge(hoff, hits):
+    """The smallest window with which a line of X above 2^31 sees a line of Y above 2^31: the least distance of two such lines."""
+    x = hits["line_no"][:int(hoff[1])].astype(np.int64)
+    y = hits["line_no"][int(hoff[1]):int(hoff[2])].astype(np.int64)
+    x, y = x[x > LINE], y[y > LINE]
+    assert x.size and y.size
+    return int(np.abs(x[:, None] - y[None, :]).min())
+
+
+@case
+def test_line_queries_anchor_and_terms_above_2_31(top, big):
+    hip = big.hip
+    _, _, hoff, hits = planted_hits(top, big)
+    W = bridge(hoff, hits)
+    assert 2 < W < M32
+    queries = [(0, [(1, 0, False)]), (0, [(1, 1, False)]), (0, [(1, W, False)]), (0, [(1, W - 1, False)]), (0, [(1, W, True)]),
+               (0, [(1, M32, False)]), (0, [(1, M32, True)]), (1, [(0, W, False)]), (1, [(0, M32, True), (1, 0, False)])]
+    want = linequery_ref.line_query(hoff, hits, queries)
+    size = np.diff(want[0].astype(np.int64)).tolist()
+    above = [int((want[1]["line_no"][int(a):int(b)] > LINE).sum()) for a, b in zip(want[0], want[0][1:])]
+    print("top bit: line queries: window %d, records %s, of them above 2^31 %s" % (W, size, above))
+    assert size[0] == size[1] == 0 and size[2] > size[3] and above[2] > above[3] == 0 and size[2] + size[4] == int(hoff[1])
+    assert size[5] == int(hoff[1]) and size[6] == 0 and above[5] > 100 and size[7] >= 1 and above[7] >= 1 and size[8] == 0
+    same_hits(hip.line_query(hoff, hits, queries), want)
+    assert hip.line_query_last()[3] == 7 * int(hoff[1]) + 2 * int(hoff[2] - hoff[1])
+
+
+@case
+def test_line_queries_all_lines_above_2_31_candidates(top, big):
+    """An ALL_LINES anchor has n_brk + 1 candidates, more than 2^31; the query behind it in the same call begins at a candidate
+    offset above 2^31.  Two of Y's seven copies lie above line 2^31 (three bytes of four are breaks, so line 2^31 begins near
+    position 2^31 * 4 / 3), five below: the lines around them stand on both sides."""
+    torch, hip = top.torch, big.hip
+    _, _, hoff, hits = planted_hits(top, big)
+    W = bridge(hoff, hits)
+    queries = [(None, [(1, 2, False)]), (0, [(1, W, False)])]
+    want = tb.line_query(hoff, hits, queries, big.ref)
+    first = want[1][:int(want[0][1])]
+    fig = {"records": int(first.size), "line_no_above": int((first["line_no"] > LINE + 1).sum()), "line_no_below": int((first["line_no"] < LINE).sum()),
+           "second_query": int(want[0][2] - want[0][1])}
+    print("top bit: all-lines query", fig)
+    assert 7 <= fig["records"] <= 35 and fig["line_no_above"] >= 2 and fig["second_query"] >= 1 and big.n_brk + 1 > LINE
+    T = want[1].size
+    d_off = torch.from_numpy(hoff.view(np.int64)).cuda()
+    d_hits = torch.from_numpy(hits.view(np.int64)).cuda()
+    d_qoff = torch.full((3,), 7, dtype=torch.int64, device="cuda")
+    d_out = torch.full((T * 48 + 48,), 0xCD, dtype=torch.uint8, device="cuda")
+    args = (d_off.data_ptr(), d_hits.data_ptr(), hits.size, 3, queries, d_qoff.data_ptr())
+    assert hip.line_query_dev(*args, 0, 0) == T                 # the counting call
+    assert hip.line_query_last()[3] == big.n_brk + 1 + int(hoff[1])
+    assert (d_out.cpu().numpy() == 0xCD).all() and np.array_equal(d_qoff.cpu().numpy().view(np.uint64), want[0])
+    assert hip.line_query_dev(*args, d_out.data_ptr(), T) == T
+    torch.cuda.synchronize()
+    raw = d_out.cpu().numpy()
+    assert raw[:T * 48].tobytes() == want[1].tobytes() and (raw[T * 48:] == 0xCD).all(), (raw[:T * 48].view(lines_ref.LINE_HIT)[:3], want[1][:3])
+    assert np.array_equal(d_qoff.cpu().numpy().view(np.uint64), want[0]) and hip.line_query_last()[3] == big.n_brk + 1 + int(hoff[1])
+    same_hits(hip.line_query(hoff, hits, queries), want)
+
+
+@case
+def test_line_queries_too_many_candidates(top, big):
+    """Two ALL_LINES queries are more than 2^32 candidates: refused with FMX_ERR_OVERFLOW before anything is allocated."""
+    torch, hip = top.torch, big.hip
+    _, _, hoff, hits = planted_hits(top, big)
+    assert 2 * (big.n_brk + 1) >= 1 << 32
+    d_off = torch.from_numpy(hoff.view(np.int64)).cuda()
+    d_hits = torch.from_numpy(hits.view(np.int64)).cuda()
+    d_qoff = torch.full((3,), 7, dtype=torch.int64, device="cuda")
+    d_out = torch.full((480,), 0xCD, dtype=torch.uint8, device="cuda")
+    queries = [(None, [(1, 2, False)]), (None, [(0, 0, True)])]
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    for cap in (1, 10):
+        with pytest.raises(findex_amd.FmxError) as ei:
+            hip.line_query_dev(d_off.data_ptr(), d_hits.data_ptr(), hits.size, 3, queries, d_qoff.data_ptr(), d_out.data_ptr(), cap)
+        assert ei.value.code == OVERFLOW and "the candidates of all queries together must be below 2^32" in str(ei.value)
+    torch.cuda.synchronize()
+    assert torch.cuda.mem_get_info()[0] == free0
+    assert d_qoff.cpu().tolist() == [7] * 3 and (d_out.cpu().numpy() == 0xCD).all()

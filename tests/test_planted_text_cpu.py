@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import lcp_checker
+import ngrams_ref
 import occ_ref
 import planted_text as pt
 import repeats_ref
@@ -132,6 +133,52 @@ def test_lcp_rows_against_kasai(seed):
     assert sorted(row_of[v.astype(np.int64)].tolist()) == sorted(planted)
     assert np.array_equal(lcp[row_of[v.astype(np.int64)]], val) and np.array_equal(sa[row_of[v.astype(np.int64)] + 1], nxt.astype(np.int64))
     assert int(lcp.max()) == len(plan.block["X"]) == int(val.max())
+
+
+def class_rows(plan, classes, L, row_of):
+    """sp of every class from the inverse suffix array: the rows of its copies, which must be consecutive."""
+    sp = np.zeros(classes.size, dtype=np.int64)
+    for j, at in enumerate(pt.ngram_occurrences(plan, classes, L)):
+        rows = np.sort(row_of[at])
+        assert np.array_equal(rows, rows[0] + np.arange(rows.size)), (L, j)
+        sp[j] = rows[0]
+    return sp
+
+
+@pytest.mark.parametrize("seed", SEEDS)
+def test_ngram_classes_against_the_definition(seed):
+    plan, text = scaled(seed)
+    s = lcp_checker.s_of_text(text)
+    sa = np_suffix_array(np.frombuffer(s, dtype=np.uint8))
+    row_of = np.empty(sa.size, dtype=np.int64)
+    row_of[sa] = np.arange(sa.size)
+    a = np.frombuffer(text, dtype=np.uint8)
+    seen = set()
+    for stop in (0, pt.STOP):
+        for L in plan.thresholds:
+            classes, summary = pt.ngram_classes(plan, L, stop)
+            sp = class_rows(plan, classes, L, row_of)
+            # the eligible window of the smallest row, for a length without a class
+            t = plan.m - L - sa[sa <= plan.m - L]
+            t = t[np.array([stop not in text[x:x + L] for x in t.tolist()], dtype=bool)] if stop else t
+            lone = (int(row_of[plan.m - L - t[0]]), int(t[0])) if t.size else None
+            rec, _ = ngrams_ref.brute(text, L, 1, "row", 0, stop)       # every eligible class, from the definition, once
+            every = tuple(rec[f].astype(np.int64) for f in ("sp", "count", "first_pos"))
+            for order in ("row", "count"):
+                for top in (0, 3):
+                    got_r, got_s = pt.ngram_result(classes, summary, sp, order, top, lone)
+                    want_r, want_s = ngrams_ref.result(every, 2, order, top, 9)
+                    assert got_r.dtype == ngrams_ref.RECORD and got_r.tobytes() == want_r.tobytes(), (L, stop, order, top)
+                    assert list(got_s) == list(ngrams_ref.FIELDS) and got_s == {f: want_s[f] for f in ngrams_ref.FIELDS}, (L, stop, order, top, got_s, want_s)
+            for bins in (1, 2, 6, 9):                             # 6: Y's seven copies are the overflow
+                assert np.array_equal(pt.ngram_spectrum(classes, summary, bins), ngrams_ref.result(every, 2, "row", 0, bins)[1]["spectrum"]), (L, stop, bins)
+            assert summary["windows"] == sum(not stop or stop not in text[x:x + L] for x in range(plan.m - L + 1))
+            seen.add((classes.size > 0, summary["largest_pos"] is None))
+            for c in classes[:3]:                                 # an entry is the window it names
+                b = plan.blocks[int(c["block"])]
+                assert text[int(c["first_pos"]):int(c["first_pos"]) + L] == b.data[int(c["offset"]):int(c["offset"]) + L]
+    assert seen == {(True, False), (False, True)} and a.size == plan.m
+    assert pt.ngram_classes(plan, plan.L0)[1]["largest_count"] == 7 and pt.ngram_classes(plan, 2 * plan.tile, pt.STOP)[0].size == 0
 
 
 def test_the_device_plan_meets_its_input_conditions():
