@@ -30,7 +30,7 @@ There is no CPU fallback: importing works anywhere, but every compute call needs
 library and a HIP device and fails loudly otherwise.
 """
 from ._lib import FmxError, MatchError, Re2PostSyntax, LIB_PATH, load  # noqa: F401
-from .searcher import HipFMSearcher  # noqa: F401
+from .searcher import HipFMSearcher, WORD_BYTES, boundary_class, class_words  # noqa: F401
 from .construct import bwt_from_text, bwt_from_text_chunked, bwt_from_text_dev, lcp_from_text, lcp_from_text_dev, write_bwt  # noqa: F401
 from .corpus import Corpus, HipCorpusSearcher, escape, is_binary, list_files  # noqa: F401
 from .regex import DFA, NFA, REParser, ReTree, SAResult, CompiledRegexes  # noqa: F401
@@ -74,4 +74,4 @@ def config_set(key, value):
     _lib.check(_lib.load().fmx_config_set(key.encode(), str(value).encode()))
 
 
-__all__ = ["Corpus", "HipCorpusSearcher", "escape", "is_binary", "list_files", "bwt_from_text", "bwt_from_text_dev", "lcp_from_text", "lcp_from_text_dev", "write_bwt", "config_set", "set_layout", "set_checkpoints", "set_ktab", "set_jump", "set_pipeline", "HipFMSearcher", "REParser", "ReTree", "SAResult", "NFA", "DFA", "CompiledRegexes", "FmxError", "MatchError", "Re2PostSyntax"]
+__all__ = ["WORD_BYTES", "boundary_class", "class_words", "Corpus", "HipCorpusSearcher", "escape", "is_binary", "list_files", "bwt_from_text", "bwt_from_text_dev", "lcp_from_text", "lcp_from_text_dev", "write_bwt", "config_set", "set_layout", "set_checkpoints", "set_ktab", "set_jump", "set_pipeline", "HipFMSearcher", "REParser", "ReTree", "SAResult", "NFA", "DFA", "CompiledRegexes", "FmxError", "MatchError", "Re2PostSyntax"]

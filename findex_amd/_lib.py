@@ -185,6 +185,14 @@ class fmx_rank_params(ctypes.Structure):
                 ("flags", ctypes.c_uint32)]
 
 
+class fmx_context_opts(ctypes.Structure):
+    _fields_ = [("left", ctypes.c_uint64 * 4), ("right", ctypes.c_uint64 * 4), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+FMX_CTX_START = 0x80
+
+
 class fmx_stats_t(ctypes.Structure):
     _fields_ = [("rank_queries", ctypes.c_uint64), ("backward_steps", ctypes.c_uint64),
                 ("launches", ctypes.c_uint64), ("last_kernel_ms", ctypes.c_double),
@@ -314,6 +322,10 @@ SYMBOLS = {
     "fmx_corpus_rank_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _P(fmx_rank_params), _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "fmx_corpus_rank_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(_u64),
                                     _P(_u64), _P(_u64)]),
+    "fmx_corpus_rank_sets": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(fmx_rank_params), _vp, _vp, _vp, _vp, _sz, _vp,
+                                    _vp]),
+    "fmx_corpus_rank_sets_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(fmx_rank_params), _vp, _vp, _vp, _vp, _sz,
+                                        _vp, _vp, _vp]),
     "fmx_occ_host": (_i32, [_vp, _i32, ctypes.c_int64, _P(_u64)]),
     "fmx_calc_gaps_chain": (_i32, [_vp, _vp, _sz, _u64, _i32, _u64, _vp, _P(_sz)]),
     "fmx_regex_compile": (_i32, [_cp, _i32, _P(_vp)]),
@@ -333,6 +345,11 @@ SYMBOLS = {
     "fmx_occurrences": (_i32, [_vp, _vp, _vp, _sz, _sz, _P(fmx_occ_opts), _vp, _vp, _sz, _P(_sz)]),
     "fmx_occurrences_dev": (_i32, [_vp, _vp, _vp, _sz, _sz, _P(fmx_occ_opts), _vp, _vp, _sz, _P(_sz), _vp]),
     "fmx_occurrences_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(_u64)]),
+    "fmx_context_filter": (_i32, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _P(_sz)]),
+    "fmx_context_filter_dev": (_i32, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _P(_sz), _vp]),
+    "fmx_context_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(_u64), _P(_u64)]),
+    "fmx_search_context_batch": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_context_opts), _vp, _vp, _sz, _P(_sz)]),
+    "fmx_search_context_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_context_opts), _vp, _vp, _sz, _P(_sz), _vp]),
     "fmx_lines_prepare": (_i32, [_vp, _vp, _sz]),
     "fmx_lines_info": (_i32, [_vp, _P(_u64), _vp, _P(_u32), _P(_u32), _P(_u64), _P(ctypes.c_double)]),
     "fmx_lines_batch": (_i32, [_vp, _vp, _sz, _vp, _vp, _vp]),

@@ -230,10 +230,12 @@ __global__ __launch_bounds__(kCoThreads) void k_corpus_map(CoMap m, const unsign
 __global__ __launch_bounds__(kCoThreads) void k_corpus_list_keys(CoMap m, const unsigned long long *__restrict__ sa, uint64_t rows,
                                                                  const unsigned long long *__restrict__ off, uint64_t k,
                                                                  uint64_t pat_len, int doc_bits,
+                                                                 const unsigned long long *__restrict__ set_off, uint64_t n_slots,
                                                                  unsigned long long *__restrict__ key, uint32_t *__restrict__ val) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < rows; j += stride) {
-    const uint64_t i = upper_bound(off, 0, k + 1, j) - 1;
+    uint64_t i = upper_bound(off, 0, k + 1, j) - 1;
+    if (set_off) i = upper_bound(set_off, 0, n_slots + 1, i) - 1;      // the slot that holds interval i (set_off[0] = 0 <= i)
     const uint64_t s = sa[j];
     uint32_t d = (uint32_t)m.n_docs;
     uint64_t eo, ro;
@@ -386,7 +388,8 @@ int corpus_index_check(const Corpus *c, const fmx_index *idx, size_t k, hipStrea
 }
 
 int corpus_doc_keys(const Corpus *c, const fmx_index *idx, const void *d_sp, const void *d_ep, size_t k, uint64_t pat_len,
-                    uint64_t max_per, hipStream_t st, const char *noun, DevMem &mem, Events<5> &ev, DocKeys &out) {
+                    uint64_t max_per, hipStream_t st, const char *noun, DevMem &mem, Events<5> &ev, DocKeys &out,
+                    const unsigned long long *d_set_off, uint64_t n_slots) {
   const std::string what = std::string("a ") + noun;
   int rc;
   if ((rc = device_room(8 * ((uint64_t)k + 1) + 4096, what))) return rc;
@@ -403,7 +406,7 @@ int corpus_doc_keys(const Corpus *c, const fmx_index *idx, const void *d_sp, con
   out.doc_bits = bits_for(c->n_docs);                               // documents 0 .. n_docs (n_docs: no document) fit
   out.rows = rows;
   if (rows == 0) return FMX_OK;
-  const int k_bits = bits_for(k);
+  const int k_bits = bits_for(d_set_off ? n_slots : (uint64_t)k);
   if ((rc = device_room(8 * rows + SortSpace::bytes(rows) + 8192, what))) return rc;
   unsigned long long *pos = nullptr;
   SortSpace &ws = out.ws;
@@ -413,7 +416,7 @@ int corpus_doc_keys(const Corpus *c, const fmx_index *idx, const void *d_sp, con
   if ((rc = fmx_locate_intervals_dev(idx, d_sp, d_ep, k, max_per, out.loc_off, pos, rows, st))) return rc;
   HIP_TRY(ev.record(1, st), "hipEventRecord");
   LAUNCH("k_corpus_list_keys", k_corpus_list_keys, dim3(co_grid(rows)), dim3(kCoThreads), st, c->map(), pos, (uint64_t)rows, out.loc_off,
-         (uint64_t)k, pat_len, out.doc_bits, ws.keys(), ws.vals());
+         (uint64_t)k, pat_len, out.doc_bits, d_set_off, n_slots, ws.keys(), ws.vals());
   HIP_TRY(ev.record(2, st), "hipEventRecord");
   HIP_TRY(ws.sort(rows, out.doc_bits + k_bits, st), "radix sort");
   HIP_TRY(ev.record(3, st), "hipEventRecord");

@@ -47,7 +47,8 @@ struct Corpus {
 // corpus_doc_keys: locate (the counts, then the rows), the key interval << doc_bits | document of every row -- the document
 // of stream position stream_len - pat_len - SA, n_docs where that is no stream position --, the radix sort over exactly
 // the significant bits, the head flags and their inclusive sum.  Allocates from `mem`, checks the room first and
-// synchronises `st` once, for the row count; records ev[0] before the locate, ev[1] after it, ev[2] after the key kernel
+// synchronises `st` once, for the row count; with d_set_off (u64[n_slots + 1], ascending from 0 to k: an interval -> slot map)
+// the key is slot << doc_bits | document, slot = the one whose [set_off[slot], set_off[slot + 1]) holds the interval; records ev[0] before the locate, ev[1] after it, ev[2] after the key kernel
 // and ev[3] after the sort.  rows == 0: nothing but loc_off is allocated and no event is recorded.
 struct DocKeys {
   unsigned long long *loc_off = nullptr;            // [k + 1]: the located rows of the intervals before i
@@ -58,6 +59,7 @@ struct DocKeys {
 };
 int corpus_index_check(const Corpus *c, const fmx_index *idx, size_t k, hipStream_t st, const char *noun);
 int corpus_doc_keys(const Corpus *c, const fmx_index *idx, const void *d_sp, const void *d_ep, size_t k, uint64_t pat_len,
-                    uint64_t max_per, hipStream_t st, const char *noun, DevMem &mem, Events<5> &ev, DocKeys &out);
+                    uint64_t max_per, hipStream_t st, const char *noun, DevMem &mem, Events<5> &ev, DocKeys &out,
+                    const unsigned long long *d_set_off = nullptr, uint64_t n_slots = 0);
 
 }  // namespace fmx

@@ -314,10 +314,19 @@ int rank_check_tables(const uint64_t *q_off, size_t n_queries, size_t n_terms, c
   return FMX_OK;
 }
 
+// set_off cuts the n_iv intervals into the n_terms slots
+int rank_check_sets(const uint64_t *set_off, size_t n_terms, size_t n_iv) {
+  if (set_off[0] != 0 || !offsets_monotonic(set_off, 0, n_terms) || set_off[n_terms] != n_iv)
+    return arg_fail("ranking: set_off must start at 0, never decrease and end at n_iv");
+  return FMX_OK;
+}
+
 // The call itself.  q_off and (when given) the weights are there twice: on the device for the kernels, on the host for
 // the checks, which the caller has made (rank_check_tables).  d_weights == nullptr: the default weights from df.
-int rank_core(const Corpus *c, const fmx_index *idx, const void *d_sp, const void *d_ep, size_t n_terms,
-              const unsigned long long *d_q_off, size_t n_queries, uint64_t max_slots, const fmx_rank_params &prm,
+// d_set_off != nullptr: n_iv intervals in n_terms slots (fmx_corpus_rank_sets); else n_iv == n_terms, a slot is an interval.
+int rank_core(const Corpus *c, const fmx_index *idx, const void *d_sp, const void *d_ep, size_t n_iv,
+              const unsigned long long *d_set_off, size_t n_terms, const unsigned long long *d_q_off, size_t n_queries,
+              uint64_t max_slots, const fmx_rank_params &prm,
               const double *d_weights, unsigned long long *d_out_off, uint32_t *d_out_doc, double *d_out_score, size_t cap,
               uint32_t *d_out_df, double *d_out_weight, hipStream_t st) {
   g_rank_last = RankLast{};
@@ -334,7 +343,7 @@ int rank_core(const Corpus *c, const fmx_index *idx, const void *d_sp, const voi
   HIP_TRY(ev2.create(), "hipEventCreate");
   DevMem mem;
   DocKeys dk;
-  if ((rc = corpus_doc_keys(c, idx, d_sp, d_ep, n_terms, 1, prm.max_per, st, "ranking", mem, ev, dk))) return rc;
+  if ((rc = corpus_doc_keys(c, idx, d_sp, d_ep, n_iv, 1, prm.max_per, st, "ranking", mem, ev, dk, d_set_off, n_terms))) return rc;
   const uint64_t rows = dk.rows;
   // df, and with it the posting count, to the host: the weights are computed there
   if ((rc = device_room(12 * ((uint64_t)n_terms + 1) + 4096, "a ranking"))) return rc;
@@ -437,19 +446,27 @@ int fmx_corpus_rank_last(double *locate_ms, double *postings_ms, double *score_m
   return FMX_OK;
 }
 
-int fmx_corpus_rank_dev(const fmx_corpus *corpus, const fmx_index *idx, const void *d_sp, const void *d_ep, size_t n_terms,
-                        const void *d_q_off, size_t n_queries, const fmx_rank_params *params, const void *d_weights,
-                        void *d_out_off, void *d_out_doc, void *d_out_score, size_t cap, void *d_out_df, void *d_out_weight,
-                        void *stream) {
-  if (!corpus || !idx || !params || !d_q_off || !d_out_off || (n_terms && (!d_sp || !d_ep)) || (cap && (!d_out_doc || !d_out_score)))
+// both device forms: d_set_off == nullptr is fmx_corpus_rank_dev (n_iv == n_terms)
+static int rank_dev(const fmx_corpus *corpus, const fmx_index *idx, const void *d_sp, const void *d_ep, size_t n_iv,
+                    const void *d_set_off, size_t n_terms, const void *d_q_off, size_t n_queries, const fmx_rank_params *params,
+                    const void *d_weights, void *d_out_off, void *d_out_doc, void *d_out_score, size_t cap, void *d_out_df,
+                    void *d_out_weight, void *stream) {
+  if (!corpus || !idx || !params || !d_q_off || !d_out_off || (n_iv && (!d_sp || !d_ep)) || (cap && (!d_out_doc || !d_out_score)))
     return arg_fail("null argument");
   int rc = rank_check_params(params);
   if (rc) return rc;
   if ((uint64_t)n_queries >= 0xffffffffull) return arg_fail("ranking: too many queries");
+  if ((uint64_t)n_terms >= 0xffffffffull) return arg_fail("ranking: too many slots");
   const Corpus *c = reinterpret_cast<const Corpus *>(corpus);
   hipStream_t st = (hipStream_t)stream;
-  if ((rc = corpus_index_check(c, idx, n_terms, st, "ranking"))) return rc;
+  if ((rc = corpus_index_check(c, idx, n_iv, st, "ranking"))) return rc;
   // the tables the checks read, on the host
+  if (d_set_off) {
+    std::vector<uint64_t> set_off(n_terms + 1);
+    HIP_TRY(hipMemcpyAsync(set_off.data(), d_set_off, 8 * ((uint64_t)n_terms + 1), hipMemcpyDeviceToHost, st), "D2H(set_off)");
+    HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
+    if ((rc = rank_check_sets(set_off.data(), n_terms, n_iv))) return rc;
+  }
   std::vector<uint64_t> q_off(n_queries + 1);
   std::vector<double> weights(d_weights ? n_terms : 0);
   HIP_TRY(hipMemcpyAsync(q_off.data(), d_q_off, 8 * ((uint64_t)n_queries + 1), hipMemcpyDeviceToHost, st), "D2H(q_off)");
@@ -457,38 +474,63 @@ int fmx_corpus_rank_dev(const fmx_corpus *corpus, const fmx_index *idx, const vo
   HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
   uint64_t max_slots = 0;
   if ((rc = rank_check_tables(q_off.data(), n_queries, n_terms, d_weights ? weights.data() : nullptr, &max_slots))) return rc;
-  return rank_core(c, idx, d_sp, d_ep, n_terms, static_cast<const unsigned long long *>(d_q_off), n_queries, max_slots, *params,
+  return rank_core(c, idx, d_sp, d_ep, n_iv, static_cast<const unsigned long long *>(d_set_off), n_terms,
+                   static_cast<const unsigned long long *>(d_q_off), n_queries, max_slots, *params,
                    static_cast<const double *>(d_weights), static_cast<unsigned long long *>(d_out_off),
                    static_cast<uint32_t *>(d_out_doc), static_cast<double *>(d_out_score), cap, static_cast<uint32_t *>(d_out_df),
                    static_cast<double *>(d_out_weight), st);
 }
 
-int fmx_corpus_rank(const fmx_corpus *corpus, const fmx_index *idx, const uint64_t *sp, const uint64_t *ep, size_t n_terms,
-                    const uint64_t *q_off, size_t n_queries, const fmx_rank_params *params, const double *weights,
-                    uint64_t *out_off, uint32_t *out_doc, double *out_score, size_t cap, uint32_t *out_df, double *out_weight) {
-  if (!corpus || !idx || !params || !q_off || !out_off || (n_terms && (!sp || !ep)) || (cap && (!out_doc || !out_score)))
+int fmx_corpus_rank_dev(const fmx_corpus *corpus, const fmx_index *idx, const void *d_sp, const void *d_ep, size_t n_terms,
+                        const void *d_q_off, size_t n_queries, const fmx_rank_params *params, const void *d_weights,
+                        void *d_out_off, void *d_out_doc, void *d_out_score, size_t cap, void *d_out_df, void *d_out_weight,
+                        void *stream) {
+  return rank_dev(corpus, idx, d_sp, d_ep, n_terms, nullptr, n_terms, d_q_off, n_queries, params, d_weights, d_out_off, d_out_doc,
+                  d_out_score, cap, d_out_df, d_out_weight, stream);
+}
+
+int fmx_corpus_rank_sets_dev(const fmx_corpus *corpus, const fmx_index *idx, const void *d_sp, const void *d_ep, size_t n_iv,
+                             const void *d_set_off, size_t n_terms, const void *d_q_off, size_t n_queries,
+                             const fmx_rank_params *params, const void *d_weights, void *d_out_off, void *d_out_doc,
+                             void *d_out_score, size_t cap, void *d_out_df, void *d_out_weight, void *stream) {
+  if (!d_set_off) return arg_fail("null argument");
+  return rank_dev(corpus, idx, d_sp, d_ep, n_iv, d_set_off, n_terms, d_q_off, n_queries, params, d_weights, d_out_off, d_out_doc,
+                  d_out_score, cap, d_out_df, d_out_weight, stream);
+}
+
+// both host forms: set_off == nullptr is fmx_corpus_rank (n_iv == n_terms)
+static int rank_host(const fmx_corpus *corpus, const fmx_index *idx, const uint64_t *sp, const uint64_t *ep, size_t n_iv,
+                     const uint64_t *set_off, size_t n_terms, const uint64_t *q_off, size_t n_queries, const fmx_rank_params *params,
+                     const double *weights, uint64_t *out_off, uint32_t *out_doc, double *out_score, size_t cap, uint32_t *out_df,
+                     double *out_weight) {
+  if (!corpus || !idx || !params || !q_off || !out_off || (n_iv && (!sp || !ep)) || (cap && (!out_doc || !out_score)))
     return arg_fail("null argument");
   int rc = rank_check_params(params);
   if (rc) return rc;
   if ((uint64_t)n_queries >= 0xffffffffull) return arg_fail("ranking: too many queries");
   uint64_t max_slots = 0;
   if ((rc = rank_check_tables(q_off, n_queries, n_terms, weights, &max_slots))) return rc;
+  if (set_off && (rc = rank_check_sets(set_off, n_terms, n_iv))) return rc;
   // everything above is decided before a handle or the device is touched
   const Corpus *c = reinterpret_cast<const Corpus *>(corpus);
   uint64_t n = 0;
   if ((rc = fmx_n(idx, &n))) return rc;
-  for (size_t t = 0; t < n_terms; t++)
+  for (size_t t = 0; t < n_iv; t++)
     if (sp[t] > n || ep[t] > n) return arg_fail("interval out of range (sp, ep <= n)");
   HostCall hc;
   if ((rc = hc.open())) return rc;
-  if ((rc = corpus_index_check(c, idx, n_terms, hc.own.s, "ranking"))) return rc;
-  const uint64_t nt = n_terms, nq = n_queries;
-  if ((rc = device_room(36 * nt + 8 * (nq + 1) + 8 * (nq + 1) + 12 * (uint64_t)cap + 8192, "a ranking"))) return rc;
-  unsigned long long *d_sp = nullptr, *d_ep = nullptr, *d_q_off = nullptr, *d_off = nullptr;
+  if ((rc = corpus_index_check(c, idx, n_iv, hc.own.s, "ranking"))) return rc;
+  const uint64_t nt = n_terms, nq = n_queries, ni = n_iv;
+  if ((rc = device_room(16 * ni + 28 * nt + 8 * (nq + 1) + 8 * (nq + 1) + 12 * (uint64_t)cap + 8192, "a ranking"))) return rc;
+  unsigned long long *d_sp = nullptr, *d_ep = nullptr, *d_q_off = nullptr, *d_off = nullptr, *d_set_off = nullptr;
   double *d_w = nullptr, *d_score = nullptr, *d_ow = nullptr;
   uint32_t *d_doc = nullptr, *d_df = nullptr;
-  DEV_ALLOC(hc.mem, d_sp, 8 * nt, "rank");
-  DEV_ALLOC(hc.mem, d_ep, 8 * nt, "rank");
+  DEV_ALLOC(hc.mem, d_sp, 8 * ni, "rank");
+  DEV_ALLOC(hc.mem, d_ep, 8 * ni, "rank");
+  if (set_off) {
+    DEV_ALLOC(hc.mem, d_set_off, 8 * (nt + 1), "rank");
+    HIP_TRY(hipMemcpyAsync(d_set_off, set_off, 8 * (nt + 1), hipMemcpyHostToDevice, hc.own.s), "H2D(set_off)");
+  }
   DEV_ALLOC(hc.mem, d_q_off, 8 * (nq + 1), "rank");
   DEV_ALLOC(hc.mem, d_off, 8 * (nq + 1), "rank");
   DEV_ALLOC(hc.mem, d_doc, 4 * (uint64_t)cap, "rank");
@@ -496,14 +538,14 @@ int fmx_corpus_rank(const fmx_corpus *corpus, const fmx_index *idx, const uint64
   DEV_ALLOC(hc.mem, d_df, 4 * nt, "rank");
   DEV_ALLOC(hc.mem, d_ow, 8 * nt, "rank");
   if (weights) DEV_ALLOC(hc.mem, d_w, 8 * nt, "rank");
-  if (nt) {
-    HIP_TRY(hipMemcpyAsync(d_sp, sp, 8 * nt, hipMemcpyHostToDevice, hc.own.s), "H2D(sp)");
-    HIP_TRY(hipMemcpyAsync(d_ep, ep, 8 * nt, hipMemcpyHostToDevice, hc.own.s), "H2D(ep)");
-    if (weights) HIP_TRY(hipMemcpyAsync(d_w, weights, 8 * nt, hipMemcpyHostToDevice, hc.own.s), "H2D(weights)");
+  if (ni) {
+    HIP_TRY(hipMemcpyAsync(d_sp, sp, 8 * ni, hipMemcpyHostToDevice, hc.own.s), "H2D(sp)");
+    HIP_TRY(hipMemcpyAsync(d_ep, ep, 8 * ni, hipMemcpyHostToDevice, hc.own.s), "H2D(ep)");
   }
+  if (nt && weights) HIP_TRY(hipMemcpyAsync(d_w, weights, 8 * nt, hipMemcpyHostToDevice, hc.own.s), "H2D(weights)");
   HIP_TRY(hipMemcpyAsync(d_q_off, q_off, 8 * (nq + 1), hipMemcpyHostToDevice, hc.own.s), "H2D(q_off)");
-  if ((rc = rank_core(c, idx, d_sp, d_ep, n_terms, d_q_off, n_queries, max_slots, *params, weights ? d_w : nullptr, d_off, d_doc,
-                      d_score, cap, d_df, d_ow, hc.own.s)))
+  if ((rc = rank_core(c, idx, d_sp, d_ep, n_iv, d_set_off, n_terms, d_q_off, n_queries, max_slots, *params, weights ? d_w : nullptr,
+                      d_off, d_doc, d_score, cap, d_df, d_ow, hc.own.s)))
     return rc;
   if (nt) {
     if ((rc = hc.download(out_df, d_df, 4 * nt, "D2H(df)")) || (rc = hc.download(out_weight, d_ow, 8 * nt, "D2H(weights)"))) return rc;
@@ -517,6 +559,22 @@ int fmx_corpus_rank(const fmx_corpus *corpus, const fmx_index *idx, const uint64
   }
   if (total > cap) return csr_overflow("corpus_rank", total, cap);
   return FMX_OK;
+}
+
+int fmx_corpus_rank(const fmx_corpus *corpus, const fmx_index *idx, const uint64_t *sp, const uint64_t *ep, size_t n_terms,
+                    const uint64_t *q_off, size_t n_queries, const fmx_rank_params *params, const double *weights,
+                    uint64_t *out_off, uint32_t *out_doc, double *out_score, size_t cap, uint32_t *out_df, double *out_weight) {
+  return rank_host(corpus, idx, sp, ep, n_terms, nullptr, n_terms, q_off, n_queries, params, weights, out_off, out_doc, out_score, cap,
+                   out_df, out_weight);
+}
+
+int fmx_corpus_rank_sets(const fmx_corpus *corpus, const fmx_index *idx, const uint64_t *sp, const uint64_t *ep, size_t n_iv,
+                         const uint64_t *set_off, size_t n_terms, const uint64_t *q_off, size_t n_queries,
+                         const fmx_rank_params *params, const double *weights, uint64_t *out_off, uint32_t *out_doc,
+                         double *out_score, size_t cap, uint32_t *out_df, double *out_weight) {
+  if (!set_off) return arg_fail("null argument");
+  return rank_host(corpus, idx, sp, ep, n_iv, set_off, n_terms, q_off, n_queries, params, weights, out_off, out_doc, out_score, cap,
+                   out_df, out_weight);
 }
 
 }  // extern "C"

@@ -2,12 +2,14 @@
 
     python -m findex_amd.grep BASE REGEX [REGEX ..] [--mode all|longest|disjoint] [--max-per N] [--max-steps N] [-C BYTES] [--count]
                                                     [-n] [-A N] [-B N] [--context-lines N] [-c] [-l] [--max-line BYTES]
-                                                    [-v] [--and REGEX ..] [--not REGEX ..] [--near N | --same-file]
+                                                    [-v] [--and REGEX ..] [--not REGEX ..] [--near N | --same-file] [-w]
 
 BASE names BASE.bwt / BASE.aux / BASE.docs as `python -m findex_amd.index --dir D --out BASE` writes them.  One line per
 match, `name:raw_off:text`, regex by regex in (file, offset) order; -C BYTES shows that many bytes of the file around the
 match, cut at newlines; --count prints one count per regex instead.  The regexes are the reference's (REParser.re2post) and are
-matched against the escaped stream (HipCorpusSearcher.grep).
+matched against the escaped stream (HipCorpusSearcher.grep).  -w keeps only matches that stand as whole words: the bytes next
+to a match are not 0-9 A-Z a-z _ or 0x80 .. 0xFF, or the file ends there; it applies to every regex of the call, --and / --not
+included.
 
 By lines (HipCorpusSearcher.grep_lines; any of the flags below): -n prints `name:line_no:line`, one line of output per matching
 line, regex by regex in (file, line) order; -A N / -B N / --context-lines N add that many lines after / before / around, as
@@ -56,6 +58,7 @@ def parser():
     near = ap.add_mutually_exclusive_group()
     near.add_argument("--near", type=line_count, default=None, metavar="N", help="--and / --not look N lines to either side (default 0: the same line)")
     near.add_argument("--same-file", action="store_true", help="--and / --not look at the whole file")
+    ap.add_argument("-w", "--word-regexp", dest="words", action="store_true", help="only matches that stand as whole words")
     ap.add_argument("--little-endian", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     return ap
@@ -141,11 +144,12 @@ def format_files(names, hits):
 def main_lines(cs, a, out):
     before, after = context_of(a)
     names = cs.corpus.names
+    w = {"words": True} if getattr(a, "words", False) else {}
     if where(a):
         queries = queries_of(a)
-        grep_lines = lambda _regexes, **kw: cs.grep_lines_where(queries, **kw)
+        grep_lines = lambda _regexes, **kw: cs.grep_lines_where(queries, **w, **kw)
     else:
-        grep_lines = cs.grep_lines
+        grep_lines = lambda regexes, **kw: cs.grep_lines(regexes, **w, **kw)
     if a.count_lines or a.files_with_matches:
         off, hits, truncated = grep_lines(a.regex, mode=a.mode, max_steps=a.max_steps, max_per=a.max_per)
         fmt = format_counts if a.count_lines else format_files
@@ -179,7 +183,7 @@ def main(argv=None):
             if truncated:
                 print("matches longer than --max-steps were cut", file=sys.stderr)
             return 0
-        off, occ, truncated = cs.grep(a.regex, mode=a.mode, max_steps=a.max_steps, max_per=a.max_per)
+        off, occ, truncated = cs.grep(a.regex, mode=a.mode, max_steps=a.max_steps, max_per=a.max_per, **({"words": True} if a.words else {}))
         out = sys.stdout.buffer
         if a.count:
             for i in range(len(a.regex)):

@@ -1,11 +1,12 @@
 """Ranked retrieval over a corpus index: which files are the best matches for these words?
 
-    python -m findex_amd.rank BASE "words of a query" ["another query" ..] [--top K] [--all] [--k1 X] [--b X] [--device D]
+    python -m findex_amd.rank BASE "words of a query" ["another query" ..] [--top K] [--all] [-w] [--k1 X] [--b X] [--device D]
                                                                             [--little-endian]
 
 BASE names BASE.bwt / BASE.aux / BASE.docs as `python -m findex_amd.index --dir D --out BASE` writes them.  Every positional
-argument is one query, split on white space into its terms.  Terms are SUBSTRINGS, as everywhere in this index: `cat` counts
-in `concatenate` too; there is no whole-word matching.  A file is scored by BM25 over its terms' occurrence counts
+argument is one query, split on white space into its terms.  Without -w terms are SUBSTRINGS, as everywhere in this index:
+`cat` counts in `concatenate` too.  With -w / --words a term counts only where it stands as a whole word: the bytes next to it are
+not 0-9 A-Z a-z _ or 0x80 .. 0xFF, or the file ends there (HipFMSearcher.search_words).  A file is scored by BM25 over its terms' occurrence counts
 (HipCorpusSearcher.rank, fmx_corpus_rank: scored and cut to the best K on the device).  Output: one line per hit,
 `score<TAB>file`, best first; the queries' blocks are separated by a blank line.  --all keeps only files that hold every term of
 the query.
@@ -16,11 +17,12 @@ import sys
 
 def parser():
     ap = argparse.ArgumentParser(prog="python -m findex_amd.rank", description=__doc__.split("\n\n")[0],
-                                 epilog="Terms are substrings, as everywhere in this index: there is no whole-word matching.")
+                                 epilog="Without -w terms are substrings, as everywhere in this index; with -w they are whole words.")
     ap.add_argument("base")
-    ap.add_argument("query", nargs="+", help="the words of one query, split on white space; every word is matched as a substring")
+    ap.add_argument("query", nargs="+", help="the words of one query, split on white space; every word is matched as a substring unless -w is given")
     ap.add_argument("--top", type=int, default=10, metavar="K", help="files per query, 1 .. 1024 (default 10)")
     ap.add_argument("--all", dest="all_", action="store_true", help="only files that hold every term of the query")
+    ap.add_argument("-w", "--words", action="store_true", help="a term counts only where it stands as a whole word")
     ap.add_argument("--k1", type=float, default=1.2)
     ap.add_argument("--b", type=float, default=0.75)
     ap.add_argument("--device", type=int, default=0)
@@ -53,7 +55,7 @@ def main(argv=None):
     from .corpus import HipCorpusSearcher
     cs = HipCorpusSearcher.open(a.base, bigEndian=not a.little_endian, device=a.device)
     try:
-        off, doc, score, _, _ = cs.rank(queries, top=a.top, k1=a.k1, b=a.b, match="all" if a.all_ else "any")
+        off, doc, score, _, _ = cs.rank(queries, top=a.top, k1=a.k1, b=a.b, match="all" if a.all_ else "any", **({"words": True} if a.words else {}))
         out = sys.stdout.buffer
         for row in render(cs.corpus.names, off, doc, score):
             out.write(row + b"\n")

@@ -8,6 +8,26 @@ import numpy as np
 from . import _lib
 
 
+# the bytes of a word: 0-9 A-Z a-z _ and 0x80 .. 0xFF, so that a UTF-8 letter is no word boundary.  The boundary class is the
+# complement: it holds 0 (the ends of the text) and 1 (the corpus separator), so no file boundary needs a special case.
+WORD_BYTES = bytes(sorted(set(b"0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz_") | set(range(0x80, 0x100))))
+
+
+def class_words(members):
+    """The 256-bit set fmx_context_filter and fmx_context_opts take, as uint64[4]: bit c of word c // 64 for every byte value of
+    `members` (bytes or an iterable of ints; 0 stands for an end of the text)."""
+    w = [0, 0, 0, 0]
+    for c in bytes(members):
+        w[c >> 6] |= 1 << (c & 63)
+    return np.array(w, dtype=np.uint64)
+
+
+def boundary_class(word=WORD_BYTES):
+    """The bytes that may stand next to a word: every byte that is not in `word`, 0 (an end of the text) included."""
+    word = set(bytes(word))
+    return bytes(c for c in range(256) if c not in word)
+
+
 def _swap_ext(filename, ext):
     """BWTTempStorage.gen*Filename, bwtmerger.scala:17-48"""
     return os.path.splitext(filename)[0] + ext
@@ -587,8 +607,145 @@ class HipFMSearcher:
         _lib.check(self._L.fmx_occurrences_last(*[ctypes.byref(x) for x in t], ctypes.byref(rows)))
         return tuple(float(x.value) for x in t) + (int(rows.value),)
 
+    # ---- context: rows whose neighbouring text bytes are in a class -- whole words (fmx_context_filter)
+    CTX_START = _lib.FMX_CTX_START
+
+    def search_context_batch(self, pat, off, left, right, cap=None):
+        """fmx_search_context_batch: the patterns as search_batch takes them (strings of reverse(text)), left / right = the byte
+        values (bytes; 0 = the text begins / ends there) that may stand in front of / behind an occurrence in the TEXT.
+        -> (off[k + 1], runs): pattern i's rows are the disjoint ranges runs[off[i]:off[i + 1]], a RESULT array {i, length,
+        sp, ep} in ascending sp.  cap=None: a counting call sizes the buffer."""
+        pat = np.ascontiguousarray(pat, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        k = off.size - 1
+        if k < 0:
+            raise ValueError("off needs at least one entry")
+        opts = _lib.fmx_context_opts()
+        for j, (lw, rw) in enumerate(zip(class_words(left), class_words(right))):
+            opts.left[j], opts.right[j] = int(lw), int(rw)
+        args = (self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts))
+        return self._csr_hits(self._L.fmx_search_context_batch, args, k, self.RESULT, cap)
+
+    def context_filter(self, records, right, mode=None, cap=None):
+        """fmx_context_filter: the runs of rows of every (group, len, sp, ep) record whose following text byte is in `right`
+        (byte values; 0 = the text ends there).  mode: None or one byte per record, lead | CTX_START.  -> (off[k + 1], runs):
+        record j's runs are runs[off[j]:off[j + 1]], a RESULT array {group, len - lead, run_sp, run_ep}."""
+        rec = np.ascontiguousarray(records, dtype=self.RESULT).reshape(-1)
+        if mode is not None:
+            mode = np.ascontiguousarray(mode, dtype=np.uint8).reshape(-1)
+            if mode.size != rec.size:
+                raise ValueError("mode: one byte per record")
+        rw = class_words(right)
+        args = (self._h, _ptr(rec), _ptr(mode) if mode is not None else None, rec.size, _ptr(rw))
+        return self._csr_hits(self._L.fmx_context_filter, args, rec.size, self.RESULT, cap)
+
+    def context_filter_dev(self, d_rec, d_mode, k, right, d_out_off, d_out, cap, stream=0, grow=False):
+        """fmx_context_filter_dev: device pointers (24-byte records in and out, k mode bytes or 0, u64 out_off[k + 1]); allocates
+        and synchronises.  -> the exact number of runs; cap = 0 is the counting call, grow as occurrences_dev."""
+        rw = class_words(right)
+        n_out = ctypes.c_size_t()
+        rc = self._L.fmx_context_filter_dev(self._h, _dp(d_rec), _dp(d_mode), int(k), _ptr(rw), _dp(d_out_off), _dp(d_out), int(cap),
+                                            ctypes.byref(n_out), _dp(stream))
+        if not (rc == _lib.FMX_ERR_OVERFLOW and (int(cap) == 0 or grow)):
+            _lib.check(rc)
+        return int(n_out.value)
+
+    def context_last(self):
+        """fmx_context_last: (search ms, chain ms, ranges + count + scans + emit ms, rows tested, runs found) of this thread's
+        last context call."""
+        t = [ctypes.c_double() for _ in range(3)]
+        rows, runs = ctypes.c_uint64(), ctypes.c_uint64()
+        _lib.check(self._L.fmx_context_last(*[ctypes.byref(x) for x in t], ctypes.byref(rows), ctypes.byref(runs)))
+        return tuple(float(x.value) for x in t) + (int(rows.value), int(runs.value))
+
+    def search_words(self, pats, word=WORD_BYTES, cap=None):
+        """The whole-word occurrences of text strings `pats` (bytes each): search_context_batch over their reverses with the
+        boundary class of `word` on both sides.  -> (off[k + 1], runs)."""
+        pats = [bytes(q) for q in pats]
+        off = np.zeros(len(pats) + 1, dtype=np.uint64)
+        np.cumsum([len(q) for q in pats], out=off[1:])
+        pat = np.frombuffer(b"".join(q[::-1] for q in pats), dtype=np.uint8)
+        cls = boundary_class(word)
+        return self.search_context_batch(pat, off, cls, cls, cap)
+
+    def locate_words(self, q, max_hits=None, word=WORD_BYTES):
+        """Sorted text offsets of the whole-word occurrences of q -- of at most max_hits rows."""
+        q = bytes(q)
+        if not q:
+            raise ValueError("empty pattern")
+        _, runs = self.search_words([q], word)
+        sp, ep = runs["sp"].copy(), runs["ep"].copy()
+        if max_hits is not None:
+            left = int(max_hits)
+            for j in range(sp.size):
+                ep[j] = min(int(ep[j]), int(sp[j]) + left)
+                left -= int(ep[j]) - int(sp[j])
+        _, pos = self.locate_intervals(sp, ep)
+        return np.sort(self.text_offsets(pos, self.n, len(q)))
+
+    def _finditer_words(self, regexes, word, mode, max_steps, max_per, lineOnly, corpus, match_cap, occ_cap):
+        """finditer(words=True): one batch of 2k.  Regex i becomes (cls)(re) -- cls = the boundary bytes >= 1 that occur in the
+        index (counts()), each backslash-quoted, as an alternation: neither engine of fmx_regex.cpp has a case for a [..] set
+        in front of a group, and none has a negated class -- and regex k + i becomes (re), for a match at text offset 0.  They
+        are compiled by REParser.createNFA: ReTree has no case for a group behind an alternation either (ConcatPoint,
+        retree.scala:240-295), and its paths stop at their first accepting state, so that a+n? would never reach the n.
+        The records of the 2k go to HBM, lead 1 for the first k and CTX_START for the rest, the group folded to i; then the
+        context filter (the byte behind), then the occurrences."""
+        import torch
+        from .regex import NFA, RegexBatch
+
+        class Source:                                            # what NFA() reads of a PostfixRe
+            def __init__(self, src):
+                self.src, self.lineOnly = src, bool(lineOnly)
+
+        res = [r if isinstance(r, str) else bytes(r).decode("latin-1") for r in regexes]
+        k = len(res)
+        counts = self.counts()
+        bnd = boundary_class(word)
+        cls = "|".join("\\" + chr(c) for c in bnd if c >= 1 and counts[c] > 0)
+        both = (["(" + cls + ")(" + r + ")" for r in res] if cls else []) + ["(" + r + ")" for r in res]
+        n_lead = k if cls else 0
+        batch = RegexBatch(self, [NFA(Source(r)) for r in both])
+        dev = ctypes.c_int()
+        _lib.check(self._L.fmx_device(self._h, ctypes.byref(dev)))
+        dev = torch.device("cuda", dev.value)
+        cap = int(match_cap)
+        while True:
+            d_res = torch.empty(3 * cap, dtype=torch.int64, device=dev)
+            try:
+                n_res = batch.match_dev(d_res.data_ptr(), cap, max_steps=max_steps + 1 if max_steps else 0)
+                break
+            except _lib.FmxError as e:
+                if e.code != _lib.FMX_ERR_OVERFLOW or "result buffer" not in str(e) or cap >= 1 << 28:
+                    raise
+                cap *= 4
+        kk = max(k, 1)
+        rec = d_res[: 3 * n_res].view(n_res, 3)
+        grp = rec[:, 0] & 0xFFFFFFFF
+        lead = grp < n_lead
+        d_mode = torch.where(lead, 1, self.CTX_START).to(torch.uint8).contiguous()
+        rec[:, 0] += (grp % kk) - grp if n_res else 0             # the group folded to i: every block of k is the k regexes
+        torch.cuda.synchronize(dev)
+        d_roff = torch.empty(n_res + 1, dtype=torch.int64, device=dev)
+        room = max(n_res, 1)
+        d_run = torch.empty(3 * room, dtype=torch.int64, device=dev)
+        n_run = self.context_filter_dev(d_res.data_ptr(), d_mode.data_ptr(), n_res, bnd, d_roff.data_ptr(), d_run.data_ptr(), room, grow=True)
+        if n_run > room:
+            d_run = torch.empty(3 * n_run, dtype=torch.int64, device=dev)
+            self.context_filter_dev(d_res.data_ptr(), d_mode.data_ptr(), n_res, bnd, d_roff.data_ptr(), d_run.data_ptr(), n_run)
+        d_off = torch.empty(kk + 1, dtype=torch.int64, device=dev)
+        room = int(occ_cap)
+        d_occ = torch.empty(4 * max(room, 1), dtype=torch.int64, device=dev)
+        total = self.occurrences_dev(d_run.data_ptr(), n_run, kk, d_off.data_ptr(), d_occ.data_ptr(), room, mode, max_per, corpus, grow=True)
+        if total > room:
+            d_occ = torch.empty(4 * total, dtype=torch.int64, device=dev)
+            self.occurrences_dev(d_run.data_ptr(), n_run, kk, d_off.data_ptr(), d_occ.data_ptr(), total, mode, max_per, corpus)
+        off = d_off.cpu().numpy().view(np.uint64)
+        occ = d_occ[: 4 * total].cpu().numpy().view(self.OCCURRENCE)
+        return off, occ, bool(batch.truncated)
+
     def finditer(self, regexes, mode="disjoint", max_steps=0, max_per=None, lineOnly=False, corpus=None, match_cap=1 << 20,
-                 occ_cap=1 << 20):
+                 occ_cap=1 << 20, words=False, word=WORD_BYTES):
         """Where a batch of regexes matches the indexed text: (off, occ, truncated) -- regex i's matches are
         occ[off[i]:off[i + 1]] (an OCCURRENCE array ascending by (pos, len)), truncated = the match was cut at max_steps
         (FMX_TRUNCATED).  regexes: strings (compiled here; lineOnly as ReTree.compile_batch), a CompiledRegexes set or a
@@ -596,9 +753,14 @@ class HipFMSearcher:
         records to begin with, four times as many after every overflow), fmx_occurrences_dev reads the results there (with room for
         occ_cap occurrences, and once more with the exact room when that was too little), and offsets and occurrences come down
         in one copy each: between the two calls only counts cross the link.  The device
-        buffers are torch tensors."""
+        buffers are torch tensors.  words=True (regex strings only): whole-word matches -- the bytes next to a match are not
+        in `word`, or the text ends there; the neighbours are not part of the match."""
         import torch
         from .regex import CompiledRegexes, RegexBatch, ReTree
+        if words:
+            if isinstance(regexes, (RegexBatch, CompiledRegexes)):
+                raise ValueError("finditer(words=True) takes regex strings: it compiles each with its left context")
+            return self._finditer_words(list(regexes), word, mode, max_steps, max_per, lineOnly, corpus, match_cap, occ_cap)
         if isinstance(regexes, RegexBatch):
             batch = regexes
         else:

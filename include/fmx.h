@@ -974,6 +974,23 @@ int fmx_corpus_rank_dev(const fmx_corpus *corpus, const fmx_index *idx, const vo
                         void *d_out_weight, void *stream);
 int fmx_corpus_rank_last(double *locate_ms, double *postings_ms, double *score_ms, double *select_ms, uint64_t *rows,
                          uint64_t *postings, uint64_t *candidates);
+/* fmx_corpus_rank_sets: the same ranking where a term slot is a SET of intervals: n_iv intervals sp[] / ep[],
+ * and set_off[n_terms + 1] (starting at 0, never decreasing, ending at n_iv; FMX_ERR_ARG otherwise) cuts them into the
+ * n_terms slots q_off speaks of.  tf(t, d) = the rows of ALL of slot t's intervals in document d: the caller promises
+ * intervals that are disjoint inside a slot, and a row given twice counts twice.  max_per applies per interval.  A slot
+ * without intervals has df = 0.  weights, out_df and out_weight are per slot.  Everything else -- the score, the tie order,
+ * the limits (with n_iv < 2^32 - 1 in the place of the interval count), the outputs, fmx_corpus_rank_last -- is
+ * fmx_corpus_rank's, and with set_off = 0, 1, .., n_terms the outputs are fmx_corpus_rank's byte for byte.  What the
+ * whole-word ranking runs on: the row ranges fmx_search_context_batch leaves are rows of the plain term.
+ * fmx_corpus_rank_sets_dev: every array a device pointer (d_set_off: u64[n_terms + 1]). */
+int fmx_corpus_rank_sets(const fmx_corpus *corpus, const fmx_index *idx, const uint64_t *sp, const uint64_t *ep, size_t n_iv,
+                         const uint64_t *set_off, size_t n_terms, const uint64_t *q_off, size_t n_queries,
+                         const fmx_rank_params *params, const double *weights, uint64_t *out_off, uint32_t *out_doc,
+                         double *out_score, size_t cap, uint32_t *out_df, double *out_weight);
+int fmx_corpus_rank_sets_dev(const fmx_corpus *corpus, const fmx_index *idx, const void *d_sp, const void *d_ep, size_t n_iv,
+                             const void *d_set_off, size_t n_terms, const void *d_q_off, size_t n_queries,
+                             const fmx_rank_params *params, const void *d_weights, void *d_out_off, void *d_out_doc,
+                             void *d_out_score, size_t cap, void *d_out_df, void *d_out_weight, void *stream);
 
 /* ---- regex: REParser.re2post (re2/re2.scala:50-185) + ReTree.apply (re2/retree.scala:156-370).
  * Bytes of `re` are Latin-1 characters.  FMX_ERR_SYNTAX / FMX_ERR_MATCH mirror the reference's
@@ -1155,6 +1172,73 @@ int fmx_occurrences(const fmx_index *idx, const fmx_corpus *corpus_or_null, cons
 int fmx_occurrences_dev(const fmx_index *idx, const fmx_corpus *corpus_or_null, const void *d_rec, size_t k, size_t n_groups,
                         const fmx_occ_opts *opts, void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream);
 int fmx_occurrences_last(double *locate_ms, double *sort_ms, double *select_ms, double *compact_ms, uint64_t *rows);
+
+/* ---- context: the rows of intervals whose NEIGHBOURING TEXT BYTES are in a class -- whole-word matching.  Beyond the
+ * reference.  DESIGN.md 27.
+ * s = reverse(text) + sentinel, n and SA as for locate.  A row r of the interval of a string of s of length len is the
+ * occurrence of the (reversed) string at text offset pos = n - 1 - len - SA[r].  THE BYTE BEHIND that occurrence, text[pos +
+ * len], is the BWT byte of row r; the occurrence that ends where the text ends is row eof, whose byte reads as 0 (no real
+ * symbol is 0).  THE BYTE IN FRONT is matched by a search: the rows of a.X (a in front of X in the text) are rows of X.
+ * The occurrence at text offset 0, if there is one, is the first row of X's interval, and it is there iff that row is
+ * LF^len(0).  The text is not needed and is not in HBM.
+ *
+ * fmx_context_filter: a per-record map.  INPUT: k records fmx_result {group, len, sp, ep}; mode, k bytes or NULL (all 0):
+ * bits 0..6 = lead, the bytes of the record's string that are left context (the front bytes of the text string), already
+ * matched by whoever made the record; bit 7 = FMX_CTX_START; right[4], a 256-bit set: bit c (word c / 64, bit c % 64) set <=>
+ * byte c may follow the occurrence, bit 0 <=> the text may end there.
+ * CANDIDATE ROWS of record j: without FMX_CTX_START every r in [sp, min(ep, n)); with it (lead must be 0, FMX_ERR_ARG
+ * otherwise) only r = sp, and only if sp < ep and sp == LF^len(0): the occurrence that begins at text offset 0.
+ * A candidate PASSES iff bit BWT[r] of right is set (BWT[eof] read as 0).  OUTPUT for record j: the maximal runs of passing
+ * rows inside the record as fmx_result {group, len - lead, run_sp, run_ep}, ascending; a record with len <= lead or sp >= ep
+ * yields nothing.  out_off[k + 1] is CSR over the INPUT RECORDS, out_off[k] == *n_out.  The runs are rows of the input
+ * record: fmx_locate_intervals, fmx_occurrences and the ranking work on them unchanged.  The same input gives the same bytes;
+ * no atomic decides an order.
+ * Capacity as fmx_occurrences: more than cap runs -> FMX_ERR_OVERFLOW with the EXACT total in *n_out (out and, in the host
+ * form, out_off then unspecified); nothing is written past out[cap - 1]; cap == 0 with out == NULL is the counting call.
+ * FMX_ERR_ARG, decided before the device is touched: a null handle, right, out_off or n_out; k > 2^26; a record with len >
+ * FMX_OCC_MAX_LEN or sp > ep, FMX_CTX_START with lead != 0 (host form).  The device form cannot see the records: its kernels
+ * skip a bad record and raise a flag, and the call returns FMX_ERR_ARG after the launch with nothing reported.  No record
+ * value leads outside the index or the outputs.  fmx_open_block handles: FMX_ERR_UNSUPPORTED.
+ * Both forms ALLOCATE AND SYNCHRONISE (FMX_ERR_HIP under a stream capture, decided before anything is allocated, the capture
+ * left valid), check the need against the free HBM before every allocation (FMX_ERR_NOMEM) and free every temporary on every
+ * path.  Rows are 64-bit and the call sets no limit on n; the rows are cut into chunks of 1024 and the run slots numbered in 32
+ * bits: 2^32 - 1 chunks or runs and more in ONE call are FMX_ERR_OVERFLOW (the runs with their exact total).  The chain LF^j(0)
+ * is walked by one lane group, as far as the longest FMX_CTX_START record of the call and never past j = n - 1; it is not kept.
+ * No derived table and no count of patterns changes; the launches are added to the handle's.
+ * fmx_context_filter_dev: d_rec (24-byte records), d_mode (bytes or NULL), d_out_off (u64[k + 1]), d_out (24-byte records) in
+ *                       device memory; right and n_out stay host pointers.
+ * fmx_context_last    : the calling thread's last call: device time (ms) of the search (fmx_search_context_batch only), of the
+ *                       chain, and of ranges + count + scans + emit; the rows tested and the runs found.
+ *
+ * fmx_search_context_batch: k literal patterns (given as fmx_search_batch takes them: strings of s, the text string reversed;
+ * non-empty, at most FMX_OCC_MAX_LEN - 1 bytes, no byte 0, FMX_ERR_ARG otherwise) with a class on each side.  opts->left /
+ * ->right are 256-bit sets as above, in TEXT terms: left bit a <=> byte a may stand in front of the occurrence, bit 0 <=> the
+ * text may begin there; flags and reserved must be 0.  RESULT for pattern i of m_i bytes: the rows of its interval whose left
+ * and right neighbours are in the classes, as disjoint ranges {i, m_i, sp, ep} in ascending sp (two ranges may be adjacent);
+ * out_off[k + 1] is CSR over the PATTERNS.  Capacity, errors and the device form's flag are the filter's.
+ * How: pattern i is expanded on the device into itself and a.P_i for every a >= 1 of left whose count in the index is not 0;
+ * ONE fmx_search_batch_dev over the expansion -- the derived search tables and the handle's pattern counters behave as for
+ * any search of that many patterns, k * (1 + such bytes), which must not exceed 2^26 --; per pattern the plain interval with
+ * FMX_CTX_START (only if bit 0 of left is set), then the a intervals with lead = 1 in ascending a, which is ascending sp; then
+ * the filter above. */
+#define FMX_CTX_START 0x80u
+typedef struct fmx_context_opts {
+  uint64_t left[4];
+  uint64_t right[4];
+  uint32_t flags;    /* must be 0 */
+  uint32_t reserved; /* must be 0 */
+} fmx_context_opts;  /* 72 bytes */
+int fmx_context_filter(const fmx_index *idx, const fmx_result *rec, const uint8_t *mode_or_null, size_t k, const uint64_t *right,
+                       uint64_t *out_off /* k + 1 */, fmx_result *out, size_t cap, size_t *n_out);
+int fmx_context_filter_dev(const fmx_index *idx, const void *d_rec, const void *d_mode_or_null, size_t k, const uint64_t *right,
+                           void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream);
+int fmx_context_last(double *search_ms, double *chain_ms, double *filter_ms, uint64_t *rows, uint64_t *runs);
+int fmx_search_context_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k,
+                             const fmx_context_opts *opts, uint64_t *out_off /* k + 1 */, fmx_result *out, size_t cap,
+                             size_t *n_out);
+int fmx_search_context_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k,
+                                 const fmx_context_opts *opts, void *d_out_off, void *d_out, size_t cap, size_t *n_out,
+                                 void *stream);
 
 /* ---- lines: the map from a text position to its line, and occurrences reduced to the distinct lines that hold them (grep -n
  * over an index).  Beyond the reference.  DESIGN.md 23.
