@@ -25,12 +25,14 @@ package is the thin host-side mirror of the reference's Scala interface for that
                                                    HipCorpusSearcher.frequent_phrases, python -m findex_amd.index --ngrams
                                                    HipFMSearcher.line_query (lines with A and B, A not C, A near B, grep -v),
                                                    HipCorpusSearcher.grep_lines_where / .grep_lines_inverted, grep -v / --and / --not
+                                                   HipFMSearcher.search_fold / .locate_fold (every case variant that occurs),
+                                                   ignore_case= on finditer, grep and rank, grep -i, rank -i
 
 There is no CPU fallback: importing works anywhere, but every compute call needs the built
 library and a HIP device and fails loudly otherwise.
 """
 from ._lib import FmxError, MatchError, Re2PostSyntax, LIB_PATH, load  # noqa: F401
-from .searcher import HipFMSearcher, WORD_BYTES, boundary_class, class_words  # noqa: F401
+from .searcher import ASCII_FOLD, HipFMSearcher, WORD_BYTES, boundary_class, check_fold, class_words, fold_map  # noqa: F401
 from .construct import bwt_from_text, bwt_from_text_chunked, bwt_from_text_dev, lcp_from_text, lcp_from_text_dev, write_bwt  # noqa: F401
 from .corpus import Corpus, HipCorpusSearcher, escape, is_binary, list_files  # noqa: F401
 from .regex import DFA, NFA, REParser, ReTree, SAResult, CompiledRegexes  # noqa: F401
@@ -74,4 +76,4 @@ def config_set(key, value):
     _lib.check(_lib.load().fmx_config_set(key.encode(), str(value).encode()))
 
 
-__all__ = ["WORD_BYTES", "boundary_class", "class_words", "Corpus", "HipCorpusSearcher", "escape", "is_binary", "list_files", "bwt_from_text", "bwt_from_text_dev", "lcp_from_text", "lcp_from_text_dev", "write_bwt", "config_set", "set_layout", "set_checkpoints", "set_ktab", "set_jump", "set_pipeline", "HipFMSearcher", "REParser", "ReTree", "SAResult", "NFA", "DFA", "CompiledRegexes", "FmxError", "MatchError", "Re2PostSyntax"]
+__all__ = ["ASCII_FOLD", "fold_map", "check_fold", "WORD_BYTES", "boundary_class", "class_words", "Corpus", "HipCorpusSearcher", "escape", "is_binary", "list_files", "bwt_from_text", "bwt_from_text_dev", "lcp_from_text", "lcp_from_text_dev", "write_bwt", "config_set", "set_layout", "set_checkpoints", "set_ktab", "set_jump", "set_pipeline", "HipFMSearcher", "REParser", "ReTree", "SAResult", "NFA", "DFA", "CompiledRegexes", "FmxError", "MatchError", "Re2PostSyntax"]

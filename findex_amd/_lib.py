@@ -193,6 +193,14 @@ class fmx_context_opts(ctypes.Structure):
 FMX_CTX_START = 0x80
 
 
+class fmx_fold_opts(ctypes.Structure):
+    _fields_ = [("fold", ctypes.c_uint8 * 256), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+FMX_FOLD_MAX_CLASS = 8
+FMX_FOLD_MAX_LEN = 255
+
+
 class fmx_stats_t(ctypes.Structure):
     _fields_ = [("rank_queries", ctypes.c_uint64), ("backward_steps", ctypes.c_uint64),
                 ("launches", ctypes.c_uint64), ("last_kernel_ms", ctypes.c_double),
@@ -350,6 +358,11 @@ SYMBOLS = {
     "fmx_context_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(_u64), _P(_u64)]),
     "fmx_search_context_batch": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_context_opts), _vp, _vp, _sz, _P(_sz)]),
     "fmx_search_context_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_context_opts), _vp, _vp, _sz, _P(_sz), _vp]),
+    "fmx_search_fold_batch": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_fold_opts), _vp, _vp, _sz, _P(_sz)]),
+    "fmx_search_fold_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_fold_opts), _vp, _vp, _sz, _P(_sz), _vp]),
+    "fmx_search_context_fold_batch": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_context_opts), _P(fmx_fold_opts), _vp, _vp, _sz, _P(_sz)]),
+    "fmx_search_context_fold_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_context_opts), _P(fmx_fold_opts), _vp, _vp, _sz, _P(_sz), _vp]),
+    "fmx_fold_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(_u64), _P(_u64)]),
     "fmx_lines_prepare": (_i32, [_vp, _vp, _sz]),
     "fmx_lines_info": (_i32, [_vp, _P(_u64), _vp, _P(_u32), _P(_u32), _P(_u64), _P(ctypes.c_double)]),
     "fmx_lines_batch": (_i32, [_vp, _vp, _sz, _vp, _vp, _vp]),

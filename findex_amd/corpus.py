@@ -16,7 +16,7 @@ import struct
 import numpy as np
 
 from . import _lib
-from .searcher import HipFMSearcher, _dp, _ptr
+from .searcher import ASCII_FOLD, HipFMSearcher, _dp, _ptr
 
 MAGIC = b"FMXDOCS1"
 SEPARATOR = 1
@@ -355,7 +355,7 @@ class HipCorpusSearcher:
         finally:
             more.close()
 
-    def locate_docs(self, q, max_hits=None, max_mismatches=0, words=False):
+    def locate_docs(self, q, max_hits=None, max_mismatches=0, words=False, ignore_case=False):
         """(doc, raw_off) arrays of the occurrences of the raw bytes q, sorted by (doc, raw_off): q is escaped, its reverse
         searched, the rows located (locate_text's arithmetic with the escaped length) and the positions mapped.
 
@@ -367,11 +367,20 @@ class HipCorpusSearcher:
         bytes differ otherwise, and a window whose raw bytes differ in an escaped byte may be missed.
 
         words=True (exact search only): whole-word occurrences, HipFMSearcher.locate_words on the escaped stream -- a raw
-        byte 0, 1 or 255 next to q shows the second byte of its escape pair there, which is a word byte."""
+        byte 0, 1 or 255 next to q shows the second byte of its escape pair there, which is a word byte.
+
+        ignore_case=True (exact search only): q in every ASCII case spelling that occurs (HipFMSearcher.locate_fold, or
+        locate_words(fold=ASCII_FOLD) with words=True)."""
         if words and max_mismatches:
             raise ValueError("words=True goes with max_mismatches=0")
+        if ignore_case and max_mismatches:
+            raise ValueError("ignore_case=True goes with max_mismatches=0")
         if not max_mismatches:
-            pos = (self.searcher.locate_words if words else self.searcher.locate_text)(escape(q), max_hits=max_hits)
+            if ignore_case:
+                pos = (self.searcher.locate_words(escape(q), max_hits=max_hits, fold=ASCII_FOLD) if words else
+                       self.searcher.locate_fold(escape(q), max_hits=max_hits))
+            else:
+                pos = (self.searcher.locate_words if words else self.searcher.locate_text)(escape(q), max_hits=max_hits)
             doc, _, raw = self.corpus.map(pos)
             order = np.lexsort((raw, doc))
             return doc[order], raw[order]
@@ -521,15 +530,16 @@ class HipCorpusSearcher:
         return doc, raw, self.read(doc, a, raw - a + np.uint64(len(q) + int(after)))
 
     # ---- regexes over the files (HipFMSearcher.finditer)
-    def grep(self, regexes, mode="disjoint", max_steps=0, max_per=None, text=False, lineOnly=False, words=False):
+    def grep(self, regexes, mode="disjoint", max_steps=0, max_per=None, text=False, lineOnly=False, words=False, ignore_case=False):
         """Where a batch of regexes matches inside the files: (off, occ, truncated) as HipFMSearcher.finditer gives them, with
         the corpus -- a match that does not lie inside one file is dropped before the reduction, and every occurrence carries
         doc, raw_off and raw_len (offset and length in the file on disk).  text=True: a fourth value, the matched raw bytes
         of every occurrence (read).  The regexes are matched against the escaped stream: a raw 0, 1 or 255 stands there as its
         escape pair, and an end that falls inside a pair maps to the byte the pair stands for.  words=True: whole-word
-        matches only (grep -w; HipFMSearcher.finditer(words=True)); the separator between two files is a word boundary."""
+        matches only (grep -w; HipFMSearcher.finditer(words=True)); the separator between two files is a word boundary.
+        ignore_case=True: grep -i, HipFMSearcher.finditer(ignore_case=True)."""
         off, occ, truncated = self.searcher.finditer(regexes, mode=mode, max_steps=max_steps, max_per=max_per, lineOnly=lineOnly,
-                                                     corpus=self.corpus, words=words)
+                                                     corpus=self.corpus, words=words, ignore_case=ignore_case)
         if not text:
             return off, occ, truncated
         return off, occ, truncated, self.read(occ["doc"], occ["raw_off"], occ["raw_len"]) if occ.size else []
@@ -584,14 +594,15 @@ class HipCorpusSearcher:
         return self._span_texts(start, end)[0]
 
     def grep_lines(self, regexes, mode="disjoint", max_steps=0, max_per=None, text=False, before=0, after=0, lineOnly=False,
-                   max_line=None, words=False):
+                   max_line=None, words=False, ignore_case=False):
         """grep, reduced to lines: (off, hits, truncated) -- regex i's matching lines are hits[off[i]:off[i + 1]], a
         HipFMSearcher.LINE_HIT array in (file, line) order, each with its 1-based line_no in the file, its raw_off / raw_len
         there and n_hits, the matches that begin on it.  text=True (or any context): a fourth value, the lines' raw bytes; a
         line longer than max_line (when given) is cut to that many bytes around its first match.  before / after > 0: a
         fifth value, per hit ([lines before], [lines after]), at most that many, clipped to the file."""
         self._lines_table()
-        off, occ, truncated = self.grep(regexes, mode=mode, max_steps=max_steps, max_per=max_per, lineOnly=lineOnly, words=words)
+        off, occ, truncated = self.grep(regexes, mode=mode, max_steps=max_steps, max_per=max_per, lineOnly=lineOnly, words=words,
+                                        ignore_case=ignore_case)
         loff, hits = self.searcher.occurrence_lines(off, occ, corpus=self.corpus)
         return self._lines_result(loff, hits, truncated, off, occ, hits["group"], text, before, after, max_line)
 
@@ -628,7 +639,7 @@ class HipCorpusSearcher:
         return loff, hits, truncated, lines, context
 
     def grep_lines_where(self, queries, mode="disjoint", max_steps=0, max_per=None, text=False, before=0, after=0, lineOnly=False,
-                         max_line=None, words=False):
+                         max_line=None, words=False, ignore_case=False):
         """Line queries over regexes (HipFMSearcher.line_query): queries = [(anchor_regex_or_None, [(regex,
         window, negate), ..]), ..] -> what grep_lines returns, with groups equal to query indices.  Query q's lines are the
         lines that hold its anchor regex (every line of every file when None) and satisfy all its terms: a term asks for a
@@ -644,7 +655,8 @@ class HipCorpusSearcher:
                 regexes.append(r)
         self._lines_table()
         if regexes:
-            off, occ, truncated = self.grep(regexes, mode=mode, max_steps=max_steps, max_per=max_per, lineOnly=lineOnly, words=words)
+            off, occ, truncated = self.grep(regexes, mode=mode, max_steps=max_steps, max_per=max_per, lineOnly=lineOnly, words=words,
+                                            ignore_case=ignore_case)
             loff, hits = self.searcher.occurrence_lines(off, occ, corpus=self.corpus)
         else:                                                # only anchors without terms: one empty group
             off, occ, truncated = np.zeros(2, dtype=np.uint64), np.zeros(0, dtype=self.searcher.OCCURRENCE), False
@@ -655,10 +667,11 @@ class HipCorpusSearcher:
         return self._lines_result(qoff, out, truncated, off, occ, anchors[out["group"].astype(np.int64)], text, before, after, max_line)
 
     def grep_lines_inverted(self, regexes, mode="disjoint", max_steps=0, max_per=None, text=False, before=0, after=0, lineOnly=False,
-                            max_line=None, words=False):
+                            max_line=None, words=False, ignore_case=False):
         """grep -v: per regex the lines of all files on which no match of it begins; returns what grep_lines returns."""
         return self.grep_lines_where([(None, [(r, 0, True)]) for r in regexes], mode=mode, max_steps=max_steps, max_per=max_per,
-                                     text=text, before=before, after=after, lineOnly=lineOnly, max_line=max_line, words=words)
+                                     text=text, before=before, after=after, lineOnly=lineOnly, max_line=max_line, words=words,
+                                     ignore_case=ignore_case)
 
     def _intervals(self, queries):
         esc = [escape(q)[::-1] for q in queries]
@@ -708,14 +721,16 @@ class HipCorpusSearcher:
         return int(off[1])
 
     # ---- ranked retrieval (fmx_corpus_rank)
-    def rank(self, queries, top=10, k1=1.2, b=0.75, match="any", weights=None, max_per=None, words=False):
+    def rank(self, queries, top=10, k1=1.2, b=0.75, match="any", weights=None, max_per=None, words=False, ignore_case=False):
         """fmx_corpus_rank: the `top` best files of every query by BM25.  `queries` is a list of lists of raw byte strings
         (terms; substrings, as everywhere in this index), escaped and searched here.  match="any": a file that holds at
         least one term of a query is a candidate; "all": only a file that holds every term.  weights: one float per term in
         the order given (default: the BM25 idf from the document frequencies).  -> (off, doc, score, df, weight): query i's
         files are doc[off[i]:off[i + 1]], best first (equal scores by document number), with their scores; df and weight per
         term.  Terms of any lengths share the one call.  words=True: a term counts only where it stands as a whole word
-        (HipFMSearcher.search_words on the escaped stream; a term slot is then the set of row ranges that pass, fmx_corpus_rank_sets)."""
+        (HipFMSearcher.search_words on the escaped stream; a term slot is then the set of row ranges that pass, fmx_corpus_rank_sets).
+        ignore_case=True: a term counts in every ASCII case spelling (HipFMSearcher.search_fold_batch, or search_words(fold=
+        ASCII_FOLD) with words=True): a term slot is the set of the intervals of the spellings that occur."""
         if match not in ("any", "all"):
             raise ValueError("match is 'any' or 'all'")
         queries = [[bytes(t) for t in q] for q in queries]
@@ -726,8 +741,23 @@ class HipCorpusSearcher:
             esc = [escape(t) for t in terms]
             if any(not e for e in esc):
                 raise ValueError("empty pattern")
-            set_off, runs = self.searcher.search_words(esc)
+            set_off, runs = self.searcher.search_words(esc, fold=ASCII_FOLD if ignore_case else None)
             return self.rank_sets_intervals(runs["sp"], runs["ep"], set_off, q_off, top=top, k1=k1, b=b, match=match, weights=weights,
+                                            max_per=max_per)
+        if terms and ignore_case:
+            esc = [escape(t)[::-1] for t in terms]
+            if any(not e for e in esc):
+                raise ValueError("empty pattern")
+            off = np.zeros(len(esc) + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(e) for e in esc])
+            pat = np.frombuffer(b"".join(esc), dtype=np.uint8)
+            try:                                                 # a first guess at the room spares the counting call's search
+                set_off, hits = self.searcher.search_fold_batch(pat, off, ASCII_FOLD, cap=64 * len(esc) + 1024)
+            except _lib.FmxError as e:
+                if e.code != _lib.FMX_ERR_OVERFLOW:
+                    raise
+                set_off, hits = self.searcher.search_fold_batch(pat, off, ASCII_FOLD)
+            return self.rank_sets_intervals(hits["sp"], hits["ep"], set_off, q_off, top=top, k1=k1, b=b, match=match, weights=weights,
                                             max_per=max_per)
         if terms:
             _, sp, ep = self._intervals(terms)
@@ -788,10 +818,10 @@ class HipCorpusSearcher:
         m = int(off[-1])
         return off, doc[:m], score[:m], df[:n_terms], w[:n_terms]
 
-    def rank_files(self, query_terms, top=10, k1=1.2, b=0.75, match="any", weights=None, max_per=None, words=False):
+    def rank_files(self, query_terms, top=10, k1=1.2, b=0.75, match="any", weights=None, max_per=None, words=False, ignore_case=False):
         """The `top` best files of ONE query (a list of raw byte strings): [(name, score)], best first."""
         _, doc, score, _, _ = self.rank([list(query_terms)], top=top, k1=k1, b=b, match=match, weights=weights, max_per=max_per,
-                                        words=words)
+                                        words=words, ignore_case=ignore_case)
         return [(self.corpus.names[int(d)], float(s)) for d, s in zip(doc, score)]
 
     def rank_last(self):

@@ -21,12 +21,14 @@
 #include <vector>
 
 #include "fmx_ctx_math.h"
+#include "fmx_fold.h"
 #include "fmx_order.h"
 
 namespace fmx {
 
 constexpr int kCtxThreads = 256;
 constexpr uint32_t kCtxChunk = 64 * kCtxLane;        // rows per chunk: one wave, one load per lane
+constexpr uint64_t kCtxMaxRecords = 1ull << 26;      // records of one filter call, whoever makes them
 constexpr uint32_t kCtxSlots = 64;                   // totals are added up in this many words, 128 bytes apart
 constexpr uint32_t kCtxSlotStride = 16;
 constexpr uint64_t kCtxNoRow = ~0ull;
@@ -262,6 +264,35 @@ __global__ __launch_bounds__(kCtxThreads) void k_ctx_records(const unsigned long
   }
 }
 
+// ---- fmx_search_context_fold_batch: the fold search (fmx_fold.hip) in the place of the exact one
+// lead[x] = 1 for the expansion's strings with a left byte: that byte's step is exact whatever the map says
+__global__ __launch_bounds__(kCtxThreads) void k_ctx_leads(uint64_t total, uint64_t per, uint8_t *__restrict__ lead) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += stride) lead[x] = x % per ? 1u : 0u;
+}
+
+// the fold search's records -> the filter's: the lead bit out of len into the mode; a plain record is an occurrence at the
+// text's beginning or nothing
+__global__ __launch_bounds__(kCtxThreads) void k_ctx_fold_modes(fmx_result *__restrict__ rec, uint64_t rows, int start,
+                                                                uint8_t *__restrict__ mode) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < rows; j += stride) {
+    const uint32_t tag = rec[j].len;
+    const bool lead = (tag & kFoldLeadBit) != 0;
+    rec[j].len = tag & ~kFoldLeadBit;
+    if (!lead && !start) rec[j].sp = rec[j].ep = 0;
+    mode[j] = lead ? 1u : (start ? (uint8_t)FMX_CTX_START : 0u);
+  }
+}
+
+// out_off[i] = the runs before the first record of pattern i
+__global__ __launch_bounds__(kCtxThreads) void k_ctx_recut(const unsigned long long *__restrict__ rec_off,
+                                                           const unsigned long long *__restrict__ run_off, uint64_t k,
+                                                           unsigned long long *__restrict__ out_off) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= k; i += stride) out_off[i] = run_off[rec_off[i]];
+}
+
 namespace {
 
 struct CtxLast {
@@ -402,7 +433,7 @@ int ctx_run(const Index *h, const fmx_result *d_rec, const uint8_t *d_mode, uint
 int ctx_filter_args(const void *rec, size_t k, const uint64_t *right, const void *out_off, const void *out, size_t cap,
                     const size_t *n_out) {
   if (!right || !out_off || !n_out) return arg_fail("context filter: right, out_off or n_out is null");
-  if ((uint64_t)k > (1ull << 26)) return arg_fail("context filter: at most 2^26 records per call");
+  if ((uint64_t)k > kCtxMaxRecords) return arg_fail("context filter: at most 2^26 records per call");
   if (k && !rec) return arg_fail("context filter: the records are null");
   if (cap && !out) return arg_fail("context filter: out is null");
   return FMX_OK;
@@ -415,10 +446,11 @@ int ctx_opts_check(const fmx_context_opts *o) {
 }
 
 // The search with context on `st`; everything in device memory, the patterns already checked as far as the caller can.
-// pat_bytes = d_off[k] - d_off[0].
+// pat_bytes = d_off[k] - d_off[0].  fold_map (256 bytes, or null: the exact search): the search under that map instead, with
+// fold_len the longest expanded pattern (the left byte included), FMX_FOLD_MAX_LEN where the lengths are not known.
 int ctx_search(const Index *h, const fmx_index *idx, const uint8_t *d_pat, const unsigned long long *d_off, uint64_t k,
-               uint64_t pat_bytes, const fmx_context_opts &o, unsigned long long *d_out_off, fmx_result *d_out, uint64_t cap,
-               hipStream_t st, uint64_t *total) {
+               uint64_t pat_bytes, const fmx_context_opts &o, const uint8_t *fold_map, uint32_t fold_len, unsigned long long *d_out_off,
+               fmx_result *d_out, uint64_t cap, hipStream_t st, uint64_t *total) {
   uint8_t lefts[256];
   uint64_t n_left = 0;
   for (uint32_t c = 1; c < 256; c++)
@@ -437,10 +469,12 @@ int ctx_search(const Index *h, const fmx_index *idx, const uint8_t *d_pat, const
   DEV_ALLOC(mem, xpat, xbytes, "search_context");
   DEV_ALLOC(mem, d_lefts, 256, "search_context");
   DEV_ALLOC(mem, xoff, 8 * (xk + 1), "search_context");
-  DEV_ALLOC(mem, sp, 8 * xk, "search_context");
-  DEV_ALLOC(mem, ep, 8 * xk, "search_context");
-  DEV_ALLOC(mem, rec, sizeof(fmx_result) * xk, "search_context");
-  DEV_ALLOC(mem, mode, xk, "search_context");
+  if (!fold_map) {
+    DEV_ALLOC(mem, sp, 8 * xk, "search_context");
+    DEV_ALLOC(mem, ep, 8 * xk, "search_context");
+    DEV_ALLOC(mem, rec, sizeof(fmx_result) * xk, "search_context");
+    DEV_ALLOC(mem, mode, xk, "search_context");
+  }
   DEV_ALLOC(mem, flag, 16, "search_context");
   HIP_TRY(hipMemsetAsync(flag, 0, 16, st), "hipMemsetAsync");
   HIP_TRY(hipMemcpyAsync(d_lefts, lefts, 256, hipMemcpyHostToDevice, st), "H2D(left bytes)");
@@ -456,6 +490,46 @@ int ctx_search(const Index *h, const fmx_index *idx, const uint8_t *d_pat, const
   if (flag_h)
     return arg_fail("search_context: an empty pattern, a pattern above 65534 bytes, a byte 0 in a pattern, or offsets that do not ascend");
   HIP_TRY(ev.record(0, st), "hipEventRecord");
+  if (fold_map) {
+    // the records are the fold search's hits: their number is known after it -- a second search when the first guess was short
+    uint8_t *lead = nullptr;
+    unsigned long long *rec_off = nullptr, *run_off = nullptr;
+    DEV_ALLOC(mem, rec_off, 8 * (k + 1), "search_context");
+    if (per > 1) {
+      DEV_ALLOC(mem, lead, xk, "search_context");
+      LAUNCH("k_ctx_leads", k_ctx_leads, dim3(flat_grid(xk)), dim3(kCtxThreads), st, xk, per, lead);
+    }
+    FoldInfo info;
+    uint64_t rcap = std::min<uint64_t>(2 * xk + 1024, kCtxMaxRecords);
+    uint64_t own_launches = 1 + (per > 1 ? 1 : 0);          // k_ctx_recut, k_ctx_leads; the fold search and the filter count their own
+    for (int pass = 0;; pass++) {
+      if ((rc = device_room(33 * rcap + 4096, "fmx_search_context_fold_batch"))) return rc;
+      DEV_ALLOC(mem, rec, sizeof(fmx_result) * rcap, "search_context");
+      if ((rc = fold_search(h, xpat, xoff, xk, fold_map, lead, per, fold_len, rec_off, rec, rcap, true, st, &info))) return rc;
+      fold_set_last(info);
+      if (info.total <= rcap) break;
+      if (pass || info.total > kCtxMaxRecords) {             // the variants are the filter's records: its limit holds for them
+        set_error("search_context_fold: " + std::to_string(info.total) + " variants occur, at most 2^26 records reach the filter in one call");
+        return FMX_ERR_ARG;
+      }
+      rcap = info.total;
+    }
+    const uint64_t n_rec = info.total;
+    DEV_ALLOC(mem, mode, n_rec, "search_context");
+    DEV_ALLOC(mem, run_off, 8 * (n_rec + 1), "search_context");
+    if (n_rec) {
+      LAUNCH("k_ctx_fold_modes", k_ctx_fold_modes, dim3(flat_grid(n_rec)), dim3(kCtxThreads), st, rec, n_rec, (int)(o.left[0] & 1), mode);
+      own_launches++;
+    }
+    rc = ctx_run(h, rec, mode, n_rec, 1, o.right, run_off, d_out, cap, st, total);
+    g_ctx_last.ms[0] = info.search_ms + info.sort_ms;
+    if (rc) return rc;
+    LAUNCH("k_ctx_recut", k_ctx_recut, dim3(flat_grid(k + 1)), dim3(kCtxThreads), st, rec_off, run_off, k, d_out_off);
+    HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");        // the temporaries go when this returns
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->launches += own_launches;
+    return FMX_OK;
+  }
   if (xk && (rc = fmx_search_batch_dev(idx, xpat, xoff, sp, ep, xk, st))) return rc;
   HIP_TRY(ev.record(1, st), "hipEventRecord");
   if (xk) {
@@ -539,14 +613,16 @@ int fmx_context_last(double *search_ms, double *chain_ms, double *filter_ms, uin
   return FMX_OK;
 }
 
-int fmx_search_context_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k, const fmx_context_opts *opts,
-                                 void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream) {
+// both device forms; fold_map: null (the exact search) or the 256 bytes of a checked map
+static int ctx_search_dev_form(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k, const fmx_context_opts *opts,
+                               const uint8_t *fold_map, void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream) {
   int rc = ctx_opts_check(opts);
   if (rc) return rc;
   if (!d_out_off || !n_out || !d_off || (cap && !d_out)) return arg_fail("search_context: null argument");
   if ((uint64_t)k > (1ull << 26)) return arg_fail("search_context: at most 2^26 patterns per call");
   if ((rc = ctx_handle(idx, "fmx_search_context_batch_dev"))) return rc;
   const Index *h = H(idx);
+  if (fold_map && (rc = fold_handle_check(h))) return rc;
   if ((rc = use_device(h))) return rc;
   hipStream_t st = (hipStream_t)stream;
   if ((rc = not_capturing(st, "fmx_search_context_batch_dev"))) return rc;
@@ -558,7 +634,8 @@ int fmx_search_context_batch_dev(const fmx_index *idx, const void *d_pat, const 
   if (ends[1] > ends[0] && !d_pat) return arg_fail("search_context: the patterns are null");
   g_ctx_last = CtxLast{};
   uint64_t total = 0;
-  if ((rc = ctx_search(h, idx, static_cast<const uint8_t *>(d_pat), static_cast<const unsigned long long *>(d_off), k, ends[1] - ends[0], *opts,
+  if ((rc = ctx_search(h, idx, static_cast<const uint8_t *>(d_pat), static_cast<const unsigned long long *>(d_off), k, ends[1] - ends[0], *opts, fold_map,
+                       FMX_FOLD_MAX_LEN,
                        static_cast<unsigned long long *>(d_out_off), static_cast<fmx_result *>(d_out), cap, st, &total))) {
     if (rc == FMX_ERR_OVERFLOW && total) *n_out = (size_t)total;
     return rc;
@@ -567,15 +644,19 @@ int fmx_search_context_batch_dev(const fmx_index *idx, const void *d_pat, const 
   return total > cap ? csr_overflow("search_context", total, cap) : FMX_OK;
 }
 
-int fmx_search_context_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k, const fmx_context_opts *opts,
-                             uint64_t *out_off, fmx_result *out, size_t cap, size_t *n_out) {
+// both host forms
+static int ctx_search_host_form(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k, const fmx_context_opts *opts,
+                                const uint8_t *fold_map, uint64_t *out_off, fmx_result *out, size_t cap, size_t *n_out) {
   int rc = ctx_opts_check(opts);
   if (rc) return rc;
   if (!out_off || !n_out || !off || (cap && !out)) return arg_fail("search_context: null argument");
   if ((uint64_t)k > (1ull << 26)) return arg_fail("search_context: at most 2^26 patterns per call");
+  uint64_t longest = 0;
   for (size_t i = 0; i < k; i++) {
     if (off[i + 1] <= off[i]) return arg_fail("search_context: an empty pattern, or offsets that do not ascend");
+    longest = std::max<uint64_t>(longest, off[i + 1] - off[i]);
     if (off[i + 1] - off[i] > FMX_OCC_MAX_LEN - 1) return arg_fail("search_context: a pattern above 65534 bytes");
+    if (fold_map && off[i + 1] - off[i] > FMX_FOLD_MAX_LEN - 1) return arg_fail("search_context_fold: a pattern above 254 bytes");
   }
   const uint64_t bytes = k ? off[k] - off[0] : 0;
   if (bytes && !pat) return arg_fail("search_context: the patterns are null");
@@ -583,6 +664,7 @@ int fmx_search_context_batch(const fmx_index *idx, const uint8_t *pat, const uin
     if (pat[off[0] + t] == 0) return arg_fail("search_context: a byte 0 in a pattern");
   if ((rc = ctx_handle(idx, "fmx_search_context_batch"))) return rc;
   const Index *h = H(idx);
+  if (fold_map && (rc = fold_handle_check(h))) return rc;
   if ((rc = use_device(h))) return rc;
   HostCall hc;
   if ((rc = hc.open())) return rc;
@@ -602,7 +684,8 @@ int fmx_search_context_batch(const fmx_index *idx, const uint8_t *pat, const uin
     *n_out = 0;
     return FMX_OK;
   }
-  if ((rc = ctx_search(h, idx, static_cast<const uint8_t *>(d_pat), reinterpret_cast<const unsigned long long *>(d_off), kk, bytes, *opts,
+  if ((rc = ctx_search(h, idx, static_cast<const uint8_t *>(d_pat), reinterpret_cast<const unsigned long long *>(d_off), kk, bytes, *opts, fold_map,
+                       (uint32_t)std::min<uint64_t>(longest + 1, FMX_FOLD_MAX_LEN),
                        d_out_off, d_out, cap, hc.own.s, &total))) {
     if (rc == FMX_ERR_OVERFLOW && total) *n_out = (size_t)total;
     return rc;
@@ -610,6 +693,34 @@ int fmx_search_context_batch(const fmx_index *idx, const uint8_t *pat, const uin
   *n_out = (size_t)total;
   if (total > cap) return csr_overflow("search_context", total, cap);
   return hc.download_csr(out_off, d_out_off, k, out, d_out, total, sizeof(fmx_result));
+}
+
+int fmx_search_context_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k, const fmx_context_opts *opts,
+                                 void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream) {
+  return ctx_search_dev_form(idx, d_pat, d_off, k, opts, nullptr, d_out_off, d_out, cap, n_out, stream);
+}
+
+int fmx_search_context_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k, const fmx_context_opts *opts,
+                             uint64_t *out_off, fmx_result *out, size_t cap, size_t *n_out) {
+  return ctx_search_host_form(idx, pat, off, k, opts, nullptr, out_off, out, cap, n_out);
+}
+
+int fmx_search_context_fold_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k,
+                                      const fmx_context_opts *ctx, const fmx_fold_opts *fold, void *d_out_off, void *d_out,
+                                      size_t cap, size_t *n_out, void *stream) {
+  uint8_t map[256];
+  int rc = fold_map_check(fold, map);
+  if (rc) return rc;
+  return ctx_search_dev_form(idx, d_pat, d_off, k, ctx, map, d_out_off, d_out, cap, n_out, stream);
+}
+
+int fmx_search_context_fold_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k,
+                                  const fmx_context_opts *ctx, const fmx_fold_opts *fold, uint64_t *out_off, fmx_result *out,
+                                  size_t cap, size_t *n_out) {
+  uint8_t map[256];
+  int rc = fold_map_check(fold, map);
+  if (rc) return rc;
+  return ctx_search_host_form(idx, pat, off, k, ctx, map, out_off, out, cap, n_out);
 }
 
 }  // extern "C"

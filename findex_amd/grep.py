@@ -2,14 +2,17 @@
 
     python -m findex_amd.grep BASE REGEX [REGEX ..] [--mode all|longest|disjoint] [--max-per N] [--max-steps N] [-C BYTES] [--count]
                                                     [-n] [-A N] [-B N] [--context-lines N] [-c] [-l] [--max-line BYTES]
-                                                    [-v] [--and REGEX ..] [--not REGEX ..] [--near N | --same-file] [-w]
+                                                    [-v] [--and REGEX ..] [--not REGEX ..] [--near N | --same-file] [-w] [-i]
 
 BASE names BASE.bwt / BASE.aux / BASE.docs as `python -m findex_amd.index --dir D --out BASE` writes them.  One line per
 match, `name:raw_off:text`, regex by regex in (file, offset) order; -C BYTES shows that many bytes of the file around the
 match, cut at newlines; --count prints one count per regex instead.  The regexes are the reference's (REParser.re2post) and are
 matched against the escaped stream (HipCorpusSearcher.grep).  -w keeps only matches that stand as whole words: the bytes next
 to a match are not 0-9 A-Z a-z _ or 0x80 .. 0xFF, or the file ends there; it applies to every regex of the call, --and / --not
-included.
+included.  -i ignores ASCII case: every regex of the call, --and / --not included, is read as Python's re reads it under
+re.IGNORECASE | re.ASCII (findex_amd.regex.fold_regex; a construct re reads differently, such as an unquoted ^ or {, is
+refused) -- but for \\w, \\d and '.', which keep the meaning they have without -i: the bytes A .. y (and z beside them, the
+image of Z), 0 .. 8 and 2 .. 254, not re's classes; it combines with -w.
 
 By lines (HipCorpusSearcher.grep_lines; any of the flags below): -n prints `name:line_no:line`, one line of output per matching
 line, regex by regex in (file, line) order; -A N / -B N / --context-lines N add that many lines after / before / around, as
@@ -59,9 +62,18 @@ def parser():
     near.add_argument("--near", type=line_count, default=None, metavar="N", help="--and / --not look N lines to either side (default 0: the same line)")
     near.add_argument("--same-file", action="store_true", help="--and / --not look at the whole file")
     ap.add_argument("-w", "--word-regexp", dest="words", action="store_true", help="only matches that stand as whole words")
+    ap.add_argument("-i", "--ignore-case", action="store_true", help="ignore ASCII case in every regex of the call")
     ap.add_argument("--little-endian", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     return ap
+
+
+def flags_of(a):
+    """The keyword arguments -w and -i add to a grep call; none when neither is given."""
+    kw = {"words": True} if getattr(a, "words", False) else {}
+    if getattr(a, "ignore_case", False):
+        kw["ignore_case"] = True
+    return kw
 
 
 def with_context(cs, occ, context):
@@ -144,7 +156,7 @@ def format_files(names, hits):
 def main_lines(cs, a, out):
     before, after = context_of(a)
     names = cs.corpus.names
-    w = {"words": True} if getattr(a, "words", False) else {}
+    w = flags_of(a)
     if where(a):
         queries = queries_of(a)
         grep_lines = lambda _regexes, **kw: cs.grep_lines_where(queries, **w, **kw)
@@ -183,7 +195,7 @@ def main(argv=None):
             if truncated:
                 print("matches longer than --max-steps were cut", file=sys.stderr)
             return 0
-        off, occ, truncated = cs.grep(a.regex, mode=a.mode, max_steps=a.max_steps, max_per=a.max_per, **({"words": True} if a.words else {}))
+        off, occ, truncated = cs.grep(a.regex, mode=a.mode, max_steps=a.max_steps, max_per=a.max_per, **flags_of(a))
         out = sys.stdout.buffer
         if a.count:
             for i in range(len(a.regex)):

@@ -1,6 +1,6 @@
 """Ranked retrieval over a corpus index: which files are the best matches for these words?
 
-    python -m findex_amd.rank BASE "words of a query" ["another query" ..] [--top K] [--all] [-w] [--k1 X] [--b X] [--device D]
+    python -m findex_amd.rank BASE "words of a query" ["another query" ..] [--top K] [--all] [-w] [-i] [--k1 X] [--b X] [--device D]
                                                                             [--little-endian]
 
 BASE names BASE.bwt / BASE.aux / BASE.docs as `python -m findex_amd.index --dir D --out BASE` writes them.  Every positional
@@ -9,7 +9,8 @@ argument is one query, split on white space into its terms.  Without -w terms ar
 not 0-9 A-Z a-z _ or 0x80 .. 0xFF, or the file ends there (HipFMSearcher.search_words).  A file is scored by BM25 over its terms' occurrence counts
 (HipCorpusSearcher.rank, fmx_corpus_rank: scored and cut to the best K on the device).  Output: one line per hit,
 `score<TAB>file`, best first; the queries' blocks are separated by a blank line.  --all keeps only files that hold every term of
-the query.
+the query.  -i / --ignore-case counts a term in every ASCII case spelling that occurs (HipFMSearcher.search_fold_batch: `error` finds
+Error and ERROR too); it combines with -w.
 """
 import argparse
 import sys
@@ -23,6 +24,7 @@ def parser():
     ap.add_argument("--top", type=int, default=10, metavar="K", help="files per query, 1 .. 1024 (default 10)")
     ap.add_argument("--all", dest="all_", action="store_true", help="only files that hold every term of the query")
     ap.add_argument("-w", "--words", action="store_true", help="a term counts only where it stands as a whole word")
+    ap.add_argument("-i", "--ignore-case", action="store_true", help="a term counts in every ASCII case spelling")
     ap.add_argument("--k1", type=float, default=1.2)
     ap.add_argument("--b", type=float, default=0.75)
     ap.add_argument("--device", type=int, default=0)
@@ -55,7 +57,10 @@ def main(argv=None):
     from .corpus import HipCorpusSearcher
     cs = HipCorpusSearcher.open(a.base, bigEndian=not a.little_endian, device=a.device)
     try:
-        off, doc, score, _, _ = cs.rank(queries, top=a.top, k1=a.k1, b=a.b, match="all" if a.all_ else "any", **({"words": True} if a.words else {}))
+        kw = {"words": True} if a.words else {}
+        if a.ignore_case:
+            kw["ignore_case"] = True
+        off, doc, score, _, _ = cs.rank(queries, top=a.top, k1=a.k1, b=a.b, match="all" if a.all_ else "any", **kw)
         out = sys.stdout.buffer
         for row in render(cs.corpus.names, off, doc, score):
             out.write(row + b"\n")

@@ -8,6 +8,116 @@ import numpy as np
 from . import _lib
 
 
+def _alternation(members):
+    """`members` (byte values) as a parenthesised alternation, ascending: what stands for a set in a regex that
+    REParser.createNFA compiles, which has no case for AltPoint, re2post's [..].  A letter or digit stands as it is (a quoted w
+    or d would be a class), every other byte backslash-quoted."""
+    return "(" + "|".join(chr(v) if chr(v).isascii() and chr(v).isalnum() else "\\" + chr(v) for v in sorted(members)) + ")"
+
+
+def fold_regex(re, fold):
+    """The regex `re` (a string of Latin-1 characters in re2post's syntax, fmx_regex.cpp) rewritten so that it matches under
+    the fold map `fold` (256 bytes, e.g. findex_amd.ASCII_FOLD) what `re` matches exactly: an unquoted letter, and a quoted
+    byte other than w or d, outside a set becomes the set of its class; inside [..] every member -- the bytes of every
+    interval included -- gets the other members of its class; \\w, \\d and '.' stay as they are where they hold whole
+    classes, and else get the missing members beside them: under ASCII folding \\w, which is A .. y here, becomes (\\w|z).  Every set, the ones `re` holds included, is written as a parenthesised alternation of its members,
+    (a|A): the result is for REParser.createNFA, which has no case for [..].  A pure function of its arguments.  With ASCII_FOLD the result is read as Python's re reads `re`
+    under re.IGNORECASE | re.ASCII -- but for \\w, \\d and '.', which keep re2post's meaning, the half-open intervals A .. y, 0 .. 8
+    and 2 .. 254 (closed under the map as said above), not re's classes; what re reads differently from re2post is refused with ValueError and not mis-matched:
+    an unquoted ^ $ { }, a set that begins with ^ or is empty, and a quoted letter or digit (re gives \\n, \\b, \\1 .. a meaning;
+    re2post takes them literally) other than \\w and \\d outside a set.  Syntax errors are left for the compiler to report."""
+    fold = bytes(fold)
+    if len(fold) != 256:
+        raise ValueError("a fold map has 256 bytes")
+    cls = {}
+    for c in range(256):
+        cls.setdefault(fold[c], []).append(c)
+    if isinstance(re, (bytes, bytearray)):
+        re = bytes(re).decode("latin-1")
+
+    def refuse(what):
+        raise ValueError("ignore_case: %s in %r is read differently by Python's re -- quote it or rewrite it" % (what, re))
+
+    def atom(c):
+        members = cls[fold[c]]
+        return _alternation(members) if len(members) > 1 else None
+
+    def interval(token, start, end):
+        # re2post's classes are intervals [start, end) (IntervalPoint, "start until end"): \\w is A .. y, \\d 0 .. 8, '.' 2 .. 254
+        extra = {m for c in range(start, end) for m in cls[fold[c]] if not start <= m < end}
+        return "(" + token + "|" + _alternation(extra)[1:] if extra else token
+
+    out, i, n = [], 0, len(re)
+    while i < n:
+        ch = re[i]
+        c = ord(ch)
+        if c > 255:
+            raise ValueError("a regex holds Latin-1 characters only")
+        if ch == "\\":
+            if i + 1 >= n:
+                out.append(ch)
+                break
+            q = re[i + 1]
+            if q in "wd":
+                out.append(interval(ch + q, *((65, 122) if q == "w" else (48, 57))))
+            else:
+                if q.isascii() and q.isalnum():
+                    refuse("\\" + q)
+                out.append(atom(ord(q)) or ch + q)
+            i += 2
+        elif ch == "[":
+            members, last, in_interval, quoted, j = set(), None, False, False, i + 1
+            if j < n and re[j] == "^":
+                refuse("a set that begins with ^")
+            ok = True
+            while j < n:
+                m = re[j]
+                if not quoted and m == "\\":
+                    quoted = True
+                elif not quoted and m == "-":
+                    in_interval = True
+                elif not quoted and m == "]":
+                    break
+                else:
+                    if quoted and m.isascii() and m.isalnum():
+                        refuse("\\" + m + " inside a set")
+                    quoted = False
+                    if ord(m) > 255:
+                        raise ValueError("a regex holds Latin-1 characters only")
+                    if in_interval:
+                        if last is None or last + 1 > ord(m):
+                            ok = False
+                            break
+                        members.update(range(last + 1, ord(m) + 1))
+                        in_interval = False
+                    else:
+                        members.add(ord(m))
+                    last = ord(m)
+                j += 1
+            if not ok or j >= n or in_interval or quoted:      # re2post's syntax error: as it stands, for the compiler to report
+                out.append(re[i:])
+                break
+            if not members:
+                refuse("an empty set")
+            closed = set()
+            for m in members:
+                closed.update(cls[fold[m]])
+            out.append(_alternation(closed))
+            i = j + 1
+        elif ch == ".":
+            out.append(interval(ch, 2, 255))
+            i += 1
+        elif ch in "()|*+?":
+            out.append(ch)
+            i += 1
+        else:
+            if ch in "^${}":
+                refuse("an unquoted " + ch)
+            out.append(atom(c) or ch)
+            i += 1
+    return "".join(out)
+
+
 class PostfixRe:
     """REParser.PostfixRe (re2.scala:49): the postfix token list, kept as the source string the
     library re-parses; str() gives re2poststr."""

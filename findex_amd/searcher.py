@@ -28,6 +28,55 @@ def boundary_class(word=WORD_BYTES):
     return bytes(c for c in range(256) if c not in word)
 
 
+# ASCII case folding as a fold map (fmx_fold_opts.fold): A..Z fold to a..z, every other byte to itself -- what the
+# library uses when it is given no map
+ASCII_FOLD = bytes(c + 32 if 65 <= c <= 90 else c for c in range(256))
+
+
+def check_fold(fold):
+    """The 256 bytes of a valid fold map, or ValueError: fold[fold[c]] == fold[c], byte 0 alone in its class, at most 8 members
+    per class (the library's own checks, made here for the callers that never reach it)."""
+    fold = bytes(fold)
+    if len(fold) != 256:
+        raise ValueError("a fold map has 256 bytes")
+    size = [0] * 256
+    for c in range(256):
+        r = fold[c]
+        if fold[r] != r:
+            raise ValueError("fold map: fold[fold[%d]] != fold[%d]" % (c, c))
+        if (r == 0) != (c == 0):
+            raise ValueError("fold map: byte 0 folds to itself and no other byte folds to 0")
+        size[r] += 1
+        if size[r] > _lib.FMX_FOLD_MAX_CLASS:
+            raise ValueError("fold map: a class of more than %d members" % _lib.FMX_FOLD_MAX_CLASS)
+    return fold
+
+
+def fold_map(pairs):
+    """A fold map from equivalences: every item of `pairs` is a bytes object or a sequence of byte values (ints or one-byte
+    strings) that are all to be equal; classes that share a member merge.  The representative of a class is its smallest
+    member.  fold_map([b"aA", b"bB"]), fold_map([(0x61, 0x41)]).  ValueError for byte 0 or a class of more than 8."""
+    parent = list(range(256))
+
+    def find(c):
+        while parent[c] != c:
+            parent[c] = parent[parent[c]]
+            c = parent[c]
+        return c
+
+    for item in pairs:
+        members = [m if isinstance(m, int) else bytes(m)[0] if len(bytes(m)) == 1 else -1 for m in (item if not isinstance(item, (bytes, bytearray)) else bytes(item))]
+        if any(not 0 <= m < 256 for m in members):
+            raise ValueError("fold_map: members are byte values or one-byte strings")
+        if len(members) > 1 and 0 in members:
+            raise ValueError("fold_map: byte 0 is equal to nothing else")
+        for m in members[1:]:
+            a, b = find(members[0]), find(m)
+            if a != b:
+                parent[max(a, b)] = min(a, b)
+    return check_fold(bytes(find(c) for c in range(256)))
+
+
 def _swap_ext(filename, ext):
     """BWTTempStorage.gen*Filename, bwtmerger.scala:17-48"""
     return os.path.splitext(filename)[0] + ext
@@ -39,6 +88,13 @@ def _ptr(a):
 
 def _dp(x):
     return ctypes.c_void_p(int(x) if x else 0)
+
+
+class _NfaSource:
+    """What regex.NFA() reads of a PostfixRe: the regex as text and lineOnly, without the postfix string."""
+
+    def __init__(self, src, lineOnly):
+        self.src, self.lineOnly = src, bool(lineOnly)
 
 
 class PinnedArray:
@@ -610,11 +666,12 @@ class HipFMSearcher:
     # ---- context: rows whose neighbouring text bytes are in a class -- whole words (fmx_context_filter)
     CTX_START = _lib.FMX_CTX_START
 
-    def search_context_batch(self, pat, off, left, right, cap=None):
+    def search_context_batch(self, pat, off, left, right, cap=None, fold=None):
         """fmx_search_context_batch: the patterns as search_batch takes them (strings of reverse(text)), left / right = the byte
         values (bytes; 0 = the text begins / ends there) that may stand in front of / behind an occurrence in the TEXT.
         -> (off[k + 1], runs): pattern i's rows are the disjoint ranges runs[off[i]:off[i + 1]], a RESULT array {i, length,
-        sp, ep} in ascending sp.  cap=None: a counting call sizes the buffer."""
+        sp, ep} in ascending sp.  cap=None: a counting call sizes the buffer.  fold (a fold map, e.g. ASCII_FOLD):
+        fmx_search_context_fold_batch -- every variant of a pattern under the map, the neighbours still compared as they are."""
         pat = np.ascontiguousarray(pat, dtype=np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
         k = off.size - 1
@@ -623,6 +680,10 @@ class HipFMSearcher:
         opts = _lib.fmx_context_opts()
         for j, (lw, rw) in enumerate(zip(class_words(left), class_words(right))):
             opts.left[j], opts.right[j] = int(lw), int(rw)
+        if fold is not None:
+            fopts = self._fold_opts(fold)
+            args = (self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts), ctypes.byref(fopts))
+            return self._csr_hits(self._L.fmx_search_context_fold_batch, args, k, self.RESULT, cap)
         args = (self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts))
         return self._csr_hits(self._L.fmx_search_context_batch, args, k, self.RESULT, cap)
 
@@ -658,23 +719,81 @@ class HipFMSearcher:
         _lib.check(self._L.fmx_context_last(*[ctypes.byref(x) for x in t], ctypes.byref(rows), ctypes.byref(runs)))
         return tuple(float(x.value) for x in t) + (int(rows.value), int(runs.value))
 
-    def search_words(self, pats, word=WORD_BYTES, cap=None):
+    def search_words(self, pats, word=WORD_BYTES, cap=None, fold=None):
         """The whole-word occurrences of text strings `pats` (bytes each): search_context_batch over their reverses with the
-        boundary class of `word` on both sides.  -> (off[k + 1], runs)."""
+        boundary class of `word` on both sides.  -> (off[k + 1], runs).  fold: a fold map the strings are matched under."""
         pats = [bytes(q) for q in pats]
         off = np.zeros(len(pats) + 1, dtype=np.uint64)
         np.cumsum([len(q) for q in pats], out=off[1:])
         pat = np.frombuffer(b"".join(q[::-1] for q in pats), dtype=np.uint8)
         cls = boundary_class(word)
-        return self.search_context_batch(pat, off, cls, cls, cap)
+        return self.search_context_batch(pat, off, cls, cls, cap, fold=fold)
 
-    def locate_words(self, q, max_hits=None, word=WORD_BYTES):
-        """Sorted text offsets of the whole-word occurrences of q -- of at most max_hits rows."""
+    def locate_words(self, q, max_hits=None, word=WORD_BYTES, fold=None):
+        """Sorted text offsets of the whole-word occurrences of q -- of at most max_hits rows.  fold: a fold map q is matched
+        under."""
         q = bytes(q)
         if not q:
             raise ValueError("empty pattern")
-        _, runs = self.search_words([q], word)
+        _, runs = self.search_words([q], word, fold=fold)
         sp, ep = runs["sp"].copy(), runs["ep"].copy()
+        if max_hits is not None:
+            left = int(max_hits)
+            for j in range(sp.size):
+                ep[j] = min(int(ep[j]), int(sp[j]) + left)
+                left -= int(ep[j]) - int(sp[j])
+        _, pos = self.locate_intervals(sp, ep)
+        return np.sort(self.text_offsets(pos, self.n, len(q)))
+
+    # ---- case folding: literal search under a byte map (fmx_search_fold_batch, DESIGN.md 28)
+    @staticmethod
+    def _fold_opts(fold):
+        opts = _lib.fmx_fold_opts()
+        ctypes.memmove(opts.fold, check_fold(fold), 256)
+        return opts
+
+    def search_fold_batch(self, pat, off, fold=ASCII_FOLD, cap=None):
+        """fmx_search_fold_batch: every string that equals a pattern under the fold map (256 bytes: a byte -> the representative
+        of its class) and occurs.  The patterns are given as search_batch takes them.  -> (off[k + 1], hits): pattern q's
+        hits are hits[off[q]:off[q + 1]], a RESULT array {q, length, sp, ep} by ascending sp -- disjoint row intervals.
+        cap=None: a counting call sizes the buffer; with a cap that is too small the library's FMX_ERR_OVERFLOW is raised."""
+        pat = np.ascontiguousarray(pat, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        k = max(off.size - 1, 0)
+        opts = self._fold_opts(fold)
+        return self._csr_hits(self._L.fmx_search_fold_batch, (self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts)), k, self.RESULT, cap)
+
+    def search_fold(self, q, fold=ASCII_FOLD):
+        """One pattern (as search takes it): the list of (sp, ep) of its variants under the map, by ascending sp."""
+        q = bytes(q)
+        _, hits = self.search_fold_batch(np.frombuffer(q, dtype=np.uint8), np.array([0, len(q)], dtype=np.uint64), fold)
+        return [(int(h["sp"]), int(h["ep"])) for h in hits]
+
+    def search_fold_batch_dev(self, d_pat, d_off, k, d_out_off, d_out, cap, fold=ASCII_FOLD, stream=0):
+        """fmx_search_fold_batch_dev: device pointers (u8 patterns, u64 offsets[k + 1], u64 out_off[k + 1], 24-byte records);
+        allocates and synchronises.  -> the exact number of hits (FMX_ERR_OVERFLOW is raised when it exceeds cap)."""
+        opts = self._fold_opts(fold)
+        n_out = ctypes.c_size_t()
+        _lib.check(self._L.fmx_search_fold_batch_dev(self._h, _dp(d_pat), _dp(d_off), int(k), ctypes.byref(opts), _dp(d_out_off),
+                                                     _dp(d_out), int(cap), ctypes.byref(n_out), _dp(stream)))
+        return int(n_out.value)
+
+    def fold_last(self):
+        """fmx_fold_last: (search kernel ms, ordering ms, backward steps, rank-dictionary requests) of this thread's last
+        fold search."""
+        a, b, c, d = ctypes.c_double(), ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64()
+        _lib.check(self._L.fmx_fold_last(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
+        return float(a.value), float(b.value), int(c.value), int(d.value)
+
+    def locate_fold(self, q, max_hits=None, fold=ASCII_FOLD):
+        """Sorted text offsets of the occurrences of the text string q under the map (overlapping ones included) -- of at most
+        max_hits rows, taken in row order."""
+        q = bytes(q)
+        if not q:
+            raise ValueError("empty pattern")
+        hits = self.search_fold(q[::-1], fold)
+        sp = np.array([h[0] for h in hits], dtype=np.uint64)
+        ep = np.array([h[1] for h in hits], dtype=np.uint64)
         if max_hits is not None:
             left = int(max_hits)
             for j in range(sp.size):
@@ -694,10 +813,6 @@ class HipFMSearcher:
         import torch
         from .regex import NFA, RegexBatch
 
-        class Source:                                            # what NFA() reads of a PostfixRe
-            def __init__(self, src):
-                self.src, self.lineOnly = src, bool(lineOnly)
-
         res = [r if isinstance(r, str) else bytes(r).decode("latin-1") for r in regexes]
         k = len(res)
         counts = self.counts()
@@ -705,7 +820,7 @@ class HipFMSearcher:
         cls = "|".join("\\" + chr(c) for c in bnd if c >= 1 and counts[c] > 0)
         both = (["(" + cls + ")(" + r + ")" for r in res] if cls else []) + ["(" + r + ")" for r in res]
         n_lead = k if cls else 0
-        batch = RegexBatch(self, [NFA(Source(r)) for r in both])
+        batch = RegexBatch(self, [NFA(_NfaSource(r, lineOnly)) for r in both])
         dev = ctypes.c_int()
         _lib.check(self._L.fmx_device(self._h, ctypes.byref(dev)))
         dev = torch.device("cuda", dev.value)
@@ -745,7 +860,7 @@ class HipFMSearcher:
         return off, occ, bool(batch.truncated)
 
     def finditer(self, regexes, mode="disjoint", max_steps=0, max_per=None, lineOnly=False, corpus=None, match_cap=1 << 20,
-                 occ_cap=1 << 20, words=False, word=WORD_BYTES):
+                 occ_cap=1 << 20, words=False, word=WORD_BYTES, ignore_case=False):
         """Where a batch of regexes matches the indexed text: (off, occ, truncated) -- regex i's matches are
         occ[off[i]:off[i + 1]] (an OCCURRENCE array ascending by (pos, len)), truncated = the match was cut at max_steps
         (FMX_TRUNCATED).  regexes: strings (compiled here; lineOnly as ReTree.compile_batch), a CompiledRegexes set or a
@@ -754,9 +869,19 @@ class HipFMSearcher:
         occ_cap occurrences, and once more with the exact room when that was too little), and offsets and occurrences come down
         in one copy each: between the two calls only counts cross the link.  The device
         buffers are torch tensors.  words=True (regex strings only): whole-word matches -- the bytes next to a match are not
-        in `word`, or the text ends there; the neighbours are not part of the match."""
+        in `word`, or the text ends there; the neighbours are not part of the match.  ignore_case=True (regex strings only):
+        every regex is rewritten by regex.fold_regex under ASCII_FOLD and compiled by REParser.createNFA (ReTree has no case
+        for a set next to a group), so that it is read as Python's re reads it under re.IGNORECASE | re.ASCII -- but for \\w,
+        \\d and '.', which keep re2post's meaning (the bytes A .. y, 0 .. 8 and 2 .. 254; \\w gets z, the image of Z, beside it);
+        a construct re reads differently is refused with ValueError."""
         import torch
-        from .regex import CompiledRegexes, RegexBatch, ReTree
+        from .regex import CompiledRegexes, NFA, RegexBatch, ReTree, fold_regex
+        if ignore_case:
+            if isinstance(regexes, (RegexBatch, CompiledRegexes)):
+                raise ValueError("finditer(ignore_case=True) takes regex strings: it rewrites each before it is compiled")
+            regexes = [fold_regex(r, ASCII_FOLD) for r in regexes]
+            if not words:
+                regexes = RegexBatch(self, [NFA(_NfaSource(r, lineOnly)) for r in regexes])
         if words:
             if isinstance(regexes, (RegexBatch, CompiledRegexes)):
                 raise ValueError("finditer(words=True) takes regex strings: it compiles each with its left context")

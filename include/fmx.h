@@ -1240,6 +1240,65 @@ int fmx_search_context_batch_dev(const fmx_index *idx, const void *d_pat, const 
                                  const fmx_context_opts *opts, void *d_out_off, void *d_out, size_t cap, size_t *n_out,
                                  void *stream);
 
+/* ---- case folding: literal search under a byte map.  Beyond the reference.  DESIGN.md 28.
+ * A FOLD MAP is uint8_t fold[256]: fold[c] is the representative of c's class, and two bytes are equivalent iff their fold
+ * values are equal.  A map is VALID when fold[fold[c]] == fold[c] for every c, fold[0] == 0 and no other byte folds to 0, and
+ * no class has more than FMX_FOLD_MAX_CLASS members; flags and reserved must be 0.  Anything else is FMX_ERR_ARG before the
+ * device is touched.  opts == NULL means ASCII case folding: A..Z fold to a..z, every other byte to itself.
+ * For a pattern P of m bytes (given as fmx_search_batch takes it: a string of s, matched last byte first) a HIT is a byte
+ * string Q of m bytes with fold[Q[j]] == fold[P[j]] at every j for which the reference's search(Q) loop (findex.scala:15-31)
+ * ends with sp < ep.  It is reported as fmx_result {group = pattern, len = m, sp, ep} with (sp, ep) exactly what
+ * fmx_search_batch returns for Q.
+ *  - The definition rests on cf / occ alone, so it holds for any handle, synthetic BWTs included.
+ *  - Distinct Q of one length have disjoint intervals (LF is a permutation).
+ *  - A position whose class is a singleton in the map is a plain step of the exact search with all its quirks, byte 0
+ *    included (a class of two or more never holds byte 0, so the EOF row is never reached by folding).
+ *  - With the identity map the hits are those of fmx_search_batch -- one for a pattern it finds, none for one it does not --
+ *    and the backward steps made are its steps.
+ *  - An empty pattern has the one hit (0, n).
+ * Only variants that occur are followed: the search branches on the index and dies where the text does; a class member that
+ * is absent from the index costs nothing.
+ * Results are in CSR form over the patterns: out_off[k + 1], 24-byte records, ascending sp within a pattern, out_off[k] ==
+ * *n_out.  The same input gives the same bytes on every run; no atomic decides an order.
+ * Capacity, the counting call (cap == 0, out == NULL), FMX_ERR_OVERFLOW with the EXACT total in *n_out, k <= 2^26 and cap <
+ * 2^32 are those of fmx_search_approx_batch, as is the order of the refusals (the null handle last).
+ * FMX_ERR_UNSUPPORTED: fmx_open_block handles and indexes of 2^38 rows or more.
+ * A pattern has at most FMX_FOLD_MAX_LEN bytes: the host form refuses a longer one (FMX_ERR_ARG, before the device is
+ * touched); the device form's kernel skips it and raises a flag, and the call returns FMX_ERR_ARG after the launch with no
+ * hits written and *n_out untouched.
+ * Both forms ALLOCATE AND SYNCHRONISE (FMX_ERR_HIP under a stream capture, decided first, the capture left valid) and free
+ * every temporary on every path: 24 cap bytes of staging, 24 bytes per hit of sort keys and values, the counters, and a stack
+ * of (FMX_FOLD_MAX_CLASS - 1) entries of 24 bytes per byte of the longest pattern -- the device form, which does not know
+ * the lengths, takes FMX_FOLD_MAX_LEN -- per resident wave, checked against the free device memory first (FMX_ERR_NOMEM with the need in the message).  They use the rank dictionary only, build no derived table and do
+ * not count as patterns seen; their steps are added to the handle's counters (rank_queries, backward_steps, search_requests)
+ * and the call to launches.
+ * fmx_search_context_fold_batch[_dev]: fmx_search_context_batch with this search in the place of fmx_search_batch_dev.  The
+ * expansion is the same (P_i, and a.P_i for every occurring a >= 1 of left); the step with a is EXACT even if the map folds
+ * a; every hit is a record of the ORIGINAL pattern, plain variants under FMX_CTX_START (dropped unless bit 0 of left is set),
+ * a variants with lead = 1, ascending sp and on equal sp the FMX_CTX_START record first; then the filter, unchanged, and its
+ * output re-cut to CSR over the patterns.  Patterns are non-empty, at most FMX_FOLD_MAX_LEN - 1 bytes, without byte 0.  The
+ * variants that occur are the filter's records and its limit is theirs: more than 2^26 in one call are FMX_ERR_ARG.
+ * fmx_fold_last: the calling thread's last call: device time (ms) of the search kernel and of the ordering step, backward
+ * steps executed (the ones that come back empty included), rank-dictionary requests issued; any pointer may be NULL. */
+#define FMX_FOLD_MAX_CLASS 8
+#define FMX_FOLD_MAX_LEN 255
+typedef struct fmx_fold_opts {
+  uint8_t fold[256];
+  uint32_t flags;    /* must be 0 */
+  uint32_t reserved; /* must be 0 */
+} fmx_fold_opts;     /* 264 bytes */
+int fmx_search_fold_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k, const fmx_fold_opts *opts,
+                          uint64_t *out_off /* k + 1 */, fmx_result *out, size_t cap, size_t *n_out);
+int fmx_search_fold_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k, const fmx_fold_opts *opts,
+                              void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream);
+int fmx_search_context_fold_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k,
+                                  const fmx_context_opts *ctx, const fmx_fold_opts *fold, uint64_t *out_off /* k + 1 */,
+                                  fmx_result *out, size_t cap, size_t *n_out);
+int fmx_search_context_fold_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k,
+                                      const fmx_context_opts *ctx, const fmx_fold_opts *fold, void *d_out_off, void *d_out,
+                                      size_t cap, size_t *n_out, void *stream);
+int fmx_fold_last(double *search_ms, double *sort_ms, uint64_t *steps, uint64_t *requests);
+
 /* ---- lines: the map from a text position to its line, and occurrences reduced to the distinct lines that hold them (grep -n
  * over an index).  Beyond the reference.  DESIGN.md 23.
  * t is the indexed text of n - 1 bytes; positions are the `pos` of fmx_occurrence, so the occurrence of a one-byte string at
