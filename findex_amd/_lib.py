@@ -185,6 +185,15 @@ class fmx_rank_params(ctypes.Structure):
                 ("flags", ctypes.c_uint32)]
 
 
+class fmx_passage_params(ctypes.Structure):
+    _fields_ = [("window", ctypes.c_uint64), ("max_per", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class fmx_passage(ctypes.Structure):
+    _fields_ = [("raw_off", ctypes.c_uint64), ("mask", ctypes.c_uint64), ("value", ctypes.c_double), ("raw_len", ctypes.c_uint32),
+                ("n_occ", ctypes.c_uint32)]
+
+
 class fmx_context_opts(ctypes.Structure):
     _fields_ = [("left", ctypes.c_uint64 * 4), ("right", ctypes.c_uint64 * 4), ("flags", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32)]
@@ -334,6 +343,12 @@ SYMBOLS = {
                                     _vp]),
     "fmx_corpus_rank_sets_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _P(fmx_rank_params), _vp, _vp, _vp, _vp, _sz,
                                         _vp, _vp, _vp]),
+    "fmx_corpus_passages": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _P(fmx_passage_params), _vp, _vp,
+                                   _sz, _P(_u32)]),
+    "fmx_corpus_passages_dev": (_i32, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _P(fmx_passage_params), _vp,
+                                       _vp, _sz, _P(_u32), _vp]),
+    "fmx_corpus_passages_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(ctypes.c_double), _P(_u64),
+                                        _P(_u64), _P(_u64)]),
     "fmx_occ_host": (_i32, [_vp, _i32, ctypes.c_int64, _P(_u64)]),
     "fmx_calc_gaps_chain": (_i32, [_vp, _vp, _sz, _u64, _i32, _u64, _vp, _P(_sz)]),
     "fmx_regex_compile": (_i32, [_cp, _i32, _P(_vp)]),

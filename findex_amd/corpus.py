@@ -733,19 +733,28 @@ class HipCorpusSearcher:
         ASCII_FOLD) with words=True): a term slot is the set of the intervals of the spellings that occur."""
         if match not in ("any", "all"):
             raise ValueError("match is 'any' or 'all'")
+        q_off, (sp, ep, set_off, _) = self._query_slots(queries, words, ignore_case)
+        return self._rank_slots(sp, ep, set_off, q_off, top=top, k1=k1, b=b, match=match, weights=weights, max_per=max_per)
+
+    def _query_slots(self, queries, words, ignore_case):
         queries = [[bytes(t) for t in q] for q in queries]
-        terms = [t for q in queries for t in q]
         q_off = np.zeros(len(queries) + 1, dtype=np.uint64)
         q_off[1:] = np.cumsum([len(q) for q in queries])
+        return q_off, self._term_slots([t for q in queries for t in q], words, ignore_case)
+
+    def _term_slots(self, terms, words=False, ignore_case=False):
+        """The one term search of rank() and passages(): (sp, ep, set_off, term_len) of the raw byte strings `terms`, one slot
+        each.  set_off is None where a slot is one interval (exact substrings); with words / ignore_case a slot is the set of
+        row ranges sp / ep[set_off[t]:set_off[t + 1]].  term_len[t]: the escaped length, which every interval of slot t shares."""
+        esc = [escape(t) for t in terms]
+        term_len = np.array([len(e) for e in esc], dtype=np.uint32)
         if terms and words:
-            esc = [escape(t) for t in terms]
             if any(not e for e in esc):
                 raise ValueError("empty pattern")
             set_off, runs = self.searcher.search_words(esc, fold=ASCII_FOLD if ignore_case else None)
-            return self.rank_sets_intervals(runs["sp"], runs["ep"], set_off, q_off, top=top, k1=k1, b=b, match=match, weights=weights,
-                                            max_per=max_per)
+            return runs["sp"], runs["ep"], set_off, term_len
         if terms and ignore_case:
-            esc = [escape(t)[::-1] for t in terms]
+            esc = [e[::-1] for e in esc]
             if any(not e for e in esc):
                 raise ValueError("empty pattern")
             off = np.zeros(len(esc) + 1, dtype=np.uint64)
@@ -757,13 +766,17 @@ class HipCorpusSearcher:
                 if e.code != _lib.FMX_ERR_OVERFLOW:
                     raise
                 set_off, hits = self.searcher.search_fold_batch(pat, off, ASCII_FOLD)
-            return self.rank_sets_intervals(hits["sp"], hits["ep"], set_off, q_off, top=top, k1=k1, b=b, match=match, weights=weights,
-                                            max_per=max_per)
+            return hits["sp"], hits["ep"], set_off, term_len
         if terms:
             _, sp, ep = self._intervals(terms)
         else:
             sp = ep = np.zeros(0, dtype=np.uint64)
-        return self.rank_intervals(sp, ep, q_off, top=top, k1=k1, b=b, match=match, weights=weights, max_per=max_per)
+        return sp, ep, None, term_len
+
+    def _rank_slots(self, sp, ep, set_off, q_off, **kw):
+        if set_off is None:
+            return self.rank_intervals(sp, ep, q_off, **kw)
+        return self.rank_sets_intervals(sp, ep, set_off, q_off, **kw)
 
     def rank_intervals(self, sp, ep, q_off, top=10, k1=1.2, b=0.75, match="any", weights=None, max_per=None, cap=None):
         """rank() for term slots given as row intervals of the index; q_off[n_queries + 1] cuts them into queries."""
@@ -818,11 +831,18 @@ class HipCorpusSearcher:
         m = int(off[-1])
         return off, doc[:m], score[:m], df[:n_terms], w[:n_terms]
 
-    def rank_files(self, query_terms, top=10, k1=1.2, b=0.75, match="any", weights=None, max_per=None, words=False, ignore_case=False):
-        """The `top` best files of ONE query (a list of raw byte strings): [(name, score)], best first."""
-        _, doc, score, _, _ = self.rank([list(query_terms)], top=top, k1=k1, b=b, match=match, weights=weights, max_per=max_per,
-                                        words=words, ignore_case=ignore_case)
-        return [(self.corpus.names[int(d)], float(s)) for d, s in zip(doc, score)]
+    def rank_files(self, query_terms, top=10, k1=1.2, b=0.75, match="any", weights=None, max_per=None, words=False, ignore_case=False,
+                   window=None):
+        """The `top` best files of ONE query (a list of raw byte strings): [(name, score)], best first.  With `window`:
+        [(name, score, raw_off, text)], text = the raw bytes of the file's best passage of `window` stream bytes (rank_passages)."""
+        if window is None:
+            _, doc, score, _, _ = self.rank([list(query_terms)], top=top, k1=k1, b=b, match=match, weights=weights, max_per=max_per,
+                                            words=words, ignore_case=ignore_case)
+            return [(self.corpus.names[int(d)], float(s)) for d, s in zip(doc, score)]
+        _, doc, score, _, _, psg, _ = self.rank_passages([list(query_terms)], top=top, window=window, k1=k1, b=b, match=match, weights=weights,
+                                                         max_per=max_per, words=words, ignore_case=ignore_case)
+        texts = self.read(doc, psg["raw_off"], psg["raw_len"]) if doc.size else []
+        return [(self.corpus.names[int(d)], float(s), int(o), t) for d, s, o, t in zip(doc, score, psg["raw_off"], texts)]
 
     def rank_last(self):
         """fmx_corpus_rank_last: {locate_ms, postings_ms, score_ms, select_ms, rows, postings, candidates} of this thread's
@@ -831,4 +851,69 @@ class HipCorpusSearcher:
         n = [ctypes.c_uint64() for _ in range(3)]
         _lib.check(self._L.fmx_corpus_rank_last(*[ctypes.byref(x) for x in ms + n]))
         keys = ("locate_ms", "postings_ms", "score_ms", "select_ms", "rows", "postings", "candidates")
+        return dict(zip(keys, [float(x.value) for x in ms] + [int(x.value) for x in n]))
+
+    # ---- passages of ranked hits (fmx_corpus_passages)
+    PASSAGE = np.dtype([("raw_off", np.uint64), ("mask", np.uint64), ("value", np.float64), ("raw_len", np.uint32), ("n_occ", np.uint32)])
+
+    def passages_sets_intervals(self, sp, ep, set_off, term_len, q_off, hit_off, hit_doc, window=160, weights=None, max_per=None, cap=None):
+        """fmx_corpus_passages: for every hit (hit_off / hit_doc: rank()'s off / doc) the best window of `window` stream bytes
+        and the count of every term slot in the hit's file.  Slots as rank_sets_intervals takes them (set_off None: a slot is
+        one interval); term_len[t]: the stream length of slot t's strings.  -> (psg, tf): psg a structured array (raw_off, mask,
+        value, raw_len, n_occ) per hit, tf[n_hits, stride] with stride = the longest query's slots."""
+        u64 = lambda a: np.ascontiguousarray(a, dtype=np.uint64).reshape(-1)
+        sp, ep, q_off, hit_off = u64(sp), u64(ep), u64(q_off), u64(hit_off)
+        term_len = np.ascontiguousarray(term_len, dtype=np.uint32).reshape(-1)
+        hit_doc = np.ascontiguousarray(hit_doc, dtype=np.uint32).reshape(-1)
+        n_queries, n_terms = q_off.size - 1, term_len.size
+        if set_off is not None:
+            set_off = u64(set_off)
+            if set_off.size != n_terms + 1:
+                raise ValueError("set_off has %d entries for %d terms" % (set_off.size, n_terms))
+        if sp.size != ep.size or hit_off.size != q_off.size or n_queries < 0:
+            raise ValueError("sp and ep, or q_off and hit_off, differ in length")
+        n_hits = int(hit_off[-1])
+        if hit_doc.size != n_hits:
+            raise ValueError("%d hit documents for %d hits" % (hit_doc.size, n_hits))
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+            if weights.size != n_terms:
+                raise ValueError("%d weights for %d terms" % (weights.size, n_terms))
+        if cap is None:
+            cap = n_hits
+        stride_max = int(np.diff(q_off.astype(np.int64)).max()) if n_queries > 0 else 0
+        prm = _lib.fmx_passage_params(int(window), int(max_per or 0), 0, 0)
+        psg = np.zeros(max(cap, 1), dtype=self.PASSAGE)
+        tf = np.zeros(max(cap * max(stride_max, 0), 1), dtype=np.uint32)
+        stride = ctypes.c_uint32(0)
+        _lib.check(self._L.fmx_corpus_passages(self.corpus.handle, self.searcher.handle, _ptr(sp), _ptr(ep), sp.size,
+                                               _ptr(set_off) if set_off is not None else None, n_terms, _ptr(term_len), _ptr(q_off),
+                                               n_queries, _ptr(hit_off), _ptr(hit_doc), _ptr(weights) if weights is not None else None,
+                                               ctypes.byref(prm), psg.ctypes.data_as(ctypes.c_void_p), _ptr(tf), int(cap),
+                                               ctypes.byref(stride)))
+        m = min(int(cap), n_hits)
+        return psg[:m], tf[:m * stride.value].reshape(m, stride.value)
+
+    def passages(self, queries, hit_off, hit_doc, window=160, weights=None, max_per=None, words=False, ignore_case=False):
+        """passages_sets_intervals for `queries` as rank() takes them, searched the same way (one helper: _term_slots)."""
+        q_off, (sp, ep, set_off, term_len) = self._query_slots(queries, words, ignore_case)
+        return self.passages_sets_intervals(sp, ep, set_off, term_len, q_off, hit_off, hit_doc, window=window, weights=weights, max_per=max_per)
+
+    def rank_passages(self, queries, top=10, window=160, k1=1.2, b=0.75, match="any", weights=None, max_per=None, words=False,
+                      ignore_case=False):
+        """One term search, then the ranking, then the passages of its hits with the ranking's weights.
+        -> (off, doc, score, df, weight, psg, tf): rank()'s five, then passages()' two."""
+        if match not in ("any", "all"):
+            raise ValueError("match is 'any' or 'all'")
+        q_off, (sp, ep, set_off, term_len) = self._query_slots(queries, words, ignore_case)
+        off, doc, score, df, w = self._rank_slots(sp, ep, set_off, q_off, top=top, k1=k1, b=b, match=match, weights=weights, max_per=max_per)
+        psg, tf = self.passages_sets_intervals(sp, ep, set_off, term_len, q_off, off, doc, window=window, weights=w, max_per=max_per)
+        return off, doc, score, df, w, psg, tf
+
+    def passages_last(self):
+        """fmx_corpus_passages_last: {locate_ms, filter_ms, sort_ms, window_ms, rows, occurrences, hits} of this thread's last call."""
+        ms = [ctypes.c_double() for _ in range(4)]
+        n = [ctypes.c_uint64() for _ in range(3)]
+        _lib.check(self._L.fmx_corpus_passages_last(*[ctypes.byref(x) for x in ms + n]))
+        keys = ("locate_ms", "filter_ms", "sort_ms", "window_ms", "rows", "occurrences", "hits")
         return dict(zip(keys, [float(x.value) for x in ms] + [int(x.value) for x in n]))

@@ -387,22 +387,31 @@ int corpus_index_check(const Corpus *c, const fmx_index *idx, size_t k, hipStrea
   return not_capturing(st, (std::string("a ") + noun).c_str());
 }
 
-int corpus_doc_keys(const Corpus *c, const fmx_index *idx, const void *d_sp, const void *d_ep, size_t k, uint64_t pat_len,
-                    uint64_t max_per, hipStream_t st, const char *noun, DevMem &mem, Events<5> &ev, DocKeys &out,
-                    const unsigned long long *d_set_off, uint64_t n_slots) {
-  const std::string what = std::string("a ") + noun;
+int corpus_locate_count(const fmx_index *idx, const void *d_sp, const void *d_ep, size_t k, uint64_t max_per, hipStream_t st,
+                        const char *noun, DevMem &mem, unsigned long long **loc_off, uint64_t *n_rows) {
   int rc;
-  if ((rc = device_room(8 * ((uint64_t)k + 1) + 4096, what))) return rc;
-  DEV_ALLOC(mem, out.loc_off, 8 * ((uint64_t)k + 1), "corpus");
+  if ((rc = device_room(8 * ((uint64_t)k + 1) + 4096, std::string("a ") + noun))) return rc;
+  DEV_ALLOC(mem, *loc_off, 8 * ((uint64_t)k + 1), "corpus");
   // the row counts first (no positions: cap 0), then room for exactly that many
-  if ((rc = fmx_locate_intervals_dev(idx, d_sp, d_ep, k, max_per, out.loc_off, nullptr, 0, st))) return rc;
+  if ((rc = fmx_locate_intervals_dev(idx, d_sp, d_ep, k, max_per, *loc_off, nullptr, 0, st))) return rc;
   unsigned long long rows = 0;
-  HIP_TRY(hipMemcpyAsync(&rows, out.loc_off + k, 8, hipMemcpyDeviceToHost, st), "D2H");
+  HIP_TRY(hipMemcpyAsync(&rows, *loc_off + k, 8, hipMemcpyDeviceToHost, st), "D2H");
   HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
   if (rows >= 0xffffffffull) {
     set_error(std::string(noun) + " of " + std::to_string(rows) + " rows: at most 2^32 - 2 per call (use max_per)");
     return FMX_ERR_UNSUPPORTED;
   }
+  *n_rows = rows;
+  return FMX_OK;
+}
+
+int corpus_doc_keys(const Corpus *c, const fmx_index *idx, const void *d_sp, const void *d_ep, size_t k, uint64_t pat_len,
+                    uint64_t max_per, hipStream_t st, const char *noun, DevMem &mem, Events<5> &ev, DocKeys &out,
+                    const unsigned long long *d_set_off, uint64_t n_slots) {
+  const std::string what = std::string("a ") + noun;
+  int rc;
+  uint64_t rows = 0;
+  if ((rc = corpus_locate_count(idx, d_sp, d_ep, k, max_per, st, noun, mem, &out.loc_off, &rows))) return rc;
   out.doc_bits = bits_for(c->n_docs);                               // documents 0 .. n_docs (n_docs: no document) fit
   out.rows = rows;
   if (rows == 0) return FMX_OK;

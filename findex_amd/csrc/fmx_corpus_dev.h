@@ -58,8 +58,19 @@ struct DocKeys {
   int doc_bits = 0;                                 // documents 0 .. n_docs (n_docs: no document) fit
 };
 int corpus_index_check(const Corpus *c, const fmx_index *idx, size_t k, hipStream_t st, const char *noun);
+// corpus_doc_keys' first step, which the passages share (fmx_passages.hip): loc_off[k + 1] from `mem`, the counting locate,
+// one synchronisation of `st` for *n_rows, and the 2^32 - 2 limit ("<noun> of .. rows")
+int corpus_locate_count(const fmx_index *idx, const void *d_sp, const void *d_ep, size_t k, uint64_t max_per, hipStream_t st,
+                        const char *noun, DevMem &mem, unsigned long long **loc_off, uint64_t *n_rows);
 int corpus_doc_keys(const Corpus *c, const fmx_index *idx, const void *d_sp, const void *d_ep, size_t k, uint64_t pat_len,
                     uint64_t max_per, hipStream_t st, const char *noun, DevMem &mem, Events<5> &ev, DocKeys &out,
                     const unsigned long long *d_set_off = nullptr, uint64_t n_slots = 0);
+
+// ---- the shapes of a call's term slots, which the ranking and the passages check alike (fmx_rank.hip); `noun` heads the
+// messages.  rank_check_tables: q_off starts at 0, never decreases and ends at n_terms, at most 64 slots per query, the
+// weights (when given) finite; *max_slots: the longest query's.  rank_check_sets: set_off cuts the n_iv intervals into the slots.
+int rank_check_tables(const char *noun, const uint64_t *q_off, size_t n_queries, size_t n_terms, const double *weights,
+                      uint64_t *max_slots);
+int rank_check_sets(const char *noun, const uint64_t *set_off, size_t n_terms, size_t n_iv);
 
 }  // namespace fmx

@@ -284,6 +284,28 @@ __global__ __launch_bounds__(kRkThreads) void k_rank_select(const unsigned long 
 }
 
 // ---------------------------------------------------------------- host side
+// The shapes of a call's term slots, for the ranking and the passages alike (fmx_corpus_dev.h): `noun` heads the messages
+int rank_check_tables(const char *noun, const uint64_t *q_off, size_t n_queries, size_t n_terms, const double *weights,
+                      uint64_t *max_slots) {
+  const auto fail = [noun](const char *what) { return arg_fail((std::string(noun) + what).c_str()); };
+  if (q_off[0] != 0 || !offsets_monotonic(q_off, 0, n_queries) || q_off[n_queries] != n_terms)
+    return fail(": q_off must start at 0, never decrease and end at n_terms");
+  uint64_t longest = 0;
+  for (size_t q = 0; q < n_queries; q++) longest = std::max<uint64_t>(longest, q_off[q + 1] - q_off[q]);
+  if (longest > kRankMaxSlots) return fail(": at most 64 term slots per query");
+  if (weights)
+    for (size_t t = 0; t < n_terms; t++)
+      if (!std::isfinite(weights[t])) return fail(": the weights must be finite");
+  *max_slots = longest;
+  return FMX_OK;
+}
+
+int rank_check_sets(const char *noun, const uint64_t *set_off, size_t n_terms, size_t n_iv) {
+  if (set_off[0] != 0 || !offsets_monotonic(set_off, 0, n_terms) || set_off[n_terms] != n_iv)
+    return arg_fail((std::string(noun) + ": set_off must start at 0, never decrease and end at n_iv").c_str());
+  return FMX_OK;
+}
+
 namespace {
 
 struct RankLast {
@@ -297,27 +319,6 @@ int rank_check_params(const fmx_rank_params *p) {
   if (!std::isfinite(p->k1) || p->k1 < 0.0) return arg_fail("ranking: k1 must be finite and >= 0");
   if (!std::isfinite(p->b) || p->b < 0.0 || p->b > 1.0) return arg_fail("ranking: b must be in 0 .. 1");
   if (p->flags & ~FMX_RANK_ALL) return arg_fail("ranking: unknown flag");
-  return FMX_OK;
-}
-
-// q_off cuts the n_terms slots into n_queries queries of at most 64 slots; the weights are finite.  *max_slots: the longest query's
-int rank_check_tables(const uint64_t *q_off, size_t n_queries, size_t n_terms, const double *weights, uint64_t *max_slots) {
-  if (q_off[0] != 0 || !offsets_monotonic(q_off, 0, n_queries) || q_off[n_queries] != n_terms)
-    return arg_fail("ranking: q_off must start at 0, never decrease and end at n_terms");
-  uint64_t longest = 0;
-  for (size_t q = 0; q < n_queries; q++) longest = std::max<uint64_t>(longest, q_off[q + 1] - q_off[q]);
-  if (longest > kRankMaxSlots) return arg_fail("ranking: at most 64 term slots per query");
-  if (weights)
-    for (size_t t = 0; t < n_terms; t++)
-      if (!std::isfinite(weights[t])) return arg_fail("ranking: the weights must be finite");
-  *max_slots = longest;
-  return FMX_OK;
-}
-
-// set_off cuts the n_iv intervals into the n_terms slots
-int rank_check_sets(const uint64_t *set_off, size_t n_terms, size_t n_iv) {
-  if (set_off[0] != 0 || !offsets_monotonic(set_off, 0, n_terms) || set_off[n_terms] != n_iv)
-    return arg_fail("ranking: set_off must start at 0, never decrease and end at n_iv");
   return FMX_OK;
 }
 
@@ -465,7 +466,7 @@ static int rank_dev(const fmx_corpus *corpus, const fmx_index *idx, const void *
     std::vector<uint64_t> set_off(n_terms + 1);
     HIP_TRY(hipMemcpyAsync(set_off.data(), d_set_off, 8 * ((uint64_t)n_terms + 1), hipMemcpyDeviceToHost, st), "D2H(set_off)");
     HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
-    if ((rc = rank_check_sets(set_off.data(), n_terms, n_iv))) return rc;
+    if ((rc = rank_check_sets("ranking", set_off.data(), n_terms, n_iv))) return rc;
   }
   std::vector<uint64_t> q_off(n_queries + 1);
   std::vector<double> weights(d_weights ? n_terms : 0);
@@ -473,7 +474,7 @@ static int rank_dev(const fmx_corpus *corpus, const fmx_index *idx, const void *
   if (d_weights && n_terms) HIP_TRY(hipMemcpyAsync(weights.data(), d_weights, 8 * (uint64_t)n_terms, hipMemcpyDeviceToHost, st), "D2H(weights)");
   HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
   uint64_t max_slots = 0;
-  if ((rc = rank_check_tables(q_off.data(), n_queries, n_terms, d_weights ? weights.data() : nullptr, &max_slots))) return rc;
+  if ((rc = rank_check_tables("ranking", q_off.data(), n_queries, n_terms, d_weights ? weights.data() : nullptr, &max_slots))) return rc;
   return rank_core(c, idx, d_sp, d_ep, n_iv, static_cast<const unsigned long long *>(d_set_off), n_terms,
                    static_cast<const unsigned long long *>(d_q_off), n_queries, max_slots, *params,
                    static_cast<const double *>(d_weights), static_cast<unsigned long long *>(d_out_off),
@@ -509,8 +510,8 @@ static int rank_host(const fmx_corpus *corpus, const fmx_index *idx, const uint6
   if (rc) return rc;
   if ((uint64_t)n_queries >= 0xffffffffull) return arg_fail("ranking: too many queries");
   uint64_t max_slots = 0;
-  if ((rc = rank_check_tables(q_off, n_queries, n_terms, weights, &max_slots))) return rc;
-  if (set_off && (rc = rank_check_sets(set_off, n_terms, n_iv))) return rc;
+  if ((rc = rank_check_tables("ranking", q_off, n_queries, n_terms, weights, &max_slots))) return rc;
+  if (set_off && (rc = rank_check_sets("ranking", set_off, n_terms, n_iv))) return rc;
   // everything above is decided before a handle or the device is touched
   const Corpus *c = reinterpret_cast<const Corpus *>(corpus);
   uint64_t n = 0;

@@ -1,7 +1,7 @@
 """Ranked retrieval over a corpus index: which files are the best matches for these words?
 
     python -m findex_amd.rank BASE "words of a query" ["another query" ..] [--top K] [--all] [-w] [-i] [--k1 X] [--b X] [--device D]
-                                                                            [--little-endian]
+                                                                            [--little-endian] [--snippets [W]] [--explain]
 
 BASE names BASE.bwt / BASE.aux / BASE.docs as `python -m findex_amd.index --dir D --out BASE` writes them.  Every positional
 argument is one query, split on white space into its terms.  Without -w terms are SUBSTRINGS, as everywhere in this index:
@@ -10,7 +10,10 @@ not 0-9 A-Z a-z _ or 0x80 .. 0xFF, or the file ends there (HipFMSearcher.search_
 (HipCorpusSearcher.rank, fmx_corpus_rank: scored and cut to the best K on the device).  Output: one line per hit,
 `score<TAB>file`, best first; the queries' blocks are separated by a blank line.  --all keeps only files that hold every term of
 the query.  -i / --ignore-case counts a term in every ASCII case spelling that occurs (HipFMSearcher.search_fold_batch: `error` finds
-Error and ERROR too); it combines with -w.
+Error and ERROR too); it combines with -w.  --snippets [W] prints under every hit `<TAB>offset<TAB>text`: the file's window of W
+stream bytes (default 160) that holds the most valuable set of the query's terms, by the ranking's weights, read back from the
+index (HipCorpusSearcher.rank_passages, fmx_corpus_passages); bytes below 0x20 are shown as a space.  --explain prints under every
+hit `<TAB>term=tf ..`: how often each term of the query occurs in the file, the counts the score was computed from.
 """
 import argparse
 import sys
@@ -25,6 +28,9 @@ def parser():
     ap.add_argument("--all", dest="all_", action="store_true", help="only files that hold every term of the query")
     ap.add_argument("-w", "--words", action="store_true", help="a term counts only where it stands as a whole word")
     ap.add_argument("-i", "--ignore-case", action="store_true", help="a term counts in every ASCII case spelling")
+    ap.add_argument("--snippets", type=int, nargs="?", const=160, default=None, metavar="W",
+                    help="under every hit its best passage of W stream bytes (default 160): <TAB>offset<TAB>text")
+    ap.add_argument("--explain", action="store_true", help="under every hit the count of every term in the file: <TAB>term=tf ..")
     ap.add_argument("--k1", type=float, default=1.2)
     ap.add_argument("--b", type=float, default=0.75)
     ap.add_argument("--device", type=int, default=0)
@@ -49,10 +55,31 @@ def render(names, off, doc, score):
     return rows
 
 
+_CONTROL = bytes(range(0x20))
+
+
+def render_passages(names, off, doc, score, queries, raw_off=None, texts=None, tf=None):
+    """render()'s lines with, under every hit, `<TAB>raw_off<TAB>text` when raw_off / texts are given (bytes below 0x20 in the
+    text shown as a space) and `<TAB>term=tf ..` in query order when the tf rows are given (queries: the terms as bytes)."""
+    rows = []
+    for i in range(len(off) - 1):
+        if i:
+            rows.append(b"")
+        for j in range(int(off[i]), int(off[i + 1])):
+            rows.append(repr(float(score[j])).encode() + b"\t" + names[int(doc[j])])
+            if texts is not None:
+                rows.append(b"\t" + str(int(raw_off[j])).encode() + b"\t" + bytes(texts[j]).translate(bytes.maketrans(_CONTROL, b" " * 32)))
+            if tf is not None:
+                rows.append(b"\t" + b" ".join(t + b"=" + str(int(tf[j][s])).encode() for s, t in enumerate(queries[i])))
+    return rows
+
+
 def main(argv=None):
     a = parser().parse_args(argv)
     if not 1 <= a.top <= 1024:
         parser().error("--top is 1 .. 1024")
+    if a.snippets is not None and not 1 <= a.snippets < (1 << 32):
+        parser().error("--snippets is 1 .. 2^32 - 1")
     queries = split_queries(a.query)
     from .corpus import HipCorpusSearcher
     cs = HipCorpusSearcher.open(a.base, bigEndian=not a.little_endian, device=a.device)
@@ -60,9 +87,18 @@ def main(argv=None):
         kw = {"words": True} if a.words else {}
         if a.ignore_case:
             kw["ignore_case"] = True
-        off, doc, score, _, _ = cs.rank(queries, top=a.top, k1=a.k1, b=a.b, match="all" if a.all_ else "any", **kw)
         out = sys.stdout.buffer
-        for row in render(cs.corpus.names, off, doc, score):
+        if a.snippets is not None or a.explain:
+            off, doc, score, _, _, psg, tf = cs.rank_passages(queries, top=a.top, window=a.snippets or 160, k1=a.k1, b=a.b,
+                                                              match="all" if a.all_ else "any", **kw)
+            texts = None
+            if a.snippets is not None:
+                texts = cs.read(doc, psg["raw_off"], psg["raw_len"]) if doc.size else []
+            rows = render_passages(cs.corpus.names, off, doc, score, queries, psg["raw_off"], texts, tf if a.explain else None)
+        else:
+            off, doc, score, _, _ = cs.rank(queries, top=a.top, k1=a.k1, b=a.b, match="all" if a.all_ else "any", **kw)
+            rows = render(cs.corpus.names, off, doc, score)
+        for row in rows:
             out.write(row + b"\n")
         out.flush()
     finally:

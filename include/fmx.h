@@ -992,6 +992,73 @@ int fmx_corpus_rank_sets_dev(const fmx_corpus *corpus, const fmx_index *idx, con
                              const fmx_rank_params *params, const void *d_weights, void *d_out_off, void *d_out_doc,
                              void *d_out_score, size_t cap, void *d_out_df, void *d_out_weight, void *stream);
 
+/* ---- passages: for every ranked hit the window of W stream bytes that holds the most valuable set of the query's terms,
+ * and the count of every term in the hit's file.  Beyond the reference.  DESIGN.md 29.  Exact, like the ranking: a result
+ * can be compared bit for bit.
+ * INPUTS.  corpus, idx and the term slots exactly as fmx_corpus_rank_sets takes them: n_iv intervals sp[] / ep[],
+ * set_off[n_terms + 1] cuts them into slots (NULL: one interval per slot, n_iv == n_terms, else FMX_ERR_ARG),
+ * q_off[n_queries + 1] cuts the slots into queries of at most 64 slots.  term_len[n_terms] (u32, >= 1, else FMX_ERR_ARG):
+ * the length in STREAM bytes of the strings of slot t; all intervals of a slot share it (an exact term, its case spellings
+ * and its whole-word runs do).  The hits: hit_off[n_queries + 1] (from 0, never decreasing) and hit_doc[n_hits], n_hits =
+ * hit_off[n_queries], are fmx_corpus_rank's out_off / out_doc as they come, in any order inside a query; every hit_doc <
+ * n_docs and no (query, document) pair twice, else FMX_ERR_ARG with the pair in the message; a document may be a hit of
+ * several queries.  weights[n_terms]: doubles, all finite, else FMX_ERR_ARG; negative ones allowed; NULL: 1.0 each.
+ * params: 1 <= window < 2^32; flags and reserved 0 (FMX_ERR_ARG otherwise); max_per rows of every INTERVAL, 0 = all, as the
+ * ranking takes them.
+ * DEFINITIONS, for hit h = (query i, document d).  A located row with suffix-array value SA of slot s has its last byte at
+ * stream position e = stream_len - 1 - SA (the ranking's rule: a row belongs to the same document in both calls) and its
+ * first at f = e - term_len[s] + 1.  It is an OCCURRENCE of (h, s) when s is a slot of query i, e lies in document d and
+ * f >= doc_start[d]; a row that fails the last condition is dropped from everything, the counts included (it cannot happen
+ * with honest term_len).  tf(h, s) = the occurrences of (h, s): for honest inputs the ranking's tf.  The window STARTS of h
+ * are the f of all its occurrences; the window of a start a is [a, a + window).  cover(a) = the slots s of the query that
+ * have an occurrence with f >= a and e < a + window.  value(a) = ((0.0 + w(s0)) + w(s1)) + .. over the slots of cover(a) in
+ * ascending slot order, IEEE double, one rounding per addition.  The BEST window is the start with the largest value (plain
+ * > on doubles), equal values to the smallest a.  It is clipped at b = min(a + window, doc_start[d + 1] - 1): the separator
+ * is never part of a passage and no passage reaches into the next document.
+ * OUTPUT.  One fmx_passage per hit in the order of hit_doc: raw_off = the raw offset of a in the document; raw_len =
+ * raw_off(b - 1) + 1 - raw_off(a), both from the corpus map, where both bytes of an escape pair stand for their raw byte;
+ * mask bit j set when the query's j-th slot is in the cover; value; n_occ = the occurrences of the hit.  A hit without
+ * occurrences gets all zeros.  out_tf: u32[n_hits * stride], stride = the slot count of the call's longest query, returned
+ * through *out_stride; entry h * stride + j = tf of the j-th slot of h's query, the padding 0.  cap counts hits: nothing is
+ * written past record cap - 1 or past cap * stride counts; FMX_ERR_OVERFLOW when n_hits > cap (the first cap hits written).
+ * LIMITS, each refused with a message that names it: fewer than 2^32 - 1 located rows per call, and bits_for(n_hits) +
+ * bits_for(slots of the longest query) + bits_for(stream_len - 1) <= 64 (FMX_ERR_UNSUPPORTED); the handles locate refuses;
+ * the shape errors of q_off / set_off / hit_off (FMX_ERR_ARG).  The host form decides every FMX_ERR_ARG that needs no
+ * handle before a handle or the device is touched.  fmx_corpus_passages_dev: every array a device pointer (u64 sp / ep /
+ * set_off / q_off / hit_off, u32 term_len / hit_doc / out_tf, f64 weights); params and out_stride stay host pointers; it
+ * reads d_hit_off[n_queries] back with its first synchronisation and returns FMX_ERR_OVERFLOW the same way.  Both forms
+ * ALLOCATE AND SYNCHRONISE (FMX_ERR_HIP under a stream capture, decided before anything is allocated); the need is checked
+ * against the free HBM before every allocation and every temporary is freed on every path.  A sort of the hits, locate, one
+ * lane per located row to keep those of hit documents, a sort of the kept ones, one wave per hit for the windows; no atomic
+ * decides an order or a value: the same input gives the same bytes.
+ * fmx_corpus_passages_last: device time (ms) of the calling thread's last call in its four phases, the rows located, the
+ * occurrences kept and the hits. */
+typedef struct fmx_passage_params {
+  uint64_t window;  /* stream bytes, 1 .. 2^32 - 1 */
+  uint64_t max_per; /* rows taken of every interval; 0 = all */
+  uint32_t flags;   /* 0 */
+  uint32_t reserved;
+} fmx_passage_params; /* 24 bytes */
+typedef struct fmx_passage {
+  uint64_t raw_off; /* of the window's first byte in its document */
+  uint64_t mask;    /* bit j: the query's j-th slot is covered */
+  double value;
+  uint32_t raw_len; /* raw bytes of the clipped window */
+  uint32_t n_occ;   /* occurrences of the hit */
+} fmx_passage;      /* 32 bytes */
+int fmx_corpus_passages(const fmx_corpus *corpus, const fmx_index *idx, const uint64_t *sp, const uint64_t *ep, size_t n_iv,
+                        const uint64_t *set_off, size_t n_terms, const uint32_t *term_len, const uint64_t *q_off,
+                        size_t n_queries, const uint64_t *hit_off, const uint32_t *hit_doc, const double *weights,
+                        const fmx_passage_params *params, fmx_passage *out, uint32_t *out_tf, size_t cap,
+                        uint32_t *out_stride);
+int fmx_corpus_passages_dev(const fmx_corpus *corpus, const fmx_index *idx, const void *d_sp, const void *d_ep, size_t n_iv,
+                            const void *d_set_off, size_t n_terms, const void *d_term_len, const void *d_q_off,
+                            size_t n_queries, const void *d_hit_off, const void *d_hit_doc, const void *d_weights,
+                            const fmx_passage_params *params, void *d_out, void *d_out_tf, size_t cap,
+                            uint32_t *out_stride, void *stream);
+int fmx_corpus_passages_last(double *locate_ms, double *filter_ms, double *sort_ms, double *window_ms, uint64_t *rows,
+                             uint64_t *occurrences, uint64_t *hits);
+
 /* ---- regex: REParser.re2post (re2/re2.scala:50-185) + ReTree.apply (re2/retree.scala:156-370).
  * Bytes of `re` are Latin-1 characters.  FMX_ERR_SYNTAX / FMX_ERR_MATCH mirror the reference's
  * "re2post syntax" exception and scala.MatchError. */
