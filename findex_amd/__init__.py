@@ -27,6 +27,9 @@ package is the thin host-side mirror of the reference's Scala interface for that
                                                    HipCorpusSearcher.grep_lines_where / .grep_lines_inverted, grep -v / --and / --not
                                                    HipFMSearcher.search_fold / .locate_fold (every case variant that occurs),
                                                    ignore_case= on finditer, grep and rank, grep -i, rank -i
+                                                   HipFMSearcher.search_classes_batch / .locate_classes, findex_amd.unicode_fold
+                                                   (UTF-8 case folding), ignore_case="unicode" on locate_docs, rank, finditer and grep,
+                                                   search_words(classes=..), rank --unicode-case, grep --unicode-case
 
 There is no CPU fallback: importing works anywhere, but every compute call needs the built
 library and a HIP device and fails loudly otherwise.

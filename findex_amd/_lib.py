@@ -210,6 +210,17 @@ FMX_FOLD_MAX_CLASS = 8
 FMX_FOLD_MAX_LEN = 255
 
 
+class fmx_class_table(ctypes.Structure):
+    _fields_ = [("cls_off", ctypes.c_void_p), ("mem_off", ctypes.c_void_p), ("mem_bytes", ctypes.c_void_p),
+                ("n_classes", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+FMX_CLASS_MAX_MEMBER_LEN = 4
+FMX_CLASS_MAX_MEMBERS = 16
+FMX_CLASS_MAX_ELEMS = 255
+FMX_CLASS_MAX_CLASSES = 65280
+
+
 class fmx_stats_t(ctypes.Structure):
     _fields_ = [("rank_queries", ctypes.c_uint64), ("backward_steps", ctypes.c_uint64),
                 ("launches", ctypes.c_uint64), ("last_kernel_ms", ctypes.c_double),
@@ -378,6 +389,11 @@ SYMBOLS = {
     "fmx_search_context_fold_batch": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_context_opts), _P(fmx_fold_opts), _vp, _vp, _sz, _P(_sz)]),
     "fmx_search_context_fold_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_context_opts), _P(fmx_fold_opts), _vp, _vp, _sz, _P(_sz), _vp]),
     "fmx_fold_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(_u64), _P(_u64)]),
+    "fmx_search_classes_batch": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_class_table), _vp, _vp, _sz, _P(_sz)]),
+    "fmx_search_classes_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_class_table), _vp, _vp, _sz, _P(_sz), _vp]),
+    "fmx_search_context_classes_batch": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_context_opts), _P(fmx_class_table), _vp, _vp, _sz, _P(_sz)]),
+    "fmx_search_context_classes_batch_dev": (_i32, [_vp, _vp, _vp, _sz, _P(fmx_context_opts), _P(fmx_class_table), _vp, _vp, _sz, _P(_sz), _vp]),
+    "fmx_classes_last": (_i32, [_P(ctypes.c_double), _P(ctypes.c_double), _P(_u64), _P(_u64)]),
     "fmx_lines_prepare": (_i32, [_vp, _vp, _sz]),
     "fmx_lines_info": (_i32, [_vp, _P(_u64), _vp, _P(_u32), _P(_u32), _P(_u64), _P(ctypes.c_double)]),
     "fmx_lines_batch": (_i32, [_vp, _vp, _sz, _vp, _vp, _vp]),

@@ -16,8 +16,8 @@ OUT_DIR = os.path.join(HERE, "lib")
 OUT = os.path.join(OUT_DIR, "libfmx.so")
 # the same library with fmx_comm.cpp's fault-injection switch compiled in (-DFMX_FAULT_INJECTION): loaded by one test only
 OUT_FAULTS = os.path.join(OUT_DIR, "libfmx_faults.so")
-SOURCES = ["fmx_api.cpp", "fmx_hostpar.cpp", "fmx_comm.cpp", "fmx_hostrank.cpp", "fmx_regex.cpp", "fmx_build.hip", "fmx_kernels.hip", "fmx_search.hip", "fmx_search4_onehot.hip", "fmx_search4_onehot_wide.hip", "fmx_search4_bytes.hip", "fmx_search4_onehot_kx.hip", "fmx_ktab.hip", "fmx_jump.hip", "fmx_select.hip", "fmx_locate.hip", "fmx_lcp.hip", "fmx_frontier.hip", "fmx_regex_batch.hip", "fmx_refmatch.hip", "fmx_order.hip", "fmx_sufsort.hip", "fmx_corpus.hip", "fmx_rank.hip", "fmx_passages.hip", "fmx_approx.hip", "fmx_edit.hip", "fmx_fold.hip", "fmx_mstat.hip", "fmx_extract.hip", "fmx_repeats.hip", "fmx_ngrams.hip", "fmx_occ.hip", "fmx_context.hip", "fmx_merge.hip", "fmx_lines.hip", "fmx_linequery.hip"]
-HEADERS = ["fmx_approx.h", "fmx_corpus_dev.h", "fmx_ctx_math.h", "fmx_device.h", "fmx_fold.h", "fmx_frontier.h", "fmx_host.h", "fmx_hostpar.h", "fmx_lines_dev.h", "fmx_nfa.h", "fmx_order.h", "fmx_order_math.h", "fmx_passage_math.h", "fmx_pool_deal.h", "fmx_rank_math.h", "fmx_regex.h", "fmx_search4.h"]
+SOURCES = ["fmx_api.cpp", "fmx_hostpar.cpp", "fmx_comm.cpp", "fmx_hostrank.cpp", "fmx_regex.cpp", "fmx_build.hip", "fmx_kernels.hip", "fmx_search.hip", "fmx_search4_onehot.hip", "fmx_search4_onehot_wide.hip", "fmx_search4_bytes.hip", "fmx_search4_onehot_kx.hip", "fmx_ktab.hip", "fmx_jump.hip", "fmx_select.hip", "fmx_locate.hip", "fmx_lcp.hip", "fmx_frontier.hip", "fmx_regex_batch.hip", "fmx_refmatch.hip", "fmx_order.hip", "fmx_sufsort.hip", "fmx_corpus.hip", "fmx_rank.hip", "fmx_passages.hip", "fmx_approx.hip", "fmx_edit.hip", "fmx_fold.hip", "fmx_classes.hip", "fmx_mstat.hip", "fmx_extract.hip", "fmx_repeats.hip", "fmx_ngrams.hip", "fmx_occ.hip", "fmx_context.hip", "fmx_merge.hip", "fmx_lines.hip", "fmx_linequery.hip"]
+HEADERS = ["fmx_approx.h", "fmx_classes.h", "fmx_corpus_dev.h", "fmx_ctx_math.h", "fmx_device.h", "fmx_fold.h", "fmx_frontier.h", "fmx_host.h", "fmx_hostpar.h", "fmx_lines_dev.h", "fmx_nfa.h", "fmx_order.h", "fmx_order_math.h", "fmx_passage_math.h", "fmx_pool_deal.h", "fmx_rank_math.h", "fmx_regex.h", "fmx_search4.h"]
 MAX_JOBS = 16       # hipcc processes at once
 ARCH = "gfx950"
 

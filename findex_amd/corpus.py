@@ -355,7 +355,7 @@ class HipCorpusSearcher:
         finally:
             more.close()
 
-    def locate_docs(self, q, max_hits=None, max_mismatches=0, words=False, ignore_case=False):
+    def locate_docs(self, q, max_hits=None, max_mismatches=0, words=False, ignore_case=False, ignore_marks=False):
         """(doc, raw_off) arrays of the occurrences of the raw bytes q, sorted by (doc, raw_off): q is escaped, its reverse
         searched, the rows located (locate_text's arithmetic with the escaped length) and the positions mapped.
 
@@ -370,7 +370,30 @@ class HipCorpusSearcher:
         byte 0, 1 or 255 next to q shows the second byte of its escape pair there, which is a word byte.
 
         ignore_case=True (exact search only): q in every ASCII case spelling that occurs (HipFMSearcher.locate_fold, or
-        locate_words(fold=ASCII_FOLD) with words=True)."""
+        locate_words(fold=ASCII_FOLD) with words=True).
+
+        ignore_case="unicode" (exact search; with words=True whole words, HipFMSearcher.search_words(classes=..)): q, read as UTF-8, in every case spelling that occurs, classes
+        of several bytes included (HipFMSearcher.search_classes_batch, DESIGN.md 30: k / U+212A, s / U+017F); ignore_marks=True
+        adds the precomposed accented forms of every letter.  A spelling may have another length than q, so the result is
+        (doc, raw_off, stream_len) sorted by (doc, raw_off, stream_len)."""
+        if ignore_marks and ignore_case != "unicode":
+            raise ValueError('ignore_marks=True goes with ignore_case="unicode"')
+        if ignore_case == "unicode":
+            if max_mismatches:
+                raise ValueError('ignore_case="unicode" goes with max_mismatches=0')
+            esc = escape(q)
+            if not esc:
+                raise ValueError("empty pattern")
+            keep = lambda m: escape(m) == m
+            if words:
+                _, hits = self.searcher.search_words([esc], classes="marks" if ignore_marks else "unicode", keep=keep)
+            else:
+                el, el_off, table = self.searcher.unicode_table([esc], ignore_marks, keep=keep)
+                _, hits = self.searcher.search_classes_batch(el, el_off, table)
+            pos, lens = self.searcher.locate_spellings(hits, max_hits)
+            doc, _, raw = self.corpus.map(pos)
+            order = np.lexsort((lens, raw, doc))
+            return doc[order], raw[order], lens[order]
         if words and max_mismatches:
             raise ValueError("words=True goes with max_mismatches=0")
         if ignore_case and max_mismatches:
@@ -721,7 +744,8 @@ class HipCorpusSearcher:
         return int(off[1])
 
     # ---- ranked retrieval (fmx_corpus_rank)
-    def rank(self, queries, top=10, k1=1.2, b=0.75, match="any", weights=None, max_per=None, words=False, ignore_case=False):
+    def rank(self, queries, top=10, k1=1.2, b=0.75, match="any", weights=None, max_per=None, words=False, ignore_case=False,
+             ignore_marks=False):
         """fmx_corpus_rank: the `top` best files of every query by BM25.  `queries` is a list of lists of raw byte strings
         (terms; substrings, as everywhere in this index), escaped and searched here.  match="any": a file that holds at
         least one term of a query is a candidate; "all": only a file that holds every term.  weights: one float per term in
@@ -730,24 +754,56 @@ class HipCorpusSearcher:
         term.  Terms of any lengths share the one call.  words=True: a term counts only where it stands as a whole word
         (HipFMSearcher.search_words on the escaped stream; a term slot is then the set of row ranges that pass, fmx_corpus_rank_sets).
         ignore_case=True: a term counts in every ASCII case spelling (HipFMSearcher.search_fold_batch, or search_words(fold=
-        ASCII_FOLD) with words=True): a term slot is the set of the intervals of the spellings that occur."""
+        ASCII_FOLD) with words=True): a term slot is the set of the intervals of the spellings that occur.
+        ignore_case="unicode": every UTF-8 case spelling, classes of several bytes included (HipFMSearcher.search_classes_batch,
+        or search_words(classes=..) with words=True); ignore_marks=True: precomposed accented forms as well."""
         if match not in ("any", "all"):
             raise ValueError("match is 'any' or 'all'")
-        q_off, (sp, ep, set_off, _) = self._query_slots(queries, words, ignore_case)
+        q_off, (sp, ep, set_off, _) = self._query_slots(queries, words, ignore_case, ignore_marks)
         return self._rank_slots(sp, ep, set_off, q_off, top=top, k1=k1, b=b, match=match, weights=weights, max_per=max_per)
 
-    def _query_slots(self, queries, words, ignore_case):
+    def _query_slots(self, queries, words, ignore_case, ignore_marks=False, same_len=False):
         queries = [[bytes(t) for t in q] for q in queries]
         q_off = np.zeros(len(queries) + 1, dtype=np.uint64)
         q_off[1:] = np.cumsum([len(q) for q in queries])
-        return q_off, self._term_slots([t for q in queries for t in q], words, ignore_case)
+        return q_off, self._term_slots([t for q in queries for t in q], words, ignore_case, ignore_marks, same_len)
 
-    def _term_slots(self, terms, words=False, ignore_case=False):
+    def _term_slots(self, terms, words=False, ignore_case=False, ignore_marks=False, same_len=False):
         """The one term search of rank() and passages(): (sp, ep, set_off, term_len) of the raw byte strings `terms`, one slot
         each.  set_off is None where a slot is one interval (exact substrings); with words / ignore_case a slot is the set of
-        row ranges sp / ep[set_off[t]:set_off[t + 1]].  term_len[t]: the escaped length, which every interval of slot t shares."""
+        row ranges sp / ep[set_off[t]:set_off[t + 1]].  term_len[t]: the escaped length, which every interval of slot t shares.
+        ignore_case="unicode": the spellings of a slot may differ in length; term_len[t] is the length of slot t's spellings
+        where they agree, the escaped length for a slot without one or with spellings that do not agree -- which with same_len
+        is a ValueError that names the term and two of the lengths."""
         esc = [escape(t) for t in terms]
         term_len = np.array([len(e) for e in esc], dtype=np.uint32)
+        if ignore_marks and ignore_case != "unicode":
+            raise ValueError('ignore_marks=True goes with ignore_case="unicode"')
+        if ignore_case == "unicode":
+            if not terms:
+                return np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint64), np.zeros(1, dtype=np.uint64), term_len
+            if any(not e for e in esc):
+                raise ValueError("empty pattern")
+            keep = lambda m: escape(m) == m
+            if words:
+                set_off, hits = self.searcher.search_words(esc, classes="marks" if ignore_marks else "unicode", keep=keep)
+            else:
+                el, el_off, table = self.searcher.unicode_table(esc, ignore_marks, keep=keep)
+                try:                                             # a first guess at the room spares the counting call's search
+                    set_off, hits = self.searcher.search_classes_batch(el, el_off, table, cap=64 * len(esc) + 1024)
+                except _lib.FmxError as e:
+                    if e.code != _lib.FMX_ERR_OVERFLOW:
+                        raise
+                    set_off, hits = self.searcher.search_classes_batch(el, el_off, table)
+            for t in range(len(esc)):
+                lens = hits["len"][int(set_off[t]):int(set_off[t + 1])]
+                if lens.size:
+                    if same_len and int(lens.min()) != int(lens.max()):
+                        raise ValueError("the spellings of %r differ in length (%d and %d bytes): passages take one length per term"
+                                         % (terms[t], int(lens.min()), int(lens.max())))
+                    if int(lens.min()) == int(lens.max()):
+                        term_len[t] = int(lens[0])
+            return hits["sp"], hits["ep"], set_off, term_len
         if terms and words:
             if any(not e for e in esc):
                 raise ValueError("empty pattern")
@@ -832,15 +888,15 @@ class HipCorpusSearcher:
         return off, doc[:m], score[:m], df[:n_terms], w[:n_terms]
 
     def rank_files(self, query_terms, top=10, k1=1.2, b=0.75, match="any", weights=None, max_per=None, words=False, ignore_case=False,
-                   window=None):
+                   window=None, ignore_marks=False):
         """The `top` best files of ONE query (a list of raw byte strings): [(name, score)], best first.  With `window`:
         [(name, score, raw_off, text)], text = the raw bytes of the file's best passage of `window` stream bytes (rank_passages)."""
         if window is None:
             _, doc, score, _, _ = self.rank([list(query_terms)], top=top, k1=k1, b=b, match=match, weights=weights, max_per=max_per,
-                                            words=words, ignore_case=ignore_case)
+                                            words=words, ignore_case=ignore_case, ignore_marks=ignore_marks)
             return [(self.corpus.names[int(d)], float(s)) for d, s in zip(doc, score)]
         _, doc, score, _, _, psg, _ = self.rank_passages([list(query_terms)], top=top, window=window, k1=k1, b=b, match=match, weights=weights,
-                                                         max_per=max_per, words=words, ignore_case=ignore_case)
+                                                         max_per=max_per, words=words, ignore_case=ignore_case, ignore_marks=ignore_marks)
         texts = self.read(doc, psg["raw_off"], psg["raw_len"]) if doc.size else []
         return [(self.corpus.names[int(d)], float(s), int(o), t) for d, s, o, t in zip(doc, score, psg["raw_off"], texts)]
 
@@ -894,18 +950,20 @@ class HipCorpusSearcher:
         m = min(int(cap), n_hits)
         return psg[:m], tf[:m * stride.value].reshape(m, stride.value)
 
-    def passages(self, queries, hit_off, hit_doc, window=160, weights=None, max_per=None, words=False, ignore_case=False):
-        """passages_sets_intervals for `queries` as rank() takes them, searched the same way (one helper: _term_slots)."""
-        q_off, (sp, ep, set_off, term_len) = self._query_slots(queries, words, ignore_case)
+    def passages(self, queries, hit_off, hit_doc, window=160, weights=None, max_per=None, words=False, ignore_case=False,
+                 ignore_marks=False):
+        """passages_sets_intervals for `queries` as rank() takes them, searched the same way (one helper: _term_slots).  Under
+        ignore_case="unicode" every spelling of a term must have one length: a ValueError names a term of which they differ."""
+        q_off, (sp, ep, set_off, term_len) = self._query_slots(queries, words, ignore_case, ignore_marks, same_len=True)
         return self.passages_sets_intervals(sp, ep, set_off, term_len, q_off, hit_off, hit_doc, window=window, weights=weights, max_per=max_per)
 
     def rank_passages(self, queries, top=10, window=160, k1=1.2, b=0.75, match="any", weights=None, max_per=None, words=False,
-                      ignore_case=False):
+                      ignore_case=False, ignore_marks=False):
         """One term search, then the ranking, then the passages of its hits with the ranking's weights.
-        -> (off, doc, score, df, weight, psg, tf): rank()'s five, then passages()' two."""
+        -> (off, doc, score, df, weight, psg, tf): rank()'s five, then passages()' two.  ignore_case="unicode": as passages()."""
         if match not in ("any", "all"):
             raise ValueError("match is 'any' or 'all'")
-        q_off, (sp, ep, set_off, term_len) = self._query_slots(queries, words, ignore_case)
+        q_off, (sp, ep, set_off, term_len) = self._query_slots(queries, words, ignore_case, ignore_marks, same_len=True)
         off, doc, score, df, w = self._rank_slots(sp, ep, set_off, q_off, top=top, k1=k1, b=b, match=match, weights=weights, max_per=max_per)
         psg, tf = self.passages_sets_intervals(sp, ep, set_off, term_len, q_off, off, doc, window=window, weights=w, max_per=max_per)
         return off, doc, score, df, w, psg, tf

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "fmx_ctx_math.h"
+#include "fmx_classes.h"
 #include "fmx_fold.h"
 #include "fmx_order.h"
 
@@ -207,7 +208,7 @@ __global__ __launch_bounds__(kCtxThreads) void k_ctx_off(const uint32_t *__restr
 
 // ---- fmx_search_context_batch: the expansion of the patterns and the record list
 struct CtxExpand {
-  const uint8_t *pat;
+  const void *pat;                                   // uint8_t bytes, or the uint16_t elements of the class search (§30)
   const unsigned long long *off;
   uint64_t k, n_left;                                // patterns; left bytes a >= 1 that occur, ascending, in lefts[]
   const uint8_t *lefts;
@@ -216,7 +217,8 @@ struct CtxExpand {
 // Pattern i (a string of s, as fmx_search_batch takes it) -> 1 + n_left strings: itself, then itself with each left byte
 // appended (a in front of the text string is a behind its reverse).  flag[0] = 1 for an empty pattern, a byte 0, offsets
 // that do not ascend or a pattern above FMX_OCC_MAX_LEN - 1 bytes; nothing is written outside the expansion's buffers.
-__global__ __launch_bounds__(kCtxThreads) void k_ctx_expand(CtxExpand e, uint8_t *__restrict__ xpat,
+template <class T>
+__global__ __launch_bounds__(kCtxThreads) void k_ctx_expand(CtxExpand e, T *__restrict__ xpat,
                                                             unsigned long long *__restrict__ xoff, uint32_t *__restrict__ flag) {
   const uint64_t per = e.n_left + 1, total = e.k * per, stride = (uint64_t)gridDim.x * blockDim.x;
   const uint64_t o0 = e.off[0], ok_ = e.off[e.k];
@@ -234,7 +236,7 @@ __global__ __launch_bounds__(kCtxThreads) void k_ctx_expand(CtxExpand e, uint8_t
     if (len == 0 || len > FMX_OCC_MAX_LEN - 1) bad = true;
     if (!bad) {
       for (uint64_t t = 0; t < len; t++) {
-        const uint8_t c = e.pat[ob + t];
+        const T c = static_cast<const T *>(e.pat)[ob + t];
         if (c == 0) bad = true;
         xpat[at + t] = c;
       }
@@ -448,14 +450,20 @@ int ctx_opts_check(const fmx_context_opts *o) {
 // The search with context on `st`; everything in device memory, the patterns already checked as far as the caller can.
 // pat_bytes = d_off[k] - d_off[0].  fold_map (256 bytes, or null: the exact search): the search under that map instead, with
 // fold_len the longest expanded pattern (the left byte included), FMX_FOLD_MAX_LEN where the lengths are not known.
-int ctx_search(const Index *h, const fmx_index *idx, const uint8_t *d_pat, const unsigned long long *d_off, uint64_t k,
-               uint64_t pat_bytes, const fmx_context_opts &o, const uint8_t *fold_map, uint32_t fold_len, unsigned long long *d_out_off,
-               fmx_result *d_out, uint64_t cap, hipStream_t st, uint64_t *total) {
+// cc (or null): the class search (fmx_classes.hip) instead -- d_pat holds uint16_t elements, pat_bytes counts elements, the left
+// byte is appended as a LITERAL element, and fold_len is in elements.  Lead bit, `per`, modes, filter and re-cut are the fold path's.
+struct CtxClasses {
+  const std::vector<ClassRec> *packed;
+  uint32_t largest;
+};
+int ctx_search(const Index *h, const fmx_index *idx, const void *d_pat, const unsigned long long *d_off, uint64_t k,
+               uint64_t pat_bytes, const fmx_context_opts &o, const uint8_t *fold_map, const CtxClasses *cc, uint32_t fold_len,
+               unsigned long long *d_out_off, fmx_result *d_out, uint64_t cap, hipStream_t st, uint64_t *total) {
   uint8_t lefts[256];
   uint64_t n_left = 0;
   for (uint32_t c = 1; c < 256; c++)
     if (((o.left[c >> 6] >> (c & 63)) & 1) && h->counts[c] > 0) lefts[n_left++] = (uint8_t)c;
-  const uint64_t per = n_left + 1, xk = k * per, xbytes = per * pat_bytes + k * n_left;
+  const uint64_t per = n_left + 1, xk = k * per, xbytes = (per * pat_bytes + k * n_left) * (cc ? 2 : 1);
   if (xk > (1ull << 26)) return arg_fail("search_context: patterns x (left bytes that occur + 1) must be at most 2^26");
   int rc = device_room(xbytes + 8 * (xk + 1) + 16 * xk + 25 * xk + 8 * (xk + 1) + 8192, "fmx_search_context_batch");
   if (rc) return rc;
@@ -469,7 +477,7 @@ int ctx_search(const Index *h, const fmx_index *idx, const uint8_t *d_pat, const
   DEV_ALLOC(mem, xpat, xbytes, "search_context");
   DEV_ALLOC(mem, d_lefts, 256, "search_context");
   DEV_ALLOC(mem, xoff, 8 * (xk + 1), "search_context");
-  if (!fold_map) {
+  if (!fold_map && !cc) {
     DEV_ALLOC(mem, sp, 8 * xk, "search_context");
     DEV_ALLOC(mem, ep, 8 * xk, "search_context");
     DEV_ALLOC(mem, rec, sizeof(fmx_result) * xk, "search_context");
@@ -479,7 +487,8 @@ int ctx_search(const Index *h, const fmx_index *idx, const uint8_t *d_pat, const
   HIP_TRY(hipMemsetAsync(flag, 0, 16, st), "hipMemsetAsync");
   HIP_TRY(hipMemcpyAsync(d_lefts, lefts, 256, hipMemcpyHostToDevice, st), "H2D(left bytes)");
   const CtxExpand e{d_pat, d_off, k, n_left, d_lefts};
-  LAUNCH("k_ctx_expand", k_ctx_expand, dim3(flat_grid(xk + 1)), dim3(kCtxThreads), st, e, xpat, xoff, flag);
+  if (cc) LAUNCH("k_ctx_expand", k_ctx_expand<uint16_t>, dim3(flat_grid(xk + 1)), dim3(kCtxThreads), st, e, reinterpret_cast<uint16_t *>(xpat), xoff, flag);
+  else LAUNCH("k_ctx_expand", k_ctx_expand<uint8_t>, dim3(flat_grid(xk + 1)), dim3(kCtxThreads), st, e, xpat, xoff, flag);
   uint32_t flag_h = 0;
   HIP_TRY(hipMemcpyAsync(&flag_h, flag, 4, hipMemcpyDeviceToHost, st), "D2H(flag)");
   HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");        // lefts[] is on the stack
@@ -490,23 +499,28 @@ int ctx_search(const Index *h, const fmx_index *idx, const uint8_t *d_pat, const
   if (flag_h)
     return arg_fail("search_context: an empty pattern, a pattern above 65534 bytes, a byte 0 in a pattern, or offsets that do not ascend");
   HIP_TRY(ev.record(0, st), "hipEventRecord");
-  if (fold_map) {
+  if (fold_map || cc) {
     // the records are the fold search's hits: their number is known after it -- a second search when the first guess was short
     uint8_t *lead = nullptr;
     unsigned long long *rec_off = nullptr, *run_off = nullptr;
     DEV_ALLOC(mem, rec_off, 8 * (k + 1), "search_context");
-    if (per > 1) {
+    if (per > 1 && !cc) {
       DEV_ALLOC(mem, lead, xk, "search_context");
       LAUNCH("k_ctx_leads", k_ctx_leads, dim3(flat_grid(xk)), dim3(kCtxThreads), st, xk, per, lead);
     }
     FoldInfo info;
     uint64_t rcap = std::min<uint64_t>(2 * xk + 1024, kCtxMaxRecords);
-    uint64_t own_launches = 1 + (per > 1 ? 1 : 0);          // k_ctx_recut, k_ctx_leads; the fold search and the filter count their own
+    uint64_t own_launches = 1 + (per > 1 && !cc ? 1 : 0);          // k_ctx_recut, k_ctx_leads; the fold search and the filter count their own
     for (int pass = 0;; pass++) {
       if ((rc = device_room(33 * rcap + 4096, "fmx_search_context_fold_batch"))) return rc;
       DEV_ALLOC(mem, rec, sizeof(fmx_result) * rcap, "search_context");
-      if ((rc = fold_search(h, xpat, xoff, xk, fold_map, lead, per, fold_len, rec_off, rec, rcap, true, st, &info))) return rc;
-      fold_set_last(info);
+      if (cc) {
+        if ((rc = classes_search(h, xpat, xoff, xk, per, *cc->packed, cc->largest, fold_len, rec_off, rec, rcap, true, st, &info))) return rc;
+        classes_set_last(info);
+      } else {
+        if ((rc = fold_search(h, xpat, xoff, xk, fold_map, lead, per, fold_len, rec_off, rec, rcap, true, st, &info))) return rc;
+        fold_set_last(info);
+      }
       if (info.total <= rcap) break;
       if (pass || info.total > kCtxMaxRecords) {             // the variants are the filter's records: its limit holds for them
         set_error("search_context_fold: " + std::to_string(info.total) + " variants occur, at most 2^26 records reach the filter in one call");
@@ -615,14 +629,14 @@ int fmx_context_last(double *search_ms, double *chain_ms, double *filter_ms, uin
 
 // both device forms; fold_map: null (the exact search) or the 256 bytes of a checked map
 static int ctx_search_dev_form(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k, const fmx_context_opts *opts,
-                               const uint8_t *fold_map, void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream) {
+                               const uint8_t *fold_map, const CtxClasses *cc, void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream) {
   int rc = ctx_opts_check(opts);
   if (rc) return rc;
   if (!d_out_off || !n_out || !d_off || (cap && !d_out)) return arg_fail("search_context: null argument");
   if ((uint64_t)k > (1ull << 26)) return arg_fail("search_context: at most 2^26 patterns per call");
   if ((rc = ctx_handle(idx, "fmx_search_context_batch_dev"))) return rc;
   const Index *h = H(idx);
-  if (fold_map && (rc = fold_handle_check(h))) return rc;
+  if ((fold_map || cc) && (rc = fold_handle_check(h))) return rc;
   if ((rc = use_device(h))) return rc;
   hipStream_t st = (hipStream_t)stream;
   if ((rc = not_capturing(st, "fmx_search_context_batch_dev"))) return rc;
@@ -634,7 +648,7 @@ static int ctx_search_dev_form(const fmx_index *idx, const void *d_pat, const vo
   if (ends[1] > ends[0] && !d_pat) return arg_fail("search_context: the patterns are null");
   g_ctx_last = CtxLast{};
   uint64_t total = 0;
-  if ((rc = ctx_search(h, idx, static_cast<const uint8_t *>(d_pat), static_cast<const unsigned long long *>(d_off), k, ends[1] - ends[0], *opts, fold_map,
+  if ((rc = ctx_search(h, idx, d_pat, static_cast<const unsigned long long *>(d_off), k, ends[1] - ends[0], *opts, fold_map, cc,
                        FMX_FOLD_MAX_LEN,
                        static_cast<unsigned long long *>(d_out_off), static_cast<fmx_result *>(d_out), cap, st, &total))) {
     if (rc == FMX_ERR_OVERFLOW && total) *n_out = (size_t)total;
@@ -645,36 +659,43 @@ static int ctx_search_dev_form(const fmx_index *idx, const void *d_pat, const vo
 }
 
 // both host forms
-static int ctx_search_host_form(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k, const fmx_context_opts *opts,
-                                const uint8_t *fold_map, uint64_t *out_off, fmx_result *out, size_t cap, size_t *n_out) {
+static int ctx_search_host_form(const fmx_index *idx, const void *pat_, const uint64_t *off, size_t k, const fmx_context_opts *opts,
+                                const uint8_t *fold_map, const CtxClasses *cc, uint64_t *out_off, fmx_result *out, size_t cap, size_t *n_out) {
   int rc = ctx_opts_check(opts);
   if (rc) return rc;
   if (!out_off || !n_out || !off || (cap && !out)) return arg_fail("search_context: null argument");
   if ((uint64_t)k > (1ull << 26)) return arg_fail("search_context: at most 2^26 patterns per call");
+  const uint8_t *pat = static_cast<const uint8_t *>(pat_);      // (cc: uint16_t elements, `bytes` and the offsets count elements)
+  const uint16_t *el = static_cast<const uint16_t *>(pat_);
+  const uint64_t es = cc ? 2 : 1;
   uint64_t longest = 0;
   for (size_t i = 0; i < k; i++) {
     if (off[i + 1] <= off[i]) return arg_fail("search_context: an empty pattern, or offsets that do not ascend");
     longest = std::max<uint64_t>(longest, off[i + 1] - off[i]);
     if (off[i + 1] - off[i] > FMX_OCC_MAX_LEN - 1) return arg_fail("search_context: a pattern above 65534 bytes");
     if (fold_map && off[i + 1] - off[i] > FMX_FOLD_MAX_LEN - 1) return arg_fail("search_context_fold: a pattern above 254 bytes");
+    if (cc && off[i + 1] - off[i] > FMX_CLASS_MAX_ELEMS - 1) return arg_fail("search_context_classes: a pattern above 254 elements");
   }
   const uint64_t bytes = k ? off[k] - off[0] : 0;
   if (bytes && !pat) return arg_fail("search_context: the patterns are null");
-  for (uint64_t t = 0; t < bytes; t++)
-    if (pat[off[0] + t] == 0) return arg_fail("search_context: a byte 0 in a pattern");
+  for (uint64_t t = 0; t < bytes; t++) {
+    if ((cc ? el[off[0] + t] : pat[off[0] + t]) == 0) return arg_fail("search_context: a byte 0 in a pattern");
+    if (cc && el[off[0] + t] >= 256u && (uint64_t)(el[off[0] + t] - 256u) >= cc->packed->size())
+      return arg_fail("search_context_classes: an element names a class that is not in the table");
+  }
   if ((rc = ctx_handle(idx, "fmx_search_context_batch"))) return rc;
   const Index *h = H(idx);
-  if (fold_map && (rc = fold_handle_check(h))) return rc;
+  if ((fold_map || cc) && (rc = fold_handle_check(h))) return rc;
   if ((rc = use_device(h))) return rc;
   HostCall hc;
   if ((rc = hc.open())) return rc;
   const uint64_t kk = k;
-  if ((rc = device_room(bytes + 16 * (kk + 1) + 24 * (uint64_t)cap + 4096, "fmx_search_context_batch"))) return rc;
+  if ((rc = device_room(es * bytes + 16 * (kk + 1) + 24 * (uint64_t)cap + 4096, "fmx_search_context_batch"))) return rc;
   void *d_pat = nullptr;
   uint64_t *d_off = nullptr;
   unsigned long long *d_out_off = nullptr;
   fmx_result *d_out = nullptr;
-  if ((rc = hc.upload("context patterns", pat ? pat + off[0] : nullptr, bytes, "context offsets", off, k, true, &d_pat, &d_off))) return rc;
+  if ((rc = hc.upload("context patterns", pat ? pat + es * off[0] : nullptr, es * bytes, "context offsets", off, k, true, &d_pat, &d_off))) return rc;
   DEV_ALLOC(hc.mem, d_out_off, 8 * (kk + 1), "context offsets");
   DEV_ALLOC(hc.mem, d_out, sizeof(fmx_result) * (uint64_t)cap, "context runs");
   g_ctx_last = CtxLast{};
@@ -684,7 +705,7 @@ static int ctx_search_host_form(const fmx_index *idx, const uint8_t *pat, const 
     *n_out = 0;
     return FMX_OK;
   }
-  if ((rc = ctx_search(h, idx, static_cast<const uint8_t *>(d_pat), reinterpret_cast<const unsigned long long *>(d_off), kk, bytes, *opts, fold_map,
+  if ((rc = ctx_search(h, idx, d_pat, reinterpret_cast<const unsigned long long *>(d_off), kk, bytes, *opts, fold_map, cc,
                        (uint32_t)std::min<uint64_t>(longest + 1, FMX_FOLD_MAX_LEN),
                        d_out_off, d_out, cap, hc.own.s, &total))) {
     if (rc == FMX_ERR_OVERFLOW && total) *n_out = (size_t)total;
@@ -697,12 +718,12 @@ static int ctx_search_host_form(const fmx_index *idx, const uint8_t *pat, const 
 
 int fmx_search_context_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k, const fmx_context_opts *opts,
                                  void *d_out_off, void *d_out, size_t cap, size_t *n_out, void *stream) {
-  return ctx_search_dev_form(idx, d_pat, d_off, k, opts, nullptr, d_out_off, d_out, cap, n_out, stream);
+  return ctx_search_dev_form(idx, d_pat, d_off, k, opts, nullptr, nullptr, d_out_off, d_out, cap, n_out, stream);
 }
 
 int fmx_search_context_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k, const fmx_context_opts *opts,
                              uint64_t *out_off, fmx_result *out, size_t cap, size_t *n_out) {
-  return ctx_search_host_form(idx, pat, off, k, opts, nullptr, out_off, out, cap, n_out);
+  return ctx_search_host_form(idx, pat, off, k, opts, nullptr, nullptr, out_off, out, cap, n_out);
 }
 
 int fmx_search_context_fold_batch_dev(const fmx_index *idx, const void *d_pat, const void *d_off, size_t k,
@@ -711,7 +732,7 @@ int fmx_search_context_fold_batch_dev(const fmx_index *idx, const void *d_pat, c
   uint8_t map[256];
   int rc = fold_map_check(fold, map);
   if (rc) return rc;
-  return ctx_search_dev_form(idx, d_pat, d_off, k, ctx, map, d_out_off, d_out, cap, n_out, stream);
+  return ctx_search_dev_form(idx, d_pat, d_off, k, ctx, map, nullptr, d_out_off, d_out, cap, n_out, stream);
 }
 
 int fmx_search_context_fold_batch(const fmx_index *idx, const uint8_t *pat, const uint64_t *off, size_t k,
@@ -720,7 +741,27 @@ int fmx_search_context_fold_batch(const fmx_index *idx, const uint8_t *pat, cons
   uint8_t map[256];
   int rc = fold_map_check(fold, map);
   if (rc) return rc;
-  return ctx_search_host_form(idx, pat, off, k, ctx, map, out_off, out, cap, n_out);
+  return ctx_search_host_form(idx, pat, off, k, ctx, map, nullptr, out_off, out, cap, n_out);
+}
+
+int fmx_search_context_classes_batch_dev(const fmx_index *idx, const void *d_el, const void *d_el_off, size_t k,
+                                         const fmx_context_opts *ctx, const fmx_class_table *tab, void *d_out_off, void *d_out,
+                                         size_t cap, size_t *n_out, void *stream) {
+  std::vector<ClassRec> packed;
+  CtxClasses cc{&packed, 1};
+  int rc = classes_table_check(tab, &packed, &cc.largest);
+  if (rc) return rc;
+  return ctx_search_dev_form(idx, d_el, d_el_off, k, ctx, nullptr, &cc, d_out_off, d_out, cap, n_out, stream);
+}
+
+int fmx_search_context_classes_batch(const fmx_index *idx, const uint16_t *el, const uint64_t *el_off, size_t k,
+                                     const fmx_context_opts *ctx, const fmx_class_table *tab, uint64_t *out_off, fmx_result *out,
+                                     size_t cap, size_t *n_out) {
+  std::vector<ClassRec> packed;
+  CtxClasses cc{&packed, 1};
+  int rc = classes_table_check(tab, &packed, &cc.largest);
+  if (rc) return rc;
+  return ctx_search_host_form(idx, el, el_off, k, ctx, nullptr, &cc, out_off, out, cap, n_out);
 }
 
 }  // extern "C"

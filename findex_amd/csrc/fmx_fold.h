@@ -34,4 +34,11 @@ int fold_search(const Index *h, const void *d_pat, const void *d_off, uint64_t k
 
 void fold_set_last(const FoldInfo &info);
 
+// The ordering step of fold_search, which the class search (fmx_classes.hip) takes as it is: `rows` staged hits
+// {group | len << 32, sp, ep} into d_out by group, then sp, then (tb == 1) the lead bit, and the CSR offsets of the `groups`
+// groups into d_out_off; rows == 0 writes the offsets alone.  Enqueues on `st`; its sort space comes from `mem`.
+constexpr int kFoldRowBits = 38;                // rows are below 2^38, groups below 2^26: the sort key
+int fold_order(DevMem &mem, unsigned long long *stage, uint64_t rows, uint64_t groups, int tb, void *d_out_off, void *d_out,
+               hipStream_t st);
+
 }  // namespace fmx

@@ -30,7 +30,7 @@ namespace fmx {
 constexpr int kFoThreads = 256;                // four waves: four patterns per workgroup
 constexpr int kFoWaves = kFoThreads / 64;
 constexpr uint32_t kFoPush = FMX_FOLD_MAX_CLASS - 1;      // stack entries per pattern byte at the most
-constexpr int kFoRowBits = 38;                 // rows are below 2^38, patterns below 2^26: the sort key
+constexpr int kFoRowBits = kFoldRowBits;       // rows are below 2^38, patterns below 2^26: the sort key
 
 struct FoEntry {
   uint64_t sp, ep, i;
@@ -271,21 +271,26 @@ int fold_search(const Index *h, const void *d_pat, const void *d_off, uint64_t k
   }
   if (info->total > cap) return FMX_OK;                      // the caller reports the overflow; nothing is ordered
   const uint64_t rows = info->total;
+  if ((rc = fold_order(mem, stage, rows, groups, tb, d_out_off, d_out, st))) return rc;
+  if (rows) HIP_TRY(ev.record(2, st), "hipEventRecord");
+  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");  // the temporaries go when this returns
+  if (rows) info->sort_ms = ev.ms(1, 2);
+  return FMX_OK;
+}
+
+int fold_order(DevMem &mem, unsigned long long *stage, uint64_t rows, uint64_t groups, int tb, void *d_out_off, void *d_out,
+               hipStream_t st) {
   unsigned long long *out_off = static_cast<unsigned long long *>(d_out_off);
   if (rows == 0) {
     HIP_TRY(launch_csr_off(nullptr, 0, groups, kFoRowBits + tb, out_off, st), "k_fold_off");
-    HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");
     return FMX_OK;
   }
   SortSpace ws;
-  if ((rc = ws.alloc(mem, rows, "fold sort"))) return rc;
+  if (const int rc = ws.alloc(mem, rows, "fold sort")) return rc;
   LAUNCH("k_fold_keys", k_fold_keys, dim3(flat_grid(rows)), dim3(256), st, stage, rows, tb, ws.keys(), ws.vals());
   HIP_TRY(ws.sort(rows, kFoRowBits + tb + std::min(26 - tb, bits_for(groups - 1)), st), "radix sort");      // group ids 0 .. groups - 1
   HIP_TRY(launch_gather3(stage, ws.vals(), rows, static_cast<unsigned long long *>(d_out), st), "k_fold_gather");
   HIP_TRY(launch_csr_off(ws.keys(), rows, groups, kFoRowBits + tb, out_off, st), "k_fold_off");
-  HIP_TRY(ev.record(2, st), "hipEventRecord");
-  HIP_TRY(hipStreamSynchronize(st), "hipStreamSynchronize");  // the temporaries go when this returns
-  info->sort_ms = ev.ms(1, 2);
   return FMX_OK;
 }
 

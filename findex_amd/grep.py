@@ -3,6 +3,7 @@
     python -m findex_amd.grep BASE REGEX [REGEX ..] [--mode all|longest|disjoint] [--max-per N] [--max-steps N] [-C BYTES] [--count]
                                                     [-n] [-A N] [-B N] [--context-lines N] [-c] [-l] [--max-line BYTES]
                                                     [-v] [--and REGEX ..] [--not REGEX ..] [--near N | --same-file] [-w] [-i]
+                                                    [--unicode-case]
 
 BASE names BASE.bwt / BASE.aux / BASE.docs as `python -m findex_amd.index --dir D --out BASE` writes them.  One line per
 match, `name:raw_off:text`, regex by regex in (file, offset) order; -C BYTES shows that many bytes of the file around the
@@ -12,7 +13,10 @@ to a match are not 0-9 A-Z a-z _ or 0x80 .. 0xFF, or the file ends there; it app
 included.  -i ignores ASCII case: every regex of the call, --and / --not included, is read as Python's re reads it under
 re.IGNORECASE | re.ASCII (findex_amd.regex.fold_regex; a construct re reads differently, such as an unquoted ^ or {, is
 refused) -- but for \\w, \\d and '.', which keep the meaning they have without -i: the bytes A .. y (and z beside them, the
-image of Z), 0 .. 8 and 2 .. 254, not re's classes; it combines with -w.
+image of Z), 0 .. 8 and 2 .. 254, not re's classes; it combines with -w.  --unicode-case reads the regexes as UTF-8 and
+ignores the case of every code point, as Python's re does on str under re.IGNORECASE (findex_amd.regex.fold_regex_unicode: `über`
+finds Über, `k` the Kelvin sign, `σ` the final sigma); a set may hold ASCII only and '.' is one byte; it combines with -w, -n and
+--and / --not.
 
 By lines (HipCorpusSearcher.grep_lines; any of the flags below): -n prints `name:line_no:line`, one line of output per matching
 line, regex by regex in (file, line) order; -A N / -B N / --context-lines N add that many lines after / before / around, as
@@ -63,6 +67,7 @@ def parser():
     near.add_argument("--same-file", action="store_true", help="--and / --not look at the whole file")
     ap.add_argument("-w", "--word-regexp", dest="words", action="store_true", help="only matches that stand as whole words")
     ap.add_argument("-i", "--ignore-case", action="store_true", help="ignore ASCII case in every regex of the call")
+    ap.add_argument("--unicode-case", action="store_true", help="ignore the case of every code point (UTF-8) in every regex of the call")
     ap.add_argument("--little-endian", action="store_true")
     ap.add_argument("--device", type=int, default=0)
     return ap
@@ -71,7 +76,9 @@ def parser():
 def flags_of(a):
     """The keyword arguments -w and -i add to a grep call; none when neither is given."""
     kw = {"words": True} if getattr(a, "words", False) else {}
-    if getattr(a, "ignore_case", False):
+    if getattr(a, "unicode_case", False):
+        kw["ignore_case"] = "unicode"
+    elif getattr(a, "ignore_case", False):
         kw["ignore_case"] = True
     return kw
 

@@ -2,6 +2,7 @@
 
     python -m findex_amd.rank BASE "words of a query" ["another query" ..] [--top K] [--all] [-w] [-i] [--k1 X] [--b X] [--device D]
                                                                             [--little-endian] [--snippets [W]] [--explain]
+                                                                            [--unicode-case [--ignore-marks]]
 
 BASE names BASE.bwt / BASE.aux / BASE.docs as `python -m findex_amd.index --dir D --out BASE` writes them.  Every positional
 argument is one query, split on white space into its terms.  Without -w terms are SUBSTRINGS, as everywhere in this index:
@@ -10,7 +11,10 @@ not 0-9 A-Z a-z _ or 0x80 .. 0xFF, or the file ends there (HipFMSearcher.search_
 (HipCorpusSearcher.rank, fmx_corpus_rank: scored and cut to the best K on the device).  Output: one line per hit,
 `score<TAB>file`, best first; the queries' blocks are separated by a blank line.  --all keeps only files that hold every term of
 the query.  -i / --ignore-case counts a term in every ASCII case spelling that occurs (HipFMSearcher.search_fold_batch: `error` finds
-Error and ERROR too); it combines with -w.  --snippets [W] prints under every hit `<TAB>offset<TAB>text`: the file's window of W
+Error and ERROR too); it combines with -w.  --unicode-case reads the terms as UTF-8 and counts a term in every case spelling
+of its code points that occurs, classes of several bytes included (HipFMSearcher.search_classes_batch: `über` finds Über, `kelvin`
+the Kelvin sign, `miss` the long s); --ignore-marks adds the precomposed accented forms of every letter (`cafe` finds café).  It
+combines with -w; with --snippets or --explain only where every spelling of a term has one length.  --snippets [W] prints under every hit `<TAB>offset<TAB>text`: the file's window of W
 stream bytes (default 160) that holds the most valuable set of the query's terms, by the ranking's weights, read back from the
 index (HipCorpusSearcher.rank_passages, fmx_corpus_passages); bytes below 0x20 are shown as a space.  --explain prints under every
 hit `<TAB>term=tf ..`: how often each term of the query occurs in the file, the counts the score was computed from.
@@ -28,6 +32,9 @@ def parser():
     ap.add_argument("--all", dest="all_", action="store_true", help="only files that hold every term of the query")
     ap.add_argument("-w", "--words", action="store_true", help="a term counts only where it stands as a whole word")
     ap.add_argument("-i", "--ignore-case", action="store_true", help="a term counts in every ASCII case spelling")
+    ap.add_argument("--unicode-case", action="store_true",
+                    help="terms are UTF-8; a term counts in every case spelling of its code points (K / k / the Kelvin sign)")
+    ap.add_argument("--ignore-marks", action="store_true", help="with --unicode-case: precomposed accented forms of a letter count too")
     ap.add_argument("--snippets", type=int, nargs="?", const=160, default=None, metavar="W",
                     help="under every hit its best passage of W stream bytes (default 160): <TAB>offset<TAB>text")
     ap.add_argument("--explain", action="store_true", help="under every hit the count of every term in the file: <TAB>term=tf ..")
@@ -38,10 +45,25 @@ def parser():
     return ap
 
 
-def split_queries(queries):
-    """Each query string split on white space into its terms, as bytes (the file system's encoding, like the names)."""
+def split_queries(queries, utf8=False):
+    """Each query string split on white space into its terms, as bytes (the file system's encoding, like the names; utf8: UTF-8,
+    a byte the command line could not decode kept as it is)."""
     import os
+    if utf8:
+        return [[w.encode("utf-8", "surrogateescape") for w in q.split()] for q in queries]
     return [[os.fsencode(w) for w in q.split()] for q in queries]
+
+
+def flags_of(a):
+    """The keyword arguments of HipCorpusSearcher.rank / rank_passages that the parsed arguments ask for."""
+    kw = {"words": True} if a.words else {}
+    if a.unicode_case:
+        kw["ignore_case"] = "unicode"
+        if a.ignore_marks:
+            kw["ignore_marks"] = True
+    elif a.ignore_case:
+        kw["ignore_case"] = True
+    return kw
 
 
 def render(names, off, doc, score):
@@ -80,13 +102,13 @@ def main(argv=None):
         parser().error("--top is 1 .. 1024")
     if a.snippets is not None and not 1 <= a.snippets < (1 << 32):
         parser().error("--snippets is 1 .. 2^32 - 1")
-    queries = split_queries(a.query)
+    if a.ignore_marks and not a.unicode_case:
+        parser().error("--ignore-marks goes with --unicode-case")
+    queries = split_queries(a.query, utf8=a.unicode_case)
     from .corpus import HipCorpusSearcher
     cs = HipCorpusSearcher.open(a.base, bigEndian=not a.little_endian, device=a.device)
     try:
-        kw = {"words": True} if a.words else {}
-        if a.ignore_case:
-            kw["ignore_case"] = True
+        kw = flags_of(a)
         out = sys.stdout.buffer
         if a.snippets is not None or a.explain:
             off, doc, score, _, _, psg, tf = cs.rank_passages(queries, top=a.top, window=a.snippets or 160, k1=a.k1, b=a.b,

@@ -118,6 +118,102 @@ def fold_regex(re, fold):
     return "".join(out)
 
 
+def _byte_alternation(strings):
+    """Byte strings as a parenthesised alternation in re2post's syntax (Latin-1), in the order given: a letter or digit stands as
+    it is, every other byte backslash-quoted.  The parentheses make a quantifier bind the whole character."""
+    quote = lambda v: chr(v) if v < 128 and chr(v).isalnum() else "\\" + chr(v)
+    return "(" + "|".join("".join(quote(v) for v in m) for m in strings) + ")"
+
+
+def fold_regex_unicode(re, ignore_marks=False):
+    """The regex `re` (a str: Unicode characters in re2post's syntax) rewritten, as a string of Latin-1 characters -- the bytes
+    of UTF-8 -- for REParser.createNFA, so that it matches what Python's re matches on str under re.IGNORECASE
+    (unicode_fold.case_classes(); ignore_marks: mark_classes()).  A character outside a set becomes a parenthesised
+    alternation of the UTF-8 byte strings of its class's members -- of its own bytes when it has no class of two -- so that a
+    quantifier binds the character, not its last byte.  A set may hold ASCII only (ValueError for anything else); it becomes
+    the alternation of its members' classes, members of several bytes included ([a-k] holds the Kelvin sign).  \\w, which is
+    A .. y here, gets z and the members of several bytes beside it; \\d and '.' stay as they are: '.' is one BYTE (2 .. 254), not
+    one code point.  Everything fold_regex refuses is refused: an unquoted ^ $ { }, a set that begins with ^ or is empty, a
+    quoted letter or digit other than \\w and \\d.  Syntax errors are left for the compiler to report."""
+    from . import unicode_fold
+    if not isinstance(re, str):
+        raise ValueError("fold_regex_unicode takes a str")
+    classes = unicode_fold.mark_classes() if ignore_marks else unicode_fold.case_classes()
+
+    def refuse(what):
+        raise ValueError("ignore_case: %s in %r is read differently by Python's re -- quote it or rewrite it" % (what, re))
+
+    def members(c):
+        return [chr(m).encode("utf-8") for m in classes.get(c, (c,))]
+
+    def interval(token, start, end):
+        extra = sorted({m for c in range(start, end) for m in members(c) if not (len(m) == 1 and start <= m[0] < end)})
+        return "(" + token + "|" + _byte_alternation(extra)[1:] if extra else token
+
+    out, i, n = [], 0, len(re)
+    while i < n:
+        ch = re[i]
+        if ch == "\\":
+            if i + 1 >= n:
+                out.append(ch)
+                break
+            q = re[i + 1]
+            if q in "wd":
+                out.append(interval(ch + q, *((65, 122) if q == "w" else (48, 57))))
+            else:
+                if q.isascii() and q.isalnum():
+                    refuse("\\" + q)
+                out.append(_byte_alternation(members(ord(q))))
+            i += 2
+        elif ch == "[":
+            got, last, in_interval, quoted, j = set(), None, False, False, i + 1
+            if j < n and re[j] == "^":
+                refuse("a set that begins with ^")
+            ok = True
+            while j < n:
+                m = re[j]
+                if not quoted and m == "\\":
+                    quoted = True
+                elif not quoted and m == "-":
+                    in_interval = True
+                elif not quoted and m == "]":
+                    break
+                else:
+                    if quoted and m.isascii() and m.isalnum():
+                        refuse("\\" + m + " inside a set")
+                    quoted = False
+                    if ord(m) > 127:
+                        raise ValueError("ignore_case=\"unicode\": a set may hold ASCII only, %r in %r" % (m, re))
+                    if in_interval:
+                        if last is None or last + 1 > ord(m):
+                            ok = False
+                            break
+                        got.update(range(last + 1, ord(m) + 1))
+                        in_interval = False
+                    else:
+                        got.add(ord(m))
+                    last = ord(m)
+                j += 1
+            if not ok or j >= n or in_interval or quoted:      # re2post's syntax error: as it stands, for the compiler to report
+                out.append(re[i:].encode("utf-8").decode("latin-1"))
+                break
+            if not got:
+                refuse("an empty set")
+            out.append(_byte_alternation(sorted({x for m in got for x in members(m)})))
+            i = j + 1
+        elif ch == "." or ch in "()|*+?":
+            out.append(ch)
+            i += 1
+        else:
+            if ch in "^${}":
+                refuse("an unquoted " + ch)
+            if 0xD800 <= ord(ch) <= 0xDFFF:
+                raise ValueError("a surrogate in %r" % re)
+            out.append(_byte_alternation(members(ord(ch))))
+            i += 1
+    return "".join(out)
+
+
 class PostfixRe:
     """REParser.PostfixRe (re2.scala:49): the postfix token list, kept as the source string the
     library re-parses; str() gives re2poststr."""

@@ -666,13 +666,17 @@ class HipFMSearcher:
     # ---- context: rows whose neighbouring text bytes are in a class -- whole words (fmx_context_filter)
     CTX_START = _lib.FMX_CTX_START
 
-    def search_context_batch(self, pat, off, left, right, cap=None, fold=None):
+    def search_context_batch(self, pat, off, left, right, cap=None, fold=None, classes=None):
         """fmx_search_context_batch: the patterns as search_batch takes them (strings of reverse(text)), left / right = the byte
         values (bytes; 0 = the text begins / ends there) that may stand in front of / behind an occurrence in the TEXT.
         -> (off[k + 1], runs): pattern i's rows are the disjoint ranges runs[off[i]:off[i + 1]], a RESULT array {i, length,
         sp, ep} in ascending sp.  cap=None: a counting call sizes the buffer.  fold (a fold map, e.g. ASCII_FOLD):
-        fmx_search_context_fold_batch -- every variant of a pattern under the map, the neighbours still compared as they are."""
-        pat = np.ascontiguousarray(pat, dtype=np.uint8)
+        fmx_search_context_fold_batch -- every variant of a pattern under the map, the neighbours still compared as they are.
+        classes (a class table (cls_off, mem_off, mem_bytes); pat then holds uint16 elements as search_classes_batch takes them):
+        fmx_search_context_classes_batch -- every spelling under the table; a run's length is that of its spelling."""
+        if fold is not None and classes is not None:
+            raise ValueError("fold and classes do not combine")
+        pat = np.ascontiguousarray(pat, dtype=np.uint16 if classes is not None else np.uint8)
         off = np.ascontiguousarray(off, dtype=np.uint64)
         k = off.size - 1
         if k < 0:
@@ -684,6 +688,12 @@ class HipFMSearcher:
             fopts = self._fold_opts(fold)
             args = (self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts), ctypes.byref(fopts))
             return self._csr_hits(self._L.fmx_search_context_fold_batch, args, k, self.RESULT, cap)
+        if classes is not None:
+            tab, keep = self._class_table(classes)
+            args = (self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts), ctypes.byref(tab))
+            out = self._csr_hits(self._L.fmx_search_context_classes_batch, args, k, self.RESULT, cap)
+            del keep
+            return out
         args = (self._h, _ptr(pat), _ptr(off), k, ctypes.byref(opts))
         return self._csr_hits(self._L.fmx_search_context_batch, args, k, self.RESULT, cap)
 
@@ -719,22 +729,34 @@ class HipFMSearcher:
         _lib.check(self._L.fmx_context_last(*[ctypes.byref(x) for x in t], ctypes.byref(rows), ctypes.byref(runs)))
         return tuple(float(x.value) for x in t) + (int(rows.value), int(runs.value))
 
-    def search_words(self, pats, word=WORD_BYTES, cap=None, fold=None):
+    def search_words(self, pats, word=WORD_BYTES, cap=None, fold=None, classes=None, keep=None):
         """The whole-word occurrences of text strings `pats` (bytes each): search_context_batch over their reverses with the
-        boundary class of `word` on both sides.  -> (off[k + 1], runs).  fold: a fold map the strings are matched under."""
+        boundary class of `word` on both sides.  -> (off[k + 1], runs).  fold: a fold map the strings are matched under.
+        classes ("unicode", "marks", or a mapping code point -> members as unicode_fold.class_table takes): the strings are read
+        as UTF-8 and matched in every spelling under the classes that occurs (unicode_table; keep: its filter on members)."""
         pats = [bytes(q) for q in pats]
+        if classes is not None:
+            if fold is not None:
+                raise ValueError("fold and classes do not combine")
+            el, el_off, table = self.unicode_table(pats, classes == "marks", keep, None if isinstance(classes, str) else classes)
+            cls = boundary_class(word)
+            return self.search_context_batch(el, el_off, cls, cls, cap, classes=table)
         off = np.zeros(len(pats) + 1, dtype=np.uint64)
         np.cumsum([len(q) for q in pats], out=off[1:])
         pat = np.frombuffer(b"".join(q[::-1] for q in pats), dtype=np.uint8)
         cls = boundary_class(word)
         return self.search_context_batch(pat, off, cls, cls, cap, fold=fold)
 
-    def locate_words(self, q, max_hits=None, word=WORD_BYTES, fold=None):
+    def locate_words(self, q, max_hits=None, word=WORD_BYTES, fold=None, classes=None):
         """Sorted text offsets of the whole-word occurrences of q -- of at most max_hits rows.  fold: a fold map q is matched
-        under."""
+        under.  classes (as search_words takes it): -> (offsets, lengths) sorted by both, every occurrence with the bytes of
+        its spelling."""
         q = bytes(q)
         if not q:
             raise ValueError("empty pattern")
+        if classes is not None:
+            _, runs = self.search_words([q], word, classes=classes)
+            return self.locate_spellings(runs, max_hits)
         _, runs = self.search_words([q], word, fold=fold)
         sp, ep = runs["sp"].copy(), runs["ep"].copy()
         if max_hits is not None:
@@ -801,6 +823,105 @@ class HipFMSearcher:
                 left -= int(ep[j]) - int(sp[j])
         _, pos = self.locate_intervals(sp, ep)
         return np.sort(self.text_offsets(pos, self.n, len(q)))
+
+    # ---- string classes: a pattern position as a set of byte strings, UTF-8 case folding (fmx_search_classes_batch)
+    @staticmethod
+    def _class_table(table):
+        """fmx_class_table of (cls_off, mem_off, mem_bytes) -- None: no classes -- and the arrays it points into."""
+        if table is None:
+            return None, ()
+        cls_off, mem_off, mem_bytes = table
+        keep = (np.ascontiguousarray(cls_off, dtype=np.uint64), np.ascontiguousarray(mem_off, dtype=np.uint64),
+                np.ascontiguousarray(mem_bytes, dtype=np.uint8))
+        if keep[0].size < 1 or keep[1].size < 1:
+            raise ValueError("a class table has at least one offset in cls_off and in mem_off")
+        tab = _lib.fmx_class_table()
+        tab.cls_off, tab.mem_off, tab.mem_bytes = (a.ctypes.data for a in keep)
+        tab.n_classes = keep[0].size - 1
+        return tab, keep
+
+    def search_classes_batch(self, el, off, table, cap=None):
+        """fmx_search_classes_batch: patterns of uint16 elements (< 256: that byte, else class element - 256 of the table) with
+        offsets off[k + 1]; table = (cls_off, mem_off, mem_bytes) or None.  Elements and member bytes are given as search_batch
+        takes a pattern: for a text string, reversed (unicode_fold.class_table does both).  -> (off[k + 1], hits): pattern q's
+        hits are hits[off[q]:off[q + 1]], a RESULT array {q, bytes of the spelling, sp, ep} by ascending sp -- disjoint row
+        intervals.  cap=None: a counting call sizes the buffer."""
+        el = np.ascontiguousarray(el, dtype=np.uint16)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        k = max(off.size - 1, 0)
+        tab, keep = self._class_table(table)
+        args = (self._h, _ptr(el), _ptr(off), k, ctypes.byref(tab) if tab is not None else None)
+        out = self._csr_hits(self._L.fmx_search_classes_batch, args, k, self.RESULT, cap)
+        del keep
+        return out
+
+    def search_classes(self, elements, table):
+        """One pattern of elements: the list of (bytes of the spelling, sp, ep) of its spellings that occur, by ascending sp."""
+        el = np.ascontiguousarray(elements, dtype=np.uint16).reshape(-1)
+        _, hits = self.search_classes_batch(el, np.array([0, el.size], dtype=np.uint64), table)
+        return [(int(h["len"]), int(h["sp"]), int(h["ep"])) for h in hits]
+
+    def search_classes_batch_dev(self, d_el, d_off, k, d_out_off, d_out, cap, table, stream=0):
+        """fmx_search_classes_batch_dev: device pointers (u16 elements, u64 offsets[k + 1], u64 out_off[k + 1], 24-byte records),
+        the table in host memory as search_classes_batch takes it; allocates and synchronises.  -> the exact number of hits
+        (FMX_ERR_OVERFLOW is raised when it exceeds cap)."""
+        tab, keep = self._class_table(table)
+        n_out = ctypes.c_size_t()
+        _lib.check(self._L.fmx_search_classes_batch_dev(self._h, _dp(d_el), _dp(d_off), int(k), ctypes.byref(tab) if tab is not None else None,
+                                                        _dp(d_out_off), _dp(d_out), int(cap), ctypes.byref(n_out), _dp(stream)))
+        del keep
+        return int(n_out.value)
+
+    def classes_last(self):
+        """fmx_classes_last: (search kernel ms, ordering ms, backward steps, rank-dictionary requests) of this thread's last
+        class search."""
+        a, b, c, d = ctypes.c_double(), ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint64()
+        _lib.check(self._L.fmx_classes_last(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
+        return float(a.value), float(b.value), int(c.value), int(d.value)
+
+    def unicode_table(self, patterns, ignore_marks=False, keep=None, classes=None):
+        """unicode_fold.class_table of text strings under UTF-8 case folding (ignore_marks: precomposed accented letters too),
+        pruned for this index: the distinct members are searched once with search_batch, and those that do not occur -- or that
+        `keep` (member bytes -> bool) turns down -- are dropped.  -> (el, el_off, (cls_off, mem_off, mem_bytes))."""
+        from . import unicode_fold
+        if classes is None:
+            classes = unicode_fold.mark_classes() if ignore_marks else unicode_fold.case_classes()
+        members = [m for m in unicode_fold.members_of(patterns, classes) if keep is None or keep(m)]
+        occurring = set()
+        if members:
+            off = np.zeros(len(members) + 1, dtype=np.uint64)
+            np.cumsum([len(m) for m in members], out=off[1:])
+            sp, ep = self.search_batch(np.frombuffer(b"".join(m[::-1] for m in members), dtype=np.uint8), off)
+            occurring = {m for m, a, b in zip(members, sp.tolist(), ep.tolist()) if a < b}
+        el, el_off, cls_off, mem_off, mem_bytes = unicode_fold.class_table(patterns, classes, occurring)
+        return el, el_off, (cls_off, mem_off, mem_bytes)
+
+    def locate_classes(self, q, max_hits=None, ignore_marks=False):
+        """Sorted text offsets of the occurrences of the text string q (raw bytes, read as UTF-8) in every case spelling that
+        occurs -- of at most max_hits rows, taken in row order.  -> (offsets, lengths): a spelling may be longer or shorter
+        than q (k / U+212A), so every occurrence comes with its bytes."""
+        q = bytes(q)
+        if not q:
+            raise ValueError("empty pattern")
+        el, el_off, table = self.unicode_table([q], ignore_marks)
+        _, hits = self.search_classes_batch(el, el_off, table)
+        return self.locate_spellings(hits, max_hits)
+
+    def locate_spellings(self, hits, max_hits=None):
+        """Where the strings of RESULT records {.., len, sp, ep} of different lengths begin in the indexed text: the rows located
+        (at most max_hits of them, taken in record order) and each position worked out with its record's own len.
+        -> (offsets, lengths), sorted by both."""
+        sp, ep = hits["sp"].copy(), hits["ep"].copy()
+        if max_hits is not None:
+            left = int(max_hits)
+            for j in range(sp.size):
+                ep[j] = min(int(ep[j]), int(sp[j]) + left)
+                left -= int(ep[j]) - int(sp[j])
+        off, pos = self.locate_intervals(sp, ep)
+        lens = np.repeat(hits["len"].astype(np.uint64), np.diff(off.astype(np.int64)))
+        at = (np.uint64(self.n - 1) - pos - lens).astype(np.uint64) if pos.size else pos.astype(np.uint64)
+        order = np.lexsort((lens, at))
+        return at[order], lens[order]
 
     def _finditer_words(self, regexes, word, mode, max_steps, max_per, lineOnly, corpus, match_cap, occ_cap):
         """finditer(words=True): one batch of 2k.  Regex i becomes (cls)(re) -- cls = the boundary bytes >= 1 that occur in the
@@ -873,13 +994,14 @@ class HipFMSearcher:
         every regex is rewritten by regex.fold_regex under ASCII_FOLD and compiled by REParser.createNFA (ReTree has no case
         for a set next to a group), so that it is read as Python's re reads it under re.IGNORECASE | re.ASCII -- but for \\w,
         \\d and '.', which keep re2post's meaning (the bytes A .. y, 0 .. 8 and 2 .. 254; \\w gets z, the image of Z, beside it);
-        a construct re reads differently is refused with ValueError."""
+        a construct re reads differently is refused with ValueError.  ignore_case="unicode" (regex strings as str): rewritten by
+        regex.fold_regex_unicode instead -- UTF-8 case folding, a character as the alternation of its class's byte strings."""
         import torch
-        from .regex import CompiledRegexes, NFA, RegexBatch, ReTree, fold_regex
+        from .regex import CompiledRegexes, NFA, RegexBatch, ReTree, fold_regex, fold_regex_unicode
         if ignore_case:
             if isinstance(regexes, (RegexBatch, CompiledRegexes)):
                 raise ValueError("finditer(ignore_case=True) takes regex strings: it rewrites each before it is compiled")
-            regexes = [fold_regex(r, ASCII_FOLD) for r in regexes]
+            regexes = [fold_regex_unicode(r) if ignore_case == "unicode" else fold_regex(r, ASCII_FOLD) for r in regexes]
             if not words:
                 regexes = RegexBatch(self, [NFA(_NfaSource(r, lineOnly)) for r in regexes])
         if words:

@@ -1366,6 +1366,76 @@ int fmx_search_context_fold_batch_dev(const fmx_index *idx, const void *d_pat, c
                                       size_t cap, size_t *n_out, void *stream);
 int fmx_fold_last(double *search_ms, double *sort_ms, uint64_t *steps, uint64_t *requests);
 
+/* ---- string classes: literal search where a pattern position stands for a set of byte strings of different lengths (UTF-8
+ * case folding: {K, k, U+212A}, {S, s, U+017F}).  Beyond the reference.  DESIGN.md 30.
+ * A CLASS TABLE (fmx_class_table, host memory in both forms of the call) holds n_classes classes: the members of class c are
+ * members cls_off[c] .. cls_off[c + 1] - 1, and member j is the bytes mem_bytes[mem_off[j] .. mem_off[j + 1]).  cls_off[0] ==
+ * mem_off[0] == 0.  The table is VALID when every member has 1 .. FMX_CLASS_MAX_MEMBER_LEN bytes and no byte 0, a class has
+ * 1 .. FMX_CLASS_MAX_MEMBERS members, the members of a class are distinct and none is a prefix of another, n_classes <=
+ * FMX_CLASS_MAX_CLASSES, and flags and reserved are 0.  Anything else is FMX_ERR_ARG before the device is touched, with the
+ * offending class in the message.  tab == NULL is the empty table (every element must be a literal then).
+ * A PATTERN is a sequence of uint16_t ELEMENTS, pattern i being el[el_off[i] .. el_off[i + 1]): an element < 256 is that
+ * literal byte, an element >= 256 is class (element - 256), which must be in the table (the host form refuses another one
+ * before the device is touched; the device form's kernel skips the pattern and the call returns FMX_ERR_ARG after the launch).
+ * Patterns and members are strings of s, as fmx_search_batch takes them: elements are matched last first, and a member's
+ * bytes last first.
+ * A HIT of pattern P of e elements is a byte string Q = m_1 m_2 .. m_e, m_j being P's j-th literal byte or a member of P's j-th
+ * class, for which the reference's search(Q) loop (findex.scala:15-31) ends with sp < ep.  It is reported as fmx_result
+ * {group = pattern, len = the bytes of Q, sp, ep} with (sp, ep) exactly what fmx_search_batch returns for Q.
+ *  - Distinct hits of one pattern have disjoint intervals: two spellings first differ inside two members of which neither is
+ *    a prefix of the other, so neither spelling is a prefix of the other and no suffix of s begins with both.  Hence
+ *    "ascending sp" is a total order and the same input gives the same bytes on every run.  (Members are strings of s: for
+ *    strings of the text, which a caller reverses, the rule reads "none is a suffix of another".  The UTF-8 encodings of
+ *    distinct code points satisfy both.)
+ *  - A literal element is a plain step of the exact search with all its quirks, byte 0 included.
+ *  - A pattern of literals only has fmx_search_batch's hit, and the call makes exactly its steps.
+ *  - A table made of a valid fold map (every class its single-byte members) gives fmx_search_fold_batch's offsets and records.
+ *  - An empty pattern has the one hit (0, n) with len 0.
+ * Only spellings that occur are followed; a member's bytes are stepped one after the other and the member dies at its first
+ * empty interval.  On a node of one row only members whose LAST byte (the first one stepped) equals BWT'[sp] are stepped (none
+ * on the EOF row).
+ * A pattern has at most FMX_CLASS_MAX_ELEMS elements: the host form refuses a longer one, the device form's kernel skips it
+ * and raises a flag, and the call returns FMX_ERR_ARG after the launch with no hits written and *n_out untouched.
+ * Results, capacity, the counting call, FMX_ERR_OVERFLOW with the EXACT total, k <= 2^26, cap < 2^32, FMX_ERR_UNSUPPORTED for
+ * fmx_open_block handles and n >= 2^38, the refusal under a stream capture (decided first), the order of the refusals and the
+ * counters are fmx_search_fold_batch's.  Temporaries: 24 cap bytes of staging, 24 bytes per hit of sort keys and values, the
+ * counters, 128 bytes per class, and per resident wave a stack of (largest class of the table - 1) entries of 24 bytes per
+ * element of the longest pattern (the device form: FMX_CLASS_MAX_ELEMS), checked against the free device memory first
+ * (FMX_ERR_NOMEM with the need in the message).  The rank dictionary only; no derived table is built or used.
+ * Of cls_off only [cls_off[c], cls_off[c + 1]) is read per class and of mem_off the entries those name: the arrays' real sizes
+ * are the caller's word, and a gap or an overlap between two classes is taken as it stands.  The sort space of the ordering
+ * step is allocated once the hits are counted (FMX_ERR_NOMEM from that allocation).
+ * fmx_search_context_classes_batch[_dev]: fmx_search_context_fold_batch with this search in the place of the fold search.  The
+ * expansion P_i, a.P_i appends a as a LITERAL element; the lead bit, the filter and the re-cut to CSR are the same code.
+ * Patterns are non-empty, at most FMX_CLASS_MAX_ELEMS - 1 elements, without the literal 0; a hit's len is the bytes of its
+ * spelling, so a term's runs may differ in len.
+ * fmx_classes_last: as fmx_fold_last, of the calling thread's last class search. */
+#define FMX_CLASS_MAX_MEMBER_LEN 4
+#define FMX_CLASS_MAX_MEMBERS 16
+#define FMX_CLASS_MAX_ELEMS 255
+#define FMX_CLASS_MAX_CLASSES 65280
+typedef struct fmx_class_table {
+  const uint64_t *cls_off;  /* n_classes + 1 */
+  const uint64_t *mem_off;  /* cls_off[n_classes] + 1 */
+  const uint8_t *mem_bytes; /* mem_off[cls_off[n_classes]] */
+  uint64_t n_classes;
+  uint32_t flags;    /* must be 0 */
+  uint32_t reserved; /* must be 0 */
+} fmx_class_table;   /* 40 bytes */
+int fmx_search_classes_batch(const fmx_index *idx, const uint16_t *el, const uint64_t *el_off, size_t k,
+                             const fmx_class_table *tab, uint64_t *out_off /* k + 1 */, fmx_result *out, size_t cap,
+                             size_t *n_out);
+int fmx_search_classes_batch_dev(const fmx_index *idx, const void *d_el, const void *d_el_off, size_t k,
+                                 const fmx_class_table *tab, void *d_out_off, void *d_out, size_t cap, size_t *n_out,
+                                 void *stream);
+int fmx_search_context_classes_batch(const fmx_index *idx, const uint16_t *el, const uint64_t *el_off, size_t k,
+                                     const fmx_context_opts *ctx, const fmx_class_table *tab, uint64_t *out_off /* k + 1 */,
+                                     fmx_result *out, size_t cap, size_t *n_out);
+int fmx_search_context_classes_batch_dev(const fmx_index *idx, const void *d_el, const void *d_el_off, size_t k,
+                                         const fmx_context_opts *ctx, const fmx_class_table *tab, void *d_out_off, void *d_out,
+                                         size_t cap, size_t *n_out, void *stream);
+int fmx_classes_last(double *search_ms, double *sort_ms, uint64_t *steps, uint64_t *requests);
+
 /* ---- lines: the map from a text position to its line, and occurrences reduced to the distinct lines that hold them (grep -n
  * over an index).  Beyond the reference.  DESIGN.md 23.
  * t is the indexed text of n - 1 bytes; positions are the `pos` of fmx_occurrence, so the occurrence of a one-byte string at
